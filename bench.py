@@ -195,6 +195,40 @@ def profile_facts() -> dict:
         return {}
 
 
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: everything written, all files together
+DUMP_SEED = 20260915          # the fixed sample of points when a run's outputs exceed DUMP_MAX_BYTES
+
+
+def dump_index(n_points: int, bytes_per_point: int, fixed_bytes: int = 4096) -> np.ndarray:
+    """Points whose outputs --dump-outputs writes: all of them if they fit DUMP_MAX_BYTES, else a fixed seeded sample
+    (ascending) of as many as fit.  The same (n_points, bytes_per_point) always gives the same points."""
+    k = min(n_points, (DUMP_MAX_BYTES - fixed_bytes) // bytes_per_point)
+    if k == n_points:
+        return np.arange(n_points)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_points, size=k, replace=False))
+
+
+def record_arrays(a_end, p_end, p_max, first_bad, idx) -> dict:
+    """A sweep record's per-point outputs at the points idx: a_end as [point][wave][re, im] in the sweep's own dtype."""
+    a = np.asarray(a_end)[idx]
+    return {"index": idx, "a_end": np.stack([a.real, a.imag], axis=-1), "p_end": np.asarray(p_end)[idx],
+            "p_max": np.asarray(p_max)[idx], "first_bad_step": np.asarray(first_bad)[idx]}
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """Write each array as out_dir/<name>.npy: float32 stays float32, everything else (integers included) is float64."""
+    conv = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        conv[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def emit(out: dict, saved_stdout_fd: int) -> None:
     sys.stdout.flush()
     os.dup2(saved_stdout_fd, 1)
@@ -254,6 +288,13 @@ def trajectory_mode(args, dev, saved_stdout_fd) -> None:
         err = max(err, float(np.max(np.abs(got - A) / np.abs(A))))
     if not err < (1e-9 if dt == "f64" else 1e-4):
         raise SystemExit(f"trajectory bench failed its parity guard: {err}")
+    if args.dump_outputs:
+        # the last timed launch: the saved rows [row][wave][point][re, im] and the record, at a fixed sample of points
+        rows = sweep.traj.shape[0]
+        idx = dump_index(pts, 8 * (rows * nw * 2 + 2 * nw + 4))
+        traj = sweep.traj.index_select(2, torch.as_tensor(idx, device=dev)).cpu().numpy()
+        r = sweep.result()
+        dump_outputs(args.dump_outputs, {**record_arrays(r.a_end, r.p_end, r.p_max, r.first_bad_step, idx), "traj": traj})
     facts = profile_facts().get("trajectory" if key == "c2" else "traj_" + key, {})
     alg_bytes = traj_bytes + sweep.layout.bytes_per_point() * pts + sweep.layout.es * pts * (2 if nw == 6 else 1)
     gbs = alg_bytes / (kern_ms * 1e-3) / 1e9
@@ -326,11 +367,17 @@ def main() -> None:
                          "round-1/2 clock, NOT the metric's)")
     ap.add_argument("--block-check", action="store_true", help="float64: test once per saved row only (first_bad_step = the "
                                                                 "last step of the first non-finite block)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, "
+                         f"at most {DUMP_MAX_BYTES >> 20} MB; a fixed seeded sample of points, listed in index.npy, when "
+                         "the whole output is larger).  Rank 0 writes its own shard")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 100 if args.mode == "trajectory" else 10
     if args.warmup is None:
         args.warmup = 30 if args.mode == "trajectory" else 2
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     cfg = CONFIGS[args.config]
     nw, n_z, pts = cfg["n_waves"], cfg["n_steps"], cfg["pts_per_gpu"]
 
@@ -468,6 +515,12 @@ def main() -> None:
         if not (err < tol_a and err_gain < tol_g and err_db <= tol_db and verify["all_finite"] and n_fin == pts
                 and abs(gain_dev[best_i] - np.max(gain_dev)) <= (1e-6 if f32 else 0.0)):
             raise SystemExit(f"bench result failed its parity guard: {verify}")
+        if args.dump_outputs:
+            # the last timed pass as delivered to pinned host memory: rank 0's record and its gain reduction
+            idx = dump_index(pts, 8 * (2 * nw + 5))
+            dump_outputs(args.dump_outputs, {**record_arrays(res.a_end, res.p_end, res.p_max, res.first_bad_step, idx),
+                                             "gain": host_summ[0][idx], "best_index": host_summ[1][:1],
+                                             "n_finite": host_summ[1][1:], "best_gain": host_summ[2]})
 
     if rank == 0:
         facts = profile_facts().get("c5one" if (args.config == "c5" and args.one_lane) else args.config, {})
