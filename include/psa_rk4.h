@@ -27,8 +27,9 @@
  *
  * Wave order everywhere: [pump1, pump2, signal, idler] (n_waves = 4) or
  * [pump1, pump2, signal1, idler1, signal2, idler2] (n_waves = 6, build-defined
- * extension; the reference has no 6-wave model).  The gain summary is taken on
- * wave index 2 (the signal), as scan_mismtach.py:376 does.
+ * extension; the reference has no 6-wave model).  psa_rk4_sweep_* summarise wave
+ * index 2 (the signal), as scan_mismtach.py:376 does; psa_rk4_sweep_waves_* add the
+ * same summary for every wave (the idler's gain, the pumps' depletion).
  */
 #ifndef PSA_RK4_H
 #define PSA_RK4_H
@@ -166,6 +167,40 @@ int psa_rk4_sweep_f32_dev(void *stream, int n_waves, int64_t n_points, int64_t n
                           int32_t save_every, const float *d_dbeta, const float *d_dbeta2, const float *d_gamma,
                           const float *d_alpha, const float *d_a0_soa, uint32_t flags, float *d_a_end_soa,
                           float *d_p_sig_end, float *d_p_sig_max, int64_t *d_first_bad_step, float *d_traj_soa);
+
+/* ---- the sweep with a per-wave power summary ----------------------------------------------------------------
+ * psa_rk4_sweep_f64 / _f32 (and their _dev forms) with two more outputs: the end and maximum power of EVERY wave, so the
+ * idler's conversion gain and the pumps' depletion need no trajectory.  The reference's seeded mismatch scan applies
+ * _select_power_metric to the idler as well as the signal and reports Gi next to Gs (scan_mismtach.py:139-153, :183-199).
+ *   p_wave_end [N][n_waves]   |A_j|^2 at the last saved row (the row of a_end); column 2 == p_sig_end bit for bit
+ *   p_wave_max [N][n_waves]   max of |A_j|^2 over the saved rows incl. z = 0, NaN-propagating like np.max; column 2 ==
+ *                             p_sig_max bit for bit
+ * _dev forms: d_p_wave_end_soa / d_p_wave_max_soa are [n_waves][N] device buffers; asynchronous on `stream`.
+ * Everything else -- arguments, a_end, p_sig_*, first_bad_step, the layout flags and the automatic layout choice -- is as
+ * for psa_rk4_sweep_*, with these restrictions (PSA_E_FLAGS): traj_or_null must be NULL (a trajectory holds every wave
+ * already), and PSA_OPT_LDS_STAGING and PSA_OPT_BLOCK64 are not offered.
+ */
+int psa_rk4_sweep_waves_f64(int device, int n_waves, int64_t n_points, int64_t n_steps, double z_max,
+                            int32_t save_every, const double *dbeta, const double *dbeta2, const double *gamma,
+                            const double *alpha, const double *a0_re_im, uint32_t flags, double *a_end_re_im,
+                            double *p_sig_end, double *p_sig_max, int64_t *first_bad_step, double *traj_or_null,
+                            double *elapsed_ms_or_null, double *p_wave_end, double *p_wave_max);
+int psa_rk4_sweep_waves_f32(int device, int n_waves, int64_t n_points, int64_t n_steps, double z_max,
+                            int32_t save_every, const float *dbeta, const float *dbeta2, const float *gamma,
+                            const float *alpha, const float *a0_re_im, uint32_t flags, float *a_end_re_im,
+                            float *p_sig_end, float *p_sig_max, int64_t *first_bad_step, float *traj_or_null,
+                            double *elapsed_ms_or_null, float *p_wave_end, float *p_wave_max);
+int psa_rk4_sweep_waves_f64_dev(void *stream, int n_waves, int64_t n_points, int64_t n_steps, double z_max,
+                                int32_t save_every, const double *d_dbeta, const double *d_dbeta2,
+                                const double *d_gamma, const double *d_alpha, const double *d_a0_soa, uint32_t flags,
+                                double *d_a_end_soa, double *d_p_sig_end, double *d_p_sig_max,
+                                int64_t *d_first_bad_step, double *d_traj_soa, double *d_p_wave_end_soa,
+                                double *d_p_wave_max_soa);
+int psa_rk4_sweep_waves_f32_dev(void *stream, int n_waves, int64_t n_points, int64_t n_steps, double z_max,
+                                int32_t save_every, const float *d_dbeta, const float *d_dbeta2, const float *d_gamma,
+                                const float *d_alpha, const float *d_a0_soa, uint32_t flags, float *d_a_end_soa,
+                                float *d_p_sig_end, float *d_p_sig_max, int64_t *d_first_bad_step, float *d_traj_soa,
+                                float *d_p_wave_end_soa, float *d_p_wave_max_soa);
 
 /* ---- B1': one RHS evaluation per point (host buffers, blocking) --------------------
  * Replaces yaman_model.rhs_yaman_simplified (yaman_model.py:10-52) for a batch:

@@ -57,6 +57,14 @@ _SIGS = {
                                         _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
     "psa_rk4_sweep_f32_dev": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int32,
                                         _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
+    "psa_rk4_sweep_waves_f64": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int32,
+                                          _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "psa_rk4_sweep_waves_f32": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int32,
+                                          _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "psa_rk4_sweep_waves_f64_dev": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int32,
+                                              _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
+    "psa_rk4_sweep_waves_f32_dev": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int32,
+                                              _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
     "psa_yaman_rhs_f64": (C.c_int, [C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "psa_gain_summary_f64": (C.c_int, [C.c_int, C.c_int64, _P, _P, C.c_double, C.c_int, _P, _P, _P, _P]),
     "psa_gain_summary_f64_dev": (C.c_int, [_P, C.c_int64, _P, _P, C.c_double, C.c_int, _P, _P, _P, _P, _P]),
@@ -182,8 +190,11 @@ def _prep(x, dtype, n_points: int, name: str):
 
 def sweep_host(dbeta, *, n_steps: int, z_max: float, save_every: int, gamma, alpha, a0, dbeta2=None,
                check_nan: bool = True, exact_step: Optional[bool] = None, want_traj: bool = False, dtype=np.float64,
-               device: int = 0, extra_flags: int = 0) -> dict:
+               device: int = 0, extra_flags: int = 0, wave_summary: bool = False) -> dict:
     """Run N independent RK4 propagations on the GPU (host buffers in, host buffers out).
+
+    wave_summary: also return p_wave_end / p_wave_max (N, n_waves), the end and maximum power of every wave
+    (psa_rk4_sweep_waves_*; no trajectory with it).  Without it both are None.
 
     exact_step: None = exact first_bad_step in float64 (free there: block test + replay of a failing block) and the
     per-save-block index in float32; True / False force either.
@@ -238,11 +249,20 @@ def sweep_host(dbeta, *, n_steps: int, z_max: float, save_every: int, gamma, alp
     bad = np.empty(N, dtype=np.int64)
     traj = np.empty((N, n_saved, nw), dtype=cdt) if want_traj else None
     ms = C.c_double(0.0)
-    fn = lib().psa_rk4_sweep_f64 if dtype == np.float64 else lib().psa_rk4_sweep_f32
-    _check(fn(int(device), nw, N, int(n_steps), float(z_max), int(save_every), _ptr(dbeta), _ptr(d2), _ptr(gamma),
-              _ptr(alpha), _ptr(a0), flags, _ptr(a_end), _ptr(p_end), _ptr(p_max), _ptr(bad), _ptr(traj),
-              C.cast(C.byref(ms), C.c_void_p)))
-    return dict(a_end=a_end, p_end=p_end, p_max=p_max, first_bad_step=bad, traj=traj, elapsed_ms=ms.value)
+    args = [int(device), nw, N, int(n_steps), float(z_max), int(save_every), _ptr(dbeta), _ptr(d2), _ptr(gamma),
+            _ptr(alpha), _ptr(a0), flags, _ptr(a_end), _ptr(p_end), _ptr(p_max), _ptr(bad), _ptr(traj),
+            C.cast(C.byref(ms), C.c_void_p)]
+    w_end = w_max = None
+    if wave_summary:
+        w_end = np.empty((N, nw), dtype=dtype)
+        w_max = np.empty((N, nw), dtype=dtype)
+        fn = lib().psa_rk4_sweep_waves_f64 if dtype == np.float64 else lib().psa_rk4_sweep_waves_f32
+        args += [_ptr(w_end), _ptr(w_max)]
+    else:
+        fn = lib().psa_rk4_sweep_f64 if dtype == np.float64 else lib().psa_rk4_sweep_f32
+    _check(fn(*args))
+    return dict(a_end=a_end, p_end=p_end, p_max=p_max, first_bad_step=bad, traj=traj, elapsed_ms=ms.value,
+                p_wave_end=w_end, p_wave_max=w_max)
 
 
 def sweep_device(*, stream: int, n_waves: int, n_points: int, n_steps: int, z_max: float, save_every: int,
@@ -254,6 +274,18 @@ def sweep_device(*, stream: int, n_waves: int, n_points: int, n_steps: int, z_ma
     _check(fn(stream or None, int(n_waves), int(n_points), int(n_steps), float(z_max), int(save_every),
               d_dbeta or None, d_dbeta2 or None, d_gamma or None, d_alpha or None, d_a0_soa or None, int(flags),
               d_a_end_soa or None, d_p_end or None, d_p_max or None, d_first_bad or None, d_traj_soa or None))
+
+
+def sweep_waves_device(*, stream: int, n_waves: int, n_points: int, n_steps: int, z_max: float, save_every: int,
+                       d_dbeta: int, d_dbeta2: int, d_gamma: int, d_alpha: int, d_a0_soa: int, flags: int,
+                       d_a_end_soa: int, d_p_end: int, d_p_max: int, d_first_bad: int, d_p_wave_end_soa: int,
+                       d_p_wave_max_soa: int, d_traj_soa: int = 0, dtype=np.float64) -> None:
+    """sweep_device with the per-wave summary ([n_waves][N] device buffers) -- see psa_rk4_sweep_waves_f64_dev."""
+    fn = lib().psa_rk4_sweep_waves_f64_dev if np.dtype(dtype) == np.float64 else lib().psa_rk4_sweep_waves_f32_dev
+    _check(fn(stream or None, int(n_waves), int(n_points), int(n_steps), float(z_max), int(save_every),
+              d_dbeta or None, d_dbeta2 or None, d_gamma or None, d_alpha or None, d_a0_soa or None, int(flags),
+              d_a_end_soa or None, d_p_end or None, d_p_max or None, d_first_bad or None, d_traj_soa or None,
+              d_p_wave_end_soa or None, d_p_wave_max_soa or None))
 
 
 def yaman_rhs_host(z, a, gamma, alpha, dbeta, *, terms: bool = False, device: int = 0):

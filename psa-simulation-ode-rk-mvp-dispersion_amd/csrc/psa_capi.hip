@@ -120,6 +120,8 @@ psa::SweepArgs<T> make_args(int n_waves, int64_t n_points, int64_t n_steps, doub
     a.alpha_stride = (flags & PSA_BCAST_ALPHA) ? 0 : 1;
     a.a0_stride = (flags & PSA_BCAST_A0) ? 0 : 1;
     a.a0_ld = (flags & PSA_BCAST_A0) ? 1 : n_points;
+    a.p_wave_end = nullptr;
+    a.p_wave_max = nullptr;
     (void)n_waves;
     return a;
 }
@@ -130,6 +132,12 @@ template <> struct Launch<double> {
                             const psa::SweepArgs<double> &a) {
         const int split = (flags & PSA_OPT_QUAD_POINT) ? 2 : ((flags & PSA_OPT_SPLIT_POINT) ? 1 : ((flags & PSA_OPT_ONE_LANE) ? 0 : -1));
         return psa::launch_sweep_f64(s, nw, chk, lds, blk, (flags & PSA_OPT_LOSSLESS) != 0, split, a);
+    }
+    static int split_of(uint32_t flags) {
+        return (flags & PSA_OPT_QUAD_POINT) ? 2 : ((flags & PSA_OPT_SPLIT_POINT) ? 1 : ((flags & PSA_OPT_ONE_LANE) ? 0 : -1));
+    }
+    static hipError_t sweep_waves(hipStream_t s, int nw, int chk, uint32_t flags, const psa::SweepArgs<double> &a) {
+        return psa::launch_sweep_waves_f64(s, nw, chk, (flags & PSA_OPT_LOSSLESS) != 0, split_of(flags), a);
     }
     static hipError_t a2s(hipStream_t s, const double *a, double *b, long long n, int nc) { return psa::launch_aos_to_soa_f64(s, a, b, n, nc); }
     static hipError_t s2a(hipStream_t s, const double *a, double *b, long long n, int nc) { return psa::launch_soa_to_aos_f64(s, a, b, n, nc); }
@@ -143,25 +151,59 @@ template <> struct Launch<float> {
         const bool lossless = (flags & PSA_OPT_LOSSLESS) != 0;
         return psa::launch_sweep_f32(s, nw, chk, lds, blk, pack, lossless && pack == 0, a);
     }
+    static hipError_t sweep_waves(hipStream_t s, int nw, int chk, uint32_t flags, const psa::SweepArgs<float> &a) {
+        const int pack = (flags & PSA_OPT_F32_PACKED) ? 1 : ((flags & PSA_OPT_F32_SCALAR) ? 0 : -1);
+        return psa::launch_sweep_waves_f32(s, nw, chk, pack, (flags & PSA_OPT_LOSSLESS) != 0 && pack == 0, a);
+    }
     static hipError_t a2s(hipStream_t s, const float *a, float *b, long long n, int nc) { return psa::launch_aos_to_soa_f32(s, a, b, n, nc); }
     static hipError_t s2a(hipStream_t s, const float *a, float *b, long long n, int nc) { return psa::launch_soa_to_aos_f32(s, a, b, n, nc); }
     static hipError_t t2a(hipStream_t s, const float *a, float *b, long long n, long long ld, long long r, int nc) { return psa::launch_traj_to_aos_f32(s, a, b, n, ld, r, nc); }
 };
 
+// The per-wave summary entry points (psa_rk4_sweep_waves_*) are offered for the register layouts without trajectory
+// and with the automatic block sizes only.
+int validate_waves(uint32_t flags, bool has_traj) {
+    if (has_traj) return fail(PSA_E_FLAGS, "the per-wave summary takes no trajectory (traj_or_null must be NULL)");
+    if (flags & PSA_OPT_LDS_STAGING) return fail(PSA_E_FLAGS, "the per-wave summary does not exist with PSA_OPT_LDS_STAGING");
+    if (flags & PSA_OPT_BLOCK64) return fail(PSA_E_FLAGS, "the per-wave summary does not exist with PSA_OPT_BLOCK64");
+    return PSA_OK;
+}
+
+// d_wave_end / d_wave_max non-NULL: the per-wave summary (SoA [n_waves][N]); the caller has run validate_waves
 template <typename T>
 int sweep_dev(void *stream, int n_waves, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
               const T *d_dbeta, const T *d_dbeta2, const T *d_gamma, const T *d_alpha, const T *d_a0_soa,
-              uint32_t flags, T *d_a_end_soa, T *d_p_end, T *d_p_max, int64_t *d_first_bad, T *d_traj_soa) {
+              uint32_t flags, T *d_a_end_soa, T *d_p_end, T *d_p_max, int64_t *d_first_bad, T *d_traj_soa,
+              T *d_wave_end = nullptr, T *d_wave_max = nullptr) {
     int rc = validate_common(n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha,
                              d_a0_soa, d_a_end_soa, d_p_end, d_p_max, d_first_bad, flags, d_traj_soa != nullptr, sizeof(T));
     if (rc != PSA_OK) return rc;
     if (n_points == 0) return PSA_OK;
     auto a = make_args<T>(n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha,
                           d_a0_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa);
-    hipError_t e = Launch<T>::sweep((hipStream_t)stream, n_waves, check_mode(flags), (flags & PSA_OPT_LDS_STAGING) != 0,
-                                    (flags & PSA_OPT_BLOCK64) ? 64 : 256, flags, a);
+    hipError_t e;
+    if (d_wave_end) {
+        a.p_wave_end = d_wave_end;
+        a.p_wave_max = d_wave_max;
+        e = Launch<T>::sweep_waves((hipStream_t)stream, n_waves, check_mode(flags), flags, a);
+    } else {
+        e = Launch<T>::sweep((hipStream_t)stream, n_waves, check_mode(flags), (flags & PSA_OPT_LDS_STAGING) != 0,
+                             (flags & PSA_OPT_BLOCK64) ? 64 : 256, flags, a);
+    }
     if (e != hipSuccess) return hip_fail(e, "rk4_sweep launch");
     return PSA_OK;
+}
+
+template <typename T>
+int sweep_waves_dev(void *stream, int n_waves, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+                    const T *d_dbeta, const T *d_dbeta2, const T *d_gamma, const T *d_alpha, const T *d_a0_soa,
+                    uint32_t flags, T *d_a_end_soa, T *d_p_end, T *d_p_max, int64_t *d_first_bad, T *d_traj_soa,
+                    T *d_wave_end, T *d_wave_max) {
+    int rc = validate_waves(flags, d_traj_soa != nullptr);
+    if (rc != PSA_OK) return rc;
+    if (n_points > 0 && (!d_wave_end || !d_wave_max)) return fail(PSA_E_NULLPTR, "p_wave_end / p_wave_max is NULL");
+    return sweep_dev<T>(stream, n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha,
+                        d_a0_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa, d_wave_end, d_wave_max);
 }
 
 // Device scratch that frees itself on every exit path of the host-buffer entry points.
@@ -322,7 +364,9 @@ static bool injected_chunk_failure(size_t chunk_index) {
 template <typename T>
 int sweep_host(int device, int n_waves, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
                const T *dbeta, const T *dbeta2, const T *gamma, const T *alpha, const T *a0, uint32_t flags,
-               T *a_end, T *p_end, T *p_max, int64_t *first_bad, T *traj, double *elapsed_ms) {
+               T *a_end, T *p_end, T *p_max, int64_t *first_bad, T *traj, double *elapsed_ms,
+               T *wave_end = nullptr, T *wave_max = nullptr) {
+    const bool waves = wave_end != nullptr;   // psa_rk4_sweep_waves_*: validated by the caller (validate_waves)
     int rc = validate_common(n_waves, n_points, n_steps, z_max, save_every, dbeta, dbeta2, gamma, alpha, a0, a_end,
                              p_end, p_max, first_bad, flags, traj != nullptr, sizeof(T));
     if (rc != PSA_OK) return rc;
@@ -365,10 +409,11 @@ int sweep_host(int device, int n_waves, int64_t n_points, int64_t n_steps, doubl
     using C = Carver;
     const size_t in_bytes = C::aligned(N * sizeof(T)) * (dbeta2 ? 2 : 1) + C::aligned(n_gamma * sizeof(T)) +
                             C::aligned(n_alpha * sizeof(T)) + C::aligned(n_a0 * nc * sizeof(T));
-    const size_t mid_bytes = C::aligned(n_a0 * nc * sizeof(T)) + C::aligned(N * nc * sizeof(T));
+    const size_t wave_bytes = waves ? 2 * C::aligned(N * n_waves * sizeof(T)) : 0;   // p_wave_end, p_wave_max
+    const size_t mid_bytes = C::aligned(n_a0 * nc * sizeof(T)) + C::aligned(N * nc * sizeof(T)) + wave_bytes;
     const bool traj_in_out = traj && N == 1;     // [rows][nw][1] and [1][rows][nw] coincide: it leaves with the outputs
     const size_t out_bytes = C::aligned(N * nc * sizeof(T)) + 2 * C::aligned(N * sizeof(T)) + C::aligned(N * sizeof(int64_t)) +
-                             (traj_in_out ? C::aligned(traj_bytes) : 0);
+                             (traj_in_out ? C::aligned(traj_bytes) : 0) + wave_bytes;
     const size_t small_total = in_bytes + mid_bytes + out_bytes;
     const size_t traj_total = (traj && !traj_in_out) ? C::aligned(traj_bytes) + 2 * C::aligned(stage_bytes) : 0;
 
@@ -414,11 +459,15 @@ int sweep_host(int device, int n_waves, int64_t n_points, int64_t n_steps, doubl
     T *d_a0_aos = small.take<T>(n_a0 * nc);
     T *d_a0_soa = small.take<T>(n_a0 * nc);
     T *d_aend_soa = small.take<T>(N * nc);
+    T *d_wend_soa = waves ? small.take<T>(N * n_waves) : nullptr;
+    T *d_wmax_soa = waves ? small.take<T>(N * n_waves) : nullptr;
     const size_t out_off = small.used;
     T *d_aend_aos = small.take<T>(N * nc);
     T *d_pend = small.take<T>(N);
     T *d_pmax = small.take<T>(N);
     int64_t *d_bad = small.take<int64_t>(N);
+    T *d_wend = waves ? small.take<T>(N * n_waves) : nullptr;   // [N][n_waves], the caller's layout
+    T *d_wmax = waves ? small.take<T>(N * n_waves) : nullptr;
     T *d_traj = nullptr, *d_stage[2] = {nullptr, nullptr};
     if (traj_in_out) {
         d_traj = small.take<T>(traj_elems);
@@ -451,10 +500,14 @@ int sweep_host(int device, int n_waves, int64_t n_points, int64_t n_steps, doubl
     HIP_RET(Launch<T>::a2s(st, d_a0_aos, d_a0_soa, (long long)n_a0, nc));
     HIP_RET(hipEventRecord(cx.ev0, st));
     rc = sweep_dev<T>(st, n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha, d_a0_soa,
-                      flags, d_aend_soa, d_pend, d_pmax, d_bad, d_traj);
+                      flags, d_aend_soa, d_pend, d_pmax, d_bad, d_traj, d_wend_soa, d_wmax_soa);
     if (rc != PSA_OK) return rc;
     HIP_RET(hipEventRecord(cx.ev1, st));
     HIP_RET(Launch<T>::s2a(st, d_aend_soa, d_aend_aos, (long long)N, nc));
+    if (waves) {
+        HIP_RET(Launch<T>::s2a(st, d_wend_soa, d_wend, (long long)N, n_waves));
+        HIP_RET(Launch<T>::s2a(st, d_wmax_soa, d_wmax, (long long)N, n_waves));
+    }
     if (mirror) {
         HIP_RET(hipMemcpyAsync(cx.pinned + CTX_PINNED_IN, small.base + out_off, out_bytes, hipMemcpyDeviceToHost, st));
     } else {
@@ -462,6 +515,10 @@ int sweep_host(int device, int n_waves, int64_t n_points, int64_t n_steps, doubl
         HIP_RET(hipMemcpyAsync(p_end, d_pend, N * sizeof(T), hipMemcpyDeviceToHost, st));
         HIP_RET(hipMemcpyAsync(p_max, d_pmax, N * sizeof(T), hipMemcpyDeviceToHost, st));
         HIP_RET(hipMemcpyAsync(first_bad, d_bad, N * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        if (waves) {
+            HIP_RET(hipMemcpyAsync(wave_end, d_wend, N * n_waves * sizeof(T), hipMemcpyDeviceToHost, st));
+            HIP_RET(hipMemcpyAsync(wave_max, d_wmax, N * n_waves * sizeof(T), hipMemcpyDeviceToHost, st));
+        }
         if (traj_in_out) HIP_RET(hipMemcpyAsync(traj, d_traj, traj_bytes, hipMemcpyDeviceToHost, st));
     }
     if (traj && !traj_in_out) {
@@ -493,6 +550,10 @@ int sweep_host(int device, int n_waves, int64_t n_points, int64_t n_steps, doubl
         get(p_end, d_pend, N * sizeof(T));
         get(p_max, d_pmax, N * sizeof(T));
         get(first_bad, d_bad, N * sizeof(int64_t));
+        if (waves) {
+            get(wave_end, d_wend, N * n_waves * sizeof(T));
+            get(wave_max, d_wmax, N * n_waves * sizeof(T));
+        }
         if (traj_in_out) get(traj, d_traj, traj_bytes);
     }
     if (elapsed_ms) {
@@ -717,6 +778,45 @@ int psa_rk4_sweep_f32_dev(void *stream, int n_waves, int64_t n_points, int64_t n
                           float *d_p_end, float *d_p_max, int64_t *d_first_bad, float *d_traj_soa) {
     return sweep_dev<float>(stream, n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha,
                             d_a0_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa);
+}
+
+int psa_rk4_sweep_waves_f64(int device, int n_waves, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+                            const double *dbeta, const double *dbeta2, const double *gamma, const double *alpha,
+                            const double *a0, uint32_t flags, double *a_end, double *p_end, double *p_max,
+                            int64_t *first_bad, double *traj, double *elapsed_ms, double *p_wave_end, double *p_wave_max) {
+    int rc = validate_waves(flags, traj != nullptr);
+    if (rc != PSA_OK) return rc;
+    if (n_points > 0 && (!p_wave_end || !p_wave_max)) return fail(PSA_E_NULLPTR, "p_wave_end / p_wave_max is NULL");
+    return sweep_host<double>(device, n_waves, n_points, n_steps, z_max, save_every, dbeta, dbeta2, gamma, alpha, a0,
+                              flags, a_end, p_end, p_max, first_bad, nullptr, elapsed_ms, p_wave_end, p_wave_max);
+}
+int psa_rk4_sweep_waves_f32(int device, int n_waves, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+                            const float *dbeta, const float *dbeta2, const float *gamma, const float *alpha,
+                            const float *a0, uint32_t flags, float *a_end, float *p_end, float *p_max,
+                            int64_t *first_bad, float *traj, double *elapsed_ms, float *p_wave_end, float *p_wave_max) {
+    int rc = validate_waves(flags, traj != nullptr);
+    if (rc != PSA_OK) return rc;
+    if (n_points > 0 && (!p_wave_end || !p_wave_max)) return fail(PSA_E_NULLPTR, "p_wave_end / p_wave_max is NULL");
+    return sweep_host<float>(device, n_waves, n_points, n_steps, z_max, save_every, dbeta, dbeta2, gamma, alpha, a0,
+                             flags, a_end, p_end, p_max, first_bad, nullptr, elapsed_ms, p_wave_end, p_wave_max);
+}
+int psa_rk4_sweep_waves_f64_dev(void *stream, int n_waves, int64_t n_points, int64_t n_steps, double z_max,
+                                int32_t save_every, const double *d_dbeta, const double *d_dbeta2, const double *d_gamma,
+                                const double *d_alpha, const double *d_a0_soa, uint32_t flags, double *d_a_end_soa,
+                                double *d_p_end, double *d_p_max, int64_t *d_first_bad, double *d_traj_soa,
+                                double *d_p_wave_end_soa, double *d_p_wave_max_soa) {
+    return sweep_waves_dev<double>(stream, n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma,
+                                   d_alpha, d_a0_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa,
+                                   d_p_wave_end_soa, d_p_wave_max_soa);
+}
+int psa_rk4_sweep_waves_f32_dev(void *stream, int n_waves, int64_t n_points, int64_t n_steps, double z_max,
+                                int32_t save_every, const float *d_dbeta, const float *d_dbeta2, const float *d_gamma,
+                                const float *d_alpha, const float *d_a0_soa, uint32_t flags, float *d_a_end_soa,
+                                float *d_p_end, float *d_p_max, int64_t *d_first_bad, float *d_traj_soa,
+                                float *d_p_wave_end_soa, float *d_p_wave_max_soa) {
+    return sweep_waves_dev<float>(stream, n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma,
+                                  d_alpha, d_a0_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa,
+                                  d_p_wave_end_soa, d_p_wave_max_soa);
 }
 
 int psa_yaman_rhs_f64(int device, int64_t n, const double *z, const double *a, const double *gamma,

@@ -26,6 +26,9 @@ struct SweepArgs {
     int save_every;
     int gamma_stride, alpha_stride, a0_stride;  // 0 | 1
     long long a0_ld;
+    // per-wave summary (the WSUM instantiations only; nullptr otherwise): SoA [NW][N]
+    T *p_wave_end;       // |A_j|^2 at the last saved row
+    T *p_wave_max;       // max over saved rows incl. z = 0 (NaN-propagating like np.max)
 };
 
 enum CheckMode : int { CHECK_NONE = 0, CHECK_BLOCK = 1, CHECK_EXACT = 2 };
@@ -37,6 +40,10 @@ hipError_t launch_sweep_f64(hipStream_t s, int n_waves, int check, bool lds, int
                             const SweepArgs<double> &a);
 hipError_t launch_sweep_f32(hipStream_t s, int n_waves, int check, bool lds, int block, int pack, bool lossless,
                             const SweepArgs<float> &a);  // pack: 1 two points/lane, 0 one, -1 auto
+// the same sweeps with the per-wave summary (a.p_wave_end / a.p_wave_max): register layouts, no trajectory, the automatic
+// block sizes (256 threads for the one-lane and packed kernels)
+hipError_t launch_sweep_waves_f64(hipStream_t s, int n_waves, int check, bool lossless, int split, const SweepArgs<double> &a);
+hipError_t launch_sweep_waves_f32(hipStream_t s, int n_waves, int check, int pack, bool lossless, const SweepArgs<float> &a);
 
 // aux kernels (psa_aux.hip)
 hipError_t launch_aos_to_soa_f64(hipStream_t s, const double *aos, double *soa, long long n, int nc);

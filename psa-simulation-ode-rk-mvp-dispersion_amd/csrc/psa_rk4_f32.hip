@@ -12,4 +12,8 @@ hipError_t launch_sweep_f32(hipStream_t s, int n_waves, int check, bool lds, int
     if (use_pack) return launch_sweep_pk(s, n_waves, check, block, a);
     return launch_sweep_t<float>(s, n_waves, check, lds, block, lossless, a);
 }
+hipError_t launch_sweep_waves_f32(hipStream_t s, int n_waves, int check, int pack, bool lossless, const SweepArgs<float> &a) {
+    if (pack == 1 || (pack < 0 && a.n_points >= 2)) return launch_sweep_pk_waves(s, n_waves, check, a);
+    return launch_waves_t<float>(s, n_waves, check, lossless, a);
+}
 }  // namespace psa

@@ -62,4 +62,14 @@ hipError_t launch_sweep_f64(hipStream_t s, int n_waves, int check, bool lds, int
     const int sb = (block == 64 || 2 * waves <= (long long)simds) ? 64 : 256;
     return lanes == 2 ? launch_sweep_split(s, n_waves, check, lossless, sb, a) : launch_sweep_quad(s, check, lossless, sb, a);
 }
+
+// The same layout choice with the per-wave summary (register layouts, no trajectory: launch_sweep_f64 with lds = false,
+// traj = nullptr, block = 256).
+hipError_t launch_sweep_waves_f64(hipStream_t s, int n_waves, int check, bool lossless, int split, const SweepArgs<double> &a) {
+    const int lanes = split == 1 ? 2 : (split == 2 && n_waves == 4 ? 4 : (split < 0 ? best_lanes_per_point(n_waves, a.n_points, simd_count(s)) : 1));
+    if (lanes == 1) return launch_waves_t<double>(s, n_waves, check, lossless, a);
+    const long long waves = ((long long)lanes * a.n_points + 63) / 64;
+    const int sb = (2 * waves <= (long long)simd_count(s)) ? 64 : 256;
+    return lanes == 2 ? launch_sweep_split_waves(s, n_waves, check, lossless, sb, a) : launch_sweep_quad_waves(s, check, lossless, sb, a);
+}
 }  // namespace psa

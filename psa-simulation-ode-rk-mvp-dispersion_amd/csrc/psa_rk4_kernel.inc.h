@@ -178,8 +178,12 @@ __device__ __forceinline__ bool any_nonfinite(const T (&y)[NC]) {
 #ifndef PSA_SWEEP_KERNEL_ATTR   // A/B hook (tools/ab_build.sh): e.g. -DPSA_SWEEP_KERNEL_ATTR='__attribute__((amdgpu_waves_per_eu(3)))'
 #define PSA_SWEEP_KERNEL_ATTR
 #endif
-template <typename T, int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS = false, bool LOSS = true>
+// WSUM = true adds the per-wave summary (A.p_wave_end / A.p_wave_max, SoA [NW][N]; register layout without trajectory
+// only): |A_j|^2 of every wave with the expression the signal's summary uses, so wave 2's columns are p_end / p_max bit for
+// bit.  The end value is formed where a_end is written; only the NW running maxima are loop state.
+template <typename T, int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS = false, bool LOSS = true, bool WSUM = false>
 __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(const SweepArgs<T> A) {
+    static_assert(!WSUM || (!TRAJ && !LDS), "the per-wave summary exists for the register layout without trajectory");
     constexpr int NC = 2 * NW;
     constexpr int NP = (NW - 2) / 2;
     constexpr int RESYNC = Phase<T>::RESYNC;
@@ -218,6 +222,19 @@ __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(
     T pe = fma_(y[4], y[4], y[5] * y[5]);  // |A_sig|^2 at the last saved row (z = 0 is a saved row)
     T pm = pe;                             // np.max over saved rows
     long long bad = -1;
+    T pwm[WSUM ? NW : 1];                  // WSUM: np.max of |A_j|^2 over saved rows, every wave
+    if constexpr (WSUM) {
+#pragma unroll
+        for (int j = 0; j < NW; ++j) pwm[j] = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
+    }
+    auto store_a_end = [&]() {             // A[-1]; with WSUM also |A_j|^2 of that row
+#pragma unroll
+        for (int c = 0; c < NC; ++c) A.a_end[(long long)c * N + idx] = y[c];
+        if constexpr (WSUM) {
+#pragma unroll
+            for (int j = 0; j < NW; ++j) A.p_wave_end[(long long)j * N + idx] = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
+        }
+    };
 
     const int se = A.save_every;
     const int n_rows = A.n_steps / se;                                 // saved rows after z = 0
@@ -238,10 +255,7 @@ __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(
             store_pair_nt(rowb + (long long)j * LD * (long long)sizeof(Pair), lane_off, Pair{y[2 * j], y[2 * j + 1]});
     };
     if constexpr (TRAJ) store_traj_row(0);
-    if (n_rows == 0) {
-#pragma unroll
-        for (int c = 0; c < NC; ++c) A.a_end[(long long)c * N + idx] = y[c];
-    }
+    if (n_rows == 0) store_a_end();
 
     // LDS-staged variant: sm_k[stage][component][lane] and sm_y[component][lane] (volatile: the traffic is the point)
     __shared__ T sm_store[LDS ? 5 * NC * BLOCK : 1];
@@ -369,6 +383,10 @@ __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(
         A.p_end[idx] = pe;
         A.p_max[idx] = pm;
         A.first_bad[idx] = bad;
+        if constexpr (WSUM) {
+#pragma unroll
+            for (int j = 0; j < NW; ++j) A.p_wave_max[(long long)j * N + idx] = pwm[j];
+        }
     };
     auto seed_phase_on = [&](const int step, T (&Er)[NP], T (&Ei)[NP]) {   // exact re-seed of the phase recurrence at z = step * h
         const double z = (double)step * hd;
@@ -505,14 +523,20 @@ __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(
             ++row;
             pe = fma_(y[4], y[4], y[5] * y[5]);
             pm = (pe > pm || pe != pe) ? pe : pm;  // np.max propagates NaN
+            if constexpr (WSUM) {
+#pragma unroll
+                for (int j = 0; j < NW; ++j) {
+                    const T pj = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
+                    pwm[j] = (pj > pwm[j] || pj != pj) ? pj : pwm[j];
+                }
+            }
             if constexpr (CHECK == CHECK_BLOCK) {
                 if (bad < 0 && any_nonfinite<T, NC>(y)) bad = i - 1;
             }
             exact_test(i);
             if constexpr (TRAJ) store_traj_row(row);
             if (row == n_rows) {  // A[-1]: the last saved row, not necessarily z_max (R8)
-#pragma unroll
-                for (int c = 0; c < NC; ++c) A.a_end[(long long)c * N + idx] = y[c];
+                store_a_end();
                 next_save = 0x7fffffff;
             } else {
                 next_save += se;
@@ -575,6 +599,30 @@ static hipError_t launch_sweep_t(hipStream_t s, int n_waves, int check, bool lds
                                  const SweepArgs<T> &a) {
     if (n_waves == 4) return launch_nw<T, 4>(s, check, block, lds, lossless, a);
     return launch_nw<T, 6>(s, check, block, lds, lossless, a);
+}
+
+// the per-wave summary (WSUM): register layout, no trajectory, 256-thread workgroups -- the automatic choice's block
+template <typename T, int NW, int CHECK>
+static hipError_t launch_waves_one(hipStream_t s, bool lossless, const SweepArgs<T> &a) {
+    if (a.n_points == 0) return hipSuccess;
+    const dim3 grid((unsigned)((a.n_points + 255) / 256));
+    if (lossless) hipLaunchKernelGGL((rk4_sweep_kernel<T, NW, CHECK, false, 256, false, false, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((rk4_sweep_kernel<T, NW, CHECK, false, 256, false, true, true>), grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+template <typename T, int NW>
+static hipError_t launch_waves_nw(hipStream_t s, int check, bool lossless, const SweepArgs<T> &a) {
+    switch (check) {
+        case CHECK_NONE: return launch_waves_one<T, NW, CHECK_NONE>(s, lossless, a);
+        case CHECK_BLOCK: return launch_waves_one<T, NW, CHECK_BLOCK>(s, lossless, a);
+        default: return launch_waves_one<T, NW, CHECK_EXACT>(s, lossless, a);
+    }
+}
+
+template <typename T>
+static hipError_t launch_waves_t(hipStream_t s, int n_waves, int check, bool lossless, const SweepArgs<T> &a) {
+    return n_waves == 4 ? launch_waves_nw<T, 4>(s, check, lossless, a) : launch_waves_nw<T, 6>(s, check, lossless, a);
 }
 
 }  // namespace psa

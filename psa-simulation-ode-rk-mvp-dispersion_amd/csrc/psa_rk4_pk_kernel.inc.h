@@ -15,8 +15,10 @@ namespace psa {
 
 __device__ __forceinline__ f32x2 splat2(float x) { return (f32x2){x, x}; }
 
-template <int NW, int CHECK, bool TRAJ, int BLOCK>
+// WSUM: the per-wave summary (see rk4_sweep_kernel), both packed points at once
+template <int NW, int CHECK, bool TRAJ, int BLOCK, bool WSUM = false>
 __global__ void __launch_bounds__(BLOCK) rk4_sweep_pk_kernel(const SweepArgs<float> A) {
+    static_assert(!WSUM || !TRAJ, "the per-wave summary exists for launches without trajectory");
     using V = f32x2;
     constexpr int NC = 2 * NW;
     constexpr int NP = (NW - 2) / 2;
@@ -97,6 +99,11 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_pk_kernel(const SweepArgs<flo
     V pe = fma_(y[4], y[4], y[5] * y[5]);
     V pm = pe;
     long long bad[2] = {-1, -1};
+    V pwm[WSUM ? NW : 1];   // WSUM: np.max of |A_j|^2 over saved rows, every wave
+    if constexpr (WSUM) {
+#pragma unroll
+        for (int j = 0; j < NW; ++j) pwm[j] = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
+    }
     auto track = [&](const int step) {  // sum_c 0*y_c is NaN exactly for a non-finite component, per packed half
         V t = V{};
 #pragma unroll
@@ -149,7 +156,16 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_pk_kernel(const SweepArgs<flo
         }
     };
     if constexpr (TRAJ) store_traj_row(0);
-    if (n_rows == 0) store_rows(A.a_end);
+    auto store_wave_end = [&]() {   // WSUM: |A_j|^2 of the row a_end holds
+        if constexpr (WSUM) {
+#pragma unroll
+            for (int j = 0; j < NW; ++j) store2(A.p_wave_end + (long long)j * N, fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]));
+        }
+    };
+    if (n_rows == 0) {
+        store_rows(A.a_end);
+        store_wave_end();
+    }
 
     auto rk4_step = [&](const int step_index) {  // integrators.py:54-59, low storage: y, y_stage, accumulator
         V k[NC], ys[NC], acc[NC];
@@ -180,6 +196,10 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_pk_kernel(const SweepArgs<flo
         store2(A.p_max, pm);
         A.first_bad[pt[0]] = bad[0];
         if (live1) A.first_bad[pt[1]] = bad[1];
+        if constexpr (WSUM) {
+#pragma unroll
+            for (int j = 0; j < NW; ++j) store2(A.p_wave_max + (long long)j * N, pwm[j]);
+        }
     };
 
     // ---- save_every == 1 with a trajectory: every step is a saved row (integrators.py:137) -- the HBM-bound regime.  A
@@ -245,10 +265,19 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_pk_kernel(const SweepArgs<flo
             pe = fma_(y[4], y[4], y[5] * y[5]);
             pm.x = (pe.x > pm.x || pe.x != pe.x) ? pe.x : pm.x;  // np.max propagates NaN
             pm.y = (pe.y > pm.y || pe.y != pe.y) ? pe.y : pm.y;
+            if constexpr (WSUM) {
+#pragma unroll
+                for (int j = 0; j < NW; ++j) {
+                    const V pj = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
+                    pwm[j].x = (pj.x > pwm[j].x || pj.x != pj.x) ? pj.x : pwm[j].x;
+                    pwm[j].y = (pj.y > pwm[j].y || pj.y != pj.y) ? pj.y : pwm[j].y;
+                }
+            }
             if constexpr (CHECK == CHECK_BLOCK) track(i - 1);
             if constexpr (TRAJ) store_traj_row(row);
             if (row == n_rows) {
                 store_rows(A.a_end);
+                store_wave_end();
                 next_save = 0x7fffffff;
             } else {
                 next_save += se;
@@ -288,6 +317,26 @@ static hipError_t launch_pk_nw(hipStream_t s, int check, int block, const SweepA
 static hipError_t launch_sweep_pk(hipStream_t s, int n_waves, int check, int block, const SweepArgs<float> &a) {
     if (a.n_points == 0) return hipSuccess;
     return n_waves == 4 ? launch_pk_nw<4>(s, check, block, a) : launch_pk_nw<6>(s, check, block, a);
+}
+
+// the per-wave summary (WSUM): no trajectory, 256-thread workgroups
+template <int NW, int CHECK>
+static hipError_t launch_pk_waves_one(hipStream_t s, const SweepArgs<float> &a) {
+    const long long lanes = (a.n_points + 1) / 2;
+    hipLaunchKernelGGL((rk4_sweep_pk_kernel<NW, CHECK, false, 256, true>), dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+template <int NW>
+static hipError_t launch_pk_waves_nw(hipStream_t s, int check, const SweepArgs<float> &a) {
+    switch (check) {
+        case CHECK_NONE: return launch_pk_waves_one<NW, CHECK_NONE>(s, a);
+        case CHECK_BLOCK: return launch_pk_waves_one<NW, CHECK_BLOCK>(s, a);
+        default: return launch_pk_waves_one<NW, CHECK_EXACT>(s, a);
+    }
+}
+static hipError_t launch_sweep_pk_waves(hipStream_t s, int n_waves, int check, const SweepArgs<float> &a) {
+    if (a.n_points == 0) return hipSuccess;
+    return n_waves == 4 ? launch_pk_waves_nw<4>(s, check, a) : launch_pk_waves_nw<6>(s, check, a);
 }
 
 }  // namespace psa

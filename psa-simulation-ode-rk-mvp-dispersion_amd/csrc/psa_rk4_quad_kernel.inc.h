@@ -58,8 +58,11 @@ __device__ __forceinline__ void quad_stage(const double x, const double y, const
     }
 }
 
-template <int CHECK, bool TRAJ, int BLOCK, bool LOSS>
+// WSUM: the per-wave summary (see rk4_sweep_kernel).  Every lane already tracks |A|^2 of its own wave (pe, pm), so each lane
+// writes its wave's rows and no loop state is added.
+template <int CHECK, bool TRAJ, int BLOCK, bool LOSS, bool WSUM = false>
 __global__ void __launch_bounds__(BLOCK) rk4_sweep_quad_kernel(const SweepArgs<double> A) {
+    static_assert(!WSUM || !TRAJ, "the per-wave summary exists for launches without trajectory");
     constexpr int NW = 4;
     constexpr int RESYNC = Phase<double>::RESYNC;
     const long long gid = (long long)blockIdx.x * BLOCK + threadIdx.x;
@@ -110,6 +113,7 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_quad_kernel(const SweepArgs<d
     auto store_a_end = [&]() {
         A.a_end[(long long)(2 * role) * N + idx] = x;
         A.a_end[(long long)(2 * role + 1) * N + idx] = y;
+        if constexpr (WSUM) A.p_wave_end[(long long)role * N + idx] = fma_(x, x, y * y);
     };
     if constexpr (TRAJ) store_traj_row(0);
     if (n_rows == 0) store_a_end();
@@ -175,6 +179,7 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_quad_kernel(const SweepArgs<d
             A.p_max[idx] = pm;
         }
         if (role == 0) A.first_bad[idx] = bad;
+        if constexpr (WSUM) A.p_wave_max[(long long)role * N + idx] = pm;
     };
 
     // ---- save_every == 1 with a trajectory: every step is a saved row (the dedicated loop of rk4_sweep_kernel)
@@ -263,17 +268,17 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_quad_kernel(const SweepArgs<d
     write_summary();
 }
 
-template <int CHECK, bool TRAJ>
+template <int CHECK, bool TRAJ, bool WSUM = false>
 static hipError_t launch_quad_one(hipStream_t s, bool lossless, int block, const SweepArgs<double> &a) {
     const long long lanes = 4 * a.n_points;
     if (block == 256) {
         const dim3 grid((unsigned)((lanes + 255) / 256));
-        if (lossless) hipLaunchKernelGGL((rk4_sweep_quad_kernel<CHECK, TRAJ, 256, false>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((rk4_sweep_quad_kernel<CHECK, TRAJ, 256, true>), grid, dim3(256), 0, s, a);
+        if (lossless) hipLaunchKernelGGL((rk4_sweep_quad_kernel<CHECK, TRAJ, 256, false, WSUM>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((rk4_sweep_quad_kernel<CHECK, TRAJ, 256, true, WSUM>), grid, dim3(256), 0, s, a);
     } else {
         const dim3 grid((unsigned)((lanes + 63) / 64));
-        if (lossless) hipLaunchKernelGGL((rk4_sweep_quad_kernel<CHECK, TRAJ, 64, false>), grid, dim3(64), 0, s, a);
-        else hipLaunchKernelGGL((rk4_sweep_quad_kernel<CHECK, TRAJ, 64, true>), grid, dim3(64), 0, s, a);
+        if (lossless) hipLaunchKernelGGL((rk4_sweep_quad_kernel<CHECK, TRAJ, 64, false, WSUM>), grid, dim3(64), 0, s, a);
+        else hipLaunchKernelGGL((rk4_sweep_quad_kernel<CHECK, TRAJ, 64, true, WSUM>), grid, dim3(64), 0, s, a);
     }
     return hipGetLastError();
 }
@@ -289,6 +294,16 @@ static hipError_t launch_sweep_quad(hipStream_t s, int check, bool lossless, int
             return traj ? launch_quad_one<CHECK_BLOCK, true>(s, lossless, block, a) : launch_quad_one<CHECK_BLOCK, false>(s, lossless, block, a);
         default:
             return traj ? launch_quad_one<CHECK_EXACT, true>(s, lossless, block, a) : launch_quad_one<CHECK_EXACT, false>(s, lossless, block, a);
+    }
+}
+
+// the per-wave summary (WSUM), no trajectory
+static hipError_t launch_sweep_quad_waves(hipStream_t s, int check, bool lossless, int block, const SweepArgs<double> &a) {
+    if (a.n_points == 0) return hipSuccess;
+    switch (check) {
+        case CHECK_NONE: return launch_quad_one<CHECK_NONE, false, true>(s, lossless, block, a);
+        case CHECK_BLOCK: return launch_quad_one<CHECK_BLOCK, false, true>(s, lossless, block, a);
+        default: return launch_quad_one<CHECK_EXACT, false, true>(s, lossless, block, a);
     }
 }
 

@@ -84,8 +84,10 @@ __device__ __forceinline__ void split_stage(const double (&a)[2 * NL], const dou
     out[U + 3] = fma_(xu, Fr, fma_(yu, Fi, link(gv, xv, U + 3)));
 }
 
-template <int NW, int CHECK, bool TRAJ, int BLOCK, bool LOSS>
+// WSUM: the per-wave summary (see rk4_sweep_kernel); each lane keeps the running maxima of its own NL waves and writes their rows
+template <int NW, int CHECK, bool TRAJ, int BLOCK, bool LOSS, bool WSUM = false>
 __global__ void __launch_bounds__(BLOCK) rk4_sweep_split_kernel(const SweepArgs<double> A) {
+    static_assert(!WSUM || !TRAJ, "the per-wave summary exists for launches without trajectory");
     constexpr int NL = NW / 2;    // waves per lane
     constexpr int NC = 2 * NL;    // real components per lane
     constexpr int RESYNC = Phase<double>::RESYNC;
@@ -135,6 +137,11 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_split_kernel(const SweepArgs<
     double pe = fma_(y[SIG], y[SIG], y[SIG + 1] * y[SIG + 1]);
     double pm = pe;
     long long bad = -1;
+    double pwm[WSUM ? NL : 1];     // WSUM: np.max of |A|^2 over saved rows, for each of the lane's waves
+    if constexpr (WSUM) {
+#pragma unroll
+        for (int j = 0; j < NL; ++j) pwm[j] = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
+    }
     // any component of the POINT non-finite (own lane's or the partner's)
     auto nonfinite_on = [&](const double (&v)[NC]) -> bool {
         double t = 0.0;
@@ -179,6 +186,7 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_split_kernel(const SweepArgs<
         for (int j = 0; j < NL; ++j) {
             A.a_end[(long long)(2 * wave_of[j]) * N + idx] = y[2 * j];
             A.a_end[(long long)(2 * wave_of[j] + 1) * N + idx] = y[2 * j + 1];
+            if constexpr (WSUM) A.p_wave_end[(long long)wave_of[j] * N + idx] = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
         }
     };
     if constexpr (TRAJ) store_traj_row(0);
@@ -362,6 +370,13 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_split_kernel(const SweepArgs<
             ++row;
             pe = fma_(y[SIG], y[SIG], y[SIG + 1] * y[SIG + 1]);
             pm = (pe > pm || pe != pe) ? pe : pm;
+            if constexpr (WSUM) {
+#pragma unroll
+                for (int j = 0; j < NL; ++j) {
+                    const double pj = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
+                    pwm[j] = (pj > pwm[j] || pj != pj) ? pj : pwm[j];
+                }
+            }
             if constexpr (CHECK == CHECK_BLOCK) {
                 if (bad < 0 && point_nonfinite()) bad = i - 1;
             }
@@ -384,19 +399,23 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_split_kernel(const SweepArgs<
         A.p_max[idx] = pm;
     }
     if (role == 0) A.first_bad[idx] = bad;
+    if constexpr (WSUM) {
+#pragma unroll
+        for (int j = 0; j < NL; ++j) A.p_wave_max[(long long)wave_of[j] * N + idx] = pwm[j];
+    }
 }
 
-template <int NW, int CHECK, bool TRAJ>
+template <int NW, int CHECK, bool TRAJ, bool WSUM = false>
 static hipError_t launch_split_one(hipStream_t s, bool lossless, int block, const SweepArgs<double> &a) {
     const long long lanes = 2 * a.n_points;
     if (block == 256) {
         const dim3 grid((unsigned)((lanes + 255) / 256));
-        if (lossless) hipLaunchKernelGGL((rk4_sweep_split_kernel<NW, CHECK, TRAJ, 256, false>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((rk4_sweep_split_kernel<NW, CHECK, TRAJ, 256, true>), grid, dim3(256), 0, s, a);
+        if (lossless) hipLaunchKernelGGL((rk4_sweep_split_kernel<NW, CHECK, TRAJ, 256, false, WSUM>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((rk4_sweep_split_kernel<NW, CHECK, TRAJ, 256, true, WSUM>), grid, dim3(256), 0, s, a);
     } else {
         const dim3 grid((unsigned)((lanes + 63) / 64));
-        if (lossless) hipLaunchKernelGGL((rk4_sweep_split_kernel<NW, CHECK, TRAJ, 64, false>), grid, dim3(64), 0, s, a);
-        else hipLaunchKernelGGL((rk4_sweep_split_kernel<NW, CHECK, TRAJ, 64, true>), grid, dim3(64), 0, s, a);
+        if (lossless) hipLaunchKernelGGL((rk4_sweep_split_kernel<NW, CHECK, TRAJ, 64, false, WSUM>), grid, dim3(64), 0, s, a);
+        else hipLaunchKernelGGL((rk4_sweep_split_kernel<NW, CHECK, TRAJ, 64, true, WSUM>), grid, dim3(64), 0, s, a);
     }
     return hipGetLastError();
 }
@@ -420,6 +439,20 @@ static hipError_t launch_split_nw(hipStream_t s, int check, bool lossless, int b
 static hipError_t launch_sweep_split(hipStream_t s, int n_waves, int check, bool lossless, int block, const SweepArgs<double> &a) {
     if (a.n_points == 0) return hipSuccess;
     return n_waves == 4 ? launch_split_nw<4>(s, check, lossless, block, a) : launch_split_nw<6>(s, check, lossless, block, a);
+}
+
+// the per-wave summary (WSUM), no trajectory
+template <int NW>
+static hipError_t launch_split_waves_nw(hipStream_t s, int check, bool lossless, int block, const SweepArgs<double> &a) {
+    switch (check) {
+        case CHECK_NONE: return launch_split_one<NW, CHECK_NONE, false, true>(s, lossless, block, a);
+        case CHECK_BLOCK: return launch_split_one<NW, CHECK_BLOCK, false, true>(s, lossless, block, a);
+        default: return launch_split_one<NW, CHECK_EXACT, false, true>(s, lossless, block, a);
+    }
+}
+static hipError_t launch_sweep_split_waves(hipStream_t s, int n_waves, int check, bool lossless, int block, const SweepArgs<double> &a) {
+    if (a.n_points == 0) return hipSuccess;
+    return n_waves == 4 ? launch_split_waves_nw<4>(s, check, lossless, block, a) : launch_split_waves_nw<6>(s, check, lossless, block, a);
 }
 
 }  // namespace psa

@@ -6,6 +6,8 @@
   point comes back NaN: its ``_omega0_from_dispersion`` looks for a field the dataclass does not have)
 * ``scan_dbeta_seeded_signal(...)``: a working direct-dbeta scan with gain_mode "end" | "max" and the
   argmax-over-sweep summary -- what the reference's dead ``scan_mismatch_seeded_signal`` (:43-259) set out to do.
+  ``with_idler=True`` adds the idler gain Gi (per-wave summary, psa_rk4_sweep_waves_*).
+* ``seeded_mismatch_scan(gain_mode)``: the scenario that dead function hard-codes (:56-93), run: delta, Gs, Gi, best point.
 * ``scan_gain_grid(...)``: the same sweep over a 2-D (pump-2 wavelength x signal wavelength) grid in one launch
   (BASELINE config 3's shape: 1024 x 1024 points); the reference has no grid builder.
 * ``scan_six_wave_grid(...)``: BASELINE config 5's shape -- a grid over the detunings (Omega1, Omega2) of two
@@ -135,7 +137,8 @@ def _run_block(shard: _Shard, ok_blk, dbeta_blk, *, dbeta2_blk=None, extras=(), 
     ok_blk, dbeta_blk (, dbeta2_blk): the block's validity mask and per-metre mismatch; ``extras``: per-point float64
     arrays of the block that travel with the record (the caller-unit dbeta).  run_kw: rk4_sweep's arguments, per-point
     ones already cut to the block.  Returns (SweepResult over the valid points of the WHOLE sweep in order | None,
-    ok[n], [extras over n])."""
+    ok[n], [extras over n]).  With ``wave_summary=True`` in run_kw the per-wave columns (p_wave_end, p_wave_max) ride in
+    the same all_gather as 2 * n_waves more extras words per point (float64; a float32 sweep's values convert exactly)."""
     ok_blk = np.asarray(ok_blk, dtype=bool)
     idx = np.flatnonzero(ok_blk)
     res = None
@@ -158,6 +161,13 @@ def _run_block(shard: _Shard, ok_blk, dbeta_blk, *, dbeta2_blk=None, extras=(), 
     bad = np.full(nb, NEVER_RAN, dtype=np.int64)
     if res is not None:
         a_end[idx], p_end[idx], p_max[idx], bad[idx] = res.a_end, res.p_end, res.p_max, res.first_bad_step
+    n_user = len(extras)
+    waves = bool(run_kw.get("wave_summary"))
+    if waves:                                   # columns j of p_wave_end, then of p_wave_max
+        wcols = np.full((nb, 2 * n_waves), np.nan)
+        if res is not None:
+            wcols[idx, :n_waves], wcols[idx, n_waves:] = res.p_wave_end, res.p_wave_max
+        extras = list(extras) + [wcols[:, k] for k in range(2 * n_waves)]
     parts = [layout.pack(a_end, p_end, p_max, bad, pad_to=shard.width)]
     for e in extras:
         buf = np.zeros(shard.width, dtype=np.float64)
@@ -173,12 +183,17 @@ def _run_block(shard: _Shard, ok_blk, dbeta_blk, *, dbeta2_blk=None, extras=(), 
         for k in range(len(extras)):
             ext[k].append(gathered[r, nrec + k * shard.width: nrec + k * shard.width + (hi - lo)].view(np.float64))
     a_end, p_end, p_max, bad = (np.concatenate(c) for c in cols)
+    ext = [np.concatenate(e) for e in ext]
     ok = bad != NEVER_RAN
     full = None
     if ok.any():
+        w_end = w_max = None
+        if waves:
+            w = np.stack(ext[n_user:], axis=1)[ok].astype(layout.dtype)
+            w_end, w_max = np.ascontiguousarray(w[:, :n_waves]), np.ascontiguousarray(w[:, n_waves:])
         full = SweepResult(a_end[ok], p_end[ok], p_max[ok], bad[ok], int(run_kw["n_steps"]), int(run_kw["save_every"]),
-                           0.0 if res is None else res.elapsed_ms)
-    return full, ok, [np.concatenate(e) for e in ext]
+                           0.0 if res is None else res.elapsed_ms, None, w_end, w_max)
+    return full, ok, ext[:n_user]
 
 
 # ---- the engine call shared by the drivers ------------------------------------------------------------------
@@ -467,12 +482,15 @@ def scan_dbeta_seeded_signal(*, cfg: SimulationConfig, delta_beta: Sequence[floa
                              p_in: Sequence[float], phase_in: Optional[Sequence[float]] = None,
                              length_unit: str = "m", gain_mode: GainMode = "end", gain_unit: str = "dB",
                              dtype=np.float64, device: Optional[int] = None,
-                             devices: Optional[Sequence[int]] = None) -> dict:
+                             devices: Optional[Sequence[int]] = None, with_idler: bool = False) -> dict:
     """Scan the phase mismatch directly (PROVIDED dbeta per point) and summarise the signal gain.
 
     delta_beta: (N,) in 1/length_unit.  gamma / alpha: scalars or (N,) in per-length_unit.
     Returns dict(delta_beta, gain, best_index, best_delta_beta, best_gain, n_finite, result=SweepResult,
     points_per_s) -- gain with the reference's NaN rules, argmax/max reduced on the GPU.
+    with_idler=True also returns, as the reference's seeded scan reports Gi next to Gs (scan_mismtach.py:139-153):
+    gain_idler (the idler's metric over the SIGNAL's input power p_in[2], its Gi definition :83, :150), best_gain_idler
+    (that gain at best_index) and p_wave_metric (N, n_waves), the gain_mode metric of every wave.
     """
     if gain_mode not in ("end", "max"):
         raise ValueError(f"Unknown gain_mode={gain_mode!r}. Use 'end' or 'max'.")
@@ -493,11 +511,73 @@ def scan_dbeta_seeded_signal(*, cfg: SimulationConfig, delta_beta: Sequence[floa
     res, _, _ = _run_block(shard, np.ones(shard.hi - shard.lo, dtype=bool), shard.block(db / scale), dtype=dtype,
                            devices=devices, z_max=L, n_steps=n_steps_of(L, dz_m), save_every=cfg.save_every,
                            check_nan=bool(cfg.check_nan), gamma=shard.block(gam), alpha=shard.block(alp),
-                           a0=make_initial_amplitudes(p0, ph0))
+                           a0=make_initial_amplitudes(p0, ph0), wave_summary=bool(with_idler))
     gain, bi, bg, nf = res.summary(p0[2], mode=gain_mode, unit=unit, device=shard.device)
     secs = max(res.elapsed_ms, 1e-9) * 1e-3
-    return dict(delta_beta=db, gain=gain, best_index=bi, best_delta_beta=(float(db[bi]) if bi >= 0 else float("nan")),
-                best_gain=bg, n_finite=nf, result=res, points_per_s=db.size / secs)
+    out = dict(delta_beta=db, gain=gain, best_index=bi, best_delta_beta=(float(db[bi]) if bi >= 0 else float("nan")),
+               best_gain=bg, n_finite=nf, result=res, points_per_s=db.size / secs)
+    if with_idler:
+        gi = res.summary(p0[2], mode=gain_mode, unit=unit, device=shard.device, wave=3)[0]
+        out.update(gain_idler=gi, best_gain_idler=(float(gi[bi]) if bi >= 0 else float("nan")),
+                   p_wave_metric=(res.p_wave_max if gain_mode == "max" else res.p_wave_end))
+    return out
+
+
+def seeded_mismatch_scan(gain_mode: GainMode = "end", *, device: Optional[int] = None,
+                         devices: Optional[Sequence[int]] = None, verbose: bool = False) -> dict:
+    """The scenario hard-coded in the reference's ``scan_mismatch_seeded_signal`` (scan_mismtach.py:43-259), which cannot
+    run upstream (it passes ``beta=`` to run_single_simulation): 200 mismatches delta over +-40 1/km put on the idler's
+    beta (beta0 = 5.8e9 1/km for every wave), gamma = 10 1/(W km), alpha = 0, p_in = [0.1, 0.1, 1e-5, 0] W, z_max = 0.5 km
+    in 1e-3 km steps (scan_mismtach.py:56-93), each point's dbeta formed as run_single_simulation(beta_legacy=betas,
+    length_unit="km") forms it.  Gains as the reference defines them (:139-153): Gs = P_s metric / (P_s(z=0) + eps),
+    Gi = P_i metric / (p_in[2] + eps), eps = 1e-30; best = argmax Gs (:183-186).
+
+    Returns dict(delta, Gs, Gi, p_wave_metric (200, 4), best_index, best_delta, best_Gs, best_Gi, result=SweepResult);
+    with verbose the reference's result block is printed."""
+    from .constants import c as c_light
+    from .phase_matching import compute_phase_mismatch
+    mode = gain_mode
+    if mode not in ("end", "max"):
+        raise ValueError(f"Unknown gain_mode={gain_mode!r}. Use 'end' or 'max'.")
+    cfg = custom_simulation_config(z_max=0.5, dz=1e-3)
+    gamma, alpha, P1_total = 10.0, 0.0, 0.1
+    p_in = np.array([P1_total, P1_total, 1e-5, 0.0])
+    beta0, omega = 5.8e9, np.full(4, c_light / 1.55e-6)
+    Ps0_ref = Pi0_ref = float(p_in[2])
+    delta = np.linspace(-40.0, 40.0, 200)
+    eps = 1e-30
+    dbeta_m = np.empty(delta.size)
+    for k, d in enumerate(delta):
+        pre = _prepare(cfg, gamma=gamma, alpha=alpha, dispersion=None, phase_matching_cfg=None,
+                       beta_legacy=beta0 * np.ones(4) + np.array([0.0, 0.0, 0.0, d]), length_unit="km")
+        dbeta_m[k] = compute_phase_mismatch(omega, None, pre["pm"].config).delta_beta
+    L, dz_m = pre["fiber"].length_m, pre["grid"].dz_m
+    shard = _Shard(delta.size, device)
+    a0 = make_initial_amplitudes(p_in, None)
+    res, _, _ = _run_block(shard, np.ones(shard.hi - shard.lo, dtype=bool), shard.block(dbeta_m), devices=devices,
+                           z_max=L, n_steps=n_steps_of(L, dz_m), save_every=cfg.save_every, check_nan=bool(cfg.check_nan),
+                           gamma=gamma / 1e3, alpha=alpha / 1e3, a0=a0, wave_summary=True)
+    metric = res.p_wave_max if mode == "max" else res.p_wave_end
+    Ps0 = float(np.abs(a0[2]) ** 2)                # Ps[0]: the saved row at z = 0
+    Gs = metric[:, 2] / (Ps0 + eps)
+    Gi = metric[:, 3] / (Pi0_ref + eps)
+    best_idx = int(np.argmax(Gs))
+    out = dict(delta=delta, Gs=Gs, Gi=Gi, p_wave_metric=metric, best_index=best_idx, best_delta=float(delta[best_idx]),
+               best_Gs=float(Gs[best_idx]), best_Gi=float(Gi[best_idx]), result=res)
+    if verbose:
+        label = "P(z_max)" if mode == "end" else "max_z P(z)"
+        print("=== Mismatch scan results ===")
+        print(f"gamma = {gamma:.6g} 1/(W*km)")
+        print(f"Total pump power P1_total = {P1_total:.6g} W  (split: {P1_total/2:.6g} + {P1_total/2:.6g} W)")
+        print(f"Seed signal Ps(0) = {Ps0_ref:.6g} W")
+        print(f"Seed idler  Pi(0) = {Pi0_ref:.6g} W")
+        print(f"Ideal_mismatch_guess = {0.0:.6g} 1/km")
+        print(f"Gain metric mode = {mode!r}  -> using {label}")
+        print("--- Best point (max signal gain) ---")
+        print(f"best_delta = {out['best_delta']:.6g} 1/km")
+        print(f"Signal gain Gs = {label}/Ps(0) = {out['best_Gs']:.6g}")
+        print(f"Idler  level Gi = {label}/Pi(0) = {out['best_Gi']:.6g}")
+    return out
 
 
 def scan_gain_grid(*, cfg: SimulationConfig, lambda_p1_m: float, lambda_p2_m: Sequence[float],

@@ -41,19 +41,30 @@ class SweepResult:
     save_every: int
     elapsed_ms: float            # kernel time (hipEvents)
     traj: Optional[np.ndarray] = None   # (N, n_saved, n_waves) when requested
+    p_wave_end: Optional[np.ndarray] = None   # (N, n_waves) |A_j|^2 at the last saved row (wave_summary=True)
+    p_wave_max: Optional[np.ndarray] = None   # (N, n_waves) max over saved rows, NaN-propagating (wave_summary=True)
 
     def gain(self, p0_sig: float, *, mode: str = "max", unit: str = "dB", device: int = 0) -> np.ndarray:
         """Per-point signal gain with the drivers' NaN rules (scan_mismtach.py:376-392); reduced on the GPU."""
         return self.summary(p0_sig, mode=mode, unit=unit, device=device)[0]
 
-    def summary(self, p0_sig: float, *, mode: str = "max", unit: str = "dB", device: int = 0):
-        """(gain[N], best_index, best_gain, n_finite) -- gain_mode "end" | "max" (scan_mismtach.py:27-40)."""
+    def summary(self, p0_sig: float, *, mode: str = "max", unit: str = "dB", device: int = 0, wave: int = 2):
+        """(gain[N], best_index, best_gain, n_finite) -- gain_mode "end" | "max" (scan_mismtach.py:27-40).  ``wave`` other
+        than 2 (the signal) reduces that wave's column of p_wave_end / p_wave_max (a sweep run with wave_summary=True)."""
         if mode not in ("end", "max"):
             raise ValueError(f"Unknown gain_mode={mode!r}. Use 'end' or 'max'.")
         u = str(unit).strip().lower()
         if u not in ("db", "linear"):
             raise ValueError("gain_unit must be 'dB' or 'linear'")
-        metric = self.p_max if mode == "max" else self.p_end
+        if int(wave) == 2:
+            metric = self.p_max if mode == "max" else self.p_end
+        else:
+            cols = self.p_wave_max if mode == "max" else self.p_wave_end
+            if cols is None:
+                raise ValueError("wave != 2 needs the per-wave summary: run the sweep with wave_summary=True")
+            if not 0 <= int(wave) < cols.shape[1]:
+                raise ValueError(f"wave must be in [0, {cols.shape[1]}), got {wave}")
+            metric = np.ascontiguousarray(cols[:, int(wave)])
         # a float32 sweep keeps float32 gains (psa_gain_summary_f32); everything else is reduced in float64
         metric = np.asarray(metric)
         if metric.dtype != np.float32:
@@ -95,6 +106,8 @@ def _sweep_over_devices(devices, dbeta, **kw) -> dict:
         parts = [p for p in pool.map(run, range(k)) if p is not None]
     out = {key: np.concatenate([p[key] for p in parts]) for key in ("a_end", "p_end", "p_max", "first_bad_step")}
     out["traj"] = np.concatenate([p["traj"] for p in parts]) if parts[0]["traj"] is not None else None
+    for key in ("p_wave_end", "p_wave_max"):
+        out[key] = np.concatenate([p[key] for p in parts]) if parts[0].get(key) is not None else None
     out["elapsed_ms"] = max(p["elapsed_ms"] for p in parts)
     return out
 
@@ -102,9 +115,10 @@ def _sweep_over_devices(devices, dbeta, **kw) -> dict:
 def rk4_sweep(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps: Optional[int] = None,
               save_every: int = 10, check_nan: bool = True, gamma, alpha, a0, dbeta2=None, dtype=np.float64,
               device: int = 0, exact_step: Optional[bool] = None, want_traj: bool = False,
-              devices: Optional[Sequence[int]] = None) -> SweepResult:
+              devices: Optional[Sequence[int]] = None, wave_summary: bool = False) -> SweepResult:
     """Propagate N points.  ``dz`` gives n = int(round(z_max/dz)) as integrators.py:194; or pass ``n_steps``.
-    ``devices=[0, 1, ...]`` splits the points over several GPUs of this process (one thread per device)."""
+    ``devices=[0, 1, ...]`` splits the points over several GPUs of this process (one thread per device).
+    ``wave_summary=True`` also fills p_wave_end / p_wave_max: the end and maximum power of every wave."""
     if z_max <= 0.0:
         raise ValueError("z_max must be positive")
     if n_steps is None:
@@ -117,6 +131,8 @@ def rk4_sweep(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps: Optio
         raise ValueError("z_max / dz rounds to zero steps")
     kw = dict(n_steps=int(n_steps), z_max=float(z_max), save_every=int(save_every), gamma=gamma, alpha=alpha, a0=a0,
               dbeta2=dbeta2, check_nan=check_nan, exact_step=exact_step, want_traj=want_traj, dtype=dtype)
+    if wave_summary:
+        kw["wave_summary"] = True
     devs = None if devices is None else [int(d) for d in devices]
     if devs is not None and len(devs) == 0:
         raise ValueError("devices must name at least one GPU")
@@ -126,4 +142,4 @@ def rk4_sweep(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps: Optio
     else:
         r = _native.sweep_host(dbeta, device=(devs[0] if devs else device), **kw)
     return SweepResult(r["a_end"], r["p_end"], r["p_max"], r["first_bad_step"], int(n_steps), int(save_every),
-                       r["elapsed_ms"], r["traj"])
+                       r["elapsed_ms"], r["traj"], r.get("p_wave_end"), r.get("p_wave_max"))
