@@ -63,6 +63,7 @@ extern "C" {
 #define PSA_BCAST_GAMMA      (1u << 0)
 #define PSA_BCAST_ALPHA      (1u << 1)
 #define PSA_BCAST_A0         (1u << 2)
+#define PSA_BCAST_TRANSFER   (1u << 3)   /* psa_rk4_chain_*: one transfer per boundary, used for every point */
 /* options */
 #define PSA_OPT_CHECK_NAN    (1u << 8)   /* SimulationConfig.check_nan (config.py:29): track first_bad_step over ALL
                                             n_steps (also the tail after the last saved row).  Without it
@@ -201,6 +202,58 @@ int psa_rk4_sweep_waves_f32_dev(void *stream, int n_waves, int64_t n_points, int
                                 const float *d_alpha, const float *d_a0_soa, uint32_t flags, float *d_a_end_soa,
                                 float *d_p_sig_end, float *d_p_sig_max, int64_t *d_first_bad_step, float *d_traj_soa,
                                 float *d_p_wave_end_soa, float *d_p_wave_max_soa);
+
+/* ---- a chain of fibre spans with mid-stage transfers (copier - mid-stage - PSA) ----------------------------------
+ * S = n_segments >= 1 spans, each ONE launch of the sweep kernel above on the layout the automatic selector picks, joined
+ * on the device by a small epilogue kernel per span (no host synchronisation between spans).  Span s has
+ *   n_steps[s], seg_len[s]   host arrays [S]: steps and length (n_steps[s] = int(round(L_s/dz_s)); every n_steps[s]
+ *                            must be a multiple of save_every, else PSA_E_SAVE_EVERY)
+ *   dbeta [S][N], dbeta2 [S][N] (n_waves == 6, else NULL)
+ *   gamma, alpha  [S][N], or [S] with PSA_BCAST_GAMMA / PSA_BCAST_ALPHA
+ * and between span s and s+1 the per-wave complex transfer T_s[j] (amplitude gain times e^{i phase}):
+ *   transfer  [S-1][N][n_waves][2], or [S-1][n_waves][2] with PSA_BCAST_TRANSFER; NULL = identity
+ * The FWM phase is the ACCUMULATED mismatch Theta(z) = sum_{k<s} dbeta_k L_k + dbeta_s zeta (zeta: the local coordinate).
+ * The kernels integrate span s in the gauge B_sig = A_sig e^{+i Theta_s} (signal of pair k for 6 waves: its own Theta),
+ * so a boundary is B' = T_s B with the signal(s) also multiplied by e^{+i dbeta_s L_s}; Theta is kept per point in float64.
+ * Outputs, all in the physical (A) frame:
+ *   a_end, p_sig_end     the last saved row of the last span
+ *   p_sig_max            max over every saved row of every span (each span's z = 0 row is the post-transfer state)
+ *   first_bad_step       cumulative step index (sum of the earlier spans' n_steps + the local index); first failure wins
+ *   p_wave_end/_max      as psa_rk4_sweep_waves_* (both NULL, or both given and traj NULL)
+ *   traj_or_null         [N][n_saved_total][n_waves][2], n_saved_total = sum_s (n_steps[s]/save_every + 1)
+ * S == 1 is psa_rk4_sweep_* / psa_rk4_sweep_waves_* exactly (bit-identical outputs).  The host-buffer form sets
+ * PSA_OPT_LOSSLESS for every span whose alpha is 0 (a broadcast 0, or, when S > 1, a per-point row that is 0 everywhere).
+ * Argument errors reuse the codes above (n_segments < 1:
+ * PSA_E_NSTEPS); a trajectory that does not fit the device gets PSA_E_TOO_LARGE before any allocation.
+ */
+int psa_rk4_chain_f64(int device, int n_waves, int64_t n_points, int n_segments, const int64_t *n_steps,
+                      const double *seg_len, int32_t save_every, const double *dbeta, const double *dbeta2,
+                      const double *gamma, const double *alpha, const double *a0_re_im, const double *transfer_re_im,
+                      uint32_t flags, double *a_end_re_im, double *p_sig_end, double *p_sig_max, int64_t *first_bad_step,
+                      double *traj_or_null, double *elapsed_ms_or_null, double *p_wave_end, double *p_wave_max);
+int psa_rk4_chain_f32(int device, int n_waves, int64_t n_points, int n_segments, const int64_t *n_steps,
+                      const double *seg_len, int32_t save_every, const float *dbeta, const float *dbeta2,
+                      const float *gamma, const float *alpha, const float *a0_re_im, const float *transfer_re_im,
+                      uint32_t flags, float *a_end_re_im, float *p_sig_end, float *p_sig_max, int64_t *first_bad_step,
+                      float *traj_or_null, double *elapsed_ms_or_null, float *p_wave_end, float *p_wave_max);
+/* _dev forms: SoA HBM buffers as psa_rk4_sweep_*_dev (a0 [2*n_waves][N | 1], a_end [2*n_waves][N], p_wave_* [n_waves][N],
+ * traj [n_saved_total][n_waves][ld][2]); d_transfer_soa is [S-1][2*n_waves][N] (or [S-1][2*n_waves] with
+ * PSA_BCAST_TRANSFER); n_steps / seg_len stay HOST arrays.  d_workspace: >= psa_rk4_chain_workspace_bytes(...) bytes of
+ * device memory (may be NULL when S == 1).  Asynchronous on `stream`, no allocation: graph-capturable. */
+int psa_rk4_chain_f64_dev(void *stream, int n_waves, int64_t n_points, int n_segments, const int64_t *n_steps,
+                          const double *seg_len, int32_t save_every, const double *d_dbeta, const double *d_dbeta2,
+                          const double *d_gamma, const double *d_alpha, const double *d_a0_soa,
+                          const double *d_transfer_soa, uint32_t flags, double *d_a_end_soa, double *d_p_sig_end,
+                          double *d_p_sig_max, int64_t *d_first_bad_step, double *d_traj_soa, double *d_p_wave_end_soa,
+                          double *d_p_wave_max_soa, void *d_workspace);
+int psa_rk4_chain_f32_dev(void *stream, int n_waves, int64_t n_points, int n_segments, const int64_t *n_steps,
+                          const double *seg_len, int32_t save_every, const float *d_dbeta, const float *d_dbeta2,
+                          const float *d_gamma, const float *d_alpha, const float *d_a0_soa, const float *d_transfer_soa,
+                          uint32_t flags, float *d_a_end_soa, float *d_p_sig_end, float *d_p_sig_max,
+                          int64_t *d_first_bad_step, float *d_traj_soa, float *d_p_wave_end_soa, float *d_p_wave_max_soa,
+                          void *d_workspace);
+/* bytes of d_workspace for a chain (elem_size 4 | 8, wave_summary 0 | 1); -1 for invalid arguments */
+int64_t psa_rk4_chain_workspace_bytes(int n_waves, int64_t n_points, int32_t elem_size, int wave_summary);
 
 /* ---- B1': one RHS evaluation per point (host buffers, blocking) --------------------
  * Replaces yaman_model.rhs_yaman_simplified (yaman_model.py:10-52) for a batch:

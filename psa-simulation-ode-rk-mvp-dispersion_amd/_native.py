@@ -27,6 +27,7 @@ LIB_PATH = os.environ.get("PSA_HIP_LIB") or os.path.join(_PKG_DIR, "libpsa_hip.s
 BCAST_GAMMA = 1 << 0
 BCAST_ALPHA = 1 << 1
 BCAST_A0 = 1 << 2
+BCAST_TRANSFER = 1 << 3
 OPT_CHECK_NAN = 1 << 8
 OPT_EXACT_STEP = 1 << 9
 OPT_LDS_STAGING = 1 << 10
@@ -65,6 +66,17 @@ _SIGS = {
                                               _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
     "psa_rk4_sweep_waves_f32_dev": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int32,
                                               _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
+    # (device|stream, n_waves, N, S, n_steps[S], seg_len[S], save_every, dbeta, dbeta2, gamma, alpha, a0, transfer, flags,
+    #  a_end, p_end, p_max, first_bad, traj, elapsed_ms | (p_wave_end, p_wave_max, workspace))
+    "psa_rk4_chain_f64": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int, _P, _P, C.c_int32] + [_P] * 6
+                          + [C.c_uint32] + [_P] * 8),
+    "psa_rk4_chain_f32": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int, _P, _P, C.c_int32] + [_P] * 6
+                          + [C.c_uint32] + [_P] * 8),
+    "psa_rk4_chain_f64_dev": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, _P, _P, C.c_int32] + [_P] * 6
+                              + [C.c_uint32] + [_P] * 8),
+    "psa_rk4_chain_f32_dev": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, _P, _P, C.c_int32] + [_P] * 6
+                              + [C.c_uint32] + [_P] * 8),
+    "psa_rk4_chain_workspace_bytes": (C.c_int64, [C.c_int, C.c_int64, C.c_int32, C.c_int]),
     "psa_yaman_rhs_f64": (C.c_int, [C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "psa_gain_summary_f64": (C.c_int, [C.c_int, C.c_int64, _P, _P, C.c_double, C.c_int, _P, _P, _P, _P]),
     "psa_gain_summary_f64_dev": (C.c_int, [_P, C.c_int64, _P, _P, C.c_double, C.c_int, _P, _P, _P, _P, _P]),
@@ -286,6 +298,102 @@ def sweep_waves_device(*, stream: int, n_waves: int, n_points: int, n_steps: int
               d_dbeta or None, d_dbeta2 or None, d_gamma or None, d_alpha or None, d_a0_soa or None, int(flags),
               d_a_end_soa or None, d_p_end or None, d_p_max or None, d_first_bad or None, d_traj_soa or None,
               d_p_wave_end_soa or None, d_p_wave_max_soa or None))
+
+
+def chain_host(dbeta, *, n_steps, seg_len, save_every: int, gamma, alpha, a0, transfers=None, dbeta2=None,
+               check_nan: bool = True, exact_step: Optional[bool] = None, want_traj: bool = False, dtype=np.float64,
+               device: int = 0, wave_summary: bool = False, extra_flags: int = 0) -> dict:
+    """A chain of S fibre spans on the GPU (psa_rk4_chain_*; host buffers in and out).
+
+    dbeta (S, N) [and dbeta2 (S, N) for 6 waves]; n_steps, seg_len (S,); gamma / alpha (S,) broadcast or (S, N);
+    a0 (n_waves,) or (N, n_waves) complex; transfers None, (S-1, n_waves) broadcast or (S-1, N, n_waves) complex.
+    Returns the keys of sweep_host; traj is (N, n_saved_total, n_waves).
+    """
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError("dtype must be float64 or float32")
+    cdt = np.complex128 if dtype == np.float64 else np.complex64
+    dbeta = np.ascontiguousarray(np.asarray(dbeta), dtype=dtype)
+    if dbeta.ndim != 2 or dbeta.shape[0] < 1:
+        raise ValueError("dbeta must have shape (S, N)")
+    S, N = (int(x) for x in dbeta.shape)
+    steps = np.ascontiguousarray(np.asarray(n_steps), dtype=np.int64)
+    lens = np.ascontiguousarray(np.asarray(seg_len), dtype=np.float64)
+    if steps.shape != (S,) or lens.shape != (S,):
+        raise ValueError(f"n_steps and seg_len must have shape ({S},)")
+    a0 = np.ascontiguousarray(np.asarray(a0), dtype=cdt)
+    if a0.ndim == 1:
+        a0 = a0[None, :]
+    if a0.ndim != 2 or a0.shape[1] not in (4, 6) or a0.shape[0] not in (1, N):
+        raise ValueError(f"a0 must have shape (n_waves,) or ({N}, n_waves) with n_waves in (4, 6)")
+    nw = int(a0.shape[1])
+    flags = int(extra_flags) | (BCAST_A0 if a0.shape[0] == 1 else 0)
+    per_span = []
+    for name, x, bit in (("gamma", gamma, BCAST_GAMMA), ("alpha", alpha, BCAST_ALPHA)):
+        arr = np.ascontiguousarray(np.asarray(x), dtype=dtype)
+        if arr.shape == (S,):
+            flags |= bit
+        elif arr.shape != (S, N):
+            raise ValueError(f"{name} must have shape ({S},) or ({S}, {N})")
+        per_span.append(arr)
+    gamma, alpha = per_span
+    if check_nan:
+        flags |= OPT_CHECK_NAN
+        if exact_step or (exact_step is None and dtype == np.float64):
+            flags |= OPT_EXACT_STEP
+    d2 = None
+    if nw == 6:
+        if dbeta2 is None:
+            raise ValueError("n_waves == 6 needs dbeta2")
+        d2 = np.ascontiguousarray(np.asarray(dbeta2), dtype=dtype)
+        if d2.shape != dbeta.shape:
+            raise ValueError("dbeta2 must match dbeta")
+    elif dbeta2 is not None:
+        raise ValueError("dbeta2 is only meaningful for 6 waves")
+    tr = None
+    if transfers is not None and S > 1:
+        tr = np.ascontiguousarray(np.asarray(transfers), dtype=cdt)
+        if tr.shape == (S - 1, nw):
+            flags |= BCAST_TRANSFER
+        elif tr.shape != (S - 1, N, nw):
+            raise ValueError(f"transfers must have shape ({S - 1}, {nw}) or ({S - 1}, {N}, {nw})")
+    n_rows = int(np.sum(steps // save_every + 1)) if save_every > 0 else 0
+    a_end = np.empty((N, nw), dtype=cdt)
+    p_end = np.empty(N, dtype=dtype)
+    p_max = np.empty(N, dtype=dtype)
+    bad = np.empty(N, dtype=np.int64)
+    traj = np.empty((N, n_rows, nw), dtype=cdt) if want_traj else None
+    w_end = np.empty((N, nw), dtype=dtype) if wave_summary else None
+    w_max = np.empty((N, nw), dtype=dtype) if wave_summary else None
+    ms = C.c_double(0.0)
+    fn = lib().psa_rk4_chain_f64 if dtype == np.float64 else lib().psa_rk4_chain_f32
+    _check(fn(int(device), nw, N, S, _ptr(steps), _ptr(lens), int(save_every), _ptr(dbeta), _ptr(d2), _ptr(gamma),
+              _ptr(alpha), _ptr(a0), _ptr(tr), flags, _ptr(a_end), _ptr(p_end), _ptr(p_max), _ptr(bad), _ptr(traj),
+              C.cast(C.byref(ms), C.c_void_p), _ptr(w_end), _ptr(w_max)))
+    return dict(a_end=a_end, p_end=p_end, p_max=p_max, first_bad_step=bad, traj=traj, elapsed_ms=ms.value,
+                p_wave_end=w_end, p_wave_max=w_max)
+
+
+def chain_workspace_bytes(n_waves: int, n_points: int, dtype=np.float64, wave_summary: bool = False) -> int:
+    """Device scratch a chain of more than one span needs (psa_rk4_chain_workspace_bytes)."""
+    return int(lib().psa_rk4_chain_workspace_bytes(int(n_waves), int(n_points), int(np.dtype(dtype).itemsize),
+                                                   int(bool(wave_summary))))
+
+
+def chain_device(*, stream: int, n_waves: int, n_points: int, n_steps, seg_len, save_every: int, d_dbeta: int,
+                 d_dbeta2: int, d_gamma: int, d_alpha: int, d_a0_soa: int, d_transfer_soa: int, flags: int,
+                 d_a_end_soa: int, d_p_end: int, d_p_max: int, d_first_bad: int, d_traj_soa: int = 0,
+                 d_p_wave_end: int = 0, d_p_wave_max: int = 0, d_workspace: int = 0, dtype=np.float64) -> None:
+    """psa_rk4_chain_*_dev on device pointers (ints); n_steps / seg_len are host sequences of length S."""
+    steps = np.ascontiguousarray(np.asarray(n_steps), dtype=np.int64)
+    lens = np.ascontiguousarray(np.asarray(seg_len), dtype=np.float64)
+    if steps.ndim != 1 or steps.shape != lens.shape:
+        raise ValueError("n_steps and seg_len must be 1-D of equal length")
+    fn = lib().psa_rk4_chain_f64_dev if np.dtype(dtype) == np.float64 else lib().psa_rk4_chain_f32_dev
+    _check(fn(stream or None, int(n_waves), int(n_points), int(steps.shape[0]), _ptr(steps), _ptr(lens),
+              int(save_every), d_dbeta or None, d_dbeta2 or None, d_gamma or None, d_alpha or None, d_a0_soa or None,
+              d_transfer_soa or None, int(flags), d_a_end_soa or None, d_p_end or None, d_p_max or None,
+              d_first_bad or None, d_traj_soa or None, d_p_wave_end or None, d_p_wave_max or None, d_workspace or None))
 
 
 def yaman_rhs_host(z, a, gamma, alpha, dbeta, *, terms: bool = False, device: int = 0):

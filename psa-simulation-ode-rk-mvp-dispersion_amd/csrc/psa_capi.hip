@@ -1,4 +1,4 @@
-// psa_capi.hip -- the extern "C" surface of libpsa_hip.so (see include/psa_rk4.h for the contract and the
+// psa_capi.hip -- the extern "C" surface of libpsa_hip.so, fibre chains (psa_rk4_chain_*) included (see include/psa_rk4.h for the contract and the
 // reference file:line each entry point replaces).  Host code only: argument validation, HBM staging for the
 // host-buffer variants, launches.  No CPU compute path exists here on purpose: without a gfx950 device the
 // host-buffer calls fail with PSA_E_DEVICE / a hipError_t -- they never fall back.
@@ -564,6 +564,280 @@ int sweep_host(int device, int n_waves, int64_t n_points, int64_t n_steps, doubl
     return PSA_OK;
 }
 
+// ---- fibre chains: S spans, one sweep launch + one epilogue (psa_chain.hip) each ------------------------------------
+template <typename T> struct EpilogueLaunch;
+template <> struct EpilogueLaunch<double> { static constexpr auto fn = psa::launch_chain_epilogue_f64; };
+template <> struct EpilogueLaunch<float> { static constexpr auto fn = psa::launch_chain_epilogue_f32; };
+
+// device scratch of a chain of more than one span: Theta (float64, one per signal), the next span's a0, and the
+// span's own outputs before they are folded into the running ones
+int64_t chain_workspace_bytes(int n_waves, int64_t n_points, size_t elem, bool waves) {
+    if ((n_waves != 4 && n_waves != 6) || n_points < 0 || (elem != 4 && elem != 8)) return -1;
+    using C = Carver;
+    const size_t N = (size_t)n_points, nc = 2 * (size_t)n_waves;
+    return (int64_t)(C::aligned(N * 8) * (n_waves == 6 ? 2 : 1) + 2 * C::aligned(nc * N * elem) +
+                     2 * C::aligned(N * elem) + C::aligned(N * 8) + (waves ? 2 * C::aligned((size_t)n_waves * N * elem) : 0));
+}
+
+// argument rules of psa_rk4_chain_*; *rows_total = sum over spans of n_steps[s] / save_every + 1
+int validate_chain(int n_waves, int64_t n_points, int n_segments, const int64_t *n_steps, const double *seg_len,
+                   int32_t save_every, const void *dbeta, const void *dbeta2, const void *gamma, const void *alpha,
+                   const void *a0, const void *a_end, const void *p_end, const void *p_max, const void *first_bad,
+                   uint32_t flags, const void *traj, const void *wave_end, const void *wave_max, size_t elem,
+                   int64_t *rows_total) {
+    if (n_segments < 1) return fail(PSA_E_NSTEPS, "n_segments must be >= 1, got %d", n_segments);
+    if (!n_steps || !seg_len) return fail(PSA_E_NULLPTR, "n_steps / seg_len is NULL");
+    int rc = validate_common(n_waves, n_points, n_steps[0], seg_len[0], save_every, dbeta, dbeta2, gamma, alpha, a0,
+                             a_end, p_end, p_max, first_bad, flags, traj != nullptr, elem);
+    if (rc != PSA_OK) return rc;
+    int64_t rows = 0;
+    for (int s = 0; s < n_segments; ++s) {
+        if (n_steps[s] <= 0 || n_steps[s] > 2147483647LL)
+            return fail(PSA_E_NSTEPS, "n_steps[%d] must be in [1, 2^31), got %lld", s, (long long)n_steps[s]);
+        if (!(seg_len[s] > 0.0) || !std::isfinite(seg_len[s])) return fail(PSA_E_ZMAX, "seg_len[%d] must be positive", s);
+        // a_end is the last saved row: a tail after it would silently shorten the span
+        if (n_steps[s] % save_every != 0)
+            return fail(PSA_E_SAVE_EVERY, "n_steps[%d] = %lld is not a multiple of save_every = %d", s,
+                        (long long)n_steps[s], (int)save_every);
+        rows += n_steps[s] / save_every + 1;
+    }
+    if ((wave_end != nullptr) != (wave_max != nullptr))
+        return fail(PSA_E_NULLPTR, "p_wave_end and p_wave_max are given together or not at all");
+    if (wave_end && (rc = validate_waves(flags, traj != nullptr)) != PSA_OK) return rc;
+    if (traj && (long double)rows * 2 * n_waves * (long double)traj_ld_of(n_points, elem) > 4.0e18L)
+        return fail(PSA_E_TOO_LARGE, "trajectory buffer too large");
+    *rows_total = rows;
+    return PSA_OK;
+}
+
+// lossless_or_null: host [S], span s gets PSA_OPT_LOSSLESS where it is non-zero (the host-buffer entry points: a
+// broadcast alpha of 0); `_dev` callers pass PSA_OPT_LOSSLESS for the whole chain instead.
+template <typename T>
+int chain_dev(void *stream, int n_waves, int64_t n_points, int n_segments, const int64_t *n_steps, const double *seg_len,
+              int32_t save_every, const T *d_dbeta, const T *d_dbeta2, const T *d_gamma, const T *d_alpha,
+              const T *d_a0_soa, const T *d_transfer_soa, uint32_t flags, T *d_a_end_soa, T *d_p_end, T *d_p_max,
+              int64_t *d_first_bad, T *d_traj_soa, T *d_wave_end, T *d_wave_max, void *d_workspace,
+              const unsigned char *lossless_or_null = nullptr) {
+    int64_t rows_total = 0;
+    int rc = validate_chain(n_waves, n_points, n_segments, n_steps, seg_len, save_every, d_dbeta, d_dbeta2, d_gamma,
+                            d_alpha, d_a0_soa, d_a_end_soa, d_p_end, d_p_max, d_first_bad, flags, d_traj_soa, d_wave_end,
+                            d_wave_max, sizeof(T), &rows_total);
+    if (rc != PSA_OK) return rc;
+    if (n_points == 0) return PSA_OK;
+    const int S = n_segments;
+    auto span_flags = [&](int s) {
+        uint32_t f = flags & ~PSA_BCAST_TRANSFER;
+        if (s > 0) f &= ~PSA_BCAST_A0;                         // the next span starts from a per-point state
+        if (lossless_or_null && lossless_or_null[s]) f |= PSA_OPT_LOSSLESS;
+        return f;
+    };
+    if (S == 1)   // one span IS the sweep: same launch, same outputs, bit for bit
+        return sweep_dev<T>(stream, n_waves, n_points, n_steps[0], seg_len[0], save_every, d_dbeta, d_dbeta2, d_gamma,
+                            d_alpha, d_a0_soa, span_flags(0), d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa,
+                            d_wave_end, d_wave_max);
+    if (!d_workspace) return fail(PSA_E_NULLPTR, "a chain of more than one span needs d_workspace");
+
+    const size_t N = (size_t)n_points;
+    const int nc = 2 * n_waves;
+    const bool waves = d_wave_end != nullptr;
+    Carver ws;
+    ws.base = (char *)d_workspace;
+    double *theta = ws.take<double>(N);
+    double *theta2 = n_waves == 6 ? ws.take<double>(N) : nullptr;
+    T *a0_next = ws.take<T>(nc * N);
+    T *a_end_s = ws.take<T>(nc * N);
+    T *p_end_s = ws.take<T>(N);
+    T *p_max_s = ws.take<T>(N);
+    int64_t *bad_s = ws.take<int64_t>(N);
+    T *wend_s = waves ? ws.take<T>(n_waves * N) : nullptr;
+    T *wmax_s = waves ? ws.take<T>(n_waves * N) : nullptr;
+
+    const size_t ld = (flags & PSA_OPT_TRAJ_LD) ? (size_t)traj_ld_of(n_points, sizeof(T)) : N;
+    const size_t g_step = (flags & PSA_BCAST_GAMMA) ? 1 : N, a_step = (flags & PSA_BCAST_ALPHA) ? 1 : N;
+    const size_t t_step = (flags & PSA_BCAST_TRANSFER) ? (size_t)nc : nc * N;
+    const T *a0 = d_a0_soa;
+    int64_t row = 0, step_off = 0;
+    for (int s = 0; s < S; ++s) {
+        const bool first = s == 0, last = s == S - 1;
+        T *traj_s = d_traj_soa ? d_traj_soa + (size_t)row * n_waves * ld * 2 : nullptr;
+        rc = sweep_dev<T>(stream, n_waves, n_points, n_steps[s], seg_len[s], save_every, d_dbeta + s * N,
+                          d_dbeta2 ? d_dbeta2 + s * N : nullptr, d_gamma + s * g_step, d_alpha + s * a_step, a0,
+                          span_flags(s), a_end_s, first ? d_p_end : p_end_s, first ? d_p_max : p_max_s,
+                          first ? d_first_bad : bad_s, traj_s, waves ? (first ? d_wave_end : wend_s) : nullptr,
+                          waves ? (first ? d_wave_max : wmax_s) : nullptr);
+        if (rc != PSA_OK) return rc;
+        psa::ChainEpilogue<T> e;
+        e.n = n_points;
+        e.n_waves = n_waves;
+        e.first = first;
+        e.fold = !first;
+        e.a_end_s = a_end_s;
+        e.p_end_s = p_end_s;
+        e.p_max_s = p_max_s;
+        e.first_bad_s = (const long long *)bad_s;
+        e.wave_end_s = wend_s;
+        e.wave_max_s = wmax_s;
+        e.p_end = d_p_end;
+        e.p_max = d_p_max;
+        e.first_bad = (long long *)d_first_bad;
+        e.wave_end = d_wave_end;
+        e.wave_max = d_wave_max;
+        e.step_offset = step_off;
+        e.theta = theta;
+        e.theta2 = theta2;
+        e.traj = traj_s;
+        e.traj_ld = (long long)ld;
+        e.rows = n_steps[s] / save_every + 1;
+        e.a_end_out = last ? d_a_end_soa : nullptr;
+        e.transfer = (!last && d_transfer_soa) ? d_transfer_soa + s * t_step : nullptr;
+        e.transfer_stride = (flags & PSA_BCAST_TRANSFER) ? 0 : 1;
+        e.dbeta = d_dbeta + s * N;
+        e.dbeta2 = d_dbeta2 ? d_dbeta2 + s * N : nullptr;
+        e.seg_len = seg_len[s];
+        e.a0_next = a0_next;
+        hipError_t he = EpilogueLaunch<T>::fn((hipStream_t)stream, e);
+        if (he != hipSuccess) return hip_fail(he, "chain epilogue launch");
+        a0 = a0_next;
+        row += e.rows;
+        step_off += n_steps[s];
+    }
+    return PSA_OK;
+}
+
+template <typename T>
+int chain_host(int device, int n_waves, int64_t n_points, int n_segments, const int64_t *n_steps, const double *seg_len,
+               int32_t save_every, const T *dbeta, const T *dbeta2, const T *gamma, const T *alpha, const T *a0,
+               const T *transfer, uint32_t flags, T *a_end, T *p_end, T *p_max, int64_t *first_bad, T *traj,
+               double *elapsed_ms, T *wave_end, T *wave_max) {
+    int64_t rows_total = 0;
+    int rc = validate_chain(n_waves, n_points, n_segments, n_steps, seg_len, save_every, dbeta, dbeta2, gamma, alpha,
+                            a0, a_end, p_end, p_max, first_bad, flags, traj, wave_end, wave_max, sizeof(T), &rows_total);
+    if (rc != PSA_OK) return rc;
+    if (elapsed_ms) *elapsed_ms = 0.0;
+    if (n_points == 0) return PSA_OK;
+    rc = check_device(device, "the fibre chain");
+    if (rc != PSA_OK) return rc;
+
+    const int S = n_segments, nc = 2 * n_waves;
+    const size_t N = (size_t)n_points;
+    const bool waves = wave_end != nullptr;
+    // the reference's alpha == 0.0 branch, span by span: a broadcast 0, or (S > 1, where a lossy span elsewhere makes the
+    // alpha array per point) a span whose row is 0 everywhere.  One span keeps psa_rk4_sweep_*'s rule: bit-identical.
+    std::vector<unsigned char> lossless((size_t)S, 0);
+    for (int s = 0; s < S; ++s) {
+        const T *a = (flags & PSA_BCAST_ALPHA) ? alpha + s : alpha + (size_t)s * N;
+        const size_t n_a = (flags & PSA_BCAST_ALPHA) ? 1 : (S > 1 ? N : 0);
+        if (n_a == 0) continue;
+        bool zero = true;
+        for (size_t i = 0; i < n_a && zero; ++i) zero = a[i] == T(0);
+        lossless[(size_t)s] = zero;
+    }
+    if (traj) flags |= PSA_OPT_TRAJ_LD;
+    const size_t n_gamma = (flags & PSA_BCAST_GAMMA) ? (size_t)S : S * N;
+    const size_t n_alpha = (flags & PSA_BCAST_ALPHA) ? (size_t)S : S * N;
+    const size_t n_a0 = (flags & PSA_BCAST_A0) ? 1 : N;
+    const size_t n_tr = transfer ? (size_t)(S - 1) * ((flags & PSA_BCAST_TRANSFER) ? 1 : N) * nc : 0;
+    const size_t ld = (size_t)traj_ld_of(n_points, sizeof(T));
+    const size_t traj_elems = traj ? (size_t)rows_total * nc * ld : 0;
+    const size_t traj_host_elems = traj ? (size_t)rows_total * nc * N : 0;
+
+    using C = Carver;
+    const size_t ws_bytes = C::aligned((size_t)chain_workspace_bytes(n_waves, n_points, sizeof(T), waves));
+    const size_t total = C::aligned(S * N * sizeof(T)) * (dbeta2 ? 2 : 1) + C::aligned(n_gamma * sizeof(T)) +
+                         C::aligned(n_alpha * sizeof(T)) + 2 * C::aligned(n_a0 * nc * sizeof(T)) +
+                         2 * C::aligned(n_tr * sizeof(T)) + 2 * C::aligned(N * nc * sizeof(T)) +
+                         2 * C::aligned(N * sizeof(T)) + C::aligned(N * 8) +
+                         (waves ? 4 * C::aligned(N * n_waves * sizeof(T)) : 0) + ws_bytes +
+                         C::aligned(traj_elems * sizeof(T)) + C::aligned(traj_host_elems * sizeof(T));
+
+    DeviceScope scope;
+    DevBuf b_all;
+    CtxLease lease;
+    HIP_RET(scope.enter(device));
+    if (traj) {   // say "too large" before hipMalloc says "out of memory"
+        size_t free_b = 0, total_b = 0;
+        HIP_RET(hipMemGetInfo(&free_b, &total_b));
+        if (total > CTX_ARENA_KEEP && total > free_b)
+            return fail(PSA_E_TOO_LARGE, "chain trajectory of %.3g GB does not fit the %.3g GB free on device %d",
+                        (double)total / 1e9, (double)free_b / 1e9, device);
+    }
+    HIP_RET(lease.acquire(device));
+    HostCtx &cx = *lease.c;
+    hipStream_t st = cx.st;
+    Carver cv;
+    if (total <= CTX_ARENA_KEEP) {
+        HIP_RET(cx.need_arena(total));
+        cv.base = (char *)cx.arena;
+    } else {
+        HIP_RET(b_all.alloc(total));
+        cv.base = (char *)b_all.p;
+    }
+    T *d_dbeta = cv.take<T>(S * N);
+    T *d_dbeta2 = dbeta2 ? cv.take<T>(S * N) : nullptr;
+    T *d_gamma = cv.take<T>(n_gamma);
+    T *d_alpha = cv.take<T>(n_alpha);
+    T *d_a0_aos = cv.take<T>(n_a0 * nc);
+    T *d_a0_soa = cv.take<T>(n_a0 * nc);
+    T *d_tr_aos = n_tr ? cv.take<T>(n_tr) : nullptr;
+    T *d_tr_soa = n_tr ? cv.take<T>(n_tr) : nullptr;
+    T *d_aend_soa = cv.take<T>(N * nc);
+    T *d_aend_aos = cv.take<T>(N * nc);
+    T *d_pend = cv.take<T>(N);
+    T *d_pmax = cv.take<T>(N);
+    int64_t *d_bad = cv.take<int64_t>(N);
+    T *d_wend_soa = waves ? cv.take<T>(N * n_waves) : nullptr;
+    T *d_wmax_soa = waves ? cv.take<T>(N * n_waves) : nullptr;
+    T *d_wend = waves ? cv.take<T>(N * n_waves) : nullptr;
+    T *d_wmax = waves ? cv.take<T>(N * n_waves) : nullptr;
+    void *d_ws = cv.take<char>(ws_bytes);
+    T *d_traj = traj ? cv.take<T>(traj_elems) : nullptr;
+    T *d_traj_aos = traj ? cv.take<T>(traj_host_elems) : nullptr;
+
+    HIP_RET(hipMemcpyAsync(d_dbeta, dbeta, S * N * sizeof(T), hipMemcpyHostToDevice, st));
+    if (dbeta2) HIP_RET(hipMemcpyAsync(d_dbeta2, dbeta2, S * N * sizeof(T), hipMemcpyHostToDevice, st));
+    HIP_RET(hipMemcpyAsync(d_gamma, gamma, n_gamma * sizeof(T), hipMemcpyHostToDevice, st));
+    HIP_RET(hipMemcpyAsync(d_alpha, alpha, n_alpha * sizeof(T), hipMemcpyHostToDevice, st));
+    HIP_RET(hipMemcpyAsync(d_a0_aos, a0, n_a0 * nc * sizeof(T), hipMemcpyHostToDevice, st));
+    HIP_RET(Launch<T>::a2s(st, d_a0_aos, d_a0_soa, (long long)n_a0, nc));
+    if (n_tr) {
+        HIP_RET(hipMemcpyAsync(d_tr_aos, transfer, n_tr * sizeof(T), hipMemcpyHostToDevice, st));
+        if (flags & PSA_BCAST_TRANSFER) {   // [S-1][n_waves][2] is already [S-1][2*n_waves]
+            HIP_RET(hipMemcpyAsync(d_tr_soa, d_tr_aos, n_tr * sizeof(T), hipMemcpyDeviceToDevice, st));
+        } else {                           // [S-1][N][n_waves][2] -> [S-1][2*n_waves][N]
+            for (int s = 0; s + 1 < S; ++s)
+                HIP_RET(Launch<T>::a2s(st, d_tr_aos + (size_t)s * N * nc, d_tr_soa + (size_t)s * N * nc, (long long)N, nc));
+        }
+    }
+    HIP_RET(hipEventRecord(cx.ev0, st));
+    rc = chain_dev<T>(st, n_waves, n_points, S, n_steps, seg_len, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha,
+                      d_a0_soa, d_tr_soa, flags, d_aend_soa, d_pend, d_pmax, d_bad, d_traj, d_wend_soa, d_wmax_soa, d_ws,
+                      lossless.data());
+    if (rc != PSA_OK) return rc;
+    HIP_RET(hipEventRecord(cx.ev1, st));
+    HIP_RET(Launch<T>::s2a(st, d_aend_soa, d_aend_aos, (long long)N, nc));
+    HIP_RET(hipMemcpyAsync(a_end, d_aend_aos, N * nc * sizeof(T), hipMemcpyDeviceToHost, st));
+    HIP_RET(hipMemcpyAsync(p_end, d_pend, N * sizeof(T), hipMemcpyDeviceToHost, st));
+    HIP_RET(hipMemcpyAsync(p_max, d_pmax, N * sizeof(T), hipMemcpyDeviceToHost, st));
+    HIP_RET(hipMemcpyAsync(first_bad, d_bad, N * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (waves) {
+        HIP_RET(Launch<T>::s2a(st, d_wend_soa, d_wend, (long long)N, n_waves));
+        HIP_RET(Launch<T>::s2a(st, d_wmax_soa, d_wmax, (long long)N, n_waves));
+        HIP_RET(hipMemcpyAsync(wave_end, d_wend, N * n_waves * sizeof(T), hipMemcpyDeviceToHost, st));
+        HIP_RET(hipMemcpyAsync(wave_max, d_wmax, N * n_waves * sizeof(T), hipMemcpyDeviceToHost, st));
+    }
+    if (traj) {
+        HIP_RET(Launch<T>::t2a(st, d_traj, d_traj_aos, (long long)N, (long long)ld, (long long)rows_total, nc));
+        HIP_RET(hipMemcpyAsync(traj, d_traj_aos, traj_host_elems * sizeof(T), hipMemcpyDeviceToHost, st));
+    }
+    HIP_RET(hipStreamSynchronize(st));
+    if (elapsed_ms) {
+        float ms = 0.f;
+        HIP_RET(hipEventElapsedTime(&ms, cx.ev0, cx.ev1));
+        *elapsed_ms = (double)ms;
+    }
+    return PSA_OK;
+}
+
 template <typename T> struct GainLaunch;
 template <> struct GainLaunch<double> { static constexpr auto fn = psa::launch_gain_summary_f64; };
 template <> struct GainLaunch<float> { static constexpr auto fn = psa::launch_gain_summary_f32; };
@@ -951,6 +1225,48 @@ int psa_dbeta_pairs_f64(int device, const int32_t *orders, int n_orders, const d
     HIP_TRY(hipMemcpy(dbeta2, o2.p, (size_t)n_points * 8, hipMemcpyDeviceToHost));
 done:
     return rc;
+}
+
+int psa_rk4_chain_f64(int device, int n_waves, int64_t n_points, int n_segments, const int64_t *n_steps,
+                      const double *seg_len, int32_t save_every, const double *dbeta, const double *dbeta2, const double *gamma,
+                      const double *alpha, const double *a0, const double *transfer, uint32_t flags, double *a_end, double *p_end,
+                      double *p_max, int64_t *first_bad, double *traj, double *elapsed_ms, double *p_wave_end, double *p_wave_max) {
+    return chain_host<double>(device, n_waves, n_points, n_segments, n_steps, seg_len, save_every, dbeta, dbeta2, gamma,
+                           alpha, a0, transfer, flags, a_end, p_end, p_max, first_bad, traj, elapsed_ms, p_wave_end,
+                           p_wave_max);
+}
+
+int psa_rk4_chain_f64_dev(void *stream, int n_waves, int64_t n_points, int n_segments, const int64_t *n_steps,
+                          const double *seg_len, int32_t save_every, const double *d_dbeta, const double *d_dbeta2,
+                          const double *d_gamma, const double *d_alpha, const double *d_a0_soa, const double *d_transfer_soa,
+                          uint32_t flags, double *d_a_end_soa, double *d_p_end, double *d_p_max, int64_t *d_first_bad,
+                          double *d_traj_soa, double *d_p_wave_end_soa, double *d_p_wave_max_soa, void *d_workspace) {
+    return chain_dev<double>(stream, n_waves, n_points, n_segments, n_steps, seg_len, save_every, d_dbeta, d_dbeta2, d_gamma,
+                          d_alpha, d_a0_soa, d_transfer_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa,
+                          d_p_wave_end_soa, d_p_wave_max_soa, d_workspace);
+}
+
+int psa_rk4_chain_f32(int device, int n_waves, int64_t n_points, int n_segments, const int64_t *n_steps,
+                      const double *seg_len, int32_t save_every, const float *dbeta, const float *dbeta2, const float *gamma,
+                      const float *alpha, const float *a0, const float *transfer, uint32_t flags, float *a_end, float *p_end,
+                      float *p_max, int64_t *first_bad, float *traj, double *elapsed_ms, float *p_wave_end, float *p_wave_max) {
+    return chain_host<float>(device, n_waves, n_points, n_segments, n_steps, seg_len, save_every, dbeta, dbeta2, gamma,
+                           alpha, a0, transfer, flags, a_end, p_end, p_max, first_bad, traj, elapsed_ms, p_wave_end,
+                           p_wave_max);
+}
+
+int psa_rk4_chain_f32_dev(void *stream, int n_waves, int64_t n_points, int n_segments, const int64_t *n_steps,
+                          const double *seg_len, int32_t save_every, const float *d_dbeta, const float *d_dbeta2,
+                          const float *d_gamma, const float *d_alpha, const float *d_a0_soa, const float *d_transfer_soa,
+                          uint32_t flags, float *d_a_end_soa, float *d_p_end, float *d_p_max, int64_t *d_first_bad,
+                          float *d_traj_soa, float *d_p_wave_end_soa, float *d_p_wave_max_soa, void *d_workspace) {
+    return chain_dev<float>(stream, n_waves, n_points, n_segments, n_steps, seg_len, save_every, d_dbeta, d_dbeta2, d_gamma,
+                          d_alpha, d_a0_soa, d_transfer_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa,
+                          d_p_wave_end_soa, d_p_wave_max_soa, d_workspace);
+}
+
+int64_t psa_rk4_chain_workspace_bytes(int n_waves, int64_t n_points, int32_t elem_size, int wave_summary) {
+    return chain_workspace_bytes(n_waves, n_points, (size_t)(elem_size > 0 ? elem_size : 0), wave_summary != 0);
 }
 
 }  // extern "C"

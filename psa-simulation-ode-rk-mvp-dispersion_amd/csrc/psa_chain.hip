@@ -1,0 +1,127 @@
+// psa_chain.hip -- the span epilogue of a fibre chain (psa_rk4_chain_*): concatenated spans, each one launch of the
+// unchanged RK4 sweep kernels, joined on the device without a host synchronisation.
+//
+// Gauge.  The sweep kernels integrate a span on its LOCAL coordinate zeta in [0, L_s] with the FWM factor e^{+-i dbeta_s
+// zeta}; the physical factor is e^{+-i Theta(z)}, Theta(z) = Theta_s + dbeta_s zeta, Theta_s = sum_{k<s} dbeta_k L_k.  The
+// kernels therefore integrate B with B_sig = A_sig e^{+i Theta_s} and every other wave equal to A (a3 a4 = b3 b4 e^{-i
+// Theta_s}; the Kerr terms are phase-blind).  Six waves: the signal of pair k (waves 2 and 4) takes its own Theta^(k).
+// At the boundary s -> s+1 the next span starts from B'_j = T_s[j] B_j, times e^{+i dbeta_s L_s} for the signal(s);
+// reported amplitudes are brought back to A with e^{-i Theta_s}.  Theta is kept per point in float64 in HBM for both
+// precisions (the kernels form dbeta*z in float64 as well).
+//
+// One epilogue launch per span, one thread per point, every access a coalesced SoA row:
+//   fold      spans >= 1 wrote their summary into scratch: p_max / p_wave_max NaN-propagating max into the running
+//             buffers, p_end / p_wave_end replaced, first_bad_step first failure wins (+ the span's step offset);
+//   traj      the span's saved rows: signal column(s) rotated by e^{-i Theta_s} (spans >= 1);
+//   last      a_end (A frame) = the span's a_end rotated by e^{-i Theta_s};
+//   boundary  otherwise: the next span's a0 = T_s B (+ the gauge phase), and Theta += dbeta_s L_s.
+#include <hip/hip_runtime.h>
+
+#include "psa_internal.h"
+
+namespace psa {
+
+namespace {
+
+// z -> z e^{-i theta} (sign = -1) or z e^{+i theta} (sign = +1), in float64, rounded to T
+template <typename T>
+__device__ __forceinline__ void rotate(T &re, T &im, double c, double s) {
+    const double r = (double)re, i = (double)im;
+    re = (T)(r * c - i * s);
+    im = (T)(r * s + i * c);
+}
+
+template <typename T>
+__device__ __forceinline__ void nanmax_into(T &m, T v) {
+    m = (v > m || v != v) ? v : m;   // np.max: a NaN on either side is sticky
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) chain_epilogue_kernel(ChainEpilogue<T> e) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= e.n) return;
+    const long long n = e.n;
+    const int nw = e.n_waves;
+
+    if (e.fold) {
+        nanmax_into(e.p_max[i], e.p_max_s[i]);
+        e.p_end[i] = e.p_end_s[i];
+        const long long b = e.first_bad_s[i];
+        if (e.first_bad[i] < 0 && b >= 0) e.first_bad[i] = b + e.step_offset;
+        if (e.wave_end) {
+            for (int w = 0; w < nw; ++w) {
+                nanmax_into(e.wave_max[(long long)w * n + i], e.wave_max_s[(long long)w * n + i]);
+                e.wave_end[(long long)w * n + i] = e.wave_end_s[(long long)w * n + i];
+            }
+        }
+    }
+
+    // Theta_s of this span's signal(s): 0 for the first span (the `theta` buffers are not read there)
+    const double th1 = e.first ? 0.0 : e.theta[i];
+    const double th2 = (nw == 6) ? (e.first ? 0.0 : e.theta2[i]) : 0.0;
+    double c1 = 1.0, s1 = 0.0, c2 = 1.0, s2 = 0.0;
+    if (!e.first) {
+        sincos(-th1, &s1, &c1);
+        if (nw == 6) sincos(-th2, &s2, &c2);
+    }
+
+    if (e.traj && !e.first) {
+        // rows [0, rows) of this span, (re, im) pairs at ((row * nw + w) * ld + i) * 2
+        for (long long r = 0; r < e.rows; ++r) {
+            T *p = e.traj + ((r * nw + 2) * e.traj_ld + i) * 2;
+            rotate(p[0], p[1], c1, s1);
+            if (nw == 6) {
+                T *q = e.traj + ((r * nw + 4) * e.traj_ld + i) * 2;
+                rotate(q[0], q[1], c2, s2);
+            }
+        }
+    }
+
+    if (e.a_end_out) {   // last span: the state in the A frame
+        for (int c = 0; c < 2 * nw; ++c) e.a_end_out[(long long)c * n + i] = e.a_end_s[(long long)c * n + i];
+        if (!e.first) {
+            rotate(e.a_end_out[4 * n + i], e.a_end_out[5 * n + i], c1, s1);
+            if (nw == 6) rotate(e.a_end_out[8 * n + i], e.a_end_out[9 * n + i], c2, s2);
+        }
+        return;
+    }
+
+    // boundary s -> s+1: B' = T_s B, signal(s) times e^{+i dbeta_s L_s}; Theta += dbeta_s L_s
+    const double ph1 = (double)e.dbeta[i] * e.seg_len;
+    const double ph2 = (nw == 6) ? (double)e.dbeta2[i] * e.seg_len : 0.0;
+    e.theta[i] = th1 + ph1;
+    if (nw == 6) e.theta2[i] = th2 + ph2;
+    for (int w = 0; w < nw; ++w) {
+        T re = e.a_end_s[(long long)(2 * w) * n + i], im = e.a_end_s[(long long)(2 * w + 1) * n + i];
+        if (w == 2 || (nw == 6 && w == 4)) {
+            double sp, cp;
+            sincos(w == 2 ? ph1 : ph2, &sp, &cp);
+            rotate(re, im, cp, sp);
+        }
+        if (e.transfer) {
+            const long long k = e.transfer_stride ? i : 0;
+            const long long ld = e.transfer_stride ? n : 1;
+            const double tr = (double)e.transfer[(long long)(2 * w) * ld + k];
+            const double ti = (double)e.transfer[(long long)(2 * w + 1) * ld + k];
+            const double r = (double)re, m = (double)im;
+            re = (T)(tr * r - ti * m);
+            im = (T)(tr * m + ti * r);
+        }
+        e.a0_next[(long long)(2 * w) * n + i] = re;
+        e.a0_next[(long long)(2 * w + 1) * n + i] = im;
+    }
+}
+
+template <typename T>
+hipError_t launch_epilogue(hipStream_t s, const ChainEpilogue<T> &e) {
+    if (e.n == 0) return hipSuccess;
+    hipLaunchKernelGGL((chain_epilogue_kernel<T>), dim3((unsigned)((e.n + 255) / 256)), dim3(256), 0, s, e);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_chain_epilogue_f64(hipStream_t s, const ChainEpilogue<double> &e) { return launch_epilogue(s, e); }
+hipError_t launch_chain_epilogue_f32(hipStream_t s, const ChainEpilogue<float> &e) { return launch_epilogue(s, e); }
+
+}  // namespace psa

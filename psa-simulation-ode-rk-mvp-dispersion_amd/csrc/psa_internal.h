@@ -65,6 +65,35 @@ hipError_t launch_gain_summary_f32(hipStream_t s, long long n, const float *p_me
                                    double *best_gain, long long *n_finite, void *workspace);
 long long gain_summary_workspace_bytes(long long n);
 
+// ---- fibre chains (psa_chain.hip): the epilogue launched after every span ------------------------------------
+// All arrays are SoA device buffers over the n points; see psa_chain.hip for what each part does.
+template <typename T>
+struct ChainEpilogue {
+    long long n;
+    int n_waves;
+    int first;                  // span 0: Theta_0 = 0, no rotation, `theta` is initialised by the boundary
+    int fold;                   // spans >= 1: fold the span's summary (the *_s buffers) into the running outputs
+    const T *a_end_s;           // [2*NW][n] the span's a_end (B frame)
+    const T *p_end_s, *p_max_s; // [n]
+    const long long *first_bad_s;
+    const T *wave_end_s, *wave_max_s;   // [NW][n] or nullptr
+    T *p_end, *p_max;           // running outputs
+    long long *first_bad;
+    T *wave_end, *wave_max;     // [NW][n] or nullptr
+    long long step_offset;      // steps of the spans before this one
+    double *theta, *theta2;     // [n] float64 accumulated mismatch phase (theta2: 6 waves)
+    T *traj;                    // first row of this span in [rows][NW][traj_ld][2], or nullptr
+    long long traj_ld, rows;
+    T *a_end_out;               // last span: [2*NW][n] A-frame a_end; nullptr otherwise
+    const T *transfer;          // boundary: [2*NW][n] (stride 1) or [2*NW] (stride 0); nullptr = identity
+    int transfer_stride;
+    const T *dbeta, *dbeta2;    // this span's [n]
+    double seg_len;
+    T *a0_next;                 // [2*NW][n]
+};
+hipError_t launch_chain_epilogue_f64(hipStream_t s, const ChainEpilogue<double> &e);
+hipError_t launch_chain_epilogue_f32(hipStream_t s, const ChainEpilogue<float> &e);
+
 // ---- device-side dbeta producer (psa_dbeta.hip) ------------------------------------------------------------
 constexpr int DBETA_MAX_ORDER = 8;
 struct DbetaModel {

@@ -8,6 +8,8 @@
   argmax-over-sweep summary -- what the reference's dead ``scan_mismatch_seeded_signal`` (:43-259) set out to do.
   ``with_idler=True`` adds the idler gain Gi (per-wave summary, psa_rk4_sweep_waves_*).
 * ``seeded_mismatch_scan(gain_mode)``: the scenario that dead function hard-codes (:56-93), run: delta, Gs, Gi, best point.
+* ``scan_copier_psa_phase(...)``: signal gain of a copier - mid-stage - PSA chain against the mid-stage phase (optionally
+  times the PSA span's dbeta) in one chain launch, with its maximum, minimum and extinction (no reference counterpart).
 * ``scan_gain_grid(...)``: the same sweep over a 2-D (pump-2 wavelength x signal wavelength) grid in one launch
   (BASELINE config 3's shape: 1024 x 1024 points); the reference has no grid builder.
 * ``scan_six_wave_grid(...)``: BASELINE config 5's shape -- a grid over the detunings (Omega1, Omega2) of two
@@ -681,3 +683,78 @@ def scan_six_wave_grid(*, cfg: SimulationConfig, lambda_p1_m: float, lambda_p2_m
     shape = (O1.size, O2.size)
     return dict(gain=gain.reshape(shape), dbeta1=db1 * pre["scale"], dbeta2=db2 * pre["scale"],
                 a_end=res.a_end.reshape(shape + (6,)), first_bad_step=res.first_bad_step.reshape(shape), result=res)
+
+
+def scan_copier_psa_phase(*, psa_cfg: SimulationConfig, psa_delta_beta, gamma: float, alpha: float, p_in: Sequence[float],
+                          phase_in: Optional[Sequence[float]] = None, copier_cfg: Optional[SimulationConfig] = None,
+                          copier_delta_beta: float = 0.0, copier_gamma: Optional[float] = None,
+                          copier_alpha: Optional[float] = None, mid_gain_db: Sequence[float] = (0.0, 0.0, 0.0, 0.0),
+                          mid_phase: Sequence[float] = (0.0, 0.0, 0.0, 0.0), phase: Optional[Sequence[float]] = None,
+                          phase_wave="pumps", length_unit: str = "m", gain_mode: GainMode = "max",
+                          gain_unit: str = "dB", dtype=np.float64, device: Optional[int] = None,
+                          devices: Optional[Sequence[int]] = None) -> dict:
+    """Signal gain of a copier - mid-stage - PSA chain against the mid-stage phase (no reference counterpart).
+
+    An optional copier span (``copier_cfg``: length, dz; its own dbeta, gamma, alpha -- gamma / alpha default to the PSA
+    span's) makes the phase-conjugated idler; the mid-stage applies ``mid_gain_db`` / ``mid_phase`` per wave plus the
+    scanned ``phase`` (K values, default 32 over [0, 2 pi)) on ``phase_wave`` -- "pumps" (both pumps) or a wave index
+    0..3; the PSA span (``psa_cfg``) then amplifies phase-sensitively.  ``psa_delta_beta`` a scalar or M values: the scan
+    runs K x M chains in ONE launch per span with per-point transfers.  Without a copier the mid-stage acts on the input.
+    dbeta in 1/length_unit, gamma / alpha per length_unit; save_every and check_nan come from psa_cfg (the copier's must
+    agree, and every span's step count must be a multiple of save_every).
+
+    gain: (K,) or (K, M), the signal's gain_mode metric over every saved row of the chain over p_in[2], with the drivers'
+    NaN rules (a point that went non-finite is NaN, scan_mismtach.py:391-392).  Returns dict(phase, psa_delta_beta, gain,
+    gain_max_db, gain_min_db, extinction_db (max - min over the finite gains, dB), result=ChainResult)."""
+    from .simulation import mid_stage
+    from .sweep import FibreSpan, rk4_chain
+    if gain_mode not in ("end", "max"):
+        raise ValueError(f"Unknown gain_mode={gain_mode!r}. Use 'end' or 'max'.")
+    unit = _norm_choice(gain_unit, "gain_unit", ("db", "linear"))
+    ph = np.linspace(0.0, 2.0 * np.pi, 32, endpoint=False) if phase is None else np.asarray(phase, dtype=float)
+    if ph.ndim != 1 or ph.size == 0 or not np.all(np.isfinite(ph)):
+        raise ValueError("phase must be a non-empty 1D sequence of finite values")
+    dbp = np.asarray(psa_delta_beta, dtype=float)
+    if dbp.ndim > 1 or dbp.size == 0 or not np.all(np.isfinite(dbp)):
+        raise ValueError("psa_delta_beta must be a finite scalar or a non-empty 1D sequence")
+    if phase_wave == "pumps":
+        mask = np.array([1.0, 1.0, 0.0, 0.0])
+    elif isinstance(phase_wave, (int, np.integer)) and 0 <= int(phase_wave) < 4:
+        mask = np.eye(4)[int(phase_wave)]
+    else:
+        raise ValueError("phase_wave must be 'pumps' or a wave index 0..3")
+    _, p0, ph0 = _check_sweep_inputs([1.0], p_in, phase_in)
+    provided = PhaseMatchingConfig(method=PhaseMatchingMethod.PROVIDED, provided_delta_beta=0.0)
+    cfgs = [psa_cfg] if copier_cfg is None else [copier_cfg, psa_cfg]
+    pres = [_prepare(c, gamma=0.0, alpha=0.0, dispersion=None, phase_matching_cfg=provided, beta_legacy=None,
+                     length_unit=length_unit) for c in cfgs]
+    if any(int(c.save_every) != int(psa_cfg.save_every) or bool(c.check_nan) != bool(psa_cfg.check_nan) for c in cfgs):
+        raise ValueError("copier_cfg and psa_cfg must share save_every and check_nan")
+    scale = pres[0]["scale"]
+    K, M = ph.size, max(dbp.size, 1)
+    db_pts = np.tile(np.atleast_1d(dbp), K) / scale                              # point k * M + m
+    T = mid_stage(np.broadcast_to(np.asarray(mid_gain_db, dtype=float), (4,)),
+                  np.asarray(mid_phase, dtype=float)[None, :] + ph[:, None] * mask[None, :])   # (K, 4)
+    T = np.repeat(T, M, axis=0)                                                  # (K * M, 4)
+    a_in = make_initial_amplitudes(p0, ph0)
+    psa = FibreSpan(pres[-1]["fiber"].length_m, dz=pres[-1]["grid"].dz_m, dbeta=db_pts, gamma=float(gamma) / scale,
+                    alpha=float(alpha) / scale)
+    if copier_cfg is None:
+        spans, transfers, a0 = [psa], None, T * a_in[None, :]
+    else:
+        cg = gamma if copier_gamma is None else copier_gamma
+        ca = alpha if copier_alpha is None else copier_alpha
+        copier = FibreSpan(pres[0]["fiber"].length_m, dz=pres[0]["grid"].dz_m, dbeta=float(copier_delta_beta) / scale,
+                           gamma=float(cg) / scale, alpha=float(ca) / scale)
+        spans, transfers, a0 = [copier, psa], [T], a_in
+    dev = 0 if device is None else int(device)
+    res = rk4_chain(spans, a0=a0, transfers=transfers, save_every=int(psa_cfg.save_every),
+                    check_nan=bool(psa_cfg.check_nan), dtype=dtype, device=dev, devices=devices)
+    gain_db = res.gain(p0[2], mode=gain_mode, unit="dB", device=(dev if not devices else int(devices[0])))
+    gain = gain_db if unit == "db" else 10.0 ** (gain_db / 10.0)
+    finite = np.isfinite(gain_db)
+    gmax = float(np.max(gain_db[finite])) if finite.any() else float("nan")
+    gmin = float(np.min(gain_db[finite])) if finite.any() else float("nan")
+    shape = (K, M) if dbp.ndim == 1 else (K,)
+    return dict(phase=ph, psa_delta_beta=dbp, gain=np.asarray(gain).reshape(shape), gain_max_db=gmax, gain_min_db=gmin,
+                extinction_db=gmax - gmin, result=res)

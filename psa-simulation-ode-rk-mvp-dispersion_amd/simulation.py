@@ -18,7 +18,7 @@ from .dispersion import DispersionParams
 from .integrators import integrate_interval
 from .parameters import FiberParams, PhaseMatchingParams, SimulationGrid, WavesParams, make_model_params
 from .phase_matching import PhaseMatchingConfig, PhaseMatchingMethod, PhaseMatchingResult, compute_phase_mismatch  # noqa: F401
-from .sweep import initial_amplitudes
+from .sweep import FibreSpan, initial_amplitudes, rk4_chain
 from .yaman_model import rhs_yaman_simplified
 
 _UNITS = {"m": 1.0, "km": 1000.0}
@@ -123,6 +123,70 @@ def run_single_simulation(cfg: SimulationConfig, *, gamma: float, alpha: float, 
                                 save_every=cfg.save_every, check_nan=cfg.check_nan)
     out_unit = length_unit if return_length_unit is None else return_length_unit
     return z_m / _length_scale_to_m(out_unit), A
+
+
+# ---- concatenated spans (copier - mid-stage - PSA chains) ------------------------------------------------------------
+def mid_stage(gain_db=(0.0, 0.0, 0.0, 0.0), phase=(0.0, 0.0, 0.0, 0.0)) -> np.ndarray:
+    """Per-wave transfer of a mid-stage (pump recovery, attenuator, phase shifter): sqrt(10^(gain_db/10)) e^{i phase}.
+    The last axis is the wave (4 or 6); leading axes (one row per sweep point) broadcast."""
+    g, ph = np.broadcast_arrays(np.asarray(gain_db, dtype=float), np.asarray(phase, dtype=float))
+    if g.ndim == 0 or g.shape[-1] not in (4, 6):
+        raise ValueError("mid_stage: gain_db / phase need one entry per wave (4 or 6)")
+    if not (np.all(np.isfinite(g)) and np.all(np.isfinite(ph))):
+        raise ValueError("mid_stage: gain_db and phase must be finite")
+    return np.sqrt(10.0 ** (g / 10.0)) * np.exp(1j * ph)
+
+
+def run_concatenated_simulation(spans, *, omega: Sequence[float], p_in: Sequence[float],
+                                phase_in: Optional[Sequence[float]] = None, transfers=None, length_unit: str = "m",
+                                return_length_unit: Optional[str] = None) -> tuple[np.ndarray, np.ndarray]:
+    """run_single_simulation over a chain of spans -> (z_out, A complex128 (n_saved_total, 4)).
+
+    ``spans``: one mapping per span with ``cfg`` (SimulationConfig: length z_max, dz, save_every, check_nan), ``gamma``,
+    ``alpha`` and one of ``dispersion`` / ``phase_matching_cfg`` / ``beta_legacy``, all in ``length_unit``.  Each span's
+    dbeta comes from compute_phase_mismatch exactly as in run_single_simulation.  ``transfers``: None or S-1 complex
+    (4,) per-wave factors (mid_stage).  The FWM phase accumulates over the spans; rows are those of every span in order,
+    each span's z = 0 row being the post-transfer state (z repeats at a boundary).  save_every and check_nan must agree
+    between spans; with check_nan a non-finite state raises FloatingPointError at the chain's step index."""
+    spans = list(spans)
+    if not spans:
+        raise ValueError("spans must name at least one span")
+    _length_scale_to_m(length_unit)
+    om = _to_omega_array(omega)
+    A0 = make_initial_amplitudes(_to_power_array(p_in), phase_in)
+    fibre, cfgs = [], []
+    for k, sp in enumerate(spans):
+        sp = dict(sp)
+        unknown = set(sp) - {"cfg", "gamma", "alpha", "dispersion", "phase_matching_cfg", "beta_legacy"}
+        if unknown or "cfg" not in sp or "gamma" not in sp or "alpha" not in sp:
+            raise ValueError(f"span {k}: needs cfg, gamma, alpha (+ dispersion / phase_matching_cfg / beta_legacy); "
+                             f"unknown keys {sorted(unknown)}")
+        cfg = sp["cfg"]
+        pre = _prepare(cfg, gamma=sp["gamma"], alpha=sp["alpha"], dispersion=sp.get("dispersion"),
+                       phase_matching_cfg=sp.get("phase_matching_cfg"), beta_legacy=sp.get("beta_legacy"),
+                       length_unit=length_unit)
+        params = make_model_params(waves=WavesParams(omega=om, symmetric=None), fiber=pre["fiber"], grid=pre["grid"],
+                                   phase_matching=pre["pm"])
+        res = compute_phase_mismatch(params.waves.omega, params.fiber.dispersion, params.phase_matching.config,
+                                     symmetric_hint=params.waves.symmetric)
+        fibre.append(FibreSpan(length=params.fiber.length_m, dz=params.grid.dz_m, dbeta=float(res.delta_beta),
+                               gamma=params.fiber.gamma_W_m, alpha=params.fiber.alpha_1_m))
+        cfgs.append(cfg)
+    save_every, check_nan = int(cfgs[0].save_every), bool(cfgs[0].check_nan)
+    if any(int(c.save_every) != save_every or bool(c.check_nan) != check_nan for c in cfgs):
+        raise ValueError("all spans must share save_every and check_nan")
+    if transfers is not None:
+        transfers = [np.asarray(t, dtype=np.complex128) for t in transfers]
+        if len(transfers) != len(spans) - 1 or any(t.shape != (4,) for t in transfers):
+            raise ValueError(f"transfers must be {len(spans) - 1} per-wave factors of shape (4,)")
+    r = rk4_chain(fibre, a0=A0, transfers=transfers, save_every=save_every, check_nan=check_nan, exact_step=True,
+                  want_traj=True)
+    bad = int(r.first_bad_step[0])
+    if check_nan and bad >= 0:
+        k = int(np.searchsorted(r.step_offsets, bad, side="right")) - 1
+        raise FloatingPointError(f"NaN or Inf detected at step {bad} (span {k}, local step {bad - r.step_offsets[k]})")
+    out_unit = length_unit if return_length_unit is None else return_length_unit
+    return r.z_out / _length_scale_to_m(out_unit), r.traj[0]
 
 
 # ---- the reference's two ready-made scenarios (simulation.py:371-447), km-unit path -----------------------

@@ -16,7 +16,7 @@ import numpy as np
 from . import _native
 from .config import n_steps_of
 
-__all__ = ["SweepResult", "initial_amplitudes", "rk4_sweep"]
+__all__ = ["ChainResult", "FibreSpan", "SweepResult", "initial_amplitudes", "rk4_chain", "rk4_sweep"]
 
 
 def initial_amplitudes(p_in, phase_in=None) -> np.ndarray:
@@ -143,3 +143,167 @@ def rk4_sweep(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps: Optio
         r = _native.sweep_host(dbeta, device=(devs[0] if devs else device), **kw)
     return SweepResult(r["a_end"], r["p_end"], r["p_max"], r["first_bad_step"], int(n_steps), int(save_every),
                        r["elapsed_ms"], r["traj"], r.get("p_wave_end"), r.get("p_wave_max"))
+
+
+# ---- chains of fibre spans ------------------------------------------------------------------------------------------
+@dataclass
+class FibreSpan:
+    """One span of a chain: ``length`` with ``dz`` (n = int(round(length/dz)), as n_steps_of) or ``n_steps``; dbeta,
+    gamma, alpha (and dbeta2 for 6 waves) a scalar or one value per sweep point, per length unit of ``length``."""
+    length: float
+    dbeta: object = 0.0
+    gamma: object = 0.0
+    alpha: object = 0.0
+    dz: Optional[float] = None
+    n_steps: Optional[int] = None
+    dbeta2: object = None
+
+    def __post_init__(self):
+        if not (np.isfinite(self.length) and self.length > 0.0):
+            raise ValueError("FibreSpan.length must be positive and finite")
+        if (self.dz is None) == (self.n_steps is None):
+            raise ValueError("FibreSpan needs exactly one of dz and n_steps")
+        if self.n_steps is None:
+            if not self.dz > 0.0:
+                raise ValueError("FibreSpan.dz must be positive")
+            self.n_steps = n_steps_of(self.length, self.dz)
+        if int(self.n_steps) < 1:
+            raise ValueError("FibreSpan: length / dz rounds to zero steps")
+        self.n_steps = int(self.n_steps)
+
+
+@dataclass
+class ChainResult(SweepResult):
+    """SweepResult of a chain: rows of every span in order (each span's z = 0 row is the post-transfer state), amplitudes
+    in the physical frame, first_bad_step counted over the whole chain.  n_steps is the chain's total."""
+    z_out: Optional[np.ndarray] = None         # (n_saved_total,) absolute z of every saved row (repeats at a boundary)
+    row_offsets: Optional[np.ndarray] = None   # (S + 1,) span s owns rows [row_offsets[s], row_offsets[s + 1])
+    step_offsets: Optional[np.ndarray] = None  # (S + 1,) span s owns steps [step_offsets[s], step_offsets[s + 1])
+
+
+def _span_column(values, S: int, N: int, name: str, dtype) -> np.ndarray:
+    """Per-span scalars -> (S,); as soon as one span gives N values -> (S, N)."""
+    arrs = [np.atleast_1d(np.asarray(v, dtype=dtype)) for v in values]
+    for a in arrs:
+        if a.ndim != 1 or a.shape[0] not in (1, N):
+            raise ValueError(f"{name} of a span must be a scalar or have {N} entries, got shape {a.shape}")
+    if all(a.shape[0] == 1 for a in arrs) and N != 1:
+        return np.array([a[0] for a in arrs], dtype=dtype)
+    return np.stack([np.broadcast_to(a, (N,)) for a in arrs]).astype(dtype)
+
+
+def _chain_over_devices(devices, N: int, kw: dict) -> dict:
+    """The points of a chain split over several GPUs of this process, as _sweep_over_devices does for one span."""
+    from concurrent.futures import ThreadPoolExecutor
+    k = len(devices)
+    base, rem = divmod(N, k)
+    bounds, lo = [], 0
+    for r in range(k):
+        hi = lo + base + (1 if r < rem else 0)
+        bounds.append((lo, hi))
+        lo = hi
+
+    def cut(x, lo, hi, axis):
+        if x is None:
+            return None
+        x = np.asarray(x)
+        if x.ndim > axis and x.shape[axis] == N and N > 1:
+            return np.take(x, np.arange(lo, hi), axis=axis)
+        return x
+
+    def run(r):
+        lo, hi = bounds[r]
+        if hi == lo:
+            return None
+        sub = dict(kw)
+        for name, axis in (("dbeta", 1), ("dbeta2", 1), ("gamma", 1), ("alpha", 1)):
+            sub[name] = cut(kw.get(name), lo, hi, axis)
+        a0 = np.asarray(kw["a0"])
+        sub["a0"] = a0[lo:hi] if a0.ndim == 2 and a0.shape[0] == N and N > 1 else a0
+        tr = kw.get("transfers")
+        sub["transfers"] = None if tr is None else (tr[:, lo:hi] if tr.ndim == 3 else tr)
+        return _native.chain_host(device=int(devices[r]), **sub)
+
+    with ThreadPoolExecutor(max_workers=k) as pool:
+        parts = [p for p in pool.map(run, range(k)) if p is not None]
+    out = {key: np.concatenate([p[key] for p in parts]) for key in ("a_end", "p_end", "p_max", "first_bad_step")}
+    for key in ("traj", "p_wave_end", "p_wave_max"):
+        out[key] = np.concatenate([p[key] for p in parts]) if parts[0].get(key) is not None else None
+    out["elapsed_ms"] = max(p["elapsed_ms"] for p in parts)
+    return out
+
+
+def rk4_chain(spans: Sequence[FibreSpan], *, a0, transfers=None, save_every: int = 10, check_nan: bool = True,
+              exact_step: Optional[bool] = None, dtype=np.float64, want_traj: bool = False, wave_summary: bool = False,
+              device: int = 0, devices: Optional[Sequence[int]] = None) -> ChainResult:
+    """Propagate N points through a chain of fibre spans (psa_rk4_chain_*): each span one launch of the sweep kernel,
+    the mismatch phase accumulated across spans, ``transfers[s]`` applied between span s and s+1.
+
+    transfers: None (identity), or S-1 entries, each (n_waves,) complex for every point or (N, n_waves) per point
+    (see simulation.mid_stage).  Every span's n_steps must be a multiple of ``save_every``."""
+    spans = list(spans)
+    if not spans or not all(isinstance(s, FibreSpan) for s in spans):
+        raise ValueError("spans must be a non-empty sequence of FibreSpan")
+    if int(save_every) <= 0:
+        raise ValueError("save_every must be a positive integer")
+    save_every = int(save_every)
+    for k, s in enumerate(spans):
+        if s.n_steps % save_every:
+            raise ValueError(f"span {k}: n_steps = {s.n_steps} is not a multiple of save_every = {save_every}")
+    dtype = np.dtype(dtype)
+    S = len(spans)
+    a0 = np.asarray(a0)
+    if a0.ndim not in (1, 2) or a0.shape[-1] not in (4, 6):
+        raise ValueError("a0 must have shape (n_waves,) or (N, n_waves) with n_waves in (4, 6)")
+    nw = int(a0.shape[-1])
+    sizes = {int(np.size(v)) for s in spans for v in (s.dbeta, s.gamma, s.alpha, s.dbeta2) if v is not None}
+    if a0.ndim == 2:
+        sizes.add(int(a0.shape[0]))
+    sizes.discard(1)
+    if len(sizes) > 1:
+        raise ValueError(f"per-point arguments disagree on the number of points: {sorted(sizes)}")
+    N = sizes.pop() if sizes else 1
+    dbeta = np.stack([np.broadcast_to(np.asarray(s.dbeta, dtype=dtype).reshape(-1), (N,)) for s in spans])
+    dbeta2 = None
+    if nw == 6:
+        if any(s.dbeta2 is None for s in spans):
+            raise ValueError("6 waves: every span needs dbeta2")
+        dbeta2 = np.stack([np.broadcast_to(np.asarray(s.dbeta2, dtype=dtype).reshape(-1), (N,)) for s in spans])
+    elif any(s.dbeta2 is not None for s in spans):
+        raise ValueError("dbeta2 is only meaningful for 6 waves")
+    gamma = _span_column([s.gamma for s in spans], S, N, "gamma", dtype)
+    alpha = _span_column([s.alpha for s in spans], S, N, "alpha", dtype)
+    tr = None
+    if transfers is not None:
+        tl = list(transfers)
+        if len(tl) != S - 1:
+            raise ValueError(f"{S} spans need {S - 1} transfers, got {len(tl)}")
+        if tl:
+            arrs = [np.asarray(t, dtype=np.complex128) for t in tl]
+            for t in arrs:
+                if t.shape not in ((nw,), (N, nw)):
+                    raise ValueError(f"a transfer must have shape ({nw},) or ({N}, {nw}), got {t.shape}")
+            if all(t.ndim == 1 for t in arrs):
+                tr = np.stack(arrs)
+            else:
+                tr = np.stack([np.broadcast_to(t, (N, nw)) for t in arrs])
+    steps = np.array([s.n_steps for s in spans], dtype=np.int64)
+    lens = np.array([float(s.length) for s in spans])
+    kw = dict(dbeta=dbeta, n_steps=steps, seg_len=lens, save_every=save_every, gamma=gamma, alpha=alpha, a0=a0,
+              transfers=tr, dbeta2=dbeta2, check_nan=check_nan, exact_step=exact_step, want_traj=want_traj,
+              dtype=dtype, wave_summary=wave_summary)
+    devs = None if devices is None else [int(d) for d in devices]
+    if devs is not None and len(devs) == 0:
+        raise ValueError("devices must name at least one GPU")
+    if devs is not None and len(devs) > 1 and N > 1:
+        r = _chain_over_devices(devs, N, kw)
+    else:
+        r = _native.chain_host(device=(devs[0] if devs else device), **kw)
+    rows = steps // save_every + 1
+    row_off = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+    step_off = np.concatenate([[0], np.cumsum(steps)]).astype(np.int64)
+    z0 = np.concatenate([[0.0], np.cumsum(lens)])
+    z_out = np.concatenate([z0[k] + np.linspace(0.0, lens[k], int(steps[k]) + 1)[::save_every] for k in range(S)])
+    return ChainResult(r["a_end"], r["p_end"], r["p_max"], r["first_bad_step"], int(step_off[-1]), save_every,
+                       r["elapsed_ms"], r["traj"], r.get("p_wave_end"), r.get("p_wave_max"), z_out=z_out,
+                       row_offsets=row_off, step_offsets=step_off)

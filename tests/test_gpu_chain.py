@@ -1,0 +1,204 @@
+"""Fibre chains on hardware (psa_rk4_chain_*, sweep.rk4_chain, simulation.run_concatenated_simulation):
+
+* one span is psa_rk4_sweep_* / _waves_* bit for bit, in the one-, two- and four-lane float64 layouts and packed / scalar
+  float32;
+* one fibre cut into 2, 3 and 7 spans with identity transfers is the unsplit run: a_end, p_max, the per-wave columns and
+  the A-frame trajectory rows, for 4 and 6 waves, float64 and float32;
+* a lossy three-span chain with unequal dbeta, gamma, alpha and per-point transfers against the CPU oracle, span by span;
+* first_bad_step of a chain that fails in span 2 is cumulative (span 1's steps + the local exact index), and the NaN
+  stays NaN in the gain;
+* devices=[0, 0] equals one device;
+* physics with no reference in it: an undepleted lossless PSA span reaches (sqrt(G) + sqrt(G-1))^2 at its best input
+  phase, G being the phase-insensitive gain of the same span with the idler dark, and max x min = 1."""
+import numpy as np
+import pytest
+
+import oracle
+import psa_amd._native as nat
+from psa_amd.config import custom_simulation_config
+from psa_amd.phase_matching import PhaseMatchingConfig, PhaseMatchingMethod
+from psa_amd.simulation import mid_stage, run_concatenated_simulation, run_single_simulation
+from psa_amd.sweep import FibreSpan, rk4_chain, rk4_sweep
+
+pytestmark = pytest.mark.gpu
+
+
+def _a0(nw, n=None):
+    p = [0.5, 0.5, 1e-5, 1e-6] if nw == 4 else [0.3, 0.25, 1e-6, 1e-6, 2e-6, 5e-7]
+    a = np.sqrt(np.array(p)).astype(complex) * np.exp(1j * np.linspace(0.1, 0.7, nw))
+    return a if n is None else np.tile(a, (n, 1)) * np.exp(1j * np.linspace(0, 1, n))[:, None]
+
+
+LAYOUTS = [(np.float64, nat.OPT_ONE_LANE), (np.float64, nat.OPT_SPLIT_POINT), (np.float64, nat.OPT_QUAD_POINT),
+           (np.float32, nat.OPT_F32_PACKED), (np.float32, nat.OPT_F32_SCALAR)]
+
+
+@pytest.mark.parametrize("dtype,layout", LAYOUTS)
+@pytest.mark.parametrize("nw", [4, 6])
+def test_one_span_is_the_sweep_bit_for_bit(dtype, layout, nw):
+    if layout == nat.OPT_QUAD_POINT and nw == 6:
+        pytest.skip("four lanes per point: 4 waves only")
+    n = 37
+    db = np.linspace(-0.05, 0.05, n)
+    d2 = np.linspace(0.03, -0.02, n) if nw == 6 else None
+    kw = dict(save_every=10, gamma=np.full(n, 0.0115), alpha=1.15e-4, a0=_a0(nw, n), dtype=dtype, extra_flags=layout)
+    for extra in (dict(want_traj=True), dict(wave_summary=True)):
+        ref = nat.sweep_host(db, n_steps=1000, z_max=100.0, dbeta2=d2, **kw, **extra)
+        got = nat.chain_host(db[None], n_steps=[1000], seg_len=[100.0], dbeta2=None if d2 is None else d2[None],
+                             **dict(kw, gamma=kw["gamma"][None], alpha=[kw["alpha"]]), **extra)
+        for key in ("a_end", "p_end", "p_max", "first_bad_step", "traj", "p_wave_end", "p_wave_max"):
+            if ref[key] is None:
+                assert got[key] is None
+            else:
+                assert np.array_equal(got[key], ref[key], equal_nan=True), (key, extra)
+
+
+def _split(n, cuts, se):
+    steps = np.full(cuts, (n // se // cuts) * se)
+    steps[-1] = n - steps[:-1].sum()
+    return [int(s) for s in steps]
+
+
+def _rows(steps, se):
+    offs = np.concatenate([[0], np.cumsum(steps)[:-1]])
+    return np.concatenate([o // se + np.arange(s // se + 1) for o, s in zip(offs, steps)])
+
+
+@pytest.mark.parametrize("cuts", [2, 3, 7])
+@pytest.mark.parametrize("nw", [4, 6])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_identity_split_equals_the_unsplit_run(cuts, nw, dtype):
+    n_pts, n, L, se = 33, 1400, 700.0, 10
+    db = np.linspace(-0.04, 0.04, n_pts)
+    d2 = np.linspace(0.02, -0.03, n_pts) if nw == 6 else None
+    gam, alp = np.linspace(0.01, 0.013, n_pts), 1.15e-4
+    a0 = _a0(nw, n_pts)
+    whole = rk4_sweep(db, z_max=L, n_steps=n, save_every=se, gamma=gam, alpha=alp, a0=a0, dbeta2=d2, dtype=dtype,
+                      want_traj=True)
+    whole_w = rk4_sweep(db, z_max=L, n_steps=n, save_every=se, gamma=gam, alpha=alp, a0=a0, dbeta2=d2, dtype=dtype,
+                        wave_summary=True)
+    steps = _split(n, cuts, se)
+    spans = [FibreSpan(L * s / n, n_steps=s, dbeta=db, gamma=gam, alpha=alp, dbeta2=d2) for s in steps]
+    got = rk4_chain(spans, a0=a0, transfers=[np.ones(nw)] * (cuts - 1), save_every=se, dtype=dtype, want_traj=True)
+    got_w = rk4_chain(spans, a0=a0, save_every=se, dtype=dtype, wave_summary=True)
+    assert got.traj.shape == (n_pts, sum(s // se + 1 for s in steps), nw)
+    np.testing.assert_allclose(got.z_out, np.linspace(0, L, n + 1)[::se][_rows(steps, se)], rtol=1e-12, atol=1e-9)
+    if dtype == np.float64:
+        def close(a, b):
+            return np.max(np.abs(a - b)) <= 1e-9 * np.max(np.abs(b))
+    else:   # point scale: each point against its own largest value
+        def close(a, b):
+            a, b = np.asarray(a).reshape(n_pts, -1), np.asarray(b).reshape(n_pts, -1)
+            return np.all(np.max(np.abs(a - b), axis=1) <= 1e-4 * np.max(np.abs(b), axis=1))
+    assert close(got.a_end, whole.a_end)
+    assert close(got.p_max, whole.p_max) and close(got.p_end, whole.p_end)
+    assert close(got.traj, whole.traj[:, _rows(steps, se)])
+    assert close(got_w.p_wave_max, whole_w.p_wave_max) and close(got_w.p_wave_end, whole_w.p_wave_end)
+    assert np.all(got.first_bad_step == -1)
+
+
+def test_lossy_chain_with_transfers_against_the_oracle():
+    n_pts, se = 9, 20
+    rng = np.random.default_rng(7)
+    spans_def = [(300.0, 600, 0.0115, 1.2e-4), (200.0, 400, 0.02, 0.0), (250.0, 500, 0.009, 2e-4)]
+    dbs = [np.linspace(-0.02, 0.03, n_pts), np.linspace(0.01, -0.015, n_pts), np.linspace(0.0, 0.04, n_pts)]
+    tr = [mid_stage(rng.uniform(-3, 1, (n_pts, 4)), rng.uniform(-np.pi, np.pi, (n_pts, 4))),
+          mid_stage((0.0, 0.0, -1.0, -20.0), (0.5, 0.0, 0.0, 0.0))]
+    a0 = _a0(4, n_pts)
+    spans = [FibreSpan(L, n_steps=n, dbeta=d, gamma=g, alpha=al) for (L, n, g, al), d in zip(spans_def, dbs)]
+    got = rk4_chain(spans, a0=a0, transfers=tr, save_every=se, want_traj=True)
+    for i in range(n_pts):
+        theta, b, rows = 0.0, a0[i].copy(), []
+        for k, (L, n, g, al) in enumerate(spans_def):
+            _, B, _ = oracle.integrate(b, z_max=L, n=n, save_every=se, gamma=g, alpha=al, dbeta=dbs[k][i])
+            A = B.copy()
+            A[:, 2] *= np.exp(-1j * theta)
+            rows.append(A)
+            if k < 2:
+                t = tr[k][i] if tr[k].ndim == 2 else tr[k]
+                b = B[-1] * t
+                b[2] *= np.exp(1j * dbs[k][i] * L)
+                theta += dbs[k][i] * L
+        want = np.concatenate(rows)
+        scale = np.max(np.abs(want), axis=0)
+        assert np.max(np.abs(got.traj[i] - want) / scale) < 1e-9, i
+        assert np.max(np.abs(got.a_end[i] - want[-1]) / scale) < 1e-9
+        assert abs(got.p_max[i] - np.max(np.abs(want[:, 2]) ** 2)) <= 1e-9 * got.p_max[i]
+
+
+def test_run_concatenated_simulation_matches_the_single_run_when_split():
+    pm = PhaseMatchingConfig(method=PhaseMatchingMethod.PROVIDED, provided_delta_beta=0.6)
+    om = np.full(4, 2.0 * np.pi * 2.99792458e8 / 1.55e-6)
+    p_in, ph = [0.3, 0.3, 1e-5, 1e-6], [0.0, 0.2, -0.4, 0.1]
+    z1, A1 = run_single_simulation(custom_simulation_config(z_max=0.5, dz=1e-3), gamma=10.0, alpha=0.1, omega=om,
+                                   p_in=p_in, phase_in=ph, phase_matching_cfg=pm, length_unit="km")
+    span = dict(gamma=10.0, alpha=0.1, phase_matching_cfg=pm)
+    z2, A2 = run_concatenated_simulation([dict(span, cfg=custom_simulation_config(z_max=0.2, dz=1e-3)),
+                                          dict(span, cfg=custom_simulation_config(z_max=0.3, dz=1e-3))],
+                                         omega=om, p_in=p_in, phase_in=ph, length_unit="km")
+    idx = _rows([200, 300], 10)
+    np.testing.assert_allclose(z2, z1[idx], rtol=1e-12, atol=1e-12)
+    assert np.max(np.abs(A2 - A1[idx]) / np.max(np.abs(A1), axis=0)) < 1e-9
+
+
+def test_first_bad_step_of_a_failure_in_span_two_is_cumulative():
+    """Span 2 is past the RK4 stability edge at points 1 and 3 (gamma 300; the model has no slow blow-up: a fibre either
+    stays finite or fails within a few steps).  The chain's index is span 1's steps + the index a lone run of span 2,
+    started from span 1's end state (B frame), reports -- exact, first failure wins."""
+    n_pts, n1, n2 = 5, 400, 600
+    db = np.linspace(-0.02, 0.02, n_pts)
+    gam2 = np.full(n_pts, 0.0115)
+    gam2[[1, 3]] = 300.0
+    a0 = _a0(4, n_pts)
+    s1 = FibreSpan(40.0, n_steps=n1, dbeta=db, gamma=0.0115, alpha=1e-4)
+    s2 = FibreSpan(60.0, n_steps=n2, dbeta=db, gamma=gam2)
+    first = rk4_chain([s1], a0=a0, save_every=10)
+    b = first.a_end.copy()
+    b[:, 2] *= np.exp(1j * db * 40.0)
+    lone = rk4_sweep(db, z_max=60.0, n_steps=n2, save_every=10, gamma=gam2, alpha=0.0, a0=b, exact_step=True)
+    assert np.all(lone.first_bad_step[[1, 3]] >= 0) and np.all(lone.first_bad_step[[0, 2, 4]] == -1)
+    got = rk4_chain([s1, s2], a0=a0, transfers=[np.ones(4)], save_every=10, exact_step=True)
+    want = np.where(lone.first_bad_step >= 0, lone.first_bad_step + n1, -1)
+    np.testing.assert_array_equal(got.first_bad_step, want)
+    # a NaN past the boundary stays NaN in the gain; the finite points keep theirs
+    g = got.gain(1e-5, mode="max")
+    assert np.all(np.isnan(g[[1, 3]])) and np.all(np.isfinite(g[[0, 2, 4]]))
+    # ... also when a third span follows, through a non-identity transfer: the first failure still wins
+    got3 = rk4_chain([s1, s2, FibreSpan(10.0, n_steps=100, dbeta=db, gamma=0.0115)], a0=a0,
+                     transfers=[np.ones(4), mid_stage((0.0, 0.0, -3.0, 0.0), (0.0, 0.0, 1.0, 0.0))], save_every=10,
+                     exact_step=True)
+    np.testing.assert_array_equal(got3.first_bad_step, want)
+    assert np.all(np.isnan(got3.p_max[[1, 3]])) and np.all(np.isfinite(got3.p_max[[0, 2, 4]]))
+
+
+def test_two_devices_equal_one():
+    n_pts = 41
+    db = np.linspace(-0.05, 0.05, n_pts)
+    spans = [FibreSpan(300.0, n_steps=600, dbeta=db, gamma=0.0115, alpha=1e-4),
+             FibreSpan(200.0, n_steps=400, dbeta=db[::-1].copy(), gamma=0.02)]
+    tr = [mid_stage(np.zeros((n_pts, 4)), np.linspace(0, 2 * np.pi, n_pts)[:, None] * np.array([1, 1, 0, 0]))]
+    one = rk4_chain(spans, a0=_a0(4, n_pts), transfers=tr, save_every=20, want_traj=True)
+    two = rk4_chain(spans, a0=_a0(4, n_pts), transfers=tr, save_every=20, want_traj=True, devices=[0, 0])
+    for key in ("a_end", "p_end", "p_max", "first_bad_step", "traj"):
+        assert np.array_equal(getattr(one, key), getattr(two, key)), key
+
+
+@pytest.mark.parametrize("dbeta", [-0.014, -0.01, -0.006])
+def test_psa_gain_extremes_of_an_undepleted_span(dbeta):
+    """Two strong equal pumps, weak equal signal and idler, no loss: the linearised signal/idler map is a Bogoliubov
+    transformation, so the maximum gain over the input phase is (sqrt(G) + sqrt(G - 1))^2 with G the phase-insensitive
+    gain (idler dark), and the minimum is its inverse.  The gain band of this span is -0.02 < dbeta < 0 (1/m)."""
+    n_ph, p_s = 4096, 1e-9
+    gamma, L, pp = 0.01, 150.0, 0.5
+    phi = np.linspace(0.0, 2 * np.pi, n_ph, endpoint=False)
+    a0 = np.tile(np.sqrt([pp, pp, p_s, p_s]).astype(complex), (n_ph, 1))
+    a0[:, 2] *= np.exp(1j * phi)
+    span = [FibreSpan(L, n_steps=1500, dbeta=dbeta, gamma=gamma)]
+    r = rk4_chain(span, a0=a0, save_every=1500)
+    g_psa = r.p_end / p_s
+    pia = rk4_chain(span, a0=np.sqrt([pp, pp, p_s, 0.0]).astype(complex), save_every=1500)
+    G = float(pia.p_end[0] / p_s)
+    assert G > 3.0
+    want = (np.sqrt(G) + np.sqrt(G - 1.0)) ** 2
+    assert abs(10 * np.log10(g_psa.max() / want)) < 0.02
+    assert abs(10 * np.log10(g_psa.max() * g_psa.min())) < 0.02
