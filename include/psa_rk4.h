@@ -131,8 +131,7 @@ int         psa_release_cache(void);         /* destroy the idle call contexts o
  *   traj_or_null   [N][n_saved][n_waves][2]  every saved row (integrators.py:137-140), or NULL.  A launch with a
  *                  trajectory takes at most 2^27 - 1 points in float64 (2^28 - 1 in float32: rows are addressed with a
  *                  32-bit lane offset kept below 2^31; with PSA_OPT_SPLIT_POINT 2^32 / (n_waves * 16) - 1) and must fit
- *                  the device's free memory, else PSA_E_TOO_LARGE; the host-buffer
- *                  variant moves it to the host in bounded chunks (two 256 MB staging buffers)
+ *                  the device's free memory, else PSA_E_TOO_LARGE
  *   elapsed_ms_or_null  kernel time from hipEvents on the launch stream, or NULL
  */
 int psa_rk4_sweep_f64(int device, int n_waves, int64_t n_points, int64_t n_steps, double z_max,

@@ -32,10 +32,10 @@ int hip_fail(hipError_t e, const char *what) {
     return (int)e;
 }
 
-#define HIP_TRY(expr)                                   \
-    do {                                                \
-        hipError_t _e = (expr);                         \
-        if (_e != hipSuccess) { rc = hip_fail(_e, #expr); goto done; } \
+#define HIP_RET(expr)                                                \
+    do {                                                             \
+        hipError_t _e = (expr);                                      \
+        if (_e != hipSuccess) return hip_fail(_e, #expr);            \
     } while (0)
 
 // Leading dimension of the trajectory buffer [n_saved][n_waves][ld][2].  The four (six) wave regions of a row, and
@@ -162,10 +162,11 @@ template <> struct Launch<float> {
 
 // The per-wave summary entry points (psa_rk4_sweep_waves_*) are offered for the register layouts without trajectory
 // and with the automatic block sizes only.
-int validate_waves(uint32_t flags, bool has_traj) {
+int validate_waves(uint32_t flags, bool has_traj, int64_t n_points, const void *wave_end, const void *wave_max) {
     if (has_traj) return fail(PSA_E_FLAGS, "the per-wave summary takes no trajectory (traj_or_null must be NULL)");
     if (flags & PSA_OPT_LDS_STAGING) return fail(PSA_E_FLAGS, "the per-wave summary does not exist with PSA_OPT_LDS_STAGING");
     if (flags & PSA_OPT_BLOCK64) return fail(PSA_E_FLAGS, "the per-wave summary does not exist with PSA_OPT_BLOCK64");
+    if (n_points > 0 && (!wave_end || !wave_max)) return fail(PSA_E_NULLPTR, "p_wave_end / p_wave_max is NULL");
     return PSA_OK;
 }
 
@@ -199,9 +200,8 @@ int sweep_waves_dev(void *stream, int n_waves, int64_t n_points, int64_t n_steps
                     const T *d_dbeta, const T *d_dbeta2, const T *d_gamma, const T *d_alpha, const T *d_a0_soa,
                     uint32_t flags, T *d_a_end_soa, T *d_p_end, T *d_p_max, int64_t *d_first_bad, T *d_traj_soa,
                     T *d_wave_end, T *d_wave_max) {
-    int rc = validate_waves(flags, d_traj_soa != nullptr);
+    int rc = validate_waves(flags, d_traj_soa != nullptr, n_points, d_wave_end, d_wave_max);
     if (rc != PSA_OK) return rc;
-    if (n_points > 0 && (!d_wave_end || !d_wave_max)) return fail(PSA_E_NULLPTR, "p_wave_end / p_wave_max is NULL");
     return sweep_dev<T>(stream, n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha,
                         d_a0_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa, d_wave_end, d_wave_max);
 }
@@ -211,7 +211,6 @@ struct DevBuf {
     void *p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
     hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8); }
-    template <typename U> U *as() { return (U *)p; }
 };
 
 // Makes `device` current for the scope of a host-buffer entry point and puts the caller's device back afterwards
@@ -331,13 +330,13 @@ struct CtxLease {
     }
 };
 
-// 256-B aligned slices of one allocation
+// 256-B aligned slices of one allocation; without a base (the sizing pass of a host call) it only measures
 struct Carver {
     char *base = nullptr;
     size_t used = 0;
     static size_t aligned(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
     template <typename U> U *take(size_t count) {
-        U *p = (U *)(base + used);
+        U *p = base ? (U *)(base + used) : nullptr;
         used += aligned(count * sizeof(U));
         return p;
     }
@@ -355,213 +354,205 @@ static bool injected_chunk_failure(size_t chunk_index) {
 }
 #endif
 
-#define HIP_RET(expr)                                                \
-    do {                                                             \
-        hipError_t _e = (expr);                                      \
-        if (_e != hipSuccess) return hip_fail(_e, #expr);            \
-    } while (0)
-
+// ---- the one staging path of every host-buffer entry point ------------------------------------------------------
+// A call declares its buffers in a layout function.  host_call() runs it twice: against unplaced Carvers to measure the
+// scratch, then against the scratch itself, where the same declarations hand out the device pointers and record the
+// copies and transposes.  Scratch: [inputs] [device-only] [outputs] [trajectory, two staging buffers].  The input and the
+// output region are each contiguous, so a small call's inputs and outputs travel in ONE copy each way through the
+// context's page-locked mirror.  A NULL host pointer declares no buffer and yields a NULL device pointer.
 template <typename T>
-int sweep_host(int device, int n_waves, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
-               const T *dbeta, const T *dbeta2, const T *gamma, const T *alpha, const T *a0, uint32_t flags,
-               T *a_end, T *p_end, T *p_max, int64_t *first_bad, T *traj, double *elapsed_ms,
-               T *wave_end = nullptr, T *wave_max = nullptr) {
-    const bool waves = wave_end != nullptr;   // psa_rk4_sweep_waves_*: validated by the caller (validate_waves)
-    int rc = validate_common(n_waves, n_points, n_steps, z_max, save_every, dbeta, dbeta2, gamma, alpha, a0, a_end,
-                             p_end, p_max, first_bad, flags, traj != nullptr, sizeof(T));
-    if (rc != PSA_OK) return rc;
-    if (elapsed_ms) *elapsed_ms = 0.0;
-    if (n_points == 0) return PSA_OK;
-    rc = check_device(device, "the RK4 sweep");
-    if (rc != PSA_OK) return rc;
+struct Staging {
+    struct Copy { void *host; void *dev; size_t bytes; };
+    struct Transpose { const T *from; T *to; size_t rows; int nc, batches; };
+    struct Traj { T *dev = nullptr, *host = nullptr, *stage[2] = {nullptr, nullptr}; size_t n = 0, rows = 0, ld = 0, chunk = 0; int nc = 0; };
+    Carver in, mid, out, big;
+    std::vector<Copy> ups, downs;
+    std::vector<Transpose> to_soa, to_aos;
+    Traj traj;
+    bool has_traj = false, traj_too_large = false;
 
-    const int nc = 2 * n_waves;
-    const size_t N = (size_t)n_points;
-    const int64_t n_saved = n_steps / save_every + 1;
-    // the device-side trajectory buffer has its own leading dimension (traj_ld_of); the caller's array is dense
-    const size_t ld = (size_t)traj_ld_of(n_points, sizeof(T));
-    size_t traj_elems = 0;
-    if (traj) {
-        // ld * n_saved * nc must fit comfortably in int64 / size_t
-        const long double te = (long double)ld * (long double)n_saved * (long double)nc;
-        if (te > 4.0e18L) return fail(PSA_E_TOO_LARGE, "trajectory buffer too large");
-        traj_elems = ld * (size_t)n_saved * (size_t)nc;
-        flags |= PSA_OPT_TRAJ_LD;
+    template <typename U> U *input(const U *host, size_t count) {            // host -> device as it is
+        if (!host) return nullptr;
+        U *d = in.take<U>(count);
+        ups.push_back({(void *)host, (void *)d, count * sizeof(U)});
+        return d;
     }
-    if ((flags & PSA_BCAST_ALPHA) && alpha[0] == T(0)) flags |= PSA_OPT_LOSSLESS;   // the reference's alpha == 0.0 branch
-    const size_t n_gamma = (flags & PSA_BCAST_GAMMA) ? 1 : N;
-    const size_t n_alpha = (flags & PSA_BCAST_ALPHA) ? 1 : N;
-    const size_t n_a0 = (flags & PSA_BCAST_A0) ? 1 : N;
-
-    // trajectory rows leave the device in chunks of points: [rows][nw][N] -> chunk [pts][rows][nw] in a bounded staging
-    // buffer (two of them, so a chunk's device-to-host copy overlaps the next chunk's transpose)
-    const size_t point_bytes = (size_t)n_saved * nc * sizeof(T);          // one point's whole trajectory
-    size_t chunk_pts = 0;
-    if (traj && N > 1) {
-        chunk_pts = (TRAJ_STAGE_BYTES / point_bytes) / 32 * 32;            // whole 32-point transpose tiles
-        if (chunk_pts < 32) chunk_pts = 32;                                // (very long single runs: one tile per chunk)
-        if (chunk_pts > N) chunk_pts = N;
+    template <typename U> U *output(U *host, size_t count) {                  // device -> host as it is
+        if (!host) return nullptr;
+        U *d = out.take<U>(count);
+        downs.push_back({(void *)host, (void *)d, count * sizeof(U)});
+        return d;
     }
-    const size_t traj_bytes = traj_elems * sizeof(T);
-    const size_t stage_bytes = chunk_pts * point_bytes;
+    template <typename U> U *scratch(size_t count) { return mid.take<U>(count); }
+    T *input_soa(const T *host, size_t rows, int nc, int batches = 1) {      // host [batches][rows][nc] -> [batches][nc][rows]
+        if (!host) return nullptr;
+        const T *aos = input(host, (size_t)batches * rows * nc);
+        T *soa = mid.take<T>((size_t)batches * rows * nc);
+        to_soa.push_back({aos, soa, rows, nc, batches});
+        return soa;
+    }
+    T *output_soa(T *host, size_t rows, int nc) {                            // device [nc][rows] -> host [rows][nc]
+        if (!host) return nullptr;
+        T *soa = mid.take<T>(rows * nc);
+        to_aos.push_back({soa, output(host, rows * nc), rows, nc, 1});
+        return soa;
+    }
+    // device [rows][nc/2][ld][2] -> host [n][rows][nc/2][2].  One point's layouts coincide: it leaves with the outputs.
+    // More points leave in chunks of whole 32-point transpose tiles (very long single runs: one tile per chunk).
+    T *trajectory(T *host, size_t n, size_t rows, int nc) {
+        if (!host) return nullptr;
+        has_traj = true;
+        if (n == 1) return output(host, rows * nc);
+        const size_t ld = (size_t)traj_ld_of((int64_t)n, sizeof(T)), point_bytes = rows * nc * sizeof(T);
+        if ((long double)ld * rows * nc * sizeof(T) > 4.0e18L) { traj_too_large = true; return nullptr; }
+        size_t chunk = (TRAJ_STAGE_BYTES / point_bytes) / 32 * 32;
+        if (chunk < 32) chunk = 32;
+        if (chunk > n) chunk = n;
+        traj.dev = big.take<T>(ld * rows * nc);
+        for (int b = 0; b < 2; ++b) traj.stage[b] = (T *)big.take<char>(chunk * point_bytes);
+        traj.host = host;
+        traj.n = n;
+        traj.rows = rows;
+        traj.ld = ld;
+        traj.chunk = chunk;
+        traj.nc = nc;
+        return traj.dev;
+    }
+};
 
-    // -- layout of the call's device scratch: [inputs] [device-only] [outputs (+ the one-point trajectory)] [trajectory] [staging]
-    using C = Carver;
-    const size_t in_bytes = C::aligned(N * sizeof(T)) * (dbeta2 ? 2 : 1) + C::aligned(n_gamma * sizeof(T)) +
-                            C::aligned(n_alpha * sizeof(T)) + C::aligned(n_a0 * nc * sizeof(T));
-    const size_t wave_bytes = waves ? 2 * C::aligned(N * n_waves * sizeof(T)) : 0;   // p_wave_end, p_wave_max
-    const size_t mid_bytes = C::aligned(n_a0 * nc * sizeof(T)) + C::aligned(N * nc * sizeof(T)) + wave_bytes;
-    const bool traj_in_out = traj && N == 1;     // [rows][nw][1] and [1][rows][nw] coincide: it leaves with the outputs
-    const size_t out_bytes = C::aligned(N * nc * sizeof(T)) + 2 * C::aligned(N * sizeof(T)) + C::aligned(N * sizeof(int64_t)) +
-                             (traj_in_out ? C::aligned(traj_bytes) : 0) + wave_bytes;
-    const size_t small_total = in_bytes + mid_bytes + out_bytes;
-    const size_t traj_total = (traj && !traj_in_out) ? C::aligned(traj_bytes) + 2 * C::aligned(stage_bytes) : 0;
+// Checks the device, leases a context, lays out and fills the scratch, runs compute(stream) (elapsed_ms: the compute alone,
+// between the context's two timing events), brings the outputs home and returns once every stream of the call has finished.
+template <typename T, typename Layout, typename Compute>
+int host_call(int device, const char *what, double *elapsed_ms, Layout &&layout, Compute &&compute) {
+    int rc = check_device(device, what);
+    if (rc != PSA_OK) return rc;
+    Staging<T> size;
+    layout(size);
+    if (size.traj_too_large) return fail(PSA_E_TOO_LARGE, "trajectory buffer too large");
+    const size_t in_b = size.in.used, mid_b = size.mid.used, out_b = size.out.used;
+    const size_t total = in_b + mid_b + out_b + size.big.used;
 
     DeviceScope scope;
-    DevBuf b_small, b_traj;                      // per-call allocations when the cached scratch is not used
-    CtxLease lease;
+    DevBuf own;          // scratch above CTX_ARENA_KEEP is allocated per call
+    CtxLease lease;      // declared last: its streams are drained before `own` is freed and the device restored
     HIP_RET(scope.enter(device));
-    if (traj) {   // say "too large" before hipMalloc says "out of memory"
+    if (size.has_traj && total > CTX_ARENA_KEEP) {   // say "too large" before hipMalloc says "out of memory"
         size_t free_b = 0, total_b = 0;
         HIP_RET(hipMemGetInfo(&free_b, &total_b));
-        const long double need = (long double)small_total + (long double)traj_total;
-        if (need > (long double)CTX_ARENA_KEEP && need > (long double)free_b)
+        if (total > free_b)
             return fail(PSA_E_TOO_LARGE, "trajectory of %.3g GB does not fit the %.3g GB free on device %d",
-                        (double)(need / 1e9L), (double)free_b / 1e9, device);
+                        (double)total / 1e9, (double)free_b / 1e9, device);
     }
     HIP_RET(lease.acquire(device));
     HostCtx &cx = *lease.c;
     hipStream_t st = cx.st;
-
-    Carver small, big;
-    const bool keep_all = small_total + traj_total <= CTX_ARENA_KEEP;
-    if (keep_all) {
-        HIP_RET(cx.need_arena(small_total + traj_total));
-        small.base = (char *)cx.arena;
-        big.base = (char *)cx.arena + small_total;
+    char *base;
+    if (total <= CTX_ARENA_KEEP) {
+        HIP_RET(cx.need_arena(total));
+        base = (char *)cx.arena;
     } else {
-        if (small_total <= CTX_ARENA_KEEP) {
-            HIP_RET(cx.need_arena(small_total));
-            small.base = (char *)cx.arena;
-        } else {
-            HIP_RET(b_small.alloc(small_total));
-            small.base = (char *)b_small.p;
-        }
-        if (traj_total) {
-            HIP_RET(b_traj.alloc(traj_total));
-            big.base = (char *)b_traj.p;
-        }
+        HIP_RET(own.alloc(total));
+        base = (char *)own.p;
     }
-    T *d_dbeta = small.take<T>(N);
-    T *d_dbeta2 = dbeta2 ? small.take<T>(N) : nullptr;
-    T *d_gamma = small.take<T>(n_gamma);
-    T *d_alpha = small.take<T>(n_alpha);
-    T *d_a0_aos = small.take<T>(n_a0 * nc);
-    T *d_a0_soa = small.take<T>(n_a0 * nc);
-    T *d_aend_soa = small.take<T>(N * nc);
-    T *d_wend_soa = waves ? small.take<T>(N * n_waves) : nullptr;
-    T *d_wmax_soa = waves ? small.take<T>(N * n_waves) : nullptr;
-    const size_t out_off = small.used;
-    T *d_aend_aos = small.take<T>(N * nc);
-    T *d_pend = small.take<T>(N);
-    T *d_pmax = small.take<T>(N);
-    int64_t *d_bad = small.take<int64_t>(N);
-    T *d_wend = waves ? small.take<T>(N * n_waves) : nullptr;   // [N][n_waves], the caller's layout
-    T *d_wmax = waves ? small.take<T>(N * n_waves) : nullptr;
-    T *d_traj = nullptr, *d_stage[2] = {nullptr, nullptr};
-    if (traj_in_out) {
-        d_traj = small.take<T>(traj_elems);
-    } else if (traj) {
-        d_traj = big.take<T>(traj_elems);
-        d_stage[0] = (T *)big.take<char>(stage_bytes);
-        d_stage[1] = (T *)big.take<char>(stage_bytes);
-    }
+    Staging<T> sg;
+    sg.in.base = base;
+    sg.mid.base = base + in_b;
+    sg.out.base = sg.mid.base + mid_b;
+    sg.big.base = sg.out.base + out_b;
+    layout(sg);
 
-    // -- inputs: a small sweep's arrive in ONE copy from the page-locked mirror (same slice offsets as on the device)
-    const bool mirror = in_bytes <= CTX_PINNED_IN && out_bytes <= CTX_PINNED_OUT;
-    if (mirror) {
-        char *m = cx.pinned;
-        auto put = [&](const T *dev, const T *src, size_t count) {
-            std::memcpy(m + ((const char *)dev - small.base), src, count * sizeof(T));
-        };
-        put(d_dbeta, dbeta, N);
-        if (dbeta2) put(d_dbeta2, dbeta2, N);
-        put(d_gamma, gamma, n_gamma);
-        put(d_alpha, alpha, n_alpha);
-        put(d_a0_aos, a0, n_a0 * nc);
-        HIP_RET(hipMemcpyAsync(small.base, m, in_bytes, hipMemcpyHostToDevice, st));
-    } else {
-        HIP_RET(hipMemcpyAsync(d_dbeta, dbeta, N * sizeof(T), hipMemcpyHostToDevice, st));
-        if (dbeta2) HIP_RET(hipMemcpyAsync(d_dbeta2, dbeta2, N * sizeof(T), hipMemcpyHostToDevice, st));
-        HIP_RET(hipMemcpyAsync(d_gamma, gamma, n_gamma * sizeof(T), hipMemcpyHostToDevice, st));
-        HIP_RET(hipMemcpyAsync(d_alpha, alpha, n_alpha * sizeof(T), hipMemcpyHostToDevice, st));
-        HIP_RET(hipMemcpyAsync(d_a0_aos, a0, n_a0 * nc * sizeof(T), hipMemcpyHostToDevice, st));
+    const bool mirror = in_b <= CTX_PINNED_IN && out_b <= CTX_PINNED_OUT;
+    char *m_in = cx.pinned, *m_out = cx.pinned + CTX_PINNED_IN;   // same offsets as the device regions
+    for (const auto &c : sg.ups) {
+        if (!c.bytes) continue;
+        if (mirror) std::memcpy(m_in + ((char *)c.dev - sg.in.base), c.host, c.bytes);
+        else HIP_RET(hipMemcpyAsync(c.dev, c.host, c.bytes, hipMemcpyHostToDevice, st));
     }
-    HIP_RET(Launch<T>::a2s(st, d_a0_aos, d_a0_soa, (long long)n_a0, nc));
-    HIP_RET(hipEventRecord(cx.ev0, st));
-    rc = sweep_dev<T>(st, n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha, d_a0_soa,
-                      flags, d_aend_soa, d_pend, d_pmax, d_bad, d_traj, d_wend_soa, d_wmax_soa);
+    if (mirror && in_b) HIP_RET(hipMemcpyAsync(sg.in.base, m_in, in_b, hipMemcpyHostToDevice, st));
+    for (const auto &t : sg.to_soa)
+        for (int b = 0; b < t.batches; ++b)
+            HIP_RET(Launch<T>::a2s(st, t.from + b * t.rows * t.nc, t.to + b * t.rows * t.nc, (long long)t.rows, t.nc));
+    if (elapsed_ms) HIP_RET(hipEventRecord(cx.ev0, st));   // only on request: two records are measurable on a small call
+    rc = compute(st);
     if (rc != PSA_OK) return rc;
-    HIP_RET(hipEventRecord(cx.ev1, st));
-    HIP_RET(Launch<T>::s2a(st, d_aend_soa, d_aend_aos, (long long)N, nc));
-    if (waves) {
-        HIP_RET(Launch<T>::s2a(st, d_wend_soa, d_wend, (long long)N, n_waves));
-        HIP_RET(Launch<T>::s2a(st, d_wmax_soa, d_wmax, (long long)N, n_waves));
-    }
+    if (elapsed_ms) HIP_RET(hipEventRecord(cx.ev1, st));
+    for (const auto &t : sg.to_aos) HIP_RET(Launch<T>::s2a(st, t.from, t.to, (long long)t.rows, t.nc));
     if (mirror) {
-        HIP_RET(hipMemcpyAsync(cx.pinned + CTX_PINNED_IN, small.base + out_off, out_bytes, hipMemcpyDeviceToHost, st));
+        if (out_b) HIP_RET(hipMemcpyAsync(m_out, sg.out.base, out_b, hipMemcpyDeviceToHost, st));
     } else {
-        HIP_RET(hipMemcpyAsync(a_end, d_aend_aos, N * nc * sizeof(T), hipMemcpyDeviceToHost, st));
-        HIP_RET(hipMemcpyAsync(p_end, d_pend, N * sizeof(T), hipMemcpyDeviceToHost, st));
-        HIP_RET(hipMemcpyAsync(p_max, d_pmax, N * sizeof(T), hipMemcpyDeviceToHost, st));
-        HIP_RET(hipMemcpyAsync(first_bad, d_bad, N * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        if (waves) {
-            HIP_RET(hipMemcpyAsync(wave_end, d_wend, N * n_waves * sizeof(T), hipMemcpyDeviceToHost, st));
-            HIP_RET(hipMemcpyAsync(wave_max, d_wmax, N * n_waves * sizeof(T), hipMemcpyDeviceToHost, st));
-        }
-        if (traj_in_out) HIP_RET(hipMemcpyAsync(traj, d_traj, traj_bytes, hipMemcpyDeviceToHost, st));
+        for (const auto &c : sg.downs)
+            if (c.bytes) HIP_RET(hipMemcpyAsync(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost, st));
     }
-    if (traj && !traj_in_out) {
+    if (const auto &tr = sg.traj; tr.dev) {
+        // [rows][nw][ld] -> chunk [pts][rows][nw] in one staging buffer while the other one's chunk is being copied home
         HIP_RET(cx.need_copy_streams());
         HIP_RET(hipEventRecord(cx.ev_kernel, st));
         for (int b = 0; b < 2; ++b) HIP_RET(hipStreamWaitEvent(cx.st_copy[b], cx.ev_kernel, 0));
+        const size_t point_elems = tr.rows * tr.nc;
         int b = 0;
-        for (size_t p0 = 0; p0 < N; p0 += chunk_pts, b ^= 1) {
-            const size_t pts = (N - p0 < chunk_pts) ? N - p0 : chunk_pts;
+        for (size_t p0 = 0; p0 < tr.n; p0 += tr.chunk, b ^= 1) {
+            const size_t pts = (tr.n - p0 < tr.chunk) ? tr.n - p0 : tr.chunk;
 #ifdef PSA_FAULT_INJECTION
-            if (injected_chunk_failure(p0 / chunk_pts)) return hip_fail(hipErrorUnknown, "injected failure in the staging loop");
+            if (injected_chunk_failure(p0 / tr.chunk)) return hip_fail(hipErrorUnknown, "injected failure in the staging loop");
 #endif
             // stream order on st_copy[b] keeps the staging buffer busy until its previous copy has finished
-            HIP_RET(Launch<T>::t2a(cx.st_copy[b], d_traj + 2 * p0, d_stage[b], (long long)pts, (long long)ld,
-                                   (long long)n_saved, nc));
-            HIP_RET(hipMemcpyAsync(traj + p0 * (size_t)n_saved * nc, d_stage[b], pts * point_bytes, hipMemcpyDeviceToHost,
-                                   cx.st_copy[b]));
+            HIP_RET(Launch<T>::t2a(cx.st_copy[b], tr.dev + 2 * p0, tr.stage[b], (long long)pts, (long long)tr.ld,
+                                   (long long)tr.rows, tr.nc));
+            HIP_RET(hipMemcpyAsync(tr.host + p0 * point_elems, tr.stage[b], pts * point_elems * sizeof(T),
+                                   hipMemcpyDeviceToHost, cx.st_copy[b]));
         }
         HIP_RET(hipStreamSynchronize(cx.st_copy[0]));
         HIP_RET(hipStreamSynchronize(cx.st_copy[1]));
     }
     HIP_RET(hipStreamSynchronize(st));
-    if (mirror) {
-        const char *m = cx.pinned + CTX_PINNED_IN;
-        auto get = [&](void *dst, const void *dev, size_t bytes) {
-            std::memcpy(dst, m + ((const char *)dev - (small.base + out_off)), bytes);
-        };
-        get(a_end, d_aend_aos, N * nc * sizeof(T));
-        get(p_end, d_pend, N * sizeof(T));
-        get(p_max, d_pmax, N * sizeof(T));
-        get(first_bad, d_bad, N * sizeof(int64_t));
-        if (waves) {
-            get(wave_end, d_wend, N * n_waves * sizeof(T));
-            get(wave_max, d_wmax, N * n_waves * sizeof(T));
-        }
-        if (traj_in_out) get(traj, d_traj, traj_bytes);
-    }
+    if (mirror)
+        for (const auto &c : sg.downs) std::memcpy(c.host, m_out + ((char *)c.dev - sg.out.base), c.bytes);
     if (elapsed_ms) {
         float ms = 0.f;
         HIP_RET(hipEventElapsedTime(&ms, cx.ev0, cx.ev1));
         *elapsed_ms = (double)ms;
     }
     return PSA_OK;
+}
+
+// waves: psa_rk4_sweep_waves_* (the per-wave summary into wave_end / wave_max)
+template <typename T>
+int sweep_host(int device, int n_waves, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+               const T *dbeta, const T *dbeta2, const T *gamma, const T *alpha, const T *a0, uint32_t flags,
+               T *a_end, T *p_end, T *p_max, int64_t *first_bad, T *traj, double *elapsed_ms,
+               bool waves = false, T *wave_end = nullptr, T *wave_max = nullptr) {
+    int rc;
+    if (waves && (rc = validate_waves(flags, traj != nullptr, n_points, wave_end, wave_max)) != PSA_OK) return rc;
+    rc = validate_common(n_waves, n_points, n_steps, z_max, save_every, dbeta, dbeta2, gamma, alpha, a0, a_end, p_end,
+                         p_max, first_bad, flags, traj != nullptr, sizeof(T));
+    if (rc != PSA_OK) return rc;
+    if (elapsed_ms) *elapsed_ms = 0.0;
+    if (n_points == 0) return PSA_OK;
+    const int nc = 2 * n_waves;
+    const size_t N = (size_t)n_points;
+    if (traj) flags |= PSA_OPT_TRAJ_LD;   // the device-side trajectory has its own leading dimension; the caller's is dense
+    if ((flags & PSA_BCAST_ALPHA) && alpha[0] == T(0)) flags |= PSA_OPT_LOSSLESS;   // the reference's alpha == 0.0 branch
+    const T *d_dbeta, *d_dbeta2, *d_gamma, *d_alpha, *d_a0;
+    T *d_aend, *d_pend, *d_pmax, *d_wend, *d_wmax, *d_traj;
+    int64_t *d_bad;
+    auto layout = [&](Staging<T> &sg) {
+        d_dbeta = sg.input(dbeta, N);
+        d_dbeta2 = sg.input(dbeta2, N);
+        d_gamma = sg.input(gamma, (flags & PSA_BCAST_GAMMA) ? 1 : N);
+        d_alpha = sg.input(alpha, (flags & PSA_BCAST_ALPHA) ? 1 : N);
+        d_a0 = sg.input_soa(a0, (flags & PSA_BCAST_A0) ? 1 : N, nc);
+        d_aend = sg.output_soa(a_end, N, nc);
+        d_pend = sg.output(p_end, N);
+        d_pmax = sg.output(p_max, N);
+        d_bad = sg.output(first_bad, N);
+        d_wend = sg.output_soa(wave_end, N, n_waves);
+        d_wmax = sg.output_soa(wave_max, N, n_waves);
+        d_traj = sg.trajectory(traj, N, (size_t)(n_steps / save_every + 1), nc);
+    };
+    return host_call<T>(device, "the RK4 sweep", elapsed_ms, layout, [&](hipStream_t st) {
+        return sweep_dev<T>(st, n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha, d_a0,
+                            flags, d_aend, d_pend, d_pmax, d_bad, d_traj, d_wend, d_wmax);
+    });
 }
 
 // ---- fibre chains: S spans, one sweep launch + one epilogue (psa_chain.hip) each ------------------------------------
@@ -603,7 +594,7 @@ int validate_chain(int n_waves, int64_t n_points, int n_segments, const int64_t 
     }
     if ((wave_end != nullptr) != (wave_max != nullptr))
         return fail(PSA_E_NULLPTR, "p_wave_end and p_wave_max are given together or not at all");
-    if (wave_end && (rc = validate_waves(flags, traj != nullptr)) != PSA_OK) return rc;
+    if (wave_end && (rc = validate_waves(flags, traj != nullptr, n_points, wave_end, wave_max)) != PSA_OK) return rc;
     if (traj && (long double)rows * 2 * n_waves * (long double)traj_ld_of(n_points, elem) > 4.0e18L)
         return fail(PSA_E_TOO_LARGE, "trajectory buffer too large");
     *rows_total = rows;
@@ -715,12 +706,9 @@ int chain_host(int device, int n_waves, int64_t n_points, int n_segments, const 
     if (rc != PSA_OK) return rc;
     if (elapsed_ms) *elapsed_ms = 0.0;
     if (n_points == 0) return PSA_OK;
-    rc = check_device(device, "the fibre chain");
-    if (rc != PSA_OK) return rc;
 
     const int S = n_segments, nc = 2 * n_waves;
     const size_t N = (size_t)n_points;
-    const bool waves = wave_end != nullptr;
     // the reference's alpha == 0.0 branch, span by span: a broadcast 0, or (S > 1, where a lossy span elsewhere makes the
     // alpha array per point) a span whose row is 0 everywhere.  One span keeps psa_rk4_sweep_*'s rule: bit-identical.
     std::vector<unsigned char> lossless((size_t)S, 0);
@@ -733,109 +721,34 @@ int chain_host(int device, int n_waves, int64_t n_points, int n_segments, const 
         lossless[(size_t)s] = zero;
     }
     if (traj) flags |= PSA_OPT_TRAJ_LD;
-    const size_t n_gamma = (flags & PSA_BCAST_GAMMA) ? (size_t)S : S * N;
-    const size_t n_alpha = (flags & PSA_BCAST_ALPHA) ? (size_t)S : S * N;
-    const size_t n_a0 = (flags & PSA_BCAST_A0) ? 1 : N;
-    const size_t n_tr = transfer ? (size_t)(S - 1) * ((flags & PSA_BCAST_TRANSFER) ? 1 : N) * nc : 0;
-    const size_t ld = (size_t)traj_ld_of(n_points, sizeof(T));
-    const size_t traj_elems = traj ? (size_t)rows_total * nc * ld : 0;
-    const size_t traj_host_elems = traj ? (size_t)rows_total * nc * N : 0;
-
-    using C = Carver;
-    const size_t ws_bytes = C::aligned((size_t)chain_workspace_bytes(n_waves, n_points, sizeof(T), waves));
-    const size_t total = C::aligned(S * N * sizeof(T)) * (dbeta2 ? 2 : 1) + C::aligned(n_gamma * sizeof(T)) +
-                         C::aligned(n_alpha * sizeof(T)) + 2 * C::aligned(n_a0 * nc * sizeof(T)) +
-                         2 * C::aligned(n_tr * sizeof(T)) + 2 * C::aligned(N * nc * sizeof(T)) +
-                         2 * C::aligned(N * sizeof(T)) + C::aligned(N * 8) +
-                         (waves ? 4 * C::aligned(N * n_waves * sizeof(T)) : 0) + ws_bytes +
-                         C::aligned(traj_elems * sizeof(T)) + C::aligned(traj_host_elems * sizeof(T));
-
-    DeviceScope scope;
-    DevBuf b_all;
-    CtxLease lease;
-    HIP_RET(scope.enter(device));
-    if (traj) {   // say "too large" before hipMalloc says "out of memory"
-        size_t free_b = 0, total_b = 0;
-        HIP_RET(hipMemGetInfo(&free_b, &total_b));
-        if (total > CTX_ARENA_KEEP && total > free_b)
-            return fail(PSA_E_TOO_LARGE, "chain trajectory of %.3g GB does not fit the %.3g GB free on device %d",
-                        (double)total / 1e9, (double)free_b / 1e9, device);
-    }
-    HIP_RET(lease.acquire(device));
-    HostCtx &cx = *lease.c;
-    hipStream_t st = cx.st;
-    Carver cv;
-    if (total <= CTX_ARENA_KEEP) {
-        HIP_RET(cx.need_arena(total));
-        cv.base = (char *)cx.arena;
-    } else {
-        HIP_RET(b_all.alloc(total));
-        cv.base = (char *)b_all.p;
-    }
-    T *d_dbeta = cv.take<T>(S * N);
-    T *d_dbeta2 = dbeta2 ? cv.take<T>(S * N) : nullptr;
-    T *d_gamma = cv.take<T>(n_gamma);
-    T *d_alpha = cv.take<T>(n_alpha);
-    T *d_a0_aos = cv.take<T>(n_a0 * nc);
-    T *d_a0_soa = cv.take<T>(n_a0 * nc);
-    T *d_tr_aos = n_tr ? cv.take<T>(n_tr) : nullptr;
-    T *d_tr_soa = n_tr ? cv.take<T>(n_tr) : nullptr;
-    T *d_aend_soa = cv.take<T>(N * nc);
-    T *d_aend_aos = cv.take<T>(N * nc);
-    T *d_pend = cv.take<T>(N);
-    T *d_pmax = cv.take<T>(N);
-    int64_t *d_bad = cv.take<int64_t>(N);
-    T *d_wend_soa = waves ? cv.take<T>(N * n_waves) : nullptr;
-    T *d_wmax_soa = waves ? cv.take<T>(N * n_waves) : nullptr;
-    T *d_wend = waves ? cv.take<T>(N * n_waves) : nullptr;
-    T *d_wmax = waves ? cv.take<T>(N * n_waves) : nullptr;
-    void *d_ws = cv.take<char>(ws_bytes);
-    T *d_traj = traj ? cv.take<T>(traj_elems) : nullptr;
-    T *d_traj_aos = traj ? cv.take<T>(traj_host_elems) : nullptr;
-
-    HIP_RET(hipMemcpyAsync(d_dbeta, dbeta, S * N * sizeof(T), hipMemcpyHostToDevice, st));
-    if (dbeta2) HIP_RET(hipMemcpyAsync(d_dbeta2, dbeta2, S * N * sizeof(T), hipMemcpyHostToDevice, st));
-    HIP_RET(hipMemcpyAsync(d_gamma, gamma, n_gamma * sizeof(T), hipMemcpyHostToDevice, st));
-    HIP_RET(hipMemcpyAsync(d_alpha, alpha, n_alpha * sizeof(T), hipMemcpyHostToDevice, st));
-    HIP_RET(hipMemcpyAsync(d_a0_aos, a0, n_a0 * nc * sizeof(T), hipMemcpyHostToDevice, st));
-    HIP_RET(Launch<T>::a2s(st, d_a0_aos, d_a0_soa, (long long)n_a0, nc));
-    if (n_tr) {
-        HIP_RET(hipMemcpyAsync(d_tr_aos, transfer, n_tr * sizeof(T), hipMemcpyHostToDevice, st));
-        if (flags & PSA_BCAST_TRANSFER) {   // [S-1][n_waves][2] is already [S-1][2*n_waves]
-            HIP_RET(hipMemcpyAsync(d_tr_soa, d_tr_aos, n_tr * sizeof(T), hipMemcpyDeviceToDevice, st));
-        } else {                           // [S-1][N][n_waves][2] -> [S-1][2*n_waves][N]
-            for (int s = 0; s + 1 < S; ++s)
-                HIP_RET(Launch<T>::a2s(st, d_tr_aos + (size_t)s * N * nc, d_tr_soa + (size_t)s * N * nc, (long long)N, nc));
-        }
-    }
-    HIP_RET(hipEventRecord(cx.ev0, st));
-    rc = chain_dev<T>(st, n_waves, n_points, S, n_steps, seg_len, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha,
-                      d_a0_soa, d_tr_soa, flags, d_aend_soa, d_pend, d_pmax, d_bad, d_traj, d_wend_soa, d_wmax_soa, d_ws,
-                      lossless.data());
-    if (rc != PSA_OK) return rc;
-    HIP_RET(hipEventRecord(cx.ev1, st));
-    HIP_RET(Launch<T>::s2a(st, d_aend_soa, d_aend_aos, (long long)N, nc));
-    HIP_RET(hipMemcpyAsync(a_end, d_aend_aos, N * nc * sizeof(T), hipMemcpyDeviceToHost, st));
-    HIP_RET(hipMemcpyAsync(p_end, d_pend, N * sizeof(T), hipMemcpyDeviceToHost, st));
-    HIP_RET(hipMemcpyAsync(p_max, d_pmax, N * sizeof(T), hipMemcpyDeviceToHost, st));
-    HIP_RET(hipMemcpyAsync(first_bad, d_bad, N * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    if (waves) {
-        HIP_RET(Launch<T>::s2a(st, d_wend_soa, d_wend, (long long)N, n_waves));
-        HIP_RET(Launch<T>::s2a(st, d_wmax_soa, d_wmax, (long long)N, n_waves));
-        HIP_RET(hipMemcpyAsync(wave_end, d_wend, N * n_waves * sizeof(T), hipMemcpyDeviceToHost, st));
-        HIP_RET(hipMemcpyAsync(wave_max, d_wmax, N * n_waves * sizeof(T), hipMemcpyDeviceToHost, st));
-    }
-    if (traj) {
-        HIP_RET(Launch<T>::t2a(st, d_traj, d_traj_aos, (long long)N, (long long)ld, (long long)rows_total, nc));
-        HIP_RET(hipMemcpyAsync(traj, d_traj_aos, traj_host_elems * sizeof(T), hipMemcpyDeviceToHost, st));
-    }
-    HIP_RET(hipStreamSynchronize(st));
-    if (elapsed_ms) {
-        float ms = 0.f;
-        HIP_RET(hipEventElapsedTime(&ms, cx.ev0, cx.ev1));
-        *elapsed_ms = (double)ms;
-    }
-    return PSA_OK;
+    const T *tr = S > 1 ? transfer : nullptr;
+    const T *d_dbeta, *d_dbeta2, *d_gamma, *d_alpha, *d_a0, *d_tr;
+    T *d_aend, *d_pend, *d_pmax, *d_wend, *d_wmax, *d_traj;
+    int64_t *d_bad;
+    void *d_ws;
+    auto layout = [&](Staging<T> &sg) {
+        d_dbeta = sg.input(dbeta, S * N);
+        d_dbeta2 = sg.input(dbeta2, S * N);
+        d_gamma = sg.input(gamma, (flags & PSA_BCAST_GAMMA) ? (size_t)S : S * N);
+        d_alpha = sg.input(alpha, (flags & PSA_BCAST_ALPHA) ? (size_t)S : S * N);
+        d_a0 = sg.input_soa(a0, (flags & PSA_BCAST_A0) ? 1 : N, nc);
+        // [S-1][n_waves][2] is already [S-1][2*n_waves]; [S-1][N][n_waves][2] -> [S-1][2*n_waves][N]
+        d_tr = (flags & PSA_BCAST_TRANSFER) ? sg.input(tr, (size_t)(S - 1) * nc) : sg.input_soa(tr, N, nc, S - 1);
+        d_ws = S > 1 ? sg.template scratch<char>((size_t)chain_workspace_bytes(n_waves, n_points, sizeof(T), wave_end != nullptr))
+                     : nullptr;
+        d_aend = sg.output_soa(a_end, N, nc);
+        d_pend = sg.output(p_end, N);
+        d_pmax = sg.output(p_max, N);
+        d_bad = sg.output(first_bad, N);
+        d_wend = sg.output_soa(wave_end, N, n_waves);
+        d_wmax = sg.output_soa(wave_max, N, n_waves);
+        d_traj = sg.trajectory(traj, N, (size_t)rows_total, nc);
+    };
+    return host_call<T>(device, "the fibre chain", elapsed_ms, layout, [&](hipStream_t st) {
+        return chain_dev<T>(st, n_waves, n_points, S, n_steps, seg_len, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha,
+                            d_a0, d_tr, flags, d_aend, d_pend, d_pmax, d_bad, d_traj, d_wend, d_wmax, d_ws,
+                            lossless.data());
+    });
 }
 
 template <typename T> struct GainLaunch;
@@ -860,58 +773,23 @@ int gain_summary_host(int device, int64_t n, const T *p_metric, const int64_t *f
     if (n < 0) return fail(PSA_E_NPOINTS, "n_points must be >= 0");
     if (!best_index || !best_gain || !n_finite || (n > 0 && !p_metric))
         return fail(PSA_E_NULLPTR, "a required buffer pointer is NULL");
-    int rc = check_device(device, "the gain summary");
-    if (rc != PSA_OK) return rc;
     const size_t N = (size_t)n;
-    using C = Carver;
-    // [inputs: p, first_bad] [workspace] [outputs: gain, (best_index, best_gain, n_finite)]
-    const size_t in_bytes = C::aligned(N * sizeof(T)) + (first_bad ? C::aligned(N * 8) : 0);
-    const size_t ws_bytes = C::aligned((size_t)psa::gain_summary_workspace_bytes(n));
-    const size_t out_bytes = (gain_out ? C::aligned(N * sizeof(T)) : 0) + C::aligned(3 * 8);
-    const size_t total = in_bytes + ws_bytes + out_bytes;
-    DeviceScope scope;
-    DevBuf b_all;
-    CtxLease lease;
-    HIP_RET(scope.enter(device));
-    HIP_RET(lease.acquire(device));
-    HostCtx &cx = *lease.c;
-    Carver cv;
-    if (total <= CTX_ARENA_KEEP) {
-        HIP_RET(cx.need_arena(total));
-        cv.base = (char *)cx.arena;
-    } else {
-        HIP_RET(b_all.alloc(total));
-        cv.base = (char *)b_all.p;
-    }
-    T *d_p = cv.take<T>(N);
-    int64_t *d_bad = first_bad ? cv.take<int64_t>(N) : nullptr;
-    void *d_ws = cv.take<char>(ws_bytes);
-    const size_t out_off = cv.used;
-    T *d_gain = gain_out ? cv.take<T>(N) : nullptr;
-    int64_t *d_scal = cv.take<int64_t>(3);          // best_index | best_gain (double) | n_finite
-    const bool mirror = in_bytes <= CTX_PINNED_IN && out_bytes <= CTX_PINNED_OUT;
-    if (mirror) {
-        if (N) std::memcpy(cx.pinned, p_metric, N * sizeof(T));
-        if (first_bad && N) std::memcpy(cx.pinned + ((char *)d_bad - cv.base), first_bad, N * 8);
-        if (N) HIP_RET(hipMemcpyAsync(cv.base, cx.pinned, in_bytes, hipMemcpyHostToDevice, cx.st));
-    } else {
-        HIP_RET(hipMemcpyAsync(d_p, p_metric, N * sizeof(T), hipMemcpyHostToDevice, cx.st));
-        if (first_bad) HIP_RET(hipMemcpyAsync(d_bad, first_bad, N * 8, hipMemcpyHostToDevice, cx.st));
-    }
-    rc = gain_summary_dev<T>(cx.st, n, d_p, d_bad, p0_sig, gain_db, d_gain, d_scal, (double *)(d_scal + 1), d_scal + 2, d_ws);
+    int64_t scal[3];   // best_index | best_gain (double) | n_finite
+    const T *d_p;
+    const int64_t *d_bad;
+    T *d_gain;
+    int64_t *d_scal;
+    void *d_ws;
+    int rc = host_call<T>(device, "the gain summary", nullptr, [&](Staging<T> &sg) {
+        d_p = sg.input(p_metric, N);
+        d_bad = sg.input(first_bad, N);
+        d_ws = sg.template scratch<char>((size_t)psa::gain_summary_workspace_bytes(n));
+        d_gain = sg.output(gain_out, N);
+        d_scal = sg.output(scal, 3);
+    }, [&](hipStream_t st) {
+        return gain_summary_dev<T>(st, n, d_p, d_bad, p0_sig, gain_db, d_gain, d_scal, (double *)(d_scal + 1), d_scal + 2, d_ws);
+    });
     if (rc != PSA_OK) return rc;
-    int64_t scal[3];
-    if (mirror) {
-        char *m = cx.pinned + CTX_PINNED_IN;
-        HIP_RET(hipMemcpyAsync(m, cv.base + out_off, out_bytes, hipMemcpyDeviceToHost, cx.st));
-        HIP_RET(hipStreamSynchronize(cx.st));
-        if (gain_out && N) std::memcpy(gain_out, m, N * sizeof(T));
-        std::memcpy(scal, m + ((char *)d_scal - (cv.base + out_off)), sizeof(scal));
-    } else {
-        if (gain_out && N) HIP_RET(hipMemcpyAsync(gain_out, d_gain, N * sizeof(T), hipMemcpyDeviceToHost, cx.st));
-        HIP_RET(hipMemcpyAsync(scal, d_scal, sizeof(scal), hipMemcpyDeviceToHost, cx.st));
-        HIP_RET(hipStreamSynchronize(cx.st));
-    }
     *best_index = scal[0];
     std::memcpy(best_gain, &scal[1], 8);
     *n_finite = scal[2];
@@ -1058,21 +936,15 @@ int psa_rk4_sweep_waves_f64(int device, int n_waves, int64_t n_points, int64_t n
                             const double *dbeta, const double *dbeta2, const double *gamma, const double *alpha,
                             const double *a0, uint32_t flags, double *a_end, double *p_end, double *p_max,
                             int64_t *first_bad, double *traj, double *elapsed_ms, double *p_wave_end, double *p_wave_max) {
-    int rc = validate_waves(flags, traj != nullptr);
-    if (rc != PSA_OK) return rc;
-    if (n_points > 0 && (!p_wave_end || !p_wave_max)) return fail(PSA_E_NULLPTR, "p_wave_end / p_wave_max is NULL");
     return sweep_host<double>(device, n_waves, n_points, n_steps, z_max, save_every, dbeta, dbeta2, gamma, alpha, a0,
-                              flags, a_end, p_end, p_max, first_bad, nullptr, elapsed_ms, p_wave_end, p_wave_max);
+                              flags, a_end, p_end, p_max, first_bad, traj, elapsed_ms, true, p_wave_end, p_wave_max);
 }
 int psa_rk4_sweep_waves_f32(int device, int n_waves, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
                             const float *dbeta, const float *dbeta2, const float *gamma, const float *alpha,
                             const float *a0, uint32_t flags, float *a_end, float *p_end, float *p_max,
                             int64_t *first_bad, float *traj, double *elapsed_ms, float *p_wave_end, float *p_wave_max) {
-    int rc = validate_waves(flags, traj != nullptr);
-    if (rc != PSA_OK) return rc;
-    if (n_points > 0 && (!p_wave_end || !p_wave_max)) return fail(PSA_E_NULLPTR, "p_wave_end / p_wave_max is NULL");
     return sweep_host<float>(device, n_waves, n_points, n_steps, z_max, save_every, dbeta, dbeta2, gamma, alpha, a0,
-                             flags, a_end, p_end, p_max, first_bad, nullptr, elapsed_ms, p_wave_end, p_wave_max);
+                             flags, a_end, p_end, p_max, first_bad, traj, elapsed_ms, true, p_wave_end, p_wave_max);
 }
 int psa_rk4_sweep_waves_f64_dev(void *stream, int n_waves, int64_t n_points, int64_t n_steps, double z_max,
                                 int32_t save_every, const double *d_dbeta, const double *d_dbeta2, const double *d_gamma,
@@ -1099,31 +971,23 @@ int psa_yaman_rhs_f64(int device, int64_t n, const double *z, const double *a, c
     if (n < 0) return fail(PSA_E_NPOINTS, "n_points must be >= 0");
     if (n == 0) return PSA_OK;
     if (!z || !a || !gamma || !alpha || !dbeta || !out) return fail(PSA_E_NULLPTR, "a required buffer pointer is NULL");
-    int rc = check_device(device, "the RHS kernel");
-    if (rc != PSA_OK) return rc;
     const size_t N = (size_t)n;
-    DeviceScope scope;
-    DevBuf bz, ba, bg, bal, bd, bo, bl, bk, bf;
-    HIP_TRY(scope.enter(device));
-    HIP_TRY(bz.alloc(N * 8)); HIP_TRY(ba.alloc(N * 64)); HIP_TRY(bg.alloc(N * 8)); HIP_TRY(bal.alloc(N * 8));
-    HIP_TRY(bd.alloc(N * 8)); HIP_TRY(bo.alloc(N * 64));
-    if (out_lin) HIP_TRY(bl.alloc(N * 64));
-    if (out_kerr) HIP_TRY(bk.alloc(N * 64));
-    if (out_fwm) HIP_TRY(bf.alloc(N * 64));
-    HIP_TRY(hipMemcpy(bz.p, z, N * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ba.p, a, N * 64, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(bg.p, gamma, N * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(bal.p, alpha, N * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(bd.p, dbeta, N * 8, hipMemcpyHostToDevice));
-    HIP_TRY(psa::launch_yaman_rhs_f64(nullptr, n, bz.as<double>(), ba.as<double>(), bg.as<double>(), bal.as<double>(),
-                                      bd.as<double>(), bo.as<double>(), out_lin ? bl.as<double>() : nullptr,
-                                      out_kerr ? bk.as<double>() : nullptr, out_fwm ? bf.as<double>() : nullptr));
-    HIP_TRY(hipMemcpy(out, bo.p, N * 64, hipMemcpyDeviceToHost));
-    if (out_lin) HIP_TRY(hipMemcpy(out_lin, bl.p, N * 64, hipMemcpyDeviceToHost));
-    if (out_kerr) HIP_TRY(hipMemcpy(out_kerr, bk.p, N * 64, hipMemcpyDeviceToHost));
-    if (out_fwm) HIP_TRY(hipMemcpy(out_fwm, bf.p, N * 64, hipMemcpyDeviceToHost));
-done:
-    return rc;
+    const double *d_z, *d_a, *d_gamma, *d_alpha, *d_dbeta;
+    double *d_out, *d_lin, *d_kerr, *d_fwm;
+    return host_call<double>(device, "the RHS kernel", nullptr, [&](Staging<double> &sg) {
+        d_z = sg.input(z, N);
+        d_a = sg.input(a, 8 * N);
+        d_gamma = sg.input(gamma, N);
+        d_alpha = sg.input(alpha, N);
+        d_dbeta = sg.input(dbeta, N);
+        d_out = sg.output(out, 8 * N);
+        d_lin = sg.output(out_lin, 8 * N);
+        d_kerr = sg.output(out_kerr, 8 * N);
+        d_fwm = sg.output(out_fwm, 8 * N);
+    }, [&](hipStream_t st) {
+        hipError_t e = psa::launch_yaman_rhs_f64(st, n, d_z, d_a, d_gamma, d_alpha, d_dbeta, d_out, d_lin, d_kerr, d_fwm);
+        return e == hipSuccess ? PSA_OK : hip_fail(e, "yaman_rhs launch");
+    });
 }
 
 int64_t psa_gain_summary_workspace_bytes(int64_t n) { return psa::gain_summary_workspace_bytes(n); }
@@ -1183,24 +1047,20 @@ int psa_dbeta_grid_f64(int device, int method, const int32_t *orders, int n_orde
                        int64_t first_index, int64_t n_points, double *dbeta, uint8_t *valid) {
     if (n_points < 0 || n2 <= 0 || n3 <= 0) return fail(PSA_E_NPOINTS, "n_points must be >= 0 and the axes non-empty");
     if (!lambda2_axis || !lambda3_axis || (n_points > 0 && !dbeta)) return fail(PSA_E_NULLPTR, "a required buffer pointer is NULL");
-    int rc = check_device(device, "the dbeta producer");
-    if (rc != PSA_OK) return rc;
-    if (n_points == 0) return PSA_OK;
-    DeviceScope scope;
-    DevBuf b2, b3, bo, bv;
-    HIP_TRY(scope.enter(device));
-    HIP_TRY(b2.alloc((size_t)n2 * 8)); HIP_TRY(b3.alloc((size_t)n3 * 8)); HIP_TRY(bo.alloc((size_t)n_points * 8));
-    if (valid) HIP_TRY(bv.alloc((size_t)n_points));
-    HIP_TRY(hipMemcpy(b2.p, lambda2_axis, (size_t)n2 * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b3.p, lambda3_axis, (size_t)n3 * 8, hipMemcpyHostToDevice));
-    rc = psa_dbeta_grid_f64_dev(nullptr, method, orders, n_orders, max_order, beta, n_beta, omega_ref, two_pi_c, atol, rtol,
-                                lambda1_m, b2.as<double>(), n2, b3.as<double>(), n3, first_index, n_points,
-                                bo.as<double>(), valid ? bv.as<uint8_t>() : nullptr);
-    if (rc != PSA_OK) goto done;
-    HIP_TRY(hipMemcpy(dbeta, bo.p, (size_t)n_points * 8, hipMemcpyDeviceToHost));
-    if (valid) HIP_TRY(hipMemcpy(valid, bv.p, (size_t)n_points, hipMemcpyDeviceToHost));
-done:
-    return rc;
+    if (n_points == 0) return check_device(device, "the dbeta producer");
+    const size_t N = (size_t)n_points;
+    const double *d_ax2, *d_ax3;
+    double *d_out;
+    uint8_t *d_valid;
+    return host_call<double>(device, "the dbeta producer", nullptr, [&](Staging<double> &sg) {
+        d_ax2 = sg.input(lambda2_axis, (size_t)n2);
+        d_ax3 = sg.input(lambda3_axis, (size_t)n3);
+        d_out = sg.output(dbeta, N);
+        d_valid = sg.output(valid, N);
+    }, [&](hipStream_t st) {
+        return dbeta_grid_dev<double>(st, method, orders, n_orders, max_order, beta, n_beta, omega_ref, two_pi_c, atol, rtol,
+                                      lambda1_m, d_ax2, n2, d_ax3, n3, first_index, n_points, d_out, d_valid);
+    });
 }
 
 int psa_dbeta_pairs_f64(int device, const int32_t *orders, int n_orders, const double *beta, int n_beta, double omega_d,
@@ -1208,23 +1068,19 @@ int psa_dbeta_pairs_f64(int device, const int32_t *orders, int n_orders, const d
                         int64_t first_index, int64_t n_points, double *dbeta1, double *dbeta2) {
     if (n_points < 0 || n1 <= 0 || n2 <= 0) return fail(PSA_E_NPOINTS, "n_points must be >= 0 and the axes non-empty");
     if (!Omega1_axis || !Omega2_axis || (n_points > 0 && (!dbeta1 || !dbeta2))) return fail(PSA_E_NULLPTR, "a required buffer pointer is NULL");
-    int rc = check_device(device, "the dbeta producer");
-    if (rc != PSA_OK) return rc;
-    if (n_points == 0) return PSA_OK;
-    DeviceScope scope;
-    DevBuf b1, b2, o1, o2;
-    HIP_TRY(scope.enter(device));
-    HIP_TRY(b1.alloc((size_t)n1 * 8)); HIP_TRY(b2.alloc((size_t)n2 * 8));
-    HIP_TRY(o1.alloc((size_t)n_points * 8)); HIP_TRY(o2.alloc((size_t)n_points * 8));
-    HIP_TRY(hipMemcpy(b1.p, Omega1_axis, (size_t)n1 * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b2.p, Omega2_axis, (size_t)n2 * 8, hipMemcpyHostToDevice));
-    rc = psa_dbeta_pairs_f64_dev(nullptr, orders, n_orders, beta, n_beta, omega_d, b1.as<double>(), n1, b2.as<double>(), n2,
-                                 first_index, n_points, o1.as<double>(), o2.as<double>());
-    if (rc != PSA_OK) goto done;
-    HIP_TRY(hipMemcpy(dbeta1, o1.p, (size_t)n_points * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(dbeta2, o2.p, (size_t)n_points * 8, hipMemcpyDeviceToHost));
-done:
-    return rc;
+    if (n_points == 0) return check_device(device, "the dbeta producer");
+    const size_t N = (size_t)n_points;
+    const double *d_ax1, *d_ax2;
+    double *d_out1, *d_out2;
+    return host_call<double>(device, "the dbeta producer", nullptr, [&](Staging<double> &sg) {
+        d_ax1 = sg.input(Omega1_axis, (size_t)n1);
+        d_ax2 = sg.input(Omega2_axis, (size_t)n2);
+        d_out1 = sg.output(dbeta1, N);
+        d_out2 = sg.output(dbeta2, N);
+    }, [&](hipStream_t st) {
+        return dbeta_pairs_dev<double>(st, orders, n_orders, beta, n_beta, omega_d, d_ax1, n1, d_ax2, n2, first_index,
+                                       n_points, d_out1, d_out2);
+    });
 }
 
 int psa_rk4_chain_f64(int device, int n_waves, int64_t n_points, int n_segments, const int64_t *n_steps,

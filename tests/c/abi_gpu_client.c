@@ -1,11 +1,14 @@
 /* GPU-side plain-C client used for host-sanitizer runs (tools/host_sanitize.sh) and by the test-suite: every host-buffer
  * entry point of psa_rk4.h through the ABI --
- *   1. a small sweep with a trajectory, the gain summary (f64), one RHS evaluation;
+ *   1. a small sweep with a trajectory, the per-wave summary (psa_rk4_sweep_waves_f64), the gain summary (f64), one RHS
+ *      evaluation;
  *   2. a trajectory that leaves the device in TWO chunks, the second one ragged (4 197 points x 1 001 rows = 269 MB through
  *      the 256 MB staging buffers), checked row by row against the small sweep's arithmetic (A[-1] == last row, row 0 == A0);
- *   3. the dbeta producers psa_dbeta_grid_f64 / psa_dbeta_pairs_f64 and the float32 sweep + psa_gain_summary_f32;
- *   4. (library built with -DPSA_FAULT_INJECTION, PSA_FAIL_CHUNK set) a failure INSIDE the staging loop, then the same call
- *      again without it: the context must come back clean; psa_release_cache() at the end.
+ *   3. the same fibre as a two-span chain (psa_rk4_chain_f64, 2 x 501 rows: again one full chunk + a ragged one), row by row
+ *      against the sweep's trajectory;
+ *   4. the dbeta producers psa_dbeta_grid_f64 / psa_dbeta_pairs_f64 and the float32 sweep + psa_gain_summary_f32;
+ *   5. (library built with -DPSA_FAULT_INJECTION, PSA_FAIL_CHUNK set) a failure INSIDE the staging loop of the sweep and of
+ *      the chain, then the same calls again without it: the context must come back clean; psa_release_cache() at the end.
  */
 #define _POSIX_C_SOURCE 200112L   /* setenv / unsetenv under -std=c99 */
 #include <math.h>
@@ -21,15 +24,14 @@
 
 static const double A0[8] = {0.7071067811865476, 0, 0.7071067811865476, 0, 0.0031622776601683794, 0, 0.0031622776601683794, 0};
 
-static int big_trajectory(int expect_failure) {
+static int big_trajectory(int expect_failure, double *traj) {
     const int64_t rows = psa_n_saved(NSBIG, 1);
     double *dbeta = (double *)malloc(sizeof(double) * NBIG), *a_end = (double *)malloc(sizeof(double) * NBIG * 8);
     double *p_end = (double *)malloc(sizeof(double) * NBIG), *p_max = (double *)malloc(sizeof(double) * NBIG);
     int64_t *bad = (int64_t *)malloc(sizeof(int64_t) * NBIG);
-    double *traj = (double *)malloc(sizeof(double) * (size_t)NBIG * rows * 8);
     double gamma = 0.0115, alpha = 0.0, ms = 0;     /* alpha == 0 broadcast: the lossless instantiation */
     int rc, ret = 0;
-    if (!dbeta || !a_end || !p_end || !p_max || !bad || !traj) return 20;
+    if (!dbeta || !a_end || !p_end || !p_max || !bad) return 20;
     for (int i = 0; i < NBIG; ++i) dbeta[i] = -0.05 + 0.1 * i / (NBIG - 1);
     rc = psa_rk4_sweep_f64(0, 4, NBIG, NSBIG, 100.0, 1, dbeta, NULL, &gamma, &alpha, A0,
                            PSA_BCAST_GAMMA | PSA_BCAST_ALPHA | PSA_BCAST_A0 | PSA_OPT_CHECK_NAN, a_end, p_end, p_max, bad, traj, &ms);
@@ -54,6 +56,47 @@ static int big_trajectory(int expect_failure) {
                 if (fabs(p - 1.00002) > 1e-9) ret = 25;
             }
         if (!ret) printf("  two-chunk trajectory ok: %d points x %lld rows, kernel %.3f ms\n", NBIG, (long long)rows, ms);
+    }
+    free(dbeta); free(a_end); free(p_end); free(p_max); free(bad);
+    return ret;
+}
+
+/* big_trajectory's fibre cut in two identical spans (identity transfer): 2 x 501 rows, where the sweep has 1 001 -- span 1's
+ * row 0 repeats span 0's last row.  4 160 points fit one staging buffer at 1 002 rows: one full chunk + 37 points. */
+static int big_chain(int expect_failure, const double *sweep_traj) {
+    const int64_t steps[2] = {NSBIG / 2, NSBIG / 2}, half = psa_n_saved(NSBIG / 2, 1), rows = 2 * half;
+    const int64_t sweep_rows = psa_n_saved(NSBIG, 1);
+    const double len[2] = {50.0, 50.0}, gamma[2] = {0.0115, 0.0115}, alpha[2] = {0.0, 0.0};
+    double *dbeta = (double *)malloc(sizeof(double) * 2 * NBIG), *a_end = (double *)malloc(sizeof(double) * NBIG * 8);
+    double *p_end = (double *)malloc(sizeof(double) * NBIG), *p_max = (double *)malloc(sizeof(double) * NBIG);
+    int64_t *bad = (int64_t *)malloc(sizeof(int64_t) * NBIG);
+    double *traj = (double *)malloc(sizeof(double) * (size_t)NBIG * rows * 8);
+    double ms = 0;
+    int rc, ret = 0;
+    if (!dbeta || !a_end || !p_end || !p_max || !bad || !traj) return 30;
+    for (int i = 0; i < NBIG; ++i) dbeta[i] = dbeta[NBIG + i] = -0.05 + 0.1 * i / (NBIG - 1);
+    rc = psa_rk4_chain_f64(0, 4, NBIG, 2, steps, len, 1, dbeta, NULL, gamma, alpha, A0, NULL,
+                           PSA_BCAST_GAMMA | PSA_BCAST_ALPHA | PSA_BCAST_A0 | PSA_OPT_CHECK_NAN, a_end, p_end, p_max, bad, traj,
+                           &ms, NULL, NULL);
+    if (expect_failure) {
+        if (rc <= 0 || !strstr(psa_last_error(), "injected")) { fprintf(stderr, "chain: expected the injected failure, got rc=%d\n", rc); ret = 31; }
+    } else if (rc) {
+        fprintf(stderr, "big chain rc=%d %s\n", rc, psa_last_error());
+        ret = 32;
+    } else {
+        for (int i = 0; i < NBIG && !ret; ++i) {
+            const double *pt = traj + (size_t)i * rows * 8, *sw = sweep_traj + (size_t)i * sweep_rows * 8;
+            for (int c = 0; c < 8; ++c)
+                if (pt[c] != A0[c] || pt[(rows - 1) * 8 + c] != a_end[i * 8 + c]) ret = 33;
+            if (bad[i] != -1 || !(p_max[i] >= p_end[i])) ret = 34;
+            /* the gauge's rotations are the only difference from the one-span run */
+            for (int64_t r = 0; r < rows && !ret; ++r) {
+                const double *want = sw + (r < half ? r : r - 1) * 8;
+                for (int c = 0; c < 8; ++c)
+                    if (fabs(pt[r * 8 + c] - want[c]) > 1e-9) ret = 35;
+            }
+        }
+        if (!ret) printf("  two-chunk chain trajectory ok: %d points x %lld rows, kernels %.3f ms\n", NBIG, (long long)rows, ms);
     }
     free(dbeta); free(a_end); free(p_end); free(p_max); free(bad); free(traj);
     return ret;
@@ -80,6 +123,15 @@ int main(void) {
     }
     rc = psa_gain_summary_f64(0, N, p_max, bad, 1e-5, 1, gain, &best, &best_gain, &nfin);
     if (rc || nfin != N || best < 0 || gain[best] != best_gain) { fprintf(stderr, "summary rc=%d\n", rc); return 5; }
+    {   /* the per-wave summary: wave 2's columns are p_end / p_max bit for bit */
+        static double w_end[N * 4], w_max[N * 4], pe[N], pm[N], ae[N * 8];
+        rc = psa_rk4_sweep_waves_f64(0, 4, N, NS, 100.5, SE, dbeta, NULL, &gamma, &alpha, A0,
+                                     PSA_BCAST_GAMMA | PSA_BCAST_ALPHA | PSA_BCAST_A0 | PSA_OPT_CHECK_NAN, ae, pe, pm, bad, NULL,
+                                     NULL, w_end, w_max);
+        if (rc) { fprintf(stderr, "sweep waves rc=%d %s\n", rc, psa_last_error()); return 19; }
+        for (int i = 0; i < N; ++i)
+            if (w_end[i * 4 + 2] != pe[i] || w_max[i * 4 + 2] != pm[i] || bad[i] != -1) return 19;
+    }
     double z = 3.0, out[8], lin[8];
     rc = psa_yaman_rhs_f64(0, 1, &z, A0, &gamma, &alpha, dbeta, out, lin, NULL, NULL);
     if (rc || fabs(lin[0] + 0.5 * alpha * A0[0]) > 1e-18) return 6;
@@ -131,14 +183,15 @@ int main(void) {
     }
 
     /* the chunked trajectory; with PSA_FAIL_CHUNK set (fault-injection build) first the failing call, then a clean one */
+    double *big = (double *)malloc(sizeof(double) * (size_t)NBIG * psa_n_saved(NSBIG, 1) * 8);
+    if (!big) return 20;
     if (getenv("PSA_FAIL_CHUNK")) {
-        rc = big_trajectory(1);
-        if (rc) return rc;
+        if ((rc = big_trajectory(1, big)) || (rc = big_chain(1, NULL))) return rc;
         unsetenv("PSA_FAIL_CHUNK");
-        printf("  injected staging-loop failure reported and cleaned up\n");
+        printf("  injected staging-loop failures (sweep, chain) reported and cleaned up\n");
     }
-    rc = big_trajectory(0);
-    if (rc) return rc;
+    if ((rc = big_trajectory(0, big)) || (rc = big_chain(0, big))) return rc;
+    free(big);
     /* an argument error after real work, then the cache goes */
     if (psa_rk4_sweep_f64(0, 4, N, NS, 100.5, 0, dbeta, NULL, &gamma, &alpha, A0, 0, a_end, p_end, p_max, bad, NULL, NULL) != PSA_E_SAVE_EVERY) return 16;
     if (psa_release_cache() < 1) return 17;

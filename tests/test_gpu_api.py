@@ -322,8 +322,9 @@ def test_device_entry_point_can_be_captured_into_a_graph_and_replayed(oracle):
 
 
 def test_plain_c_program_drives_a_sweep_through_the_abi(tmp_path):
-    """tests/c/abi_gpu_client.c: a C99 program (no Python, no torch) runs a 257-point sweep with trajectories, the gain
-    summary and one RHS evaluation through libpsa_hip.so and checks A[-1] == last saved row."""
+    """tests/c/abi_gpu_client.c: a C99 program (no Python, no torch) runs a 257-point sweep with trajectories, the per-wave
+    sweep, the gain summary, one RHS evaluation, the dbeta producers and two-chunk sweep and chain trajectories through
+    libpsa_hip.so and checks A[-1] == last saved row."""
     import os
     import shutil
     import subprocess

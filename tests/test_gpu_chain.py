@@ -5,6 +5,7 @@
 * one fibre cut into 2, 3 and 7 spans with identity transfers is the unsplit run: a_end, p_max, the per-wave columns and
   the A-frame trajectory rows, for 4 and 6 waves, float64 and float32;
 * a lossy three-span chain with unequal dbeta, gamma, alpha and per-point transfers against the CPU oracle, span by span;
+* a chain trajectory that leaves the host-buffer API in two chunks (the second ragged) against the same oracle;
 * first_bad_step of a chain that fails in span 2 is cumulative (span 1's steps + the local exact index), and the NaN
   stays NaN in the gain;
 * devices=[0, 0] equals one device;
@@ -97,6 +98,22 @@ def test_identity_split_equals_the_unsplit_run(cuts, nw, dtype):
     assert np.all(got.first_bad_step == -1)
 
 
+def _oracle_rows(a0, spans_def, dbeta, transfers, se):
+    """One point, span by span through oracle.integrate in the B frame (boundary B' = T B with the signal times
+    e^{i dbeta_s L_s}) -> its A-frame rows.  spans_def: (L, n_steps, gamma, alpha) per span; dbeta: one value per span."""
+    theta, b, rows = 0.0, np.asarray(a0, dtype=complex).copy(), []
+    for k, (L, n, g, al) in enumerate(spans_def):
+        _, B, _ = oracle.integrate(b, z_max=L, n=n, save_every=se, gamma=g, alpha=al, dbeta=dbeta[k])
+        A = B.copy()
+        A[:, 2] *= np.exp(-1j * theta)
+        rows.append(A)
+        if k + 1 < len(spans_def):
+            b = B[-1] * transfers[k]
+            b[2] *= np.exp(1j * dbeta[k] * L)
+            theta += dbeta[k] * L
+    return np.concatenate(rows)
+
+
 def test_lossy_chain_with_transfers_against_the_oracle():
     n_pts, se = 9, 20
     rng = np.random.default_rng(7)
@@ -108,22 +125,35 @@ def test_lossy_chain_with_transfers_against_the_oracle():
     spans = [FibreSpan(L, n_steps=n, dbeta=d, gamma=g, alpha=al) for (L, n, g, al), d in zip(spans_def, dbs)]
     got = rk4_chain(spans, a0=a0, transfers=tr, save_every=se, want_traj=True)
     for i in range(n_pts):
-        theta, b, rows = 0.0, a0[i].copy(), []
-        for k, (L, n, g, al) in enumerate(spans_def):
-            _, B, _ = oracle.integrate(b, z_max=L, n=n, save_every=se, gamma=g, alpha=al, dbeta=dbs[k][i])
-            A = B.copy()
-            A[:, 2] *= np.exp(-1j * theta)
-            rows.append(A)
-            if k < 2:
-                t = tr[k][i] if tr[k].ndim == 2 else tr[k]
-                b = B[-1] * t
-                b[2] *= np.exp(1j * dbs[k][i] * L)
-                theta += dbs[k][i] * L
-        want = np.concatenate(rows)
+        want = _oracle_rows(a0[i], spans_def, [d[i] for d in dbs], [t[i] if t.ndim == 2 else t for t in tr], se)
         scale = np.max(np.abs(want), axis=0)
         assert np.max(np.abs(got.traj[i] - want) / scale) < 1e-9, i
         assert np.max(np.abs(got.a_end[i] - want[-1]) / scale) < 1e-9
         assert abs(got.p_max[i] - np.max(np.abs(want[:, 2]) ** 2)) <= 1e-9 * got.p_max[i]
+
+
+def test_chain_trajectory_leaves_the_device_in_chunks():
+    """Host-buffer chain: a 457 MB trajectory (70 001 points x 2 spans x 51 rows) leaves the device in two chunks through
+    the bounded staging buffers, the second one ragged, on the sweep's path (test_gpu_parity.py::
+    test_trajectory_leaves_the_device_in_chunks).  Rows of points on both sides of the chunk boundary against the per-span
+    oracle; a_end == last row everywhere."""
+    N, se = 70_001, 1
+    spans_def = [(10.0, 50, 0.0115, 1.15e-4), (8.0, 50, 0.02, 0.0)]
+    dbs = np.stack([np.linspace(-0.06, 0.06, N), np.linspace(0.03, -0.02, N)])
+    tr = mid_stage((0.0, 0.0, -1.0, -20.0), (0.5, 0.0, 0.0, 0.0))
+    a0 = _a0(4)
+    got = nat.chain_host(dbs, n_steps=[n for _, n, _, _ in spans_def], seg_len=[L for L, _, _, _ in spans_def],
+                         save_every=se, gamma=[g for _, _, g, _ in spans_def], alpha=[al for _, _, _, al in spans_def],
+                         a0=a0, transfers=tr[None], want_traj=True)
+    rows = sum(n // se + 1 for _, n, _, _ in spans_def)
+    assert got["traj"].shape == (N, rows, 4)
+    assert np.array_equal(got["traj"][:, -1, :], got["a_end"]) and np.all(got["traj"][:, 0, :] == a0)
+    boundary = (256 * 2**20 // (rows * 64)) // 32 * 32            # first point of the second chunk
+    assert boundary < N and (N - boundary) % 32
+    for i in (0, 31, 32, boundary - 1, boundary, boundary + 1, N - 2, N - 1):
+        want = _oracle_rows(a0, spans_def, dbs[:, i], [tr], se)
+        scale = np.max(np.abs(want), axis=0)
+        assert np.max(np.abs(got["traj"][i] - want) / scale) < 1e-9, i
 
 
 def test_run_concatenated_simulation_matches_the_single_run_when_split():

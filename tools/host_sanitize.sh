@@ -9,13 +9,13 @@ SRC=psa-simulation-ode-rk-mvp-dispersion_amd/csrc
 OUT=${TMPDIR:-/tmp}/psa_san
 mkdir -p "$OUT"
 SAN="-Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-omit-frame-pointer"
-for f in psa_rk4_f64 psa_rk4_f32 psa_aux psa_dbeta psa_capi; do
+for f in psa_rk4_f64 psa_rk4_f32 psa_aux psa_dbeta psa_chain psa_capi; do
   EXTRA=""
   [ $f = psa_dbeta ] && EXTRA="-ffp-contract=off"
   [ $f = psa_capi ] && EXTRA="-DPSA_FAULT_INJECTION"
   /opt/rocm/bin/hipcc -O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -Iinclude -I$SRC $SAN $EXTRA -c $SRC/$f.hip -o $OUT/$f.o
 done
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 $SAN -o $OUT/libpsa_hip.so $OUT/psa_rk4_f64.o $OUT/psa_rk4_f32.o $OUT/psa_aux.o $OUT/psa_dbeta.o $OUT/psa_capi.o
+/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 $SAN -o $OUT/libpsa_hip.so $OUT/psa_rk4_f64.o $OUT/psa_rk4_f32.o $OUT/psa_aux.o $OUT/psa_dbeta.o $OUT/psa_chain.o $OUT/psa_capi.o
 /opt/rocm/bin/hipcc -x c -std=c99 -Iinclude $SAN tests/c/abi_gpu_client.c -o $OUT/abi_gpu_client -L$OUT -lpsa_hip -Wl,-rpath,$OUT -lm
 export ASAN_OPTIONS=detect_leaks=0:protect_shadow_gap=0 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1
 echo "== host ASan + UBSan build of $(git rev-parse --short HEAD 2>/dev/null || echo HEAD): client, clean run"
