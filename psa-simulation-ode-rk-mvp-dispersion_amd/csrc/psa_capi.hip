@@ -91,11 +91,6 @@ int validate_common(int n_waves, int64_t n_points, int64_t n_steps, double z_max
     return PSA_OK;
 }
 
-int check_mode(uint32_t flags) {
-    if (!(flags & PSA_OPT_CHECK_NAN)) return psa::CHECK_NONE;
-    return (flags & PSA_OPT_EXACT_STEP) ? psa::CHECK_EXACT : psa::CHECK_BLOCK;
-}
-
 template <typename T>
 psa::SweepArgs<T> make_args(int n_waves, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
                             const T *dbeta, const T *dbeta2, const T *gamma, const T *alpha, const T *a0_soa,
@@ -128,33 +123,13 @@ psa::SweepArgs<T> make_args(int n_waves, int64_t n_points, int64_t n_steps, doub
 
 template <typename T> struct Launch;
 template <> struct Launch<double> {
-    static hipError_t sweep(hipStream_t s, int nw, int chk, bool lds, int blk, uint32_t flags,
-                            const psa::SweepArgs<double> &a) {
-        const int split = (flags & PSA_OPT_QUAD_POINT) ? 2 : ((flags & PSA_OPT_SPLIT_POINT) ? 1 : ((flags & PSA_OPT_ONE_LANE) ? 0 : -1));
-        return psa::launch_sweep_f64(s, nw, chk, lds, blk, (flags & PSA_OPT_LOSSLESS) != 0, split, a);
-    }
-    static int split_of(uint32_t flags) {
-        return (flags & PSA_OPT_QUAD_POINT) ? 2 : ((flags & PSA_OPT_SPLIT_POINT) ? 1 : ((flags & PSA_OPT_ONE_LANE) ? 0 : -1));
-    }
-    static hipError_t sweep_waves(hipStream_t s, int nw, int chk, uint32_t flags, const psa::SweepArgs<double> &a) {
-        return psa::launch_sweep_waves_f64(s, nw, chk, (flags & PSA_OPT_LOSSLESS) != 0, split_of(flags), a);
-    }
+    static constexpr auto sweep = psa::launch_sweep_f64;
     static hipError_t a2s(hipStream_t s, const double *a, double *b, long long n, int nc) { return psa::launch_aos_to_soa_f64(s, a, b, n, nc); }
     static hipError_t s2a(hipStream_t s, const double *a, double *b, long long n, int nc) { return psa::launch_soa_to_aos_f64(s, a, b, n, nc); }
     static hipError_t t2a(hipStream_t s, const double *a, double *b, long long n, long long ld, long long r, int nc) { return psa::launch_traj_to_aos_f64(s, a, b, n, ld, r, nc); }
 };
 template <> struct Launch<float> {
-    static hipError_t sweep(hipStream_t s, int nw, int chk, bool lds, int blk, uint32_t flags,
-                            const psa::SweepArgs<float> &a) {
-        const int pack = (flags & PSA_OPT_F32_PACKED) ? 1 : ((flags & PSA_OPT_F32_SCALAR) ? 0 : -1);
-        // the packed kernel has no lossless form: with the promise given, prefer it only when packing was forced
-        const bool lossless = (flags & PSA_OPT_LOSSLESS) != 0;
-        return psa::launch_sweep_f32(s, nw, chk, lds, blk, pack, lossless && pack == 0, a);
-    }
-    static hipError_t sweep_waves(hipStream_t s, int nw, int chk, uint32_t flags, const psa::SweepArgs<float> &a) {
-        const int pack = (flags & PSA_OPT_F32_PACKED) ? 1 : ((flags & PSA_OPT_F32_SCALAR) ? 0 : -1);
-        return psa::launch_sweep_waves_f32(s, nw, chk, pack, (flags & PSA_OPT_LOSSLESS) != 0 && pack == 0, a);
-    }
+    static constexpr auto sweep = psa::launch_sweep_f32;
     static hipError_t a2s(hipStream_t s, const float *a, float *b, long long n, int nc) { return psa::launch_aos_to_soa_f32(s, a, b, n, nc); }
     static hipError_t s2a(hipStream_t s, const float *a, float *b, long long n, int nc) { return psa::launch_soa_to_aos_f32(s, a, b, n, nc); }
     static hipError_t t2a(hipStream_t s, const float *a, float *b, long long n, long long ld, long long r, int nc) { return psa::launch_traj_to_aos_f32(s, a, b, n, ld, r, nc); }
@@ -182,15 +157,9 @@ int sweep_dev(void *stream, int n_waves, int64_t n_points, int64_t n_steps, doub
     if (n_points == 0) return PSA_OK;
     auto a = make_args<T>(n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha,
                           d_a0_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa);
-    hipError_t e;
-    if (d_wave_end) {
-        a.p_wave_end = d_wave_end;
-        a.p_wave_max = d_wave_max;
-        e = Launch<T>::sweep_waves((hipStream_t)stream, n_waves, check_mode(flags), flags, a);
-    } else {
-        e = Launch<T>::sweep((hipStream_t)stream, n_waves, check_mode(flags), (flags & PSA_OPT_LDS_STAGING) != 0,
-                             (flags & PSA_OPT_BLOCK64) ? 64 : 256, flags, a);
-    }
+    a.p_wave_end = d_wave_end;
+    a.p_wave_max = d_wave_max;
+    hipError_t e = Launch<T>::sweep((hipStream_t)stream, n_waves, flags, a);
     if (e != hipSuccess) return hip_fail(e, "rk4_sweep launch");
     return PSA_OK;
 }

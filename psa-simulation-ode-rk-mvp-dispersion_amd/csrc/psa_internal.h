@@ -33,17 +33,12 @@ struct SweepArgs {
 
 enum CheckMode : int { CHECK_NONE = 0, CHECK_BLOCK = 1, CHECK_EXACT = 2 };
 
-// launchers (defined in psa_rk4_f64.hip / psa_rk4_f32.hip)
-// lossless: the caller promises alpha == 0 for every point -> instantiation without the loss links
-// split: 1 two lanes per point, 2 four lanes per point (4 waves) -- float64 only --, 0 one lane per point, -1 auto (psa_rk4_f64.hip)
-hipError_t launch_sweep_f64(hipStream_t s, int n_waves, int check, bool lds, int block, bool lossless, int split,
-                            const SweepArgs<double> &a);
-hipError_t launch_sweep_f32(hipStream_t s, int n_waves, int check, bool lds, int block, int pack, bool lossless,
-                            const SweepArgs<float> &a);  // pack: 1 two points/lane, 0 one, -1 auto
-// the same sweeps with the per-wave summary (a.p_wave_end / a.p_wave_max): register layouts, no trajectory, the automatic
-// block sizes (256 threads for the one-lane and packed kernels)
-hipError_t launch_sweep_waves_f64(hipStream_t s, int n_waves, int check, bool lossless, int split, const SweepArgs<double> &a);
-hipError_t launch_sweep_waves_f32(hipStream_t s, int n_waves, int check, int pack, bool lossless, const SweepArgs<float> &a);
+// Sweep launchers (psa_rk4_f64.hip / psa_rk4_f32.hip): one kernel launch on s, nothing for n_points == 0.  They own
+// every launch-related PSA_OPT_* bit of `flags` (check mode, LDS staging, block size, LOSSLESS, the float64 lane layout,
+// float32 packing) and take the trajectory from a.traj and the per-wave summary from a.p_wave_end being non-null.  The
+// caller has validated the arguments (the per-wave summary: no trajectory, no LDS staging, no BLOCK64).
+hipError_t launch_sweep_f64(hipStream_t s, int n_waves, uint32_t flags, const SweepArgs<double> &a);
+hipError_t launch_sweep_f32(hipStream_t s, int n_waves, uint32_t flags, const SweepArgs<float> &a);
 
 // aux kernels (psa_aux.hip)
 hipError_t launch_aos_to_soa_f64(hipStream_t s, const double *aos, double *soa, long long n, int nc);

@@ -48,28 +48,27 @@ static int best_lanes_per_point(int n_waves, long long n_points, int simds) {
     return best;
 }
 
-// split: 1 = two lanes per point, 2 = four lanes per point (4 waves only), 0 = one, -1 = choose by the cost model above.
-hipError_t launch_sweep_f64(hipStream_t s, int n_waves, int check, bool lds, int block, bool lossless, int split,
-                            const SweepArgs<double> &a) {
+// Layout precedence: PSA_OPT_QUAD_POINT (4 waves only; one lane otherwise), PSA_OPT_SPLIT_POINT, PSA_OPT_ONE_LANE, then
+// the cost model above.  Multi-lane layouts exist for the register layout only, and a multi-lane trajectory launch folds
+// the lane's wave offset into the 32-bit store offset (NW * ld * 16 B < 2^32): otherwise one lane per point, forced or not.
+hipError_t launch_sweep_f64(hipStream_t s, int n_waves, uint32_t flags, const SweepArgs<double> &a) {
+    Pick p = pick_one_lane(n_waves, flags, a);
     const int simds = simd_count(s);
-    // a multi-lane trajectory launch folds the lane's wave offset into the 32-bit store offset: NW * ld * 16 B < 2^32
-    const bool multi_ok = !lds && (a.traj == nullptr || (unsigned long long)a.traj_ld * n_waves * 16ull < (1ull << 32));
+    const bool multi_ok = !p.lds && (!p.traj || (unsigned long long)a.traj_ld * n_waves * 16ull < (1ull << 32));
     int lanes = 1;
-    if (multi_ok) lanes = split == 1 ? 2 : (split == 2 && n_waves == 4 ? 4 : (split < 0 ? best_lanes_per_point(n_waves, a.n_points, simds) : 1));
-    if (lanes == 1) return launch_sweep_t<double>(s, n_waves, check, lds, block, lossless, a);
-    // 64-thread workgroups while the sweep's waves fit half the SIMDs (spread over as many CUs as it has waves), 256 beyond
+    if (multi_ok && !(flags & PSA_OPT_ONE_LANE)) {
+        if (flags & PSA_OPT_QUAD_POINT) lanes = n_waves == 4 ? 4 : 1;
+        else if (flags & PSA_OPT_SPLIT_POINT) lanes = 2;
+        else lanes = best_lanes_per_point(n_waves, a.n_points, simds);
+    }
+    if (lanes == 1) return launch_family<OneLane<double>>(s, p, a);
+    // 64-thread workgroups while the sweep's waves fit half the SIMDs (a sweep of few waves is spread over as many CUs as
+    // it has waves), 256 beyond (four waves per workgroup land on the four SIMDs of one CU: the placement that gives every
+    // wave its own SIMD when the sweep fills the chip -- 1 024 single-wave workgroups measured 12 % slower at N = 32 768
+    // because some SIMDs received two)
     const long long waves = ((long long)lanes * a.n_points + 63) / 64;
-    const int sb = (block == 64 || 2 * waves <= (long long)simds) ? 64 : 256;
-    return lanes == 2 ? launch_sweep_split(s, n_waves, check, lossless, sb, a) : launch_sweep_quad(s, check, lossless, sb, a);
-}
-
-// The same layout choice with the per-wave summary (register layouts, no trajectory: launch_sweep_f64 with lds = false,
-// traj = nullptr, block = 256).
-hipError_t launch_sweep_waves_f64(hipStream_t s, int n_waves, int check, bool lossless, int split, const SweepArgs<double> &a) {
-    const int lanes = split == 1 ? 2 : (split == 2 && n_waves == 4 ? 4 : (split < 0 ? best_lanes_per_point(n_waves, a.n_points, simd_count(s)) : 1));
-    if (lanes == 1) return launch_waves_t<double>(s, n_waves, check, lossless, a);
-    const long long waves = ((long long)lanes * a.n_points + 63) / 64;
-    const int sb = (2 * waves <= (long long)simd_count(s)) ? 64 : 256;
-    return lanes == 2 ? launch_sweep_split_waves(s, n_waves, check, lossless, sb, a) : launch_sweep_quad_waves(s, check, lossless, sb, a);
+    p.block = ((flags & PSA_OPT_BLOCK64) || 2 * waves <= (long long)simds) ? 64 : 256;
+    p.lossless = (flags & PSA_OPT_LOSSLESS) != 0;
+    return lanes == 2 ? launch_family<SplitLanes>(s, p, a) : launch_family<QuadLanes>(s, p, a);
 }
 }  // namespace psa

@@ -20,7 +20,10 @@
 // The independent variable follows the reference grid: z_i = i * (z_max / n_steps)
 // (np.linspace, integrators.py:195) formed from the INTEGER step index, never accumulated.
 #pragma once
+#include <type_traits>
+
 #include "psa_internal.h"
+#include "psa_rk4.h"
 
 namespace psa {
 
@@ -550,79 +553,73 @@ __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(
     write_summary();
 }
 
-template <typename T, int NW, int CHECK, bool TRAJ>
-static hipError_t launch_one(hipStream_t s, int block, bool lds, bool lossless, const SweepArgs<T> &a) {
+// One lane per point.  LDS staging (an A/B variant: 5 * 2*NW * 64 * sizeof(T) bytes of LDS, 20 KB for f64 with 4 waves)
+// is one 64-thread wave per workgroup with the loss links; the per-wave summary is register-only, without trajectory,
+// in 256-thread workgroups.
+template <typename T> struct OneLane {
+    static long long lanes(long long n_points) { return n_points; }
+    template <int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS, bool LOSS, bool WSUM>
+    static constexpr auto kernel() {
+        if constexpr ((WSUM && (TRAJ || LDS || BLOCK != 256)) || (LDS && (BLOCK != 64 || !LOSS))) return nullptr;
+        else return rk4_sweep_kernel<T, NW, CHECK, TRAJ, BLOCK, LDS, LOSS, WSUM>;
+    }
+};
+
+// ---- the one launch path of every sweep kernel family (OneLane, SplitLanes, QuadLanes, PackedPoints) ------------
+// The layout choice (launch_sweep_f64 / launch_sweep_f32) fills a Pick; launch_family turns its runtime values into
+// template arguments once.  A family says how many lanes its launch takes and which instantiations exist: a
+// combination that does not is never named, so the set of compiled kernels is exactly the families' own.
+struct Pick {
+    int n_waves, check, block;  // 4 | 6, CheckMode, 64 | 256
+    bool traj, lds, lossless, wsum;
+};
+
+// What every layout shares, filled for one lane per point: the check mode, trajectory and per-wave summary (from the
+// buffers), LDS staging and BLOCK64 (LDS staging is always 64 threads; BLOCK64 is rejected with the per-wave summary,
+// so those launches get 256), and LOSSLESS -- the caller's promise that alpha == 0 for every point, which compiles the
+// 8 loss links per RHS out -- for the register layout only.
+template <typename T>
+static Pick pick_one_lane(int n_waves, uint32_t flags, const SweepArgs<T> &a) {
+    Pick p;
+    p.n_waves = n_waves;
+    p.check = !(flags & PSA_OPT_CHECK_NAN) ? CHECK_NONE : ((flags & PSA_OPT_EXACT_STEP) ? CHECK_EXACT : CHECK_BLOCK);
+    p.traj = a.traj != nullptr;
+    p.wsum = a.p_wave_end != nullptr;
+    p.lds = (flags & PSA_OPT_LDS_STAGING) != 0;
+    p.lossless = (flags & PSA_OPT_LOSSLESS) && !p.lds;
+    p.block = (p.lds || (flags & PSA_OPT_BLOCK64)) ? 64 : 256;
+    return p;
+}
+
+// f(std::integral_constant<int, V>{}) for the V equal to v -- the last one when none is
+template <int V, int... Vs, typename F>
+static hipError_t with_int(int v, F &&f) {
+    if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V>{});
+    else return v == V ? f(std::integral_constant<int, V>{}) : with_int<Vs...>(v, f);
+}
+template <typename F>
+static hipError_t with_bool(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+template <typename Family, typename T>
+static hipError_t launch_family(hipStream_t s, const Pick &p, const SweepArgs<T> &a) {
     if (a.n_points == 0) return hipSuccess;
-    if (lossless && !lds) {  // alpha == 0 for every point (caller's promise): the 8 loss links per RHS are compiled out
-        if (block == 64) {
-            hipLaunchKernelGGL((rk4_sweep_kernel<T, NW, CHECK, TRAJ, 64, false, false>), dim3((unsigned)((a.n_points + 63) / 64)),
-                               dim3(64), 0, s, a);
-        } else {
-            hipLaunchKernelGGL((rk4_sweep_kernel<T, NW, CHECK, TRAJ, 256, false, false>),
-                               dim3((unsigned)((a.n_points + 255) / 256)), dim3(256), 0, s, a);
+    const dim3 grid((unsigned)((Family::lanes(a.n_points) + p.block - 1) / p.block)), block(p.block);
+    return with_int<4, 6>(p.n_waves, [&](auto nw) {
+    return with_int<CHECK_NONE, CHECK_BLOCK, CHECK_EXACT>(p.check, [&](auto check) {
+    return with_int<64, 256>(p.block, [&](auto blk) {
+    return with_bool(p.traj, [&](auto traj) {
+    return with_bool(p.lds, [&](auto lds) {
+    return with_bool(p.lossless, [&](auto lossless) {
+    return with_bool(p.wsum, [&](auto wsum) {
+        constexpr auto k = Family::template kernel<nw, check, traj, blk, lds, !lossless, wsum>();
+        if constexpr (std::is_null_pointer_v<std::remove_const_t<decltype(k)>>) {
+            return hipErrorInvalidDeviceFunction;   // no such instantiation: the layout choice never picks one
+        } else {   // by the kernel's address: a <<< >>> call through a pointer is lost in the host-sanitizer build
+            void *args[] = {const_cast<SweepArgs<T> *>(&a)};
+            (void)hipLaunchKernel(reinterpret_cast<const void *>(k), grid, block, args, 0, s);
+            return hipGetLastError();
         }
-        return hipGetLastError();
-    }
-    if (lds) {  // A/B variant: one wave per workgroup, 5 * 2*NW * 64 * sizeof(T) bytes of LDS (20 KB for f64, 4 waves)
-        const unsigned grid = (unsigned)((a.n_points + 63) / 64);
-        hipLaunchKernelGGL((rk4_sweep_kernel<T, NW, CHECK, TRAJ, 64, true>), dim3(grid), dim3(64), 0, s, a);
-        return hipGetLastError();
-    }
-    if (block == 64) {
-        const unsigned grid = (unsigned)((a.n_points + 63) / 64);
-        hipLaunchKernelGGL((rk4_sweep_kernel<T, NW, CHECK, TRAJ, 64>), dim3(grid), dim3(64), 0, s, a);
-    } else {
-        const unsigned grid = (unsigned)((a.n_points + 255) / 256);
-        hipLaunchKernelGGL((rk4_sweep_kernel<T, NW, CHECK, TRAJ, 256>), dim3(grid), dim3(256), 0, s, a);
-    }
-    return hipGetLastError();
-}
-
-template <typename T, int NW>
-static hipError_t launch_nw(hipStream_t s, int check, int block, bool lds, bool lossless, const SweepArgs<T> &a) {
-    const bool traj = a.traj != nullptr;
-    switch (check) {
-        case CHECK_NONE:
-            return traj ? launch_one<T, NW, CHECK_NONE, true>(s, block, lds, lossless, a)
-                        : launch_one<T, NW, CHECK_NONE, false>(s, block, lds, lossless, a);
-        case CHECK_BLOCK:
-            return traj ? launch_one<T, NW, CHECK_BLOCK, true>(s, block, lds, lossless, a)
-                        : launch_one<T, NW, CHECK_BLOCK, false>(s, block, lds, lossless, a);
-        default:
-            return traj ? launch_one<T, NW, CHECK_EXACT, true>(s, block, lds, lossless, a)
-                        : launch_one<T, NW, CHECK_EXACT, false>(s, block, lds, lossless, a);
-    }
-}
-
-template <typename T>
-static hipError_t launch_sweep_t(hipStream_t s, int n_waves, int check, bool lds, int block, bool lossless,
-                                 const SweepArgs<T> &a) {
-    if (n_waves == 4) return launch_nw<T, 4>(s, check, block, lds, lossless, a);
-    return launch_nw<T, 6>(s, check, block, lds, lossless, a);
-}
-
-// the per-wave summary (WSUM): register layout, no trajectory, 256-thread workgroups -- the automatic choice's block
-template <typename T, int NW, int CHECK>
-static hipError_t launch_waves_one(hipStream_t s, bool lossless, const SweepArgs<T> &a) {
-    if (a.n_points == 0) return hipSuccess;
-    const dim3 grid((unsigned)((a.n_points + 255) / 256));
-    if (lossless) hipLaunchKernelGGL((rk4_sweep_kernel<T, NW, CHECK, false, 256, false, false, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((rk4_sweep_kernel<T, NW, CHECK, false, 256, false, true, true>), grid, dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-template <typename T, int NW>
-static hipError_t launch_waves_nw(hipStream_t s, int check, bool lossless, const SweepArgs<T> &a) {
-    switch (check) {
-        case CHECK_NONE: return launch_waves_one<T, NW, CHECK_NONE>(s, lossless, a);
-        case CHECK_BLOCK: return launch_waves_one<T, NW, CHECK_BLOCK>(s, lossless, a);
-        default: return launch_waves_one<T, NW, CHECK_EXACT>(s, lossless, a);
-    }
-}
-
-template <typename T>
-static hipError_t launch_waves_t(hipStream_t s, int n_waves, int check, bool lossless, const SweepArgs<T> &a) {
-    return n_waves == 4 ? launch_waves_nw<T, 4>(s, check, lossless, a) : launch_waves_nw<T, 6>(s, check, lossless, a);
+    }); }); }); }); }); }); });
 }
 
 }  // namespace psa

@@ -290,53 +290,15 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_pk_kernel(const SweepArgs<flo
     write_summary();
 }
 
-template <int NW, int CHECK, bool TRAJ>
-static hipError_t launch_pk_one(hipStream_t s, int block, const SweepArgs<float> &a) {
-    const long long lanes = (a.n_points + 1) / 2;
-    if (block == 64) {
-        hipLaunchKernelGGL((rk4_sweep_pk_kernel<NW, CHECK, TRAJ, 64>), dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, s, a);
-    } else {
-        hipLaunchKernelGGL((rk4_sweep_pk_kernel<NW, CHECK, TRAJ, 256>), dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, a);
+// Two float32 points per lane: register layout with the loss links only (no lossless form); the per-wave summary
+// without trajectory, in 256-thread workgroups.
+struct PackedPoints {
+    static long long lanes(long long n_points) { return (n_points + 1) / 2; }
+    template <int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS, bool LOSS, bool WSUM>
+    static constexpr auto kernel() {
+        if constexpr (LDS || !LOSS || (WSUM && (TRAJ || BLOCK != 256))) return nullptr;
+        else return rk4_sweep_pk_kernel<NW, CHECK, TRAJ, BLOCK, WSUM>;
     }
-    return hipGetLastError();
-}
-
-template <int NW>
-static hipError_t launch_pk_nw(hipStream_t s, int check, int block, const SweepArgs<float> &a) {
-    const bool traj = a.traj != nullptr;
-    switch (check) {
-        case CHECK_NONE:
-            return traj ? launch_pk_one<NW, CHECK_NONE, true>(s, block, a) : launch_pk_one<NW, CHECK_NONE, false>(s, block, a);
-        case CHECK_BLOCK:
-            return traj ? launch_pk_one<NW, CHECK_BLOCK, true>(s, block, a) : launch_pk_one<NW, CHECK_BLOCK, false>(s, block, a);
-        default:
-            return traj ? launch_pk_one<NW, CHECK_EXACT, true>(s, block, a) : launch_pk_one<NW, CHECK_EXACT, false>(s, block, a);
-    }
-}
-
-static hipError_t launch_sweep_pk(hipStream_t s, int n_waves, int check, int block, const SweepArgs<float> &a) {
-    if (a.n_points == 0) return hipSuccess;
-    return n_waves == 4 ? launch_pk_nw<4>(s, check, block, a) : launch_pk_nw<6>(s, check, block, a);
-}
-
-// the per-wave summary (WSUM): no trajectory, 256-thread workgroups
-template <int NW, int CHECK>
-static hipError_t launch_pk_waves_one(hipStream_t s, const SweepArgs<float> &a) {
-    const long long lanes = (a.n_points + 1) / 2;
-    hipLaunchKernelGGL((rk4_sweep_pk_kernel<NW, CHECK, false, 256, true>), dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-template <int NW>
-static hipError_t launch_pk_waves_nw(hipStream_t s, int check, const SweepArgs<float> &a) {
-    switch (check) {
-        case CHECK_NONE: return launch_pk_waves_one<NW, CHECK_NONE>(s, a);
-        case CHECK_BLOCK: return launch_pk_waves_one<NW, CHECK_BLOCK>(s, a);
-        default: return launch_pk_waves_one<NW, CHECK_EXACT>(s, a);
-    }
-}
-static hipError_t launch_sweep_pk_waves(hipStream_t s, int n_waves, int check, const SweepArgs<float> &a) {
-    if (a.n_points == 0) return hipSuccess;
-    return n_waves == 4 ? launch_pk_waves_nw<4>(s, check, a) : launch_pk_waves_nw<6>(s, check, a);
-}
+};
 
 }  // namespace psa

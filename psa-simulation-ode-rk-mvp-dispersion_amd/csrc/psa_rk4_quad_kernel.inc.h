@@ -268,43 +268,14 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_quad_kernel(const SweepArgs<d
     write_summary();
 }
 
-template <int CHECK, bool TRAJ, bool WSUM = false>
-static hipError_t launch_quad_one(hipStream_t s, bool lossless, int block, const SweepArgs<double> &a) {
-    const long long lanes = 4 * a.n_points;
-    if (block == 256) {
-        const dim3 grid((unsigned)((lanes + 255) / 256));
-        if (lossless) hipLaunchKernelGGL((rk4_sweep_quad_kernel<CHECK, TRAJ, 256, false, WSUM>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((rk4_sweep_quad_kernel<CHECK, TRAJ, 256, true, WSUM>), grid, dim3(256), 0, s, a);
-    } else {
-        const dim3 grid((unsigned)((lanes + 63) / 64));
-        if (lossless) hipLaunchKernelGGL((rk4_sweep_quad_kernel<CHECK, TRAJ, 64, false, WSUM>), grid, dim3(64), 0, s, a);
-        else hipLaunchKernelGGL((rk4_sweep_quad_kernel<CHECK, TRAJ, 64, true, WSUM>), grid, dim3(64), 0, s, a);
+// Four lanes per point: the 4-wave model's register layout only; the per-wave summary without trajectory.
+struct QuadLanes {
+    static long long lanes(long long n_points) { return 4 * n_points; }
+    template <int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS, bool LOSS, bool WSUM>
+    static constexpr auto kernel() {
+        if constexpr (NW != 4 || LDS || (WSUM && TRAJ)) return nullptr;
+        else return rk4_sweep_quad_kernel<CHECK, TRAJ, BLOCK, LOSS, WSUM>;
     }
-    return hipGetLastError();
-}
-
-// 4-wave model only.  block: 64 | 256 as for launch_sweep_split.
-static hipError_t launch_sweep_quad(hipStream_t s, int check, bool lossless, int block, const SweepArgs<double> &a) {
-    if (a.n_points == 0) return hipSuccess;
-    const bool traj = a.traj != nullptr;
-    switch (check) {
-        case CHECK_NONE:
-            return traj ? launch_quad_one<CHECK_NONE, true>(s, lossless, block, a) : launch_quad_one<CHECK_NONE, false>(s, lossless, block, a);
-        case CHECK_BLOCK:
-            return traj ? launch_quad_one<CHECK_BLOCK, true>(s, lossless, block, a) : launch_quad_one<CHECK_BLOCK, false>(s, lossless, block, a);
-        default:
-            return traj ? launch_quad_one<CHECK_EXACT, true>(s, lossless, block, a) : launch_quad_one<CHECK_EXACT, false>(s, lossless, block, a);
-    }
-}
-
-// the per-wave summary (WSUM), no trajectory
-static hipError_t launch_sweep_quad_waves(hipStream_t s, int check, bool lossless, int block, const SweepArgs<double> &a) {
-    if (a.n_points == 0) return hipSuccess;
-    switch (check) {
-        case CHECK_NONE: return launch_quad_one<CHECK_NONE, false, true>(s, lossless, block, a);
-        case CHECK_BLOCK: return launch_quad_one<CHECK_BLOCK, false, true>(s, lossless, block, a);
-        default: return launch_quad_one<CHECK_EXACT, false, true>(s, lossless, block, a);
-    }
-}
+};
 
 }  // namespace psa

@@ -405,54 +405,14 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_split_kernel(const SweepArgs<
     }
 }
 
-template <int NW, int CHECK, bool TRAJ, bool WSUM = false>
-static hipError_t launch_split_one(hipStream_t s, bool lossless, int block, const SweepArgs<double> &a) {
-    const long long lanes = 2 * a.n_points;
-    if (block == 256) {
-        const dim3 grid((unsigned)((lanes + 255) / 256));
-        if (lossless) hipLaunchKernelGGL((rk4_sweep_split_kernel<NW, CHECK, TRAJ, 256, false, WSUM>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((rk4_sweep_split_kernel<NW, CHECK, TRAJ, 256, true, WSUM>), grid, dim3(256), 0, s, a);
-    } else {
-        const dim3 grid((unsigned)((lanes + 63) / 64));
-        if (lossless) hipLaunchKernelGGL((rk4_sweep_split_kernel<NW, CHECK, TRAJ, 64, false, WSUM>), grid, dim3(64), 0, s, a);
-        else hipLaunchKernelGGL((rk4_sweep_split_kernel<NW, CHECK, TRAJ, 64, true, WSUM>), grid, dim3(64), 0, s, a);
+// Two lanes per point: register layout only; the per-wave summary without trajectory.
+struct SplitLanes {
+    static long long lanes(long long n_points) { return 2 * n_points; }
+    template <int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS, bool LOSS, bool WSUM>
+    static constexpr auto kernel() {
+        if constexpr (LDS || (WSUM && TRAJ)) return nullptr;
+        else return rk4_sweep_split_kernel<NW, CHECK, TRAJ, BLOCK, LOSS, WSUM>;
     }
-    return hipGetLastError();
-}
-
-template <int NW>
-static hipError_t launch_split_nw(hipStream_t s, int check, bool lossless, int block, const SweepArgs<double> &a) {
-    const bool traj = a.traj != nullptr;
-    switch (check) {
-        case CHECK_NONE:
-            return traj ? launch_split_one<NW, CHECK_NONE, true>(s, lossless, block, a) : launch_split_one<NW, CHECK_NONE, false>(s, lossless, block, a);
-        case CHECK_BLOCK:
-            return traj ? launch_split_one<NW, CHECK_BLOCK, true>(s, lossless, block, a) : launch_split_one<NW, CHECK_BLOCK, false>(s, lossless, block, a);
-        default:
-            return traj ? launch_split_one<NW, CHECK_EXACT, true>(s, lossless, block, a) : launch_split_one<NW, CHECK_EXACT, false>(s, lossless, block, a);
-    }
-}
-
-// block: 64 (one wave per workgroup: a sweep of few waves is spread over as many CUs as it has waves) or 256 (four waves
-// per workgroup land on the four SIMDs of one CU: the placement that gives every wave its own SIMD when the sweep fills
-// the chip -- 1 024 single-wave workgroups measured 12 % slower at N = 32 768 because some SIMDs received two).
-static hipError_t launch_sweep_split(hipStream_t s, int n_waves, int check, bool lossless, int block, const SweepArgs<double> &a) {
-    if (a.n_points == 0) return hipSuccess;
-    return n_waves == 4 ? launch_split_nw<4>(s, check, lossless, block, a) : launch_split_nw<6>(s, check, lossless, block, a);
-}
-
-// the per-wave summary (WSUM), no trajectory
-template <int NW>
-static hipError_t launch_split_waves_nw(hipStream_t s, int check, bool lossless, int block, const SweepArgs<double> &a) {
-    switch (check) {
-        case CHECK_NONE: return launch_split_one<NW, CHECK_NONE, false, true>(s, lossless, block, a);
-        case CHECK_BLOCK: return launch_split_one<NW, CHECK_BLOCK, false, true>(s, lossless, block, a);
-        default: return launch_split_one<NW, CHECK_EXACT, false, true>(s, lossless, block, a);
-    }
-}
-static hipError_t launch_sweep_split_waves(hipStream_t s, int n_waves, int check, bool lossless, int block, const SweepArgs<double> &a) {
-    if (a.n_points == 0) return hipSuccess;
-    return n_waves == 4 ? launch_split_waves_nw<4>(s, check, lossless, block, a) : launch_split_waves_nw<6>(s, check, lossless, block, a);
-}
+};
 
 }  // namespace psa
