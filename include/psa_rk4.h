@@ -53,6 +53,8 @@ extern "C" {
 #define PSA_E_TOO_LARGE  -9   /* trajectory does not fit (int64 / device memory), or n_points exceeds the launch grid */
 #define PSA_E_DBETA_MODEL -10 /* dbeta producer: unknown method, bad even_orders / max_order / beta count  */
 #define PSA_E_FLAGS      -11  /* options that exclude each other (two of SPLIT_POINT / ONE_LANE / QUAD_POINT, F32_SCALAR + F32_PACKED, QUAD with 6 waves) */
+#define PSA_E_TOL        -12  /* psa_rk45_*: rtol < 100*DBL_EPSILON or not finite, atol <= 0 or not finite, h_max <= 0,
+                                 first_step < 0 or not finite, max_steps < 1, n_out < 0 */
 
 /* The most points one launch takes: a launch has at most 2^32 - 1 threads in x and the two-lane float64 layout uses two
  * per point.  (2^31 - 256 float64 records are 189 GB: a 288 GB MI355X holds them, so the limit is stated, not theoretical.) */
@@ -333,6 +335,43 @@ int psa_dbeta_pairs_f32_dev(void *stream, const int32_t *even_orders, int n_even
 int psa_dbeta_pairs_f64(int device, const int32_t *even_orders, int n_even_orders, const double *beta, int n_beta,
                         double omega_d, const double *Omega1_axis, int64_t n1, const double *Omega2_axis, int64_t n2,
                         int64_t first_index, int64_t n_points, double *dbeta1, double *dbeta2);
+
+/* ---- the adaptive sweep: embedded Dormand-Prince 5(4) with per-point step-size control ------------------------
+ * The same N independent propagations as psa_rk4_sweep_f64, integrated to a tolerance instead of on a fixed grid:
+ * scipy.integrate.RK45 (scipy 1.15) step for step on the complex state A[n_waves], one sweep point per lane, each point
+ * with its own step size and step count.  float64 only, 4 and 6 waves.
+ *   rtol, atol   error norm = RMS over the n_waves complex components of err_j / (atol + rtol * max(|y_j|, |y_new_j|))
+ *   h_max        cap of every step (INFINITY: none)
+ *   first_step   0: scipy's select_initial_step (two RHS evaluations); otherwise the first step.  Unlike scipy, which
+ *                raises for first_step > z_max, a larger value is accepted and behaves as first_step = z_max (the
+ *                first step's end is clamped onto z_max, and the next step grows from that step)
+ *   max_steps    attempts (accepted + rejected) per point; the hard bound of every lane's loop
+ *   n_out        dense-output rows at z_k = k * (z_max / n_out), k = 0..n_out (np.linspace(0, z_max, n_out + 1)), from
+ *                RK45's quartic interpolant; row 0 is a0; rows past z_end are NaN.  Only with traj_or_null.
+ *   flags        PSA_BCAST_GAMMA / ALPHA / A0 and PSA_OPT_LOSSLESS (set automatically for a broadcast alpha == 0 by the
+ *                host form); anything else is PSA_E_FLAGS
+ * Per point:
+ *   a_end_re_im [N][n_waves][2]  the state at z_end;  p_sig_end [N]  |A_sig|^2 there
+ *   p_sig_max   [N]  max of |A_sig|^2 over z = 0 and every accepted step end (NaN-propagating)
+ *   status      [N]  0 reached z_max; 1 the step fell below 10 * ulp(z) (a non-finite state ends here; a non-finite a0
+ *                    at z = 0 with no step); 2 max_steps attempts used up
+ *   z_end       [N]  the z reached (z_max when status == 0);  n_accepted / n_rejected [N]  attempts of each kind
+ *   traj_or_null [N][n_out + 1][n_waves][2]  the dense-output rows, or NULL; subject to the trajectory limits
+ * The other argument rules and error codes are those of psa_rk4_sweep_f64.
+ */
+int psa_rk45_sweep_f64(int device, int n_waves, int64_t n_points, double z_max, double rtol, double atol, double h_max,
+                       double first_step, int64_t max_steps, int64_t n_out, const double *dbeta, const double *dbeta2,
+                       const double *gamma, const double *alpha, const double *a0_re_im, uint32_t flags,
+                       double *a_end_re_im, double *p_sig_end, double *p_sig_max, int32_t *status, double *z_end,
+                       int64_t *n_accepted, int64_t *n_rejected, double *traj_or_null, double *elapsed_ms_or_null);
+/* On device buffers, asynchronous on `stream`, no allocation (graph-capturable): SoA as psa_rk4_sweep_f64_dev;
+ * d_traj_soa [n_out + 1][n_waves][N][2] or NULL. */
+int psa_rk45_sweep_f64_dev(void *stream, int n_waves, int64_t n_points, double z_max, double rtol, double atol,
+                           double h_max, double first_step, int64_t max_steps, int64_t n_out, const double *d_dbeta,
+                           const double *d_dbeta2, const double *d_gamma, const double *d_alpha, const double *d_a0_soa,
+                           uint32_t flags, double *d_a_end_soa, double *d_p_sig_end, double *d_p_sig_max,
+                           int32_t *d_status, double *d_z_end, int64_t *d_n_accepted, int64_t *d_n_rejected,
+                           double *d_traj_soa);
 
 #ifdef __cplusplus
 }

@@ -77,6 +77,12 @@ _SIGS = {
     "psa_rk4_chain_f32_dev": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, _P, _P, C.c_int32] + [_P] * 6
                               + [C.c_uint32] + [_P] * 8),
     "psa_rk4_chain_workspace_bytes": (C.c_int64, [C.c_int, C.c_int64, C.c_int32, C.c_int]),
+    # (device|stream, n_waves, N, z_max, rtol, atol, h_max, first_step, max_steps, n_out, dbeta, dbeta2, gamma, alpha, a0,
+    #  flags, a_end, p_end, p_max, status, z_end, n_accepted, n_rejected, traj [, elapsed_ms])
+    "psa_rk45_sweep_f64": (C.c_int, [C.c_int, C.c_int, C.c_int64] + [C.c_double] * 5 + [C.c_int64, C.c_int64]
+                           + [_P] * 5 + [C.c_uint32] + [_P] * 9),
+    "psa_rk45_sweep_f64_dev": (C.c_int, [_P, C.c_int, C.c_int64] + [C.c_double] * 5 + [C.c_int64, C.c_int64]
+                               + [_P] * 5 + [C.c_uint32] + [_P] * 8),
     "psa_yaman_rhs_f64": (C.c_int, [C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "psa_gain_summary_f64": (C.c_int, [C.c_int, C.c_int64, _P, _P, C.c_double, C.c_int, _P, _P, _P, _P]),
     "psa_gain_summary_f64_dev": (C.c_int, [_P, C.c_int64, _P, _P, C.c_double, C.c_int, _P, _P, _P, _P, _P]),
@@ -394,6 +400,71 @@ def chain_device(*, stream: int, n_waves: int, n_points: int, n_steps, seg_len, 
               int(save_every), d_dbeta or None, d_dbeta2 or None, d_gamma or None, d_alpha or None, d_a0_soa or None,
               d_transfer_soa or None, int(flags), d_a_end_soa or None, d_p_end or None, d_p_max or None,
               d_first_bad or None, d_traj_soa or None, d_p_wave_end or None, d_p_wave_max or None, d_workspace or None))
+
+
+def rk45_sweep_host(dbeta, *, z_max: float, rtol: float, atol: float, h_max: float = float("inf"),
+                    first_step: float = 0.0, max_steps: int = 1_000_000, n_out: int = 0, gamma, alpha, a0, dbeta2=None,
+                    device: int = 0, extra_flags: int = 0) -> dict:
+    """N independent adaptive (RK45) propagations on the GPU (psa_rk45_sweep_f64; host buffers in and out, float64).
+
+    dbeta (N,); gamma / alpha scalar or (N,); a0 (n_waves,) or (N, n_waves) complex.  n_out > 0 also returns the
+    dense-output rows traj (N, n_out + 1, n_waves) at np.linspace(0, z_max, n_out + 1).
+    Returns a_end (N, n_waves) complex, p_end, p_max, z_end (N,), status (N,) int32, n_accepted, n_rejected (N,) int64,
+    traj or None, elapsed_ms (kernel only)."""
+    dbeta = np.ascontiguousarray(np.atleast_1d(np.asarray(dbeta)), dtype=np.float64)
+    if dbeta.ndim != 1:
+        raise ValueError("dbeta must be 1-D")
+    N = int(dbeta.shape[0])
+    a0 = np.ascontiguousarray(np.asarray(a0), dtype=np.complex128)
+    if a0.ndim == 1:
+        a0 = a0[None, :]
+    if a0.ndim != 2 or a0.shape[1] not in (4, 6):
+        raise ValueError("a0 must have shape (n_waves,) or (N, n_waves) with n_waves in (4, 6)")
+    nw = int(a0.shape[1])
+    flags = int(extra_flags)
+    if a0.shape[0] == 1:
+        flags |= BCAST_A0
+    elif a0.shape[0] != N:
+        raise ValueError(f"a0 must have 1 or {N} rows, got {a0.shape[0]}")
+    gamma, gb = _prep(gamma, np.float64, N, "gamma")
+    alpha, ab = _prep(alpha, np.float64, N, "alpha")
+    flags |= (BCAST_GAMMA if gb else 0) | (BCAST_ALPHA if ab else 0)
+    d2 = None
+    if nw == 6:
+        if dbeta2 is None:
+            raise ValueError("n_waves == 6 needs dbeta2")
+        d2 = np.ascontiguousarray(np.atleast_1d(np.asarray(dbeta2)), dtype=np.float64)
+        if d2.shape != dbeta.shape:
+            raise ValueError("dbeta2 must match dbeta")
+    elif dbeta2 is not None:
+        raise ValueError("dbeta2 is only meaningful for 6 waves")
+    n_out = int(n_out)
+    a_end = np.empty((N, nw), dtype=np.complex128)
+    p_end, p_max, z_end = (np.empty(N, dtype=np.float64) for _ in range(3))
+    status = np.empty(N, dtype=np.int32)
+    n_acc, n_rej = np.empty(N, dtype=np.int64), np.empty(N, dtype=np.int64)
+    traj = np.empty((N, n_out + 1, nw), dtype=np.complex128) if n_out > 0 else None
+    ms = C.c_double(0.0)
+    _check(lib().psa_rk45_sweep_f64(int(device), nw, N, float(z_max), float(rtol), float(atol), float(h_max),
+                                    float(first_step), int(max_steps), n_out, _ptr(dbeta), _ptr(d2), _ptr(gamma),
+                                    _ptr(alpha), _ptr(a0), flags, _ptr(a_end), _ptr(p_end), _ptr(p_max), _ptr(status),
+                                    _ptr(z_end), _ptr(n_acc), _ptr(n_rej), _ptr(traj), C.cast(C.byref(ms), C.c_void_p)))
+    return dict(a_end=a_end, p_end=p_end, p_max=p_max, status=status, z_end=z_end, n_accepted=n_acc,
+                n_rejected=n_rej, traj=traj, elapsed_ms=ms.value)
+
+
+def rk45_sweep_device(*, stream: int, n_waves: int, n_points: int, z_max: float, rtol: float, atol: float,
+                      h_max: float, first_step: float, max_steps: int, n_out: int, d_dbeta: int, d_dbeta2: int,
+                      d_gamma: int, d_alpha: int, d_a0_soa: int, flags: int, d_a_end_soa: int, d_p_end: int,
+                      d_p_max: int, d_status: int, d_z_end: int, d_n_accepted: int, d_n_rejected: int,
+                      d_traj_soa: int = 0) -> None:
+    """Asynchronous adaptive launch on device pointers (ints), SoA layout -- see psa_rk45_sweep_f64_dev."""
+    _check(lib().psa_rk45_sweep_f64_dev(stream or None, int(n_waves), int(n_points), float(z_max), float(rtol),
+                                        float(atol), float(h_max), float(first_step), int(max_steps), int(n_out),
+                                        d_dbeta or None, d_dbeta2 or None, d_gamma or None, d_alpha or None,
+                                        d_a0_soa or None, int(flags), d_a_end_soa or None, d_p_end or None,
+                                        d_p_max or None, d_status or None, d_z_end or None, d_n_accepted or None,
+                                        d_n_rejected or None, d_traj_soa or None))
 
 
 def yaman_rhs_host(z, a, gamma, alpha, dbeta, *, terms: bool = False, device: int = 0):

@@ -4,10 +4,12 @@ sites keep working.  Lengths are in the caller's ``length_unit`` (see simulation
 """
 from __future__ import annotations
 
+import math
+import sys
 from dataclasses import dataclass
 
-__all__ = ["SimulationConfig", "default_simulation_config", "custom_simulation_config", "validate_config",
-           "n_steps_of"]
+__all__ = ["AdaptiveConfig", "SimulationConfig", "default_simulation_config", "custom_simulation_config",
+           "validate_config", "n_steps_of"]
 
 
 @dataclass(frozen=True)
@@ -46,3 +48,32 @@ def validate_config(cfg: SimulationConfig) -> None:
 def n_steps_of(z_max: float, dz: float) -> int:
     """``int(round(z_max / dz))`` -- the reference's step count (integrators.py:194), round-half-even."""
     return int(round(z_max / dz))
+
+
+@dataclass(frozen=True)
+class AdaptiveConfig:
+    """Tolerances of the adaptive (RK45) integrator -- scipy.integrate.RK45's rtol / atol / max_step / first_step, plus a
+    cap on the attempts (accepted + rejected steps) per point.  first_step = 0 selects the first step as scipy does; a
+    first_step beyond the interval, which scipy rejects, acts as first_step = z_max.  h_max and first_step are lengths in
+    the caller's unit: metres for the sweep engine and the operator form, ``length_unit`` for
+    simulation.run_single_simulation_adaptive."""
+    rtol: float = 1e-9
+    atol: float = 1e-12
+    h_max: float = math.inf
+    first_step: float = 0.0
+    max_steps: int = 1_000_000
+
+    def validate(self) -> None:
+        """ValueError for what psa_rk45_sweep_f64 rejects with PSA_E_TOL."""
+        rtol, atol, h_max, first = (float(x) for x in (self.rtol, self.atol, self.h_max, self.first_step))
+        problems = (
+            (not (math.isfinite(rtol) and rtol >= 100.0 * sys.float_info.epsilon),
+             "rtol must be finite and >= 100 * machine epsilon"),
+            (not (math.isfinite(atol) and atol > 0.0), "atol must be positive and finite"),
+            (not h_max > 0.0, "h_max must be positive"),
+            (not (math.isfinite(first) and first >= 0.0), "first_step must be >= 0 and finite (0: select it)"),
+            (int(self.max_steps) != self.max_steps or int(self.max_steps) < 1, "max_steps must be an integer >= 1"),
+        )
+        for bad, msg in problems:
+            if bad:
+                raise ValueError(msg)

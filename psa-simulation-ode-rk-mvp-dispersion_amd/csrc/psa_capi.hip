@@ -837,6 +837,117 @@ int dbeta_pairs_dev(void *stream, const int32_t *orders, int n_orders, const dou
     return PSA_OK;
 }
 
+// ---- the adaptive (RK45) sweep ----------------------------------------------------------------------------------
+// Argument rules of psa_rk45_sweep_*: those of the sweep (validate_common, with one step and a stride of one standing in
+// for the grid an adaptive run does not have), the flags it takes, the tolerances, the extra outputs and the row count.
+int validate_rk45(int n_waves, int64_t n_points, double z_max, double rtol, double atol, double h_max, double first_step,
+                  int64_t max_steps, int64_t n_out, const void *dbeta, const void *dbeta2, const void *gamma,
+                  const void *alpha, const void *a0, uint32_t flags, const void *a_end, const void *p_end,
+                  const void *p_max, const void *status, const void *z_end, const void *n_acc, const void *n_rej,
+                  const void *traj) {
+    int rc = validate_common(n_waves, n_points, 1, z_max, 1, dbeta, dbeta2, gamma, alpha, a0, a_end, p_end, p_max, status,
+                             0u, traj != nullptr, sizeof(double));
+    if (rc != PSA_OK) return rc;
+    const uint32_t allowed = PSA_BCAST_GAMMA | PSA_BCAST_ALPHA | PSA_BCAST_A0 | PSA_OPT_LOSSLESS;
+    if (flags & ~allowed)
+        return fail(PSA_E_FLAGS, "the adaptive sweep takes PSA_BCAST_GAMMA/ALPHA/A0 and PSA_OPT_LOSSLESS only, got 0x%x",
+                    flags);
+    if (!(rtol >= 100.0 * 2.220446049250313e-16) || !std::isfinite(rtol))
+        return fail(PSA_E_TOL, "rtol must be finite and >= 100 * DBL_EPSILON");
+    if (!(atol > 0.0) || !std::isfinite(atol)) return fail(PSA_E_TOL, "atol must be positive and finite");
+    if (!(h_max > 0.0)) return fail(PSA_E_TOL, "h_max must be positive");
+    if (!(first_step >= 0.0) || !std::isfinite(first_step))
+        return fail(PSA_E_TOL, "first_step must be >= 0 and finite (0: select it)");
+    if (max_steps < 1) return fail(PSA_E_TOL, "max_steps must be >= 1, got %lld", (long long)max_steps);
+    if (n_out < 0) return fail(PSA_E_TOL, "n_out must be >= 0, got %lld", (long long)n_out);
+    if (n_points > 0 && (!z_end || !n_acc || !n_rej)) return fail(PSA_E_NULLPTR, "a required buffer pointer is NULL");
+    if (traj && ((long double)n_out + 1.0L) * (long double)n_points * (2.0L * n_waves) * sizeof(double) > 4.0e18L)
+        return fail(PSA_E_TOO_LARGE, "dense-output buffer too large");
+    return PSA_OK;
+}
+
+// traj_ld: the device rows' leading dimension (n_points for the _dev form, traj_ld_of for the host form's staging)
+int rk45_dev(void *stream, int n_waves, int64_t n_points, double z_max, double rtol, double atol, double h_max,
+             double first_step, int64_t max_steps, int64_t n_out, const double *d_dbeta, const double *d_dbeta2,
+             const double *d_gamma, const double *d_alpha, const double *d_a0_soa, uint32_t flags, double *d_a_end_soa,
+             double *d_p_end, double *d_p_max, int32_t *d_status, double *d_z_end, int64_t *d_n_acc, int64_t *d_n_rej,
+             double *d_traj, int64_t traj_ld) {
+    int rc = validate_rk45(n_waves, n_points, z_max, rtol, atol, h_max, first_step, max_steps, n_out, d_dbeta, d_dbeta2,
+                           d_gamma, d_alpha, d_a0_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_status, d_z_end, d_n_acc,
+                           d_n_rej, d_traj);
+    if (rc != PSA_OK) return rc;
+    if (n_points == 0) return PSA_OK;
+    psa::AdaptiveArgs<double> a;
+    a.dbeta = d_dbeta;
+    a.dbeta2 = d_dbeta2;
+    a.gamma = d_gamma;
+    a.alpha = d_alpha;
+    a.a0 = d_a0_soa;
+    a.a_end = d_a_end_soa;
+    a.p_end = d_p_end;
+    a.p_max = d_p_max;
+    a.status = d_status;
+    a.z_end = d_z_end;
+    a.n_accepted = (long long *)d_n_acc;
+    a.n_rejected = (long long *)d_n_rej;
+    a.traj = d_traj;
+    a.traj_ld = traj_ld;
+    a.n_points = n_points;
+    a.z_max = z_max;
+    a.rtol = rtol;
+    a.atol = atol;
+    a.h_max = h_max;
+    a.first_step = first_step;
+    a.max_steps = max_steps;
+    a.n_out = n_out;
+    a.gamma_stride = (flags & PSA_BCAST_GAMMA) ? 0 : 1;
+    a.alpha_stride = (flags & PSA_BCAST_ALPHA) ? 0 : 1;
+    a.a0_stride = (flags & PSA_BCAST_A0) ? 0 : 1;
+    a.a0_ld = (flags & PSA_BCAST_A0) ? 1 : n_points;
+    hipError_t e = psa::launch_rk45_sweep_f64((hipStream_t)stream, n_waves, flags, a);
+    if (e != hipSuccess) return hip_fail(e, "rk45_sweep launch");
+    return PSA_OK;
+}
+
+int rk45_host(int device, int n_waves, int64_t n_points, double z_max, double rtol, double atol, double h_max,
+              double first_step, int64_t max_steps, int64_t n_out, const double *dbeta, const double *dbeta2,
+              const double *gamma, const double *alpha, const double *a0, uint32_t flags, double *a_end, double *p_end,
+              double *p_max, int32_t *status, double *z_end, int64_t *n_acc, int64_t *n_rej, double *traj,
+              double *elapsed_ms) {
+    int rc = validate_rk45(n_waves, n_points, z_max, rtol, atol, h_max, first_step, max_steps, n_out, dbeta, dbeta2,
+                           gamma, alpha, a0, flags, a_end, p_end, p_max, status, z_end, n_acc, n_rej, traj);
+    if (rc != PSA_OK) return rc;
+    if (elapsed_ms) *elapsed_ms = 0.0;
+    if (n_points == 0) return PSA_OK;
+    const int nc = 2 * n_waves;
+    const size_t N = (size_t)n_points;
+    if ((flags & PSA_BCAST_ALPHA) && alpha[0] == 0.0) flags |= PSA_OPT_LOSSLESS;   // the reference's alpha == 0.0 branch
+    const double *d_dbeta, *d_dbeta2, *d_gamma, *d_alpha, *d_a0;
+    double *d_aend, *d_pend, *d_pmax, *d_zend, *d_traj;
+    int32_t *d_status;
+    int64_t *d_nacc, *d_nrej;
+    auto layout = [&](Staging<double> &sg) {
+        d_dbeta = sg.input(dbeta, N);
+        d_dbeta2 = sg.input(dbeta2, N);
+        d_gamma = sg.input(gamma, (flags & PSA_BCAST_GAMMA) ? 1 : N);
+        d_alpha = sg.input(alpha, (flags & PSA_BCAST_ALPHA) ? 1 : N);
+        d_a0 = sg.input_soa(a0, (flags & PSA_BCAST_A0) ? 1 : N, nc);
+        d_aend = sg.output_soa(a_end, N, nc);
+        d_pend = sg.output(p_end, N);
+        d_pmax = sg.output(p_max, N);
+        d_status = sg.output(status, N);
+        d_zend = sg.output(z_end, N);
+        d_nacc = sg.output(n_acc, N);
+        d_nrej = sg.output(n_rej, N);
+        d_traj = sg.trajectory(traj, N, (size_t)n_out + 1, nc);
+    };
+    return host_call<double>(device, "the RK45 sweep", elapsed_ms, layout, [&](hipStream_t st) {
+        return rk45_dev(st, n_waves, n_points, z_max, rtol, atol, h_max, first_step, max_steps, n_out, d_dbeta, d_dbeta2,
+                        d_gamma, d_alpha, d_a0, flags, d_aend, d_pend, d_pmax, d_status, d_zend, d_nacc, d_nrej, d_traj,
+                        traj_ld_of(n_points, sizeof(double)));
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1092,6 +1203,26 @@ int psa_rk4_chain_f32_dev(void *stream, int n_waves, int64_t n_points, int n_seg
 
 int64_t psa_rk4_chain_workspace_bytes(int n_waves, int64_t n_points, int32_t elem_size, int wave_summary) {
     return chain_workspace_bytes(n_waves, n_points, (size_t)(elem_size > 0 ? elem_size : 0), wave_summary != 0);
+}
+
+int psa_rk45_sweep_f64(int device, int n_waves, int64_t n_points, double z_max, double rtol, double atol, double h_max,
+                       double first_step, int64_t max_steps, int64_t n_out, const double *dbeta, const double *dbeta2,
+                       const double *gamma, const double *alpha, const double *a0_re_im, uint32_t flags,
+                       double *a_end_re_im, double *p_sig_end, double *p_sig_max, int32_t *status, double *z_end,
+                       int64_t *n_accepted, int64_t *n_rejected, double *traj_or_null, double *elapsed_ms_or_null) {
+    return rk45_host(device, n_waves, n_points, z_max, rtol, atol, h_max, first_step, max_steps, n_out, dbeta, dbeta2,
+                     gamma, alpha, a0_re_im, flags, a_end_re_im, p_sig_end, p_sig_max, status, z_end, n_accepted,
+                     n_rejected, traj_or_null, elapsed_ms_or_null);
+}
+int psa_rk45_sweep_f64_dev(void *stream, int n_waves, int64_t n_points, double z_max, double rtol, double atol,
+                           double h_max, double first_step, int64_t max_steps, int64_t n_out, const double *d_dbeta,
+                           const double *d_dbeta2, const double *d_gamma, const double *d_alpha, const double *d_a0_soa,
+                           uint32_t flags, double *d_a_end_soa, double *d_p_sig_end, double *d_p_sig_max,
+                           int32_t *d_status, double *d_z_end, int64_t *d_n_accepted, int64_t *d_n_rejected,
+                           double *d_traj_soa) {
+    return rk45_dev(stream, n_waves, n_points, z_max, rtol, atol, h_max, first_step, max_steps, n_out, d_dbeta, d_dbeta2,
+                    d_gamma, d_alpha, d_a0_soa, flags, d_a_end_soa, d_p_sig_end, d_p_sig_max, d_status, d_z_end,
+                    d_n_accepted, d_n_rejected, d_traj_soa, n_points);
 }
 
 }  // extern "C"

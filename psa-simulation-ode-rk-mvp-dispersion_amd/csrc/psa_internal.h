@@ -31,6 +31,24 @@ struct SweepArgs {
     T *p_wave_max;       // max over saved rows incl. z = 0 (NaN-propagating like np.max)
 };
 
+// Everything one adaptive (RK45) sweep launch needs; inputs as SweepArgs, per-point outputs SoA / [N].
+template <typename T>
+struct AdaptiveArgs {
+    const T *dbeta, *dbeta2, *gamma, *alpha, *a0;
+    T *a_end;                 // SoA [2*NW][N]
+    T *p_end, *p_max;         // [N]
+    int32_t *status;          // [N] 0 reached z_max, 1 step below the minimum, 2 max_steps attempts used
+    T *z_end;                 // [N]
+    long long *n_accepted, *n_rejected;   // [N]
+    T *traj;                  // dense-output rows [n_out + 1][NW][traj_ld][2] or nullptr
+    long long traj_ld;
+    long long n_points;
+    double z_max, rtol, atol, h_max, first_step;   // first_step 0: scipy's select_initial_step
+    long long max_steps, n_out;
+    int gamma_stride, alpha_stride, a0_stride;
+    long long a0_ld;
+};
+
 enum CheckMode : int { CHECK_NONE = 0, CHECK_BLOCK = 1, CHECK_EXACT = 2 };
 
 // Sweep launchers (psa_rk4_f64.hip / psa_rk4_f32.hip): one kernel launch on s, nothing for n_points == 0.  They own
@@ -39,6 +57,9 @@ enum CheckMode : int { CHECK_NONE = 0, CHECK_BLOCK = 1, CHECK_EXACT = 2 };
 // caller has validated the arguments (the per-wave summary: no trajectory, no LDS staging, no BLOCK64).
 hipError_t launch_sweep_f64(hipStream_t s, int n_waves, uint32_t flags, const SweepArgs<double> &a);
 hipError_t launch_sweep_f32(hipStream_t s, int n_waves, uint32_t flags, const SweepArgs<float> &a);
+// Adaptive sweep launcher (psa_rk45.hip): one launch on s, nothing for n_points == 0; PSA_OPT_LOSSLESS is the only flag
+// it reads and the dense-output rows come from a.traj being non-null.  The caller has validated the arguments.
+hipError_t launch_rk45_sweep_f64(hipStream_t s, int n_waves, uint32_t flags, const AdaptiveArgs<double> &a);
 
 // aux kernels (psa_aux.hip)
 hipError_t launch_aos_to_soa_f64(hipStream_t s, const double *aos, double *soa, long long n, int nc);

@@ -7,15 +7,16 @@ propagation to the HIP kernel through ``integrators.integrate_interval(rhs_yaman
 """
 from __future__ import annotations
 
+import dataclasses
 from typing import Optional, Sequence
 
 import numpy as np
 
 from . import constants
-from .config import (SimulationConfig, custom_simulation_config, default_simulation_config,  # noqa: F401
-                     validate_config)
+from .config import (AdaptiveConfig, SimulationConfig, custom_simulation_config, default_simulation_config,  # noqa: F401
+                     n_steps_of, validate_config)
 from .dispersion import DispersionParams
-from .integrators import integrate_interval
+from .integrators import integrate_adaptive, integrate_interval
 from .parameters import FiberParams, PhaseMatchingParams, SimulationGrid, WavesParams, make_model_params
 from .phase_matching import PhaseMatchingConfig, PhaseMatchingMethod, PhaseMatchingResult, compute_phase_mismatch  # noqa: F401
 from .sweep import FibreSpan, initial_amplitudes, rk4_chain
@@ -121,6 +122,54 @@ def run_single_simulation(cfg: SimulationConfig, *, gamma: float, alpha: float, 
     params.cache.set_phase_mismatch(res.delta_beta, symmetric=res.symmetric)
     z_m, A = integrate_interval(rhs_yaman_simplified, params.fiber.length_m, params.grid.dz_m, A0, params,
                                 save_every=cfg.save_every, check_nan=cfg.check_nan)
+    out_unit = length_unit if return_length_unit is None else return_length_unit
+    return z_m / _length_scale_to_m(out_unit), A
+
+
+def run_single_simulation_adaptive(cfg: SimulationConfig, *, tol: AdaptiveConfig = AdaptiveConfig(), gamma: float,
+                                   alpha: float, omega: Sequence[float], p_in: Sequence[float],
+                                   phase_in: Optional[Sequence[float]] = None,
+                                   dispersion: Optional[DispersionParams] = None,
+                                   phase_matching_cfg: Optional[PhaseMatchingConfig] = None,
+                                   beta_legacy: Optional[Sequence[float]] = None, length_unit: str = "m",
+                                   return_length_unit: Optional[str] = None) -> tuple[np.ndarray, np.ndarray]:
+    """run_single_simulation integrated to the tolerance ``tol`` (adaptive RK45 on the GPU) -> (z_out, A (n_rows, 4)).
+
+    z_out is the grid run_single_simulation(cfg, ...) returns, bit for bit: np.linspace(0, z_max, n_steps + 1)[::save_every]
+    with n_steps = n_steps_of(z_max, dz) -- when save_every does not divide n_steps the last row lies short of z_max, as
+    there.  The rows are the dense output at those z: cfg.dz and cfg.save_every only say where rows are sampled, the step
+    is chosen by ``tol``, and the integration always runs to z_max.  tol.h_max and tol.first_step are lengths in
+    ``length_unit``, like cfg.z_max and cfg.dz; rtol and atol are amplitude tolerances and take no unit.  With
+    cfg.check_nan a non-finite state (status 1) raises FloatingPointError; running out of tol.max_steps (status 2) always
+    raises RuntimeError."""
+    validate_config(cfg)
+    if not isinstance(tol, AdaptiveConfig):
+        raise TypeError("tol must be an AdaptiveConfig")
+    tol.validate()
+    _length_scale_to_m(length_unit)
+    om = _to_omega_array(omega)
+    A0 = make_initial_amplitudes(_to_power_array(p_in), phase_in)
+    pre = _prepare(cfg, gamma=gamma, alpha=alpha, dispersion=dispersion, phase_matching_cfg=phase_matching_cfg,
+                   beta_legacy=beta_legacy, length_unit=length_unit)
+    params = make_model_params(waves=WavesParams(omega=om, symmetric=None), fiber=pre["fiber"], grid=pre["grid"],
+                               phase_matching=pre["pm"])
+    res = compute_phase_mismatch(params.waves.omega, params.fiber.dispersion, params.phase_matching.config,
+                                 symmetric_hint=params.waves.symmetric)
+    params.cache.set_phase_mismatch(res.delta_beta, symmetric=res.symmetric)
+    n_steps = n_steps_of(params.fiber.length_m, params.grid.dz_m)
+    if n_steps < 1:
+        raise ValueError("z_max / dz rounds to zero steps")
+    scale = pre["scale"]
+    tol_m = dataclasses.replace(tol, h_max=float(tol.h_max) * scale, first_step=float(tol.first_step) * scale)
+    # every point of the fixed-step grid, then its stride: the same z values as integrate_interval's rows
+    z_m, A, info = integrate_adaptive(rhs_yaman_simplified, params.fiber.length_m, A0, params, tol=tol_m, n_out=n_steps)
+    se = int(cfg.save_every)
+    z_m, A = z_m[::se].copy(), A[::se].copy()
+    if info["status"] == 2:
+        raise RuntimeError(f"adaptive integration used up max_steps = {tol.max_steps} attempts at z = {info['z_end']} "
+                           f"of {params.fiber.length_m} m")
+    if info["status"] == 1 and cfg.check_nan:
+        raise FloatingPointError(f"NaN or Inf detected: adaptive step fell below the minimum at z = {info['z_end']}")
     out_unit = length_unit if return_length_unit is None else return_length_unit
     return z_m / _length_scale_to_m(out_unit), A
 

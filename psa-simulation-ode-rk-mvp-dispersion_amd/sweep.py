@@ -14,9 +14,10 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _native
-from .config import n_steps_of
+from .config import AdaptiveConfig, n_steps_of
 
-__all__ = ["ChainResult", "FibreSpan", "SweepResult", "initial_amplitudes", "rk4_chain", "rk4_sweep"]
+__all__ = ["AdaptiveResult", "ChainResult", "FibreSpan", "SweepResult", "initial_amplitudes", "rk4_chain", "rk4_sweep",
+           "rk45_sweep"]
 
 
 def initial_amplitudes(p_in, phase_in=None) -> np.ndarray:
@@ -307,3 +308,57 @@ def rk4_chain(spans: Sequence[FibreSpan], *, a0, transfers=None, save_every: int
     return ChainResult(r["a_end"], r["p_end"], r["p_max"], r["first_bad_step"], int(step_off[-1]), save_every,
                        r["elapsed_ms"], r["traj"], r.get("p_wave_end"), r.get("p_wave_max"), z_out=z_out,
                        row_offsets=row_off, step_offsets=step_off)
+
+
+# ---- adaptive (RK45) sweeps ----------------------------------------------------------------------------------------
+@dataclass
+class AdaptiveResult:
+    """Per-point outcome of an adaptive sweep (psa_rk45_sweep_f64)."""
+    a_end: np.ndarray            # (N, n_waves) complex: the state at z_end
+    p_end: np.ndarray            # (N,) |A_signal|^2 there
+    p_max: np.ndarray            # (N,) max over z = 0 and every accepted step end, NaN-propagating
+    status: np.ndarray           # (N,) int32: 0 reached z_max, 1 step below the minimum (non-finite state), 2 max_steps
+    z_end: np.ndarray            # (N,) the z reached
+    n_accepted: np.ndarray       # (N,) int64
+    n_rejected: np.ndarray       # (N,) int64
+    elapsed_ms: float            # kernel time (hipEvents)
+    traj: Optional[np.ndarray] = None    # (N, n_out + 1, n_waves) dense-output rows (NaN past z_end) when n_out > 0
+    z_out: Optional[np.ndarray] = None   # (n_out + 1,) np.linspace(0, z_max, n_out + 1)
+
+    @property
+    def first_bad_step(self) -> np.ndarray:
+        """-1 where the point reached z_max, else its accepted step count: what the gain reduction marks as failed."""
+        return np.where(self.status == 0, -1, self.n_accepted).astype(np.int64)
+
+    def gain(self, p0_sig: float, *, mode: str = "max", unit: str = "dB", device: int = 0) -> np.ndarray:
+        """Per-point signal gain with SweepResult's meaning; NaN exactly where status != 0."""
+        return self.summary(p0_sig, mode=mode, unit=unit, device=device)[0]
+
+    def summary(self, p0_sig: float, *, mode: str = "max", unit: str = "dB", device: int = 0):
+        """(gain[N], best_index, best_gain, n_finite), reduced on the GPU by psa_gain_summary_f64."""
+        if mode not in ("end", "max"):
+            raise ValueError(f"Unknown gain_mode={mode!r}. Use 'end' or 'max'.")
+        u = str(unit).strip().lower()
+        if u not in ("db", "linear"):
+            raise ValueError("gain_unit must be 'dB' or 'linear'")
+        metric = np.ascontiguousarray(self.p_max if mode == "max" else self.p_end, dtype=np.float64)
+        return _native.gain_summary_host(metric, self.first_bad_step, float(p0_sig), gain_db=(u == "db"), device=device)
+
+
+def rk45_sweep(dbeta, *, z_max: float, tol: AdaptiveConfig = AdaptiveConfig(), gamma, alpha, a0, dbeta2=None,
+               n_out: int = 0, device: int = 0) -> AdaptiveResult:
+    """Propagate N points to the tolerance ``tol`` with embedded Dormand-Prince 5(4) (scipy's RK45, step for step), each
+    point with its own step size.  ``n_out > 0`` also returns the dense-output rows at np.linspace(0, z_max, n_out + 1)."""
+    if not (np.isfinite(z_max) and z_max > 0.0):
+        raise ValueError("z_max must be positive")
+    if not isinstance(tol, AdaptiveConfig):
+        raise TypeError("tol must be an AdaptiveConfig")
+    tol.validate()
+    if int(n_out) < 0:
+        raise ValueError("n_out must be >= 0")
+    r = _native.rk45_sweep_host(dbeta, z_max=float(z_max), rtol=tol.rtol, atol=tol.atol, h_max=tol.h_max,
+                                first_step=tol.first_step, max_steps=int(tol.max_steps), n_out=int(n_out), gamma=gamma,
+                                alpha=alpha, a0=a0, dbeta2=dbeta2, device=device)
+    z_out = np.linspace(0.0, float(z_max), int(n_out) + 1) if int(n_out) > 0 else None
+    return AdaptiveResult(r["a_end"], r["p_end"], r["p_max"], r["status"], r["z_end"], r["n_accepted"], r["n_rejected"],
+                          r["elapsed_ms"], r["traj"], z_out)
