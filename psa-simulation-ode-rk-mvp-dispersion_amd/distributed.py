@@ -3,7 +3,11 @@
 Sweep points are independent initial-value problems (the reference's loop body has no cross-iteration state,
 scan_mismtach.py:694-738), so the path shards with NO data-path collective: rank r integrates the contiguous
 block ``shard_bounds(N, world, r)`` on its own GPU.  The only exchange is one ``all_gather`` of the per-point
-output record (RCCL over xGMI when the process group is ``nccl``; ``gloo`` on CPU tensors in the tests).
+output record (RCCL over xGMI when the process group is ``nccl``; ``gloo`` on CPU tensors in the tests).  For host
+buffers that exchange is ``exchange_blocks``, the one path of ``sweep_sharded`` and of the ``scan_mismtach`` drivers:
+this rank's share (``_partition.Share``) runs its block, the record travels with optional float64 extra columns and one
+status word per rank, and a block that raised on any rank makes every rank raise after the gather (none is left waiting
+in the collective).
 
 The record is the flat byte image the sweep kernel itself writes (``RecordLayout``), for n points of a sweep with
 n_waves waves in float64 or float32 (element size es):
@@ -23,26 +27,18 @@ One process per GPU (``torchrun`` / ``python -m torch.distributed.run``).  ``imp
 """
 from __future__ import annotations
 
-from typing import Callable, Optional, Tuple
+from typing import Callable, Optional
 
 import numpy as np
 import torch  # noqa: F401  (must precede the native library: one HIP runtime per process)
 import torch.distributed as dist
 
 from . import _native
-from .sweep import SweepResult
+from ._partition import SWEEP_AXES, Share, cut, shard_bounds
+from .sweep import SweepResult, check_gain
 
-__all__ = ["shard_bounds", "RecordLayout", "unpack_gathered", "all_gather_host_words", "local_device", "sweep_sharded",
-           "DeviceSweep"]
-
-
-def shard_bounds(n_points: int, world: int, rank: int) -> Tuple[int, int]:
-    """Contiguous block split; the first ``n_points % world`` ranks get one extra point."""
-    if world < 1 or not 0 <= rank < world:
-        raise ValueError(f"bad rank/world: {rank}/{world}")
-    base, rem = divmod(int(n_points), world)
-    lo = rank * base + min(rank, rem)
-    return lo, lo + base + (1 if rank < rem else 0)
+__all__ = ["shard_bounds", "RecordLayout", "unpack_gathered", "all_gather_host_words", "exchange_blocks", "local_device",
+           "sweep_sharded", "DeviceSweep"]
 
 
 class RecordLayout:
@@ -114,10 +110,6 @@ def unpack_gathered(layout: RecordLayout, gathered: np.ndarray, n_points: int, w
     return tuple(np.concatenate([p[k] for p in parts]) for k in range(4))
 
 
-def _native_executor(dbeta, **kw):
-    return _native.sweep_host(dbeta, **kw)
-
-
 def _all_gather_words(t_local: torch.Tensor, world: int, group, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The single collective of the path: every rank contributes the same number of int64 words."""
     if out is None:
@@ -147,6 +139,41 @@ def local_device(group=None) -> int:
     return int(os.environ.get("LOCAL_RANK", dist.get_rank(group))) % n
 
 
+def exchange_blocks(share: Share, layout: RecordLayout, block: Callable[[], Optional[dict]], n_extras: int = 0):
+    """Run ``block()`` for this rank's points [share.lo, share.hi), then ONE all_gather over ``share.group`` of
+    [status word | its record (RecordLayout, padded to share.width) | n_extras float64 columns].
+
+    ``block()`` returns None (no points) or a dict with a_end, p_end, p_max, first_bad_step and, when n_extras > 0,
+    ``extras``: n_extras per-point arrays of the block.  A rank whose block raises still joins the gather with a zeroed
+    image and its status set; afterwards it re-raises its exception and every other rank raises RuntimeError naming it.
+    Returns (this rank's dict | None, (a_end, p_end, p_max, first_bad) of the whole sweep, [n_extras columns over n])."""
+    n_words = layout.words(share.width) + n_extras * share.width
+    status, err, local, words = 0, None, None, np.zeros(n_words, dtype=np.int64)
+    try:
+        local = block()
+        if local is not None:
+            cols = [np.pad(np.asarray(e, dtype=np.float64), (0, share.width - len(e))).view(np.int64)
+                    for e in local.get("extras", ())]
+            words = np.concatenate([layout.pack(local["a_end"], local["p_end"], local["p_max"], local["first_bad_step"],
+                                                pad_to=share.width)] + cols)
+            if words.size != n_words:
+                raise ValueError(f"block image has {words.size} words, expected {n_words}")
+    except Exception as exc:          # still take part: the other ranks are already waiting in the collective
+        status, err, words = 1, exc, np.zeros(n_words, dtype=np.int64)
+    gathered = all_gather_host_words(np.concatenate([[status], words]), share.group, device=share.device)
+    if err is not None:
+        raise err
+    failed = np.flatnonzero(gathered[:, 0]).tolist()
+    if failed:
+        raise RuntimeError(f"sharded sweep: the block of rank(s) {failed} failed")
+    nrec = layout.words(share.width)
+    whole = unpack_gathered(layout, gathered[:, 1:1 + nrec], share.n, share.world)
+    sizes = [hi - lo for lo, hi in (shard_bounds(share.n, share.world, r) for r in range(share.world))]
+    ext = [np.concatenate([gathered[r, 1 + nrec + k * share.width:][:sizes[r]].view(np.float64) for r in range(share.world)])
+           for k in range(n_extras)]
+    return local, whole, ext
+
+
 def sweep_sharded(dbeta, *, n_steps: int, z_max: float, save_every: int = 10, gamma, alpha, a0, dbeta2=None,
                   check_nan: bool = True, dtype=np.float64, group=None, device: Optional[int] = None,
                   executor: Optional[Callable[..., dict]] = None) -> SweepResult:
@@ -156,45 +183,31 @@ def sweep_sharded(dbeta, *, n_steps: int, z_max: float, save_every: int = 10, ga
     rank's block; scalars and a single a0 are broadcast.  ``dtype`` float64 | float32 selects the kernel and the record
     (BASELINE config 4 is float32); six-column ``a0`` + ``dbeta2`` select the 6-wave model (config 5).
     ``executor(dbeta_local, **kw) -> dict`` runs the local shard; the default is the HIP kernel on ``device`` (default:
-    LOCAL_RANK-th GPU).  Tests inject the CPU oracle here to exercise the shard/gather logic under ``gloo`` without a GPU.
+    ``local_device``).  Tests inject the CPU oracle here to exercise the shard/gather logic under ``gloo`` without a GPU.
     """
     if not dist.is_initialized():
         raise RuntimeError("torch.distributed is not initialised (launch with torchrun, one process per GPU)")
-    world, rank = dist.get_world_size(group), dist.get_rank(group)
     dbeta = np.ascontiguousarray(np.asarray(dbeta, dtype=np.float64))
-    N = dbeta.shape[0]
-    lo, hi = shard_bounds(N, world, rank)
-
-    def cut(x, per_point_ndim):
-        x = np.asarray(x)
-        return x[lo:hi] if (x.ndim == per_point_ndim and x.shape[0] == N and N > 1) else x
-
-    a0 = np.asarray(a0)
-    nw = int(a0.shape[-1])
-    layout = RecordLayout(nw, dtype)
-    kw = dict(n_steps=int(n_steps), z_max=float(z_max), save_every=int(save_every), gamma=cut(gamma, 1),
-              alpha=cut(alpha, 1), a0=cut(a0, 2), check_nan=bool(check_nan))
+    share = Share(dbeta.shape[0], device, group)
+    layout = RecordLayout(int(np.shape(a0)[-1]), dtype)
+    kw = dict(dbeta=dbeta, n_steps=int(n_steps), z_max=float(z_max), save_every=int(save_every), gamma=gamma, alpha=alpha,
+              a0=a0, check_nan=bool(check_nan))
     if dbeta2 is not None:
-        kw["dbeta2"] = cut(dbeta2, 1)
+        kw["dbeta2"] = dbeta2
     if layout.es == 4:
         kw["dtype"] = np.float32
     if executor is None:
-        executor = _native_executor
-        if device is None:
-            import os
-            device = int(os.environ.get("LOCAL_RANK", rank))
-        kw["device"] = int(device) % max(1, _native.device_count())
-    local = executor(dbeta[lo:hi], **kw) if hi > lo else dict(
-        a_end=np.zeros((0, nw), layout.cdtype), p_end=np.zeros(0, layout.dtype), p_max=np.zeros(0, layout.dtype),
-        first_bad_step=np.zeros(0, np.int64))
+        executor, kw["device"] = _native.sweep_host, share.device
 
-    width = (N + world - 1) // world                     # widest shard; shorter ones are zero-padded
-    words = layout.pack(local["a_end"], local["p_end"], local["p_max"], local["first_bad_step"], pad_to=width)
-    # the collective runs on the GPU that computed the shard, also for a rank whose block is empty
-    gathered = all_gather_host_words(words, group, device=kw.get("device", device))
-    a_end, p_end, p_max, first_bad = unpack_gathered(layout, gathered, N, world)
+    def block():
+        if share.hi == share.lo:
+            return None
+        blk = cut(kw, SWEEP_AXES, share.n, slice(share.lo, share.hi))
+        return executor(blk.pop("dbeta"), **blk)
+
+    local, (a_end, p_end, p_max, first_bad), _ = exchange_blocks(share, layout, block)
     return SweepResult(a_end, p_end, p_max, first_bad, int(n_steps), int(save_every),
-                       float(local.get("elapsed_ms", 0.0)))
+                       float((local or {}).get("elapsed_ms", 0.0)))
 
 
 _TORCH_DTYPE = {np.dtype(np.float64): torch.float64, np.dtype(np.float32): torch.float32}
@@ -338,8 +351,7 @@ class DeviceSweep:
     def summarize(self, p0_sig: float, *, mode: str = "max", gain_db: bool = True) -> None:
         """Enqueue the gain reduction of the sweep drivers (scan_mismtach.py:376-389 + argmax) on the same stream:
         fills ``self.gain`` (n_local,), ``self.best`` = [best_index, n_finite] (int64) and ``self.best_gain`` (1,)."""
-        if mode not in ("end", "max"):
-            raise ValueError(f"Unknown gain_mode={mode!r}. Use 'end' or 'max'.")
+        check_gain(mode)
         b = self._last
         if self._summ[b] is None:
             self._summ[b] = (torch.empty(self.n_local, dtype=self.tdtype, device=self.device),

@@ -20,10 +20,12 @@ build every plan and every dbeta at once on the host (``plan_from_wavelengths_ba
 ``compute_phase_mismatch_batch``), launch ONE HIP sweep over all valid points and reduce the gain on the GPU.
 
 Several GPUs (the reference's loop over points is embarrassingly parallel, scan_mismtach.py:357-392, :694-738):
-* under a ``torch.distributed`` process group (one process per GPU, ``torchrun``) every driver splits its points into
-  contiguous blocks, each rank produces the phase mismatch of ITS block (on its GPU with the device producer), integrates it
-  and contributes the block's output record to ONE all_gather (RCCL under ``nccl``); every rank returns the full arrays;
-* a plain Python caller passes ``devices=[0, 1, ...]``: one host thread per GPU over ``psa_rk4_sweep_f64(device=k)``.
+* under a ``torch.distributed`` process group (one process per GPU, ``torchrun``) every driver takes its rank's share of
+  the points (``_partition.Share``), produces the phase mismatch of ITS block (on its GPU with the device producer),
+  integrates it and hands the block to ``distributed.exchange_blocks``: ONE all_gather of the output record (RCCL under
+  ``nccl``); every rank returns the full arrays.  If a rank's block raises (a native error in its producer or its sweep),
+  every rank raises after the gather -- except a failing Δβ producer of ``_sweep_gain``'s grid, whose points become NaN;
+* a plain Python caller passes ``devices=[0, 1, ...]``: one host thread per GPU (``_partition.over_devices``).
 
 Failure conventions kept from the reference: malformed arguments raise ``ValueError`` up front
 (:315-349, :630-671); anything that would raise INSIDE the per-point ``try`` (an impossible plan, a bad cfg,
@@ -39,9 +41,10 @@ import numpy as np
 from .config import SimulationConfig, custom_simulation_config, n_steps_of  # noqa: F401
 from .dispersion import DispersionParams, delta_beta_symmetric_array
 from .frequency_plan import plan_from_wavelengths_batch
+from ._partition import SWEEP_AXES, Share, cut
 from .phase_matching import PhaseMatchingConfig, PhaseMatchingMethod, compute_phase_mismatch_batch
 from .simulation import _prepare, make_initial_amplitudes
-from .sweep import SweepResult, rk4_sweep
+from .sweep import SweepResult, check_gain, rk4_sweep
 
 GainMode = Literal["end", "max"]
 
@@ -51,11 +54,8 @@ def _select_power_metric(Pz: np.ndarray, mode: GainMode) -> float:
     Pz = np.asarray(Pz)
     if Pz.ndim != 1:
         raise ValueError("Pz must be a 1D array of power versus z.")
-    if mode == "end":
-        return float(Pz[-1])
-    if mode == "max":
-        return float(np.max(Pz))
-    raise ValueError(f"Unknown gain_mode={mode!r}. Use 'end' or 'max'.")
+    check_gain(mode)
+    return float(Pz[-1]) if mode == "end" else float(np.max(Pz))
 
 
 # ---- argument checks shared by the two lambda3 drivers ---------------------------------------------------
@@ -85,8 +85,7 @@ def _check_sweep_inputs(lambda_signal_m, p_in, phase_in):
 def _norm_choice(value, name, allowed):
     v = str(value).strip().lower()
     if v not in allowed:
-        pretty = " or ".join(f"'{a}'" for a in allowed) if name != "gain_unit" else "'dB' or 'linear'"
-        raise ValueError(f"{name} must be {pretty}")
+        raise ValueError(f"{name} must be " + " or ".join(f"'{a}'" for a in allowed))
     return v
 
 
@@ -99,103 +98,66 @@ def _wavelength_axis(lam3, unit):
     raise ValueError("return_wavelength_unit must be 'm' or 'nm'")
 
 
-# ---- how a driver call's points are divided --------------------------------------------------------------------
-class _Shard:
-    """This process's share [lo, hi) of a driver call over n points: everything when no process group is up."""
-
-    def __init__(self, n: int, device: Optional[int]):
-        import sys
-        self.n, self.world, self.rank, self.group = int(n), 1, 0, None
-        td = sys.modules.get("torch.distributed")      # a caller who initialised a process group has imported it
-        if td is not None and td.is_available() and td.is_initialized() and td.get_world_size() > 1:
-            self.world, self.rank = td.get_world_size(), td.get_rank()
-        if self.world > 1:
-            from .distributed import local_device, shard_bounds
-            self.lo, self.hi = shard_bounds(self.n, self.world, self.rank)
-            self.device = local_device() if device is None else int(device)
-        else:
-            self.lo, self.hi = 0, self.n
-            self.device = 0 if device is None else int(device)
-        self.width = -(-self.n // self.world)            # widest block
-
-    @property
-    def sharded(self) -> bool:
-        return self.world > 1
-
-    def block(self, x, per_point_ndim: int = 1):
-        """This rank's rows of a per-point argument; scalars and single rows pass through."""
-        x = np.asarray(x)
-        return x[self.lo:self.hi] if (x.ndim == per_point_ndim and x.shape[0] == self.n and self.n > 1) else x
-
-
 NEVER_RAN = -2    # first_bad_step of a point whose plan / dbeta was invalid: it never reached the kernel
 
 
-def _run_block(shard: _Shard, ok_blk, dbeta_blk, *, dbeta2_blk=None, extras=(), n_waves=4, dtype=np.float64, devices=None,
-               **run_kw):
+def _run_block(share: Share, inputs, *, n_extras=0, n_waves=4, dtype=np.float64, devices=None, **run_kw):
     """Integrate the valid points of this process's block and, when the call is sharded over a process group, exchange
-    the blocks: ONE all_gather of [output record | extras], every rank ends up with the whole sweep.
+    the blocks (``distributed.exchange_blocks``): every rank ends up with the whole sweep.
 
-    ok_blk, dbeta_blk (, dbeta2_blk): the block's validity mask and per-metre mismatch; ``extras``: per-point float64
-    arrays of the block that travel with the record (the caller-unit dbeta).  run_kw: rk4_sweep's arguments, per-point
-    ones already cut to the block.  Returns (SweepResult over the valid points of the WHOLE sweep in order | None,
-    ok[n], [extras over n]).  With ``wave_summary=True`` in run_kw the per-wave columns (p_wave_end, p_wave_max) ride in
-    the same all_gather as 2 * n_waves more extras words per point (float64; a float32 sweep's values convert exactly)."""
-    ok_blk = np.asarray(ok_blk, dtype=bool)
-    idx = np.flatnonzero(ok_blk)
-    res = None
-    if idx.size:
-        kw = dict(run_kw)
-        for name, nd in (("gamma", 1), ("alpha", 1), ("a0", 2)):
-            v = np.asarray(kw[name])
-            if v.ndim == nd and v.shape[0] == ok_blk.size and ok_blk.size > 1:
-                kw[name] = v[idx]
-        res = rk4_sweep(np.asarray(dbeta_blk)[idx], dbeta2=(None if dbeta2_blk is None else np.asarray(dbeta2_blk)[idx]),
-                        dtype=dtype, device=shard.device, devices=(None if shard.sharded else devices), **kw)
-    if not shard.sharded:
-        return res, ok_blk, [np.asarray(e) for e in extras]
-
-    from .distributed import RecordLayout, all_gather_host_words, shard_bounds
-    layout = RecordLayout(n_waves, dtype)
-    nb = ok_blk.size
-    a_end = np.full((nb, n_waves), np.nan, dtype=layout.cdtype)
-    p_end, p_max = np.full(nb, np.nan, dtype=layout.dtype), np.full(nb, np.nan, dtype=layout.dtype)
-    bad = np.full(nb, NEVER_RAN, dtype=np.int64)
-    if res is not None:
-        a_end[idx], p_end[idx], p_max[idx], bad[idx] = res.a_end, res.p_end, res.p_max, res.first_bad_step
-    n_user = len(extras)
+    ``inputs()`` -> (ok | None (all valid), dbeta, dbeta2 | None, extras) of the block: its validity mask, per-metre
+    mismatch and ``n_extras`` per-point float64 arrays that travel with the record (the caller-unit dbeta); it runs inside
+    the exchange, so a rank whose producer raises makes every rank raise.  run_kw: rk4_sweep's arguments for the WHOLE
+    sweep.  Returns (SweepResult over the valid points of the whole sweep in order | None, ok[n], [extras over n]).  With
+    ``wave_summary=True`` in run_kw the per-wave columns (p_wave_end, p_wave_max) ride in the same all_gather as
+    2 * n_waves more extras (float64; a float32 sweep's values convert exactly)."""
     waves = bool(run_kw.get("wave_summary"))
-    if waves:                                   # columns j of p_wave_end, then of p_wave_max
-        wcols = np.full((nb, 2 * n_waves), np.nan)
+
+    def block():
+        ok, db, db2, extras = inputs()
+        ok = np.ones(len(db), dtype=bool) if ok is None else np.asarray(ok, dtype=bool)
+        idx = np.flatnonzero(ok)
+        res = None
+        if idx.size:
+            res = rk4_sweep(np.asarray(db)[idx], dbeta2=(None if db2 is None else np.asarray(db2)[idx]), dtype=dtype,
+                            device=share.device, devices=(None if share.sharded else devices),
+                            **cut(run_kw, SWEEP_AXES, share.n, share.lo + idx if share.lo else idx))
+        return ok, idx, res, list(extras)
+
+    if not share.sharded:
+        ok, _, res, extras = block()
+        return res, ok, [np.asarray(e) for e in extras]
+
+    from .distributed import RecordLayout, exchange_blocks
+    layout = RecordLayout(n_waves, dtype)
+
+    def record():
+        ok, idx, res, extras = block()
+        nb = ok.size
+        a_end = np.full((nb, n_waves), np.nan, dtype=layout.cdtype)
+        p_end, p_max = np.full(nb, np.nan, dtype=layout.dtype), np.full(nb, np.nan, dtype=layout.dtype)
+        bad = np.full(nb, NEVER_RAN, dtype=np.int64)
         if res is not None:
-            wcols[idx, :n_waves], wcols[idx, n_waves:] = res.p_wave_end, res.p_wave_max
-        extras = list(extras) + [wcols[:, k] for k in range(2 * n_waves)]
-    parts = [layout.pack(a_end, p_end, p_max, bad, pad_to=shard.width)]
-    for e in extras:
-        buf = np.zeros(shard.width, dtype=np.float64)
-        buf[:nb] = e
-        parts.append(buf.view(np.int64))
-    gathered = all_gather_host_words(np.concatenate(parts), shard.group, device=shard.device)
-    nrec = layout.words(shard.width)
-    cols, ext = [[], [], [], []], [[] for _ in extras]
-    for r in range(shard.world):
-        lo, hi = shard_bounds(shard.n, shard.world, r)
-        for c, part in zip(cols, layout.unpack(gathered[r, :nrec], hi - lo)):
-            c.append(part)
-        for k in range(len(extras)):
-            ext[k].append(gathered[r, nrec + k * shard.width: nrec + k * shard.width + (hi - lo)].view(np.float64))
-    a_end, p_end, p_max, bad = (np.concatenate(c) for c in cols)
-    ext = [np.concatenate(e) for e in ext]
+            a_end[idx], p_end[idx], p_max[idx], bad[idx] = res.a_end, res.p_end, res.p_max, res.first_bad_step
+        if waves:                               # columns j of p_wave_end, then of p_wave_max
+            wcols = np.full((nb, 2 * n_waves), np.nan)
+            if res is not None:
+                wcols[idx, :n_waves], wcols[idx, n_waves:] = res.p_wave_end, res.p_wave_max
+            extras += [wcols[:, k] for k in range(2 * n_waves)]
+        return dict(a_end=a_end, p_end=p_end, p_max=p_max, first_bad_step=bad, extras=extras,
+                    elapsed_ms=(0.0 if res is None else res.elapsed_ms))
+
+    local, (a_end, p_end, p_max, bad), ext = exchange_blocks(share, layout, record, n_extras + (2 * n_waves if waves else 0))
     ok = bad != NEVER_RAN
     full = None
     if ok.any():
         w_end = w_max = None
         if waves:
-            w = np.stack(ext[n_user:], axis=1)[ok].astype(layout.dtype)
+            w = np.stack(ext[n_extras:], axis=1)[ok].astype(layout.dtype)
             w_end, w_max = np.ascontiguousarray(w[:, :n_waves]), np.ascontiguousarray(w[:, n_waves:])
         full = SweepResult(a_end[ok], p_end[ok], p_max[ok], bad[ok], int(run_kw["n_steps"]), int(run_kw["save_every"]),
-                           0.0 if res is None else res.elapsed_ms, None, w_end, w_max)
-    return full, ok, ext[:n_user]
+                           local["elapsed_ms"], None, w_end, w_max)
+    return full, ok, ext[:n_extras]
 
 
 # ---- the engine call shared by the drivers ------------------------------------------------------------------
@@ -253,7 +215,7 @@ def _sweep_gain(*, cfg, lam1, grid_axes, gamma, alpha, p0, ph0, dispersion, pm_c
         raise ValueError("dbeta_producer must be 'auto', 'host' or 'device'")
     ax2, ax3 = np.atleast_1d(grid_axes[0]), np.atleast_1d(grid_axes[1])
     N = ax2.size * ax3.size
-    shard = _Shard(N, device)
+    shard = Share(N, device)
     gain = np.full(N, np.nan)
     nb = shard.hi - shard.lo
     try:
@@ -263,7 +225,6 @@ def _sweep_gain(*, cfg, lam1, grid_axes, gamma, alpha, p0, ph0, dispersion, pm_c
         a0 = make_initial_amplitudes(p0, ph0)
         fiber, grid, pm = pre["fiber"], pre["grid"], pre["pm"].config
         producer = _pick_producer(dbeta_producer, N, fiber.dispersion, pm)
-        dbeta_m, ok = _grid_dbeta(lam1, ax2, ax3, fiber.dispersion, pm, producer, shard.device, shard.lo, shard.hi)
         n_steps = n_steps_of(fiber.length_m, grid.dz_m)
         if n_steps < 1:
             raise ValueError("no steps")
@@ -280,16 +241,24 @@ def _sweep_gain(*, cfg, lam1, grid_axes, gamma, alpha, p0, ph0, dispersion, pm_c
             except Exception:
                 cd = np.full(N, np.nan)
         return gain, cd, None
-    extras = []
-    if caller_dbeta is not None:
+
+    def inputs():
         try:
-            cd, _ = _grid_dbeta(lam1, ax2, ax3, caller_dbeta[0], caller_dbeta[1],
-                                _pick_producer(dbeta_producer, N, caller_dbeta[0], caller_dbeta[1]), shard.device,
-                                shard.lo, shard.hi)
-        except Exception:
-            cd = np.full(nb, np.nan)
-        extras = [cd]
-    res, ok_full, extras_full = _run_block(shard, ok, dbeta_m, extras=extras, devices=devices, **run_kw)
+            dbeta_m, ok = _grid_dbeta(lam1, ax2, ax3, fiber.dispersion, pm, producer, shard.device, shard.lo, shard.hi)
+        except Exception:       # this block's producer failed (e.g. a native error on this rank only): its points are NaN
+            dbeta_m, ok = np.full(nb, np.nan), np.zeros(nb, dtype=bool)
+        extras = []
+        if caller_dbeta is not None:
+            try:
+                cd, _ = _grid_dbeta(lam1, ax2, ax3, caller_dbeta[0], caller_dbeta[1],
+                                    _pick_producer(dbeta_producer, N, caller_dbeta[0], caller_dbeta[1]), shard.device,
+                                    shard.lo, shard.hi)
+            except Exception:
+                cd = np.full(nb, np.nan)
+            extras = [cd]
+        return ok, dbeta_m, None, extras
+
+    res, ok_full, extras_full = _run_block(shard, inputs, n_extras=int(caller_dbeta is not None), devices=devices, **run_kw)
     if res is not None:
         gain[ok_full] = res.gain(p0[2], mode=gain_mode, unit=gain_unit, device=shard.device)
     return gain, (extras_full[0] if extras_full else None), res
@@ -329,7 +298,7 @@ def plot_max_signal_gain_vs_lambda_signal(*, cfg: SimulationConfig, lambda_p1_m:
     """
     lam1, lam2 = float(lambda_p1_m), float(lambda_p2_m)
     lam3, p0, ph0 = _check_sweep_inputs(lambda_signal_m, p_in, phase_in)
-    unit = _norm_choice(gain_unit, "gain_unit", ("db", "linear"))
+    unit = check_gain(unit=gain_unit)
     xs = _norm_choice(xscale, "xscale", ("linear", "log"))
     ys = _norm_choice(yscale, "yscale", ("linear", "log"))
     if ys == "log" and unit == "db":
@@ -379,7 +348,7 @@ def plot_max_gain_and_dbeta_vs_lambda_signal(*, cfg: SimulationConfig, lambda_p1
     lam3, p0, ph0 = _check_sweep_inputs(lambda_signal_m, p_in, phase_in)
     if dispersion is None:
         raise ValueError("dispersion must be provided to compute dBeta(λ3)")
-    unit = _norm_choice(gain_unit, "gain_unit", ("db", "linear"))
+    unit = check_gain(unit=gain_unit)
     xs = _norm_choice(xscale, "xscale", ("linear", "log"))
     ysg = _norm_choice(yscale_gain, "yscale_gain", ("linear", "log"))
     ysd = _norm_choice(yscale_dbeta, "yscale_dbeta", ("linear", "log"))
@@ -494,9 +463,7 @@ def scan_dbeta_seeded_signal(*, cfg: SimulationConfig, delta_beta: Sequence[floa
     gain_idler (the idler's metric over the SIGNAL's input power p_in[2], its Gi definition :83, :150), best_gain_idler
     (that gain at best_index) and p_wave_metric (N, n_waves), the gain_mode metric of every wave.
     """
-    if gain_mode not in ("end", "max"):
-        raise ValueError(f"Unknown gain_mode={gain_mode!r}. Use 'end' or 'max'.")
-    unit = _norm_choice(gain_unit, "gain_unit", ("db", "linear"))
+    unit = check_gain(gain_mode, gain_unit)
     db = np.asarray(delta_beta, dtype=float)
     if db.ndim != 1 or db.size == 0:
         raise ValueError("delta_beta must be a non-empty 1D sequence")
@@ -505,15 +472,14 @@ def scan_dbeta_seeded_signal(*, cfg: SimulationConfig, delta_beta: Sequence[floa
                    phase_matching_cfg=PhaseMatchingConfig(method=PhaseMatchingMethod.PROVIDED, provided_delta_beta=0.0),
                    beta_legacy=None, length_unit=length_unit)
     scale, L, dz_m = pre["scale"], pre["fiber"].length_m, pre["grid"].dz_m
-    shard = _Shard(db.size, device)
+    shard = Share(db.size, device)
     gam, alp = np.asarray(gamma, dtype=float) / scale, np.asarray(alpha, dtype=float) / scale
     for name, v in (("gamma", gam), ("alpha", alp)):
         if v.ndim > 1 or (v.ndim == 1 and v.shape[0] not in (1, db.size)):
             raise ValueError(f"{name} must be a scalar or have one entry per delta_beta point")
-    res, _, _ = _run_block(shard, np.ones(shard.hi - shard.lo, dtype=bool), shard.block(db / scale), dtype=dtype,
-                           devices=devices, z_max=L, n_steps=n_steps_of(L, dz_m), save_every=cfg.save_every,
-                           check_nan=bool(cfg.check_nan), gamma=shard.block(gam), alpha=shard.block(alp),
-                           a0=make_initial_amplitudes(p0, ph0), wave_summary=bool(with_idler))
+    res, _, _ = _run_block(shard, lambda: (None, db[shard.lo:shard.hi] / scale, None, ()), dtype=dtype, devices=devices,
+                           z_max=L, n_steps=n_steps_of(L, dz_m), save_every=cfg.save_every, check_nan=bool(cfg.check_nan),
+                           gamma=gam, alpha=alp, a0=make_initial_amplitudes(p0, ph0), wave_summary=bool(with_idler))
     gain, bi, bg, nf = res.summary(p0[2], mode=gain_mode, unit=unit, device=shard.device)
     secs = max(res.elapsed_ms, 1e-9) * 1e-3
     out = dict(delta_beta=db, gain=gain, best_index=bi, best_delta_beta=(float(db[bi]) if bi >= 0 else float("nan")),
@@ -539,8 +505,7 @@ def seeded_mismatch_scan(gain_mode: GainMode = "end", *, device: Optional[int] =
     from .constants import c as c_light
     from .phase_matching import compute_phase_mismatch
     mode = gain_mode
-    if mode not in ("end", "max"):
-        raise ValueError(f"Unknown gain_mode={gain_mode!r}. Use 'end' or 'max'.")
+    check_gain(mode)
     cfg = custom_simulation_config(z_max=0.5, dz=1e-3)
     gamma, alpha, P1_total = 10.0, 0.0, 0.1
     p_in = np.array([P1_total, P1_total, 1e-5, 0.0])
@@ -554,9 +519,9 @@ def seeded_mismatch_scan(gain_mode: GainMode = "end", *, device: Optional[int] =
                        beta_legacy=beta0 * np.ones(4) + np.array([0.0, 0.0, 0.0, d]), length_unit="km")
         dbeta_m[k] = compute_phase_mismatch(omega, None, pre["pm"].config).delta_beta
     L, dz_m = pre["fiber"].length_m, pre["grid"].dz_m
-    shard = _Shard(delta.size, device)
+    shard = Share(delta.size, device)
     a0 = make_initial_amplitudes(p_in, None)
-    res, _, _ = _run_block(shard, np.ones(shard.hi - shard.lo, dtype=bool), shard.block(dbeta_m), devices=devices,
+    res, _, _ = _run_block(shard, lambda: (None, dbeta_m[shard.lo:shard.hi], None, ()), devices=devices,
                            z_max=L, n_steps=n_steps_of(L, dz_m), save_every=cfg.save_every, check_nan=bool(cfg.check_nan),
                            gamma=gamma / 1e3, alpha=alpha / 1e3, a0=a0, wave_summary=True)
     metric = res.p_wave_max if mode == "max" else res.p_wave_end
@@ -598,9 +563,7 @@ def scan_gain_grid(*, cfg: SimulationConfig, lambda_p1_m: float, lambda_p2_m: Se
     or several of this process; under a ``torch.distributed`` process group the ranks split the grid.  Returns dict(gain (Ny, Nx), dbeta (Ny, Nx) in 1/length_unit,
     best_index (iy, ix) | None, best_gain, n_finite, result=SweepResult | None).
     """
-    if gain_mode not in ("end", "max"):
-        raise ValueError(f"Unknown gain_mode={gain_mode!r}. Use 'end' or 'max'.")
-    unit = _norm_choice(gain_unit, "gain_unit", ("db", "linear"))
+    unit = check_gain(gain_mode, gain_unit)
     lam3, p0, ph0 = _check_sweep_inputs(lambda_signal_m, p_in, phase_in)
     lam2 = np.asarray(list(lambda_p2_m), dtype=float)
     if lam2.ndim != 1 or lam2.size == 0 or not np.all(np.isfinite(lam2)) or np.any(lam2 <= 0.0):
@@ -637,9 +600,7 @@ def scan_six_wave_grid(*, cfg: SimulationConfig, lambda_p1_m: float, lambda_p2_m
     dbeta2 (Nx,), a_end (Ny, Nx, 6), first_bad_step (Ny, Nx), result=SweepResult).  The 6-wave model is build-defined:
     with pair 2 dark every row equals the 4-wave run at dbeta1 (tested), beyond that parity is unpinned.
     """
-    if gain_mode not in ("end", "max"):
-        raise ValueError(f"Unknown gain_mode={gain_mode!r}. Use 'end' or 'max'.")
-    unit = _norm_choice(gain_unit, "gain_unit", ("db", "linear"))
+    unit = check_gain(gain_mode, gain_unit)
     p0 = np.asarray(list(p_in), dtype=float)
     if p0.shape != (6,) or not np.all(np.isfinite(p0)) or np.any(p0 < 0.0):
         raise ValueError("p_in must hold six finite non-negative powers [p1, p2, s1, i1, s2, i2]")
@@ -664,19 +625,19 @@ def scan_six_wave_grid(*, cfg: SimulationConfig, lambda_p1_m: float, lambda_p2_m
     db1 = delta_beta_symmetric_array(wd, O1, disp_m, even_orders=even_orders)      # per metre
     db2 = delta_beta_symmetric_array(wd, O2, disp_m, even_orders=even_orders)
     dbeta_producer = _pick_producer(dbeta_producer, O1.size * O2.size, disp_m, None, even_orders=even_orders)
-    shard = _Shard(O1.size * O2.size, device)
-    if shard.hi == shard.lo:
-        d1_blk, d2_blk = np.zeros(0), np.zeros(0)
-    elif dbeta_producer == "device":     # this block's (dbeta_1, dbeta_2) from the GPU producer (psa_dbeta_pairs_f64)
-        from . import _native
-        d1_blk, d2_blk = _native.dbeta_pairs_host(_native.dbeta_model(disp_m, None, even_orders=even_orders), wd, O1, O2,
-                                                  first=shard.lo, n_points=shard.hi - shard.lo, device=shard.device)
-    else:
+    shard = Share(O1.size * O2.size, device)
+
+    def inputs():
+        if dbeta_producer == "device" and shard.hi > shard.lo:   # the block's (dbeta_1, dbeta_2) from psa_dbeta_pairs_f64
+            from . import _native
+            d1, d2 = _native.dbeta_pairs_host(_native.dbeta_model(disp_m, None, even_orders=even_orders), wd, O1, O2,
+                                              first=shard.lo, n_points=shard.hi - shard.lo, device=shard.device)
+            return None, d1, d2, ()
         i = np.arange(shard.lo, shard.hi)
-        d1_blk, d2_blk = db1[i // O2.size], db2[i % O2.size]
+        return None, db1[i // O2.size], db2[i % O2.size], ()
+
     from .sweep import initial_amplitudes
-    res, _, _ = _run_block(shard, np.ones(shard.hi - shard.lo, dtype=bool), d1_blk, dbeta2_blk=d2_blk, n_waves=6,
-                           devices=devices, z_max=fiber.length_m, n_steps=n_steps_of(fiber.length_m, grid.dz_m),
+    res, _, _ = _run_block(shard, inputs, n_waves=6, devices=devices, z_max=fiber.length_m, n_steps=n_steps_of(fiber.length_m, grid.dz_m),
                            save_every=cfg.save_every, check_nan=bool(cfg.check_nan), gamma=fiber.gamma_W_m,
                            alpha=fiber.alpha_1_m, a0=initial_amplitudes(p0, ph))
     gain = res.gain(p0[2], mode=gain_mode, unit=unit, device=shard.device)
@@ -708,9 +669,7 @@ def scan_copier_psa_phase(*, psa_cfg: SimulationConfig, psa_delta_beta, gamma: f
     gain_max_db, gain_min_db, extinction_db (max - min over the finite gains, dB), result=ChainResult)."""
     from .simulation import mid_stage
     from .sweep import FibreSpan, rk4_chain
-    if gain_mode not in ("end", "max"):
-        raise ValueError(f"Unknown gain_mode={gain_mode!r}. Use 'end' or 'max'.")
-    unit = _norm_choice(gain_unit, "gain_unit", ("db", "linear"))
+    unit = check_gain(gain_mode, gain_unit)
     ph = np.linspace(0.0, 2.0 * np.pi, 32, endpoint=False) if phase is None else np.asarray(phase, dtype=float)
     if ph.ndim != 1 or ph.size == 0 or not np.all(np.isfinite(ph)):
         raise ValueError("phase must be a non-empty 1D sequence of finite values")

@@ -14,10 +14,11 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _native
+from ._partition import CHAIN_AXES, SWEEP_AXES, over_devices
 from .config import AdaptiveConfig, n_steps_of
 
-__all__ = ["AdaptiveResult", "ChainResult", "FibreSpan", "SweepResult", "initial_amplitudes", "rk4_chain", "rk4_sweep",
-           "rk45_sweep"]
+__all__ = ["AdaptiveResult", "ChainResult", "FibreSpan", "SweepResult", "check_gain", "initial_amplitudes", "rk4_chain",
+           "rk4_sweep", "rk45_sweep"]
 
 
 def initial_amplitudes(p_in, phase_in=None) -> np.ndarray:
@@ -30,6 +31,17 @@ def initial_amplitudes(p_in, phase_in=None) -> np.ndarray:
         if np.any(ph != 0.0):
             amp = amp * np.exp(1j * ph)
     return amp
+
+
+def check_gain(mode: str = "max", unit: str = "dB") -> str:
+    """The gain rules every summary accepts: gain_mode "end" | "max", gain_unit "dB" | "linear" (any case, spaces
+    ignored).  Returns the unit lower-cased; raises ValueError otherwise."""
+    if mode not in ("end", "max"):
+        raise ValueError(f"Unknown gain_mode={mode!r}. Use 'end' or 'max'.")
+    u = str(unit).strip().lower()
+    if u not in ("db", "linear"):
+        raise ValueError("gain_unit must be 'dB' or 'linear'")
+    return u
 
 
 @dataclass
@@ -52,11 +64,7 @@ class SweepResult:
     def summary(self, p0_sig: float, *, mode: str = "max", unit: str = "dB", device: int = 0, wave: int = 2):
         """(gain[N], best_index, best_gain, n_finite) -- gain_mode "end" | "max" (scan_mismtach.py:27-40).  ``wave`` other
         than 2 (the signal) reduces that wave's column of p_wave_end / p_wave_max (a sweep run with wave_summary=True)."""
-        if mode not in ("end", "max"):
-            raise ValueError(f"Unknown gain_mode={mode!r}. Use 'end' or 'max'.")
-        u = str(unit).strip().lower()
-        if u not in ("db", "linear"):
-            raise ValueError("gain_unit must be 'dB' or 'linear'")
+        u = check_gain(mode, unit)
         if int(wave) == 2:
             metric = self.p_max if mode == "max" else self.p_end
         else:
@@ -71,46 +79,6 @@ class SweepResult:
         if metric.dtype != np.float32:
             metric = metric.astype(np.float64, copy=False)
         return _native.gain_summary_host(metric, self.first_bad_step, float(p0_sig), gain_db=(u == "db"), device=device)
-
-
-def _cut(x, lo: int, hi: int, n: int, per_point_ndim: int):
-    """The [lo, hi) block of a per-point argument (leading dimension n); scalars / single rows pass through."""
-    if x is None:
-        return None
-    x = np.asarray(x)
-    return x[lo:hi] if (x.ndim == per_point_ndim and x.shape[0] == n and n > 1) else x
-
-
-def _sweep_over_devices(devices, dbeta, **kw) -> dict:
-    """One host thread per device, each integrating a contiguous block through ``psa_rk4_sweep_*(device=k)`` (ctypes
-    drops the GIL for the duration of the call; the C-ABI is thread-safe for distinct devices).  Blocks are the same
-    split the multi-process path uses (``distributed.shard_bounds``): the first ``N % len(devices)`` get one point more."""
-    from concurrent.futures import ThreadPoolExecutor
-    n, k = int(dbeta.shape[0]), len(devices)
-    base, rem = divmod(n, k)
-    bounds, lo = [], 0
-    for r in range(k):
-        hi = lo + base + (1 if r < rem else 0)
-        bounds.append((lo, hi))
-        lo = hi
-
-    def run(r):
-        lo, hi = bounds[r]
-        if hi == lo:
-            return None
-        sub = dict(kw)
-        for name, nd in (("gamma", 1), ("alpha", 1), ("dbeta2", 1), ("a0", 2)):
-            sub[name] = _cut(kw.get(name), lo, hi, n, nd)
-        return _native.sweep_host(dbeta[lo:hi], device=int(devices[r]), **sub)
-
-    with ThreadPoolExecutor(max_workers=k) as pool:
-        parts = [p for p in pool.map(run, range(k)) if p is not None]
-    out = {key: np.concatenate([p[key] for p in parts]) for key in ("a_end", "p_end", "p_max", "first_bad_step")}
-    out["traj"] = np.concatenate([p["traj"] for p in parts]) if parts[0]["traj"] is not None else None
-    for key in ("p_wave_end", "p_wave_max"):
-        out[key] = np.concatenate([p[key] for p in parts]) if parts[0].get(key) is not None else None
-    out["elapsed_ms"] = max(p["elapsed_ms"] for p in parts)
-    return out
 
 
 def rk4_sweep(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps: Optional[int] = None,
@@ -139,11 +107,11 @@ def rk4_sweep(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps: Optio
         raise ValueError("devices must name at least one GPU")
     db = np.atleast_1d(np.asarray(dbeta))
     if devs is not None and len(devs) > 1 and db.ndim == 1 and db.shape[0] > 1:
-        r = _sweep_over_devices(devs, db, **kw)
+        r = over_devices(_native.sweep_host, devs, db.shape[0], SWEEP_AXES, dict(kw, dbeta=db))
     else:
         r = _native.sweep_host(dbeta, device=(devs[0] if devs else device), **kw)
     return SweepResult(r["a_end"], r["p_end"], r["p_max"], r["first_bad_step"], int(n_steps), int(save_every),
-                       r["elapsed_ms"], r["traj"], r.get("p_wave_end"), r.get("p_wave_max"))
+                       r["elapsed_ms"], r.get("traj"), r.get("p_wave_end"), r.get("p_wave_max"))
 
 
 # ---- chains of fibre spans ------------------------------------------------------------------------------------------
@@ -191,47 +159,6 @@ def _span_column(values, S: int, N: int, name: str, dtype) -> np.ndarray:
     if all(a.shape[0] == 1 for a in arrs) and N != 1:
         return np.array([a[0] for a in arrs], dtype=dtype)
     return np.stack([np.broadcast_to(a, (N,)) for a in arrs]).astype(dtype)
-
-
-def _chain_over_devices(devices, N: int, kw: dict) -> dict:
-    """The points of a chain split over several GPUs of this process, as _sweep_over_devices does for one span."""
-    from concurrent.futures import ThreadPoolExecutor
-    k = len(devices)
-    base, rem = divmod(N, k)
-    bounds, lo = [], 0
-    for r in range(k):
-        hi = lo + base + (1 if r < rem else 0)
-        bounds.append((lo, hi))
-        lo = hi
-
-    def cut(x, lo, hi, axis):
-        if x is None:
-            return None
-        x = np.asarray(x)
-        if x.ndim > axis and x.shape[axis] == N and N > 1:
-            return np.take(x, np.arange(lo, hi), axis=axis)
-        return x
-
-    def run(r):
-        lo, hi = bounds[r]
-        if hi == lo:
-            return None
-        sub = dict(kw)
-        for name, axis in (("dbeta", 1), ("dbeta2", 1), ("gamma", 1), ("alpha", 1)):
-            sub[name] = cut(kw.get(name), lo, hi, axis)
-        a0 = np.asarray(kw["a0"])
-        sub["a0"] = a0[lo:hi] if a0.ndim == 2 and a0.shape[0] == N and N > 1 else a0
-        tr = kw.get("transfers")
-        sub["transfers"] = None if tr is None else (tr[:, lo:hi] if tr.ndim == 3 else tr)
-        return _native.chain_host(device=int(devices[r]), **sub)
-
-    with ThreadPoolExecutor(max_workers=k) as pool:
-        parts = [p for p in pool.map(run, range(k)) if p is not None]
-    out = {key: np.concatenate([p[key] for p in parts]) for key in ("a_end", "p_end", "p_max", "first_bad_step")}
-    for key in ("traj", "p_wave_end", "p_wave_max"):
-        out[key] = np.concatenate([p[key] for p in parts]) if parts[0].get(key) is not None else None
-    out["elapsed_ms"] = max(p["elapsed_ms"] for p in parts)
-    return out
 
 
 def rk4_chain(spans: Sequence[FibreSpan], *, a0, transfers=None, save_every: int = 10, check_nan: bool = True,
@@ -297,7 +224,7 @@ def rk4_chain(spans: Sequence[FibreSpan], *, a0, transfers=None, save_every: int
     if devs is not None and len(devs) == 0:
         raise ValueError("devices must name at least one GPU")
     if devs is not None and len(devs) > 1 and N > 1:
-        r = _chain_over_devices(devs, N, kw)
+        r = over_devices(_native.chain_host, devs, N, CHAIN_AXES, kw)
     else:
         r = _native.chain_host(device=(devs[0] if devs else device), **kw)
     rows = steps // save_every + 1
@@ -306,7 +233,7 @@ def rk4_chain(spans: Sequence[FibreSpan], *, a0, transfers=None, save_every: int
     z0 = np.concatenate([[0.0], np.cumsum(lens)])
     z_out = np.concatenate([z0[k] + np.linspace(0.0, lens[k], int(steps[k]) + 1)[::save_every] for k in range(S)])
     return ChainResult(r["a_end"], r["p_end"], r["p_max"], r["first_bad_step"], int(step_off[-1]), save_every,
-                       r["elapsed_ms"], r["traj"], r.get("p_wave_end"), r.get("p_wave_max"), z_out=z_out,
+                       r["elapsed_ms"], r.get("traj"), r.get("p_wave_end"), r.get("p_wave_max"), z_out=z_out,
                        row_offsets=row_off, step_offsets=step_off)
 
 
@@ -335,14 +262,8 @@ class AdaptiveResult:
         return self.summary(p0_sig, mode=mode, unit=unit, device=device)[0]
 
     def summary(self, p0_sig: float, *, mode: str = "max", unit: str = "dB", device: int = 0):
-        """(gain[N], best_index, best_gain, n_finite), reduced on the GPU by psa_gain_summary_f64."""
-        if mode not in ("end", "max"):
-            raise ValueError(f"Unknown gain_mode={mode!r}. Use 'end' or 'max'.")
-        u = str(unit).strip().lower()
-        if u not in ("db", "linear"):
-            raise ValueError("gain_unit must be 'dB' or 'linear'")
-        metric = np.ascontiguousarray(self.p_max if mode == "max" else self.p_end, dtype=np.float64)
-        return _native.gain_summary_host(metric, self.first_bad_step, float(p0_sig), gain_db=(u == "db"), device=device)
+        """(gain[N], best_index, best_gain, n_finite): SweepResult's reduction of the signal's p_max / p_end."""
+        return SweepResult.summary(self, p0_sig, mode=mode, unit=unit, device=device)
 
 
 def rk45_sweep(dbeta, *, z_max: float, tol: AdaptiveConfig = AdaptiveConfig(), gamma, alpha, a0, dbeta2=None,

@@ -51,6 +51,38 @@ def test_rk4_chain_rules():
         rk4_chain([FibreSpan(10.0, n_steps=100, dbeta2=0.1)], a0=A0)
 
 
+def test_devices_list_splits_the_chain_points_over_threads(monkeypatch):
+    """rk4_chain(devices=[...]) without a GPU: a spy chain_host sees contiguous blocks (4, 4, 3 of 11 points), every
+    per-point argument cut on its own axis, broadcast ones whole, and the concatenated outputs come back in point order."""
+    seen = []
+
+    def spy(dbeta, *, device, n_steps, seg_len, gamma, alpha, a0, transfers, **kw):
+        n = dbeta.shape[1]
+        seen.append((int(device), n, dbeta.shape, gamma.shape, alpha.shape, a0.shape, transfers.shape, n_steps.shape))
+        return dict(a_end=np.asarray(a0, dtype=complex), p_end=dbeta[0].copy(), p_max=gamma[1].copy(),
+                    first_bad_step=np.full(n, -1, dtype=np.int64), traj=None, elapsed_ms=float(device) + 1.0,
+                    p_wave_end=transfers[0].real.copy(), p_wave_max=None)
+
+    monkeypatch.setattr(nat, "chain_host", spy)
+    rng = np.random.default_rng(4)
+    N = 11
+    db0, gam1 = np.linspace(-0.02, 0.02, N), rng.uniform(5e-3, 2e-2, N)
+    a0 = np.sqrt(rng.uniform(1e-5, 0.5, (N, 4))).astype(complex)
+    T = np.exp(1j * rng.uniform(-3, 3, (N, 4)))
+    spans = [FibreSpan(10.0, n_steps=100, dbeta=db0, gamma=0.01, alpha=1e-4),
+             FibreSpan(20.0, n_steps=200, dbeta=0.001, gamma=gam1, alpha=2e-4),
+             FibreSpan(5.0, n_steps=50, dbeta=-0.003, gamma=0.01, alpha=1e-4)]
+    one = rk4_chain(spans, a0=a0, transfers=[T, np.ones(4)], devices=[0])
+    seen.clear()
+    many = rk4_chain(spans, a0=a0, transfers=[T, np.ones(4)], devices=[0, 1, 2])
+    assert sorted(seen) == [(d, n, (3, n), (3, n), (3,), (n, 4), (2, n, 4), (3,)) for d, n in ((0, 4), (1, 4), (2, 3))]
+    assert np.array_equal(many.a_end, a0) and np.array_equal(many.p_end, db0) and np.array_equal(many.p_max, gam1)
+    assert np.array_equal(many.p_wave_end, T.real) and many.p_wave_max is None and many.traj is None
+    assert many.elapsed_ms == 3.0
+    for f in ("a_end", "p_end", "p_max", "first_bad_step", "p_wave_end", "z_out", "row_offsets", "step_offsets"):
+        assert np.array_equal(getattr(one, f), getattr(many, f)), f
+
+
 def test_mid_stage():
     t = mid_stage((0.0, -10.0, 3.0, 0.0), (0.0, 0.0, np.pi / 2, 0.1))
     np.testing.assert_allclose(np.abs(t) ** 2, 10.0 ** (np.array([0.0, -10.0, 3.0, 0.0]) / 10.0), rtol=1e-15)

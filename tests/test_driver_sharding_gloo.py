@@ -9,6 +9,8 @@ test-suite's oracle -- inside the worker process only (``_install_cpu_executor``
 import os
 import socket
 import sys
+import time
+from datetime import timedelta
 
 import numpy as np
 import pytest
@@ -226,3 +228,112 @@ def test_devices_list_splits_the_points_over_threads():
             sweep.rk4_sweep(db, devices=[], **kw)
     finally:
         nat.sweep_host, nat.gain_summary_host = saved
+
+
+# ---- a failure on one rank only: every rank returns or every rank raises, none waits in the collective -----------------
+def _spawn_bounded(fn, world, args, deadline_s=150.0):
+    """Workers report through files; a rank left waiting in the gather fails the test at the deadline instead of hanging."""
+    ctx = mp.spawn(fn, args=args, nprocs=world, join=False)
+    end = time.monotonic() + deadline_s
+    while not ctx.join(timeout=2):
+        if time.monotonic() > end:
+            for p in ctx.processes:
+                p.kill()
+            pytest.fail("a rank is still running past the deadline (stuck in the collective)")
+
+
+def _init_group(rank, world, port):
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=timedelta(seconds=60))
+    return dist
+
+
+def _grid_call():
+    from psa_amd import config, dispersion, scan_mismtach
+    g13 = np.load(os.path.join(GOLDEN, "G13.npz"))
+    dv = g13["disp"]
+    out = scan_mismtach.scan_gain_grid(cfg=config.custom_simulation_config(z_max=250.0, dz=0.25, save_every=5),
+                                       lambda_p1_m=1550e-9, lambda_p2_m=g13["lambda2"], lambda_signal_m=g13["lambda3"],
+                                       gamma=0.0115, alpha=1.0e-4, p_in=g13["grid_p_in"], dbeta_producer="device",
+                                       dispersion=dispersion.DispersionParams(omega_ref=dv[0], beta2=dv[1], beta3=dv[2],
+                                                                              beta4=dv[3]))
+    return out["gain"].reshape(-1), out["dbeta"].reshape(-1)
+
+
+def _worker_producer_fails(rank, world, port, out_dir):
+    """The device dbeta producer is replaced by the host one; under the group it raises on rank 1 only."""
+    for p in (ROOT, os.path.join(ROOT, "oracle")):
+        sys.path.insert(0, p)
+    import psa_amd._native as nat
+    from psa_amd import scan_mismtach
+    _install_cpu_executor()
+    real_model = nat.dbeta_model
+
+    def dbeta_model(disp, pm_cfg=None, **kw):
+        return dict(real_model(disp, pm_cfg, **kw), src=(disp, pm_cfg))
+
+    def dbeta_grid_host(model, lambda1_m, ax2, ax3, *, first=0, n_points=None, device=0):
+        import torch.distributed as dist
+        if dist.is_initialized() and dist.get_rank() == 1:
+            raise RuntimeError("injected: device producer out of memory")
+        return scan_mismtach._grid_dbeta(lambda1_m, ax2, ax3, *model["src"], "host", device, first, first + n_points)
+
+    nat.dbeta_model, nat.dbeta_grid_host = dbeta_model, dbeta_grid_host
+    whole = _grid_call()
+    dist = _init_group(rank, world, port)
+    try:
+        gain, dbeta = _grid_call()
+        np.savez(os.path.join(out_dir, f"rank{rank}.npz"), gain=gain, dbeta=dbeta, whole_gain=whole[0],
+                 whole_dbeta=whole[1])
+    finally:
+        dist.destroy_process_group()
+
+
+def test_a_failing_dbeta_producer_on_one_rank_makes_its_block_nan(tmp_path):
+    """scan_gain_grid under world 2, the block dbeta producer of rank 1 raising: every rank returns the same arrays, rank
+    1's block is NaN and rank 0's equals the unsharded call (the drivers' never-raise, NaN-per-point contract)."""
+    _spawn_bounded(_worker_producer_fails, 2, (2, _free_port(), str(tmp_path)))
+    r0, r1 = (np.load(tmp_path / f"rank{r}.npz") for r in range(2))
+    lo, hi = 0, 18                                                   # 4 x 9 grid: rank 0 holds points [0, 18)
+    for k in ("gain", "dbeta"):
+        assert np.array_equal(r0[k], r1[k], equal_nan=True), k
+        assert np.isnan(r0[k][hi:]).all(), k
+        assert np.array_equal(r0[k][lo:hi], r0["whole_" + k][lo:hi]), k
+    assert np.isfinite(r0["whole_gain"]).all()
+
+
+def _worker_sweep_fails(rank, world, port, out_dir):
+    for p in (ROOT, os.path.join(ROOT, "oracle")):
+        sys.path.insert(0, p)
+    import psa_amd._native as nat
+    from psa_amd import config, scan_mismtach
+    inner = _install_cpu_executor()
+
+    def sweep_host(dbeta, **kw):
+        if rank == 1:
+            raise MemoryError("injected: sweep failed on rank 1")
+        return inner(dbeta, **kw)
+
+    nat.sweep_host = sweep_host
+    dist = _init_group(rank, world, port)
+    try:
+        scan_mismtach.scan_dbeta_seeded_signal(cfg=config.custom_simulation_config(z_max=20.0, dz=0.1),
+                                               delta_beta=np.linspace(-0.05, 0.05, 9), gamma=0.0115, alpha=1e-4,
+                                               p_in=[0.5, 0.5, 1e-5, 1e-5])
+        outcome = "returned"
+    except Exception as exc:
+        outcome = f"{type(exc).__name__}: {exc}"
+    finally:
+        dist.destroy_process_group()
+    with open(os.path.join(out_dir, f"rank{rank}.txt"), "w") as f:
+        f.write(outcome)
+
+
+def test_a_failing_sweep_on_one_rank_raises_on_every_rank(tmp_path):
+    """scan_dbeta_seeded_signal under world 2 with rank 1's native sweep raising: rank 1 re-raises its own error, rank 0
+    raises a RuntimeError that names rank 1 -- and neither waits in the gather."""
+    _spawn_bounded(_worker_sweep_fails, 2, (2, _free_port(), str(tmp_path)))
+    r0, r1 = ((tmp_path / f"rank{r}.txt").read_text() for r in range(2))
+    assert r1 == "MemoryError: injected: sweep failed on rank 1"
+    assert r0.startswith("RuntimeError") and "[1]" in r0, r0
