@@ -55,10 +55,14 @@ extern "C" {
 #define PSA_E_FLAGS      -11  /* options that exclude each other (two of SPLIT_POINT / ONE_LANE / QUAD_POINT, F32_SCALAR + F32_PACKED, QUAD with 6 waves) */
 #define PSA_E_TOL        -12  /* psa_rk45_*: rtol < 100*DBL_EPSILON or not finite, atol <= 0 or not finite, h_max <= 0,
                                  first_step < 0 or not finite, max_steps < 1, n_out < 0 */
+#define PSA_E_NPAIRS     -13  /* psa_rk4_sweep_pairs_*: n_pairs outside 1..PSA_MAX_PAIRS */
 
 /* The most points one launch takes: a launch has at most 2^32 - 1 threads in x and the two-lane float64 layout uses two
  * per point.  (2^31 - 256 float64 records are 189 GB: a 288 GB MI355X holds them, so the limit is stated, not theoretical.) */
 #define PSA_MAX_POINTS   2147483392LL
+/* The most signal/idler pairs of the multi-channel sweep (psa_rk4_sweep_pairs_*): one lane per pair, a point within one
+ * 16-lane DPP row. */
+#define PSA_MAX_PAIRS    16
 
 /* ---- flags ----------------------------------------------------------------- */
 /* broadcast: the array has ONE entry used for every sweep point */
@@ -372,6 +376,39 @@ int psa_rk45_sweep_f64_dev(void *stream, int n_waves, int64_t n_points, double z
                            uint32_t flags, double *d_a_end_soa, double *d_p_sig_end, double *d_p_sig_max,
                            int32_t *d_status, double *d_z_end, int64_t *d_n_accepted, int64_t *d_n_rejected,
                            double *d_traj_soa);
+
+/* ---- the multi-channel sweep: two pumps and K = n_pairs signal/idler pairs (1 <= K <= PSA_MAX_PAIRS) ---------------
+ * Build-defined like the 6-wave model, which it extends: waves [p1, p2, s_1, i_1, ..., s_K, i_K],
+ * NW = 2 + 2K, pair k with its own mismatch dbeta_k.  With P_j = |A_j|^2, S = sum_j P_j, E_k(z) = 2 gamma exp(i dbeta_k z):
+ *   dA_p1/dz = (-alpha/2 + i gamma (2S - P_p1)) A_p1 + i conj(A_p2) sum_k E_k A_sk A_ik        (p2: p1 <-> p2)
+ *   dA_sk/dz = (-alpha/2 + i gamma (2S - P_sk)) A_sk + i conj(A_ik) conj(E_k) A_p1 A_p2        (ik: sk <-> ik)
+ * K = 1 is the reference's system (yaman_model.py:123-186), K = 2 the 6-wave model of psa_rk4_sweep_f64.  The channels
+ * couple through pump depletion and SPM/XPM only: FWM products between channels (signal-signal mixing) are NOT modelled.
+ * Classic fixed-step RK4 on z_i = i * z_max / n_steps with the save and NaN semantics of psa_rk4_sweep_f64; float64 only.
+ * One lane per pair, L = the power of two >= K (at least 2) lanes per point: K = 5 pays for 8 lanes.
+ *   dbeta       [N][n_pairs]            mismatch of every pair, 1/length
+ *   gamma, alpha  [N] | [1]
+ *   a0_re_im    [N][NW][2] | [1][NW][2]
+ *   a_end_re_im [N][NW][2]   state at the last saved row
+ *   p_wave_end  [N][NW]      |A_j|^2 at that row
+ *   p_wave_max  [N][NW]      max of |A_j|^2 over the saved rows incl. z = 0, NaN-propagating like np.max
+ *   first_bad_step [N]       as psa_rk4_sweep_f64 (PSA_OPT_CHECK_NAN, PSA_OPT_EXACT_STEP)
+ * All four outputs are always written.  flags: PSA_BCAST_GAMMA / ALPHA / A0, PSA_OPT_CHECK_NAN, PSA_OPT_EXACT_STEP,
+ * PSA_OPT_LOSSLESS (set by the host form itself for a broadcast alpha == 0) and PSA_OPT_BLOCK64; anything else (a layout,
+ * float32 or LDS flag) is PSA_E_FLAGS.  n_pairs outside 1..PSA_MAX_PAIRS: PSA_E_NPAIRS; L * n_points beyond the launch
+ * grid (2 * PSA_MAX_POINTS lanes): PSA_E_TOO_LARGE; the other codes as psa_rk4_sweep_f64.  All of it is checked before
+ * any device call; n_points == 0 is a successful no-op.  No trajectory rows, chains or adaptive form.
+ */
+int psa_rk4_sweep_pairs_f64(int device, int n_pairs, int64_t n_points, int64_t n_steps, double z_max,
+                            int32_t save_every, const double *dbeta, const double *gamma, const double *alpha,
+                            const double *a0_re_im, uint32_t flags, double *a_end_re_im, double *p_wave_end,
+                            double *p_wave_max, int64_t *first_bad_step, double *elapsed_ms_or_null);
+/* On device buffers, asynchronous on `stream`, no allocation and no synchronisation: d_dbeta_soa [n_pairs][N],
+ * d_a0_soa [2*NW][N | 1], d_a_end_soa [2*NW][N], d_p_wave_end_soa / d_p_wave_max_soa [NW][N], d_first_bad_step [N]. */
+int psa_rk4_sweep_pairs_f64_dev(void *stream, int n_pairs, int64_t n_points, int64_t n_steps, double z_max,
+                                int32_t save_every, const double *d_dbeta_soa, const double *d_gamma,
+                                const double *d_alpha, const double *d_a0_soa, uint32_t flags, double *d_a_end_soa,
+                                double *d_p_wave_end_soa, double *d_p_wave_max_soa, int64_t *d_first_bad_step);
 
 #ifdef __cplusplus
 }

@@ -40,6 +40,7 @@ OPT_ONE_LANE = 1 << 16
 OPT_TRAJ_LD = 1 << 17
 OPT_QUAD_POINT = 1 << 18
 MAX_POINTS = 2**31 - 256          # PSA_MAX_POINTS: the most points one launch takes
+MAX_PAIRS = 16                    # PSA_MAX_PAIRS: the most signal/idler pairs of the multi-channel sweep
 
 # every symbol the header declares, with (restype, argtypes)
 _P = C.c_void_p
@@ -83,6 +84,12 @@ _SIGS = {
                            + [_P] * 5 + [C.c_uint32] + [_P] * 9),
     "psa_rk45_sweep_f64_dev": (C.c_int, [_P, C.c_int, C.c_int64] + [C.c_double] * 5 + [C.c_int64, C.c_int64]
                                + [_P] * 5 + [C.c_uint32] + [_P] * 8),
+    # (device|stream, n_pairs, N, n_steps, z_max, save_every, dbeta, gamma, alpha, a0, flags, a_end, p_wave_end, p_wave_max,
+    #  first_bad [, elapsed_ms])
+    "psa_rk4_sweep_pairs_f64": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int32,
+                                          _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
+    "psa_rk4_sweep_pairs_f64_dev": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int32,
+                                              _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P]),
     "psa_yaman_rhs_f64": (C.c_int, [C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "psa_gain_summary_f64": (C.c_int, [C.c_int, C.c_int64, _P, _P, C.c_double, C.c_int, _P, _P, _P, _P]),
     "psa_gain_summary_f64_dev": (C.c_int, [_P, C.c_int64, _P, _P, C.c_double, C.c_int, _P, _P, _P, _P, _P]),
@@ -304,6 +311,57 @@ def sweep_waves_device(*, stream: int, n_waves: int, n_points: int, n_steps: int
               d_dbeta or None, d_dbeta2 or None, d_gamma or None, d_alpha or None, d_a0_soa or None, int(flags),
               d_a_end_soa or None, d_p_end or None, d_p_max or None, d_first_bad or None, d_traj_soa or None,
               d_p_wave_end_soa or None, d_p_wave_max_soa or None))
+
+
+def sweep_pairs_host(dbeta, *, n_steps: int, z_max: float, save_every: int, gamma, alpha, a0, check_nan: bool = True,
+                     exact_step: Optional[bool] = None, device: int = 0, extra_flags: int = 0) -> dict:
+    """N independent propagations of two pumps and K signal/idler pairs on the GPU (psa_rk4_sweep_pairs_f64; host buffers
+    in and out, float64).  The channels couple through pump depletion and SPM/XPM; signal-signal FWM is not modelled.
+
+    dbeta (N, K) with 1 <= K <= 16; gamma / alpha scalar or (N,); a0 (NW,) or (N, NW) complex, NW = 2 + 2K, waves
+    [p1, p2, s_1, i_1, ..., s_K, i_K].  exact_step None or True: the exact first_bad_step; False: the save block's last step.
+    Returns a_end (N, NW) complex, p_wave_end, p_wave_max (N, NW), first_bad_step (N,) int64, elapsed_ms (kernel only)."""
+    dbeta = np.ascontiguousarray(np.asarray(dbeta), dtype=np.float64)
+    if dbeta.ndim != 2 or not 1 <= dbeta.shape[1] <= MAX_PAIRS:
+        raise ValueError(f"dbeta must have shape (N, K) with 1 <= K <= {MAX_PAIRS}, got {dbeta.shape}")
+    N, K = (int(x) for x in dbeta.shape)
+    nw = 2 + 2 * K
+    a0 = np.ascontiguousarray(np.asarray(a0), dtype=np.complex128)
+    if a0.ndim == 1:
+        a0 = a0[None, :]
+    if a0.ndim != 2 or a0.shape[1] != nw:
+        raise ValueError(f"a0 must have shape ({nw},) or ({N}, {nw}) for {K} pairs, got {a0.shape}")
+    flags = int(extra_flags)
+    if a0.shape[0] == 1:
+        flags |= BCAST_A0
+    elif a0.shape[0] != N:
+        raise ValueError(f"a0 must have 1 or {N} rows, got {a0.shape[0]}")
+    gamma, gb = _prep(gamma, np.float64, N, "gamma")
+    alpha, ab = _prep(alpha, np.float64, N, "alpha")
+    flags |= (BCAST_GAMMA if gb else 0) | (BCAST_ALPHA if ab else 0)
+    if check_nan:
+        flags |= OPT_CHECK_NAN
+        if exact_step or exact_step is None:
+            flags |= OPT_EXACT_STEP
+    a_end = np.empty((N, nw), dtype=np.complex128)
+    w_end = np.empty((N, nw), dtype=np.float64)
+    w_max = np.empty((N, nw), dtype=np.float64)
+    bad = np.empty(N, dtype=np.int64)
+    ms = C.c_double(0.0)
+    _check(lib().psa_rk4_sweep_pairs_f64(int(device), K, N, int(n_steps), float(z_max), int(save_every), _ptr(dbeta),
+                                         _ptr(gamma), _ptr(alpha), _ptr(a0), flags, _ptr(a_end), _ptr(w_end), _ptr(w_max),
+                                         _ptr(bad), C.cast(C.byref(ms), C.c_void_p)))
+    return dict(a_end=a_end, p_wave_end=w_end, p_wave_max=w_max, first_bad_step=bad, elapsed_ms=ms.value)
+
+
+def sweep_pairs_device(*, stream: int, n_pairs: int, n_points: int, n_steps: int, z_max: float, save_every: int,
+                       d_dbeta_soa: int, d_gamma: int, d_alpha: int, d_a0_soa: int, flags: int, d_a_end_soa: int,
+                       d_p_wave_end_soa: int, d_p_wave_max_soa: int, d_first_bad: int) -> None:
+    """Asynchronous multi-channel launch on device pointers (ints), SoA layout -- see psa_rk4_sweep_pairs_f64_dev."""
+    _check(lib().psa_rk4_sweep_pairs_f64_dev(stream or None, int(n_pairs), int(n_points), int(n_steps), float(z_max),
+                                             int(save_every), d_dbeta_soa or None, d_gamma or None, d_alpha or None,
+                                             d_a0_soa or None, int(flags), d_a_end_soa or None, d_p_wave_end_soa or None,
+                                             d_p_wave_max_soa or None, d_first_bad or None))
 
 
 def chain_host(dbeta, *, n_steps, seg_len, save_every: int, gamma, alpha, a0, transfers=None, dbeta2=None,

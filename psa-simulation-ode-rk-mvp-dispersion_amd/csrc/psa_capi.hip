@@ -524,6 +524,92 @@ int sweep_host(int device, int n_waves, int64_t n_points, int64_t n_steps, doubl
     });
 }
 
+// ---- the multi-channel sweep (psa_rk4_sweep_pairs_f64*): two pumps and n_pairs signal/idler pairs -----------------------
+int validate_pairs(int n_pairs, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every, const void *dbeta,
+                   const void *gamma, const void *alpha, const void *a0, uint32_t flags, const void *a_end,
+                   const void *wave_end, const void *wave_max, const void *first_bad) {
+    if (n_pairs < 1 || n_pairs > PSA_MAX_PAIRS)
+        return fail(PSA_E_NPAIRS, "n_pairs must be in [1, %d], got %d", PSA_MAX_PAIRS, n_pairs);
+    if (n_points < 0) return fail(PSA_E_NPOINTS, "n_points must be >= 0, got %lld", (long long)n_points);
+    // a launch is at most 2^32 - 1 threads in x and a point takes L of them: the power of two >= n_pairs (at least 2)
+    const long long lanes_per_point = psa::pairs_lanes_per_point(n_pairs);
+    if (n_points > 2 * PSA_MAX_POINTS / lanes_per_point)
+        return fail(PSA_E_TOO_LARGE, "n_points %lld exceeds the launch limit of %lld points at %lld lanes per point",
+                    (long long)n_points, 2 * PSA_MAX_POINTS / lanes_per_point, lanes_per_point);
+    if (n_steps <= 0 || n_steps > 2147483647LL)
+        return fail(PSA_E_NSTEPS, "n_steps must be in [1, 2^31), got %lld", (long long)n_steps);
+    if (!(z_max > 0.0) || !std::isfinite(z_max)) return fail(PSA_E_ZMAX, "z_max must be positive");
+    if (save_every <= 0) return fail(PSA_E_SAVE_EVERY, "save_every must be a positive integer");
+    const uint32_t accepted = PSA_BCAST_GAMMA | PSA_BCAST_ALPHA | PSA_BCAST_A0 | PSA_OPT_CHECK_NAN | PSA_OPT_EXACT_STEP |
+                              PSA_OPT_LOSSLESS | PSA_OPT_BLOCK64;
+    if (flags & ~accepted)
+        return fail(PSA_E_FLAGS, "the multi-channel sweep takes the BCAST bits, CHECK_NAN, EXACT_STEP, LOSSLESS and BLOCK64 "
+                                 "only (no layout, float32 or LDS flag): 0x%x", (unsigned)(flags & ~accepted));
+    if (n_points > 0 && (!dbeta || !gamma || !alpha || !a0 || !a_end || !wave_end || !wave_max || !first_bad))
+        return fail(PSA_E_NULLPTR, "a required buffer pointer is NULL");
+    return PSA_OK;
+}
+
+int pairs_dev(void *stream, int n_pairs, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+              const double *d_dbeta, const double *d_gamma, const double *d_alpha, const double *d_a0_soa, uint32_t flags,
+              double *d_a_end_soa, double *d_wave_end, double *d_wave_max, int64_t *d_first_bad) {
+    int rc = validate_pairs(n_pairs, n_points, n_steps, z_max, save_every, d_dbeta, d_gamma, d_alpha, d_a0_soa, flags,
+                            d_a_end_soa, d_wave_end, d_wave_max, d_first_bad);
+    if (rc != PSA_OK) return rc;
+    if (n_points == 0) return PSA_OK;
+    psa::PairsArgs a;
+    a.dbeta = d_dbeta;
+    a.gamma = d_gamma;
+    a.alpha = d_alpha;
+    a.a0 = d_a0_soa;
+    a.a_end = d_a_end_soa;
+    a.p_wave_end = d_wave_end;
+    a.p_wave_max = d_wave_max;
+    a.first_bad = (long long *)d_first_bad;
+    a.n_points = n_points;
+    a.z_max = z_max;
+    a.n_steps = (int)n_steps;
+    a.save_every = save_every;
+    a.n_pairs = n_pairs;
+    a.gamma_stride = (flags & PSA_BCAST_GAMMA) ? 0 : 1;
+    a.alpha_stride = (flags & PSA_BCAST_ALPHA) ? 0 : 1;
+    a.a0_stride = (flags & PSA_BCAST_A0) ? 0 : 1;
+    a.a0_ld = (flags & PSA_BCAST_A0) ? 1 : n_points;
+    hipError_t e = psa::launch_sweep_pairs_f64((hipStream_t)stream, flags, a);
+    if (e != hipSuccess) return hip_fail(e, "rk4_sweep_pairs launch");
+    return PSA_OK;
+}
+
+int pairs_host(int device, int n_pairs, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+               const double *dbeta, const double *gamma, const double *alpha, const double *a0, uint32_t flags,
+               double *a_end, double *wave_end, double *wave_max, int64_t *first_bad, double *elapsed_ms) {
+    int rc = validate_pairs(n_pairs, n_points, n_steps, z_max, save_every, dbeta, gamma, alpha, a0, flags, a_end, wave_end,
+                            wave_max, first_bad);
+    if (rc != PSA_OK) return rc;
+    if (elapsed_ms) *elapsed_ms = 0.0;
+    if (n_points == 0) return PSA_OK;
+    const int nw = 2 + 2 * n_pairs;
+    const size_t N = (size_t)n_points;
+    if ((flags & PSA_BCAST_ALPHA) && alpha[0] == 0.0) flags |= PSA_OPT_LOSSLESS;   // the reference's alpha == 0.0 branch
+    const double *d_dbeta, *d_gamma, *d_alpha, *d_a0;
+    double *d_aend, *d_wend, *d_wmax;
+    int64_t *d_bad;
+    auto layout = [&](Staging<double> &sg) {
+        d_dbeta = sg.input_soa(dbeta, N, n_pairs);             // [N][n_pairs] -> [n_pairs][N]
+        d_gamma = sg.input(gamma, (flags & PSA_BCAST_GAMMA) ? 1 : N);
+        d_alpha = sg.input(alpha, (flags & PSA_BCAST_ALPHA) ? 1 : N);
+        d_a0 = sg.input_soa(a0, (flags & PSA_BCAST_A0) ? 1 : N, 2 * nw);
+        d_aend = sg.output_soa(a_end, N, 2 * nw);
+        d_wend = sg.output_soa(wave_end, N, nw);
+        d_wmax = sg.output_soa(wave_max, N, nw);
+        d_bad = sg.output(first_bad, N);
+    };
+    return host_call<double>(device, "the multi-channel RK4 sweep", elapsed_ms, layout, [&](hipStream_t st) {
+        return pairs_dev(st, n_pairs, n_points, n_steps, z_max, save_every, d_dbeta, d_gamma, d_alpha, d_a0, flags, d_aend,
+                         d_wend, d_wmax, d_bad);
+    });
+}
+
 // ---- fibre chains: S spans, one sweep launch + one epilogue (psa_chain.hip) each ------------------------------------
 template <typename T> struct EpilogueLaunch;
 template <> struct EpilogueLaunch<double> { static constexpr auto fn = psa::launch_chain_epilogue_f64; };
@@ -1223,6 +1309,21 @@ int psa_rk45_sweep_f64_dev(void *stream, int n_waves, int64_t n_points, double z
     return rk45_dev(stream, n_waves, n_points, z_max, rtol, atol, h_max, first_step, max_steps, n_out, d_dbeta, d_dbeta2,
                     d_gamma, d_alpha, d_a0_soa, flags, d_a_end_soa, d_p_sig_end, d_p_sig_max, d_status, d_z_end,
                     d_n_accepted, d_n_rejected, d_traj_soa, n_points);
+}
+
+int psa_rk4_sweep_pairs_f64(int device, int n_pairs, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+                            const double *dbeta, const double *gamma, const double *alpha, const double *a0_re_im,
+                            uint32_t flags, double *a_end_re_im, double *p_wave_end, double *p_wave_max,
+                            int64_t *first_bad_step, double *elapsed_ms_or_null) {
+    return pairs_host(device, n_pairs, n_points, n_steps, z_max, save_every, dbeta, gamma, alpha, a0_re_im, flags,
+                      a_end_re_im, p_wave_end, p_wave_max, first_bad_step, elapsed_ms_or_null);
+}
+int psa_rk4_sweep_pairs_f64_dev(void *stream, int n_pairs, int64_t n_points, int64_t n_steps, double z_max,
+                                int32_t save_every, const double *d_dbeta_soa, const double *d_gamma, const double *d_alpha,
+                                const double *d_a0_soa, uint32_t flags, double *d_a_end_soa, double *d_p_wave_end_soa,
+                                double *d_p_wave_max_soa, int64_t *d_first_bad_step) {
+    return pairs_dev(stream, n_pairs, n_points, n_steps, z_max, save_every, d_dbeta_soa, d_gamma, d_alpha, d_a0_soa, flags,
+                     d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step);
 }
 
 }  // extern "C"

@@ -49,6 +49,26 @@ struct AdaptiveArgs {
     long long a0_ld;
 };
 
+// Everything one multi-channel sweep launch needs (two pumps and n_pairs signal/idler pairs, NW = 2 + 2*n_pairs waves
+// [p1, p2, s_1, i_1, ..., s_K, i_K]; float64 only).  Strides as in SweepArgs; every output is always written.
+struct PairsArgs {
+    const double *dbeta;     // SoA [n_pairs][N]
+    const double *gamma;     // [N] | [1]
+    const double *alpha;     // [N] | [1]
+    const double *a0;        // SoA [2*NW][a0_ld]
+    double *a_end;           // SoA [2*NW][N]
+    double *p_wave_end;      // SoA [NW][N] |A_j|^2 at the last saved row
+    double *p_wave_max;      // SoA [NW][N] max over saved rows incl. z = 0 (NaN-propagating like np.max)
+    long long *first_bad;    // [N]
+    long long n_points;
+    double z_max;
+    int n_steps;
+    int save_every;
+    int n_pairs;             // 1..16
+    int gamma_stride, alpha_stride, a0_stride;  // 0 | 1
+    long long a0_ld;
+};
+
 enum CheckMode : int { CHECK_NONE = 0, CHECK_BLOCK = 1, CHECK_EXACT = 2 };
 
 // Sweep launchers (psa_rk4_f64.hip / psa_rk4_f32.hip): one kernel launch on s, nothing for n_points == 0.  They own
@@ -57,6 +77,11 @@ enum CheckMode : int { CHECK_NONE = 0, CHECK_BLOCK = 1, CHECK_EXACT = 2 };
 // caller has validated the arguments (the per-wave summary: no trajectory, no LDS staging, no BLOCK64).
 hipError_t launch_sweep_f64(hipStream_t s, int n_waves, uint32_t flags, const SweepArgs<double> &a);
 hipError_t launch_sweep_f32(hipStream_t s, int n_waves, uint32_t flags, const SweepArgs<float> &a);
+// Multi-channel sweep launcher (psa_rk4_pairs.hip): one launch on s of L * n_points lanes, L = pairs_lanes_per_point;
+// nothing for n_points == 0.  Reads PSA_OPT_CHECK_NAN / EXACT_STEP / LOSSLESS / BLOCK64 of `flags`; the caller has
+// validated the arguments (1 <= n_pairs <= 16, the lanes fit the launch grid).
+int pairs_lanes_per_point(int n_pairs);
+hipError_t launch_sweep_pairs_f64(hipStream_t s, uint32_t flags, const PairsArgs &a);
 // Adaptive sweep launcher (psa_rk45.hip): one launch on s, nothing for n_points == 0; PSA_OPT_LOSSLESS is the only flag
 // it reads and the dense-output rows come from a.traj being non-null.  The caller has validated the arguments.
 hipError_t launch_rk45_sweep_f64(hipStream_t s, int n_waves, uint32_t flags, const AdaptiveArgs<double> &a);

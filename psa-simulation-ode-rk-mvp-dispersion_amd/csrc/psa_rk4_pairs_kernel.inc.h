@@ -1,0 +1,293 @@
+// psa_rk4_pairs_kernel.inc.h -- float64 RK4 sweep of the MULTI-CHANNEL model: two pumps and K = 1..16 signal/idler pairs,
+// ONE LANE PER PAIR (gfx950).  Build-defined, like the 6-wave model it extends; K = 1 is the reference's
+// system (yaman_model.py:123-186), K = 2 the 6-wave model of rk4_sweep_kernel.
+//
+//     waves [p1, p2, s_1, i_1, ..., s_K, i_K],  P_j = |A_j|^2,  S = sum_j P_j,  E_k(z) = 2*gamma*exp(i*dbeta_k*z)
+//     dA_p1/dz = (-alpha/2 + i*gamma*(2S - P_p1)) A_p1 + i*conj(A_p2) * sum_k E_k A_sk A_ik        (p2: p1 <-> p2)
+//     dA_sk/dz = (-alpha/2 + i*gamma*(2S - P_sk)) A_sk + i*conj(A_ik) * conj(E_k) A_p1 A_p2        (ik: sk <-> ik)
+//
+// The channels couple through pump depletion and SPM/XPM only: FWM products BETWEEN channels (signal-signal mixing) are not
+// modelled.
+//
+// Layout: L lanes per sweep point, L the power of two >= K in {2, 4, 8, 16} (K = 1 runs with L = 2 and one dark lane; a lane
+// never holds more than one pair, so K = 5 pays for 8 lanes).  Lane r = gid % L holds pair r AND ITS OWN COPY OF BOTH PUMPS:
+// four complex amplitudes, the state of the 4-wave one-lane kernel, however many channels there are -- a one-lane kernel for
+// K = 16 would keep ~270 doubles live.  Lanes r >= K are padding: a dark pair (zero amplitudes, dbeta = 0) that adds exact
+// zeros to every sum and writes nothing.  L divides 16, so a point never straddles a DPP row and its L lanes enter and leave
+// the kernel together.
+//
+// Per RHS evaluation a lane forms three values for the point's sums -- its pair's power P_s + P_i and the complex pair
+// product E_k A_s A_i -- and the L lanes all-reduce these three doubles by a butterfly of DPP moves (quad_perm:[1,0,3,2],
+// quad_perm:[2,3,0,1], row_half_mirror, row_mirror; two v_mov_b32_dpp and one add per double and level).  Everything else is
+// the arithmetic of the 4-wave stage (yaman_stage) on the lane's own four amplitudes.
+//
+// The pump copies of a point stay BIT-IDENTICAL in all its lanes.  Each butterfly level adds a register value to the
+// partner's register value; IEEE addition commutes, so the two lanes of a level hold equal bits afterwards, and by
+// induction all L lanes hold the same three sums.  The pumps' arithmetic reads only these sums, the pumps themselves and
+// per-point constants (gamma, alpha, h), through the same instruction stream in every lane: equal inputs, equal outputs.
+// The per-lane quantities (the pair, its E_k) enter the pumps through the sums alone.  This holds under -ffp-contract=fast
+// because every value handed to the butterfly is the RESULT of an explicit fma or of an add, never of a bare multiply:
+// contraction fuses a multiply with the add that consumes it, and a level `v + partner(v)` whose v were an unrounded product
+// on the own side and a rounded one on the partner's would break the symmetry.  With no multiply feeding a level there is
+// nothing to fuse.  Lane 0 writes the pumps; the sidebands are written by their own lanes.
+//
+// No divergent control flow surrounds an exchange (DPP reads lanes that EXEC has disabled): the non-finite test is an
+// all-reduce followed by a ballot, as in rk4_sweep_quad_kernel, and loads and stores are the only lane-dependent branches.
+//
+// Same RK4 regrouping, phase recurrence with seeds on the absolute RESYNC grid, event-driven z-loop and save / NaN
+// semantics as rk4_sweep_kernel (see that file):  CHECK_NONE: first_bad_step = -1, NaNs propagate;  CHECK_BLOCK: the last
+// step of the first non-finite save block (or of the unsaved tail);  CHECK_EXACT: the exact step, found by replaying the
+// failing block from the last test point with a per-step test -- and if that replay should stay finite (it repeats the
+// forward pass operation for operation, so it should not), `bad` becomes the block-mode answer rather than staying -1.
+//
+// Out of scope: trajectory rows, float32, LDS staging, RK45, chains.
+#pragma once
+#include "psa_rk4_quad_kernel.inc.h"
+
+namespace psa {
+
+constexpr int ROW_HALF_MIRROR = 0x141;   // row_half_mirror: lane i <-> 7 - i of each 8
+constexpr int ROW_MIRROR = 0x140;        // row_mirror: lane i <-> 15 - i of each 16
+
+// Sum of v over the L lanes of a point, the same bits in every one of them.  v must be the result of an fma or an add.
+template <int L> __device__ __forceinline__ double pairs_allreduce(double v) {
+    static_assert(L == 2 || L == 4 || L == 8 || L == 16, "L lanes per point: a power of two that divides a DPP row");
+    v += quad_xchg<QUAD_PAIR>(v);
+    if constexpr (L >= 4) v += quad_xchg<QUAD_OTHER>(v);
+    if constexpr (L >= 8) v += quad_xchg<ROW_HALF_MIRROR>(v);
+    if constexpr (L >= 16) v += quad_xchg<ROW_MIRROR>(v);
+    return v;
+}
+
+// out = base + c * dA/dz of the lane's four waves a = [Re p1, Im p1, Re p2, Im p2, Re s, Im s, Re i, Im i] (stage
+// coefficient c folded into g, tg, ha, E as in yaman_stage).  With one pair lit the sums are that pair's own values plus
+// exact zeros, and the arithmetic is yaman_stage<double, 4, true> operation for operation.
+template <int L, bool LOSS>
+__device__ __forceinline__ void pairs_stage(const double (&a)[8], const double (&base)[8], const double Er, const double Ei,
+                                            const double g, const double tg, const double ha, double (&out)[8]) {
+    double p[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) p[j] = fma_(a[2 * j], a[2 * j], a[2 * j + 1] * a[2 * j + 1]);
+    const double s = (p[0] + p[1]) + pairs_allreduce<L>(p[2] + p[3]);   // every wave of the point
+    const double gs = tg * s;
+    double gj[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) gj[j] = fma_(-g, p[j], gs);
+
+    auto link = [&](const double gsig, const double v, const int c) -> double {
+        if constexpr (LOSS) return fma_(gsig, v, fma_(ha, a[c], base[c]));
+        else return fma_(gsig, v, base[c]);
+    };
+    const double x1 = a[0], y1 = a[1], x2 = a[2], y2 = a[3], xs = a[4], ys = a[5], xi = a[6], yi = a[7];
+    const double q12r = fma_(x1, x2, -(y1 * y2)), q12i = fma_(x1, y2, y1 * x2);   // A_p1 A_p2
+    const double qr = fma_(xs, xi, -(ys * yi)), qi = fma_(xs, yi, ys * xi);        // A_s A_i
+    // sum_k E_k (A_s A_i)_k: drives both pumps
+    const double Fpr = pairs_allreduce<L>(fma_(Er, qr, -(Ei * qi)));
+    const double Fpi = pairs_allreduce<L>(fma_(Er, qi, Ei * qr));
+    // conj(E_k) (A_p1 A_p2): drives this lane's signal and idler
+    const double Fsr = fma_(Er, q12r, Ei * q12i);
+    const double Fsi = fma_(Er, q12i, -(Ei * q12r));
+    out[0] = fma_(y2, Fpr, fma_(-x2, Fpi, link(-gj[0], y1, 0)));
+    out[1] = fma_(x2, Fpr, fma_(y2, Fpi, link(gj[0], x1, 1)));
+    out[2] = fma_(y1, Fpr, fma_(-x1, Fpi, link(-gj[1], y2, 2)));
+    out[3] = fma_(x1, Fpr, fma_(y1, Fpi, link(gj[1], x2, 3)));
+    out[4] = fma_(yi, Fsr, fma_(-xi, Fsi, link(-gj[2], ys, 4)));
+    out[5] = fma_(xi, Fsr, fma_(yi, Fsi, link(gj[2], xs, 5)));
+    out[6] = fma_(ys, Fsr, fma_(-xs, Fsi, link(-gj[3], yi, 6)));
+    out[7] = fma_(xs, Fsr, fma_(ys, Fsi, link(gj[3], xi, 7)));
+}
+
+template <int L, int CHECK, int BLOCK, bool LOSS>
+__global__ void __launch_bounds__(BLOCK) rk4_sweep_pairs_kernel(const PairsArgs A) {
+    constexpr int RESYNC = Phase<double>::RESYNC;
+    const long long gid = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    const long long idx = gid / L;          // sweep point: its L lanes share one
+    const int r = (int)(gid % L);           // = the pair this lane holds
+    const long long N = A.n_points;
+    if (idx >= N) return;                   // the L lanes of a point leave together
+    const bool lit = r < A.n_pairs;         // padding lanes: a dark pair
+    const int rr = lit ? r : 0;             // ... that reads pair 0's (in-bounds) entries and drops them
+
+    double a[8];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) a[c] = A.a0[(long long)c * A.a0_ld + idx * A.a0_stride];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const double v = A.a0[(long long)(4 + 4 * rr + c) * A.a0_ld + idx * A.a0_stride];
+        a[4 + c] = lit ? v : 0.0;
+    }
+    const double g = A.gamma[idx * A.gamma_stride];
+    const double tg = g + g;
+    const double ha = -0.5 * A.alpha[idx * A.alpha_stride];
+    const double db = A.dbeta[(long long)rr * N + idx];
+    const double dbd = lit ? db : 0.0;
+
+    const double hd = A.z_max / (double)A.n_steps;
+    const double hh = 0.5 * hd;
+    const double g_d = hh * g, tg_d = hh * tg, ha_d = hh * ha;
+    const double g_h = hd * g, tg_h = hd * tg, ha_h = hd * ha;
+    const double third = 1.0 / 3.0;
+    const double e_amp = tg_d;
+
+    double rc, rs, Er = e_amp, Ei = 0.0;
+    Phase<double>::eval(dbd * (0.5 * hd), rc, rs);
+
+    double pm[4];                           // np.max of |A_j|^2 over saved rows (z = 0 is one): p1, p2, s, i
+#pragma unroll
+    for (int j = 0; j < 4; ++j) pm[j] = fma_(a[2 * j], a[2 * j], a[2 * j + 1] * a[2 * j + 1]);
+    long long bad = -1;
+    auto nonfinite_on = [&](const double (&v)[8]) -> bool {   // any component of the POINT non-finite
+        double t = 0.0;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) t = fma_(v[c], 0.0, t);
+        t = pairs_allreduce<L>(t);
+        return t != t;
+    };
+
+    const int se = A.save_every;
+    const int n_rows = A.n_steps / se;
+    const int n_run = (CHECK != CHECK_NONE) ? A.n_steps : n_rows * se;
+
+    // lane 0 writes the pumps (waves 0, 1), lane r < K its pair (waves 2 + 2r, 3 + 2r)
+    auto store_a_end = [&]() {
+        if (r == 0) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) A.a_end[(long long)c * N + idx] = a[c];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) A.p_wave_end[(long long)j * N + idx] = fma_(a[2 * j], a[2 * j], a[2 * j + 1] * a[2 * j + 1]);
+        }
+        if (lit) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) A.a_end[(long long)(4 + 4 * r + c) * N + idx] = a[4 + c];
+#pragma unroll
+            for (int j = 2; j < 4; ++j)
+                A.p_wave_end[(long long)(2 * r + j) * N + idx] = fma_(a[2 * j], a[2 * j], a[2 * j + 1] * a[2 * j + 1]);
+        }
+    };
+    auto write_summary = [&]() {
+        if (r == 0) {
+            A.p_wave_max[idx] = pm[0];
+            A.p_wave_max[N + idx] = pm[1];
+            A.first_bad[idx] = bad;
+        }
+        if (lit) {
+            A.p_wave_max[(long long)(2 * r + 2) * N + idx] = pm[2];
+            A.p_wave_max[(long long)(2 * r + 3) * N + idx] = pm[3];
+        }
+    };
+    if (n_rows == 0) store_a_end();
+
+    // one classic RK4 step, regrouped as in rk4_sweep_kernel; (Er, Ei) enters at z_step and leaves rotated to z_step + h
+    auto rk4_step_on = [&](double (&y)[8], double &er, double &ei) {
+        double Y2[8], Y3[8], Y4[8], t[8], D[8];
+        pairs_stage<L, LOSS>(y, y, er, ei, g_d, tg_d, ha_d, Y2);
+        rotate(er, ei, rc, rs);  // z + h/2
+        pairs_stage<L, LOSS>(Y2, y, er, ei, g_d, tg_d, ha_d, Y3);
+        pairs_stage<L, LOSS>(Y3, y, er + er, ei + ei, g_h, tg_h, ha_h, Y4);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) t[c] = fma_(2.0, Y3[c], fma_(-4.0, y[c], Y2[c])) + Y4[c];
+        rotate(er, ei, rc, rs);  // z + h
+        pairs_stage<L, LOSS>(Y4, t, er, ei, g_d, tg_d, ha_d, D);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) y[c] = fma_(D[c], third, y[c]);
+    };
+    auto rk4_step = [&]() { rk4_step_on(a, Er, Ei); };
+    auto seed_on = [&](const int step, double &er, double &ei) {
+        double c, s;
+        Phase<double>::eval(dbd * ((double)step * hd), c, s);
+        er = e_amp * c;
+        ei = e_amp * s;
+    };
+
+    // CHECK_EXACT by replay of the failing block (see rk4_sweep_kernel).  The branch is wave-uniform (a ballot), `bad` and
+    // the test's result are the same in the L lanes of a point: no exchange runs with part of a point masked off.
+    constexpr bool REPLAY = CHECK == CHECK_EXACT;
+    double a_chk[REPLAY ? 8 : 1], Er_chk = Er, Ei_chk = Ei;
+    int i_chk = 0;
+    auto checkpoint = [&](const int step) {
+        if constexpr (REPLAY) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) a_chk[c] = a[c];
+            Er_chk = Er;
+            Ei_chk = Ei;
+            i_chk = step;
+        }
+    };
+    auto exact_test = [&](const int i_now) {
+        if constexpr (REPLAY) {
+            const bool now_bad = nonfinite_on(a);
+            const bool newly_bad = bad < 0 && now_bad;
+            if (__builtin_amdgcn_ballot_w64(newly_bad) != 0) {
+                double yy[8], er = Er_chk, ei = Ei_chk;
+#pragma unroll
+                for (int c = 0; c < 8; ++c) yy[c] = a_chk[c];
+                int ii = i_chk;
+                while (ii < i_now) {
+                    if (ii % RESYNC == 0) seed_on(ii, er, ei);
+                    const int to_seed = RESYNC - ii % RESYNC;
+                    const int e = (i_now - ii > to_seed) ? ii + to_seed : i_now;
+#pragma nounroll
+                    for (int st = ii; st < e; ++st) {
+                        rk4_step_on(yy, er, ei);
+                        const bool nf = nonfinite_on(yy);
+                        if (bad < 0 && nf) bad = st;
+                    }
+                    ii = e;
+                }
+                if (newly_bad && bad < 0) bad = i_now - 1;   // the replay stayed finite: the block-mode answer
+            }
+            checkpoint(i_now);
+        }
+    };
+
+    // ---- z-loop, event driven, seeds on the absolute grid i = 0, RESYNC, ... (see rk4_sweep_kernel)
+    int i = 0, row = 0;
+    int next_save = (n_rows > 0) ? se : 0x7fffffff;
+    int next_seed = 0;
+    checkpoint(0);
+    while (i < n_run) {
+        if (i == next_seed) {
+            seed_on(i, Er, Ei);
+            next_seed = (n_run - i > RESYNC) ? i + RESYNC : 0x7fffffff;
+        }
+        int end = n_run < next_seed ? n_run : next_seed;
+        end = end < next_save ? end : next_save;
+        const int m = end - i;
+        int j = 0;
+        for (; j + 2 <= m; j += 2) {
+            rk4_step();
+            rk4_step();
+        }
+        if (j < m) rk4_step();
+        i = end;
+        if (i == next_save) {
+            ++row;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const double pw = fma_(a[2 * w], a[2 * w], a[2 * w + 1] * a[2 * w + 1]);
+                pm[w] = (pw > pm[w] || pw != pw) ? pw : pm[w];   // np.max propagates NaN
+            }
+            if constexpr (CHECK == CHECK_BLOCK) {
+                const bool nf = nonfinite_on(a);
+                if (bad < 0 && nf) bad = i - 1;
+            }
+            exact_test(i);
+            if (row == n_rows) {
+                store_a_end();
+                next_save = 0x7fffffff;
+            } else {
+                next_save += se;
+            }
+        }
+    }
+    if constexpr (CHECK == CHECK_BLOCK) {
+        if (n_run > 0) {
+            const bool nf = nonfinite_on(a);
+            if (bad < 0 && nf) bad = n_run - 1;
+        }
+    }
+    if (n_run > i_chk) exact_test(n_run);   // the unsaved tail (CHECK_EXACT only)
+    write_summary();
+}
+
+}  // namespace psa

@@ -646,6 +646,68 @@ def scan_six_wave_grid(*, cfg: SimulationConfig, lambda_p1_m: float, lambda_p2_m
                 a_end=res.a_end.reshape(shape + (6,)), first_bad_step=res.first_bad_step.reshape(shape), result=res)
 
 
+def scan_wdm_gain(*, cfg: SimulationConfig, lambda_p1_m: float, lambda_p2_m: float, Omega: Sequence[float],
+                  p_pump: Sequence[float], p_signal, p_idler=0.0, phase_in: Optional[Sequence[float]] = None, gamma: float,
+                  alpha: float, dispersion: DispersionParams, even_orders: Tuple[int, ...] = (2, 4), length_unit: str = "m",
+                  gain_unit: str = "dB", gain_mode: GainMode = "max", device: Optional[int] = None,
+                  devices: Optional[Sequence[int]] = None) -> dict:
+    """A dual-pump amplifier carrying K = 1..16 channels at once (no reference counterpart): waves
+    [p1, p2, s_1, i_1, ..., s_K, i_K], channel k at omega_c +- Omega_k with dbeta_k = delta_beta_symmetric(omega_d, Omega_k)
+    as scan_six_wave_grid computes its two.  All channels draw on the same two pumps and shift each other's phase matching
+    through XPM; FWM products between channels (signal-signal mixing) are not modelled.
+
+    The N sweep points are input-power settings: p_signal (K,) is one point, (N, K) is N of them; p_idler a scalar, (K,)
+    or (N, K); p_pump (2,); phase_in None or NW = 2 + 2K phases.  One launch of the multi-channel kernel
+    (sweep.rk4_sweep_pairs) on ``device``, or split over ``devices``; sharding over a ``torch.distributed`` process group
+    is out of scope here -- every rank would run the whole sweep.
+
+    Returns dict(gain (N, K) of every signal over its seed, idler (N, K) every idler's power over its signal's seed,
+    pump_depletion (N,), dbeta (K,) in 1/length_unit, first_bad_step (N,), result=PairsResult)."""
+    from .frequency_plan import omega_from_lambda
+    from .sweep import initial_amplitudes, rk4_sweep_pairs
+    unit = check_gain(gain_mode, gain_unit)
+    Om = np.asarray(list(Omega), dtype=float)
+    if Om.ndim != 1 or not 1 <= Om.size <= 16 or not np.all(np.isfinite(Om)):
+        raise ValueError("Omega must be a 1D sequence of 1..16 finite detunings (rad/s)")
+    K = int(Om.size)
+    pp = np.asarray(list(p_pump), dtype=float)
+    if pp.shape != (2,) or not np.all(np.isfinite(pp)) or np.any(pp < 0.0):
+        raise ValueError("p_pump must hold two finite non-negative powers [p1, p2]")
+    ps = np.asarray(p_signal, dtype=float)
+    if ps.ndim not in (1, 2) or ps.shape[-1] != K or ps.size == 0:
+        raise ValueError(f"p_signal must have shape ({K},) or (N, {K})")
+    ps = np.atleast_2d(ps)
+    if not np.all(np.isfinite(ps)) or np.any(ps <= 0.0):
+        raise ValueError("p_signal (the seed powers) must be finite and > 0 to define gain")
+    N = int(ps.shape[0])
+    pi = np.asarray(p_idler, dtype=float)
+    if pi.shape not in ((), (K,), (N, K)) or not np.all(np.isfinite(pi)) or np.any(pi < 0.0):
+        raise ValueError(f"p_idler must be a scalar, ({K},) or ({N}, {K}) of finite non-negative powers")
+    ph = None if phase_in is None else np.asarray(list(phase_in), dtype=float)
+    if ph is not None and (ph.shape != (2 + 2 * K,) or not np.all(np.isfinite(ph))):
+        raise ValueError(f"phase_in must hold {2 + 2 * K} finite phases")
+    if dispersion is None:
+        raise ValueError("dispersion must be provided")
+    w1, w2 = omega_from_lambda(lambda_p1_m), omega_from_lambda(lambda_p2_m)
+    wc, wd = 0.5 * (w1 + w2), 0.5 * (w1 - w2)
+    if np.any(np.abs(Om) >= wc):
+        raise ValueError("|Omega| must stay below omega_c (sideband frequencies must be positive)")
+    pre = _prepare(cfg, gamma=gamma, alpha=alpha, dispersion=dispersion, phase_matching_cfg=None, beta_legacy=None,
+                   length_unit=length_unit)
+    fiber, grid = pre["fiber"], pre["grid"]
+    db = delta_beta_symmetric_array(wd, Om, fiber.dispersion, even_orders=even_orders)      # per metre
+    p_all = np.empty((N, 2 + 2 * K))
+    p_all[:, :2] = pp
+    p_all[:, 2::2] = ps
+    p_all[:, 3::2] = np.broadcast_to(pi, (N, K))
+    res = rk4_sweep_pairs(np.broadcast_to(db, (N, K)), z_max=fiber.length_m, n_steps=n_steps_of(fiber.length_m, grid.dz_m),
+                          save_every=cfg.save_every, check_nan=bool(cfg.check_nan), gamma=fiber.gamma_W_m,
+                          alpha=fiber.alpha_1_m, a0=initial_amplitudes(p_all, ph), device=(0 if device is None else int(device)),
+                          devices=devices)
+    return dict(gain=res.channel_gain(ps, mode=gain_mode, unit=unit), idler=res.idler_conversion(ps, mode=gain_mode, unit=unit),
+                pump_depletion=res.pump_depletion(), dbeta=db * pre["scale"], first_bad_step=res.first_bad_step, result=res)
+
+
 def scan_copier_psa_phase(*, psa_cfg: SimulationConfig, psa_delta_beta, gamma: float, alpha: float, p_in: Sequence[float],
                           phase_in: Optional[Sequence[float]] = None, copier_cfg: Optional[SimulationConfig] = None,
                           copier_delta_beta: float = 0.0, copier_gamma: Optional[float] = None,

@@ -14,11 +14,11 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _native
-from ._partition import CHAIN_AXES, SWEEP_AXES, over_devices
+from ._partition import CHAIN_AXES, PAIRS_AXES, SWEEP_AXES, over_devices
 from .config import AdaptiveConfig, n_steps_of
 
-__all__ = ["AdaptiveResult", "ChainResult", "FibreSpan", "SweepResult", "check_gain", "initial_amplitudes", "rk4_chain",
-           "rk4_sweep", "rk45_sweep"]
+__all__ = ["AdaptiveResult", "ChainResult", "FibreSpan", "PairsResult", "SweepResult", "check_gain", "initial_amplitudes",
+           "rk4_chain", "rk4_sweep", "rk4_sweep_pairs", "rk45_sweep"]
 
 
 def initial_amplitudes(p_in, phase_in=None) -> np.ndarray:
@@ -112,6 +112,103 @@ def rk4_sweep(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps: Optio
         r = _native.sweep_host(dbeta, device=(devs[0] if devs else device), **kw)
     return SweepResult(r["a_end"], r["p_end"], r["p_max"], r["first_bad_step"], int(n_steps), int(save_every),
                        r["elapsed_ms"], r.get("traj"), r.get("p_wave_end"), r.get("p_wave_max"))
+
+
+# ---- multi-channel sweeps: two pumps and K signal/idler pairs ----------------------------------------------------------
+@dataclass
+class PairsResult:
+    """Outcome of a multi-channel sweep; waves [p1, p2, s_1, i_1, ..., s_K, i_K], NW = 2 + 2K columns."""
+    a_end: np.ndarray            # (N, NW) complex: state at the last SAVED row
+    p_wave_end: np.ndarray       # (N, NW) |A_j|^2 there
+    p_wave_max: np.ndarray       # (N, NW) max over saved rows (z = 0 included), NaN-propagating
+    first_bad_step: np.ndarray   # (N,) int64, -1 = finite everywhere (or check_nan off)
+    n_steps: int
+    save_every: int
+    elapsed_ms: float            # kernel time (hipEvents)
+    p_wave_in: Optional[np.ndarray] = None   # (1 | N, NW) |A_j(0)|^2: what pump_depletion compares with
+
+    @property
+    def n_pairs(self) -> int:
+        return (int(self.p_wave_end.shape[1]) - 2) // 2
+
+    def _ratio(self, first_wave: int, p0, mode: str, unit: str) -> np.ndarray:
+        """metric of waves first_wave, first_wave + 2, ... over the seed powers p0, with the drivers' NaN rule
+        (scan_mismtach.py:376-392): a point with first_bad_step >= 0, a non-positive seed power, a non-finite or
+        non-positive ratio give NaN."""
+        u = check_gain(mode, unit)
+        N, K = int(self.p_wave_end.shape[0]), self.n_pairs
+        p0 = np.asarray(p0, dtype=float)
+        if p0.shape not in ((K,), (N, K)):
+            raise ValueError(f"p0 must have shape ({K},) or ({N}, {K}), got {p0.shape}")
+        p0 = np.broadcast_to(p0, (N, K))
+        metric = (self.p_wave_max if mode == "max" else self.p_wave_end)[:, first_wave::2][:, :K]
+        with np.errstate(all="ignore"):
+            ok = (p0 > 0.0) & np.isfinite(p0) & (np.asarray(self.first_bad_step) < 0)[:, None]
+            g = metric / np.where(ok, p0, 1.0)
+            ok &= np.isfinite(g) & (g > 0.0)
+            return np.where(ok, g if u == "linear" else 10.0 * np.log10(np.where(ok, g, 1.0)), np.nan)
+
+    def channel_gain(self, p0, *, mode: str = "max", unit: str = "dB") -> np.ndarray:
+        """(N, K): every signal's gain over its seed power p0 (K,) or (N, K); gain_mode "end" | "max"."""
+        return self._ratio(2, p0, mode, unit)
+
+    def idler_conversion(self, p0, *, mode: str = "max", unit: str = "dB") -> np.ndarray:
+        """(N, K): every idler's power over the SIGNAL's seed power p0 (K,) or (N, K): the conversion efficiency."""
+        return self._ratio(3, p0, mode, unit)
+
+    def pump_depletion(self) -> np.ndarray:
+        """(N,): the fraction of the two pumps' input power that is gone at the last saved row,
+        1 - (P_p1 + P_p2)_end / (P_p1 + P_p2)_in (fibre loss included); NaN for a failed point or dark pumps."""
+        if self.p_wave_in is None:
+            raise ValueError("pump_depletion needs p_wave_in (set by rk4_sweep_pairs)")
+        N = int(self.p_wave_end.shape[0])
+        p_in = np.broadcast_to(self.p_wave_in[:, :2].sum(axis=1), (N,))
+        with np.errstate(all="ignore"):
+            ok = (p_in > 0.0) & np.isfinite(p_in) & (np.asarray(self.first_bad_step) < 0)
+            d = 1.0 - self.p_wave_end[:, :2].sum(axis=1) / np.where(ok, p_in, 1.0)
+            return np.where(ok & np.isfinite(d), d, np.nan)
+
+
+def rk4_sweep_pairs(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps: Optional[int] = None,
+                    save_every: int = 10, check_nan: bool = True, exact_step: Optional[bool] = None, gamma, alpha, a0,
+                    device: int = 0, devices: Optional[Sequence[int]] = None) -> PairsResult:
+    """Propagate N points of the multi-channel model: two pumps and K = 1..16 signal/idler pairs, waves
+    [p1, p2, s_1, i_1, ..., s_K, i_K] (build-defined; K = 1 is the reference's 4-wave system, K = 2 the
+    6-wave model).  All channels draw on the same two pumps and shift each other's phase matching through SPM/XPM; FWM
+    products between channels (signal-signal mixing) are NOT modelled.
+
+    dbeta (N, K): the mismatch of every pair; gamma / alpha a scalar or (N,); a0 (NW,) or (N, NW) complex, NW = 2 + 2K.
+    ``dz`` gives n = int(round(z_max/dz)) as integrators.py:194; or pass ``n_steps``.  ``devices=[0, 1, ...]`` splits the
+    points over several GPUs of this process.  Fixed-step float64 only: no trajectory, float32, chain or adaptive form."""
+    if not (np.isfinite(z_max) and z_max > 0.0):
+        raise ValueError("z_max must be positive")
+    if n_steps is None:
+        if dz is None or dz <= 0.0:
+            raise ValueError("dz must be positive")
+        n_steps = n_steps_of(z_max, dz)
+    if save_every <= 0:
+        raise ValueError("save_every must be a positive integer")
+    if n_steps < 1:
+        raise ValueError("z_max / dz rounds to zero steps")
+    db = np.asarray(dbeta, dtype=float)
+    if db.ndim != 2 or not 1 <= db.shape[1] <= _native.MAX_PAIRS:
+        raise ValueError(f"dbeta must have shape (N, K) with 1 <= K <= {_native.MAX_PAIRS}, got {db.shape}")
+    nw = 2 + 2 * int(db.shape[1])
+    a0 = np.asarray(a0, dtype=np.complex128)
+    if a0.shape not in ((nw,), (1, nw), (db.shape[0], nw)):
+        raise ValueError(f"a0 must have shape ({nw},) or ({db.shape[0]}, {nw}) for {db.shape[1]} pairs, got {a0.shape}")
+    kw = dict(n_steps=int(n_steps), z_max=float(z_max), save_every=int(save_every), gamma=gamma, alpha=alpha, a0=a0,
+              check_nan=check_nan, exact_step=exact_step)
+    devs = None if devices is None else [int(d) for d in devices]
+    if devs is not None and len(devs) == 0:
+        raise ValueError("devices must name at least one GPU")
+    if devs is not None and len(devs) > 1 and db.shape[0] > 1:
+        r = over_devices(_native.sweep_pairs_host, devs, db.shape[0], PAIRS_AXES, dict(kw, dbeta=db))
+    else:
+        r = _native.sweep_pairs_host(db, device=(devs[0] if devs else device), **kw)
+    p_in = np.abs(np.atleast_2d(a0)) ** 2
+    return PairsResult(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"], int(n_steps), int(save_every),
+                       r["elapsed_ms"], p_in)
 
 
 # ---- chains of fibre spans ------------------------------------------------------------------------------------------
