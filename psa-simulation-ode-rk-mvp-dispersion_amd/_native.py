@@ -43,74 +43,53 @@ MAX_POINTS = 2**31 - 256          # PSA_MAX_POINTS: the most points one launch t
 MAX_PAIRS = 16                    # PSA_MAX_PAIRS: the most signal/idler pairs of the multi-channel sweep
 
 # every symbol the header declares, with (restype, argtypes)
-_P = C.c_void_p
+_P, _I, _L, _D, _I32, _U32 = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_int32, C.c_uint32
+_BOTH = ("f64", "f32")
+
+
+def _family(stem, body, host=(), dev=(), host_types=_BOTH, dev_types=_BOTH, dev_first=False) -> dict:
+    """The faces of one entry point: ``<stem>_<type>(device, *body, *host)`` and ``<stem>_<type>_dev(stream, *body, *dev)``,
+    in the header's order (the host faces first unless ``dev_first``)."""
+    hosts = {f"{stem}_{t}": (_I, [_I, *body, *host]) for t in host_types}
+    devs = {f"{stem}_{t}_dev": (_I, [_P, *body, *dev]) for t in dev_types}
+    return {**devs, **hosts} if dev_first else {**hosts, **devs}
+
+
+# n_waves, N, n_steps, z_max, save_every, dbeta, dbeta2, gamma, alpha, a0, flags, a_end, p_end, p_max, first_bad, traj
+_SWEEP = [_I, _L, _L, _D, _I32] + [_P] * 5 + [_U32] + [_P] * 5
+# method, orders, n_orders, max_order, beta, n_beta, omega_ref, two_pi_c, atol, rtol
+_MODEL = [_I, _P, _I, _I, _P, _I] + [_D] * 4
+_GAIN = [_L, _P, _P, _D, _I] + [_P] * 4
 _SIGS = {
-    "psa_device_count": (C.c_int, []),
+    "psa_device_count": (_I, []),
     "psa_last_error": (C.c_char_p, []),
     "psa_version": (C.c_char_p, []),
-    "psa_n_saved": (C.c_int64, [C.c_int64, C.c_int32]),
-    "psa_release_cache": (C.c_int, []),
-    "psa_traj_ld": (C.c_int64, [C.c_int64, C.c_int32]),
-    "psa_rk4_sweep_f64": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int32,
-                                    _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P]),
-    "psa_rk4_sweep_f32": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int32,
-                                    _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P]),
-    "psa_rk4_sweep_f64_dev": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int32,
-                                        _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
-    "psa_rk4_sweep_f32_dev": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int32,
-                                        _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
-    "psa_rk4_sweep_waves_f64": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int32,
-                                          _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "psa_rk4_sweep_waves_f32": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int32,
-                                          _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "psa_rk4_sweep_waves_f64_dev": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int32,
-                                              _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
-    "psa_rk4_sweep_waves_f32_dev": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int32,
-                                              _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
-    # (device|stream, n_waves, N, S, n_steps[S], seg_len[S], save_every, dbeta, dbeta2, gamma, alpha, a0, transfer, flags,
-    #  a_end, p_end, p_max, first_bad, traj, elapsed_ms | (p_wave_end, p_wave_max, workspace))
-    "psa_rk4_chain_f64": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int, _P, _P, C.c_int32] + [_P] * 6
-                          + [C.c_uint32] + [_P] * 8),
-    "psa_rk4_chain_f32": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int, _P, _P, C.c_int32] + [_P] * 6
-                          + [C.c_uint32] + [_P] * 8),
-    "psa_rk4_chain_f64_dev": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, _P, _P, C.c_int32] + [_P] * 6
-                              + [C.c_uint32] + [_P] * 8),
-    "psa_rk4_chain_f32_dev": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, _P, _P, C.c_int32] + [_P] * 6
-                              + [C.c_uint32] + [_P] * 8),
-    "psa_rk4_chain_workspace_bytes": (C.c_int64, [C.c_int, C.c_int64, C.c_int32, C.c_int]),
-    # (device|stream, n_waves, N, z_max, rtol, atol, h_max, first_step, max_steps, n_out, dbeta, dbeta2, gamma, alpha, a0,
-    #  flags, a_end, p_end, p_max, status, z_end, n_accepted, n_rejected, traj [, elapsed_ms])
-    "psa_rk45_sweep_f64": (C.c_int, [C.c_int, C.c_int, C.c_int64] + [C.c_double] * 5 + [C.c_int64, C.c_int64]
-                           + [_P] * 5 + [C.c_uint32] + [_P] * 9),
-    "psa_rk45_sweep_f64_dev": (C.c_int, [_P, C.c_int, C.c_int64] + [C.c_double] * 5 + [C.c_int64, C.c_int64]
-                               + [_P] * 5 + [C.c_uint32] + [_P] * 8),
-    # (device|stream, n_pairs, N, n_steps, z_max, save_every, dbeta, gamma, alpha, a0, flags, a_end, p_wave_end, p_wave_max,
-    #  first_bad [, elapsed_ms])
-    "psa_rk4_sweep_pairs_f64": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int32,
-                                          _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
-    "psa_rk4_sweep_pairs_f64_dev": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int32,
-                                              _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P]),
-    "psa_yaman_rhs_f64": (C.c_int, [C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "psa_gain_summary_f64": (C.c_int, [C.c_int, C.c_int64, _P, _P, C.c_double, C.c_int, _P, _P, _P, _P]),
-    "psa_gain_summary_f64_dev": (C.c_int, [_P, C.c_int64, _P, _P, C.c_double, C.c_int, _P, _P, _P, _P, _P]),
-    "psa_gain_summary_workspace_bytes": (C.c_int64, [C.c_int64]),
-    "psa_gain_summary_f32": (C.c_int, [C.c_int, C.c_int64, _P, _P, C.c_double, C.c_int, _P, _P, _P, _P]),
-    "psa_gain_summary_f32_dev": (C.c_int, [_P, C.c_int64, _P, _P, C.c_double, C.c_int, _P, _P, _P, _P, _P]),
-    # (stream|device, method, orders, n_orders, max_order, beta, n_beta, omega_ref, two_pi_c, atol, rtol, lambda1,
-    #  axis2, n2, axis3, n3, first, n, out, valid)
-    "psa_dbeta_grid_f64_dev": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int] + [C.c_double] * 5
-                               + [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
-    "psa_dbeta_grid_f32_dev": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int] + [C.c_double] * 5
-                               + [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
-    "psa_dbeta_grid_f64": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int] + [C.c_double] * 5
-                           + [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
-    # (stream|device, orders, n_orders, beta, n_beta, omega_d, axis1, n1, axis2, n2, first, n, out1, out2)
-    "psa_dbeta_pairs_f64_dev": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_double, _P, C.c_int64, _P, C.c_int64,
-                                          C.c_int64, C.c_int64, _P, _P]),
-    "psa_dbeta_pairs_f32_dev": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_double, _P, C.c_int64, _P, C.c_int64,
-                                          C.c_int64, C.c_int64, _P, _P]),
-    "psa_dbeta_pairs_f64": (C.c_int, [C.c_int, _P, C.c_int, _P, C.c_int, C.c_double, _P, C.c_int64, _P, C.c_int64,
-                                      C.c_int64, C.c_int64, _P, _P]),
+    "psa_n_saved": (_L, [_L, _I32]),
+    "psa_release_cache": (_I, []),
+    "psa_traj_ld": (_L, [_L, _I32]),
+    **_family("psa_rk4_sweep", _SWEEP, host=[_P]),                               # host: elapsed_ms
+    **_family("psa_rk4_sweep_waves", _SWEEP, host=[_P] * 3, dev=[_P] * 2),       # [elapsed_ms,] p_wave_end, p_wave_max
+    # n_waves, N, S, n_steps[S], seg_len[S], save_every, dbeta, dbeta2, gamma, alpha, a0, transfer, flags, a_end, p_end, p_max,
+    # first_bad, traj; host: elapsed_ms, p_wave_end, p_wave_max; dev: p_wave_end, p_wave_max, workspace
+    **_family("psa_rk4_chain", [_I, _L, _I, _P, _P, _I32] + [_P] * 6 + [_U32] + [_P] * 5, host=[_P] * 3, dev=[_P] * 3),
+    "psa_rk4_chain_workspace_bytes": (_L, [_I, _L, _I32, _I]),
+    # n_waves, N, z_max, rtol, atol, h_max, first_step, max_steps, n_out, dbeta, dbeta2, gamma, alpha, a0, flags, a_end, p_end,
+    # p_max, status, z_end, n_accepted, n_rejected, traj; host: elapsed_ms
+    **_family("psa_rk45_sweep", [_I, _L] + [_D] * 5 + [_L, _L] + [_P] * 5 + [_U32] + [_P] * 8, host=[_P],
+              host_types=("f64",), dev_types=("f64",)),
+    # n_pairs, N, n_steps, z_max, save_every, dbeta, gamma, alpha, a0, flags, a_end, p_wave_end, p_wave_max, first_bad; host: elapsed_ms
+    **_family("psa_rk4_sweep_pairs", [_I, _L, _L, _D, _I32] + [_P] * 4 + [_U32] + [_P] * 4, host=[_P],
+              host_types=("f64",), dev_types=("f64",)),
+    "psa_yaman_rhs_f64": (_I, [_I, _L] + [_P] * 9),
+    # N, p_metric, first_bad, p0_sig, gain_db, gain, best_index, best_gain, n_finite; dev: workspace
+    **_family("psa_gain_summary", _GAIN, dev=[_P], host_types=("f64",), dev_types=("f64",)),
+    "psa_gain_summary_workspace_bytes": (_L, [_L]),
+    **_family("psa_gain_summary", _GAIN, dev=[_P], host_types=("f32",), dev_types=("f32",)),
+    # model, lambda1, axis2, n2, axis3, n3, first, n, out, valid
+    **_family("psa_dbeta_grid", _MODEL + [_D, _P, _L, _P, _L, _L, _L, _P, _P], host_types=("f64",), dev_first=True),
+    # orders, n_orders, beta, n_beta, omega_d, axis1, n1, axis2, n2, first, n, out1, out2
+    **_family("psa_dbeta_pairs", [_P, _I, _P, _I, _D, _P, _L, _P, _L, _L, _L, _P, _P], host_types=("f64",),
+              dev_first=True),
 }
 DBETA_SYMMETRIC_EVEN, DBETA_GENERAL_TAYLOR = 0, 1
 DBETA_MAX_ORDER = 8
@@ -201,8 +180,8 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-def _prep(x, dtype, n_points: int, name: str):
-    """-> (contiguous 1-D array, is_broadcast)."""
+def _prep(x, dtype, n_points: int, name: str, spans=None):
+    """A scalar or (N,) -> (contiguous 1-D array, is_broadcast)."""
     arr = np.ascontiguousarray(np.atleast_1d(np.asarray(x)), dtype=dtype)
     if arr.ndim != 1:
         raise ValueError(f"{name} must be a scalar or 1-D array")
@@ -211,6 +190,87 @@ def _prep(x, dtype, n_points: int, name: str):
     if arr.shape[0] == 1:
         return arr, True
     raise ValueError(f"{name} must have 1 or {n_points} entries, got {arr.shape[0]}")
+
+
+def _prep_spans(x, dtype, n_points: int, name: str, spans: int):
+    """(S,) or (S, N) of a chain -> (contiguous array, is_broadcast)."""
+    arr = np.ascontiguousarray(np.asarray(x), dtype=dtype)
+    if arr.shape == (spans,):
+        return arr, True
+    if arr.shape != (spans, n_points):
+        raise ValueError(f"{name} must have shape ({spans},) or ({spans}, {n_points})")
+    return arr, False
+
+
+_FN: dict = {}    # (stem, f64, dev) -> bound C function: resolved once, one dictionary look-up per call afterwards
+
+
+def _fn(stem: str, f64: bool = True, dev: bool = False):
+    """The entry point ``<stem>_f64`` or (``f64`` false) ``<stem>_f32``, its ``_dev`` face on request."""
+    try:
+        return _FN[stem, f64, dev]
+    except KeyError:
+        fn = _FN[stem, f64, dev] = getattr(lib(), f"{stem}_{'f64' if f64 else 'f32'}{'_dev' if dev else ''}")
+        return fn
+
+
+def _is_f64(dtype) -> bool:
+    """A ``_dev`` wrapper's dtype argument: float64 selects the _f64 entry point, anything else the _f32 one."""
+    return np.dtype(dtype) == np.float64
+
+
+_F64, _F32 = np.dtype(np.float64), np.dtype(np.float32)
+
+
+def _dtypes(dtype):
+    """-> (real dtype, its complex dtype, is it float64) of a host wrapper's dtype argument: float64 or float32."""
+    dtype = np.dtype(dtype)
+    if dtype == _F64:
+        return dtype, np.complex128, True
+    if dtype == _F32:
+        return dtype, np.complex64, False
+    raise ValueError("dtype must be float64 or float32")
+
+
+def _check_flags(check_nan: bool, exact_step: Optional[bool], f64: bool = True) -> int:
+    """OPT_CHECK_NAN, and with it OPT_EXACT_STEP where asked for or (exact_step None) where it is free: in float64."""
+    if not check_nan:
+        return 0
+    return OPT_CHECK_NAN | (OPT_EXACT_STEP if exact_step or (exact_step is None and f64) else 0)
+
+
+def _point_inputs(N: int, dtype, cdt, flags: int, gamma, alpha, a0, widths, dbeta=None, dbeta2=None, spans=None):
+    """The per-point inputs of a host wrapper -> (flags with the BCAST bits, gamma, alpha, a0, dbeta2).
+
+    a0 (n_waves,) or (N, n_waves) complex with n_waves in ``widths``; gamma / alpha a scalar or (N,) -- for a chain of
+    ``spans`` spans (S,) or (S, N); dbeta2 shaped as ``dbeta`` for 6 waves and absent for 4 (a family without dbeta2 passes
+    no ``dbeta``).  One value where N are possible sets the argument's BCAST bit."""
+    a0 = np.ascontiguousarray(np.asarray(a0), dtype=cdt)
+    if a0.ndim == 1:
+        a0 = a0[None, :]
+    if a0.ndim != 2 or a0.shape[1] not in widths:
+        raise ValueError(f"a0 must have shape (n_waves,) or ({N}, n_waves) with n_waves in {tuple(widths)}, got {a0.shape}")
+    if a0.shape[0] == 1:
+        flags |= BCAST_A0
+    elif a0.shape[0] != N:
+        raise ValueError(f"a0 must have 1 or {N} rows, got {a0.shape[0]}")
+    prep = _prep if spans is None else _prep_spans
+    gamma, bcast = prep(gamma, dtype, N, "gamma", spans)
+    if bcast:
+        flags |= BCAST_GAMMA
+    alpha, bcast = prep(alpha, dtype, N, "alpha", spans)
+    if bcast:
+        flags |= BCAST_ALPHA
+    d2 = None
+    if dbeta is not None and a0.shape[1] == 6:
+        if dbeta2 is None:
+            raise ValueError("n_waves == 6 needs dbeta2")
+        d2 = np.ascontiguousarray(np.atleast_1d(np.asarray(dbeta2)), dtype=dtype)
+        if d2.shape != dbeta.shape:
+            raise ValueError("dbeta2 must match dbeta")
+    elif dbeta2 is not None:
+        raise ValueError("dbeta2 is only meaningful for 6 waves")
+    return flags, gamma, alpha, a0, d2
 
 
 def sweep_host(dbeta, *, n_steps: int, z_max: float, save_every: int, gamma, alpha, a0, dbeta2=None,
@@ -228,64 +288,27 @@ def sweep_host(dbeta, *, n_steps: int, z_max: float, save_every: int, gamma, alp
     Returns a_end (N, n_waves) complex, p_end, p_max (N,), first_bad_step (N,) int64,
     traj (N, n_saved, n_waves) complex or None, elapsed_ms (kernel only).
     """
-    dtype = np.dtype(dtype)
-    if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
-        raise ValueError("dtype must be float64 or float32")
-    cdt = np.complex128 if dtype == np.float64 else np.complex64
+    dtype, cdt, f64 = _dtypes(dtype)
     dbeta = np.ascontiguousarray(np.atleast_1d(np.asarray(dbeta)), dtype=dtype)
     if dbeta.ndim != 1:
         raise ValueError("dbeta must be 1-D")
     N = int(dbeta.shape[0])
-    a0 = np.ascontiguousarray(np.asarray(a0), dtype=cdt)
-    if a0.ndim == 1:
-        a0 = a0[None, :]
-    if a0.ndim != 2 or a0.shape[1] not in (4, 6):
-        raise ValueError("a0 must have shape (n_waves,) or (N, n_waves) with n_waves in (4, 6)")
+    flags, gamma, alpha, a0, d2 = _point_inputs(N, dtype, cdt, int(extra_flags), gamma, alpha, a0, (4, 6), dbeta, dbeta2)
+    flags |= _check_flags(check_nan, exact_step, f64)
     nw = int(a0.shape[1])
-    flags = int(extra_flags)
-    if a0.shape[0] == 1:
-        flags |= BCAST_A0
-    elif a0.shape[0] != N:
-        raise ValueError(f"a0 must have 1 or {N} rows, got {a0.shape[0]}")
-    gamma, gb = _prep(gamma, dtype, N, "gamma")
-    alpha, ab = _prep(alpha, dtype, N, "alpha")
-    if gb:
-        flags |= BCAST_GAMMA
-    if ab:
-        flags |= BCAST_ALPHA
-    if check_nan:
-        flags |= OPT_CHECK_NAN
-        if exact_step or (exact_step is None and dtype == np.float64):
-            flags |= OPT_EXACT_STEP
-    d2 = None
-    if nw == 6:
-        if dbeta2 is None:
-            raise ValueError("n_waves == 6 needs dbeta2")
-        d2 = np.ascontiguousarray(np.atleast_1d(np.asarray(dbeta2)), dtype=dtype)
-        if d2.shape != dbeta.shape:
-            raise ValueError("dbeta2 must match dbeta")
-    elif dbeta2 is not None:
-        raise ValueError("dbeta2 is only meaningful for 6 waves")
-
     n_saved = int(n_steps) // int(save_every) + 1 if save_every > 0 else 0
     a_end = np.empty((N, nw), dtype=cdt)
     p_end = np.empty(N, dtype=dtype)
     p_max = np.empty(N, dtype=dtype)
     bad = np.empty(N, dtype=np.int64)
     traj = np.empty((N, n_saved, nw), dtype=cdt) if want_traj else None
+    w_end = np.empty((N, nw), dtype=dtype) if wave_summary else None
+    w_max = np.empty((N, nw), dtype=dtype) if wave_summary else None
     ms = C.c_double(0.0)
-    args = [int(device), nw, N, int(n_steps), float(z_max), int(save_every), _ptr(dbeta), _ptr(d2), _ptr(gamma),
-            _ptr(alpha), _ptr(a0), flags, _ptr(a_end), _ptr(p_end), _ptr(p_max), _ptr(bad), _ptr(traj),
-            C.cast(C.byref(ms), C.c_void_p)]
-    w_end = w_max = None
-    if wave_summary:
-        w_end = np.empty((N, nw), dtype=dtype)
-        w_max = np.empty((N, nw), dtype=dtype)
-        fn = lib().psa_rk4_sweep_waves_f64 if dtype == np.float64 else lib().psa_rk4_sweep_waves_f32
-        args += [_ptr(w_end), _ptr(w_max)]
-    else:
-        fn = lib().psa_rk4_sweep_f64 if dtype == np.float64 else lib().psa_rk4_sweep_f32
-    _check(fn(*args))
+    _check(_fn("psa_rk4_sweep_waves" if wave_summary else "psa_rk4_sweep", f64)(
+        int(device), nw, N, int(n_steps), float(z_max), int(save_every), _ptr(dbeta), _ptr(d2), _ptr(gamma), _ptr(alpha),
+        _ptr(a0), flags, _ptr(a_end), _ptr(p_end), _ptr(p_max), _ptr(bad), _ptr(traj), C.cast(C.byref(ms), _P),
+        *((_ptr(w_end), _ptr(w_max)) if wave_summary else ())))
     return dict(a_end=a_end, p_end=p_end, p_max=p_max, first_bad_step=bad, traj=traj, elapsed_ms=ms.value,
                 p_wave_end=w_end, p_wave_max=w_max)
 
@@ -295,10 +318,10 @@ def sweep_device(*, stream: int, n_waves: int, n_points: int, n_steps: int, z_ma
                  d_a_end_soa: int, d_p_end: int, d_p_max: int, d_first_bad: int, d_traj_soa: int = 0,
                  dtype=np.float64) -> None:
     """Asynchronous launch on device pointers (ints), SoA layout -- see psa_rk4_sweep_f64_dev."""
-    fn = lib().psa_rk4_sweep_f64_dev if np.dtype(dtype) == np.float64 else lib().psa_rk4_sweep_f32_dev
-    _check(fn(stream or None, int(n_waves), int(n_points), int(n_steps), float(z_max), int(save_every),
-              d_dbeta or None, d_dbeta2 or None, d_gamma or None, d_alpha or None, d_a0_soa or None, int(flags),
-              d_a_end_soa or None, d_p_end or None, d_p_max or None, d_first_bad or None, d_traj_soa or None))
+    _check(_fn("psa_rk4_sweep", _is_f64(dtype), dev=True)(
+        stream or None, int(n_waves), int(n_points), int(n_steps), float(z_max), int(save_every),
+        d_dbeta or None, d_dbeta2 or None, d_gamma or None, d_alpha or None, d_a0_soa or None, int(flags),
+        d_a_end_soa or None, d_p_end or None, d_p_max or None, d_first_bad or None, d_traj_soa or None))
 
 
 def sweep_waves_device(*, stream: int, n_waves: int, n_points: int, n_steps: int, z_max: float, save_every: int,
@@ -306,11 +329,11 @@ def sweep_waves_device(*, stream: int, n_waves: int, n_points: int, n_steps: int
                        d_a_end_soa: int, d_p_end: int, d_p_max: int, d_first_bad: int, d_p_wave_end_soa: int,
                        d_p_wave_max_soa: int, d_traj_soa: int = 0, dtype=np.float64) -> None:
     """sweep_device with the per-wave summary ([n_waves][N] device buffers) -- see psa_rk4_sweep_waves_f64_dev."""
-    fn = lib().psa_rk4_sweep_waves_f64_dev if np.dtype(dtype) == np.float64 else lib().psa_rk4_sweep_waves_f32_dev
-    _check(fn(stream or None, int(n_waves), int(n_points), int(n_steps), float(z_max), int(save_every),
-              d_dbeta or None, d_dbeta2 or None, d_gamma or None, d_alpha or None, d_a0_soa or None, int(flags),
-              d_a_end_soa or None, d_p_end or None, d_p_max or None, d_first_bad or None, d_traj_soa or None,
-              d_p_wave_end_soa or None, d_p_wave_max_soa or None))
+    _check(_fn("psa_rk4_sweep_waves", _is_f64(dtype), dev=True)(
+        stream or None, int(n_waves), int(n_points), int(n_steps), float(z_max), int(save_every),
+        d_dbeta or None, d_dbeta2 or None, d_gamma or None, d_alpha or None, d_a0_soa or None, int(flags),
+        d_a_end_soa or None, d_p_end or None, d_p_max or None, d_first_bad or None, d_traj_soa or None,
+        d_p_wave_end_soa or None, d_p_wave_max_soa or None))
 
 
 def sweep_pairs_host(dbeta, *, n_steps: int, z_max: float, save_every: int, gamma, alpha, a0, check_nan: bool = True,
@@ -326,31 +349,16 @@ def sweep_pairs_host(dbeta, *, n_steps: int, z_max: float, save_every: int, gamm
         raise ValueError(f"dbeta must have shape (N, K) with 1 <= K <= {MAX_PAIRS}, got {dbeta.shape}")
     N, K = (int(x) for x in dbeta.shape)
     nw = 2 + 2 * K
-    a0 = np.ascontiguousarray(np.asarray(a0), dtype=np.complex128)
-    if a0.ndim == 1:
-        a0 = a0[None, :]
-    if a0.ndim != 2 or a0.shape[1] != nw:
-        raise ValueError(f"a0 must have shape ({nw},) or ({N}, {nw}) for {K} pairs, got {a0.shape}")
-    flags = int(extra_flags)
-    if a0.shape[0] == 1:
-        flags |= BCAST_A0
-    elif a0.shape[0] != N:
-        raise ValueError(f"a0 must have 1 or {N} rows, got {a0.shape[0]}")
-    gamma, gb = _prep(gamma, np.float64, N, "gamma")
-    alpha, ab = _prep(alpha, np.float64, N, "alpha")
-    flags |= (BCAST_GAMMA if gb else 0) | (BCAST_ALPHA if ab else 0)
-    if check_nan:
-        flags |= OPT_CHECK_NAN
-        if exact_step or exact_step is None:
-            flags |= OPT_EXACT_STEP
+    flags, gamma, alpha, a0, _ = _point_inputs(N, np.float64, np.complex128, int(extra_flags), gamma, alpha, a0, (nw,))
+    flags |= _check_flags(check_nan, exact_step)
     a_end = np.empty((N, nw), dtype=np.complex128)
     w_end = np.empty((N, nw), dtype=np.float64)
     w_max = np.empty((N, nw), dtype=np.float64)
     bad = np.empty(N, dtype=np.int64)
     ms = C.c_double(0.0)
-    _check(lib().psa_rk4_sweep_pairs_f64(int(device), K, N, int(n_steps), float(z_max), int(save_every), _ptr(dbeta),
-                                         _ptr(gamma), _ptr(alpha), _ptr(a0), flags, _ptr(a_end), _ptr(w_end), _ptr(w_max),
-                                         _ptr(bad), C.cast(C.byref(ms), C.c_void_p)))
+    _check(_fn("psa_rk4_sweep_pairs")(int(device), K, N, int(n_steps), float(z_max), int(save_every), _ptr(dbeta),
+                                      _ptr(gamma), _ptr(alpha), _ptr(a0), flags, _ptr(a_end), _ptr(w_end), _ptr(w_max),
+                                      _ptr(bad), C.cast(C.byref(ms), _P)))
     return dict(a_end=a_end, p_wave_end=w_end, p_wave_max=w_max, first_bad_step=bad, elapsed_ms=ms.value)
 
 
@@ -358,10 +366,10 @@ def sweep_pairs_device(*, stream: int, n_pairs: int, n_points: int, n_steps: int
                        d_dbeta_soa: int, d_gamma: int, d_alpha: int, d_a0_soa: int, flags: int, d_a_end_soa: int,
                        d_p_wave_end_soa: int, d_p_wave_max_soa: int, d_first_bad: int) -> None:
     """Asynchronous multi-channel launch on device pointers (ints), SoA layout -- see psa_rk4_sweep_pairs_f64_dev."""
-    _check(lib().psa_rk4_sweep_pairs_f64_dev(stream or None, int(n_pairs), int(n_points), int(n_steps), float(z_max),
-                                             int(save_every), d_dbeta_soa or None, d_gamma or None, d_alpha or None,
-                                             d_a0_soa or None, int(flags), d_a_end_soa or None, d_p_wave_end_soa or None,
-                                             d_p_wave_max_soa or None, d_first_bad or None))
+    _check(_fn("psa_rk4_sweep_pairs", dev=True)(
+        stream or None, int(n_pairs), int(n_points), int(n_steps), float(z_max), int(save_every), d_dbeta_soa or None,
+        d_gamma or None, d_alpha or None, d_a0_soa or None, int(flags), d_a_end_soa or None, d_p_wave_end_soa or None,
+        d_p_wave_max_soa or None, d_first_bad or None))
 
 
 def chain_host(dbeta, *, n_steps, seg_len, save_every: int, gamma, alpha, a0, transfers=None, dbeta2=None,
@@ -373,10 +381,7 @@ def chain_host(dbeta, *, n_steps, seg_len, save_every: int, gamma, alpha, a0, tr
     a0 (n_waves,) or (N, n_waves) complex; transfers None, (S-1, n_waves) broadcast or (S-1, N, n_waves) complex.
     Returns the keys of sweep_host; traj is (N, n_saved_total, n_waves).
     """
-    dtype = np.dtype(dtype)
-    if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
-        raise ValueError("dtype must be float64 or float32")
-    cdt = np.complex128 if dtype == np.float64 else np.complex64
+    dtype, cdt, f64 = _dtypes(dtype)
     dbeta = np.ascontiguousarray(np.asarray(dbeta), dtype=dtype)
     if dbeta.ndim != 2 or dbeta.shape[0] < 1:
         raise ValueError("dbeta must have shape (S, N)")
@@ -385,35 +390,9 @@ def chain_host(dbeta, *, n_steps, seg_len, save_every: int, gamma, alpha, a0, tr
     lens = np.ascontiguousarray(np.asarray(seg_len), dtype=np.float64)
     if steps.shape != (S,) or lens.shape != (S,):
         raise ValueError(f"n_steps and seg_len must have shape ({S},)")
-    a0 = np.ascontiguousarray(np.asarray(a0), dtype=cdt)
-    if a0.ndim == 1:
-        a0 = a0[None, :]
-    if a0.ndim != 2 or a0.shape[1] not in (4, 6) or a0.shape[0] not in (1, N):
-        raise ValueError(f"a0 must have shape (n_waves,) or ({N}, n_waves) with n_waves in (4, 6)")
+    flags, gamma, alpha, a0, d2 = _point_inputs(N, dtype, cdt, int(extra_flags), gamma, alpha, a0, (4, 6), dbeta, dbeta2, S)
+    flags |= _check_flags(check_nan, exact_step, f64)
     nw = int(a0.shape[1])
-    flags = int(extra_flags) | (BCAST_A0 if a0.shape[0] == 1 else 0)
-    per_span = []
-    for name, x, bit in (("gamma", gamma, BCAST_GAMMA), ("alpha", alpha, BCAST_ALPHA)):
-        arr = np.ascontiguousarray(np.asarray(x), dtype=dtype)
-        if arr.shape == (S,):
-            flags |= bit
-        elif arr.shape != (S, N):
-            raise ValueError(f"{name} must have shape ({S},) or ({S}, {N})")
-        per_span.append(arr)
-    gamma, alpha = per_span
-    if check_nan:
-        flags |= OPT_CHECK_NAN
-        if exact_step or (exact_step is None and dtype == np.float64):
-            flags |= OPT_EXACT_STEP
-    d2 = None
-    if nw == 6:
-        if dbeta2 is None:
-            raise ValueError("n_waves == 6 needs dbeta2")
-        d2 = np.ascontiguousarray(np.asarray(dbeta2), dtype=dtype)
-        if d2.shape != dbeta.shape:
-            raise ValueError("dbeta2 must match dbeta")
-    elif dbeta2 is not None:
-        raise ValueError("dbeta2 is only meaningful for 6 waves")
     tr = None
     if transfers is not None and S > 1:
         tr = np.ascontiguousarray(np.asarray(transfers), dtype=cdt)
@@ -430,10 +409,10 @@ def chain_host(dbeta, *, n_steps, seg_len, save_every: int, gamma, alpha, a0, tr
     w_end = np.empty((N, nw), dtype=dtype) if wave_summary else None
     w_max = np.empty((N, nw), dtype=dtype) if wave_summary else None
     ms = C.c_double(0.0)
-    fn = lib().psa_rk4_chain_f64 if dtype == np.float64 else lib().psa_rk4_chain_f32
-    _check(fn(int(device), nw, N, S, _ptr(steps), _ptr(lens), int(save_every), _ptr(dbeta), _ptr(d2), _ptr(gamma),
-              _ptr(alpha), _ptr(a0), _ptr(tr), flags, _ptr(a_end), _ptr(p_end), _ptr(p_max), _ptr(bad), _ptr(traj),
-              C.cast(C.byref(ms), C.c_void_p), _ptr(w_end), _ptr(w_max)))
+    _check(_fn("psa_rk4_chain", f64)(
+        int(device), nw, N, S, _ptr(steps), _ptr(lens), int(save_every), _ptr(dbeta), _ptr(d2), _ptr(gamma),
+        _ptr(alpha), _ptr(a0), _ptr(tr), flags, _ptr(a_end), _ptr(p_end), _ptr(p_max), _ptr(bad), _ptr(traj),
+        C.cast(C.byref(ms), _P), _ptr(w_end), _ptr(w_max)))
     return dict(a_end=a_end, p_end=p_end, p_max=p_max, first_bad_step=bad, traj=traj, elapsed_ms=ms.value,
                 p_wave_end=w_end, p_wave_max=w_max)
 
@@ -453,11 +432,11 @@ def chain_device(*, stream: int, n_waves: int, n_points: int, n_steps, seg_len, 
     lens = np.ascontiguousarray(np.asarray(seg_len), dtype=np.float64)
     if steps.ndim != 1 or steps.shape != lens.shape:
         raise ValueError("n_steps and seg_len must be 1-D of equal length")
-    fn = lib().psa_rk4_chain_f64_dev if np.dtype(dtype) == np.float64 else lib().psa_rk4_chain_f32_dev
-    _check(fn(stream or None, int(n_waves), int(n_points), int(steps.shape[0]), _ptr(steps), _ptr(lens),
-              int(save_every), d_dbeta or None, d_dbeta2 or None, d_gamma or None, d_alpha or None, d_a0_soa or None,
-              d_transfer_soa or None, int(flags), d_a_end_soa or None, d_p_end or None, d_p_max or None,
-              d_first_bad or None, d_traj_soa or None, d_p_wave_end or None, d_p_wave_max or None, d_workspace or None))
+    _check(_fn("psa_rk4_chain", _is_f64(dtype), dev=True)(
+        stream or None, int(n_waves), int(n_points), int(steps.shape[0]), _ptr(steps), _ptr(lens),
+        int(save_every), d_dbeta or None, d_dbeta2 or None, d_gamma or None, d_alpha or None, d_a0_soa or None,
+        d_transfer_soa or None, int(flags), d_a_end_soa or None, d_p_end or None, d_p_max or None,
+        d_first_bad or None, d_traj_soa or None, d_p_wave_end or None, d_p_wave_max or None, d_workspace or None))
 
 
 def rk45_sweep_host(dbeta, *, z_max: float, rtol: float, atol: float, h_max: float = float("inf"),
@@ -473,29 +452,9 @@ def rk45_sweep_host(dbeta, *, z_max: float, rtol: float, atol: float, h_max: flo
     if dbeta.ndim != 1:
         raise ValueError("dbeta must be 1-D")
     N = int(dbeta.shape[0])
-    a0 = np.ascontiguousarray(np.asarray(a0), dtype=np.complex128)
-    if a0.ndim == 1:
-        a0 = a0[None, :]
-    if a0.ndim != 2 or a0.shape[1] not in (4, 6):
-        raise ValueError("a0 must have shape (n_waves,) or (N, n_waves) with n_waves in (4, 6)")
+    flags, gamma, alpha, a0, d2 = _point_inputs(N, np.float64, np.complex128, int(extra_flags), gamma, alpha, a0, (4, 6),
+                                                dbeta, dbeta2)
     nw = int(a0.shape[1])
-    flags = int(extra_flags)
-    if a0.shape[0] == 1:
-        flags |= BCAST_A0
-    elif a0.shape[0] != N:
-        raise ValueError(f"a0 must have 1 or {N} rows, got {a0.shape[0]}")
-    gamma, gb = _prep(gamma, np.float64, N, "gamma")
-    alpha, ab = _prep(alpha, np.float64, N, "alpha")
-    flags |= (BCAST_GAMMA if gb else 0) | (BCAST_ALPHA if ab else 0)
-    d2 = None
-    if nw == 6:
-        if dbeta2 is None:
-            raise ValueError("n_waves == 6 needs dbeta2")
-        d2 = np.ascontiguousarray(np.atleast_1d(np.asarray(dbeta2)), dtype=np.float64)
-        if d2.shape != dbeta.shape:
-            raise ValueError("dbeta2 must match dbeta")
-    elif dbeta2 is not None:
-        raise ValueError("dbeta2 is only meaningful for 6 waves")
     n_out = int(n_out)
     a_end = np.empty((N, nw), dtype=np.complex128)
     p_end, p_max, z_end = (np.empty(N, dtype=np.float64) for _ in range(3))
@@ -503,10 +462,10 @@ def rk45_sweep_host(dbeta, *, z_max: float, rtol: float, atol: float, h_max: flo
     n_acc, n_rej = np.empty(N, dtype=np.int64), np.empty(N, dtype=np.int64)
     traj = np.empty((N, n_out + 1, nw), dtype=np.complex128) if n_out > 0 else None
     ms = C.c_double(0.0)
-    _check(lib().psa_rk45_sweep_f64(int(device), nw, N, float(z_max), float(rtol), float(atol), float(h_max),
-                                    float(first_step), int(max_steps), n_out, _ptr(dbeta), _ptr(d2), _ptr(gamma),
-                                    _ptr(alpha), _ptr(a0), flags, _ptr(a_end), _ptr(p_end), _ptr(p_max), _ptr(status),
-                                    _ptr(z_end), _ptr(n_acc), _ptr(n_rej), _ptr(traj), C.cast(C.byref(ms), C.c_void_p)))
+    _check(_fn("psa_rk45_sweep")(int(device), nw, N, float(z_max), float(rtol), float(atol), float(h_max),
+                                 float(first_step), int(max_steps), n_out, _ptr(dbeta), _ptr(d2), _ptr(gamma),
+                                 _ptr(alpha), _ptr(a0), flags, _ptr(a_end), _ptr(p_end), _ptr(p_max), _ptr(status),
+                                 _ptr(z_end), _ptr(n_acc), _ptr(n_rej), _ptr(traj), C.cast(C.byref(ms), _P)))
     return dict(a_end=a_end, p_end=p_end, p_max=p_max, status=status, z_end=z_end, n_accepted=n_acc,
                 n_rejected=n_rej, traj=traj, elapsed_ms=ms.value)
 
@@ -517,12 +476,11 @@ def rk45_sweep_device(*, stream: int, n_waves: int, n_points: int, z_max: float,
                       d_p_max: int, d_status: int, d_z_end: int, d_n_accepted: int, d_n_rejected: int,
                       d_traj_soa: int = 0) -> None:
     """Asynchronous adaptive launch on device pointers (ints), SoA layout -- see psa_rk45_sweep_f64_dev."""
-    _check(lib().psa_rk45_sweep_f64_dev(stream or None, int(n_waves), int(n_points), float(z_max), float(rtol),
-                                        float(atol), float(h_max), float(first_step), int(max_steps), int(n_out),
-                                        d_dbeta or None, d_dbeta2 or None, d_gamma or None, d_alpha or None,
-                                        d_a0_soa or None, int(flags), d_a_end_soa or None, d_p_end or None,
-                                        d_p_max or None, d_status or None, d_z_end or None, d_n_accepted or None,
-                                        d_n_rejected or None, d_traj_soa or None))
+    _check(_fn("psa_rk45_sweep", dev=True)(
+        stream or None, int(n_waves), int(n_points), float(z_max), float(rtol), float(atol), float(h_max),
+        float(first_step), int(max_steps), int(n_out), d_dbeta or None, d_dbeta2 or None, d_gamma or None,
+        d_alpha or None, d_a0_soa or None, int(flags), d_a_end_soa or None, d_p_end or None, d_p_max or None,
+        d_status or None, d_z_end or None, d_n_accepted or None, d_n_rejected or None, d_traj_soa or None))
 
 
 def yaman_rhs_host(z, a, gamma, alpha, dbeta, *, terms: bool = False, device: int = 0):
@@ -554,9 +512,8 @@ def gain_summary_host(p_metric, first_bad_step, p0_sig: float, *, gain_db: bool 
     bi = C.c_int64(-1)
     bg = C.c_double(float("nan"))
     nf = C.c_int64(0)
-    fn = lib().psa_gain_summary_f32 if f32 else lib().psa_gain_summary_f64
-    _check(fn(int(device), N, _ptr(p), _ptr(bad), float(p0_sig), int(bool(gain_db)), _ptr(gain),
-              C.cast(C.byref(bi), _P), C.cast(C.byref(bg), _P), C.cast(C.byref(nf), _P)))
+    _check(_fn("psa_gain_summary", not f32)(int(device), N, _ptr(p), _ptr(bad), float(p0_sig), int(bool(gain_db)), _ptr(gain),
+                                            C.cast(C.byref(bi), _P), C.cast(C.byref(bg), _P), C.cast(C.byref(nf), _P)))
     return gain, int(bi.value), float(bg.value), int(nf.value)
 
 
@@ -564,10 +521,9 @@ def gain_summary_device(*, stream: int, n_points: int, d_p_metric: int, d_first_
                         d_gain: int, d_best_index: int, d_best_gain: int, d_n_finite: int, d_workspace: int,
                         dtype=np.float64) -> None:
     """Asynchronous gain reduction on device pointers (ints) -- see psa_gain_summary_f64_dev / _f32_dev."""
-    fn = lib().psa_gain_summary_f64_dev if np.dtype(dtype) == np.float64 else lib().psa_gain_summary_f32_dev
-    _check(fn(stream or None, int(n_points), d_p_metric or None, d_first_bad or None, float(p0_sig),
-              int(bool(gain_db)), d_gain or None, d_best_index or None, d_best_gain or None, d_n_finite or None,
-              d_workspace or None))
+    _check(_fn("psa_gain_summary", _is_f64(dtype), dev=True)(
+        stream or None, int(n_points), d_p_metric or None, d_first_bad or None, float(p0_sig), int(bool(gain_db)),
+        d_gain or None, d_best_index or None, d_best_gain or None, d_n_finite or None, d_workspace or None))
 
 
 def gain_summary_workspace_bytes(n_points: int) -> int:
@@ -623,9 +579,9 @@ def dbeta_grid_host(model: dict, lambda1_m: float, lambda2_axis, lambda3_axis, *
 
 def dbeta_grid_device(model: dict, lambda1_m: float, *, stream: int, d_lambda2_axis: int, n2: int, d_lambda3_axis: int,
                       n3: int, first: int, n_points: int, d_dbeta: int, d_valid: int = 0, dtype=np.float64) -> None:
-    fn = lib().psa_dbeta_grid_f64_dev if np.dtype(dtype) == np.float64 else lib().psa_dbeta_grid_f32_dev
-    _check(fn(stream or None, *_model_head(model), float(lambda1_m), d_lambda2_axis or None, int(n2),
-              d_lambda3_axis or None, int(n3), int(first), int(n_points), d_dbeta or None, d_valid or None))
+    _check(_fn("psa_dbeta_grid", _is_f64(dtype), dev=True)(
+        stream or None, *_model_head(model), float(lambda1_m), d_lambda2_axis or None, int(n2), d_lambda3_axis or None,
+        int(n3), int(first), int(n_points), d_dbeta or None, d_valid or None))
 
 
 def dbeta_pairs_host(model: dict, omega_d: float, Omega1_axis, Omega2_axis, *, first: int = 0,
@@ -642,7 +598,7 @@ def dbeta_pairs_host(model: dict, omega_d: float, Omega1_axis, Omega2_axis, *, f
 
 def dbeta_pairs_device(model: dict, omega_d: float, *, stream: int, d_Omega1_axis: int, n1: int, d_Omega2_axis: int,
                        n2: int, first: int, n_points: int, d_dbeta1: int, d_dbeta2: int, dtype=np.float64) -> None:
-    fn = lib().psa_dbeta_pairs_f64_dev if np.dtype(dtype) == np.float64 else lib().psa_dbeta_pairs_f32_dev
-    _check(fn(stream or None, _ptr(model["orders"]), int(model["orders"].size), _ptr(model["beta"]),
-              int(model["beta"].size), float(omega_d), d_Omega1_axis or None, int(n1), d_Omega2_axis or None, int(n2),
-              int(first), int(n_points), d_dbeta1 or None, d_dbeta2 or None))
+    _check(_fn("psa_dbeta_pairs", _is_f64(dtype), dev=True)(
+        stream or None, _ptr(model["orders"]), int(model["orders"].size), _ptr(model["beta"]), int(model["beta"].size),
+        float(omega_d), d_Omega1_axis or None, int(n1), d_Omega2_axis or None, int(n2), int(first), int(n_points),
+        d_dbeta1 or None, d_dbeta2 or None))

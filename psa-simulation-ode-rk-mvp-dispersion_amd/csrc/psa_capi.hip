@@ -50,75 +50,147 @@ int64_t traj_ld_of(int64_t n_points, size_t elem_size) {
     return n_points + 4352 / pair;          // 17 x 256 B: 272 float64 points, 544 float32 points
 }
 
-int validate_common(int n_waves, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
-                    const void *dbeta, const void *dbeta2, const void *gamma, const void *alpha, const void *a0,
-                    const void *a_end, const void *p_end, const void *p_max, const void *first_bad, uint32_t flags,
-                    bool has_traj, size_t elem_size) {
-    if (n_waves != 4 && n_waves != 6) return fail(PSA_E_NWAVES, "n_waves must be 4 or 6, got %d", n_waves);
+// ---- call records ------------------------------------------------------------------------------------------------------
+// What one call of a sweep family asks for, fields in the order of its C arguments.  The extern "C" function builds the record
+// once; validation, the `_dev` path and the host path take it by reference.  The host path copies it, has its layout function
+// put device pointers (Staging) in place of the copy's buffer pointers and hands the copy to the same `_dev` function.  A new
+// family brings its record, its validator, its `_dev` function and its layout; the rules the families share are stated once
+// below (validate_grid, validate_common, fill_point_args, lossless_bit).
+template <typename T>
+struct SweepCall {   // psa_rk4_sweep_*, psa_rk4_sweep_waves_* and one span of a chain
+    int n_waves;
+    int64_t n_points, n_steps;
+    double z_max;
+    int32_t save_every;
+    const T *dbeta, *dbeta2, *gamma, *alpha, *a0;
+    uint32_t flags;
+    T *a_end, *p_end, *p_max;
+    int64_t *first_bad;
+    T *traj;
+    T *wave_end = nullptr, *wave_max = nullptr;   // the per-wave summary (on the device SoA [n_waves][N]); launched where set
+    bool waves = false;                           // psa_rk4_sweep_waves_*: the summary is required, its rules are checked first
+};
+struct PairsCall {   // psa_rk4_sweep_pairs_f64*
+    int n_pairs;
+    int64_t n_points, n_steps;
+    double z_max;
+    int32_t save_every;
+    const double *dbeta, *gamma, *alpha, *a0;
+    uint32_t flags;
+    double *a_end, *wave_end, *wave_max;
+    int64_t *first_bad;
+};
+struct Rk45Call {    // psa_rk45_sweep_f64*
+    int n_waves;
+    int64_t n_points;
+    double z_max, rtol, atol, h_max, first_step;
+    int64_t max_steps, n_out;
+    const double *dbeta, *dbeta2, *gamma, *alpha, *a0;
+    uint32_t flags;
+    double *a_end, *p_end, *p_max;
+    int32_t *status;
+    double *z_end;
+    int64_t *n_acc, *n_rej;
+    double *traj;
+    int64_t traj_ld;   // leading dimension of the device rows: n_points (`_dev`), traj_ld_of (the host form's staging)
+};
+template <typename T>
+struct ChainCall {   // psa_rk4_chain_*
+    SweepCall<T> s;             // what the spans share; its n_steps and z_max are set span by span from the arrays below
+    int n_segments;
+    const int64_t *n_steps;     // host [S]
+    const double *seg_len;      // host [S]
+    const T *transfer;
+    void *workspace;            // device scratch of more than one span (chain_workspace_bytes)
+    // host [S] or NULL: span s gets PSA_OPT_LOSSLESS where it is non-zero (the host-buffer entry points: a broadcast alpha
+    // of 0); `_dev` callers pass PSA_OPT_LOSSLESS for the whole chain instead
+    const unsigned char *lossless = nullptr;
+};
+
+// The grid rules of every fixed-step family.  lanes_per_point: named in the message when the launch limit depends on it (0: not).
+int validate_grid(int64_t n_points, long long max_points, long long lanes_per_point, int64_t n_steps, double z_max,
+                  int32_t save_every) {
     if (n_points < 0) return fail(PSA_E_NPOINTS, "n_points must be >= 0, got %lld", (long long)n_points);
-    // a launch is at most 2^32 - 1 threads in x, and the two-lane float64 layout spends two of them per point
-    if (n_points > PSA_MAX_POINTS)
-        return fail(PSA_E_TOO_LARGE, "n_points %lld exceeds the launch limit of %lld points", (long long)n_points,
-                    (long long)PSA_MAX_POINTS);
+    if (n_points > max_points)   // the wording without the lanes leaves the last argument unread
+        return fail(PSA_E_TOO_LARGE,
+                    lanes_per_point ? "n_points %lld exceeds the launch limit of %lld points at %lld lanes per point"
+                                    : "n_points %lld exceeds the launch limit of %lld points",
+                    (long long)n_points, max_points, lanes_per_point);
     if (n_steps <= 0 || n_steps > 2147483647LL)
         return fail(PSA_E_NSTEPS, "n_steps must be in [1, 2^31), got %lld", (long long)n_steps);
     if (!(z_max > 0.0) || !std::isfinite(z_max)) return fail(PSA_E_ZMAX, "z_max must be positive");
     if (save_every <= 0) return fail(PSA_E_SAVE_EVERY, "save_every must be a positive integer");
-    if (n_waves == 6 && !dbeta2 && n_points > 0) return fail(PSA_E_DBETA2, "n_waves == 6 requires dbeta2");
-    if (n_waves == 4 && dbeta2) return fail(PSA_E_DBETA2, "dbeta2 must be NULL for n_waves == 4");
-    {
-        const int layouts = !!(flags & PSA_OPT_SPLIT_POINT) + !!(flags & PSA_OPT_ONE_LANE) + !!(flags & PSA_OPT_QUAD_POINT);
-        if (layouts > 1)
-            return fail(PSA_E_FLAGS, "PSA_OPT_SPLIT_POINT, PSA_OPT_ONE_LANE and PSA_OPT_QUAD_POINT exclude each other");
-        if ((flags & PSA_OPT_QUAD_POINT) && n_waves != 4)
-            return fail(PSA_E_FLAGS, "PSA_OPT_QUAD_POINT (four lanes per point) exists for the 4-wave model only");
-    }
-    if ((flags & PSA_OPT_F32_SCALAR) && (flags & PSA_OPT_F32_PACKED))
-        return fail(PSA_E_FLAGS, "PSA_OPT_F32_SCALAR and PSA_OPT_F32_PACKED exclude each other");
-    if (n_points > 0 && (!dbeta || !gamma || !alpha || !a0 || !a_end || !p_end || !p_max || !first_bad))
-        return fail(PSA_E_NULLPTR, "a required buffer pointer is NULL");
-    if (has_traj) {
-        // trajectory rows are addressed as a wave-uniform (row, wave) base + a 32-bit byte offset per lane, kept below 2^31
-        const unsigned long long pair = 2ull * elem_size;
-        if ((unsigned long long)n_points * pair >= (1ull << 31))
-            return fail(PSA_E_TOO_LARGE, "a trajectory launch takes at most %llu points", (1ull << 31) / pair - 1);
-        // the two-lane layout folds the lane's wave offset into that 32-bit offset
-        const unsigned long long ld = (flags & PSA_OPT_TRAJ_LD) ? (unsigned long long)traj_ld_of(n_points, elem_size) : (unsigned long long)n_points;
-        if ((flags & (PSA_OPT_SPLIT_POINT | PSA_OPT_QUAD_POINT)) && ld * n_waves * pair >= (1ull << 32))
-            return fail(PSA_E_TOO_LARGE, "a two-lane trajectory launch takes at most %llu points",
-                        (1ull << 32) / (n_waves * pair) - 1);
-    }
+    return PSA_OK;
+}
+
+// The per-wave summary entry points (psa_rk4_sweep_waves_*) are offered for the register layouts without trajectory
+// and with the automatic block sizes only.
+template <typename T>
+int validate_waves(const SweepCall<T> &c) {
+    if (c.traj) return fail(PSA_E_FLAGS, "the per-wave summary takes no trajectory (traj_or_null must be NULL)");
+    if (c.flags & PSA_OPT_LDS_STAGING) return fail(PSA_E_FLAGS, "the per-wave summary does not exist with PSA_OPT_LDS_STAGING");
+    if (c.flags & PSA_OPT_BLOCK64) return fail(PSA_E_FLAGS, "the per-wave summary does not exist with PSA_OPT_BLOCK64");
+    if (c.n_points > 0 && (!c.wave_end || !c.wave_max)) return fail(PSA_E_NULLPTR, "p_wave_end / p_wave_max is NULL");
     return PSA_OK;
 }
 
 template <typename T>
-psa::SweepArgs<T> make_args(int n_waves, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
-                            const T *dbeta, const T *dbeta2, const T *gamma, const T *alpha, const T *a0_soa,
-                            uint32_t flags, T *a_end, T *p_end, T *p_max, int64_t *first_bad, T *traj) {
-    psa::SweepArgs<T> a;
-    a.dbeta = dbeta;
-    a.dbeta2 = dbeta2;
-    a.gamma = gamma;
-    a.alpha = alpha;
-    a.a0 = a0_soa;
-    a.a_end = a_end;
-    a.p_end = p_end;
-    a.p_max = p_max;
-    a.first_bad = (long long *)first_bad;
-    a.traj = traj;
-    a.traj_ld = (flags & PSA_OPT_TRAJ_LD) ? traj_ld_of(n_points, sizeof(T)) : n_points;
-    a.n_points = n_points;
-    a.z_max = z_max;
-    a.n_steps = (int)n_steps;
-    a.save_every = save_every;
-    a.gamma_stride = (flags & PSA_BCAST_GAMMA) ? 0 : 1;
-    a.alpha_stride = (flags & PSA_BCAST_ALPHA) ? 0 : 1;
-    a.a0_stride = (flags & PSA_BCAST_A0) ? 0 : 1;
-    a.a0_ld = (flags & PSA_BCAST_A0) ? 1 : n_points;
-    a.p_wave_end = nullptr;
-    a.p_wave_max = nullptr;
-    (void)n_waves;
-    return a;
+int validate_common(const SweepCall<T> &c) {
+    int rc;
+    if (c.waves && (rc = validate_waves(c)) != PSA_OK) return rc;
+    if (c.n_waves != 4 && c.n_waves != 6) return fail(PSA_E_NWAVES, "n_waves must be 4 or 6, got %d", c.n_waves);
+    // a launch is at most 2^32 - 1 threads in x, and the two-lane float64 layout spends two of them per point
+    rc = validate_grid(c.n_points, PSA_MAX_POINTS, 0, c.n_steps, c.z_max, c.save_every);
+    if (rc != PSA_OK) return rc;
+    if (c.n_waves == 6 && !c.dbeta2 && c.n_points > 0) return fail(PSA_E_DBETA2, "n_waves == 6 requires dbeta2");
+    if (c.n_waves == 4 && c.dbeta2) return fail(PSA_E_DBETA2, "dbeta2 must be NULL for n_waves == 4");
+    const uint32_t flags = c.flags;
+    {
+        const int layouts = !!(flags & PSA_OPT_SPLIT_POINT) + !!(flags & PSA_OPT_ONE_LANE) + !!(flags & PSA_OPT_QUAD_POINT);
+        if (layouts > 1)
+            return fail(PSA_E_FLAGS, "PSA_OPT_SPLIT_POINT, PSA_OPT_ONE_LANE and PSA_OPT_QUAD_POINT exclude each other");
+        if ((flags & PSA_OPT_QUAD_POINT) && c.n_waves != 4)
+            return fail(PSA_E_FLAGS, "PSA_OPT_QUAD_POINT (four lanes per point) exists for the 4-wave model only");
+    }
+    if ((flags & PSA_OPT_F32_SCALAR) && (flags & PSA_OPT_F32_PACKED))
+        return fail(PSA_E_FLAGS, "PSA_OPT_F32_SCALAR and PSA_OPT_F32_PACKED exclude each other");
+    if (c.n_points > 0 && (!c.dbeta || !c.gamma || !c.alpha || !c.a0 || !c.a_end || !c.p_end || !c.p_max || !c.first_bad))
+        return fail(PSA_E_NULLPTR, "a required buffer pointer is NULL");
+    if (c.traj) {
+        // trajectory rows are addressed as a wave-uniform (row, wave) base + a 32-bit byte offset per lane, kept below 2^31
+        const unsigned long long pair = 2ull * sizeof(T);
+        if ((unsigned long long)c.n_points * pair >= (1ull << 31))
+            return fail(PSA_E_TOO_LARGE, "a trajectory launch takes at most %llu points", (1ull << 31) / pair - 1);
+        // the two-lane layout folds the lane's wave offset into that 32-bit offset
+        const unsigned long long ld = (flags & PSA_OPT_TRAJ_LD) ? (unsigned long long)traj_ld_of(c.n_points, sizeof(T)) : (unsigned long long)c.n_points;
+        if ((flags & (PSA_OPT_SPLIT_POINT | PSA_OPT_QUAD_POINT)) && ld * c.n_waves * pair >= (1ull << 32))
+            return fail(PSA_E_TOO_LARGE, "a two-lane trajectory launch takes at most %llu points",
+                        (1ull << 32) / (c.n_waves * pair) - 1);
+    }
+    return PSA_OK;
+}
+
+// What SweepArgs, AdaptiveArgs and PairsArgs share (they agree on the field names): the per-point inputs with the strides the
+// PSA_BCAST_* bits select, a_end, n_points and z_max.
+template <typename Args, typename Call>
+void fill_point_args(Args &a, const Call &c) {
+    a.dbeta = c.dbeta;
+    a.gamma = c.gamma;
+    a.alpha = c.alpha;
+    a.a0 = c.a0;
+    a.a_end = c.a_end;
+    a.n_points = c.n_points;
+    a.z_max = c.z_max;
+    a.gamma_stride = (c.flags & PSA_BCAST_GAMMA) ? 0 : 1;
+    a.alpha_stride = (c.flags & PSA_BCAST_ALPHA) ? 0 : 1;
+    a.a0_stride = (c.flags & PSA_BCAST_A0) ? 0 : 1;
+    a.a0_ld = (c.flags & PSA_BCAST_A0) ? 1 : c.n_points;
+}
+
+// The reference's alpha == 0.0 branch: a broadcast alpha (host pointer) of 0 selects PSA_OPT_LOSSLESS.
+template <typename T>
+uint32_t lossless_bit(uint32_t flags, const T *alpha) {
+    return ((flags & PSA_BCAST_ALPHA) && alpha[0] == T(0)) ? PSA_OPT_LOSSLESS : 0u;
 }
 
 template <typename T> struct Launch;
@@ -135,44 +207,27 @@ template <> struct Launch<float> {
     static hipError_t t2a(hipStream_t s, const float *a, float *b, long long n, long long ld, long long r, int nc) { return psa::launch_traj_to_aos_f32(s, a, b, n, ld, r, nc); }
 };
 
-// The per-wave summary entry points (psa_rk4_sweep_waves_*) are offered for the register layouts without trajectory
-// and with the automatic block sizes only.
-int validate_waves(uint32_t flags, bool has_traj, int64_t n_points, const void *wave_end, const void *wave_max) {
-    if (has_traj) return fail(PSA_E_FLAGS, "the per-wave summary takes no trajectory (traj_or_null must be NULL)");
-    if (flags & PSA_OPT_LDS_STAGING) return fail(PSA_E_FLAGS, "the per-wave summary does not exist with PSA_OPT_LDS_STAGING");
-    if (flags & PSA_OPT_BLOCK64) return fail(PSA_E_FLAGS, "the per-wave summary does not exist with PSA_OPT_BLOCK64");
-    if (n_points > 0 && (!wave_end || !wave_max)) return fail(PSA_E_NULLPTR, "p_wave_end / p_wave_max is NULL");
-    return PSA_OK;
-}
-
-// d_wave_end / d_wave_max non-NULL: the per-wave summary (SoA [n_waves][N]); the caller has run validate_waves
+// every pointer of c is a device pointer (a0, a_end, traj and the wave summary SoA)
 template <typename T>
-int sweep_dev(void *stream, int n_waves, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
-              const T *d_dbeta, const T *d_dbeta2, const T *d_gamma, const T *d_alpha, const T *d_a0_soa,
-              uint32_t flags, T *d_a_end_soa, T *d_p_end, T *d_p_max, int64_t *d_first_bad, T *d_traj_soa,
-              T *d_wave_end = nullptr, T *d_wave_max = nullptr) {
-    int rc = validate_common(n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha,
-                             d_a0_soa, d_a_end_soa, d_p_end, d_p_max, d_first_bad, flags, d_traj_soa != nullptr, sizeof(T));
+int sweep_dev(void *stream, const SweepCall<T> &c) {
+    int rc = validate_common(c);
     if (rc != PSA_OK) return rc;
-    if (n_points == 0) return PSA_OK;
-    auto a = make_args<T>(n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha,
-                          d_a0_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa);
-    a.p_wave_end = d_wave_end;
-    a.p_wave_max = d_wave_max;
-    hipError_t e = Launch<T>::sweep((hipStream_t)stream, n_waves, flags, a);
+    if (c.n_points == 0) return PSA_OK;
+    psa::SweepArgs<T> a;
+    fill_point_args(a, c);
+    a.dbeta2 = c.dbeta2;
+    a.p_end = c.p_end;
+    a.p_max = c.p_max;
+    a.first_bad = (long long *)c.first_bad;
+    a.traj = c.traj;
+    a.traj_ld = (c.flags & PSA_OPT_TRAJ_LD) ? traj_ld_of(c.n_points, sizeof(T)) : c.n_points;
+    a.n_steps = (int)c.n_steps;
+    a.save_every = c.save_every;
+    a.p_wave_end = c.wave_end;
+    a.p_wave_max = c.wave_max;
+    hipError_t e = Launch<T>::sweep((hipStream_t)stream, c.n_waves, c.flags, a);
     if (e != hipSuccess) return hip_fail(e, "rk4_sweep launch");
     return PSA_OK;
-}
-
-template <typename T>
-int sweep_waves_dev(void *stream, int n_waves, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
-                    const T *d_dbeta, const T *d_dbeta2, const T *d_gamma, const T *d_alpha, const T *d_a0_soa,
-                    uint32_t flags, T *d_a_end_soa, T *d_p_end, T *d_p_max, int64_t *d_first_bad, T *d_traj_soa,
-                    T *d_wave_end, T *d_wave_max) {
-    int rc = validate_waves(flags, d_traj_soa != nullptr, n_points, d_wave_end, d_wave_max);
-    if (rc != PSA_OK) return rc;
-    return sweep_dev<T>(stream, n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha,
-                        d_a0_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa, d_wave_end, d_wave_max);
 }
 
 // Device scratch that frees itself on every exit path of the host-buffer entry points.
@@ -484,130 +539,90 @@ int host_call(int device, const char *what, double *elapsed_ms, Layout &&layout,
     return PSA_OK;
 }
 
-// waves: psa_rk4_sweep_waves_* (the per-wave summary into wave_end / wave_max)
 template <typename T>
-int sweep_host(int device, int n_waves, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
-               const T *dbeta, const T *dbeta2, const T *gamma, const T *alpha, const T *a0, uint32_t flags,
-               T *a_end, T *p_end, T *p_max, int64_t *first_bad, T *traj, double *elapsed_ms,
-               bool waves = false, T *wave_end = nullptr, T *wave_max = nullptr) {
-    int rc;
-    if (waves && (rc = validate_waves(flags, traj != nullptr, n_points, wave_end, wave_max)) != PSA_OK) return rc;
-    rc = validate_common(n_waves, n_points, n_steps, z_max, save_every, dbeta, dbeta2, gamma, alpha, a0, a_end, p_end,
-                         p_max, first_bad, flags, traj != nullptr, sizeof(T));
+int sweep_host(int device, const SweepCall<T> &c, double *elapsed_ms) {
+    int rc = validate_common(c);
     if (rc != PSA_OK) return rc;
     if (elapsed_ms) *elapsed_ms = 0.0;
-    if (n_points == 0) return PSA_OK;
-    const int nc = 2 * n_waves;
-    const size_t N = (size_t)n_points;
-    if (traj) flags |= PSA_OPT_TRAJ_LD;   // the device-side trajectory has its own leading dimension; the caller's is dense
-    if ((flags & PSA_BCAST_ALPHA) && alpha[0] == T(0)) flags |= PSA_OPT_LOSSLESS;   // the reference's alpha == 0.0 branch
-    const T *d_dbeta, *d_dbeta2, *d_gamma, *d_alpha, *d_a0;
-    T *d_aend, *d_pend, *d_pmax, *d_wend, *d_wmax, *d_traj;
-    int64_t *d_bad;
+    if (c.n_points == 0) return PSA_OK;
+    const int nc = 2 * c.n_waves;
+    const size_t N = (size_t)c.n_points;
+    SweepCall<T> d = c;                       // the call on device buffers: the layout fills in the pointers
+    if (c.traj) d.flags |= PSA_OPT_TRAJ_LD;   // the device-side trajectory has its own leading dimension; the caller's is dense
+    d.flags |= lossless_bit(c.flags, c.alpha);
     auto layout = [&](Staging<T> &sg) {
-        d_dbeta = sg.input(dbeta, N);
-        d_dbeta2 = sg.input(dbeta2, N);
-        d_gamma = sg.input(gamma, (flags & PSA_BCAST_GAMMA) ? 1 : N);
-        d_alpha = sg.input(alpha, (flags & PSA_BCAST_ALPHA) ? 1 : N);
-        d_a0 = sg.input_soa(a0, (flags & PSA_BCAST_A0) ? 1 : N, nc);
-        d_aend = sg.output_soa(a_end, N, nc);
-        d_pend = sg.output(p_end, N);
-        d_pmax = sg.output(p_max, N);
-        d_bad = sg.output(first_bad, N);
-        d_wend = sg.output_soa(wave_end, N, n_waves);
-        d_wmax = sg.output_soa(wave_max, N, n_waves);
-        d_traj = sg.trajectory(traj, N, (size_t)(n_steps / save_every + 1), nc);
+        d.dbeta = sg.input(c.dbeta, N);
+        d.dbeta2 = sg.input(c.dbeta2, N);
+        d.gamma = sg.input(c.gamma, (c.flags & PSA_BCAST_GAMMA) ? 1 : N);
+        d.alpha = sg.input(c.alpha, (c.flags & PSA_BCAST_ALPHA) ? 1 : N);
+        d.a0 = sg.input_soa(c.a0, (c.flags & PSA_BCAST_A0) ? 1 : N, nc);
+        d.a_end = sg.output_soa(c.a_end, N, nc);
+        d.p_end = sg.output(c.p_end, N);
+        d.p_max = sg.output(c.p_max, N);
+        d.first_bad = sg.output(c.first_bad, N);
+        d.wave_end = sg.output_soa(c.wave_end, N, c.n_waves);
+        d.wave_max = sg.output_soa(c.wave_max, N, c.n_waves);
+        d.traj = sg.trajectory(c.traj, N, (size_t)(c.n_steps / c.save_every + 1), nc);
     };
-    return host_call<T>(device, "the RK4 sweep", elapsed_ms, layout, [&](hipStream_t st) {
-        return sweep_dev<T>(st, n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha, d_a0,
-                            flags, d_aend, d_pend, d_pmax, d_bad, d_traj, d_wend, d_wmax);
-    });
+    return host_call<T>(device, "the RK4 sweep", elapsed_ms, layout, [&](hipStream_t st) { return sweep_dev<T>(st, d); });
 }
 
 // ---- the multi-channel sweep (psa_rk4_sweep_pairs_f64*): two pumps and n_pairs signal/idler pairs -----------------------
-int validate_pairs(int n_pairs, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every, const void *dbeta,
-                   const void *gamma, const void *alpha, const void *a0, uint32_t flags, const void *a_end,
-                   const void *wave_end, const void *wave_max, const void *first_bad) {
-    if (n_pairs < 1 || n_pairs > PSA_MAX_PAIRS)
-        return fail(PSA_E_NPAIRS, "n_pairs must be in [1, %d], got %d", PSA_MAX_PAIRS, n_pairs);
-    if (n_points < 0) return fail(PSA_E_NPOINTS, "n_points must be >= 0, got %lld", (long long)n_points);
+int validate_pairs(const PairsCall &c) {
+    if (c.n_pairs < 1 || c.n_pairs > PSA_MAX_PAIRS)
+        return fail(PSA_E_NPAIRS, "n_pairs must be in [1, %d], got %d", PSA_MAX_PAIRS, c.n_pairs);
     // a launch is at most 2^32 - 1 threads in x and a point takes L of them: the power of two >= n_pairs (at least 2)
-    const long long lanes_per_point = psa::pairs_lanes_per_point(n_pairs);
-    if (n_points > 2 * PSA_MAX_POINTS / lanes_per_point)
-        return fail(PSA_E_TOO_LARGE, "n_points %lld exceeds the launch limit of %lld points at %lld lanes per point",
-                    (long long)n_points, 2 * PSA_MAX_POINTS / lanes_per_point, lanes_per_point);
-    if (n_steps <= 0 || n_steps > 2147483647LL)
-        return fail(PSA_E_NSTEPS, "n_steps must be in [1, 2^31), got %lld", (long long)n_steps);
-    if (!(z_max > 0.0) || !std::isfinite(z_max)) return fail(PSA_E_ZMAX, "z_max must be positive");
-    if (save_every <= 0) return fail(PSA_E_SAVE_EVERY, "save_every must be a positive integer");
+    const long long lanes_per_point = psa::pairs_lanes_per_point(c.n_pairs);
+    int rc = validate_grid(c.n_points, 2 * PSA_MAX_POINTS / lanes_per_point, lanes_per_point, c.n_steps, c.z_max, c.save_every);
+    if (rc != PSA_OK) return rc;
     const uint32_t accepted = PSA_BCAST_GAMMA | PSA_BCAST_ALPHA | PSA_BCAST_A0 | PSA_OPT_CHECK_NAN | PSA_OPT_EXACT_STEP |
                               PSA_OPT_LOSSLESS | PSA_OPT_BLOCK64;
-    if (flags & ~accepted)
+    if (c.flags & ~accepted)
         return fail(PSA_E_FLAGS, "the multi-channel sweep takes the BCAST bits, CHECK_NAN, EXACT_STEP, LOSSLESS and BLOCK64 "
-                                 "only (no layout, float32 or LDS flag): 0x%x", (unsigned)(flags & ~accepted));
-    if (n_points > 0 && (!dbeta || !gamma || !alpha || !a0 || !a_end || !wave_end || !wave_max || !first_bad))
+                                 "only (no layout, float32 or LDS flag): 0x%x", (unsigned)(c.flags & ~accepted));
+    if (c.n_points > 0 && (!c.dbeta || !c.gamma || !c.alpha || !c.a0 || !c.a_end || !c.wave_end || !c.wave_max || !c.first_bad))
         return fail(PSA_E_NULLPTR, "a required buffer pointer is NULL");
     return PSA_OK;
 }
 
-int pairs_dev(void *stream, int n_pairs, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
-              const double *d_dbeta, const double *d_gamma, const double *d_alpha, const double *d_a0_soa, uint32_t flags,
-              double *d_a_end_soa, double *d_wave_end, double *d_wave_max, int64_t *d_first_bad) {
-    int rc = validate_pairs(n_pairs, n_points, n_steps, z_max, save_every, d_dbeta, d_gamma, d_alpha, d_a0_soa, flags,
-                            d_a_end_soa, d_wave_end, d_wave_max, d_first_bad);
+int pairs_dev(void *stream, const PairsCall &c) {
+    int rc = validate_pairs(c);
     if (rc != PSA_OK) return rc;
-    if (n_points == 0) return PSA_OK;
+    if (c.n_points == 0) return PSA_OK;
     psa::PairsArgs a;
-    a.dbeta = d_dbeta;
-    a.gamma = d_gamma;
-    a.alpha = d_alpha;
-    a.a0 = d_a0_soa;
-    a.a_end = d_a_end_soa;
-    a.p_wave_end = d_wave_end;
-    a.p_wave_max = d_wave_max;
-    a.first_bad = (long long *)d_first_bad;
-    a.n_points = n_points;
-    a.z_max = z_max;
-    a.n_steps = (int)n_steps;
-    a.save_every = save_every;
-    a.n_pairs = n_pairs;
-    a.gamma_stride = (flags & PSA_BCAST_GAMMA) ? 0 : 1;
-    a.alpha_stride = (flags & PSA_BCAST_ALPHA) ? 0 : 1;
-    a.a0_stride = (flags & PSA_BCAST_A0) ? 0 : 1;
-    a.a0_ld = (flags & PSA_BCAST_A0) ? 1 : n_points;
-    hipError_t e = psa::launch_sweep_pairs_f64((hipStream_t)stream, flags, a);
+    fill_point_args(a, c);
+    a.p_wave_end = c.wave_end;
+    a.p_wave_max = c.wave_max;
+    a.first_bad = (long long *)c.first_bad;
+    a.n_steps = (int)c.n_steps;
+    a.save_every = c.save_every;
+    a.n_pairs = c.n_pairs;
+    hipError_t e = psa::launch_sweep_pairs_f64((hipStream_t)stream, c.flags, a);
     if (e != hipSuccess) return hip_fail(e, "rk4_sweep_pairs launch");
     return PSA_OK;
 }
 
-int pairs_host(int device, int n_pairs, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
-               const double *dbeta, const double *gamma, const double *alpha, const double *a0, uint32_t flags,
-               double *a_end, double *wave_end, double *wave_max, int64_t *first_bad, double *elapsed_ms) {
-    int rc = validate_pairs(n_pairs, n_points, n_steps, z_max, save_every, dbeta, gamma, alpha, a0, flags, a_end, wave_end,
-                            wave_max, first_bad);
+int pairs_host(int device, const PairsCall &c, double *elapsed_ms) {
+    int rc = validate_pairs(c);
     if (rc != PSA_OK) return rc;
     if (elapsed_ms) *elapsed_ms = 0.0;
-    if (n_points == 0) return PSA_OK;
-    const int nw = 2 + 2 * n_pairs;
-    const size_t N = (size_t)n_points;
-    if ((flags & PSA_BCAST_ALPHA) && alpha[0] == 0.0) flags |= PSA_OPT_LOSSLESS;   // the reference's alpha == 0.0 branch
-    const double *d_dbeta, *d_gamma, *d_alpha, *d_a0;
-    double *d_aend, *d_wend, *d_wmax;
-    int64_t *d_bad;
+    if (c.n_points == 0) return PSA_OK;
+    const int nw = 2 + 2 * c.n_pairs;
+    const size_t N = (size_t)c.n_points;
+    PairsCall d = c;
+    d.flags |= lossless_bit(c.flags, c.alpha);
     auto layout = [&](Staging<double> &sg) {
-        d_dbeta = sg.input_soa(dbeta, N, n_pairs);             // [N][n_pairs] -> [n_pairs][N]
-        d_gamma = sg.input(gamma, (flags & PSA_BCAST_GAMMA) ? 1 : N);
-        d_alpha = sg.input(alpha, (flags & PSA_BCAST_ALPHA) ? 1 : N);
-        d_a0 = sg.input_soa(a0, (flags & PSA_BCAST_A0) ? 1 : N, 2 * nw);
-        d_aend = sg.output_soa(a_end, N, 2 * nw);
-        d_wend = sg.output_soa(wave_end, N, nw);
-        d_wmax = sg.output_soa(wave_max, N, nw);
-        d_bad = sg.output(first_bad, N);
+        d.dbeta = sg.input_soa(c.dbeta, N, c.n_pairs);             // [N][n_pairs] -> [n_pairs][N]
+        d.gamma = sg.input(c.gamma, (c.flags & PSA_BCAST_GAMMA) ? 1 : N);
+        d.alpha = sg.input(c.alpha, (c.flags & PSA_BCAST_ALPHA) ? 1 : N);
+        d.a0 = sg.input_soa(c.a0, (c.flags & PSA_BCAST_A0) ? 1 : N, 2 * nw);
+        d.a_end = sg.output_soa(c.a_end, N, 2 * nw);
+        d.wave_end = sg.output_soa(c.wave_end, N, nw);
+        d.wave_max = sg.output_soa(c.wave_max, N, nw);
+        d.first_bad = sg.output(c.first_bad, N);
     };
-    return host_call<double>(device, "the multi-channel RK4 sweep", elapsed_ms, layout, [&](hipStream_t st) {
-        return pairs_dev(st, n_pairs, n_points, n_steps, z_max, save_every, d_dbeta, d_gamma, d_alpha, d_a0, flags, d_aend,
-                         d_wend, d_wmax, d_bad);
-    });
+    return host_call<double>(device, "the multi-channel RK4 sweep", elapsed_ms, layout,
+                             [&](hipStream_t st) { return pairs_dev(st, d); });
 }
 
 // ---- fibre chains: S spans, one sweep launch + one epilogue (psa_chain.hip) each ------------------------------------
@@ -626,68 +641,63 @@ int64_t chain_workspace_bytes(int n_waves, int64_t n_points, size_t elem, bool w
 }
 
 // argument rules of psa_rk4_chain_*; *rows_total = sum over spans of n_steps[s] / save_every + 1
-int validate_chain(int n_waves, int64_t n_points, int n_segments, const int64_t *n_steps, const double *seg_len,
-                   int32_t save_every, const void *dbeta, const void *dbeta2, const void *gamma, const void *alpha,
-                   const void *a0, const void *a_end, const void *p_end, const void *p_max, const void *first_bad,
-                   uint32_t flags, const void *traj, const void *wave_end, const void *wave_max, size_t elem,
-                   int64_t *rows_total) {
-    if (n_segments < 1) return fail(PSA_E_NSTEPS, "n_segments must be >= 1, got %d", n_segments);
-    if (!n_steps || !seg_len) return fail(PSA_E_NULLPTR, "n_steps / seg_len is NULL");
-    int rc = validate_common(n_waves, n_points, n_steps[0], seg_len[0], save_every, dbeta, dbeta2, gamma, alpha, a0,
-                             a_end, p_end, p_max, first_bad, flags, traj != nullptr, elem);
+template <typename T>
+int validate_chain(const ChainCall<T> &c, int64_t *rows_total) {
+    if (c.n_segments < 1) return fail(PSA_E_NSTEPS, "n_segments must be >= 1, got %d", c.n_segments);
+    if (!c.n_steps || !c.seg_len) return fail(PSA_E_NULLPTR, "n_steps / seg_len is NULL");
+    SweepCall<T> first = c.s;   // the sweep's rules, on the first span's grid
+    first.n_steps = c.n_steps[0];
+    first.z_max = c.seg_len[0];
+    int rc = validate_common(first);
     if (rc != PSA_OK) return rc;
+    const int32_t save_every = c.s.save_every;
     int64_t rows = 0;
-    for (int s = 0; s < n_segments; ++s) {
-        if (n_steps[s] <= 0 || n_steps[s] > 2147483647LL)
-            return fail(PSA_E_NSTEPS, "n_steps[%d] must be in [1, 2^31), got %lld", s, (long long)n_steps[s]);
-        if (!(seg_len[s] > 0.0) || !std::isfinite(seg_len[s])) return fail(PSA_E_ZMAX, "seg_len[%d] must be positive", s);
+    for (int s = 0; s < c.n_segments; ++s) {
+        if (c.n_steps[s] <= 0 || c.n_steps[s] > 2147483647LL)
+            return fail(PSA_E_NSTEPS, "n_steps[%d] must be in [1, 2^31), got %lld", s, (long long)c.n_steps[s]);
+        if (!(c.seg_len[s] > 0.0) || !std::isfinite(c.seg_len[s])) return fail(PSA_E_ZMAX, "seg_len[%d] must be positive", s);
         // a_end is the last saved row: a tail after it would silently shorten the span
-        if (n_steps[s] % save_every != 0)
+        if (c.n_steps[s] % save_every != 0)
             return fail(PSA_E_SAVE_EVERY, "n_steps[%d] = %lld is not a multiple of save_every = %d", s,
-                        (long long)n_steps[s], (int)save_every);
-        rows += n_steps[s] / save_every + 1;
+                        (long long)c.n_steps[s], (int)save_every);
+        rows += c.n_steps[s] / save_every + 1;
     }
-    if ((wave_end != nullptr) != (wave_max != nullptr))
+    if ((c.s.wave_end != nullptr) != (c.s.wave_max != nullptr))
         return fail(PSA_E_NULLPTR, "p_wave_end and p_wave_max are given together or not at all");
-    if (wave_end && (rc = validate_waves(flags, traj != nullptr, n_points, wave_end, wave_max)) != PSA_OK) return rc;
-    if (traj && (long double)rows * 2 * n_waves * (long double)traj_ld_of(n_points, elem) > 4.0e18L)
+    if (c.s.wave_end && (rc = validate_waves(c.s)) != PSA_OK) return rc;
+    if (c.s.traj && (long double)rows * 2 * c.s.n_waves * (long double)traj_ld_of(c.s.n_points, sizeof(T)) > 4.0e18L)
         return fail(PSA_E_TOO_LARGE, "trajectory buffer too large");
     *rows_total = rows;
     return PSA_OK;
 }
 
-// lossless_or_null: host [S], span s gets PSA_OPT_LOSSLESS where it is non-zero (the host-buffer entry points: a
-// broadcast alpha of 0); `_dev` callers pass PSA_OPT_LOSSLESS for the whole chain instead.
 template <typename T>
-int chain_dev(void *stream, int n_waves, int64_t n_points, int n_segments, const int64_t *n_steps, const double *seg_len,
-              int32_t save_every, const T *d_dbeta, const T *d_dbeta2, const T *d_gamma, const T *d_alpha,
-              const T *d_a0_soa, const T *d_transfer_soa, uint32_t flags, T *d_a_end_soa, T *d_p_end, T *d_p_max,
-              int64_t *d_first_bad, T *d_traj_soa, T *d_wave_end, T *d_wave_max, void *d_workspace,
-              const unsigned char *lossless_or_null = nullptr) {
+int chain_dev(void *stream, const ChainCall<T> &c) {
     int64_t rows_total = 0;
-    int rc = validate_chain(n_waves, n_points, n_segments, n_steps, seg_len, save_every, d_dbeta, d_dbeta2, d_gamma,
-                            d_alpha, d_a0_soa, d_a_end_soa, d_p_end, d_p_max, d_first_bad, flags, d_traj_soa, d_wave_end,
-                            d_wave_max, sizeof(T), &rows_total);
+    int rc = validate_chain(c, &rows_total);
     if (rc != PSA_OK) return rc;
-    if (n_points == 0) return PSA_OK;
-    const int S = n_segments;
-    auto span_flags = [&](int s) {
-        uint32_t f = flags & ~PSA_BCAST_TRANSFER;
-        if (s > 0) f &= ~PSA_BCAST_A0;                         // the next span starts from a per-point state
-        if (lossless_or_null && lossless_or_null[s]) f |= PSA_OPT_LOSSLESS;
-        return f;
+    if (c.s.n_points == 0) return PSA_OK;
+    const int S = c.n_segments, n_waves = c.s.n_waves;
+    const uint32_t flags = c.s.flags;
+    SweepCall<T> sp = c.s;   // the span being run
+    auto set_span = [&](int s) {
+        sp.n_steps = c.n_steps[s];
+        sp.z_max = c.seg_len[s];
+        sp.flags = flags & ~PSA_BCAST_TRANSFER;
+        if (s > 0) sp.flags &= ~PSA_BCAST_A0;                  // the next span starts from a per-point state
+        if (c.lossless && c.lossless[s]) sp.flags |= PSA_OPT_LOSSLESS;
     };
-    if (S == 1)   // one span IS the sweep: same launch, same outputs, bit for bit
-        return sweep_dev<T>(stream, n_waves, n_points, n_steps[0], seg_len[0], save_every, d_dbeta, d_dbeta2, d_gamma,
-                            d_alpha, d_a0_soa, span_flags(0), d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa,
-                            d_wave_end, d_wave_max);
-    if (!d_workspace) return fail(PSA_E_NULLPTR, "a chain of more than one span needs d_workspace");
+    if (S == 1) {   // one span IS the sweep: same launch, same outputs, bit for bit
+        set_span(0);
+        return sweep_dev<T>(stream, sp);
+    }
+    if (!c.workspace) return fail(PSA_E_NULLPTR, "a chain of more than one span needs d_workspace");
 
-    const size_t N = (size_t)n_points;
+    const size_t N = (size_t)c.s.n_points;
     const int nc = 2 * n_waves;
-    const bool waves = d_wave_end != nullptr;
+    const bool waves = c.s.wave_end != nullptr;
     Carver ws;
-    ws.base = (char *)d_workspace;
+    ws.base = (char *)c.workspace;
     double *theta = ws.take<double>(N);
     double *theta2 = n_waves == 6 ? ws.take<double>(N) : nullptr;
     T *a0_next = ws.take<T>(nc * N);
@@ -698,22 +708,29 @@ int chain_dev(void *stream, int n_waves, int64_t n_points, int n_segments, const
     T *wend_s = waves ? ws.take<T>(n_waves * N) : nullptr;
     T *wmax_s = waves ? ws.take<T>(n_waves * N) : nullptr;
 
-    const size_t ld = (flags & PSA_OPT_TRAJ_LD) ? (size_t)traj_ld_of(n_points, sizeof(T)) : N;
+    const size_t ld = (flags & PSA_OPT_TRAJ_LD) ? (size_t)traj_ld_of(c.s.n_points, sizeof(T)) : N;
     const size_t g_step = (flags & PSA_BCAST_GAMMA) ? 1 : N, a_step = (flags & PSA_BCAST_ALPHA) ? 1 : N;
     const size_t t_step = (flags & PSA_BCAST_TRANSFER) ? (size_t)nc : nc * N;
-    const T *a0 = d_a0_soa;
     int64_t row = 0, step_off = 0;
     for (int s = 0; s < S; ++s) {
         const bool first = s == 0, last = s == S - 1;
-        T *traj_s = d_traj_soa ? d_traj_soa + (size_t)row * n_waves * ld * 2 : nullptr;
-        rc = sweep_dev<T>(stream, n_waves, n_points, n_steps[s], seg_len[s], save_every, d_dbeta + s * N,
-                          d_dbeta2 ? d_dbeta2 + s * N : nullptr, d_gamma + s * g_step, d_alpha + s * a_step, a0,
-                          span_flags(s), a_end_s, first ? d_p_end : p_end_s, first ? d_p_max : p_max_s,
-                          first ? d_first_bad : bad_s, traj_s, waves ? (first ? d_wave_end : wend_s) : nullptr,
-                          waves ? (first ? d_wave_max : wmax_s) : nullptr);
+        set_span(s);
+        sp.dbeta = c.s.dbeta + s * N;
+        sp.dbeta2 = c.s.dbeta2 ? c.s.dbeta2 + s * N : nullptr;
+        sp.gamma = c.s.gamma + s * g_step;
+        sp.alpha = c.s.alpha + s * a_step;
+        sp.a0 = first ? c.s.a0 : a0_next;
+        sp.a_end = a_end_s;
+        sp.p_end = first ? c.s.p_end : p_end_s;
+        sp.p_max = first ? c.s.p_max : p_max_s;
+        sp.first_bad = first ? c.s.first_bad : bad_s;
+        sp.traj = c.s.traj ? c.s.traj + (size_t)row * n_waves * ld * 2 : nullptr;
+        sp.wave_end = waves ? (first ? c.s.wave_end : wend_s) : nullptr;
+        sp.wave_max = waves ? (first ? c.s.wave_max : wmax_s) : nullptr;
+        rc = sweep_dev<T>(stream, sp);
         if (rc != PSA_OK) return rc;
         psa::ChainEpilogue<T> e;
-        e.n = n_points;
+        e.n = c.s.n_points;
         e.n_waves = n_waves;
         e.first = first;
         e.fold = !first;
@@ -723,87 +740,79 @@ int chain_dev(void *stream, int n_waves, int64_t n_points, int n_segments, const
         e.first_bad_s = (const long long *)bad_s;
         e.wave_end_s = wend_s;
         e.wave_max_s = wmax_s;
-        e.p_end = d_p_end;
-        e.p_max = d_p_max;
-        e.first_bad = (long long *)d_first_bad;
-        e.wave_end = d_wave_end;
-        e.wave_max = d_wave_max;
+        e.p_end = c.s.p_end;
+        e.p_max = c.s.p_max;
+        e.first_bad = (long long *)c.s.first_bad;
+        e.wave_end = c.s.wave_end;
+        e.wave_max = c.s.wave_max;
         e.step_offset = step_off;
         e.theta = theta;
         e.theta2 = theta2;
-        e.traj = traj_s;
+        e.traj = sp.traj;
         e.traj_ld = (long long)ld;
-        e.rows = n_steps[s] / save_every + 1;
-        e.a_end_out = last ? d_a_end_soa : nullptr;
-        e.transfer = (!last && d_transfer_soa) ? d_transfer_soa + s * t_step : nullptr;
+        e.rows = sp.n_steps / sp.save_every + 1;
+        e.a_end_out = last ? c.s.a_end : nullptr;
+        e.transfer = (!last && c.transfer) ? c.transfer + s * t_step : nullptr;
         e.transfer_stride = (flags & PSA_BCAST_TRANSFER) ? 0 : 1;
-        e.dbeta = d_dbeta + s * N;
-        e.dbeta2 = d_dbeta2 ? d_dbeta2 + s * N : nullptr;
-        e.seg_len = seg_len[s];
+        e.dbeta = sp.dbeta;
+        e.dbeta2 = sp.dbeta2;
+        e.seg_len = sp.z_max;
         e.a0_next = a0_next;
         hipError_t he = EpilogueLaunch<T>::fn((hipStream_t)stream, e);
         if (he != hipSuccess) return hip_fail(he, "chain epilogue launch");
-        a0 = a0_next;
         row += e.rows;
-        step_off += n_steps[s];
+        step_off += sp.n_steps;
     }
     return PSA_OK;
 }
 
 template <typename T>
-int chain_host(int device, int n_waves, int64_t n_points, int n_segments, const int64_t *n_steps, const double *seg_len,
-               int32_t save_every, const T *dbeta, const T *dbeta2, const T *gamma, const T *alpha, const T *a0,
-               const T *transfer, uint32_t flags, T *a_end, T *p_end, T *p_max, int64_t *first_bad, T *traj,
-               double *elapsed_ms, T *wave_end, T *wave_max) {
+int chain_host(int device, const ChainCall<T> &c, double *elapsed_ms) {
     int64_t rows_total = 0;
-    int rc = validate_chain(n_waves, n_points, n_segments, n_steps, seg_len, save_every, dbeta, dbeta2, gamma, alpha,
-                            a0, a_end, p_end, p_max, first_bad, flags, traj, wave_end, wave_max, sizeof(T), &rows_total);
+    int rc = validate_chain(c, &rows_total);
     if (rc != PSA_OK) return rc;
     if (elapsed_ms) *elapsed_ms = 0.0;
-    if (n_points == 0) return PSA_OK;
+    if (c.s.n_points == 0) return PSA_OK;
 
-    const int S = n_segments, nc = 2 * n_waves;
-    const size_t N = (size_t)n_points;
+    const int S = c.n_segments, n_waves = c.s.n_waves, nc = 2 * n_waves;
+    const size_t N = (size_t)c.s.n_points;
+    const uint32_t flags = c.s.flags;
     // the reference's alpha == 0.0 branch, span by span: a broadcast 0, or (S > 1, where a lossy span elsewhere makes the
     // alpha array per point) a span whose row is 0 everywhere.  One span keeps psa_rk4_sweep_*'s rule: bit-identical.
     std::vector<unsigned char> lossless((size_t)S, 0);
     for (int s = 0; s < S; ++s) {
-        const T *a = (flags & PSA_BCAST_ALPHA) ? alpha + s : alpha + (size_t)s * N;
-        const size_t n_a = (flags & PSA_BCAST_ALPHA) ? 1 : (S > 1 ? N : 0);
-        if (n_a == 0) continue;
-        bool zero = true;
-        for (size_t i = 0; i < n_a && zero; ++i) zero = a[i] == T(0);
+        bool zero = lossless_bit(flags, c.s.alpha + s) != 0;
+        if (!(flags & PSA_BCAST_ALPHA) && S > 1) {
+            const T *a = c.s.alpha + (size_t)s * N;
+            zero = true;
+            for (size_t i = 0; i < N && zero; ++i) zero = a[i] == T(0);
+        }
         lossless[(size_t)s] = zero;
     }
-    if (traj) flags |= PSA_OPT_TRAJ_LD;
-    const T *tr = S > 1 ? transfer : nullptr;
-    const T *d_dbeta, *d_dbeta2, *d_gamma, *d_alpha, *d_a0, *d_tr;
-    T *d_aend, *d_pend, *d_pmax, *d_wend, *d_wmax, *d_traj;
-    int64_t *d_bad;
-    void *d_ws;
+    ChainCall<T> d = c;
+    if (c.s.traj) d.s.flags |= PSA_OPT_TRAJ_LD;
+    d.lossless = lossless.data();
+    const T *tr = S > 1 ? c.transfer : nullptr;
     auto layout = [&](Staging<T> &sg) {
-        d_dbeta = sg.input(dbeta, S * N);
-        d_dbeta2 = sg.input(dbeta2, S * N);
-        d_gamma = sg.input(gamma, (flags & PSA_BCAST_GAMMA) ? (size_t)S : S * N);
-        d_alpha = sg.input(alpha, (flags & PSA_BCAST_ALPHA) ? (size_t)S : S * N);
-        d_a0 = sg.input_soa(a0, (flags & PSA_BCAST_A0) ? 1 : N, nc);
+        d.s.dbeta = sg.input(c.s.dbeta, S * N);
+        d.s.dbeta2 = sg.input(c.s.dbeta2, S * N);
+        d.s.gamma = sg.input(c.s.gamma, (flags & PSA_BCAST_GAMMA) ? (size_t)S : S * N);
+        d.s.alpha = sg.input(c.s.alpha, (flags & PSA_BCAST_ALPHA) ? (size_t)S : S * N);
+        d.s.a0 = sg.input_soa(c.s.a0, (flags & PSA_BCAST_A0) ? 1 : N, nc);
         // [S-1][n_waves][2] is already [S-1][2*n_waves]; [S-1][N][n_waves][2] -> [S-1][2*n_waves][N]
-        d_tr = (flags & PSA_BCAST_TRANSFER) ? sg.input(tr, (size_t)(S - 1) * nc) : sg.input_soa(tr, N, nc, S - 1);
-        d_ws = S > 1 ? sg.template scratch<char>((size_t)chain_workspace_bytes(n_waves, n_points, sizeof(T), wave_end != nullptr))
-                     : nullptr;
-        d_aend = sg.output_soa(a_end, N, nc);
-        d_pend = sg.output(p_end, N);
-        d_pmax = sg.output(p_max, N);
-        d_bad = sg.output(first_bad, N);
-        d_wend = sg.output_soa(wave_end, N, n_waves);
-        d_wmax = sg.output_soa(wave_max, N, n_waves);
-        d_traj = sg.trajectory(traj, N, (size_t)rows_total, nc);
+        d.transfer = (flags & PSA_BCAST_TRANSFER) ? sg.input(tr, (size_t)(S - 1) * nc) : sg.input_soa(tr, N, nc, S - 1);
+        d.workspace = S > 1 ? sg.template scratch<char>((size_t)chain_workspace_bytes(n_waves, c.s.n_points, sizeof(T),
+                                                                                      c.s.wave_end != nullptr))
+                            : nullptr;
+        d.s.a_end = sg.output_soa(c.s.a_end, N, nc);
+        d.s.p_end = sg.output(c.s.p_end, N);
+        d.s.p_max = sg.output(c.s.p_max, N);
+        d.s.first_bad = sg.output(c.s.first_bad, N);
+        d.s.wave_end = sg.output_soa(c.s.wave_end, N, n_waves);
+        d.s.wave_max = sg.output_soa(c.s.wave_max, N, n_waves);
+        d.s.traj = sg.trajectory(c.s.traj, N, (size_t)rows_total, nc);
     };
-    return host_call<T>(device, "the fibre chain", elapsed_ms, layout, [&](hipStream_t st) {
-        return chain_dev<T>(st, n_waves, n_points, S, n_steps, seg_len, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha,
-                            d_a0, d_tr, flags, d_aend, d_pend, d_pmax, d_bad, d_traj, d_wend, d_wmax, d_ws,
-                            lossless.data());
-    });
+    return host_call<T>(device, "the fibre chain", elapsed_ms, layout, [&](hipStream_t st) { return chain_dev<T>(st, d); });
 }
 
 template <typename T> struct GainLaunch;
@@ -926,112 +935,82 @@ int dbeta_pairs_dev(void *stream, const int32_t *orders, int n_orders, const dou
 // ---- the adaptive (RK45) sweep ----------------------------------------------------------------------------------
 // Argument rules of psa_rk45_sweep_*: those of the sweep (validate_common, with one step and a stride of one standing in
 // for the grid an adaptive run does not have), the flags it takes, the tolerances, the extra outputs and the row count.
-int validate_rk45(int n_waves, int64_t n_points, double z_max, double rtol, double atol, double h_max, double first_step,
-                  int64_t max_steps, int64_t n_out, const void *dbeta, const void *dbeta2, const void *gamma,
-                  const void *alpha, const void *a0, uint32_t flags, const void *a_end, const void *p_end,
-                  const void *p_max, const void *status, const void *z_end, const void *n_acc, const void *n_rej,
-                  const void *traj) {
-    int rc = validate_common(n_waves, n_points, 1, z_max, 1, dbeta, dbeta2, gamma, alpha, a0, a_end, p_end, p_max, status,
-                             0u, traj != nullptr, sizeof(double));
+int validate_rk45(const Rk45Call &c) {
+    // status stands in for first_bad_step: the sweep's rules only ask whether it is NULL
+    const SweepCall<double> as_sweep{c.n_waves, c.n_points, 1, c.z_max, 1, c.dbeta, c.dbeta2, c.gamma, c.alpha, c.a0, 0u,
+                                     c.a_end, c.p_end, c.p_max, reinterpret_cast<int64_t *>(c.status), c.traj};
+    int rc = validate_common(as_sweep);
     if (rc != PSA_OK) return rc;
     const uint32_t allowed = PSA_BCAST_GAMMA | PSA_BCAST_ALPHA | PSA_BCAST_A0 | PSA_OPT_LOSSLESS;
-    if (flags & ~allowed)
+    if (c.flags & ~allowed)
         return fail(PSA_E_FLAGS, "the adaptive sweep takes PSA_BCAST_GAMMA/ALPHA/A0 and PSA_OPT_LOSSLESS only, got 0x%x",
-                    flags);
-    if (!(rtol >= 100.0 * 2.220446049250313e-16) || !std::isfinite(rtol))
+                    c.flags);
+    if (!(c.rtol >= 100.0 * 2.220446049250313e-16) || !std::isfinite(c.rtol))
         return fail(PSA_E_TOL, "rtol must be finite and >= 100 * DBL_EPSILON");
-    if (!(atol > 0.0) || !std::isfinite(atol)) return fail(PSA_E_TOL, "atol must be positive and finite");
-    if (!(h_max > 0.0)) return fail(PSA_E_TOL, "h_max must be positive");
-    if (!(first_step >= 0.0) || !std::isfinite(first_step))
+    if (!(c.atol > 0.0) || !std::isfinite(c.atol)) return fail(PSA_E_TOL, "atol must be positive and finite");
+    if (!(c.h_max > 0.0)) return fail(PSA_E_TOL, "h_max must be positive");
+    if (!(c.first_step >= 0.0) || !std::isfinite(c.first_step))
         return fail(PSA_E_TOL, "first_step must be >= 0 and finite (0: select it)");
-    if (max_steps < 1) return fail(PSA_E_TOL, "max_steps must be >= 1, got %lld", (long long)max_steps);
-    if (n_out < 0) return fail(PSA_E_TOL, "n_out must be >= 0, got %lld", (long long)n_out);
-    if (n_points > 0 && (!z_end || !n_acc || !n_rej)) return fail(PSA_E_NULLPTR, "a required buffer pointer is NULL");
-    if (traj && ((long double)n_out + 1.0L) * (long double)n_points * (2.0L * n_waves) * sizeof(double) > 4.0e18L)
+    if (c.max_steps < 1) return fail(PSA_E_TOL, "max_steps must be >= 1, got %lld", (long long)c.max_steps);
+    if (c.n_out < 0) return fail(PSA_E_TOL, "n_out must be >= 0, got %lld", (long long)c.n_out);
+    if (c.n_points > 0 && (!c.z_end || !c.n_acc || !c.n_rej)) return fail(PSA_E_NULLPTR, "a required buffer pointer is NULL");
+    if (c.traj && ((long double)c.n_out + 1.0L) * (long double)c.n_points * (2.0L * c.n_waves) * sizeof(double) > 4.0e18L)
         return fail(PSA_E_TOO_LARGE, "dense-output buffer too large");
     return PSA_OK;
 }
 
-// traj_ld: the device rows' leading dimension (n_points for the _dev form, traj_ld_of for the host form's staging)
-int rk45_dev(void *stream, int n_waves, int64_t n_points, double z_max, double rtol, double atol, double h_max,
-             double first_step, int64_t max_steps, int64_t n_out, const double *d_dbeta, const double *d_dbeta2,
-             const double *d_gamma, const double *d_alpha, const double *d_a0_soa, uint32_t flags, double *d_a_end_soa,
-             double *d_p_end, double *d_p_max, int32_t *d_status, double *d_z_end, int64_t *d_n_acc, int64_t *d_n_rej,
-             double *d_traj, int64_t traj_ld) {
-    int rc = validate_rk45(n_waves, n_points, z_max, rtol, atol, h_max, first_step, max_steps, n_out, d_dbeta, d_dbeta2,
-                           d_gamma, d_alpha, d_a0_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_status, d_z_end, d_n_acc,
-                           d_n_rej, d_traj);
+int rk45_dev(void *stream, const Rk45Call &c) {
+    int rc = validate_rk45(c);
     if (rc != PSA_OK) return rc;
-    if (n_points == 0) return PSA_OK;
+    if (c.n_points == 0) return PSA_OK;
     psa::AdaptiveArgs<double> a;
-    a.dbeta = d_dbeta;
-    a.dbeta2 = d_dbeta2;
-    a.gamma = d_gamma;
-    a.alpha = d_alpha;
-    a.a0 = d_a0_soa;
-    a.a_end = d_a_end_soa;
-    a.p_end = d_p_end;
-    a.p_max = d_p_max;
-    a.status = d_status;
-    a.z_end = d_z_end;
-    a.n_accepted = (long long *)d_n_acc;
-    a.n_rejected = (long long *)d_n_rej;
-    a.traj = d_traj;
-    a.traj_ld = traj_ld;
-    a.n_points = n_points;
-    a.z_max = z_max;
-    a.rtol = rtol;
-    a.atol = atol;
-    a.h_max = h_max;
-    a.first_step = first_step;
-    a.max_steps = max_steps;
-    a.n_out = n_out;
-    a.gamma_stride = (flags & PSA_BCAST_GAMMA) ? 0 : 1;
-    a.alpha_stride = (flags & PSA_BCAST_ALPHA) ? 0 : 1;
-    a.a0_stride = (flags & PSA_BCAST_A0) ? 0 : 1;
-    a.a0_ld = (flags & PSA_BCAST_A0) ? 1 : n_points;
-    hipError_t e = psa::launch_rk45_sweep_f64((hipStream_t)stream, n_waves, flags, a);
+    fill_point_args(a, c);
+    a.dbeta2 = c.dbeta2;
+    a.p_end = c.p_end;
+    a.p_max = c.p_max;
+    a.status = c.status;
+    a.z_end = c.z_end;
+    a.n_accepted = (long long *)c.n_acc;
+    a.n_rejected = (long long *)c.n_rej;
+    a.traj = c.traj;
+    a.traj_ld = c.traj_ld;
+    a.rtol = c.rtol;
+    a.atol = c.atol;
+    a.h_max = c.h_max;
+    a.first_step = c.first_step;
+    a.max_steps = c.max_steps;
+    a.n_out = c.n_out;
+    hipError_t e = psa::launch_rk45_sweep_f64((hipStream_t)stream, c.n_waves, c.flags, a);
     if (e != hipSuccess) return hip_fail(e, "rk45_sweep launch");
     return PSA_OK;
 }
 
-int rk45_host(int device, int n_waves, int64_t n_points, double z_max, double rtol, double atol, double h_max,
-              double first_step, int64_t max_steps, int64_t n_out, const double *dbeta, const double *dbeta2,
-              const double *gamma, const double *alpha, const double *a0, uint32_t flags, double *a_end, double *p_end,
-              double *p_max, int32_t *status, double *z_end, int64_t *n_acc, int64_t *n_rej, double *traj,
-              double *elapsed_ms) {
-    int rc = validate_rk45(n_waves, n_points, z_max, rtol, atol, h_max, first_step, max_steps, n_out, dbeta, dbeta2,
-                           gamma, alpha, a0, flags, a_end, p_end, p_max, status, z_end, n_acc, n_rej, traj);
+int rk45_host(int device, const Rk45Call &c, double *elapsed_ms) {
+    int rc = validate_rk45(c);
     if (rc != PSA_OK) return rc;
     if (elapsed_ms) *elapsed_ms = 0.0;
-    if (n_points == 0) return PSA_OK;
-    const int nc = 2 * n_waves;
-    const size_t N = (size_t)n_points;
-    if ((flags & PSA_BCAST_ALPHA) && alpha[0] == 0.0) flags |= PSA_OPT_LOSSLESS;   // the reference's alpha == 0.0 branch
-    const double *d_dbeta, *d_dbeta2, *d_gamma, *d_alpha, *d_a0;
-    double *d_aend, *d_pend, *d_pmax, *d_zend, *d_traj;
-    int32_t *d_status;
-    int64_t *d_nacc, *d_nrej;
+    if (c.n_points == 0) return PSA_OK;
+    const int nc = 2 * c.n_waves;
+    const size_t N = (size_t)c.n_points;
+    Rk45Call d = c;
+    d.flags |= lossless_bit(c.flags, c.alpha);
+    d.traj_ld = traj_ld_of(c.n_points, sizeof(double));
     auto layout = [&](Staging<double> &sg) {
-        d_dbeta = sg.input(dbeta, N);
-        d_dbeta2 = sg.input(dbeta2, N);
-        d_gamma = sg.input(gamma, (flags & PSA_BCAST_GAMMA) ? 1 : N);
-        d_alpha = sg.input(alpha, (flags & PSA_BCAST_ALPHA) ? 1 : N);
-        d_a0 = sg.input_soa(a0, (flags & PSA_BCAST_A0) ? 1 : N, nc);
-        d_aend = sg.output_soa(a_end, N, nc);
-        d_pend = sg.output(p_end, N);
-        d_pmax = sg.output(p_max, N);
-        d_status = sg.output(status, N);
-        d_zend = sg.output(z_end, N);
-        d_nacc = sg.output(n_acc, N);
-        d_nrej = sg.output(n_rej, N);
-        d_traj = sg.trajectory(traj, N, (size_t)n_out + 1, nc);
+        d.dbeta = sg.input(c.dbeta, N);
+        d.dbeta2 = sg.input(c.dbeta2, N);
+        d.gamma = sg.input(c.gamma, (c.flags & PSA_BCAST_GAMMA) ? 1 : N);
+        d.alpha = sg.input(c.alpha, (c.flags & PSA_BCAST_ALPHA) ? 1 : N);
+        d.a0 = sg.input_soa(c.a0, (c.flags & PSA_BCAST_A0) ? 1 : N, nc);
+        d.a_end = sg.output_soa(c.a_end, N, nc);
+        d.p_end = sg.output(c.p_end, N);
+        d.p_max = sg.output(c.p_max, N);
+        d.status = sg.output(c.status, N);
+        d.z_end = sg.output(c.z_end, N);
+        d.n_acc = sg.output(c.n_acc, N);
+        d.n_rej = sg.output(c.n_rej, N);
+        d.traj = sg.trajectory(c.traj, N, (size_t)c.n_out + 1, nc);
     };
-    return host_call<double>(device, "the RK45 sweep", elapsed_ms, layout, [&](hipStream_t st) {
-        return rk45_dev(st, n_waves, n_points, z_max, rtol, atol, h_max, first_step, max_steps, n_out, d_dbeta, d_dbeta2,
-                        d_gamma, d_alpha, d_a0, flags, d_aend, d_pend, d_pmax, d_status, d_zend, d_nacc, d_nrej, d_traj,
-                        traj_ld_of(n_points, sizeof(double)));
-    });
+    return host_call<double>(device, "the RK45 sweep", elapsed_ms, layout, [&](hipStream_t st) { return rk45_dev(st, d); });
 }
 
 }  // namespace
@@ -1073,62 +1052,62 @@ int psa_rk4_sweep_f64(int device, int n_waves, int64_t n_points, int64_t n_steps
                       const double *dbeta, const double *dbeta2, const double *gamma, const double *alpha,
                       const double *a0, uint32_t flags, double *a_end, double *p_end, double *p_max,
                       int64_t *first_bad, double *traj, double *elapsed_ms) {
-    return sweep_host<double>(device, n_waves, n_points, n_steps, z_max, save_every, dbeta, dbeta2, gamma, alpha, a0,
-                              flags, a_end, p_end, p_max, first_bad, traj, elapsed_ms);
+    return sweep_host<double>(device, {n_waves, n_points, n_steps, z_max, save_every, dbeta, dbeta2, gamma, alpha, a0, flags,
+                                       a_end, p_end, p_max, first_bad, traj}, elapsed_ms);
 }
 int psa_rk4_sweep_f32(int device, int n_waves, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
                       const float *dbeta, const float *dbeta2, const float *gamma, const float *alpha, const float *a0,
                       uint32_t flags, float *a_end, float *p_end, float *p_max, int64_t *first_bad, float *traj,
                       double *elapsed_ms) {
-    return sweep_host<float>(device, n_waves, n_points, n_steps, z_max, save_every, dbeta, dbeta2, gamma, alpha, a0,
-                             flags, a_end, p_end, p_max, first_bad, traj, elapsed_ms);
+    return sweep_host<float>(device, {n_waves, n_points, n_steps, z_max, save_every, dbeta, dbeta2, gamma, alpha, a0, flags,
+                                      a_end, p_end, p_max, first_bad, traj}, elapsed_ms);
 }
 int psa_rk4_sweep_f64_dev(void *stream, int n_waves, int64_t n_points, int64_t n_steps, double z_max,
                           int32_t save_every, const double *d_dbeta, const double *d_dbeta2, const double *d_gamma,
                           const double *d_alpha, const double *d_a0_soa, uint32_t flags, double *d_a_end_soa,
                           double *d_p_end, double *d_p_max, int64_t *d_first_bad, double *d_traj_soa) {
-    return sweep_dev<double>(stream, n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma,
-                             d_alpha, d_a0_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa);
+    return sweep_dev<double>(stream, {n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha,
+                                      d_a0_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa});
 }
 int psa_rk4_sweep_f32_dev(void *stream, int n_waves, int64_t n_points, int64_t n_steps, double z_max,
                           int32_t save_every, const float *d_dbeta, const float *d_dbeta2, const float *d_gamma,
                           const float *d_alpha, const float *d_a0_soa, uint32_t flags, float *d_a_end_soa,
                           float *d_p_end, float *d_p_max, int64_t *d_first_bad, float *d_traj_soa) {
-    return sweep_dev<float>(stream, n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha,
-                            d_a0_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa);
+    return sweep_dev<float>(stream, {n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha,
+                                     d_a0_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa});
 }
 
 int psa_rk4_sweep_waves_f64(int device, int n_waves, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
                             const double *dbeta, const double *dbeta2, const double *gamma, const double *alpha,
                             const double *a0, uint32_t flags, double *a_end, double *p_end, double *p_max,
                             int64_t *first_bad, double *traj, double *elapsed_ms, double *p_wave_end, double *p_wave_max) {
-    return sweep_host<double>(device, n_waves, n_points, n_steps, z_max, save_every, dbeta, dbeta2, gamma, alpha, a0,
-                              flags, a_end, p_end, p_max, first_bad, traj, elapsed_ms, true, p_wave_end, p_wave_max);
+    return sweep_host<double>(device, {n_waves, n_points, n_steps, z_max, save_every, dbeta, dbeta2, gamma, alpha, a0, flags,
+                                       a_end, p_end, p_max, first_bad, traj, p_wave_end, p_wave_max, true}, elapsed_ms);
 }
 int psa_rk4_sweep_waves_f32(int device, int n_waves, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
                             const float *dbeta, const float *dbeta2, const float *gamma, const float *alpha,
                             const float *a0, uint32_t flags, float *a_end, float *p_end, float *p_max,
                             int64_t *first_bad, float *traj, double *elapsed_ms, float *p_wave_end, float *p_wave_max) {
-    return sweep_host<float>(device, n_waves, n_points, n_steps, z_max, save_every, dbeta, dbeta2, gamma, alpha, a0,
-                             flags, a_end, p_end, p_max, first_bad, traj, elapsed_ms, true, p_wave_end, p_wave_max);
+    return sweep_host<float>(device, {n_waves, n_points, n_steps, z_max, save_every, dbeta, dbeta2, gamma, alpha, a0, flags,
+                                      a_end, p_end, p_max, first_bad, traj, p_wave_end, p_wave_max, true}, elapsed_ms);
 }
 int psa_rk4_sweep_waves_f64_dev(void *stream, int n_waves, int64_t n_points, int64_t n_steps, double z_max,
                                 int32_t save_every, const double *d_dbeta, const double *d_dbeta2, const double *d_gamma,
                                 const double *d_alpha, const double *d_a0_soa, uint32_t flags, double *d_a_end_soa,
                                 double *d_p_end, double *d_p_max, int64_t *d_first_bad, double *d_traj_soa,
                                 double *d_p_wave_end_soa, double *d_p_wave_max_soa) {
-    return sweep_waves_dev<double>(stream, n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma,
-                                   d_alpha, d_a0_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa,
-                                   d_p_wave_end_soa, d_p_wave_max_soa);
+    return sweep_dev<double>(stream, {n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha,
+                                      d_a0_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa, d_p_wave_end_soa,
+                                      d_p_wave_max_soa, true});
 }
 int psa_rk4_sweep_waves_f32_dev(void *stream, int n_waves, int64_t n_points, int64_t n_steps, double z_max,
                                 int32_t save_every, const float *d_dbeta, const float *d_dbeta2, const float *d_gamma,
                                 const float *d_alpha, const float *d_a0_soa, uint32_t flags, float *d_a_end_soa,
                                 float *d_p_end, float *d_p_max, int64_t *d_first_bad, float *d_traj_soa,
                                 float *d_p_wave_end_soa, float *d_p_wave_max_soa) {
-    return sweep_waves_dev<float>(stream, n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma,
-                                  d_alpha, d_a0_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa,
-                                  d_p_wave_end_soa, d_p_wave_max_soa);
+    return sweep_dev<float>(stream, {n_waves, n_points, n_steps, z_max, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha,
+                                     d_a0_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa, d_p_wave_end_soa,
+                                     d_p_wave_max_soa, true});
 }
 
 int psa_yaman_rhs_f64(int device, int64_t n, const double *z, const double *a, const double *gamma,
@@ -1249,13 +1228,14 @@ int psa_dbeta_pairs_f64(int device, const int32_t *orders, int n_orders, const d
     });
 }
 
+// the chain's record: the spans' shared part has no grid of its own (n_steps 0, z_max 0: set span by span)
 int psa_rk4_chain_f64(int device, int n_waves, int64_t n_points, int n_segments, const int64_t *n_steps,
                       const double *seg_len, int32_t save_every, const double *dbeta, const double *dbeta2, const double *gamma,
                       const double *alpha, const double *a0, const double *transfer, uint32_t flags, double *a_end, double *p_end,
                       double *p_max, int64_t *first_bad, double *traj, double *elapsed_ms, double *p_wave_end, double *p_wave_max) {
-    return chain_host<double>(device, n_waves, n_points, n_segments, n_steps, seg_len, save_every, dbeta, dbeta2, gamma,
-                           alpha, a0, transfer, flags, a_end, p_end, p_max, first_bad, traj, elapsed_ms, p_wave_end,
-                           p_wave_max);
+    return chain_host<double>(device, {{n_waves, n_points, 0, 0.0, save_every, dbeta, dbeta2, gamma, alpha, a0, flags, a_end,
+                                       p_end, p_max, first_bad, traj, p_wave_end, p_wave_max}, n_segments, n_steps, seg_len,
+                                       transfer, nullptr}, elapsed_ms);
 }
 
 int psa_rk4_chain_f64_dev(void *stream, int n_waves, int64_t n_points, int n_segments, const int64_t *n_steps,
@@ -1263,18 +1243,18 @@ int psa_rk4_chain_f64_dev(void *stream, int n_waves, int64_t n_points, int n_seg
                           const double *d_gamma, const double *d_alpha, const double *d_a0_soa, const double *d_transfer_soa,
                           uint32_t flags, double *d_a_end_soa, double *d_p_end, double *d_p_max, int64_t *d_first_bad,
                           double *d_traj_soa, double *d_p_wave_end_soa, double *d_p_wave_max_soa, void *d_workspace) {
-    return chain_dev<double>(stream, n_waves, n_points, n_segments, n_steps, seg_len, save_every, d_dbeta, d_dbeta2, d_gamma,
-                          d_alpha, d_a0_soa, d_transfer_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa,
-                          d_p_wave_end_soa, d_p_wave_max_soa, d_workspace);
+    return chain_dev<double>(stream, {{n_waves, n_points, 0, 0.0, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha, d_a0_soa,
+                                      flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa, d_p_wave_end_soa,
+                                      d_p_wave_max_soa}, n_segments, n_steps, seg_len, d_transfer_soa, d_workspace});
 }
 
 int psa_rk4_chain_f32(int device, int n_waves, int64_t n_points, int n_segments, const int64_t *n_steps,
                       const double *seg_len, int32_t save_every, const float *dbeta, const float *dbeta2, const float *gamma,
                       const float *alpha, const float *a0, const float *transfer, uint32_t flags, float *a_end, float *p_end,
                       float *p_max, int64_t *first_bad, float *traj, double *elapsed_ms, float *p_wave_end, float *p_wave_max) {
-    return chain_host<float>(device, n_waves, n_points, n_segments, n_steps, seg_len, save_every, dbeta, dbeta2, gamma,
-                           alpha, a0, transfer, flags, a_end, p_end, p_max, first_bad, traj, elapsed_ms, p_wave_end,
-                           p_wave_max);
+    return chain_host<float>(device, {{n_waves, n_points, 0, 0.0, save_every, dbeta, dbeta2, gamma, alpha, a0, flags, a_end,
+                                      p_end, p_max, first_bad, traj, p_wave_end, p_wave_max}, n_segments, n_steps, seg_len,
+                                      transfer, nullptr}, elapsed_ms);
 }
 
 int psa_rk4_chain_f32_dev(void *stream, int n_waves, int64_t n_points, int n_segments, const int64_t *n_steps,
@@ -1282,9 +1262,9 @@ int psa_rk4_chain_f32_dev(void *stream, int n_waves, int64_t n_points, int n_seg
                           const float *d_gamma, const float *d_alpha, const float *d_a0_soa, const float *d_transfer_soa,
                           uint32_t flags, float *d_a_end_soa, float *d_p_end, float *d_p_max, int64_t *d_first_bad,
                           float *d_traj_soa, float *d_p_wave_end_soa, float *d_p_wave_max_soa, void *d_workspace) {
-    return chain_dev<float>(stream, n_waves, n_points, n_segments, n_steps, seg_len, save_every, d_dbeta, d_dbeta2, d_gamma,
-                          d_alpha, d_a0_soa, d_transfer_soa, flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa,
-                          d_p_wave_end_soa, d_p_wave_max_soa, d_workspace);
+    return chain_dev<float>(stream, {{n_waves, n_points, 0, 0.0, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha, d_a0_soa,
+                                     flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa, d_p_wave_end_soa,
+                                     d_p_wave_max_soa}, n_segments, n_steps, seg_len, d_transfer_soa, d_workspace});
 }
 
 int64_t psa_rk4_chain_workspace_bytes(int n_waves, int64_t n_points, int32_t elem_size, int wave_summary) {
@@ -1296,9 +1276,9 @@ int psa_rk45_sweep_f64(int device, int n_waves, int64_t n_points, double z_max, 
                        const double *gamma, const double *alpha, const double *a0_re_im, uint32_t flags,
                        double *a_end_re_im, double *p_sig_end, double *p_sig_max, int32_t *status, double *z_end,
                        int64_t *n_accepted, int64_t *n_rejected, double *traj_or_null, double *elapsed_ms_or_null) {
-    return rk45_host(device, n_waves, n_points, z_max, rtol, atol, h_max, first_step, max_steps, n_out, dbeta, dbeta2,
-                     gamma, alpha, a0_re_im, flags, a_end_re_im, p_sig_end, p_sig_max, status, z_end, n_accepted,
-                     n_rejected, traj_or_null, elapsed_ms_or_null);
+    return rk45_host(device, {n_waves, n_points, z_max, rtol, atol, h_max, first_step, max_steps, n_out, dbeta, dbeta2, gamma,
+                              alpha, a0_re_im, flags, a_end_re_im, p_sig_end, p_sig_max, status, z_end, n_accepted, n_rejected,
+                              traj_or_null, n_points}, elapsed_ms_or_null);
 }
 int psa_rk45_sweep_f64_dev(void *stream, int n_waves, int64_t n_points, double z_max, double rtol, double atol,
                            double h_max, double first_step, int64_t max_steps, int64_t n_out, const double *d_dbeta,
@@ -1306,24 +1286,24 @@ int psa_rk45_sweep_f64_dev(void *stream, int n_waves, int64_t n_points, double z
                            uint32_t flags, double *d_a_end_soa, double *d_p_sig_end, double *d_p_sig_max,
                            int32_t *d_status, double *d_z_end, int64_t *d_n_accepted, int64_t *d_n_rejected,
                            double *d_traj_soa) {
-    return rk45_dev(stream, n_waves, n_points, z_max, rtol, atol, h_max, first_step, max_steps, n_out, d_dbeta, d_dbeta2,
-                    d_gamma, d_alpha, d_a0_soa, flags, d_a_end_soa, d_p_sig_end, d_p_sig_max, d_status, d_z_end,
-                    d_n_accepted, d_n_rejected, d_traj_soa, n_points);
+    return rk45_dev(stream, {n_waves, n_points, z_max, rtol, atol, h_max, first_step, max_steps, n_out, d_dbeta, d_dbeta2,
+                             d_gamma, d_alpha, d_a0_soa, flags, d_a_end_soa, d_p_sig_end, d_p_sig_max, d_status, d_z_end,
+                             d_n_accepted, d_n_rejected, d_traj_soa, n_points});
 }
 
 int psa_rk4_sweep_pairs_f64(int device, int n_pairs, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
                             const double *dbeta, const double *gamma, const double *alpha, const double *a0_re_im,
                             uint32_t flags, double *a_end_re_im, double *p_wave_end, double *p_wave_max,
                             int64_t *first_bad_step, double *elapsed_ms_or_null) {
-    return pairs_host(device, n_pairs, n_points, n_steps, z_max, save_every, dbeta, gamma, alpha, a0_re_im, flags,
-                      a_end_re_im, p_wave_end, p_wave_max, first_bad_step, elapsed_ms_or_null);
+    return pairs_host(device, {n_pairs, n_points, n_steps, z_max, save_every, dbeta, gamma, alpha, a0_re_im, flags, a_end_re_im,
+                               p_wave_end, p_wave_max, first_bad_step}, elapsed_ms_or_null);
 }
 int psa_rk4_sweep_pairs_f64_dev(void *stream, int n_pairs, int64_t n_points, int64_t n_steps, double z_max,
                                 int32_t save_every, const double *d_dbeta_soa, const double *d_gamma, const double *d_alpha,
                                 const double *d_a0_soa, uint32_t flags, double *d_a_end_soa, double *d_p_wave_end_soa,
                                 double *d_p_wave_max_soa, int64_t *d_first_bad_step) {
-    return pairs_dev(stream, n_pairs, n_points, n_steps, z_max, save_every, d_dbeta_soa, d_gamma, d_alpha, d_a0_soa, flags,
-                     d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step);
+    return pairs_dev(stream, {n_pairs, n_points, n_steps, z_max, save_every, d_dbeta_soa, d_gamma, d_alpha, d_a0_soa, flags,
+                              d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step});
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@ rows, first non-finite step) written back.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
@@ -81,14 +82,10 @@ class SweepResult:
         return _native.gain_summary_host(metric, self.first_bad_step, float(p0_sig), gain_db=(u == "db"), device=device)
 
 
-def rk4_sweep(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps: Optional[int] = None,
-              save_every: int = 10, check_nan: bool = True, gamma, alpha, a0, dbeta2=None, dtype=np.float64,
-              device: int = 0, exact_step: Optional[bool] = None, want_traj: bool = False,
-              devices: Optional[Sequence[int]] = None, wave_summary: bool = False) -> SweepResult:
-    """Propagate N points.  ``dz`` gives n = int(round(z_max/dz)) as integrators.py:194; or pass ``n_steps``.
-    ``devices=[0, 1, ...]`` splits the points over several GPUs of this process (one thread per device).
-    ``wave_summary=True`` also fills p_wave_end / p_wave_max: the end and maximum power of every wave."""
-    if z_max <= 0.0:
+def _fixed_grid(z_max, dz, n_steps, save_every):
+    """The fixed-step grid arguments -> (n_steps, save_every): z_max positive and finite, ``dz`` giving
+    n = int(round(z_max/dz)) as integrators.py:194 unless ``n_steps`` is passed, at least one step, save_every positive."""
+    if not 0.0 < z_max < math.inf:   # NaN included; plain comparisons: a NumPy call here shows in a 50 us sweep
         raise ValueError("z_max must be positive")
     if n_steps is None:
         if dz is None or dz <= 0.0:
@@ -98,19 +95,36 @@ def rk4_sweep(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps: Optio
         raise ValueError("save_every must be a positive integer")
     if n_steps < 1:
         raise ValueError("z_max / dz rounds to zero steps")
-    kw = dict(n_steps=int(n_steps), z_max=float(z_max), save_every=int(save_every), gamma=gamma, alpha=alpha, a0=a0,
-              dbeta2=dbeta2, check_nan=check_nan, exact_step=exact_step, want_traj=want_traj, dtype=dtype)
-    if wave_summary:
-        kw["wave_summary"] = True
+    return int(n_steps), int(save_every)
+
+
+def _run(host_fn, axes, n_points: int, kw: dict, device: int, devices) -> dict:
+    """host_fn(**kw) on ``device`` (on devices[0] where a list names one GPU), or the points split over several ``devices``
+    of this process (one thread per device)."""
     devs = None if devices is None else [int(d) for d in devices]
     if devs is not None and len(devs) == 0:
         raise ValueError("devices must name at least one GPU")
+    if devs is not None and len(devs) > 1 and n_points > 1:
+        return over_devices(host_fn, devs, n_points, axes, kw)
+    return host_fn(device=(devs[0] if devs else device), **kw)
+
+
+def rk4_sweep(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps: Optional[int] = None,
+              save_every: int = 10, check_nan: bool = True, gamma, alpha, a0, dbeta2=None, dtype=np.float64,
+              device: int = 0, exact_step: Optional[bool] = None, want_traj: bool = False,
+              devices: Optional[Sequence[int]] = None, wave_summary: bool = False) -> SweepResult:
+    """Propagate N points.  ``dz`` gives n = int(round(z_max/dz)) as integrators.py:194; or pass ``n_steps``.
+    ``devices=[0, 1, ...]`` splits the points over several GPUs of this process (one thread per device).
+    ``wave_summary=True`` also fills p_wave_end / p_wave_max: the end and maximum power of every wave."""
+    n_steps, save_every = _fixed_grid(z_max, dz, n_steps, save_every)
     db = np.atleast_1d(np.asarray(dbeta))
-    if devs is not None and len(devs) > 1 and db.ndim == 1 and db.shape[0] > 1:
-        r = over_devices(_native.sweep_host, devs, db.shape[0], SWEEP_AXES, dict(kw, dbeta=db))
-    else:
-        r = _native.sweep_host(dbeta, device=(devs[0] if devs else device), **kw)
-    return SweepResult(r["a_end"], r["p_end"], r["p_max"], r["first_bad_step"], int(n_steps), int(save_every),
+    kw = dict(dbeta=db, n_steps=n_steps, z_max=float(z_max), save_every=save_every, gamma=gamma, alpha=alpha, a0=a0,
+              dbeta2=dbeta2, check_nan=check_nan, exact_step=exact_step, want_traj=want_traj, dtype=dtype)
+    if wave_summary:
+        kw["wave_summary"] = True
+    # a dbeta that is not 1-D goes to sweep_host as it is, which rejects it
+    r = _run(_native.sweep_host, SWEEP_AXES, db.shape[0] if db.ndim == 1 else 1, kw, device, devices)
+    return SweepResult(r["a_end"], r["p_end"], r["p_max"], r["first_bad_step"], n_steps, save_every,
                        r["elapsed_ms"], r.get("traj"), r.get("p_wave_end"), r.get("p_wave_max"))
 
 
@@ -180,16 +194,7 @@ def rk4_sweep_pairs(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps:
     dbeta (N, K): the mismatch of every pair; gamma / alpha a scalar or (N,); a0 (NW,) or (N, NW) complex, NW = 2 + 2K.
     ``dz`` gives n = int(round(z_max/dz)) as integrators.py:194; or pass ``n_steps``.  ``devices=[0, 1, ...]`` splits the
     points over several GPUs of this process.  Fixed-step float64 only: no trajectory, float32, chain or adaptive form."""
-    if not (np.isfinite(z_max) and z_max > 0.0):
-        raise ValueError("z_max must be positive")
-    if n_steps is None:
-        if dz is None or dz <= 0.0:
-            raise ValueError("dz must be positive")
-        n_steps = n_steps_of(z_max, dz)
-    if save_every <= 0:
-        raise ValueError("save_every must be a positive integer")
-    if n_steps < 1:
-        raise ValueError("z_max / dz rounds to zero steps")
+    n_steps, save_every = _fixed_grid(z_max, dz, n_steps, save_every)
     db = np.asarray(dbeta, dtype=float)
     if db.ndim != 2 or not 1 <= db.shape[1] <= _native.MAX_PAIRS:
         raise ValueError(f"dbeta must have shape (N, K) with 1 <= K <= {_native.MAX_PAIRS}, got {db.shape}")
@@ -197,17 +202,11 @@ def rk4_sweep_pairs(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps:
     a0 = np.asarray(a0, dtype=np.complex128)
     if a0.shape not in ((nw,), (1, nw), (db.shape[0], nw)):
         raise ValueError(f"a0 must have shape ({nw},) or ({db.shape[0]}, {nw}) for {db.shape[1]} pairs, got {a0.shape}")
-    kw = dict(n_steps=int(n_steps), z_max=float(z_max), save_every=int(save_every), gamma=gamma, alpha=alpha, a0=a0,
+    kw = dict(dbeta=db, n_steps=n_steps, z_max=float(z_max), save_every=save_every, gamma=gamma, alpha=alpha, a0=a0,
               check_nan=check_nan, exact_step=exact_step)
-    devs = None if devices is None else [int(d) for d in devices]
-    if devs is not None and len(devs) == 0:
-        raise ValueError("devices must name at least one GPU")
-    if devs is not None and len(devs) > 1 and db.shape[0] > 1:
-        r = over_devices(_native.sweep_pairs_host, devs, db.shape[0], PAIRS_AXES, dict(kw, dbeta=db))
-    else:
-        r = _native.sweep_pairs_host(db, device=(devs[0] if devs else device), **kw)
+    r = _run(_native.sweep_pairs_host, PAIRS_AXES, db.shape[0], kw, device, devices)
     p_in = np.abs(np.atleast_2d(a0)) ** 2
-    return PairsResult(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"], int(n_steps), int(save_every),
+    return PairsResult(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"], n_steps, save_every,
                        r["elapsed_ms"], p_in)
 
 
@@ -317,13 +316,7 @@ def rk4_chain(spans: Sequence[FibreSpan], *, a0, transfers=None, save_every: int
     kw = dict(dbeta=dbeta, n_steps=steps, seg_len=lens, save_every=save_every, gamma=gamma, alpha=alpha, a0=a0,
               transfers=tr, dbeta2=dbeta2, check_nan=check_nan, exact_step=exact_step, want_traj=want_traj,
               dtype=dtype, wave_summary=wave_summary)
-    devs = None if devices is None else [int(d) for d in devices]
-    if devs is not None and len(devs) == 0:
-        raise ValueError("devices must name at least one GPU")
-    if devs is not None and len(devs) > 1 and N > 1:
-        r = over_devices(_native.chain_host, devs, N, CHAIN_AXES, kw)
-    else:
-        r = _native.chain_host(device=(devs[0] if devs else device), **kw)
+    r = _run(_native.chain_host, CHAIN_AXES, N, kw, device, devices)
     rows = steps // save_every + 1
     row_off = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
     step_off = np.concatenate([[0], np.cumsum(steps)]).astype(np.int64)

@@ -98,6 +98,11 @@ def test_python_wrapper_shape_checks():
         nat.sweep_host(np.zeros(3), n_steps=1, z_max=1.0, save_every=1, gamma=1.0, alpha=0.0, a0=np.ones(6, complex))
     with pytest.raises(ValueError):
         nat.sweep_host(np.zeros(3), n_steps=1, z_max=1.0, save_every=1, gamma=1.0, alpha=0.0, a0=a0, dtype=np.float16)
+    # a NaN z_max stops at the Python check of rk4_sweep as it does for its siblings, whichever way the grid is given
+    from psa_amd import sweep
+    for grid in (dict(n_steps=10), dict(dz=0.1)):
+        with pytest.raises(ValueError, match="z_max must be positive"):
+            sweep.rk4_sweep(np.zeros(3), z_max=float("nan"), gamma=1.0, alpha=0.0, a0=a0, **grid)
 
 
 @pytest.mark.skipif(nat.device_count() > 0, reason="CPU box only")

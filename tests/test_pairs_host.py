@@ -147,6 +147,31 @@ def test_python_wrapper_shape_rules():
         sweep.rk4_sweep_pairs(np.zeros((3, 2)), z_max=1.0, dz=0.1, gamma=1.0, alpha=0.0, a0=np.ones(4, complex))
 
 
+# the four host wrappers on N = 3 points and 4 waves (one pair; a chain of two spans): valid but for what a case replaces
+_WRAPPERS = {"sweep": (nat.sweep_host, dict(dbeta=np.zeros(3), n_steps=1, z_max=1.0, save_every=1)),
+             "pairs": (nat.sweep_pairs_host, dict(dbeta=np.zeros((3, 1)), n_steps=1, z_max=1.0, save_every=1)),
+             "chain": (nat.chain_host, dict(dbeta=np.zeros((2, 3)), n_steps=[1, 1], seg_len=[1.0, 1.0], save_every=1)),
+             "rk45": (nat.rk45_sweep_host, dict(dbeta=np.zeros(3), z_max=1.0, rtol=1e-8, atol=1e-12))}
+_WRONG = {"gamma_2d": dict(gamma=np.ones((3, 2))), "alpha_wrong_length": dict(alpha=np.ones(4)),
+          "a0_wrong_width": dict(a0=np.ones(5, complex)), "a0_wrong_row_count": dict(a0=np.ones((2, 4), complex)),
+          "a0_3d": dict(a0=np.ones((3, 1, 4), complex)), "six_waves_without_dbeta2": dict(a0=np.ones(6, complex)),
+          "four_waves_with_dbeta2": dict(dbeta2=0)}       # 0: replaced by zeros shaped as the wrapper's dbeta
+
+
+@pytest.mark.parametrize("wrapper,wrong", [(w, x) for w in sorted(_WRAPPERS) for x in sorted(_WRONG)
+                                           if (w, x) != ("pairs", "four_waves_with_dbeta2")])   # pairs take no dbeta2
+def test_the_host_wrappers_share_their_per_point_shape_rules(wrapper, wrong):
+    """One helper prepares gamma, alpha, a0 and dbeta2 for all four: each wrapper refuses the same wrong inputs with a
+    ValueError, before any native call."""
+    fn, kw = _WRAPPERS[wrapper]
+    bad = dict(_WRONG[wrong])
+    if "dbeta2" in bad:
+        bad["dbeta2"] = np.zeros_like(kw["dbeta"])
+    with pytest.raises(ValueError):
+        fn(**dict(kw, gamma=1.0 if wrapper != "chain" else [1.0, 1.0], alpha=0.0 if wrapper != "chain" else [0.0, 0.0],
+                  a0=np.ones(4, complex)) | bad)
+
+
 def test_the_device_split_cuts_dbeta_by_points():
     kw = dict(dbeta=np.arange(12.0).reshape(6, 2), gamma=np.arange(6.0), alpha=0.5, a0=np.ones((6, 6), complex), n_steps=3)
     part = cut(kw, PAIRS_AXES, 6, slice(2, 5))
