@@ -8,7 +8,7 @@
 // What bounds it: FP64 vector FMA issue (16 lanes/clk/SIMD on CDNA4), NOT HBM and not MFMA:
 // a point reads 8..88 B and writes 88 B for its entire z-loop, and the RHS is an elementwise
 // complex polynomial (no contraction to tile).  So the design rules here are
-//   * minimum DP instructions per step (298 for 4 waves; see the count in DESIGN.md),
+//   * minimum DP instructions per step (298 for 4 waves, 186 where waves 2 and 4 mirror 1 and 3; see the counts in DESIGN.md),
 //   * no transcendental in the steady-state loop: E(z) = 2*gamma*exp(i*dbeta*z) is carried by a
 //     complex rotation per half step and re-seeded from an exact sincos at every multiple of RESYNC steps
 //     (64 in float64: drift <= 128 multiplications ~1.4e-14, far inside the 1e-9 parity budget),
@@ -147,6 +147,38 @@ __device__ __forceinline__ void yaman_stage(const T (&a)[2 * NW], const T (&base
     out[3] = fma_(x1, Fpr, fma_(y1, Fpi, link(gj[1], x2, 3)));
 }
 
+// ---- the fused stage for MIRRORED points: A2 == A1 and A4 == A3 bit for bit (4 waves) ------------------------------
+// yaman_stage's chains for out[0..1] / out[2..3] are one expression with (x1, y1) and (x2, y2) exchanged, those for
+// out[4..5] / out[6..7] one with (xs, ys) and (xi, yi) exchanged, and both members of a pair read the same Fp / Fs.  So a
+// point that starts with equal pumps and equal sidebands keeps them equal, in every bit, through every stage and step, and
+// half of yaman_stage repeats the other half.  This is yaman_stage restricted to waves 1 and 3 with the partner's operands
+// replaced by the wave's own:  a = [Re A1, Im A1, Re A3, Im A3],  sg = 2*tg.  Every value keeps the expression it has there,
+// with one exception:  tg * ((p0 + p0) + (p2 + p2))  is formed as  (2*tg) * (p0 + p2).  Scaling by two commutes with
+// rounding, so the two are the same number unless 2*(p0 + p2) overflows (a power above 2^1022); there the general form
+// gives inf and this one a finite gs, but gj * max(|x|, |y|) >= g * 2^1532 overflows all the same and the step ends
+// non-finite in both -- first_bad_step is the same, only the inf / NaN pattern of a state that has already failed may differ.
+// 40 DP instructions instead of 64 (p: 4, gs: 2, g_j: 2, two squares: 8, Fp and Fs: 8, four 4-deep chains: 16).
+template <typename T, bool LOSS = true>
+__device__ __forceinline__ void yaman_stage_mirrored(const T (&a)[4], const T (&base)[4], const T Er, const T Ei, const T g,
+                                                     const T sg, const T ha, T (&out)[4]) {
+    const T x1 = a[0], y1 = a[1], xs = a[2], ys = a[3];
+    const T p0 = fma_(x1, x1, y1 * y1), p2 = fma_(xs, xs, ys * ys);
+    const T gs = sg * (p0 + p2);
+    const T g1 = fma_(-g, p0, gs), g3 = fma_(-g, p2, gs);
+    auto link = [&](const T gsig, const T v, const int c) -> T {
+        if constexpr (LOSS) return fma_(gsig, v, fma_(ha, a[c], base[c]));
+        else return fma_(gsig, v, base[c]);
+    };
+    const T q11r = fma_(x1, x1, -(y1 * y1)), q11i = fma_(x1, y1, y1 * x1);  // A1*A1
+    const T qr = fma_(xs, xs, -(ys * ys)), qi = fma_(xs, ys, ys * xs);      // A3*A3
+    const T Fpr = fma_(Er, qr, -(Ei * qi)), Fpi = fma_(Er, qi, Ei * qr);
+    const T Fsr = fma_(Er, q11r, Ei * q11i), Fsi = fma_(Er, q11i, -(Ei * q11r));
+    out[2] = fma_(ys, Fsr, fma_(-xs, Fsi, link(-g3, ys, 2)));
+    out[3] = fma_(xs, Fsr, fma_(ys, Fsi, link(g3, xs, 3)));
+    out[0] = fma_(y1, Fpr, fma_(-x1, Fpi, link(-g1, y1, 0)));
+    out[1] = fma_(x1, Fpr, fma_(y1, Fpi, link(g1, x1, 1)));
+}
+
 // plain dA/dz (used by the LDS-staged A/B variant, which keeps k1..k4 as such)
 template <typename T, int NW, bool LOSS = true>
 __device__ __forceinline__ void yaman_rhs(const T (&a)[2 * NW], const T (&Er)[(NW - 2) / 2],
@@ -184,20 +216,26 @@ __device__ __forceinline__ bool any_nonfinite(const T (&y)[NC]) {
 // WSUM = true adds the per-wave summary (A.p_wave_end / A.p_wave_max, SoA [NW][N]; register layout without trajectory
 // only): |A_j|^2 of every wave with the expression the signal's summary uses, so wave 2's columns are p_end / p_max bit for
 // bit.  The end value is formed where a_end is written; only the NW running maxima are loop state.
-template <typename T, int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS = false, bool LOSS = true, bool WSUM = false>
-__global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(const SweepArgs<T> A) {
-    static_assert(!WSUM || (!TRAJ && !LDS), "the per-wave summary exists for the register layout without trajectory");
-    constexpr int NC = 2 * NW;
+//
+// The per-lane body is sweep_point<..., MIRROR>: everything behind the a0 loads.  MIRROR = true (float64, 4 waves, register
+// layout) is the same body on HALF the state -- y = [Re A1, Im A1, Re A3, Im A3], the stage yaman_stage_mirrored -- for
+// points whose a0 has A2 == A1 and A4 == A3 bit for bit (every scenario of the reference: equal pumps, equal signal and
+// idler seeds, zero phases).  The step, the rotations, the re-seeds, the event loop, the checkpoint and replay, the block
+// test and the tail are the one text below for both; the outputs are the full record, waves 2 and 4 written from the
+// registers of waves 1 and 3.  186 DP instructions per step instead of 298 (4 * 40 + 12 + 4 + 10); 178 as built, the
+// compiler forms each y*y once for |A|^2 and A*A.
+template <typename T, int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS, bool LOSS, bool WSUM, bool MIRROR>
+__device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long long idx, T (&y)[MIRROR ? NW : 2 * NW]) {
+    static_assert(!MIRROR || (sizeof(T) == 8 && NW == 4 && !LDS), "the mirrored body exists for the fused float64 4-wave step");
+    constexpr int NC = 2 * NW;                  // components of the record
+    constexpr int NS = MIRROR ? NW : NC;        // components of the state this lane carries
+    constexpr int NWS = NS / 2;                 // waves of that state
+    constexpr int SIG = MIRROR ? 2 : 4;         // Re A_sig in the state
     constexpr int NP = (NW - 2) / 2;
     constexpr int RESYNC = Phase<T>::RESYNC;
-    const long long idx = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    auto at = [](const int c) { return MIRROR ? (((c >> 2) << 1) | (c & 1)) : c; };   // record component -> state component
     const long long N = A.n_points;
-    if (idx >= N) return;
 
-    // -- per-point inputs: one coalesced load per array (512 B per wave instruction in f64)
-    T y[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) y[c] = A.a0[(long long)c * A.a0_ld + idx * A.a0_stride];
     const T g = A.gamma[idx * A.gamma_stride];
     const T tg = g + g;
     const T ha = T(-0.5) * A.alpha[idx * A.alpha_stride];
@@ -222,20 +260,23 @@ __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(
         Ei[p] = T(0);
     }
 
-    T pe = fma_(y[4], y[4], y[5] * y[5]);  // |A_sig|^2 at the last saved row (z = 0 is a saved row)
+    T pe = fma_(y[SIG], y[SIG], y[SIG + 1] * y[SIG + 1]);  // |A_sig|^2 at the last saved row (z = 0 is a saved row)
     T pm = pe;                             // np.max over saved rows
     long long bad = -1;
-    T pwm[WSUM ? NW : 1];                  // WSUM: np.max of |A_j|^2 over saved rows, every wave
+    T pwm[WSUM ? NWS : 1];                 // WSUM: np.max of |A_j|^2 over saved rows, every wave of the state
     if constexpr (WSUM) {
 #pragma unroll
-        for (int j = 0; j < NW; ++j) pwm[j] = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
+        for (int j = 0; j < NWS; ++j) pwm[j] = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
     }
     auto store_a_end = [&]() {             // A[-1]; with WSUM also |A_j|^2 of that row
 #pragma unroll
-        for (int c = 0; c < NC; ++c) A.a_end[(long long)c * N + idx] = y[c];
+        for (int c = 0; c < NC; ++c) A.a_end[(long long)c * N + idx] = y[at(c)];
         if constexpr (WSUM) {
 #pragma unroll
-            for (int j = 0; j < NW; ++j) A.p_wave_end[(long long)j * N + idx] = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
+            for (int j = 0; j < NW; ++j) {
+                const T xr = y[at(2 * j)], xi = y[at(2 * j + 1)];
+                A.p_wave_end[(long long)j * N + idx] = fma_(xr, xr, xi * xi);
+            }
         }
     };
 
@@ -255,7 +296,7 @@ __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(
         const char *rowb = reinterpret_cast<const char *>(A.traj) + (long long)r * NW * LD * (long long)sizeof(Pair);
 #pragma unroll
         for (int j = 0; j < NW; ++j)
-            store_pair_nt(rowb + (long long)j * LD * (long long)sizeof(Pair), lane_off, Pair{y[2 * j], y[2 * j + 1]});
+            store_pair_nt(rowb + (long long)j * LD * (long long)sizeof(Pair), lane_off, Pair{y[at(2 * j)], y[at(2 * j + 1)]});
     };
     if constexpr (TRAJ) store_traj_row(0);
     if (n_rows == 0) store_a_end();
@@ -269,37 +310,39 @@ __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(
         for (int c = 0; c < NC; ++c) sm_y[c * BLOCK] = y[c];
     }
     auto rk4_step_lds = [&](const int step_index) {
-        T k[NC], ys[NC];
-        const T coef[3] = {hh, hh, h};
+        if constexpr (LDS) {
+            T k[NC], ys[NC];
+            const T coef[3] = {hh, hh, h};
 #pragma unroll
-        for (int c = 0; c < NC; ++c) ys[c] = sm_y[c * BLOCK];
+            for (int c = 0; c < NC; ++c) ys[c] = sm_y[c * BLOCK];
 #pragma unroll
-        for (int st = 0; st < 4; ++st) {
-            yaman_rhs<T, NW>(ys, Er, Ei, g, tg, ha, k);
+            for (int st = 0; st < 4; ++st) {
+                yaman_rhs<T, NW>(ys, Er, Ei, g, tg, ha, k);
 #pragma unroll
-            for (int c = 0; c < NC; ++c) sm_k[(st * NC + c) * BLOCK] = k[c];
-            if (st == 0 || st == 2) {
+                for (int c = 0; c < NC; ++c) sm_k[(st * NC + c) * BLOCK] = k[c];
+                if (st == 0 || st == 2) {
 #pragma unroll
-                for (int p = 0; p < NP; ++p) rotate(Er[p], Ei[p], rc[p], rs[p]);
+                    for (int p = 0; p < NP; ++p) rotate(Er[p], Ei[p], rc[p], rs[p]);
+                }
+                if (st < 3) {
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) ys[c] = fma_(coef[st], (T)sm_k[(st * NC + c) * BLOCK], (T)sm_y[c * BLOCK]);
+                }
             }
-            if (st < 3) {
 #pragma unroll
-                for (int c = 0; c < NC; ++c) ys[c] = fma_(coef[st], (T)sm_k[(st * NC + c) * BLOCK], (T)sm_y[c * BLOCK]);
+            for (int c = 0; c < NC; ++c) {
+                const T k1 = sm_k[(0 * NC + c) * BLOCK], k2 = sm_k[(1 * NC + c) * BLOCK];
+                const T k3 = sm_k[(2 * NC + c) * BLOCK], k4 = sm_k[(3 * NC + c) * BLOCK];
+                y[c] = fma_(h6, fma_(T(2), k3, fma_(T(2), k2, k1)) + k4, (T)sm_y[c * BLOCK]);
+                sm_y[c * BLOCK] = y[c];
             }
-        }
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const T k1 = sm_k[(0 * NC + c) * BLOCK], k2 = sm_k[(1 * NC + c) * BLOCK];
-            const T k3 = sm_k[(2 * NC + c) * BLOCK], k4 = sm_k[(3 * NC + c) * BLOCK];
-            y[c] = fma_(h6, fma_(T(2), k3, fma_(T(2), k2, k1)) + k4, (T)sm_y[c * BLOCK]);
-            sm_y[c * BLOCK] = y[c];
-        }
-        if constexpr (CHECK == CHECK_EXACT) {
-            if (bad < 0 && any_nonfinite<T, NC>(y)) bad = step_index;
+            if constexpr (CHECK == CHECK_EXACT) {
+                if (bad < 0 && any_nonfinite<T, NC>(y)) bad = step_index;
+            }
         }
     };
 
-    // ---- one classic RK4 step (integrators.py:54-59) in 298 DP instructions (4 waves).
+    // ---- one classic RK4 step (integrators.py:54-59) in 298 DP instructions (4 waves; 186 on the mirrored state).
     // Each stage's axpy is folded into the RHS chains (yaman_stage, FUSED): with d = h/2
     //     Y2 = y + d*f(z, y)          Y3 = y + d*f(z+d, Y2)          Y4 = y + 2d*f(z+d, Y3)
     //     t  = Y2 + 2*Y3 + Y4 - 4*y                 ( = d*k1 + 2d*k2 + 2d*k3 )
@@ -308,26 +351,31 @@ __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(
     // which is the reference's k1..k4 combination regrouped (no change of variables, same truncation error; the
     // regrouping costs ~1 ulp(y) of rounding noise per step, ~1e-13 after 1e5 steps).  (Ed_r, Ed_i) carries
     // 2*d*gamma*exp(i*dbeta*z): on entry at z_step, on exit rotated to z_step + h.
-    auto rk4_step_on = [&](T (&y)[NC], T (&Er)[NP], T (&Ei)[NP]) {
-        T Y2[NC], Y3[NC], Y4[NC], t[NC], D[NC];
-        yaman_stage<T, NW, true, LOSS>(y, y, Er, Ei, g_d, tg_d, ha_d, Y2);  // Y2 = y + d k1
+    auto stage = [&](const T (&a)[NS], const T (&base)[NS], const T (&er)[NP], const T (&ei)[NP], const T g_c, const T tg_c,
+                     const T ha_c, T (&out)[NS]) {
+        if constexpr (MIRROR) yaman_stage_mirrored<T, LOSS>(a, base, er[0], ei[0], g_c, tg_c + tg_c, ha_c, out);
+        else yaman_stage<T, NW, true, LOSS>(a, base, er, ei, g_c, tg_c, ha_c, out);
+    };
+    auto rk4_step_on = [&](T (&y)[NS], T (&Er)[NP], T (&Ei)[NP]) {
+        T Y2[NS], Y3[NS], Y4[NS], t[NS], D[NS];
+        stage(y, y, Er, Ei, g_d, tg_d, ha_d, Y2);  // Y2 = y + d k1
 #pragma unroll
         for (int p = 0; p < NP; ++p) rotate(Er[p], Ei[p], rc[p], rs[p]);  // z + h/2
-        yaman_stage<T, NW, true, LOSS>(Y2, y, Er, Ei, g_d, tg_d, ha_d, Y3);  // Y3 = y + d k2
+        stage(Y2, y, Er, Ei, g_d, tg_d, ha_d, Y3);  // Y3 = y + d k2
         T E2r[NP], E2i[NP];
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
             E2r[p] = Er[p] + Er[p];
             E2i[p] = Ei[p] + Ei[p];
         }
-        yaman_stage<T, NW, true, LOSS>(Y3, y, E2r, E2i, g_h, tg_h, ha_h, Y4);  // Y4 = y + h k3
+        stage(Y3, y, E2r, E2i, g_h, tg_h, ha_h, Y4);  // Y4 = y + h k3
 #pragma unroll
-        for (int c = 0; c < NC; ++c) t[c] = fma_(T(2), Y3[c], fma_(T(-4), y[c], Y2[c])) + Y4[c];
+        for (int c = 0; c < NS; ++c) t[c] = fma_(T(2), Y3[c], fma_(T(-4), y[c], Y2[c])) + Y4[c];
 #pragma unroll
         for (int p = 0; p < NP; ++p) rotate(Er[p], Ei[p], rc[p], rs[p]);  // z + h
-        yaman_stage<T, NW, true, LOSS>(Y4, t, Er, Ei, g_d, tg_d, ha_d, D);  // D = t + d k4
+        stage(Y4, t, Er, Ei, g_d, tg_d, ha_d, D);  // D = t + d k4
 #pragma unroll
-        for (int c = 0; c < NC; ++c) y[c] = fma_(D[c], third, y[c]);
+        for (int c = 0; c < NS; ++c) y[c] = fma_(D[c], third, y[c]);
     };
     // The per-step finite test of the reference (integrators.py:132-135) is NOT in the float64 step: CHECK_EXACT finds the
     // exact index by REPLAY (below) -- the forward pass tests once per saved row, like CHECK_BLOCK.
@@ -336,45 +384,47 @@ __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(
     // ---- float32: the classic low-storage form (y, y_stage, accumulator; 320 instructions).  The regrouping above
     // quantises every stage increment to ulp(y); harmless at 1e-16 but measured 17x worse at float32 (6.7e-3 vs
     // 3.8e-4 relative after 1e4 steps), so single precision keeps k1..k4 at full precision.
-    T y_lo[NC];  // Kahan residue of the state (float32 path only)
+    T y_lo[NS];  // Kahan residue of the state (float32 path only)
 #pragma unroll
-    for (int c = 0; c < NC; ++c) y_lo[c] = T{};
+    for (int c = 0; c < NS; ++c) y_lo[c] = T{};
     auto rk4_step_classic = [&](const int step_index) {
-        T k[NC], ys[NC], acc[NC];
-        yaman_rhs<T, NW, LOSS>(y, Er, Ei, g, tg, ha, k);  // k1 at z
+        if constexpr (!FUSE) {
+            T k[NC], ys[NC], acc[NC];
+            yaman_rhs<T, NW, LOSS>(y, Er, Ei, g, tg, ha, k);  // k1 at z
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            acc[c] = k[c];
-            ys[c] = fma_(hh, k[c], y[c]);
-        }
+            for (int c = 0; c < NC; ++c) {
+                acc[c] = k[c];
+                ys[c] = fma_(hh, k[c], y[c]);
+            }
 #pragma unroll
-        for (int p = 0; p < NP; ++p) rotate(Er[p], Ei[p], rc[p], rs[p]);  // z + h/2
-        yaman_rhs<T, NW, LOSS>(ys, Er, Ei, g, tg, ha, k);  // k2
+            for (int p = 0; p < NP; ++p) rotate(Er[p], Ei[p], rc[p], rs[p]);  // z + h/2
+            yaman_rhs<T, NW, LOSS>(ys, Er, Ei, g, tg, ha, k);  // k2
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            acc[c] = fma_(T(2), k[c], acc[c]);
-            ys[c] = fma_(hh, k[c], y[c]);
-        }
-        yaman_rhs<T, NW, LOSS>(ys, Er, Ei, g, tg, ha, k);  // k3
+            for (int c = 0; c < NC; ++c) {
+                acc[c] = fma_(T(2), k[c], acc[c]);
+                ys[c] = fma_(hh, k[c], y[c]);
+            }
+            yaman_rhs<T, NW, LOSS>(ys, Er, Ei, g, tg, ha, k);  // k3
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            acc[c] = fma_(T(2), k[c], acc[c]);
-            ys[c] = fma_(h, k[c], y[c]);
-        }
+            for (int c = 0; c < NC; ++c) {
+                acc[c] = fma_(T(2), k[c], acc[c]);
+                ys[c] = fma_(h, k[c], y[c]);
+            }
 #pragma unroll
-        for (int p = 0; p < NP; ++p) rotate(Er[p], Ei[p], rc[p], rs[p]);  // z + h
-        yaman_rhs<T, NW, LOSS>(ys, Er, Ei, g, tg, ha, k);  // k4
-        // compensated (Kahan) state update: keeps the part of the increment that y + inc rounds away (see the
-        // packed kernel); without it float32 drifts ~n * ulp and misses its 1e-3 tolerance at 1e6 steps.
+            for (int p = 0; p < NP; ++p) rotate(Er[p], Ei[p], rc[p], rs[p]);  // z + h
+            yaman_rhs<T, NW, LOSS>(ys, Er, Ei, g, tg, ha, k);  // k4
+            // compensated (Kahan) state update: keeps the part of the increment that y + inc rounds away (see the
+            // packed kernel); without it float32 drifts ~n * ulp and misses its 1e-3 tolerance at 1e6 steps.
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const T inc = fma_(h6, acc[c] + k[c], y_lo[c]);
-            const T sum = y[c] + inc;
-            y_lo[c] = inc - (sum - y[c]);
-            y[c] = sum;
-        }
-        if constexpr (CHECK == CHECK_EXACT) {
-            if (bad < 0 && any_nonfinite<T, NC>(y)) bad = step_index;
+            for (int c = 0; c < NC; ++c) {
+                const T inc = fma_(h6, acc[c] + k[c], y_lo[c]);
+                const T sum = y[c] + inc;
+                y_lo[c] = inc - (sum - y[c]);
+                y[c] = sum;
+            }
+            if constexpr (CHECK == CHECK_EXACT) {
+                if (bad < 0 && any_nonfinite<T, NC>(y)) bad = step_index;
+            }
         }
     };
     auto rk4_step = [&](const int step_index) {
@@ -388,7 +438,7 @@ __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(
         A.first_bad[idx] = bad;
         if constexpr (WSUM) {
 #pragma unroll
-            for (int j = 0; j < NW; ++j) A.p_wave_max[(long long)j * N + idx] = pwm[j];
+            for (int j = 0; j < NW; ++j) A.p_wave_max[(long long)j * N + idx] = pwm[at(2 * j) / 2];
         }
     };
     auto seed_phase_on = [&](const int step, T (&Er)[NP], T (&Ei)[NP]) {   // exact re-seed of the phase recurrence at z = step * h
@@ -408,15 +458,15 @@ __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(
     // wave newly non-finite, the steps since then are REPLAYED on a copy with the reference's per-step test
     // (integrators.py:132-135).  The replay repeats the forward pass operation for operation (same chunks, same re-seeds,
     // same FMA sequence), so it reproduces this kernel's own trajectory bit for bit and the index it finds is exact.  Only
-    // waves with a failing lane ever take the (wave-uniform) branch: +20 VGPRs, no instruction in the steady-state loop
+    // waves with a failing lane ever take the (wave-uniform) branch: +20 VGPRs (+12 on the mirrored state), no instruction in the steady-state loop
     // (the per-step test cost 9.9 of 310.6 instructions per step, profiles/r03_c2x_pmc.csv).
     constexpr bool REPLAY = FUSE && CHECK == CHECK_EXACT;
-    T y_chk[REPLAY ? NC : 1], Er_chk[REPLAY ? NP : 1], Ei_chk[REPLAY ? NP : 1];
+    T y_chk[REPLAY ? NS : 1], Er_chk[REPLAY ? NP : 1], Ei_chk[REPLAY ? NP : 1];
     int i_chk = 0;
     auto checkpoint = [&](const int step) {
         if constexpr (REPLAY) {
 #pragma unroll
-            for (int c = 0; c < NC; ++c) y_chk[c] = y[c];
+            for (int c = 0; c < NS; ++c) y_chk[c] = y[c];
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
                 Er_chk[p] = Er[p];
@@ -427,11 +477,11 @@ __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(
     };
     auto exact_test = [&](const int i_now) {   // at a test point: y is the state after step i_now - 1
         if constexpr (REPLAY) {
-            const bool newly_bad = bad < 0 && any_nonfinite<T, NC>(y);
+            const bool newly_bad = bad < 0 && any_nonfinite<T, NS>(y);
             if (__builtin_amdgcn_ballot_w64(newly_bad) != 0) {
-                T yy[NC], er[NP], ei[NP];
+                T yy[NS], er[NP], ei[NP];
 #pragma unroll
-                for (int c = 0; c < NC; ++c) yy[c] = y_chk[c];
+                for (int c = 0; c < NS; ++c) yy[c] = y_chk[c];
 #pragma unroll
                 for (int p = 0; p < NP; ++p) {
                     er[p] = Er_chk[p];
@@ -445,7 +495,7 @@ __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(
 #pragma nounroll
                     for (int st = ii; st < e; ++st) {
                         rk4_step_on(yy, er, ei);
-                        if (bad < 0 && any_nonfinite<T, NC>(yy)) bad = st;
+                        if (bad < 0 && any_nonfinite<T, NS>(yy)) bad = st;
                     }
                     ii = e;
                 }
@@ -461,10 +511,10 @@ __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(
     if constexpr (TRAJ && !LDS) {
         if (se == 1) {
             auto save_row = [&](const int r) {
-                pe = fma_(y[4], y[4], y[5] * y[5]);
+                pe = fma_(y[SIG], y[SIG], y[SIG + 1] * y[SIG + 1]);
                 pm = pe > pm ? pe : pm;               // NaN is made to propagate after the loop (it is sticky in y)
                 if constexpr (CHECK == CHECK_BLOCK || (CHECK == CHECK_EXACT && FUSE)) {   // a row is a step here: exact either way
-                    if (bad < 0 && any_nonfinite<T, NC>(y)) bad = r - 1;
+                    if (bad < 0 && any_nonfinite<T, NS>(y)) bad = r - 1;
                 }
                 store_traj_row(r);
             };
@@ -486,7 +536,7 @@ __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(
             }
             if (pe != pe) pm = pe;                    // np.max over the saved rows propagates NaN
 #pragma unroll
-            for (int c = 0; c < NC; ++c) A.a_end[(long long)c * N + idx] = y[c];
+            for (int c = 0; c < NC; ++c) A.a_end[(long long)c * N + idx] = y[at(c)];
             write_summary();
             return;
         }
@@ -524,17 +574,17 @@ __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(
         i = end;
         if (i == next_save) {  // (i % save_every == 0), integrators.py:137 -- wave-uniform
             ++row;
-            pe = fma_(y[4], y[4], y[5] * y[5]);
+            pe = fma_(y[SIG], y[SIG], y[SIG + 1] * y[SIG + 1]);
             pm = (pe > pm || pe != pe) ? pe : pm;  // np.max propagates NaN
             if constexpr (WSUM) {
 #pragma unroll
-                for (int j = 0; j < NW; ++j) {
+                for (int j = 0; j < NWS; ++j) {
                     const T pj = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
                     pwm[j] = (pj > pwm[j] || pj != pj) ? pj : pwm[j];
                 }
             }
             if constexpr (CHECK == CHECK_BLOCK) {
-                if (bad < 0 && any_nonfinite<T, NC>(y)) bad = i - 1;
+                if (bad < 0 && any_nonfinite<T, NS>(y)) bad = i - 1;
             }
             exact_test(i);
             if constexpr (TRAJ) store_traj_row(row);
@@ -547,10 +597,54 @@ __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(
         }
     }
     if constexpr (CHECK == CHECK_BLOCK) {  // covers the unsaved tail
-        if (bad < 0 && n_run > 0 && any_nonfinite<T, NC>(y)) bad = n_run - 1;
+        if (bad < 0 && n_run > 0 && any_nonfinite<T, NS>(y)) bad = n_run - 1;
     }
     if (n_run > i_chk) exact_test(n_run);   // the unsaved tail (REPLAY only; compiled out otherwise)
     write_summary();
+}
+
+// Does every live lane of this wave start MIRRORED?  A lane agrees when A2 == A1 and A4 == A3 as bit patterns (+0 and -0
+// differ: their products differ in sign) and all eight components are finite (a NaN payload need not survive the same way
+// in both loops).  One ballot over the active lanes: the answer is wave-uniform.
+__device__ __forceinline__ bool wave_starts_mirrored(const double (&y)[8]) {
+    bool same = true;
+#pragma unroll
+    for (int c = 0; c < 8; c += 4) {
+        same = same && __builtin_bit_cast(long long, y[c]) == __builtin_bit_cast(long long, y[c + 2]) &&
+               __builtin_bit_cast(long long, y[c + 1]) == __builtin_bit_cast(long long, y[c + 3]);
+    }
+    const bool objects = !same || any_nonfinite<double, 8>(y);
+    return __builtin_amdgcn_ballot_w64(objects) == 0;
+}
+
+template <typename T, int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS = false, bool LOSS = true, bool WSUM = false>
+__global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(const SweepArgs<T> A) {
+    static_assert(!WSUM || (!TRAJ && !LDS), "the per-wave summary exists for the register layout without trajectory");
+    constexpr int NC = 2 * NW;
+    const long long idx = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (idx >= A.n_points) return;
+
+    // -- per-point inputs: one coalesced load per array (512 B per wave instruction in f64)
+    T y[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) y[c] = A.a0[(long long)c * A.a0_ld + idx * A.a0_stride];
+    // float64, 4 waves, register layout: a wave whose live lanes all start mirrored integrates waves 1 and 3 only.  The
+    // branch is taken once, before the z-loop; the lanes past n_points have left and do not vote.
+    if constexpr (sizeof(T) == 8 && NW == 4 && !LDS) {
+        if (wave_starts_mirrored(y)) {
+            // The mirrored body loads A1 and A3 again, through an index the compiler cannot see through: with y[0], y[1],
+            // y[4], y[5] handed over instead, those four registers stay live into both branches, the general branch works on
+            // copies of them and every instantiation needs 8 VGPRs more (206 instead of 198 in the headline one).
+            long long idx_m = idx;
+            asm volatile("" : "+v"(idx_m));
+            T ym[NW];
+#pragma unroll
+            for (int c = 0; c < NW; ++c) ym[c] = A.a0[(long long)(c < 2 ? c : c + 2) * A.a0_ld + idx_m * A.a0_stride];
+            sweep_point<T, NW, CHECK, TRAJ, BLOCK, LDS, LOSS, WSUM, true>(A, idx_m, ym);
+            return;
+        }
+    }
+    sweep_point<T, NW, CHECK, TRAJ, BLOCK, LDS, LOSS, WSUM, false>(A, idx, y);
 }
 
 // One lane per point.  LDS staging (an A/B variant: 5 * 2*NW * 64 * sizeof(T) bytes of LDS, 20 KB for f64 with 4 waves)

@@ -5,6 +5,8 @@
                                                                     profiles/r02_<cfg>_pmc.csv            (dominant kernel's counters per dispatch)
                                                                     profiles/kernels.json                 (read by bench.py)
 
+A third argument names the recipe the passes came from (the `source` field; default tools/profile_<tag>.sh).
+
 kernels.json, per configuration: the dominant kernel's symbol, average / min duration, VALU instructions per wave per
 z-step (SQ_INSTS_VALU / SQ_WAVES / n_zsteps), held clock (GRBM_GUI_ACTIVE / 8 XCDs / duration), and HBM bytes per launch
 from the FETCH_SIZE / WRITE_SIZE passes with the guide's gfx950 correction (bytes = counter x 1024; FETCH_SIZE doubled).
@@ -61,7 +63,8 @@ def db_counters(db, kernel):
     return counters, durations
 
 
-def main(src, tag):
+def main(src, tag, recipe=None):
+    recipe = recipe or f"tools/profile_{tag}.sh"
     out_dir = os.path.join(ROOT, "profiles")
     facts = {}
     path = os.path.join(out_dir, "kernels.json")
@@ -85,7 +88,7 @@ def main(src, tag):
         kernel = dom["Name"]
         rec = {"kernel": kernel, "calls": int(dom["Calls"]), "avg_ms": float(dom["AverageNs"]) / 1e6,
                "min_ms": float(dom["MinNs"]) / 1e6, "lanes_per_point": LANES_PER_POINT[cfg],
-               "source": f"rocprofv3 --kernel-trace --stats / --pmc passes of tools/profile_{tag}.sh ({tag}), "
+               "source": f"rocprofv3 --kernel-trace --stats / --pmc passes of {recipe} ({tag}), "
                          f"profiles/{tag}_{cfg}_kernel_stats.csv + profiles/{tag}_{cfg}_pmc.csv"}
         counters = {}
         durations = {}
@@ -162,4 +165,4 @@ def main(src, tag):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else "r02")
+    main(sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else "r02", sys.argv[3] if len(sys.argv) > 3 else None)
