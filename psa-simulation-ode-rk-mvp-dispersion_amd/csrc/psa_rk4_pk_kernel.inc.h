@@ -15,7 +15,28 @@ namespace psa {
 
 __device__ __forceinline__ f32x2 splat2(float x) { return (f32x2){x, x}; }
 
-// WSUM: the per-wave summary (see rk4_sweep_kernel), both packed points at once
+// Does every live lane of this wave start MIRRORED in both of its points?  As wave_starts_mirrored: A2 == A1 and A4 == A3
+// as bit patterns -- one 64-bit compare per packed pair, so both halves must agree, +0 and -0 differ -- and all eight
+// components of both halves finite.  One ballot over the active lanes: the answer is wave-uniform.
+__device__ __forceinline__ bool wave_starts_mirrored_pk(const f32x2 (&y)[8]) {
+    bool same = true;
+    f32x2 t = f32x2{};
+#pragma unroll
+    for (int c = 0; c < 8; c += 4) {
+        same = same && __builtin_bit_cast(long long, y[c]) == __builtin_bit_cast(long long, y[c + 2]) &&
+               __builtin_bit_cast(long long, y[c + 1]) == __builtin_bit_cast(long long, y[c + 3]);
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c) t = fma_(y[c], f32x2{}, t);   // NaN exactly for a non-finite component, per half
+    const bool objects = !same || t.x != t.x || t.y != t.y;
+    return __builtin_amdgcn_ballot_w64(objects) == 0;
+}
+
+// WSUM: the per-wave summary (see rk4_sweep_kernel), both packed points at once.
+//
+// The per-lane body is psa_rk4_pk_body.inc.h.  4 waves: a wave whose live lanes all start mirrored IN BOTH packed points runs
+// it with MIRROR = true -- waves 1 and 3 only, see rk4_sweep_kernel.  One branch before the z-loop; the lanes past n_points
+// have left and do not vote, and the odd-tail lane's slot 1 is its slot 0 again.
 template <int NW, int CHECK, bool TRAJ, int BLOCK, bool WSUM = false>
 __global__ void __launch_bounds__(BLOCK) rk4_sweep_pk_kernel(const SweepArgs<float> A) {
     static_assert(!WSUM || !TRAJ, "the per-wave summary exists for launches without trajectory");
@@ -42,252 +63,36 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_pk_kernel(const SweepArgs<flo
     V y[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) y[c] = load2(A.a0 + (long long)c * A.a0_ld, A.a0_stride);
-    const V g = load2(A.gamma, A.gamma_stride);
-    const V tg = g + g;
-    const V ha = splat2(-0.5f) * load2(A.alpha, A.alpha_stride);
-    double dbd[NP][2];
-    {
-        const V d0 = load2(A.dbeta, 1);
-        dbd[0][0] = (double)d0.x;
-        dbd[0][1] = (double)d0.y;
-        if constexpr (NP == 2) {
-            const V d1 = load2(A.dbeta2, 1);
-            dbd[1][0] = (double)d1.x;
-            dbd[1][1] = (double)d1.y;
-        }
-    }
-    const double hd = A.z_max / (double)A.n_steps;
-    const V h = splat2((float)hd), hh = splat2((float)(0.5 * hd)), h6 = splat2((float)(hd / 6.0));
-    const V two = splat2(2.0f);
-
-    V rc[NP], rs[NP], Er[NP], Ei[NP];
-    auto seed = [&](const double z, V (&outc)[NP], V (&outs)[NP], const V amp) {
+    if constexpr (NW == 4) {
+        if (wave_starts_mirrored_pk(y)) {
+            // The mirrored body loads A1 and A3 again, through an index the compiler cannot see through, so that no a0 register
+            // stays live into both branches (see rk4_sweep_kernel) -- an index taken from pt[0], which the general branch keeps
+            // anyway, so that idx does not stay live up to the branch either: the general instantiations keep their VGPR counts.
+            long long idx_m = pt[0];
+            asm volatile("" : "+v"(idx_m));
+            idx_m >>= 1;
+            {
+                constexpr bool MIRROR = true;
+                const long long idx = idx_m;
+                const long long pt[2] = {2 * idx, (2 * idx + 1 < N) ? 2 * idx + 1 : 2 * idx};
+                const bool live1 = 2 * idx + 1 < N;
+                auto load2 = [&](const float *base, const int stride) -> V {
+                    if (stride == 0) return splat2(base[0]);
+                    if (wave_full) return *reinterpret_cast<const f32x2_u *>(base + pt[0]);
+                    return (V){base[pt[0]], base[pt[1]]};
+                };
+                V y[NW];
 #pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            float c0, s0, c1, s1;
-            Phase<float>::eval(dbd[p][0] * z, c0, s0);
-            Phase<float>::eval(dbd[p][1] * z, c1, s1);
-            outc[p] = amp * (V){c0, c1};
-            outs[p] = amp * (V){s0, s1};
-        }
-    };
-    seed(0.5 * hd, rc, rs, splat2(1.0f));   // half-step rotator exp(i*dbeta*h/2)
-#pragma unroll
-    for (int p = 0; p < NP; ++p) { Er[p] = tg; Ei[p] = V{}; }
-
-    // Compensated state.  float32 loses the part of each increment (~1e-5 |y| at 1e6 steps) below ulp(y): plain y += inc
-    // drifts ~n * ulp (5e-3 at BASELINE config 4's 1e6 steps).  The state is therefore kept as  yb + dl : a base yb and a
-    // SMALL running offset dl that collects the increments (rounded at ulp(dl) ~ 1e-4 ulp(y)); y = fl(yb + dl) is formed once
-    // per step for the stage inputs, and every FOLD steps dl is folded into yb with its rounding residue kept (Fast2Sum).
-    // 16 + 8 + 24/FOLD instructions per step and component pair against 40 for a Kahan update of y every step.
-    constexpr int FOLD = RESYNC;      // folded where the phase is re-seeded
-    V yb[NC], dl[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        yb[c] = y[c];
-        dl[c] = V{};
-    }
-    auto fold = [&]() {
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const V sum = yb[c] + dl[c];
-            dl[c] = dl[c] - (sum - yb[c]);
-            yb[c] = sum;
-            y[c] = sum;
-        }
-    };
-    V pe = fma_(y[4], y[4], y[5] * y[5]);
-    V pm = pe;
-    long long bad[2] = {-1, -1};
-    V pwm[WSUM ? NW : 1];   // WSUM: np.max of |A_j|^2 over saved rows, every wave
-    if constexpr (WSUM) {
-#pragma unroll
-        for (int j = 0; j < NW; ++j) pwm[j] = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
-    }
-    auto track = [&](const int step) {  // sum_c 0*y_c is NaN exactly for a non-finite component, per packed half
-        V t = V{};
-#pragma unroll
-        for (int c = 0; c < NC; ++c) t = fma_(y[c], V{}, t);
-        if (bad[0] < 0 && t.x != t.x) bad[0] = step;
-        if (bad[1] < 0 && t.y != t.y) bad[1] = step;
-    };
-    auto store_rows = [&](float *base) {  // base[c * N + point]
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            float *dst = base + (long long)c * N + pt[0];
-            if (wave_full) {
-                *reinterpret_cast<f32x2_u *>(dst) = y[c];
-            } else {
-                dst[0] = y[c].x;
-                if (live1) dst[1] = y[c].y;
+                for (int c = 0; c < NW; ++c) y[c] = load2(A.a0 + (long long)(c < 2 ? c : c + 2) * A.a0_ld, A.a0_stride);
+#include "psa_rk4_pk_body.inc.h"
             }
-        }
-    };
-    auto store2 = [&](float *base, const V v) {   // base[pt0], base[pt1]
-        if (wave_full) {
-            *reinterpret_cast<f32x2_u *>(base + pt[0]) = v;
-        } else {
-            base[pt[0]] = v.x;
-            if (live1) base[pt[1]] = v.y;
-        }
-    };
-
-    const int se = A.save_every;
-    const int n_rows = A.n_steps / se;
-    const int n_run = (CHECK != CHECK_NONE) ? A.n_steps : n_rows * se;
-    // trajectory rows [row][wave][N][2]: the lane's two points are adjacent, so each wave of the model is ONE 16-B streaming
-    // store per lane (1 KiB per wave instruction); the (row, wave) part of the address stays in SGPRs and the lane adds a
-    // 32-bit byte offset (the C-ABI keeps N * 8 B < 2^31 for trajectory launches), exactly as rk4_sweep_kernel does.
-    const long long LD = A.traj_ld;   // points per (row, wave) region (psa_traj_ld)
-    const unsigned lane_off = (unsigned)idx * 16u;
-    auto store_traj_row = [&](const int r) {
-        const char *rowb = reinterpret_cast<const char *>(A.traj) + (long long)r * NW * LD * 8;
-        if (wave_full) {
-#pragma unroll
-            for (int j = 0; j < NW; ++j)
-                store_quad_nt(rowb + (long long)j * LD * 8, lane_off, (f32x4){y[2 * j].x, y[2 * j + 1].x, y[2 * j].y, y[2 * j + 1].y});
-        } else {
-#pragma unroll
-            for (int j = 0; j < NW; ++j) {
-                const char *wb = rowb + (long long)j * LD * 8;
-                store_pair_nt(wb, lane_off, (f32x2){y[2 * j].x, y[2 * j + 1].x});
-                if (live1) store_pair_nt(wb, lane_off + 8u, (f32x2){y[2 * j].y, y[2 * j + 1].y});
-            }
-        }
-    };
-    if constexpr (TRAJ) store_traj_row(0);
-    auto store_wave_end = [&]() {   // WSUM: |A_j|^2 of the row a_end holds
-        if constexpr (WSUM) {
-#pragma unroll
-            for (int j = 0; j < NW; ++j) store2(A.p_wave_end + (long long)j * N, fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]));
-        }
-    };
-    if (n_rows == 0) {
-        store_rows(A.a_end);
-        store_wave_end();
-    }
-
-    auto rk4_step = [&](const int step_index) {  // integrators.py:54-59, low storage: y, y_stage, accumulator
-        V k[NC], ys[NC], acc[NC];
-        yaman_rhs<V, NW>(y, Er, Ei, g, tg, ha, k);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) { acc[c] = k[c]; ys[c] = fma_(hh, k[c], y[c]); }
-#pragma unroll
-        for (int p = 0; p < NP; ++p) rotate(Er[p], Ei[p], rc[p], rs[p]);
-        yaman_rhs<V, NW>(ys, Er, Ei, g, tg, ha, k);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) { acc[c] = fma_(two, k[c], acc[c]); ys[c] = fma_(hh, k[c], y[c]); }
-        yaman_rhs<V, NW>(ys, Er, Ei, g, tg, ha, k);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) { acc[c] = fma_(two, k[c], acc[c]); ys[c] = fma_(h, k[c], y[c]); }
-#pragma unroll
-        for (int p = 0; p < NP; ++p) rotate(Er[p], Ei[p], rc[p], rs[p]);
-        yaman_rhs<V, NW>(ys, Er, Ei, g, tg, ha, k);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            dl[c] = fma_(h6, acc[c] + k[c], dl[c]);   // the increment joins the small offset ...
-            y[c] = yb[c] + dl[c];                     // ... and y is the rounded state again (next stage input, saved rows)
-        }
-        if constexpr (CHECK == CHECK_EXACT) track(step_index);
-    };
-
-    auto write_summary = [&]() {
-        store2(A.p_end, pe);
-        store2(A.p_max, pm);
-        A.first_bad[pt[0]] = bad[0];
-        if (live1) A.first_bad[pt[1]] = bad[1];
-        if constexpr (WSUM) {
-#pragma unroll
-            for (int j = 0; j < NW; ++j) store2(A.p_wave_max + (long long)j * N, pwm[j]);
-        }
-    };
-
-    // ---- save_every == 1 with a trajectory: every step is a saved row (integrators.py:137) -- the HBM-bound regime.  A
-    // dedicated loop, as in rk4_sweep_kernel: per row only |A_sig|^2, the running maximum, the block-mode finite test and
-    // the NW streaming stores; two steps per trip so one row's stores issue under the next step.
-    if constexpr (TRAJ) {
-        if (se == 1) {
-            auto save_row = [&](const int r) {
-                pe = fma_(y[4], y[4], y[5] * y[5]);
-                pm = (V){__builtin_fmaxf(pe.x, pm.x), __builtin_fmaxf(pe.y, pm.y)};   // NaN is made to propagate below
-                if constexpr (CHECK == CHECK_BLOCK) track(r - 1);
-                store_traj_row(r);
-            };
-            int i = 0;
-            while (i < n_run) {
-                seed((double)i * hd, Er, Ei, tg);
-                fold();                               // RESYNC == FOLD steps since the last one
-                const int end = (n_run - i > RESYNC) ? i + RESYNC : n_run;
-                for (; i + 2 <= end; i += 2) {
-                    rk4_step(i);
-                    save_row(i + 1);
-                    rk4_step(i + 1);
-                    save_row(i + 2);
-                }
-                if (i < end) {
-                    rk4_step(i);
-                    save_row(i + 1);
-                    ++i;
-                }
-            }
-            if (pe.x != pe.x) pm.x = pe.x;   // np.max over the saved rows propagates NaN (sticky in y)
-            if (pe.y != pe.y) pm.y = pe.y;
-            store_rows(A.a_end);
-            write_summary();
             return;
         }
     }
-
-    // seeds (and the folds of the compensated state, FOLD == RESYNC) on the absolute grid i = 0, RESYNC, ...: the trajectory
-    // does not depend on save_every (see rk4_sweep_kernel)
-    static_assert(FOLD == RESYNC, "the state is folded where the phase is re-seeded");
-    int i = 0, row = 0;
-    int next_save = (n_rows > 0) ? se : 0x7fffffff;
-    int next_seed = 0;
-    while (i < n_run) {
-        if (i == next_seed) {
-            seed((double)i * hd, Er, Ei, tg);
-            fold();
-            next_seed = (n_run - i > RESYNC) ? i + RESYNC : 0x7fffffff;
-        }
-        int end = n_run < next_seed ? n_run : next_seed;
-        end = end < next_save ? end : next_save;
-        const int m = end - i;
-        int j = 0;
-        for (; j + 2 <= m; j += 2) {
-            rk4_step(i + j);
-            rk4_step(i + j + 1);
-        }
-        if (j < m) rk4_step(i + j);
-        i = end;
-        if (i == next_save) {
-            ++row;
-            pe = fma_(y[4], y[4], y[5] * y[5]);
-            pm.x = (pe.x > pm.x || pe.x != pe.x) ? pe.x : pm.x;  // np.max propagates NaN
-            pm.y = (pe.y > pm.y || pe.y != pe.y) ? pe.y : pm.y;
-            if constexpr (WSUM) {
-#pragma unroll
-                for (int j = 0; j < NW; ++j) {
-                    const V pj = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
-                    pwm[j].x = (pj.x > pwm[j].x || pj.x != pj.x) ? pj.x : pwm[j].x;
-                    pwm[j].y = (pj.y > pwm[j].y || pj.y != pj.y) ? pj.y : pwm[j].y;
-                }
-            }
-            if constexpr (CHECK == CHECK_BLOCK) track(i - 1);
-            if constexpr (TRAJ) store_traj_row(row);
-            if (row == n_rows) {
-                store_rows(A.a_end);
-                store_wave_end();
-                next_save = 0x7fffffff;
-            } else {
-                next_save += se;
-            }
-        }
+    {
+        constexpr bool MIRROR = false;
+#include "psa_rk4_pk_body.inc.h"
     }
-    if constexpr (CHECK == CHECK_BLOCK) {
-        if (n_run > 0) track(n_run - 1);
-    }
-    write_summary();
 }
 
 // Two float32 points per lane: register layout with the loss links only (no lossless form); the per-wave summary

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Developer tool: instruction mix of the largest basic block (the 2x-unrolled z-loop body) of kernels in a gfx950 .s file.
 Usage: tools/isa_loop_stats.py file.s [--top=K] substring [substring...]   (.s from hipcc -S --cuda-device-only)
---top=K lists the K largest blocks: the one-lane float64 4-wave kernels hold two z-loops (general and mirrored)."""
+--top=K lists the K largest blocks: the one-lane float64 and the packed float32 4-wave kernels hold two z-loops (general and
+mirrored).  For the float32 unit:  SRC=psa_rk4_f32.hip OUT=/tmp/f32.s tools/asm_f64.sh  and then
+tools/isa_loop_stats.py /tmp/f32.s --top=2 rk4_sweep_pk_kernel  (valu = packed instructions per two-step trip and point pair)."""
 import re, sys
 from collections import Counter
 top = max([int(a[6:]) for a in sys.argv if a.startswith('--top=')] or [1])
