@@ -410,6 +410,42 @@ int psa_rk4_sweep_pairs_f64_dev(void *stream, int n_pairs, int64_t n_points, int
                                 const double *d_alpha, const double *d_a0_soa, uint32_t flags, double *d_a_end_soa,
                                 double *d_p_wave_end_soa, double *d_p_wave_max_soa, int64_t *d_first_bad_step);
 
+/* ---- the single-pump (degenerate) sweep: one pump, a signal and an idler at w_i = 2 w_p - w_s ----------------------------
+ * Build-defined, no reference counterpart: waves [p, s, i], NW = 3.  With P_j = |A_j|^2,
+ * S = P_p + P_s + P_i, E(z) = 2 gamma exp(i dbeta z), dbeta = beta(w_s) + beta(w_i) - 2 beta(w_p):
+ *   dA_p/dz = (-alpha/2 + i gamma (2S - P_p)) A_p + i conj(A_p) E A_s A_i
+ *   dA_s/dz = (-alpha/2 + i gamma (2S - P_s)) A_s + i conj(A_i) (conj(E)/2) A_p^2              (i: s <-> i)
+ * This is not psa_rk4_sweep_f64 with A1 == A2: there the pump's self-phase term is 1.5 gamma |A_p|^2 (A_p = sqrt(2) A1), so
+ * the phase matching is off by gamma P_p / 2.  For alpha = 0 the model conserves P_p + P_s + P_i, P_s - P_i and P_p + 2 P_s.
+ * Classic fixed-step RK4 on z_i = i * z_max / n_steps with the save and NaN semantics of psa_rk4_sweep_f64; float64 only,
+ * one sweep point per lane.
+ *   dbeta       [N]                     mismatch per point, 1/length
+ *   gamma, alpha  [N] | [1]
+ *   a0_re_im    [N][3][2] | [1][3][2]
+ *   a_end_re_im [N][3][2]   state at the last saved row
+ *   p_wave_end  [N][3]      |A_j|^2 at that row
+ *   p_wave_max  [N][3]      max of |A_j|^2 over the saved rows incl. z = 0, NaN-propagating like np.max
+ *   first_bad_step [N]      as psa_rk4_sweep_f64 (PSA_OPT_CHECK_NAN, PSA_OPT_EXACT_STEP)
+ *   traj_or_null [N][n_saved][3][2]  every saved row, or NULL
+ * The four summary outputs are always written.  flags: PSA_BCAST_GAMMA / ALPHA / A0, PSA_OPT_CHECK_NAN, PSA_OPT_EXACT_STEP,
+ * PSA_OPT_LOSSLESS (set by the host form itself for a broadcast alpha == 0), PSA_OPT_BLOCK64 and, on the `_dev` form only,
+ * PSA_OPT_TRAJ_LD; anything else is PSA_E_FLAGS.  n_points above PSA_MAX_POINTS, a trajectory whose leading dimension ld
+ * (n_points, or psa_traj_ld(n_points, 8)) has ld * 16 >= 2^32 (rows are addressed with a 32-bit lane offset) or that does not
+ * fit the device's free memory: PSA_E_TOO_LARGE; the other codes as psa_rk4_sweep_f64.  All of it is checked before any
+ * device call, in the order of psa_rk4_sweep_f64; n_points == 0 is a successful no-op.
+ */
+int psa_rk4_single_pump_f64(int device, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+                            const double *dbeta, const double *gamma, const double *alpha, const double *a0_re_im,
+                            uint32_t flags, double *a_end_re_im, double *p_wave_end, double *p_wave_max,
+                            int64_t *first_bad_step, double *traj_or_null, double *elapsed_ms_or_null);
+/* On device buffers, asynchronous on `stream`, no allocation and no synchronisation: d_dbeta [N], d_a0_soa [6][N | 1],
+ * d_a_end_soa [6][N], d_p_wave_end_soa / d_p_wave_max_soa [3][N], d_first_bad_step [N], d_traj_soa_or_null
+ * [n_saved][3][ld][2] with ld = N, or psa_traj_ld(N, 8) with PSA_OPT_TRAJ_LD. */
+int psa_rk4_single_pump_f64_dev(void *stream, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+                                const double *d_dbeta, const double *d_gamma, const double *d_alpha,
+                                const double *d_a0_soa, uint32_t flags, double *d_a_end_soa, double *d_p_wave_end_soa,
+                                double *d_p_wave_max_soa, int64_t *d_first_bad_step, double *d_traj_soa_or_null);
+
 #ifdef __cplusplus
 }
 #endif

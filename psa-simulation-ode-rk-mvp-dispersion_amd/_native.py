@@ -80,6 +80,9 @@ _SIGS = {
     # n_pairs, N, n_steps, z_max, save_every, dbeta, gamma, alpha, a0, flags, a_end, p_wave_end, p_wave_max, first_bad; host: elapsed_ms
     **_family("psa_rk4_sweep_pairs", [_I, _L, _L, _D, _I32] + [_P] * 4 + [_U32] + [_P] * 4, host=[_P],
               host_types=("f64",), dev_types=("f64",)),
+    # N, n_steps, z_max, save_every, dbeta, gamma, alpha, a0, flags, a_end, p_wave_end, p_wave_max, first_bad, traj; host: elapsed_ms
+    **_family("psa_rk4_single_pump", [_L, _L, _D, _I32] + [_P] * 4 + [_U32] + [_P] * 5, host=[_P],
+              host_types=("f64",), dev_types=("f64",)),
     "psa_yaman_rhs_f64": (_I, [_I, _L] + [_P] * 9),
     # N, p_metric, first_bad, p0_sig, gain_db, gain, best_index, best_gain, n_finite; dev: workspace
     **_family("psa_gain_summary", _GAIN, dev=[_P], host_types=("f64",), dev_types=("f64",)),
@@ -370,6 +373,44 @@ def sweep_pairs_device(*, stream: int, n_pairs: int, n_points: int, n_steps: int
         stream or None, int(n_pairs), int(n_points), int(n_steps), float(z_max), int(save_every), d_dbeta_soa or None,
         d_gamma or None, d_alpha or None, d_a0_soa or None, int(flags), d_a_end_soa or None, d_p_wave_end_soa or None,
         d_p_wave_max_soa or None, d_first_bad or None))
+
+
+def single_pump_host(dbeta, *, n_steps: int, z_max: float, save_every: int, gamma, alpha, a0, check_nan: bool = True,
+                     exact_step: Optional[bool] = None, want_traj: bool = False, device: int = 0, extra_flags: int = 0) -> dict:
+    """N independent propagations of the single-pump three-wave model on the GPU (psa_rk4_single_pump_f64; host buffers in
+    and out, float64): one pump, a signal and an idler at 2 w_p - w_s, waves [p, s, i].
+
+    dbeta (N,); gamma / alpha scalar or (N,); a0 (3,) or (N, 3) complex.  exact_step None or True: the exact first_bad_step;
+    False: the save block's last step.
+    Returns a_end (N, 3) complex, p_wave_end, p_wave_max (N, 3), first_bad_step (N,) int64, traj (N, n_saved, 3) complex or
+    None, elapsed_ms (kernel only)."""
+    dbeta = np.ascontiguousarray(np.atleast_1d(np.asarray(dbeta)), dtype=np.float64)
+    if dbeta.ndim != 1:
+        raise ValueError("dbeta must be 1-D")
+    N = int(dbeta.shape[0])
+    flags, gamma, alpha, a0, _ = _point_inputs(N, np.float64, np.complex128, int(extra_flags), gamma, alpha, a0, (3,))
+    flags |= _check_flags(check_nan, exact_step)
+    n_saved = int(n_steps) // int(save_every) + 1 if save_every > 0 else 0
+    a_end = np.empty((N, 3), dtype=np.complex128)
+    w_end = np.empty((N, 3), dtype=np.float64)
+    w_max = np.empty((N, 3), dtype=np.float64)
+    bad = np.empty(N, dtype=np.int64)
+    traj = np.empty((N, n_saved, 3), dtype=np.complex128) if want_traj else None
+    ms = C.c_double(0.0)
+    _check(_fn("psa_rk4_single_pump")(int(device), N, int(n_steps), float(z_max), int(save_every), _ptr(dbeta), _ptr(gamma),
+                                      _ptr(alpha), _ptr(a0), flags, _ptr(a_end), _ptr(w_end), _ptr(w_max), _ptr(bad),
+                                      _ptr(traj), C.cast(C.byref(ms), _P)))
+    return dict(a_end=a_end, p_wave_end=w_end, p_wave_max=w_max, first_bad_step=bad, traj=traj, elapsed_ms=ms.value)
+
+
+def single_pump_device(*, stream: int, n_points: int, n_steps: int, z_max: float, save_every: int, d_dbeta: int,
+                       d_gamma: int, d_alpha: int, d_a0_soa: int, flags: int, d_a_end_soa: int, d_p_wave_end_soa: int,
+                       d_p_wave_max_soa: int, d_first_bad: int, d_traj_soa: int = 0) -> None:
+    """Asynchronous single-pump launch on device pointers (ints), SoA layout -- see psa_rk4_single_pump_f64_dev."""
+    _check(_fn("psa_rk4_single_pump", dev=True)(
+        stream or None, int(n_points), int(n_steps), float(z_max), int(save_every), d_dbeta or None, d_gamma or None,
+        d_alpha or None, d_a0_soa or None, int(flags), d_a_end_soa or None, d_p_wave_end_soa or None,
+        d_p_wave_max_soa or None, d_first_bad or None, d_traj_soa or None))
 
 
 def chain_host(dbeta, *, n_steps, seg_len, save_every: int, gamma, alpha, a0, transfers=None, dbeta2=None,

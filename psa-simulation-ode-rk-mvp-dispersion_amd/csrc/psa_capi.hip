@@ -80,6 +80,16 @@ struct PairsCall {   // psa_rk4_sweep_pairs_f64*
     double *a_end, *wave_end, *wave_max;
     int64_t *first_bad;
 };
+struct SinglePumpCall {   // psa_rk4_single_pump_f64*
+    int64_t n_points, n_steps;
+    double z_max;
+    int32_t save_every;
+    const double *dbeta, *gamma, *alpha, *a0;
+    uint32_t flags;
+    double *a_end, *wave_end, *wave_max;
+    int64_t *first_bad;
+    double *traj;
+};
 struct Rk45Call {    // psa_rk45_sweep_f64*
     int n_waves;
     int64_t n_points;
@@ -623,6 +633,71 @@ int pairs_host(int device, const PairsCall &c, double *elapsed_ms) {
     };
     return host_call<double>(device, "the multi-channel RK4 sweep", elapsed_ms, layout,
                              [&](hipStream_t st) { return pairs_dev(st, d); });
+}
+
+// ---- the single-pump sweep (psa_rk4_single_pump_f64*): one pump, a signal and an idler ---------------------------------
+// host_form: the call as the host-buffer entry point received it (PSA_OPT_TRAJ_LD is the `_dev` form's; the host form's
+// device-side trajectory always has the padded leading dimension).  The order is validate_common's.
+int validate_single_pump(const SinglePumpCall &c, bool host_form) {
+    int rc = validate_grid(c.n_points, PSA_MAX_POINTS, 0, c.n_steps, c.z_max, c.save_every);
+    if (rc != PSA_OK) return rc;
+    const uint32_t accepted = PSA_BCAST_GAMMA | PSA_BCAST_ALPHA | PSA_BCAST_A0 | PSA_OPT_CHECK_NAN | PSA_OPT_EXACT_STEP |
+                              PSA_OPT_LOSSLESS | PSA_OPT_BLOCK64 | (host_form ? 0u : PSA_OPT_TRAJ_LD);
+    if (c.flags & ~accepted)
+        return fail(PSA_E_FLAGS, "the single-pump sweep takes the BCAST bits, CHECK_NAN, EXACT_STEP, LOSSLESS, BLOCK64 and (its "
+                                 "_dev form) TRAJ_LD only (no layout, float32 or LDS flag): 0x%x", (unsigned)(c.flags & ~accepted));
+    if (c.n_points > 0 && (!c.dbeta || !c.gamma || !c.alpha || !c.a0 || !c.a_end || !c.wave_end || !c.wave_max || !c.first_bad))
+        return fail(PSA_E_NULLPTR, "a required buffer pointer is NULL");
+    if (c.traj) {
+        // trajectory rows are addressed as a wave-uniform (row, wave) base + the lane's 32-bit byte offset
+        const bool padded = host_form || (c.flags & PSA_OPT_TRAJ_LD);
+        const unsigned long long ld = (unsigned long long)(padded ? traj_ld_of(c.n_points, sizeof(double)) : c.n_points);
+        if (ld * 16ull >= (1ull << 32))
+            return fail(PSA_E_TOO_LARGE, "a single-pump trajectory launch takes a leading dimension below 2^28 points, got %llu", ld);
+    }
+    return PSA_OK;
+}
+
+int single_pump_dev(void *stream, const SinglePumpCall &c) {
+    int rc = validate_single_pump(c, false);
+    if (rc != PSA_OK) return rc;
+    if (c.n_points == 0) return PSA_OK;
+    psa::SinglePumpArgs a;
+    fill_point_args(a, c);
+    a.p_wave_end = c.wave_end;
+    a.p_wave_max = c.wave_max;
+    a.first_bad = (long long *)c.first_bad;
+    a.traj = c.traj;
+    a.traj_ld = (c.flags & PSA_OPT_TRAJ_LD) ? traj_ld_of(c.n_points, sizeof(double)) : c.n_points;
+    a.n_steps = (int)c.n_steps;
+    a.save_every = c.save_every;
+    hipError_t e = psa::launch_sweep_single_pump_f64((hipStream_t)stream, c.flags, a);
+    if (e != hipSuccess) return hip_fail(e, "rk4_sweep_single_pump launch");
+    return PSA_OK;
+}
+
+int single_pump_host(int device, const SinglePumpCall &c, double *elapsed_ms) {
+    int rc = validate_single_pump(c, true);
+    if (rc != PSA_OK) return rc;
+    if (elapsed_ms) *elapsed_ms = 0.0;
+    if (c.n_points == 0) return PSA_OK;
+    const size_t N = (size_t)c.n_points;
+    SinglePumpCall d = c;
+    if (c.traj) d.flags |= PSA_OPT_TRAJ_LD;   // the device-side trajectory has its own leading dimension; the caller's is dense
+    d.flags |= lossless_bit(c.flags, c.alpha);
+    auto layout = [&](Staging<double> &sg) {
+        d.dbeta = sg.input(c.dbeta, N);
+        d.gamma = sg.input(c.gamma, (c.flags & PSA_BCAST_GAMMA) ? 1 : N);
+        d.alpha = sg.input(c.alpha, (c.flags & PSA_BCAST_ALPHA) ? 1 : N);
+        d.a0 = sg.input_soa(c.a0, (c.flags & PSA_BCAST_A0) ? 1 : N, 6);
+        d.a_end = sg.output_soa(c.a_end, N, 6);
+        d.wave_end = sg.output_soa(c.wave_end, N, 3);
+        d.wave_max = sg.output_soa(c.wave_max, N, 3);
+        d.first_bad = sg.output(c.first_bad, N);
+        d.traj = sg.trajectory(c.traj, N, (size_t)(c.n_steps / c.save_every + 1), 6);
+    };
+    return host_call<double>(device, "the single-pump RK4 sweep", elapsed_ms, layout,
+                             [&](hipStream_t st) { return single_pump_dev(st, d); });
 }
 
 // ---- fibre chains: S spans, one sweep launch + one epilogue (psa_chain.hip) each ------------------------------------
@@ -1304,6 +1379,22 @@ int psa_rk4_sweep_pairs_f64_dev(void *stream, int n_pairs, int64_t n_points, int
                                 double *d_p_wave_max_soa, int64_t *d_first_bad_step) {
     return pairs_dev(stream, {n_pairs, n_points, n_steps, z_max, save_every, d_dbeta_soa, d_gamma, d_alpha, d_a0_soa, flags,
                               d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step});
+}
+
+
+int psa_rk4_single_pump_f64(int device, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+                            const double *dbeta, const double *gamma, const double *alpha, const double *a0_re_im,
+                            uint32_t flags, double *a_end_re_im, double *p_wave_end, double *p_wave_max,
+                            int64_t *first_bad_step, double *traj_or_null, double *elapsed_ms_or_null) {
+    return single_pump_host(device, {n_points, n_steps, z_max, save_every, dbeta, gamma, alpha, a0_re_im, flags, a_end_re_im,
+                                     p_wave_end, p_wave_max, first_bad_step, traj_or_null}, elapsed_ms_or_null);
+}
+int psa_rk4_single_pump_f64_dev(void *stream, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+                                const double *d_dbeta, const double *d_gamma, const double *d_alpha, const double *d_a0_soa,
+                                uint32_t flags, double *d_a_end_soa, double *d_p_wave_end_soa, double *d_p_wave_max_soa,
+                                int64_t *d_first_bad_step, double *d_traj_soa_or_null) {
+    return single_pump_dev(stream, {n_points, n_steps, z_max, save_every, d_dbeta, d_gamma, d_alpha, d_a0_soa, flags,
+                                    d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step, d_traj_soa_or_null});
 }
 
 }  // extern "C"

@@ -1,0 +1,244 @@
+// psa_rk4_single_pump_kernel.inc.h -- float64 RK4 sweep of the SINGLE-PUMP (degenerate) three-wave model (gfx950): one pump,
+// a signal at w_s and an idler at w_i = 2 w_p - w_s.  Build-defined, no reference counterpart.
+//
+//     waves [p, s, i],  P_j = |A_j|^2,  S = P_p + P_s + P_i,  E(z) = 2*gamma*exp(i*dbeta*z),  dbeta = b(w_s) + b(w_i) - 2 b(w_p)
+//     dA_p/dz = (-alpha/2 + i*gamma*(2S - P_p)) A_p + i*conj(A_p) * E * A_s A_i
+//     dA_s/dz = (-alpha/2 + i*gamma*(2S - P_s)) A_s + i*conj(A_i) * (conj(E)/2) * A_p^2            (i: s <-> i)
+//
+// Sign and phase conventions are yaman_stage's (the pump reads e^{+i dbeta z}).  This is NOT the 4-wave system with A1 == A2:
+// with a = A1 = A2 and A_p = sqrt(2) a the sideband equations coincide, but the pump's self-phase term there is
+// 3*gamma*|a|^2 = 1.5*gamma*|A_p|^2 instead of gamma*|A_p|^2.
+//
+// Layout and loop are rk4_sweep_kernel's: one sweep point per lane, the whole z-loop in the kernel, the six state components
+// in VGPRs, the fused regrouped stage (stage coefficient folded into g, tg, ha and the carried phase factor), z_i formed from
+// the integer step index, the half-step rotation re-seeded exactly on the absolute grid i = 0, RESYNC, 2*RESYNC, ..., the
+// event-driven loop, and the save / NaN semantics:  CHECK_NONE: first_bad_step = -1, NaNs propagate;  CHECK_BLOCK: the last
+// step of the first non-finite save block (or of the unsaved tail);  CHECK_EXACT: the exact step, found by replaying the
+// failing block from the last test point with a per-step test -- and if that replay should stay finite (it repeats the
+// forward pass operation for operation, so it should not), `bad` becomes the block-mode answer rather than staying -1.
+// Wave-uniform control flow only: every branch is on a kernel argument, the loop counters or a ballot.
+//
+// What is carried is H = E/2, not E.  The sidebands need conj(E)/2 * A_p^2 and Im(A_p^2) = fma(x, y, y*x) = 2*RN(x*y) for every
+// input (the FOLD note on yaman_stage_mirrored), so with m = RN(x*y)
+//     Re (conj(E)/2 * A_p^2) = H_r*Re(A_p^2) + H_i*(2m) = H_r*Re(A_p^2) + E_i*m        E = H + H: an exact doubling
+//     Im (conj(E)/2 * A_p^2) = H_r*(2m) - H_i*Re(A_p^2) = E_r*m - H_i*Re(A_p^2)
+// are the same real products, hence the same rounded numbers, and Im(A_p^2) is never formed.  The pump reads E, the sidebands
+// H and E; every value is the result of an explicit fma, of a bare product that feeds one, or of an add of such results, so
+// -ffp-contract=fast has nothing left to fuse and the result is bit-defined whatever the instantiation.  The one edge is the
+// overflow of E = H + H, |2 d gamma| >= 2^1023, where the cubic terms of step 0 overflow all the same.
+//
+// Per stage 50 DP instructions (|A_j|^2: 6, S and g_j: 6, A_s A_i: 4, E * A_s A_i: 4, Re(A_p^2) and m: 2 -- the y*y of |A_p|^2
+// is shared --, conj(H) A_p^2: 4, six 4-deep chains: 24; 44 without the loss links), per step 4 * 50 + 18 (t) + 6 (update) +
+// 8 (two rotations of H) + 6 (three doublings: E at z + h/2, 2E for stage 3, E at z + h) = 238 against 298 for four waves;
+// 239 as built (215 without the loss links), see the table in DESIGN.md 3.3c.
+//
+// Out of scope: float32, lane-pair / lane-quad layouts, RK45, chains, LDS staging, a mirrored variant, a dedicated
+// save_every == 1 trajectory loop (every stride goes through the event loop).
+#pragma once
+#include "psa_rk4_kernel.inc.h"
+
+namespace psa {
+
+// out = base + c * dA/dz of a = [Re p, Im p, Re s, Im s, Re i, Im i]; c is folded into g = c*gamma, tg = 2*c*gamma,
+// ha = -c*alpha/2, (Hr, Hi) = c*gamma*exp(i*dbeta*z) and (Er, Ei) = twice that.
+template <bool LOSS>
+__device__ __forceinline__ void single_pump_stage(const double (&a)[6], const double (&base)[6], const double Hr, const double Hi,
+                                                  const double Er, const double Ei, const double g, const double tg,
+                                                  const double ha, double (&out)[6]) {
+    const double xp = a[0], yp = a[1], xs = a[2], ys = a[3], xi = a[4], yi = a[5];
+    const double ypyp = yp * yp;   // shared by |A_p|^2 and Re A_p^2
+    const double p[3] = {fma_(xp, xp, ypyp), fma_(xs, xs, ys * ys), fma_(xi, xi, yi * yi)};
+    const double s = (p[0] + p[1]) + p[2];
+    const double gs = tg * s;   // c*gamma * 2S
+    double gj[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) gj[j] = fma_(-g, p[j], gs);   // c*gamma * (2S - P_j)
+
+    auto link = [&](const double gsig, const double v, const int c) -> double {
+        if constexpr (LOSS) return fma_(gsig, v, fma_(ha, a[c], base[c]));
+        else return fma_(gsig, v, base[c]);
+    };
+    const double qr = fma_(xs, xi, -(ys * yi)), qi = fma_(xs, yi, ys * xi);   // A_s A_i
+    const double Fpr = fma_(Er, qr, -(Ei * qi)), Fpi = fma_(Er, qi, Ei * qr);  // E A_s A_i: drives the pump
+    const double ppr = fma_(xp, xp, -ypyp);                                   // Re A_p^2
+    const double m = yp * xp;                                                 // Im A_p^2 = 2m
+    const double Fsr = fma_(Hr, ppr, Ei * m), Fsi = fma_(Er, m, -(Hi * ppr));  // conj(E)/2 A_p^2: drives signal and idler
+    // pump: (ha + i g_p) A_p + i conj(A_p) Fp
+    out[0] = fma_(yp, Fpr, fma_(-xp, Fpi, link(-gj[0], yp, 0)));
+    out[1] = fma_(xp, Fpr, fma_(yp, Fpi, link(gj[0], xp, 1)));
+    // signal: (ha + i g_s) A_s + i conj(A_i) Fs ;  idler: (ha + i g_i) A_i + i conj(A_s) Fs
+    out[2] = fma_(yi, Fsr, fma_(-xi, Fsi, link(-gj[1], ys, 2)));
+    out[3] = fma_(xi, Fsr, fma_(yi, Fsi, link(gj[1], xs, 3)));
+    out[4] = fma_(ys, Fsr, fma_(-xs, Fsi, link(-gj[2], yi, 4)));
+    out[5] = fma_(xs, Fsr, fma_(ys, Fsi, link(gj[2], xi, 5)));
+}
+
+template <int CHECK, bool TRAJ, int BLOCK, bool LOSS>
+__global__ void __launch_bounds__(BLOCK) rk4_sweep_single_pump_kernel(const SinglePumpArgs A) {
+    constexpr int RESYNC = Phase<double>::RESYNC;
+    const long long idx = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    const long long N = A.n_points;
+    if (idx >= N) return;
+
+    double a[6];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) a[c] = A.a0[(long long)c * A.a0_ld + idx * A.a0_stride];
+    const double g = A.gamma[idx * A.gamma_stride];
+    const double tg = g + g;
+    const double ha = -0.5 * A.alpha[idx * A.alpha_stride];
+    const double dbd = A.dbeta[idx];
+
+    const double hd = A.z_max / (double)A.n_steps;   // np.linspace step
+    const double hh = 0.5 * hd;
+    // stage coefficients folded into the physics constants: d = h/2 (stages 1, 2, 4) and h (stage 3)
+    const double g_d = hh * g, tg_d = hh * tg, ha_d = hh * ha;
+    const double g_h = hd * g, tg_h = hd * tg, ha_h = hd * ha;
+    const double third = 1.0 / 3.0;
+    const double h_amp = g_d;   // modulus of the carried H = E/2 = d*gamma*exp(i*dbeta*z)
+
+    double rc, rs, Hr = h_amp, Hi = 0.0;   // half-step rotator and the running H
+    Phase<double>::eval(dbd * (0.5 * hd), rc, rs);
+
+    double pm[3];   // np.max of |A_j|^2 over saved rows (z = 0 is one)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) pm[j] = fma_(a[2 * j], a[2 * j], a[2 * j + 1] * a[2 * j + 1]);
+    long long bad = -1;
+
+    const int se = A.save_every;
+    const int n_rows = A.n_steps / se;                                  // saved rows after z = 0
+    const int n_run = (CHECK != CHECK_NONE) ? A.n_steps : n_rows * se;   // the tail only matters for the check
+
+    auto store_a_end = [&]() {   // the last saved row and |A_j|^2 there
+#pragma unroll
+        for (int c = 0; c < 6; ++c) A.a_end[(long long)c * N + idx] = a[c];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) A.p_wave_end[(long long)j * N + idx] = fma_(a[2 * j], a[2 * j], a[2 * j + 1] * a[2 * j + 1]);
+    };
+    auto write_summary = [&]() {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) A.p_wave_max[(long long)j * N + idx] = pm[j];
+        A.first_bad[idx] = bad;
+    };
+    // trajectory rows [row][wave][ld][2]: a wave-uniform (row, wave) base and the lane's 32-bit byte offset, as in
+    // rk4_sweep_kernel; the C-ABI keeps ld * 16 below 2^32 for trajectory launches
+    using Pair = typename PairOf<double>::type;
+    const long long LD = A.traj_ld;
+    const unsigned lane_off = (unsigned)idx * (unsigned)sizeof(Pair);
+    auto store_traj_row = [&](const int r) {
+        const char *rowb = reinterpret_cast<const char *>(A.traj) + (long long)r * 3 * LD * (long long)sizeof(Pair);
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            store_pair_nt(rowb + (long long)j * LD * (long long)sizeof(Pair), lane_off, Pair{a[2 * j], a[2 * j + 1]});
+    };
+    if constexpr (TRAJ) store_traj_row(0);
+    if (n_rows == 0) store_a_end();
+
+    // one classic RK4 step, regrouped as in rk4_sweep_kernel; (hr, hi) enters at z_step and leaves rotated to z_step + h
+    auto rk4_step_on = [&](double (&y)[6], double &hr, double &hi) {
+        double Y2[6], Y3[6], Y4[6], t[6], D[6];
+        single_pump_stage<LOSS>(y, y, hr, hi, hr + hr, hi + hi, g_d, tg_d, ha_d, Y2);      // Y2 = y + d k1
+        rotate(hr, hi, rc, rs);  // z + h/2
+        const double er = hr + hr, ei = hi + hi;
+        single_pump_stage<LOSS>(Y2, y, hr, hi, er, ei, g_d, tg_d, ha_d, Y3);               // Y3 = y + d k2
+        single_pump_stage<LOSS>(Y3, y, er, ei, er + er, ei + ei, g_h, tg_h, ha_h, Y4);     // Y4 = y + h k3: H is stage 2's E
+#pragma unroll
+        for (int c = 0; c < 6; ++c) t[c] = fma_(2.0, Y3[c], fma_(-4.0, y[c], Y2[c])) + Y4[c];
+        rotate(hr, hi, rc, rs);  // z + h
+        single_pump_stage<LOSS>(Y4, t, hr, hi, hr + hr, hi + hi, g_d, tg_d, ha_d, D);      // D = t + d k4
+#pragma unroll
+        for (int c = 0; c < 6; ++c) y[c] = fma_(D[c], third, y[c]);
+    };
+    auto rk4_step = [&]() { rk4_step_on(a, Hr, Hi); };
+    auto seed_on = [&](const int step, double &hr, double &hi) {   // exact re-seed at z = step * h
+        double c, s;
+        Phase<double>::eval(dbd * ((double)step * hd), c, s);
+        hr = h_amp * c;
+        hi = h_amp * s;
+    };
+
+    // CHECK_EXACT by replay of the failing block (see rk4_sweep_kernel): the branch is wave-uniform (a ballot)
+    constexpr bool REPLAY = CHECK == CHECK_EXACT;
+    double a_chk[REPLAY ? 6 : 1], Hr_chk = Hr, Hi_chk = Hi;
+    int i_chk = 0;
+    auto checkpoint = [&](const int step) {
+        if constexpr (REPLAY) {
+#pragma unroll
+            for (int c = 0; c < 6; ++c) a_chk[c] = a[c];
+            Hr_chk = Hr;
+            Hi_chk = Hi;
+            i_chk = step;
+        }
+    };
+    auto exact_test = [&](const int i_now) {   // at a test point: a is the state after step i_now - 1
+        if constexpr (REPLAY) {
+            const bool newly_bad = bad < 0 && any_nonfinite<double, 6>(a);
+            if (__builtin_amdgcn_ballot_w64(newly_bad) != 0) {
+                double yy[6], hr = Hr_chk, hi = Hi_chk;
+#pragma unroll
+                for (int c = 0; c < 6; ++c) yy[c] = a_chk[c];
+                int ii = i_chk;
+                while (ii < i_now) {
+                    if (ii % RESYNC == 0) seed_on(ii, hr, hi);   // the forward pass seeds at the same steps
+                    const int to_seed = RESYNC - ii % RESYNC;
+                    const int e = (i_now - ii > to_seed) ? ii + to_seed : i_now;
+#pragma nounroll
+                    for (int st = ii; st < e; ++st) {
+                        rk4_step_on(yy, hr, hi);
+                        if (bad < 0 && any_nonfinite<double, 6>(yy)) bad = st;
+                    }
+                    ii = e;
+                }
+                if (newly_bad && bad < 0) bad = i_now - 1;   // the replay stayed finite: the block-mode answer
+            }
+            checkpoint(i_now);
+        }
+    };
+
+    // ---- z-loop, event driven, seeds on the absolute grid i = 0, RESYNC, ... (see rk4_sweep_kernel)
+    int i = 0, row = 0;
+    int next_save = (n_rows > 0) ? se : 0x7fffffff;
+    int next_seed = 0;
+    checkpoint(0);
+    while (i < n_run) {
+        if (i == next_seed) {
+            seed_on(i, Hr, Hi);
+            next_seed = (n_run - i > RESYNC) ? i + RESYNC : 0x7fffffff;
+        }
+        int end = n_run < next_seed ? n_run : next_seed;
+        end = end < next_save ? end : next_save;
+        const int m = end - i;
+        int j = 0;
+        for (; j + 2 <= m; j += 2) {
+            rk4_step();
+            rk4_step();
+        }
+        if (j < m) rk4_step();
+        i = end;
+        if (i == next_save) {
+            ++row;
+#pragma unroll
+            for (int w = 0; w < 3; ++w) {
+                const double pw = fma_(a[2 * w], a[2 * w], a[2 * w + 1] * a[2 * w + 1]);
+                pm[w] = (pw > pm[w] || pw != pw) ? pw : pm[w];   // np.max propagates NaN
+            }
+            if constexpr (CHECK == CHECK_BLOCK) {
+                if (bad < 0 && any_nonfinite<double, 6>(a)) bad = i - 1;
+            }
+            exact_test(i);
+            if constexpr (TRAJ) store_traj_row(row);
+            if (row == n_rows) {   // the last saved row, not necessarily z_max
+                store_a_end();
+                next_save = 0x7fffffff;
+            } else {
+                next_save += se;
+            }
+        }
+    }
+    if constexpr (CHECK == CHECK_BLOCK) {   // covers the unsaved tail
+        if (bad < 0 && n_run > 0 && any_nonfinite<double, 6>(a)) bad = n_run - 1;
+    }
+    if (n_run > i_chk) exact_test(n_run);   // the unsaved tail (CHECK_EXACT only)
+    write_summary();
+}
+
+}  // namespace psa

@@ -708,6 +708,63 @@ def scan_wdm_gain(*, cfg: SimulationConfig, lambda_p1_m: float, lambda_p2_m: flo
                 pump_depletion=res.pump_depletion(), dbeta=db * pre["scale"], first_bad_step=res.first_bad_step, result=res)
 
 
+def scan_single_pump_gain(*, cfg: SimulationConfig, lambda_pump_m: float, lambda_signal_m: Sequence[float], p_pump: float,
+                          p_signal: float, p_idler: float = 0.0, phase_in: Optional[Sequence[float]] = None, gamma: float,
+                          alpha: float, dispersion: DispersionParams, max_order: int = 4, length_unit: str = "m",
+                          gain_unit: str = "dB", gain_mode: GainMode = "max", device: Optional[int] = None,
+                          devices: Optional[Sequence[int]] = None) -> dict:
+    """The gain spectrum of a single-pump amplifier (no reference counterpart): waves [p, s, i], the pump at lambda_pump_m,
+    sweep point k with its signal at lambda_signal_m[k] and its idler at 2 w_p - w_s, dbeta = beta(w_s) + beta(w_i) -
+    2 beta(w_p) from the Taylor expansion of ``dispersion`` up to ``max_order``, formed on the host.  One launch of the
+    single-pump kernel (sweep.rk4_sweep_single_pump) over the signal wavelengths on ``device``, or split over ``devices``;
+    sharding over a ``torch.distributed`` process group is out of scope here -- every rank would run the whole sweep.
+    A point whose plan is invalid (a wavelength that is not positive and finite, an idler frequency <= 0, a non-finite
+    dbeta) gets NaN in every output instead of an exception.
+
+    Returns dict(gain (n,) of the signal over p_signal, idler (n,) the idler's power over p_signal, pump_depletion (n,),
+    dbeta (n,) in 1/length_unit, first_bad_step (n,), result=SinglePumpResult)."""
+    from .dispersion import delta_beta_from_omegas_array
+    from .frequency_plan import omega_from_lambda, omega_from_lambda_array
+    from .sweep import initial_amplitudes, rk4_sweep_single_pump
+    unit = check_gain(gain_mode, gain_unit)
+    lam = np.asarray(lambda_signal_m, dtype=float)
+    if lam.ndim != 1 or lam.size == 0:
+        raise ValueError("lambda_signal_m must be a non-empty 1D sequence")
+    p0 = np.array([p_pump, p_signal, p_idler], dtype=float)
+    if not np.all(np.isfinite(p0)) or np.any(p0 < 0.0):
+        raise ValueError("p_pump, p_signal and p_idler must be finite non-negative powers")
+    if not p0[1] > 0.0:
+        raise ValueError("p_signal (the seed power) must be > 0 to define gain")
+    ph = None if phase_in is None else np.asarray(list(phase_in), dtype=float)
+    if ph is not None and (ph.shape != (3,) or not np.all(np.isfinite(ph))):
+        raise ValueError("phase_in must hold 3 finite phases")
+    if dispersion is None:
+        raise ValueError("dispersion must be provided")
+    if not isinstance(max_order, int) or max_order < 0:
+        raise ValueError("max_order must be a non-negative int")
+    wp = omega_from_lambda(lambda_pump_m)
+    pre = _prepare(cfg, gamma=gamma, alpha=alpha, dispersion=dispersion, phase_matching_cfg=None, beta_legacy=None,
+                   length_unit=length_unit)
+    fiber, grid = pre["fiber"], pre["grid"]
+    n = int(lam.size)
+    with np.errstate(all="ignore"):
+        ok = np.isfinite(lam) & (lam > 0.0)
+        ws = omega_from_lambda_array(np.where(ok, lam, 1.0))
+        wi = 2.0 * wp - ws
+        ok &= np.isfinite(ws) & (wi > 0.0)
+        om = np.stack([np.full(n, wp), np.full(n, wp), np.where(ok, ws, wp), np.where(ok, wi, wp)], axis=-1)
+        db = delta_beta_from_omegas_array(om, fiber.dispersion, max_order=max_order)      # per metre
+        ok &= np.isfinite(db)
+    res = rk4_sweep_single_pump(np.where(ok, db, 0.0), z_max=fiber.length_m, n_steps=n_steps_of(fiber.length_m, grid.dz_m),
+                                save_every=cfg.save_every, check_nan=bool(cfg.check_nan), gamma=fiber.gamma_W_m,
+                                alpha=fiber.alpha_1_m, a0=initial_amplitudes(p0, ph), device=(0 if device is None else int(device)),
+                                devices=devices)
+    nan = lambda x: np.where(ok, x, np.nan)   # noqa: E731
+    return dict(gain=nan(res.signal_gain(p0[1], mode=gain_mode, unit=unit)),
+                idler=nan(res.idler_conversion(p0[1], mode=gain_mode, unit=unit)), pump_depletion=nan(res.pump_depletion()),
+                dbeta=nan(db) * pre["scale"], first_bad_step=res.first_bad_step, result=res)
+
+
 def scan_copier_psa_phase(*, psa_cfg: SimulationConfig, psa_delta_beta, gamma: float, alpha: float, p_in: Sequence[float],
                           phase_in: Optional[Sequence[float]] = None, copier_cfg: Optional[SimulationConfig] = None,
                           copier_delta_beta: float = 0.0, copier_gamma: Optional[float] = None,

@@ -15,11 +15,11 @@ import numpy as np
 from . import constants
 from .config import (AdaptiveConfig, SimulationConfig, custom_simulation_config, default_simulation_config,  # noqa: F401
                      n_steps_of, validate_config)
-from .dispersion import DispersionParams
+from .dispersion import DispersionParams, delta_beta_from_omegas_array
 from .integrators import integrate_adaptive, integrate_interval
 from .parameters import FiberParams, PhaseMatchingParams, SimulationGrid, WavesParams, make_model_params
 from .phase_matching import PhaseMatchingConfig, PhaseMatchingMethod, PhaseMatchingResult, compute_phase_mismatch  # noqa: F401
-from .sweep import FibreSpan, initial_amplitudes, rk4_chain
+from .sweep import FibreSpan, initial_amplitudes, rk4_chain, rk4_sweep_single_pump
 from .yaman_model import rhs_yaman_simplified
 
 _UNITS = {"m": 1.0, "km": 1000.0}
@@ -172,6 +172,68 @@ def run_single_simulation_adaptive(cfg: SimulationConfig, *, tol: AdaptiveConfig
         raise FloatingPointError(f"NaN or Inf detected: adaptive step fell below the minimum at z = {info['z_end']}")
     out_unit = length_unit if return_length_unit is None else return_length_unit
     return z_m / _length_scale_to_m(out_unit), A
+
+
+# ---- single-pump (degenerate) amplifier: one pump, a signal, an idler at 2 w_p - w_s ---------------------------------------
+def _vec3(x, name: str, *, what: str, lower: Optional[float] = None) -> np.ndarray:
+    arr = np.asarray(list(x), dtype=float)
+    if arr.shape != (3,):
+        raise ValueError(f"{name} must have shape (3,), got {arr.shape}")
+    if not np.all(np.isfinite(arr)):
+        raise ValueError(f"{name} must be finite")
+    if lower is not None and np.any(arr < lower):
+        raise ValueError(f"{name} must be {what}")
+    return arr
+
+
+def _positive_omega(x, name: str) -> float:
+    v = float(x)
+    if not np.isfinite(v):
+        raise ValueError(f"{name} must be finite")
+    if v <= 0.0:
+        raise ValueError(f"{name} must be positive (rad/s)")
+    return v
+
+
+def run_single_pump_simulation(cfg: SimulationConfig, *, gamma: float, alpha: float, omega_pump: float, omega_signal: float,
+                               p_in: Sequence[float], phase_in: Optional[Sequence[float]] = None,
+                               dispersion: DispersionParams, max_order: int = 4, length_unit: str = "m",
+                               return_length_unit: Optional[str] = None) -> tuple[np.ndarray, np.ndarray]:
+    """One propagation of the single-pump model on the GPU -> (z_out in ``return_length_unit``, A complex128 (n_saved, 3)),
+    waves [pump, signal, idler] (no reference counterpart).  The idler sits at 2 omega_pump - omega_signal,
+    which must be positive; dbeta = beta(w_s) + beta(w_i) - 2 beta(w_p) from the Taylor expansion of ``dispersion`` up to
+    ``max_order`` (delta_beta_from_omegas_array on [w_p, w_p, w_s, w_i]).  Validation, units and the failure behaviour are
+    run_single_simulation's: with cfg.check_nan a non-finite state raises FloatingPointError at its step."""
+    validate_config(cfg)
+    _length_scale_to_m(length_unit)
+    wp, ws = _positive_omega(omega_pump, "omega_pump"), _positive_omega(omega_signal, "omega_signal")
+    wi = 2.0 * wp - ws
+    if wi <= 0.0:
+        raise ValueError("the idler frequency 2*omega_pump - omega_signal must be positive")
+    A0 = initial_amplitudes(_vec3(p_in, "p_in", what="non-negative (W)", lower=0.0),
+                            np.zeros(3) if phase_in is None else _vec3(phase_in, "phase_in", what=""))
+    if dispersion is None:
+        raise ValueError("dispersion must be provided")
+    if not isinstance(max_order, int):
+        raise TypeError("max_order must be int")
+    if max_order < 0:
+        raise ValueError("max_order must be >= 0")
+    pre = _prepare(cfg, gamma=gamma, alpha=alpha, dispersion=dispersion, phase_matching_cfg=None, beta_legacy=None,
+                   length_unit=length_unit)
+    fiber, grid = pre["fiber"], pre["grid"]
+    dbeta = float(delta_beta_from_omegas_array(np.array([wp, wp, ws, wi]), fiber.dispersion, max_order=max_order))
+    if not np.isfinite(dbeta):
+        raise ValueError("the phase mismatch is not finite")
+    n_steps = n_steps_of(fiber.length_m, grid.dz_m)
+    r = rk4_sweep_single_pump([dbeta], z_max=fiber.length_m, n_steps=n_steps, save_every=int(cfg.save_every),
+                              check_nan=bool(cfg.check_nan), exact_step=True, gamma=fiber.gamma_W_m, alpha=fiber.alpha_1_m,
+                              a0=A0, want_traj=True)
+    z_m = np.linspace(0.0, fiber.length_m, n_steps + 1)
+    bad = int(r.first_bad_step[0])
+    if cfg.check_nan and bad >= 0:
+        raise FloatingPointError(f"NaN or Inf detected at step {bad}, z = {z_m[bad]}")
+    out_unit = length_unit if return_length_unit is None else return_length_unit
+    return z_m[::int(cfg.save_every)] / _length_scale_to_m(out_unit), r.traj[0]
 
 
 # ---- concatenated spans (copier - mid-stage - PSA chains) ------------------------------------------------------------

@@ -18,8 +18,8 @@ from . import _native
 from ._partition import CHAIN_AXES, PAIRS_AXES, SWEEP_AXES, over_devices
 from .config import AdaptiveConfig, n_steps_of
 
-__all__ = ["AdaptiveResult", "ChainResult", "FibreSpan", "PairsResult", "SweepResult", "check_gain", "initial_amplitudes",
-           "rk4_chain", "rk4_sweep", "rk4_sweep_pairs", "rk45_sweep"]
+__all__ = ["AdaptiveResult", "ChainResult", "FibreSpan", "PairsResult", "SinglePumpResult", "SweepResult", "check_gain",
+           "initial_amplitudes", "rk4_chain", "rk4_sweep", "rk4_sweep_pairs", "rk4_sweep_single_pump", "rk45_sweep"]
 
 
 def initial_amplitudes(p_in, phase_in=None) -> np.ndarray:
@@ -208,6 +208,84 @@ def rk4_sweep_pairs(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps:
     p_in = np.abs(np.atleast_2d(a0)) ** 2
     return PairsResult(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"], n_steps, save_every,
                        r["elapsed_ms"], p_in)
+
+
+# ---- single-pump (degenerate) sweeps: one pump, a signal and an idler ---------------------------------------------------
+@dataclass
+class SinglePumpResult:
+    """Outcome of a single-pump sweep; waves [p, s, i], 3 columns."""
+    a_end: np.ndarray            # (N, 3) complex: state at the last SAVED row
+    p_wave_end: np.ndarray       # (N, 3) |A_j|^2 there
+    p_wave_max: np.ndarray       # (N, 3) max over saved rows (z = 0 included), NaN-propagating
+    first_bad_step: np.ndarray   # (N,) int64, -1 = finite everywhere (or check_nan off)
+    n_steps: int
+    save_every: int
+    elapsed_ms: float            # kernel time (hipEvents)
+    p_wave_in: Optional[np.ndarray] = None   # (1 | N, 3) |A_j(0)|^2: what pump_depletion compares with
+    traj: Optional[np.ndarray] = None        # (N, n_saved, 3) complex when requested
+
+    def _ratio(self, wave: int, p0, mode: str, unit: str) -> np.ndarray:
+        """metric of ``wave`` over the seed power p0, with PairsResult._ratio's NaN rule: a point with first_bad_step >= 0, a
+        non-positive or non-finite seed power, a non-finite or non-positive ratio give NaN."""
+        u = check_gain(mode, unit)
+        N = int(self.p_wave_end.shape[0])
+        p0 = np.asarray(p0, dtype=float)
+        if p0.shape not in ((), (1,), (N,)):
+            raise ValueError(f"p0 must be a scalar or have shape ({N},), got {p0.shape}")
+        p0 = np.broadcast_to(p0, (N,))
+        metric = (self.p_wave_max if mode == "max" else self.p_wave_end)[:, wave]
+        with np.errstate(all="ignore"):
+            ok = (p0 > 0.0) & np.isfinite(p0) & (np.asarray(self.first_bad_step) < 0)
+            g = metric / np.where(ok, p0, 1.0)
+            ok &= np.isfinite(g) & (g > 0.0)
+            return np.where(ok, g if u == "linear" else 10.0 * np.log10(np.where(ok, g, 1.0)), np.nan)
+
+    def signal_gain(self, p0, *, mode: str = "max", unit: str = "dB") -> np.ndarray:
+        """(N,): the signal's gain over its seed power p0, a scalar or (N,); gain_mode "end" | "max"."""
+        return self._ratio(1, p0, mode, unit)
+
+    def idler_conversion(self, p0, *, mode: str = "max", unit: str = "dB") -> np.ndarray:
+        """(N,): the idler's power over the SIGNAL's seed power p0, a scalar or (N,): the conversion efficiency."""
+        return self._ratio(2, p0, mode, unit)
+
+    def pump_depletion(self) -> np.ndarray:
+        """(N,): the fraction of the pump's input power that is gone at the last saved row, 1 - P_p_end / P_p_in (fibre
+        loss included); NaN for a failed point or a dark pump."""
+        if self.p_wave_in is None:
+            raise ValueError("pump_depletion needs p_wave_in (set by rk4_sweep_single_pump)")
+        N = int(self.p_wave_end.shape[0])
+        p_in = np.broadcast_to(self.p_wave_in[:, 0], (N,))
+        with np.errstate(all="ignore"):
+            ok = (p_in > 0.0) & np.isfinite(p_in) & (np.asarray(self.first_bad_step) < 0)
+            d = 1.0 - self.p_wave_end[:, 0] / np.where(ok, p_in, 1.0)
+            return np.where(ok & np.isfinite(d), d, np.nan)
+
+
+def rk4_sweep_single_pump(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps: Optional[int] = None,
+                          save_every: int = 10, check_nan: bool = True, exact_step: Optional[bool] = None, gamma, alpha, a0,
+                          want_traj: bool = False, device: int = 0,
+                          devices: Optional[Sequence[int]] = None) -> SinglePumpResult:
+    """Propagate N points of the single-pump (degenerate) model: one pump, a signal and an idler at 2 w_p - w_s, waves
+    [p, s, i] (build-defined).  Not rk4_sweep with equal pumps: that system gives the pump 1.5 times the
+    self-phase modulation.
+
+    dbeta (N,): beta(w_s) + beta(w_i) - 2 beta(w_p) per point; gamma / alpha a scalar or (N,); a0 (3,) or (N, 3) complex.
+    ``dz`` gives n = int(round(z_max/dz)) as integrators.py:194; or pass ``n_steps``.  ``want_traj`` also returns every saved
+    row; ``devices=[0, 1, ...]`` splits the points (and the trajectory) over several GPUs of this process.  Fixed-step
+    float64 only: no float32, chain or adaptive form."""
+    n_steps, save_every = _fixed_grid(z_max, dz, n_steps, save_every)
+    db = np.atleast_1d(np.asarray(dbeta, dtype=float))
+    if db.ndim != 1:
+        raise ValueError(f"dbeta must be a scalar or have shape (N,), got {db.shape}")
+    a0 = np.asarray(a0, dtype=np.complex128)
+    if a0.shape not in ((3,), (1, 3), (db.shape[0], 3)):
+        raise ValueError(f"a0 must have shape (3,) or ({db.shape[0]}, 3), got {a0.shape}")
+    kw = dict(dbeta=db, n_steps=n_steps, z_max=float(z_max), save_every=save_every, gamma=gamma, alpha=alpha, a0=a0,
+              check_nan=check_nan, exact_step=exact_step, want_traj=want_traj)
+    r = _run(_native.single_pump_host, SWEEP_AXES, db.shape[0], kw, device, devices)
+    p_in = np.abs(np.atleast_2d(a0)) ** 2
+    return SinglePumpResult(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"], n_steps, save_every,
+                            r["elapsed_ms"], p_in, r.get("traj"))
 
 
 # ---- chains of fibre spans ------------------------------------------------------------------------------------------
