@@ -35,8 +35,9 @@ static int simd_count(hipStream_t s) {
 // full-length ones); in between (32 768 < N <= 65 536) every SIMD that holds 64 points needs I1 whatever the layout, so one
 // lane per point is the floor there -- a hybrid launch cannot beat its slowest wave (profiles/r03_split_cliff.log).
 // I1 is the general loop's count.  For mirrored inputs (A2 == A1, A4 == A3: psa_rk4_kernel.inc.h) the one-lane kernel issues
-// about 0.6 of it, which this choice -- made on the host, where a0 cannot be seen -- does not know: in the second window
-// above the two-lane layout it picks is then the slower one.
+// about half of it, which this choice -- made on the host, where a0 cannot be seen -- does not know: in the second window
+// above the two-lane layout it picks is then the slower one, although a mirrored wave of the two-lane
+// kernel runs that same mirrored loop on its even lanes.
 // -> lanes per point: 1, 2 or (4 waves only) 4
 static int best_lanes_per_point(int n_waves, long long n_points, int simds) {
     const double i1 = (n_waves == 4) ? 300.7 : 471.9, i2 = (n_waves == 4) ? 183.6 : 296.8, i4 = 157.0;

@@ -8,7 +8,7 @@
 // What bounds it: FP64 vector FMA issue (16 lanes/clk/SIMD on CDNA4), NOT HBM and not MFMA:
 // a point reads 8..88 B and writes 88 B for its entire z-loop, and the RHS is an elementwise
 // complex polynomial (no contraction to tile).  So the design rules here are
-//   * minimum DP instructions per step (298 for 4 waves, 174 where waves 2 and 4 mirror 1 and 3; see the counts in DESIGN.md),
+//   * minimum DP instructions per step (298 for 4 waves, 154 where waves 2 and 4 mirror 1 and 3; see the counts in DESIGN.md),
 //   * no transcendental in the steady-state loop: E(z) = 2*gamma*exp(i*dbeta*z) is carried by a
 //     complex rotation per half step and re-seeded from an exact sincos at every multiple of RESYNC steps
 //     (64 in float64: drift <= 128 multiplications ~1.4e-14, far inside the 1e-9 parity budget),
@@ -92,7 +92,17 @@ template <> struct Phase<float> {
 // 64 DP instructions for NW = 4 either way (p: 8, S/g_j: 8, two products: 8, two F: 8, eight 4-deep chains: 32).
 // LOSS = false is the reference's own `alpha == 0.0` branch (_linear_loss_terms returns zeros, yaman_model.py:130-131):
 // the -alpha/2 links disappear from all 2*NW chains (8 instructions per evaluation for 4 waves).
-template <typename T, int NW, bool FUSED, bool LOSS = true>
+//
+// CROSS = true (4 waves; the RK4 sweep steps ask for it) pairs the same triple products CROSSWISE, at the same 64:
+//   H23 = E*(conj(A2)*A3)   H14 = E*(conj(A1)*A4)
+//   pump 1: i*H23*A4    pump 2: i*H14*A3    signal: i*conj(H14)*A2    idler: i*conj(H23)*A1
+// (two conjugate products: 8, two H: 8, the chains as before).  Every pair of members -- waves 1 and 2, waves 3 and 4 -- is
+// then ONE expression with the partner's operands exchanged, the H included: exchanging (A1 <-> A2, A3 <-> A4) permutes the
+// outputs and changes no bit, and where A2 == A1 and A4 == A3 the two H are the same expression on the same operands, so
+// half of the stage repeats the other half (yaman_stage_mirrored).  With six waves the pumps sum over the pairs and the
+// crosswise form would cost 64 instead of 52: NW == 6 keeps the form above whatever CROSS says, and so does RK45
+// (psa_rk45.hip: its goldens pin accepted and rejected step counts).
+template <typename T, int NW, bool FUSED, bool LOSS = true, bool CROSS = false>
 __device__ __forceinline__ void yaman_stage(const T (&a)[2 * NW], const T (&base)[2 * NW],
                                             const T (&Er)[(NW - 2) / 2], const T (&Ei)[(NW - 2) / 2], const T g,
                                             const T tg, const T ha, T (&out)[2 * NW]) {
@@ -114,6 +124,24 @@ __device__ __forceinline__ void yaman_stage(const T (&a)[2 * NW], const T (&base
     };
 
     const T x1 = a[0], y1 = a[1], x2 = a[2], y2 = a[3];
+    if constexpr (CROSS && NW == 4) {
+        const T x3 = a[4], y3 = a[5], x4 = a[6], y4 = a[7];
+        const T b23r = fma_(x2, x3, y2 * y3), b23i = fma_(x2, y3, -(y2 * x3));  // conj(A2)*A3
+        const T b14r = fma_(x1, x4, y1 * y4), b14i = fma_(x1, y4, -(y1 * x4));  // conj(A1)*A4
+        const T h23r = fma_(Er[0], b23r, -(Ei[0] * b23i)), h23i = fma_(Er[0], b23i, Ei[0] * b23r);
+        const T h14r = fma_(Er[0], b14r, -(Ei[0] * b14i)), h14i = fma_(Er[0], b14i, Ei[0] * b14r);
+        // pump1: (ha + i g1) A1 + i H23 A4 ;  pump2: (ha + i g2) A2 + i H14 A3
+        out[0] = fma_(-y4, h23r, fma_(-x4, h23i, link(-gj[0], y1, 0)));
+        out[1] = fma_(x4, h23r, fma_(-y4, h23i, link(gj[0], x1, 1)));
+        out[2] = fma_(-y3, h14r, fma_(-x3, h14i, link(-gj[1], y2, 2)));
+        out[3] = fma_(x3, h14r, fma_(-y3, h14i, link(gj[1], x2, 3)));
+        // signal: (ha + i g3) A3 + i conj(H14) A2 ;  idler: (ha + i g4) A4 + i conj(H23) A1
+        out[4] = fma_(-y2, h14r, fma_(x2, h14i, link(-gj[2], y3, 4)));
+        out[5] = fma_(x2, h14r, fma_(y2, h14i, link(gj[2], x3, 5)));
+        out[6] = fma_(-y1, h23r, fma_(x1, h23i, link(-gj[3], y4, 6)));
+        out[7] = fma_(x1, h23r, fma_(y1, h23i, link(gj[3], x4, 7)));
+        return;
+    }
     const T q12r = fma_(x1, x2, -(y1 * y2)), q12i = fma_(x1, y2, y1 * x2);  // A1*A2
 
     T Fpr = T{}, Fpi = T{};  // sum over pairs of E_p * (A_s A_i): drives both pumps
@@ -147,31 +175,23 @@ __device__ __forceinline__ void yaman_stage(const T (&a)[2 * NW], const T (&base
     out[3] = fma_(x1, Fpr, fma_(y1, Fpi, link(gj[1], x2, 3)));
 }
 
-// ---- the fused stage for MIRRORED points: A2 == A1 and A4 == A3 bit for bit (4 waves) ------------------------------
-// yaman_stage's chains for out[0..1] / out[2..3] are one expression with (x1, y1) and (x2, y2) exchanged, those for
-// out[4..5] / out[6..7] one with (xs, ys) and (xi, yi) exchanged, and both members of a pair read the same Fp / Fs.  So a
-// point that starts with equal pumps and equal sidebands keeps them equal, in every bit, through every stage and step, and
-// half of yaman_stage repeats the other half.  This is yaman_stage restricted to waves 1 and 3 with the partner's operands
-// replaced by the wave's own:  a = [Re A1, Im A1, Re A3, Im A3],  sg = 2*tg.  Every value keeps the expression it has there,
-// with one exception:  tg * ((p0 + p0) + (p2 + p2))  is formed as  (2*tg) * (p0 + p2).  Scaling by two commutes with
-// rounding, so the two are the same number unless 2*(p0 + p2) overflows (a power above 2^1022); there the general form
-// gives inf and this one a finite gs, but gj * max(|x|, |y|) >= g * 2^1532 overflows all the same and the step ends
-// non-finite in both -- first_bad_step is the same, only the inf / NaN pattern of a state that has already failed may differ.
-// 40 DP instructions instead of 64 (p: 4, gs: 2, g_j: 2, two squares: 8, Fp and Fs: 8, four 4-deep chains: 16).
-//
-// FOLD = true takes 38: the imaginary part of a square,  q_i = fma(x, y, y*x),  is  2 * RN(x*y)  for EVERY input -- the exact
-// sum is 2m + e with m = RN(x*y) and |e| <= ulp(m)/2, a quarter of the spacing at 2m (half of it below a power of two, a tie
-// to the even 2m among subnormals), so it rounds back to 2m; zeros keep their sign, an overflowing or NaN product stays what
-// it is.  Each F product that reads q_i can therefore read m and the DOUBLED phase factor (Dr, Di) = (Er + Er, Ei + Ei)
-// instead:  Er * q_i = Dr * m  and  Ei * q_i = Di * m  are the same real products, hence the same rounded numbers, and the
-// two q_i FMAs go.  The edge is overflow of a doubling, which is not exact: 2m where m is finite (|x*y| >= 2^1023 in
-// float64: the general form then reads q_i = inf, this one a finite m, but the cubic terms g_j * max(|x|, |y|) overflow in
-// the same stage all the same, as above: equal first_bad_step, only the inf / NaN pattern of a failed state may differ), and
-// 2E, which overflows only for |2 d gamma| >= 2^1023, where the step's own E2 = E + E overflows in step 0 already.
-// FOLD = false ignores (Dr, Di).  FUSED = false is the plain dA/dz, as in yaman_stage (the float32 steps).
-template <typename T, bool LOSS = true, bool FUSED = true, bool FOLD = true>
-__device__ __forceinline__ void yaman_stage_mirrored(const T (&a)[4], const T (&base)[4], const T Er, const T Ei, const T Dr,
-                                                     const T Di, const T g, const T sg, const T ha, T (&out)[4]) {
+// ---- the stage for MIRRORED points: A2 == A1 and A4 == A3 bit for bit (4 waves) ------------------------------------
+// The crosswise yaman_stage (CROSS) with the duplicates removed.  There, out[0..1] / out[2..3] are one expression with
+// (A1, A4, H23) and (A2, A3, H14) exchanged, out[4..5] / out[6..7] likewise, and on a mirrored point H23 and H14 are the same
+// expression on the same operands.  So a point that starts with equal pumps and equal sidebands keeps them equal, in every
+// bit, through every stage and step, and half of the stage repeats the other half.  This is that stage restricted to waves
+// 1 and 3 with the partner's operands replaced by the wave's own:  a = [Re A1, Im A1, Re A3, Im A3],  sg = 2*tg,
+//   b = conj(A1)*A3,  h = E*b,   pump: i*h*A3,   sideband: i*conj(h)*A1.
+// Every value keeps the expression it has there, with one exception:  tg * ((p0 + p0) + (p2 + p2))  is formed as
+// (2*tg) * (p0 + p2).  Scaling by two commutes with rounding, so the two are the same number unless 2*(p0 + p2) overflows
+// (a power above 2^1022); there the general form gives inf and this one a finite gs, but gj * max(|x|, |y|) >= g * 2^1532
+// overflows all the same and the step ends non-finite in both -- first_bad_step is the same, only the inf / NaN pattern of
+// a state that has already failed may differ.
+// 32 DP instructions instead of 64 (p: 4, gs: 2, g_j: 2, b: 4, h: 4, four 4-deep chains: 16), in every stage of the step.
+// FUSED = false is the plain dA/dz, as in yaman_stage (the float32 steps).
+template <typename T, bool LOSS = true, bool FUSED = true>
+__device__ __forceinline__ void yaman_stage_mirrored(const T (&a)[4], const T (&base)[4], const T Er, const T Ei, const T g,
+                                                     const T sg, const T ha, T (&out)[4]) {
     const T x1 = a[0], y1 = a[1], xs = a[2], ys = a[3];
     const T p0 = fma_(x1, x1, y1 * y1), p2 = fma_(xs, xs, ys * ys);
     const T gs = sg * (p0 + p2);
@@ -180,34 +200,20 @@ __device__ __forceinline__ void yaman_stage_mirrored(const T (&a)[4], const T (&
         if constexpr (LOSS) return fma_(gsig, v, FUSED ? fma_(ha, a[c], base[c]) : ha * a[c]);
         else return FUSED ? fma_(gsig, v, base[c]) : gsig * v;
     };
-    const T q11r = fma_(x1, x1, -(y1 * y1));  // Re A1*A1
-    const T qr = fma_(xs, xs, -(ys * ys));    // Re A3*A3
-    T Fpr, Fpi, Fsr, Fsi;
-    if constexpr (FOLD) {
-        const T m1 = y1 * x1, ms = ys * xs;   // Im A1*A1 = 2*m1, Im A3*A3 = 2*ms
-        Fpr = fma_(Er, qr, -(Di * ms));
-        Fpi = fma_(Dr, ms, Ei * qr);
-        Fsr = fma_(Er, q11r, Di * m1);
-        Fsi = fma_(Dr, m1, -(Ei * q11r));
-    } else {
-        const T q11i = fma_(x1, y1, y1 * x1), qi = fma_(xs, ys, ys * xs);
-        Fpr = fma_(Er, qr, -(Ei * qi));
-        Fpi = fma_(Er, qi, Ei * qr);
-        Fsr = fma_(Er, q11r, Ei * q11i);
-        Fsi = fma_(Er, q11i, -(Ei * q11r));
-    }
-    out[2] = fma_(ys, Fsr, fma_(-xs, Fsi, link(-g3, ys, 2)));
-    out[3] = fma_(xs, Fsr, fma_(ys, Fsi, link(g3, xs, 3)));
-    out[0] = fma_(y1, Fpr, fma_(-x1, Fpi, link(-g1, y1, 0)));
-    out[1] = fma_(x1, Fpr, fma_(y1, Fpi, link(g1, x1, 1)));
+    const T br = fma_(x1, xs, y1 * ys), bi = fma_(x1, ys, -(y1 * xs));  // conj(A1)*A3
+    const T hr = fma_(Er, br, -(Ei * bi)), hi = fma_(Er, bi, Ei * br);
+    out[0] = fma_(-ys, hr, fma_(-xs, hi, link(-g1, y1, 0)));
+    out[1] = fma_(xs, hr, fma_(-ys, hi, link(g1, x1, 1)));
+    out[2] = fma_(-y1, hr, fma_(x1, hi, link(-g3, ys, 2)));
+    out[3] = fma_(x1, hr, fma_(y1, hi, link(g3, xs, 3)));
 }
 
-// plain dA/dz (used by the LDS-staged A/B variant, which keeps k1..k4 as such)
+// plain dA/dz of the RK4 sweeps (the float32 steps and the LDS-staged A/B variant, which keep k1..k4 as such): crosswise for 4 waves
 template <typename T, int NW, bool LOSS = true>
 __device__ __forceinline__ void yaman_rhs(const T (&a)[2 * NW], const T (&Er)[(NW - 2) / 2],
                                           const T (&Ei)[(NW - 2) / 2], const T g, const T tg, const T ha,
                                           T (&k)[2 * NW]) {
-    yaman_stage<T, NW, false, LOSS>(a, a, Er, Ei, g, tg, ha, k);
+    yaman_stage<T, NW, false, LOSS, true>(a, a, Er, Ei, g, tg, ha, k);
 }
 
 // (Er,Ei) *= (rc,rs)
@@ -245,9 +251,7 @@ __device__ __forceinline__ bool any_nonfinite(const T (&y)[NC]) {
 // points whose a0 has A2 == A1 and A4 == A3 bit for bit (every scenario of the reference: equal pumps, equal signal and
 // idler seeds, zero phases).  The step, the rotations, the re-seeds, the event loop, the checkpoint and replay, the block
 // test and the tail are the one text below for both; the outputs are the full record, waves 2 and 4 written from the
-// registers of waves 1 and 3.  186 DP instructions per step instead of 298 (4 * 40 + 12 + 4 + 10) with the plain stage and
-// 182 with the folded one in stages 1, 2 and 4 (3 * 2 FMAs less, one doubling of the phase factor more); 174 as built, the
-// compiler forms each y*y once for |A|^2 and A*A.
+// registers of waves 1 and 3.  154 DP instructions per step instead of 298 (4 * 32 + 12 + 4 + 10).
 template <typename T, int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS, bool LOSS, bool WSUM, bool MIRROR>
 __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long long idx, T (&y)[MIRROR ? NW : 2 * NW]) {
     static_assert(!MIRROR || (sizeof(T) == 8 && NW == 4 && !LDS), "the mirrored body exists for the fused float64 4-wave step");
@@ -277,16 +281,11 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
     const T e_amp = FUSE ? tg_d : tg;  // modulus of the carried phase factor: 2*d*gamma (fused) or 2*gamma
 
     T rc[NP], rs[NP], Er[NP], Ei[NP];  // half-step rotator and the running 2*gamma*exp(i dbeta z)
-    T Dr[NP], Di[NP];                  // MIRROR: twice that (the folded stage's second operand), carried with it
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
         Phase<T>::eval(dbd[p] * (0.5 * hd), rc[p], rs[p]);
         Er[p] = e_amp;
         Ei[p] = T(0);
-        if constexpr (MIRROR) {
-            Dr[p] = e_amp + e_amp;
-            Di[p] = T(0);
-        }
     }
 
     T pe = fma_(y[SIG], y[SIG], y[SIG + 1] * y[SIG + 1]);  // |A_sig|^2 at the last saved row (z = 0 is a saved row)
@@ -371,7 +370,7 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
         }
     };
 
-    // ---- one classic RK4 step (integrators.py:54-59) in 298 DP instructions (4 waves; 174 on the mirrored state).
+    // ---- one classic RK4 step (integrators.py:54-59) in 298 DP instructions (4 waves; 154 on the mirrored state).
     // Each stage's axpy is folded into the RHS chains (yaman_stage, FUSED): with d = h/2
     //     Y2 = y + d*f(z, y)          Y3 = y + d*f(z+d, Y2)          Y4 = y + 2d*f(z+d, Y3)
     //     t  = Y2 + 2*Y3 + Y4 - 4*y                 ( = d*k1 + 2d*k2 + 2d*k3 )
@@ -380,45 +379,36 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
     // which is the reference's k1..k4 combination regrouped (no change of variables, same truncation error; the
     // regrouping costs ~1 ulp(y) of rounding noise per step, ~1e-13 after 1e5 steps).  (Ed_r, Ed_i) carries
     // 2*d*gamma*exp(i*dbeta*z): on entry at z_step, on exit rotated to z_step + h.
-    // MIRROR: stages 1, 2 and 4 are the folded stage (yaman_stage_mirrored, FOLD) and read the doubled phase factor next to the
-    // plain one.  Stage 2's is the E2 that stage 3 needs anyway; stage 4's, 2E(z + h), is formed once after the second rotation
-    // and is the next step's stage-1 operand: (Dr, Di) is carried with (Er, Ei) and re-formed wherever those are re-seeded.
-    // Stage 3 works on 2E already, would need 4E, and keeps the plain stage.  174 DP instructions per step as built.
-    auto stage = [&](auto fold, const T (&a)[NS], const T (&base)[NS], const T (&er)[NP], const T (&ei)[NP], const T (&dr)[NP],
-                     const T (&di)[NP], const T g_c, const T tg_c, const T ha_c, T (&out)[NS]) {
-        if constexpr (MIRROR)
-            yaman_stage_mirrored<T, LOSS, true, decltype(fold)::value>(a, base, er[0], ei[0], dr[0], di[0], g_c, tg_c + tg_c, ha_c, out);
-        else yaman_stage<T, NW, true, LOSS>(a, base, er, ei, g_c, tg_c, ha_c, out);
+    // MIRROR: the same step on the half state, every stage yaman_stage_mirrored.
+    auto stage = [&](const T (&a)[NS], const T (&base)[NS], const T (&er)[NP], const T (&ei)[NP], const T g_c, const T tg_c,
+                     const T ha_c, T (&out)[NS]) {
+        if constexpr (MIRROR) yaman_stage_mirrored<T, LOSS, true>(a, base, er[0], ei[0], g_c, tg_c + tg_c, ha_c, out);
+        else yaman_stage<T, NW, true, LOSS, true>(a, base, er, ei, g_c, tg_c, ha_c, out);
     };
-    auto double_phase = [&](const T (&er)[NP], const T (&ei)[NP], T (&dr)[NP], T (&di)[NP]) {
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            dr[p] = er[p] + er[p];
-            di[p] = ei[p] + ei[p];
-        }
-    };
-    auto rk4_step_on = [&](T (&y)[NS], T (&Er)[NP], T (&Ei)[NP], T (&Dr)[NP], T (&Di)[NP]) {
+    auto rk4_step_on = [&](T (&y)[NS], T (&Er)[NP], T (&Ei)[NP]) {
         T Y2[NS], Y3[NS], Y4[NS], t[NS], D[NS];
-        stage(std::true_type{}, y, y, Er, Ei, Dr, Di, g_d, tg_d, ha_d, Y2);  // Y2 = y + d k1
+        stage(y, y, Er, Ei, g_d, tg_d, ha_d, Y2);  // Y2 = y + d k1
 #pragma unroll
         for (int p = 0; p < NP; ++p) rotate(Er[p], Ei[p], rc[p], rs[p]);  // z + h/2
+        stage(Y2, y, Er, Ei, g_d, tg_d, ha_d, Y3);  // Y3 = y + d k2
         T E2r[NP], E2i[NP];
-        if constexpr (MIRROR) double_phase(Er, Ei, E2r, E2i);
-        stage(std::true_type{}, Y2, y, Er, Ei, E2r, E2i, g_d, tg_d, ha_d, Y3);  // Y3 = y + d k2
-        if constexpr (!MIRROR) double_phase(Er, Ei, E2r, E2i);
-        stage(std::false_type{}, Y3, y, E2r, E2i, E2r, E2i, g_h, tg_h, ha_h, Y4);  // Y4 = y + h k3
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            E2r[p] = Er[p] + Er[p];
+            E2i[p] = Ei[p] + Ei[p];
+        }
+        stage(Y3, y, E2r, E2i, g_h, tg_h, ha_h, Y4);  // Y4 = y + h k3
 #pragma unroll
         for (int c = 0; c < NS; ++c) t[c] = fma_(T(2), Y3[c], fma_(T(-4), y[c], Y2[c])) + Y4[c];
 #pragma unroll
         for (int p = 0; p < NP; ++p) rotate(Er[p], Ei[p], rc[p], rs[p]);  // z + h
-        if constexpr (MIRROR) double_phase(Er, Ei, Dr, Di);
-        stage(std::true_type{}, Y4, t, Er, Ei, Dr, Di, g_d, tg_d, ha_d, D);  // D = t + d k4
+        stage(Y4, t, Er, Ei, g_d, tg_d, ha_d, D);  // D = t + d k4
 #pragma unroll
         for (int c = 0; c < NS; ++c) y[c] = fma_(D[c], third, y[c]);
     };
     // The per-step finite test of the reference (integrators.py:132-135) is NOT in the float64 step: CHECK_EXACT finds the
     // exact index by REPLAY (below) -- the forward pass tests once per saved row, like CHECK_BLOCK.
-    auto rk4_step_reg = [&](const int) { rk4_step_on(y, Er, Ei, Dr, Di); };
+    auto rk4_step_reg = [&](const int) { rk4_step_on(y, Er, Ei); };
 
     // ---- float32: the classic low-storage form (y, y_stage, accumulator; 320 instructions).  The regrouping above
     // quantises every stage increment to ulp(y); harmless at 1e-16 but measured 17x worse at float32 (6.7e-3 vs
@@ -480,7 +470,7 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
             for (int j = 0; j < NW; ++j) A.p_wave_max[(long long)j * N + idx] = pwm[at(2 * j) / 2];
         }
     };
-    auto seed_phase_on = [&](const int step, T (&Er)[NP], T (&Ei)[NP], T (&Dr)[NP], T (&Di)[NP]) {   // exact re-seed of the phase recurrence at z = step * h
+    auto seed_phase_on = [&](const int step, T (&Er)[NP], T (&Ei)[NP]) {   // exact re-seed of the phase recurrence at z = step * h
         const double z = (double)step * hd;
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
@@ -489,9 +479,8 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
             Er[p] = e_amp * c;
             Ei[p] = e_amp * s;
         }
-        if constexpr (MIRROR && FUSE) double_phase(Er, Ei, Dr, Di);
     };
-    auto seed_phase = [&](const int step) { seed_phase_on(step, Er, Ei, Dr, Di); };
+    auto seed_phase = [&](const int step) { seed_phase_on(step, Er, Ei); };
 
     // ---- CHECK_EXACT for the float64 register variant: exact first_bad_step at the price of the block test.  The state at
     // the last test point (y and the carried phase factor) is kept; when a test finds a lane of the
@@ -519,7 +508,7 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
         if constexpr (REPLAY) {
             const bool newly_bad = bad < 0 && any_nonfinite<T, NS>(y);
             if (__builtin_amdgcn_ballot_w64(newly_bad) != 0) {
-                T yy[NS], er[NP], ei[NP], dr[NP], di[NP];
+                T yy[NS], er[NP], ei[NP];
 #pragma unroll
                 for (int c = 0; c < NS; ++c) yy[c] = y_chk[c];
 #pragma unroll
@@ -527,15 +516,14 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
                     er[p] = Er_chk[p];
                     ei[p] = Ei_chk[p];
                 }
-                if constexpr (MIRROR) double_phase(er, ei, dr, di);   // not part of the checkpoint: doubling the restored factor is exact
                 int ii = i_chk;
                 while (ii < i_now) {
-                    if (ii % RESYNC == 0) seed_phase_on(ii, er, ei, dr, di);   // the forward pass seeds at the same steps
+                    if (ii % RESYNC == 0) seed_phase_on(ii, er, ei);   // the forward pass seeds at the same steps
                     const int to_seed = RESYNC - ii % RESYNC;
                     const int e = (i_now - ii > to_seed) ? ii + to_seed : i_now;
 #pragma nounroll
                     for (int st = ii; st < e; ++st) {
-                        rk4_step_on(yy, er, ei, dr, di);
+                        rk4_step_on(yy, er, ei);
                         if (bad < 0 && any_nonfinite<T, NS>(yy)) bad = st;
                     }
                     ii = e;

@@ -61,7 +61,9 @@ template <int L> __device__ __forceinline__ double pairs_allreduce(double v) {
 
 // out = base + c * dA/dz of the lane's four waves a = [Re p1, Im p1, Re p2, Im p2, Re s, Im s, Re i, Im i] (stage
 // coefficient c folded into g, tg, ha, E as in yaman_stage).  With one pair lit the sums are that pair's own values plus
-// exact zeros, and the arithmetic is yaman_stage<double, 4, true> operation for operation.
+// exact zeros, and the arithmetic is the pairwise form of yaman_stage<double, 4, true> (CROSS = false) operation for
+// operation.  The RK4 sweep of rk4_sweep_kernel takes the crosswise form: the same triple products in another order, so
+// the two kernels agree to rounding there, not bit for bit.
 template <int L, bool LOSS>
 __device__ __forceinline__ void pairs_stage(const double (&a)[8], const double (&base)[8], const double Er, const double Ei,
                                             const double g, const double tg, const double ha, double (&out)[8]) {

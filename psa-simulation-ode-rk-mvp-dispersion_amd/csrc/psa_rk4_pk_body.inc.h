@@ -3,10 +3,10 @@
 //     MIRROR (constexpr bool), A, idx, N, pt[2], live1, wave_full, load2(base, stride)  and the state  V y[MIRROR ? NW : 2 * NW].
 // MIRROR = true (4 waves) is the same body on HALF the state, as in sweep_point: y, yb, dl, k, ys and acc hold
 // [Re A1, Im A1, Re A3, Im A3] of points whose a0 has A2 == A1 and A4 == A3 bit for bit, the stage is yaman_stage_mirrored
-// (un-fused, folded), and waves 2 and 4 of the record are written from the registers of waves 1 and 3.  The step, seeds,
+// (un-fused), and waves 2 and 4 of the record are written from the registers of waves 1 and 3.  The step, seeds,
 // fold(), event loop, track, tail, every-step loop and summary are this one text for both.
-// 188 packed instructions per step and point pair instead of 328 (4 * 38 stage + 4 doublings + 6 rotation + 6 * 4 update
-// + 2 * 4 state = 194 by hand; the general step 4 * 64 + 6 + 6 * 8 + 2 * 8 = 326; as built, tools/isa_loop_stats.py).
+// 168 packed instructions per step and point pair instead of 328 (4 * 32 stage + 6 rotation + 6 * 4 update + 2 * 4 state
+// = 166 by hand; the general step 4 * 64 + 6 + 6 * 8 + 2 * 8 = 326; as built, tools/isa_loop_stats.py).
 //
 // Why text and not a function template like sweep_point: a function, even a forced-inline one, is optimised on its own
 // before it is inlined, the kernel-argument loads of the general instantiations then all move to the kernel's entry and
@@ -50,19 +50,7 @@
     seed(0.5 * hd, rc, rs, splat2(1.0f));   // half-step rotator exp(i*dbeta*h/2)
 #pragma unroll
     for (int p = 0; p < NP; ++p) { Er[p] = tg; Ei[p] = V{}; }
-    // MIRROR: the folded stage reads 2E next to E (yaman_stage_mirrored).  Stages 2 and 3 share E(z + h/2), stage 4 and the
-    // next step's stage 1 share E(z + h): two doublings per step, (Dr, Di) carried with (Er, Ei) and re-formed at every seed.
-    V Dr[NP], Di[NP];
-    auto double_phase = [&]() {
-        if constexpr (MIRROR) {
-#pragma unroll
-            for (int p = 0; p < NP; ++p) { Dr[p] = Er[p] + Er[p]; Di[p] = Ei[p] + Ei[p]; }
-        }
-    };
-    auto seed_phase = [&](const int step) {   // exact re-seed of the phase recurrence at z = step * h
-        seed((double)step * hd, Er, Ei, tg);
-        double_phase();
-    };
+    auto seed_phase = [&](const int step) { seed((double)step * hd, Er, Ei, tg); };   // exact re-seed of the phase recurrence at z = step * h
 
     // Compensated state.  float32 loses the part of each increment (~1e-5 |y| at 1e6 steps) below ulp(y): plain y += inc
     // drifts ~n * ulp (5e-3 at BASELINE config 4's 1e6 steps).  The state is therefore kept as  yb + dl : a base yb and a
@@ -160,7 +148,7 @@
     }
 
     auto rhs = [&](const V (&a)[NS], V (&k)[NS]) {   // dA/dz(a) at the carried phase factor
-        if constexpr (MIRROR) yaman_stage_mirrored<V, true, false, true>(a, a, Er[0], Ei[0], Dr[0], Di[0], g, tg + tg, ha, k);
+        if constexpr (MIRROR) yaman_stage_mirrored<V, true, false>(a, a, Er[0], Ei[0], g, tg + tg, ha, k);
         else yaman_rhs<V, NW>(a, Er, Ei, g, tg, ha, k);
     };
     auto rk4_step = [&](const int step_index) {  // integrators.py:54-59, low storage: y, y_stage, accumulator
@@ -170,7 +158,6 @@
         for (int c = 0; c < NS; ++c) { acc[c] = k[c]; ys[c] = fma_(hh, k[c], y[c]); }
 #pragma unroll
         for (int p = 0; p < NP; ++p) rotate(Er[p], Ei[p], rc[p], rs[p]);
-        double_phase();
         rhs(ys, k);
 #pragma unroll
         for (int c = 0; c < NS; ++c) { acc[c] = fma_(two, k[c], acc[c]); ys[c] = fma_(hh, k[c], y[c]); }
@@ -179,7 +166,6 @@
         for (int c = 0; c < NS; ++c) { acc[c] = fma_(two, k[c], acc[c]); ys[c] = fma_(h, k[c], y[c]); }
 #pragma unroll
         for (int p = 0; p < NP; ++p) rotate(Er[p], Ei[p], rc[p], rs[p]);
-        double_phase();
         rhs(ys, k);
 #pragma unroll
         for (int c = 0; c < NS; ++c) {

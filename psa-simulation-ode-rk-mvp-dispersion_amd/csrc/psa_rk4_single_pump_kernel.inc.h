@@ -19,7 +19,7 @@
 // Wave-uniform control flow only: every branch is on a kernel argument, the loop counters or a ballot.
 //
 // What is carried is H = E/2, not E.  The sidebands need conj(E)/2 * A_p^2 and Im(A_p^2) = fma(x, y, y*x) = 2*RN(x*y) for every
-// input (the FOLD note on yaman_stage_mirrored), so with m = RN(x*y)
+// input (tests/test_fold_identity.py; DESIGN.md 3.1 item 8, history), so with m = RN(x*y)
 //     Re (conj(E)/2 * A_p^2) = H_r*Re(A_p^2) + H_i*(2m) = H_r*Re(A_p^2) + E_i*m        E = H + H: an exact doubling
 //     Im (conj(E)/2 * A_p^2) = H_r*(2m) - H_i*Re(A_p^2) = E_r*m - H_i*Re(A_p^2)
 // are the same real products, hence the same rounded numbers, and Im(A_p^2) is never formed.  The pump reads E, the sidebands

@@ -19,6 +19,8 @@
 // DP ALU accepts no quad_perm, so the exchange cannot be folded into the consuming v_fma_f64).  Per RHS evaluation:
 // 4 waves 39 instructions (6 of them moves) instead of 64; 6 waves 65 (10 moves) instead of 100.
 // Same RK4 regrouping, phase recurrence, save / NaN semantics as rk4_sweep_kernel -- see that file.
+// 4 waves: a wave whose points all start mirrored (A2 == A1, A4 == A3) does not run this stage at all but the mirrored z-loop of
+// rk4_sweep_kernel on its even lanes (see the kernel below).
 #pragma once
 #include "psa_rk4_kernel.inc.h"
 
@@ -115,6 +117,27 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_split_kernel(const SweepArgs<
     for (int j = 0; j < NL; ++j) {
         y[2 * j] = A.a0[(long long)(2 * wave_of[j]) * A.a0_ld + idx * A.a0_stride];
         y[2 * j + 1] = A.a0[(long long)(2 * wave_of[j] + 1) * A.a0_ld + idx * A.a0_stride];
+    }
+    // 4 waves: a wave whose live points all start mirrored (A2 == A1 and A4 == A3 bit for bit, all finite: each lane tests its
+    // own two waves, one ballot) takes the mirrored z-loop of rk4_sweep_kernel -- sweep_point<..., MIRROR> on the even lane
+    // of each point, the odd lane leaves.  The z-loop is issue-bound, so what counts is the wave's instruction stream, not
+    // how many of its lanes work: 154 instructions per step instead of this kernel's 183.6.  And the record is then the
+    // one-lane kernel's in every bit, whatever layout a sweep's size selects (the stage below pairs the products as
+    // A_u * A_v per lane, the one-lane kernel crosswise: on other points the two layouts agree to rounding).
+    if constexpr (NL == 2) {
+        const bool same = __builtin_bit_cast(long long, y[0]) == __builtin_bit_cast(long long, y[2]) &&
+                          __builtin_bit_cast(long long, y[1]) == __builtin_bit_cast(long long, y[3]);
+        const bool objects = !same || any_nonfinite<double, NC>(y);
+        if (__builtin_amdgcn_ballot_w64(objects) == 0) {
+            if (role) return;
+            long long idx_m = idx;            // A1 and A3 loaded again through an opaque index, as in rk4_sweep_kernel
+            asm volatile("" : "+v"(idx_m));
+            double ym[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) ym[c] = A.a0[(long long)(c < 2 ? c : c + 2) * A.a0_ld + idx_m * A.a0_stride];
+            sweep_point<double, 4, CHECK, TRAJ, BLOCK, false, LOSS, WSUM, true>(A, idx_m, ym);
+            return;
+        }
     }
     const double g = A.gamma[idx * A.gamma_stride];
     const double tg = g + g;
