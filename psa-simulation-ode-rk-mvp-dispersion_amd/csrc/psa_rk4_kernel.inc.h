@@ -8,10 +8,16 @@
 // What bounds it: FP64 vector FMA issue (16 lanes/clk/SIMD on CDNA4), NOT HBM and not MFMA:
 // a point reads 8..88 B and writes 88 B for its entire z-loop, and the RHS is an elementwise
 // complex polynomial (no contraction to tile).  So the design rules here are
-//   * minimum DP instructions per step (298 for 4 waves, 154 where waves 2 and 4 mirror 1 and 3; see the counts in DESIGN.md),
-//   * no transcendental in the steady-state loop: E(z) = 2*gamma*exp(i*dbeta*z) is carried by a
-//     complex rotation per half step and re-seeded from an exact sincos at every multiple of RESYNC steps
-//     (64 in float64: drift <= 128 multiplications ~1.4e-14, far inside the 1e-9 parity budget),
+//   * minimum DP instructions per step (288 for 4 waves, 144 where waves 2 and 4 mirror 1 and 3; see the counts in DESIGN.md),
+//   * no transcendental in the steady-state loop.  The fused float64 4-wave step (FRAME) integrates the sidebands in a frame
+//     anchored at the midpoint of each step, where the phase factor 2*d*gamma*exp(i*dbeta*(z - z_mid)) takes the same four
+//     values in every step -- lane constants, two of them real -- and the state moves to the next step's frame by one
+//     rotation of the sidebands: nothing is carried and nothing re-seeded.  Only what leaves the kernel as amplitudes (A[-1],
+//     trajectory rows) is taken out of the frame, by F(step) = exp(i*dbeta*(z_step + d)/2): one function of the absolute step
+//     index, an exact sincos at the multiples of RESYNC and one rotation per step from there, carried by the trajectory
+//     instantiations (+4 per step) and built once, where A[-1] is stored, by the others.  Six waves, float32 and the LDS
+//     variant carry E(z) = 2*gamma*exp(i*dbeta*z) by a complex rotation per half step, re-seeded from an exact sincos at
+//     every multiple of RESYNC steps (64 in float64: drift <= 128 multiplications ~1.4e-14, far inside the 1e-9 budget),
 //   * all per-lane arrays statically indexed and in VGPRs (178 for the bench instantiation: 2 waves/SIMD; capping
 //     at 168 (3 waves) or 128 (4 waves, 16 spilled) was measured no faster -- the loop is issue-bound),
 //   * wave-uniform control flow only (save stride, resync and NaN tracking never diverge),
@@ -102,10 +108,14 @@ template <> struct Phase<float> {
 // half of the stage repeats the other half (yaman_stage_mirrored).  With six waves the pumps sum over the pairs and the
 // crosswise form would cost 64 instead of 52: NW == 6 keeps the form above whatever CROSS says, and so does RK45
 // (psa_rk45.hip: its goldens pin accepted and rejected step counts).
-template <typename T, int NW, bool FUSED, bool LOSS = true, bool CROSS = false>
+//
+// REALE = true (crosswise 4 waves only; the frame-anchored step's two midpoint stages) is the same stage where the phase
+// factor is REAL: Er[0] holds it, Ei is not read, and each H = e*b is two multiplications instead of a complex product.
+template <typename T, int NW, bool FUSED, bool LOSS = true, bool CROSS = false, bool REALE = false>
 __device__ __forceinline__ void yaman_stage(const T (&a)[2 * NW], const T (&base)[2 * NW],
                                             const T (&Er)[(NW - 2) / 2], const T (&Ei)[(NW - 2) / 2], const T g,
                                             const T tg, const T ha, T (&out)[2 * NW]) {
+    static_assert(!REALE || (CROSS && NW == 4), "the real phase factor exists for the crosswise 4-wave stage");
     constexpr int NP = (NW - 2) / 2;
     T p[NW];
 #pragma unroll
@@ -128,8 +138,10 @@ __device__ __forceinline__ void yaman_stage(const T (&a)[2 * NW], const T (&base
         const T x3 = a[4], y3 = a[5], x4 = a[6], y4 = a[7];
         const T b23r = fma_(x2, x3, y2 * y3), b23i = fma_(x2, y3, -(y2 * x3));  // conj(A2)*A3
         const T b14r = fma_(x1, x4, y1 * y4), b14i = fma_(x1, y4, -(y1 * x4));  // conj(A1)*A4
-        const T h23r = fma_(Er[0], b23r, -(Ei[0] * b23i)), h23i = fma_(Er[0], b23i, Ei[0] * b23r);
-        const T h14r = fma_(Er[0], b14r, -(Ei[0] * b14i)), h14i = fma_(Er[0], b14i, Ei[0] * b14r);
+        const T h23r = REALE ? Er[0] * b23r : fma_(Er[0], b23r, -(Ei[0] * b23i));
+        const T h23i = REALE ? Er[0] * b23i : fma_(Er[0], b23i, Ei[0] * b23r);
+        const T h14r = REALE ? Er[0] * b14r : fma_(Er[0], b14r, -(Ei[0] * b14i));
+        const T h14i = REALE ? Er[0] * b14i : fma_(Er[0], b14i, Ei[0] * b14r);
         // pump1: (ha + i g1) A1 + i H23 A4 ;  pump2: (ha + i g2) A2 + i H14 A3
         out[0] = fma_(-y4, h23r, fma_(-x4, h23i, link(-gj[0], y1, 0)));
         out[1] = fma_(x4, h23r, fma_(-y4, h23i, link(gj[0], x1, 1)));
@@ -187,9 +199,10 @@ __device__ __forceinline__ void yaman_stage(const T (&a)[2 * NW], const T (&base
 // (a power above 2^1022); there the general form gives inf and this one a finite gs, but gj * max(|x|, |y|) >= g * 2^1532
 // overflows all the same and the step ends non-finite in both -- first_bad_step is the same, only the inf / NaN pattern of
 // a state that has already failed may differ.
-// 32 DP instructions instead of 64 (p: 4, gs: 2, g_j: 2, b: 4, h: 4, four 4-deep chains: 16), in every stage of the step.
+// 32 DP instructions instead of 64 (p: 4, gs: 2, g_j: 2, b: 4, h: 4, four 4-deep chains: 16), in every stage of the step;
+// 30 with REALE (h = Er*b: 2), as in yaman_stage.
 // FUSED = false is the plain dA/dz, as in yaman_stage (the float32 steps).
-template <typename T, bool LOSS = true, bool FUSED = true>
+template <typename T, bool LOSS = true, bool FUSED = true, bool REALE = false>
 __device__ __forceinline__ void yaman_stage_mirrored(const T (&a)[4], const T (&base)[4], const T Er, const T Ei, const T g,
                                                      const T sg, const T ha, T (&out)[4]) {
     const T x1 = a[0], y1 = a[1], xs = a[2], ys = a[3];
@@ -201,7 +214,8 @@ __device__ __forceinline__ void yaman_stage_mirrored(const T (&a)[4], const T (&
         else return FUSED ? fma_(gsig, v, base[c]) : gsig * v;
     };
     const T br = fma_(x1, xs, y1 * ys), bi = fma_(x1, ys, -(y1 * xs));  // conj(A1)*A3
-    const T hr = fma_(Er, br, -(Ei * bi)), hi = fma_(Er, bi, Ei * br);
+    const T hr = REALE ? Er * br : fma_(Er, br, -(Ei * bi));
+    const T hi = REALE ? Er * bi : fma_(Er, bi, Ei * br);
     out[0] = fma_(-ys, hr, fma_(-xs, hi, link(-g1, y1, 0)));
     out[1] = fma_(xs, hr, fma_(-ys, hi, link(g1, x1, 1)));
     out[2] = fma_(-y1, hr, fma_(x1, hi, link(-g3, ys, 2)));
@@ -251,7 +265,7 @@ __device__ __forceinline__ bool any_nonfinite(const T (&y)[NC]) {
 // points whose a0 has A2 == A1 and A4 == A3 bit for bit (every scenario of the reference: equal pumps, equal signal and
 // idler seeds, zero phases).  The step, the rotations, the re-seeds, the event loop, the checkpoint and replay, the block
 // test and the tail are the one text below for both; the outputs are the full record, waves 2 and 4 written from the
-// registers of waves 1 and 3.  154 DP instructions per step instead of 298 (4 * 32 + 12 + 4 + 10).
+// registers of waves 1 and 3.  144 DP instructions per step instead of 288 (32 + 30 + 30 + 32 stages, 12 + 4, 4 to move the frame).
 template <typename T, int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS, bool LOSS, bool WSUM, bool MIRROR>
 __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long long idx, T (&y)[MIRROR ? NW : 2 * NW]) {
     static_assert(!MIRROR || (sizeof(T) == 8 && NW == 4 && !LDS), "the mirrored body exists for the fused float64 4-wave step");
@@ -278,7 +292,10 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
     const T g_h = h * g, tg_h = h * tg, ha_h = h * ha;
     const T third = T(1.0 / 3.0);
     constexpr bool FUSE = (sizeof(T) == 8) && !LDS;   // fused-stage step: float64 register variant only
-    const T e_amp = FUSE ? tg_d : tg;  // modulus of the carried phase factor: 2*d*gamma (fused) or 2*gamma
+    const T e_amp = FUSE ? tg_d : tg;  // modulus of the phase factor: 2*d*gamma (fused) or 2*gamma
+    // FRAME: the fused 4-wave step integrates the sidebands in a frame anchored at the midpoint of each step (rk4_step_on)
+    // and carries no phase factor at all
+    constexpr bool FRAME = FUSE && NW == 4;
 
     T rc[NP], rs[NP], Er[NP], Ei[NP];  // half-step rotator and the running 2*gamma*exp(i dbeta z)
 #pragma unroll
@@ -287,6 +304,38 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
         Er[p] = e_amp;
         Ei[p] = T(0);
     }
+    // FRAME: the phase factor at the two ends of a step, e*conj(r) and e*r = (ec, -+es); e (= tg_d) and 2e (= tg_h) in between
+    const T ec = e_amp * rc[0], es = e_amp * rs[0];
+    // F(step) = exp(i*dbeta*(z_step + d)/2): what the sidebands of the frame of step `step` carry over the record's.
+    // ONE function of the absolute step index -- an exact sincos at the multiples of RESYNC, one rotation by r per step
+    // from there -- so that a row is the same bits whether F was carried through the loop (TRAJ) or built for that row.
+    auto frame_seed = [&](const int step, T &fc, T &fs) {   // step a multiple of RESYNC
+        Phase<T>::eval(dbd[0] * (0.5 * fma_((double)step, hd, 0.5 * hd)), fc, fs);
+    };
+    auto frame_at = [&](const int step, T &fc, T &fs) {
+        const int k = step % RESYNC;
+        frame_seed(step - k, fc, fs);
+#pragma nounroll
+        for (int q = 0; q < k; ++q) rotate(fc, fs, rc[0], rs[0]);
+    };
+    // record <- frame: pumps as they are, sidebands times conj(F), one expression for both (the exchange still permutes).
+    // The summaries are moduli of the FRAME's sidebands and must be the record's to a few ulp (|A_j|^2 of a row against
+    // p_wave_end / p_wave_max: 1e-15).  F carried k steps from a seed is off unit modulus by k roundings of r that all have one
+    // sign (|r| - 1 is a constant of the lane, up to 5.5e-17): up to 7e-15 in |F|^2 before the next seed.  So the F that is
+    // applied is renormalised to first order, F * (1 - (|F|^2 - 1)/2), the defect formed without cancellation error; what is
+    // left is its square, ~1e-29.  A function of F alone: carried or rebuilt, the row has the same bits.
+    auto leave_frame = [&](const T (&b)[NS], const T fc, const T fs, T (&a)[NS]) {
+        const T ce = T(-0.5) * fma_(fs, fs, fma_(fc, fc, T(-1)));
+        const T nc = fma_(fc, ce, fc), ns = fma_(fs, ce, fs);
+#pragma unroll
+        for (int c = 0; c < SIG; ++c) a[c] = b[c];
+#pragma unroll
+        for (int c = SIG; c < NS; c += 2) {
+            a[c] = fma_(b[c], nc, b[c + 1] * ns);
+            a[c + 1] = fma_(b[c + 1], nc, -(b[c] * ns));
+        }
+    };
+    T Fc = T(1), Fs = T(0);            // FRAME && TRAJ: F of the step about to run, carried through the loop
 
     T pe = fma_(y[SIG], y[SIG], y[SIG + 1] * y[SIG + 1]);  // |A_sig|^2 at the last saved row (z = 0 is a saved row)
     T pm = pe;                             // np.max over saved rows
@@ -296,9 +345,9 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
 #pragma unroll
         for (int j = 0; j < NWS; ++j) pwm[j] = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
     }
-    auto store_a_end = [&]() {             // A[-1]; with WSUM also |A_j|^2 of that row
+    auto store_a_end = [&](const T (&a)[NS]) {   // A[-1] (a: y in the record's variables); with WSUM also |A_j|^2 of that row, from y
 #pragma unroll
-        for (int c = 0; c < NC; ++c) A.a_end[(long long)c * N + idx] = y[at(c)];
+        for (int c = 0; c < NC; ++c) A.a_end[(long long)c * N + idx] = a[at(c)];
         if constexpr (WSUM) {
 #pragma unroll
             for (int j = 0; j < NW; ++j) {
@@ -320,14 +369,39 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
     using Pair = typename PairOf<T>::type;
     const long long LD = A.traj_ld;   // points per (row, wave) region: N, or N padded off a power of two (psa_traj_ld)
     const unsigned lane_off = (unsigned)idx * (unsigned)sizeof(Pair);
-    auto store_traj_row = [&](const int r) {
+    auto store_traj_row_of = [&](const int r, const T (&a)[NS]) {
         const char *rowb = reinterpret_cast<const char *>(A.traj) + (long long)r * NW * LD * (long long)sizeof(Pair);
 #pragma unroll
         for (int j = 0; j < NW; ++j)
-            store_pair_nt(rowb + (long long)j * LD * (long long)sizeof(Pair), lane_off, Pair{y[at(2 * j)], y[at(2 * j + 1)]});
+            store_pair_nt(rowb + (long long)j * LD * (long long)sizeof(Pair), lane_off, Pair{a[at(2 * j)], a[at(2 * j + 1)]});
     };
-    if constexpr (TRAJ) store_traj_row(0);
-    if (n_rows == 0) store_a_end();
+    auto store_traj_row = [&](const int r) {     // FRAME: F is F(step) of the row's step
+        if constexpr (FRAME) {
+            T a[NS];
+            leave_frame(y, Fc, Fs, a);
+            store_traj_row_of(r, a);
+        } else {
+            store_traj_row_of(r, y);
+        }
+    };
+    auto store_a_end_at = [&](const int step) {  // A[-1] = the state after `step` steps
+        if constexpr (FRAME) {
+            T a[NS], fc = Fc, fs = Fs;
+            if constexpr (!TRAJ) frame_at(step, fc, fs);
+            leave_frame(y, fc, fs, a);
+            store_a_end(a);
+        } else {
+            store_a_end(y);
+        }
+    };
+    // z = 0 is a0 as given: row 0, and A[-1] when no row follows, are written before the frame is entered
+    if constexpr (TRAJ) store_traj_row_of(0, y);
+    if (n_rows == 0) store_a_end(y);
+    if constexpr (FRAME) {                       // B = A * F(0) on the sidebands
+        frame_seed(0, Fc, Fs);
+#pragma unroll
+        for (int c = SIG; c < NS; c += 2) rotate(y[c], y[c + 1], Fc, Fs);
+    }
 
     // LDS-staged variant: sm_k[stage][component][lane] and sm_y[component][lane] (volatile: the traffic is the point)
     __shared__ T sm_store[LDS ? 5 * NC * BLOCK : 1];
@@ -370,45 +444,75 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
         }
     };
 
-    // ---- one classic RK4 step (integrators.py:54-59) in 298 DP instructions (4 waves; 154 on the mirrored state).
+    // ---- one classic RK4 step (integrators.py:54-59) in 288 DP instructions (4 waves; 144 on the mirrored state; six
+    // waves, which carry the phase factor, 468).
     // Each stage's axpy is folded into the RHS chains (yaman_stage, FUSED): with d = h/2
     //     Y2 = y + d*f(z, y)          Y3 = y + d*f(z+d, Y2)          Y4 = y + 2d*f(z+d, Y3)
     //     t  = Y2 + 2*Y3 + Y4 - 4*y                 ( = d*k1 + 2d*k2 + 2d*k3 )
     //     D  = t + d*f(z+h, Y4)                     ( = d*(k1 + 2*k2 + 2*k3 + k4) )
     //     y <- y + D/3                              ( = y + h/6*(k1 + 2*k2 + 2*k3 + k4) )
     // which is the reference's k1..k4 combination regrouped (no change of variables, same truncation error; the
-    // regrouping costs ~1 ulp(y) of rounding noise per step, ~1e-13 after 1e5 steps).  (Ed_r, Ed_i) carries
-    // 2*d*gamma*exp(i*dbeta*z): on entry at z_step, on exit rotated to z_step + h.
+    // regrouping costs ~1 ulp(y) of rounding noise per step, ~1e-13 after 1e5 steps).  Six waves: (Er, Ei) carries
+    // 2*d*gamma*exp(i*dbeta*z), on entry at z_step, on exit rotated to z_step + h.
     // MIRROR: the same step on the half state, every stage yaman_stage_mirrored.
-    auto stage = [&](const T (&a)[NS], const T (&base)[NS], const T (&er)[NP], const T (&ei)[NP], const T g_c, const T tg_c,
-                     const T ha_c, T (&out)[NS]) {
-        if constexpr (MIRROR) yaman_stage_mirrored<T, LOSS, true>(a, base, er[0], ei[0], g_c, tg_c + tg_c, ha_c, out);
-        else yaman_stage<T, NW, true, LOSS, true>(a, base, er, ei, g_c, tg_c, ha_c, out);
+    auto stage = [&](auto reale, const T (&a)[NS], const T (&base)[NS], const T (&er)[NP], const T (&ei)[NP], const T g_c,
+                     const T tg_c, const T ha_c, T (&out)[NS]) {
+        constexpr bool RE = decltype(reale)::value;
+        if constexpr (MIRROR) yaman_stage_mirrored<T, LOSS, true, RE>(a, base, er[0], ei[0], g_c, tg_c + tg_c, ha_c, out);
+        else yaman_stage<T, NW, true, LOSS, true, RE>(a, base, er, ei, g_c, tg_c, ha_c, out);
     };
+    constexpr std::false_type cplx{};
+    constexpr std::true_type real{};
+    // FRAME (4 waves): 288 (144 mirrored).  A Runge-Kutta step is exactly invariant under a CONSTANT linear change of
+    // variables, so the step is taken on B = diag(1, 1, tau, tau) * A with tau = exp(+i*dbeta*(z + d)/2) fixed over the step:
+    // the equations keep their form with the phase factor 2*d*gamma*exp(i*dbeta*(z' - (z + d))), which is e*conj(r), e, e, e*r
+    // at the four stages of EVERY step (stage 3 takes it doubled, with its coefficient h) -- lane constants, real in the
+    // middle -- and nothing is carried or re-seeded.  Moving
+    // from the frame of one step to the next multiplies the sidebands by r = exp(i*dbeta*d), the same expression for both
+    // (so the exchange of the members still permutes the outputs bit for bit).  Between steps the map is linear and exact:
+    // method, grid and truncation error are the reference's, only rounding moves (the modulus of the rounded r, <= 5.5e-17
+    // off one, now accumulates in the sidebands: ~5e-12 after 1e5 steps).  The record leaves the frame by conj(F(step)).
     auto rk4_step_on = [&](T (&y)[NS], T (&Er)[NP], T (&Ei)[NP]) {
         T Y2[NS], Y3[NS], Y4[NS], t[NS], D[NS];
-        stage(y, y, Er, Ei, g_d, tg_d, ha_d, Y2);  // Y2 = y + d k1
+        if constexpr (FRAME) {
+            const T c1[NP] = {ec}, s1[NP] = {-es}, s4[NP] = {es}, e1[NP] = {tg_d}, e2[NP] = {tg_h};
+            stage(cplx, y, y, c1, s1, g_d, tg_d, ha_d, Y2);    // Y2 = y + d k1      e*conj(r)
+            stage(real, Y2, y, e1, e1, g_d, tg_d, ha_d, Y3);   // Y3 = y + d k2      e
+            stage(real, Y3, y, e2, e2, g_h, tg_h, ha_h, Y4);   // Y4 = y + h k3      2e
+#pragma unroll
+            for (int c = 0; c < NS; ++c) t[c] = fma_(T(2), Y3[c], fma_(T(-4), y[c], Y2[c])) + Y4[c];
+            stage(cplx, Y4, t, c1, s4, g_d, tg_d, ha_d, D);    // D = t + d k4       e*r
+#pragma unroll
+            for (int c = 0; c < NS; ++c) y[c] = fma_(D[c], third, y[c]);
+#pragma unroll
+            for (int c = SIG; c < NS; c += 2) rotate(y[c], y[c + 1], rc[0], rs[0]);   // into the frame of the next step
+            return;
+        }
+        stage(cplx, y, y, Er, Ei, g_d, tg_d, ha_d, Y2);  // Y2 = y + d k1
 #pragma unroll
         for (int p = 0; p < NP; ++p) rotate(Er[p], Ei[p], rc[p], rs[p]);  // z + h/2
-        stage(Y2, y, Er, Ei, g_d, tg_d, ha_d, Y3);  // Y3 = y + d k2
+        stage(cplx, Y2, y, Er, Ei, g_d, tg_d, ha_d, Y3);  // Y3 = y + d k2
         T E2r[NP], E2i[NP];
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
             E2r[p] = Er[p] + Er[p];
             E2i[p] = Ei[p] + Ei[p];
         }
-        stage(Y3, y, E2r, E2i, g_h, tg_h, ha_h, Y4);  // Y4 = y + h k3
+        stage(cplx, Y3, y, E2r, E2i, g_h, tg_h, ha_h, Y4);  // Y4 = y + h k3
 #pragma unroll
         for (int c = 0; c < NS; ++c) t[c] = fma_(T(2), Y3[c], fma_(T(-4), y[c], Y2[c])) + Y4[c];
 #pragma unroll
         for (int p = 0; p < NP; ++p) rotate(Er[p], Ei[p], rc[p], rs[p]);  // z + h
-        stage(Y4, t, Er, Ei, g_d, tg_d, ha_d, D);  // D = t + d k4
+        stage(cplx, Y4, t, Er, Ei, g_d, tg_d, ha_d, D);  // D = t + d k4
 #pragma unroll
         for (int c = 0; c < NS; ++c) y[c] = fma_(D[c], third, y[c]);
     };
     // The per-step finite test of the reference (integrators.py:132-135) is NOT in the float64 step: CHECK_EXACT finds the
     // exact index by REPLAY (below) -- the forward pass tests once per saved row, like CHECK_BLOCK.
-    auto rk4_step_reg = [&](const int) { rk4_step_on(y, Er, Ei); };
+    auto rk4_step_reg = [&](const int) {
+        rk4_step_on(y, Er, Ei);
+        if constexpr (FRAME && TRAJ) rotate(Fc, Fs, rc[0], rs[0]);   // F of the next step (re-seeded where a row is due)
+    };
 
     // ---- float32: the classic low-storage form (y, y_stage, accumulator; 320 instructions).  The regrouping above
     // quantises every stage increment to ulp(y); harmless at 1e-16 but measured 17x worse at float32 (6.7e-3 vs
@@ -483,23 +587,25 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
     auto seed_phase = [&](const int step) { seed_phase_on(step, Er, Ei); };
 
     // ---- CHECK_EXACT for the float64 register variant: exact first_bad_step at the price of the block test.  The state at
-    // the last test point (y and the carried phase factor) is kept; when a test finds a lane of the
+    // the last test point (y, and with six waves the carried phase factor) is kept; when a test finds a lane of the
     // wave newly non-finite, the steps since then are REPLAYED on a copy with the reference's per-step test
     // (integrators.py:132-135).  The replay repeats the forward pass operation for operation (same chunks, same re-seeds,
     // same FMA sequence), so it reproduces this kernel's own trajectory bit for bit and the index it finds is exact.  Only
-    // waves with a failing lane ever take the (wave-uniform) branch: +20 VGPRs (+12 on the mirrored state), no instruction in the steady-state loop
+    // waves with a failing lane ever take the (wave-uniform) branch: +16 VGPRs (+8 on the mirrored state), no instruction in the steady-state loop
     // (the per-step test cost 9.9 of 310.6 instructions per step, profiles/r03_c2x_pmc.csv).
     constexpr bool REPLAY = FUSE && CHECK == CHECK_EXACT;
-    T y_chk[REPLAY ? NS : 1], Er_chk[REPLAY ? NP : 1], Ei_chk[REPLAY ? NP : 1];
+    T y_chk[REPLAY ? NS : 1], Er_chk[REPLAY && !FRAME ? NP : 1], Ei_chk[REPLAY && !FRAME ? NP : 1];   // FRAME carries no phase factor
     int i_chk = 0;
     auto checkpoint = [&](const int step) {
         if constexpr (REPLAY) {
 #pragma unroll
             for (int c = 0; c < NS; ++c) y_chk[c] = y[c];
+            if constexpr (!FRAME) {
 #pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                Er_chk[p] = Er[p];
-                Ei_chk[p] = Ei[p];
+                for (int p = 0; p < NP; ++p) {
+                    Er_chk[p] = Er[p];
+                    Ei_chk[p] = Ei[p];
+                }
             }
             i_chk = step;
         }
@@ -513,13 +619,15 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
                 for (int c = 0; c < NS; ++c) yy[c] = y_chk[c];
 #pragma unroll
                 for (int p = 0; p < NP; ++p) {
-                    er[p] = Er_chk[p];
-                    ei[p] = Ei_chk[p];
+                    er[p] = FRAME ? T(0) : Er_chk[FRAME ? 0 : p];
+                    ei[p] = FRAME ? T(0) : Ei_chk[FRAME ? 0 : p];
                 }
                 int ii = i_chk;
                 while (ii < i_now) {
-                    if (ii % RESYNC == 0) seed_phase_on(ii, er, ei);   // the forward pass seeds at the same steps
-                    const int to_seed = RESYNC - ii % RESYNC;
+                    if constexpr (!FRAME) {
+                        if (ii % RESYNC == 0) seed_phase_on(ii, er, ei);   // the forward pass seeds at the same steps
+                    }
+                    const int to_seed = FRAME ? i_now - ii : RESYNC - ii % RESYNC;   // FRAME: the step has no seeds to repeat
                     const int e = (i_now - ii > to_seed) ? ii + to_seed : i_now;
 #pragma nounroll
                     for (int st = ii; st < e; ++st) {
@@ -549,12 +657,15 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
             };
             int i = 0;
             while (i < n_run) {                       // n_run == n_steps == n_rows
-                seed_phase(i);
+                if constexpr (!FRAME) seed_phase(i);
                 const int end = (n_run - i > RESYNC) ? i + RESYNC : n_run;
-                for (; i + 2 <= end; i += 2) {
+                for (; i + 2 <= end; i += 2) {        // i is even: only the second row of a trip can fall on a multiple of RESYNC
                     rk4_step(i);
                     save_row(i + 1);
                     rk4_step(i + 1);
+                    if constexpr (FRAME) {
+                        if ((i + 2) % RESYNC == 0) frame_seed(i + 2, Fc, Fs);
+                    }
                     save_row(i + 2);
                 }
                 if (i < end) {
@@ -564,8 +675,15 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
                 }
             }
             if (pe != pe) pm = pe;                    // np.max over the saved rows propagates NaN
+            if constexpr (FRAME) {
+                T a[NS];
+                leave_frame(y, Fc, Fs, a);            // F(n_run), as the last row's
 #pragma unroll
-            for (int c = 0; c < NC; ++c) A.a_end[(long long)c * N + idx] = y[at(c)];
+                for (int c = 0; c < NC; ++c) A.a_end[(long long)c * N + idx] = a[at(c)];
+            } else {
+#pragma unroll
+                for (int c = 0; c < NC; ++c) A.a_end[(long long)c * N + idx] = y[at(c)];
+            }
             write_summary();
             return;
         }
@@ -577,15 +695,20 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
     // Seeds fall on the ABSOLUTE grid i = 0, RESYNC, 2*RESYNC, ... whatever save_every is (the save_every == 1 loop above does
     // the same), so the computed trajectory does not depend on which rows are saved -- as upstream, where the stride only
     // selects rows (integrators.py:137-140): A[-1] at any stride equals the same row of the every-step run bit for bit.
+    // FRAME has no phase factor to seed.  With a trajectory its F is seeded on the same grid, AFTER the steps that reach a
+    // multiple of RESYNC and before the row that may be due there (F(step) is seeded, not carried, at the multiples);
+    // without one there is no seed event at all and F is built where A[-1] is stored (store_a_end_at).
     int i = 0;
     int row = 0;
     checkpoint(0);
     int next_save = (n_rows > 0) ? se : 0x7fffffff;
-    int next_seed = 0;
+    int next_seed = !FRAME ? 0 : ((TRAJ && n_run >= RESYNC) ? RESYNC : 0x7fffffff);
     while (i < n_run) {
-        if (i == next_seed) {          // wave-uniform: exact re-seed of the phase recurrence at z_i = i*h
-            seed_phase(i);
-            next_seed = (n_run - i > RESYNC) ? i + RESYNC : 0x7fffffff;   // no overflow near 2^31 steps
+        if constexpr (!FRAME) {
+            if (i == next_seed) {          // wave-uniform: exact re-seed of the phase recurrence at z_i = i*h
+                seed_phase(i);
+                next_seed = (n_run - i > RESYNC) ? i + RESYNC : 0x7fffffff;   // no overflow near 2^31 steps
+            }
         }
         int end = n_run < next_seed ? n_run : next_seed;
         end = end < next_save ? end : next_save;
@@ -601,6 +724,12 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
             if (j < m) rk4_step(i + j);
         }
         i = end;
+        if constexpr (FRAME && TRAJ) {
+            if (i == next_seed) {          // wave-uniform: F(i) exactly
+                frame_seed(i, Fc, Fs);
+                next_seed = (n_run - i >= RESYNC) ? i + RESYNC : 0x7fffffff;
+            }
+        }
         if (i == next_save) {  // (i % save_every == 0), integrators.py:137 -- wave-uniform
             ++row;
             pe = fma_(y[SIG], y[SIG], y[SIG + 1] * y[SIG + 1]);
@@ -618,7 +747,7 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
             exact_test(i);
             if constexpr (TRAJ) store_traj_row(row);
             if (row == n_rows) {  // A[-1]: the last saved row, not necessarily z_max (R8)
-                store_a_end();
+                store_a_end_at(i);
                 next_save = 0x7fffffff;
             } else {
                 next_save += se;

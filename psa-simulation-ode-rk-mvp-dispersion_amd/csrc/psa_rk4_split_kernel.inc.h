@@ -121,7 +121,7 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_split_kernel(const SweepArgs<
     // 4 waves: a wave whose live points all start mirrored (A2 == A1 and A4 == A3 bit for bit, all finite: each lane tests its
     // own two waves, one ballot) takes the mirrored z-loop of rk4_sweep_kernel -- sweep_point<..., MIRROR> on the even lane
     // of each point, the odd lane leaves.  The z-loop is issue-bound, so what counts is the wave's instruction stream, not
-    // how many of its lanes work: 154 instructions per step instead of this kernel's 183.6.  And the record is then the
+    // how many of its lanes work: 144 instructions per step instead of this kernel's 183.6.  And the record is then the
     // one-lane kernel's in every bit, whatever layout a sweep's size selects (the stage below pairs the products as
     // A_u * A_v per lane, the one-lane kernel crosswise: on other points the two layouts agree to rounding).
     if constexpr (NL == 2) {
