@@ -34,14 +34,14 @@
 // No divergent control flow surrounds an exchange (DPP reads lanes that EXEC has disabled): the non-finite test is an
 // all-reduce followed by a ballot, as in rk4_sweep_quad_kernel, and loads and stores are the only lane-dependent branches.
 //
-// Same RK4 regrouping, phase recurrence with seeds on the absolute RESYNC grid, event-driven z-loop and save / NaN
-// semantics as rk4_sweep_kernel (see that file):  CHECK_NONE: first_bad_step = -1, NaNs propagate;  CHECK_BLOCK: the last
-// step of the first non-finite save block (or of the unsaved tail);  CHECK_EXACT: the exact step, found by replaying the
-// failing block from the last test point with a per-step test -- and if that replay should stay finite (it repeats the
-// forward pass operation for operation, so it should not), `bad` becomes the block-mode answer rather than staying -1.
+// The regrouped RK4 step, the phase recurrence with seeds on the absolute RESYNC grid, the event-driven z-loop, the save /
+// NaN semantics and the replay that finds the exact first_bad_step are the shared ones of psa_rk4_carried.inc.h (see that
+// file).  `bad` and the non-finite test's result are the same in the L lanes of a point, so no exchange runs with part of
+// a point masked off.
 //
 // Out of scope: trajectory rows, float32, LDS staging, RK45, chains.
 #pragma once
+#include "psa_rk4_carried.inc.h"
 #include "psa_rk4_quad_kernel.inc.h"
 
 namespace psa {
@@ -101,7 +101,6 @@ __device__ __forceinline__ void pairs_stage(const double (&a)[8], const double (
 
 template <int L, int CHECK, int BLOCK, bool LOSS>
 __global__ void __launch_bounds__(BLOCK) rk4_sweep_pairs_kernel(const PairsArgs A) {
-    constexpr int RESYNC = Phase<double>::RESYNC;
     const long long gid = (long long)blockIdx.x * BLOCK + threadIdx.x;
     const long long idx = gid / L;          // sweep point: its L lanes share one
     const int r = (int)(gid % L);           // = the pair this lane holds
@@ -119,25 +118,16 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_pairs_kernel(const PairsArgs 
         a[4 + c] = lit ? v : 0.0;
     }
     const double g = A.gamma[idx * A.gamma_stride];
-    const double tg = g + g;
     const double ha = -0.5 * A.alpha[idx * A.alpha_stride];
     const double db = A.dbeta[(long long)rr * N + idx];
     const double dbd = lit ? db : 0.0;
-
-    const double hd = A.z_max / (double)A.n_steps;
-    const double hh = 0.5 * hd;
-    const double g_d = hh * g, tg_d = hh * tg, ha_d = hh * ha;
-    const double g_h = hd * g, tg_h = hd * tg, ha_h = hd * ha;
-    const double third = 1.0 / 3.0;
-    const double e_amp = tg_d;
-
-    double rc, rs, Er = e_amp, Ei = 0.0;
-    Phase<double>::eval(dbd * (0.5 * hd), rc, rs);
+    const CarriedConsts K = carried_consts(g, ha, dbd, A.z_max, A.n_steps);
+    const double e_amp = K.tg_d;
+    double Er = e_amp, Ei = 0.0;
 
     double pm[4];                           // np.max of |A_j|^2 over saved rows (z = 0 is one): p1, p2, s, i
 #pragma unroll
     for (int j = 0; j < 4; ++j) pm[j] = fma_(a[2 * j], a[2 * j], a[2 * j + 1] * a[2 * j + 1]);
-    long long bad = -1;
     auto nonfinite_on = [&](const double (&v)[8]) -> bool {   // any component of the POINT non-finite
         double t = 0.0;
 #pragma unroll
@@ -145,10 +135,6 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_pairs_kernel(const PairsArgs 
         t = pairs_allreduce<L>(t);
         return t != t;
     };
-
-    const int se = A.save_every;
-    const int n_rows = A.n_steps / se;
-    const int n_run = (CHECK != CHECK_NONE) ? A.n_steps : n_rows * se;
 
     // lane 0 writes the pumps (waves 0, 1), lane r < K its pair (waves 2 + 2r, 3 + 2r)
     auto store_a_end = [&]() {
@@ -166,130 +152,34 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_pairs_kernel(const PairsArgs 
                 A.p_wave_end[(long long)(2 * r + j) * N + idx] = fma_(a[2 * j], a[2 * j], a[2 * j + 1] * a[2 * j + 1]);
         }
     };
-    auto write_summary = [&]() {
-        if (r == 0) {
-            A.p_wave_max[idx] = pm[0];
-            A.p_wave_max[N + idx] = pm[1];
-            A.first_bad[idx] = bad;
-        }
-        if (lit) {
-            A.p_wave_max[(long long)(2 * r + 2) * N + idx] = pm[2];
-            A.p_wave_max[(long long)(2 * r + 3) * N + idx] = pm[3];
-        }
-    };
-    if (n_rows == 0) store_a_end();
+    if (A.n_steps / A.save_every == 0) store_a_end();   // no saved row after z = 0
 
-    // one classic RK4 step, regrouped as in rk4_sweep_kernel; (Er, Ei) enters at z_step and leaves rotated to z_step + h
-    auto rk4_step_on = [&](double (&y)[8], double &er, double &ei) {
-        double Y2[8], Y3[8], Y4[8], t[8], D[8];
-        pairs_stage<L, LOSS>(y, y, er, ei, g_d, tg_d, ha_d, Y2);
-        rotate(er, ei, rc, rs);  // z + h/2
-        pairs_stage<L, LOSS>(Y2, y, er, ei, g_d, tg_d, ha_d, Y3);
-        pairs_stage<L, LOSS>(Y3, y, er + er, ei + ei, g_h, tg_h, ha_h, Y4);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) t[c] = fma_(2.0, Y3[c], fma_(-4.0, y[c], Y2[c])) + Y4[c];
-        rotate(er, ei, rc, rs);  // z + h
-        pairs_stage<L, LOSS>(Y4, t, er, ei, g_d, tg_d, ha_d, D);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) y[c] = fma_(D[c], third, y[c]);
+    auto stage = [&](auto full, const double (&y)[8], const double (&base)[8], const double er, const double ei, double (&out)[8]) {
+        if constexpr (decltype(full)::value) pairs_stage<L, LOSS>(y, base, er, ei, K.g_h, K.tg_h, K.ha_h, out);
+        else pairs_stage<L, LOSS>(y, base, er, ei, K.g_d, K.tg_d, K.ha_d, out);
     };
-    auto rk4_step = [&]() { rk4_step_on(a, Er, Ei); };
-    auto seed_on = [&](const int step, double &er, double &ei) {
-        double c, s;
-        Phase<double>::eval(dbd * ((double)step * hd), c, s);
-        er = e_amp * c;
-        ei = e_amp * s;
-    };
-
-    // CHECK_EXACT by replay of the failing block (see rk4_sweep_kernel).  The branch is wave-uniform (a ballot), `bad` and
-    // the test's result are the same in the L lanes of a point: no exchange runs with part of a point masked off.
-    constexpr bool REPLAY = CHECK == CHECK_EXACT;
-    double a_chk[REPLAY ? 8 : 1], Er_chk = Er, Ei_chk = Ei;
-    int i_chk = 0;
-    auto checkpoint = [&](const int step) {
-        if constexpr (REPLAY) {
+    auto step_on = [&](double (&y)[8], double &er, double &ei) { carried_step<8>(y, er, ei, K.rc, K.rs, stage); };
+    auto seed_on = [&](const int step, double &er, double &ei) { carried_seed(e_amp, dbd, K.hd, step, er, ei); };
+    auto summarise = [&]() {
 #pragma unroll
-            for (int c = 0; c < 8; ++c) a_chk[c] = a[c];
-            Er_chk = Er;
-            Ei_chk = Ei;
-            i_chk = step;
+        for (int w = 0; w < 4; ++w) {
+            const double pw = fma_(a[2 * w], a[2 * w], a[2 * w + 1] * a[2 * w + 1]);
+            pm[w] = (pw > pm[w] || pw != pw) ? pw : pm[w];   // np.max propagates NaN
         }
     };
-    auto exact_test = [&](const int i_now) {
-        if constexpr (REPLAY) {
-            const bool now_bad = nonfinite_on(a);
-            const bool newly_bad = bad < 0 && now_bad;
-            if (__builtin_amdgcn_ballot_w64(newly_bad) != 0) {
-                double yy[8], er = Er_chk, ei = Ei_chk;
-#pragma unroll
-                for (int c = 0; c < 8; ++c) yy[c] = a_chk[c];
-                int ii = i_chk;
-                while (ii < i_now) {
-                    if (ii % RESYNC == 0) seed_on(ii, er, ei);
-                    const int to_seed = RESYNC - ii % RESYNC;
-                    const int e = (i_now - ii > to_seed) ? ii + to_seed : i_now;
-#pragma nounroll
-                    for (int st = ii; st < e; ++st) {
-                        rk4_step_on(yy, er, ei);
-                        const bool nf = nonfinite_on(yy);
-                        if (bad < 0 && nf) bad = st;
-                    }
-                    ii = e;
-                }
-                if (newly_bad && bad < 0) bad = i_now - 1;   // the replay stayed finite: the block-mode answer
-            }
-            checkpoint(i_now);
-        }
+    auto save_row = [&](const int, const bool last) {
+        if (last) store_a_end();
     };
-
-    // ---- z-loop, event driven, seeds on the absolute grid i = 0, RESYNC, ... (see rk4_sweep_kernel)
-    int i = 0, row = 0;
-    int next_save = (n_rows > 0) ? se : 0x7fffffff;
-    int next_seed = 0;
-    checkpoint(0);
-    while (i < n_run) {
-        if (i == next_seed) {
-            seed_on(i, Er, Ei);
-            next_seed = (n_run - i > RESYNC) ? i + RESYNC : 0x7fffffff;
-        }
-        int end = n_run < next_seed ? n_run : next_seed;
-        end = end < next_save ? end : next_save;
-        const int m = end - i;
-        int j = 0;
-        for (; j + 2 <= m; j += 2) {
-            rk4_step();
-            rk4_step();
-        }
-        if (j < m) rk4_step();
-        i = end;
-        if (i == next_save) {
-            ++row;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const double pw = fma_(a[2 * w], a[2 * w], a[2 * w + 1] * a[2 * w + 1]);
-                pm[w] = (pw > pm[w] || pw != pw) ? pw : pm[w];   // np.max propagates NaN
-            }
-            if constexpr (CHECK == CHECK_BLOCK) {
-                const bool nf = nonfinite_on(a);
-                if (bad < 0 && nf) bad = i - 1;
-            }
-            exact_test(i);
-            if (row == n_rows) {
-                store_a_end();
-                next_save = 0x7fffffff;
-            } else {
-                next_save += se;
-            }
-        }
+    const long long bad = carried_event_loop<CHECK, 2>(a, Er, Ei, A.n_steps, A.save_every, step_on, seed_on, nonfinite_on, summarise, save_row);
+    if (r == 0) {
+        A.p_wave_max[idx] = pm[0];
+        A.p_wave_max[N + idx] = pm[1];
+        A.first_bad[idx] = bad;
     }
-    if constexpr (CHECK == CHECK_BLOCK) {
-        if (n_run > 0) {
-            const bool nf = nonfinite_on(a);
-            if (bad < 0 && nf) bad = n_run - 1;
-        }
+    if (lit) {
+        A.p_wave_max[(long long)(2 * r + 2) * N + idx] = pm[2];
+        A.p_wave_max[(long long)(2 * r + 3) * N + idx] = pm[3];
     }
-    if (n_run > i_chk) exact_test(n_run);   // the unsaved tail (CHECK_EXACT only)
-    write_summary();
 }
 
 }  // namespace psa

@@ -17,9 +17,10 @@
 // ~1e-12 after 1e4 steps, like one lane and two lanes do.  Measured: x0.81-0.88 of the two-lane kernel's time for
 // N <= 4 096 (tools/quad_lane_probe.hip, profiles/r03_quad_lane_probe.log); chosen by
 // the cost model of psa_rk4_f64.hip while 4*N lanes still give every wave its own SIMD (N <= 16 384 on MI355X).
-// Same RK4 regrouping, phase recurrence on the absolute seed grid, save / NaN semantics (exact index by replay) and
-// trajectory stores as rk4_sweep_kernel -- see that file.
+// The regrouped RK4 step, the phase recurrence on the absolute seed grid, both z-loops and the save / NaN semantics (exact
+// index by replay) are the shared ones of psa_rk4_carried.inc.h -- see that file; trajectory stores as rk4_sweep_kernel.
 #pragma once
+#include "psa_rk4_carried.inc.h"
 #include "psa_rk4_split_kernel.inc.h"
 
 namespace psa {
@@ -64,43 +65,29 @@ template <int CHECK, bool TRAJ, int BLOCK, bool LOSS, bool WSUM = false>
 __global__ void __launch_bounds__(BLOCK) rk4_sweep_quad_kernel(const SweepArgs<double> A) {
     static_assert(!WSUM || !TRAJ, "the per-wave summary exists for launches without trajectory");
     constexpr int NW = 4;
-    constexpr int RESYNC = Phase<double>::RESYNC;
     const long long gid = (long long)blockIdx.x * BLOCK + threadIdx.x;
     const long long idx = gid >> 2;   // sweep point: the four lanes of a quad share one
     const int role = (int)(gid & 3);  // = the wave this lane holds
     const long long N = A.n_points;
     if (idx >= N) return;             // the four lanes of a quad leave together
 
-    double x = A.a0[(long long)(2 * role) * A.a0_ld + idx * A.a0_stride];
-    double y = A.a0[(long long)(2 * role + 1) * A.a0_ld + idx * A.a0_stride];
+    double a[2] = {A.a0[(long long)(2 * role) * A.a0_ld + idx * A.a0_stride],
+                   A.a0[(long long)(2 * role + 1) * A.a0_ld + idx * A.a0_stride]};   // (re, im) of the lane's wave
     const double g = A.gamma[idx * A.gamma_stride];
-    const double tg = g + g;
     const double ha = -0.5 * A.alpha[idx * A.alpha_stride];
     const double dbd = (role < 2) ? A.dbeta[idx] : -A.dbeta[idx];   // pumps: E, sidebands: conj(E)
+    const CarriedConsts K = carried_consts(g, ha, dbd, A.z_max, A.n_steps);
+    const double e_amp = K.tg_d;
+    double Er = e_amp, Ei = 0.0;
 
-    const double hd = A.z_max / (double)A.n_steps;
-    const double hh = 0.5 * hd;
-    const double g_d = hh * g, tg_d = hh * tg, ha_d = hh * ha;
-    const double g_h = hd * g, tg_h = hd * tg, ha_h = hd * ha;
-    const double third = 1.0 / 3.0;
-    const double e_amp = tg_d;
-
-    double rc, rs, Er = e_amp, Ei = 0.0;
-    Phase<double>::eval(dbd * (0.5 * hd), rc, rs);
-
-    double pe = fma_(x, x, y * y);   // meaningful on the signal's lane (role 2), which writes the summary
+    double pe = fma_(a[0], a[0], a[1] * a[1]);   // meaningful on the signal's lane (role 2), which writes the summary
     double pm = pe;
-    long long bad = -1;
-    auto nonfinite_on = [&](const double vx, const double vy) -> bool {   // any component of the POINT non-finite
-        double t = fma_(vy, 0.0, fma_(vx, 0.0, 0.0));
+    auto nonfinite_on = [&](const double (&v)[2]) -> bool {   // any component of the POINT non-finite
+        double t = fma_(v[1], 0.0, fma_(v[0], 0.0, 0.0));
         t += quad_xchg<QUAD_PAIR>(t);
         t += quad_xchg<QUAD_OTHER>(t);
         return t != t;
     };
-
-    const int se = A.save_every;
-    const int n_rows = A.n_steps / se;
-    const int n_run = (CHECK != CHECK_NONE) ? A.n_steps : n_rows * se;
 
     // trajectory rows [row][wave][ld][2]: the lane's wave is its role, so the address is a wave-uniform row base plus the
     // per-lane constant 32-bit offset (role * ld + idx) * 16 (the C-ABI keeps 4 * ld * 16 B < 2^32 for these launches)
@@ -108,72 +95,23 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_quad_kernel(const SweepArgs<d
     const long long LD = A.traj_ld;
     const unsigned lane_off = (unsigned)((unsigned long long)(role * LD + idx) * sizeof(Pair));
     auto store_traj_row = [&](const int r) {
-        store_pair_nt(reinterpret_cast<const char *>(A.traj) + (long long)r * NW * LD * (long long)sizeof(Pair), lane_off, Pair{x, y});
+        store_pair_nt(reinterpret_cast<const char *>(A.traj) + (long long)r * NW * LD * (long long)sizeof(Pair), lane_off, Pair{a[0], a[1]});
     };
     auto store_a_end = [&]() {
-        A.a_end[(long long)(2 * role) * N + idx] = x;
-        A.a_end[(long long)(2 * role + 1) * N + idx] = y;
-        if constexpr (WSUM) A.p_wave_end[(long long)role * N + idx] = fma_(x, x, y * y);
+        A.a_end[(long long)(2 * role) * N + idx] = a[0];
+        A.a_end[(long long)(2 * role + 1) * N + idx] = a[1];
+        if constexpr (WSUM) A.p_wave_end[(long long)role * N + idx] = fma_(a[0], a[0], a[1] * a[1]);
     };
     if constexpr (TRAJ) store_traj_row(0);
-    if (n_rows == 0) store_a_end();
+    if (A.n_steps / A.save_every == 0) store_a_end();   // no saved row after z = 0
 
-    auto rk4_step_on = [&](double &x, double &y, double &Er, double &Ei) {
-        double x2, y2, x3, y3, x4, y4, dx, dy;
-        quad_stage<LOSS>(x, y, x, y, Er, Ei, g_d, tg_d, ha_d, x2, y2);
-        rotate(Er, Ei, rc, rs);  // z + h/2
-        quad_stage<LOSS>(x2, y2, x, y, Er, Ei, g_d, tg_d, ha_d, x3, y3);
-        quad_stage<LOSS>(x3, y3, x, y, Er + Er, Ei + Ei, g_h, tg_h, ha_h, x4, y4);
-        const double tx = fma_(2.0, x3, fma_(-4.0, x, x2)) + x4;
-        const double ty = fma_(2.0, y3, fma_(-4.0, y, y2)) + y4;
-        rotate(Er, Ei, rc, rs);  // z + h
-        quad_stage<LOSS>(x4, y4, tx, ty, Er, Ei, g_d, tg_d, ha_d, dx, dy);
-        x = fma_(dx, third, x);
-        y = fma_(dy, third, y);
+    auto stage = [&](auto full, const double (&y)[2], const double (&base)[2], const double er, const double ei, double (&out)[2]) {
+        if constexpr (decltype(full)::value) quad_stage<LOSS>(y[0], y[1], base[0], base[1], er, ei, K.g_h, K.tg_h, K.ha_h, out[0], out[1]);
+        else quad_stage<LOSS>(y[0], y[1], base[0], base[1], er, ei, K.g_d, K.tg_d, K.ha_d, out[0], out[1]);
     };
-    auto rk4_step = [&]() { rk4_step_on(x, y, Er, Ei); };
-    auto seed_on = [&](const int step, double &er, double &ei) {
-        double c, s;
-        Phase<double>::eval(dbd * ((double)step * hd), c, s);
-        er = e_amp * c;
-        ei = e_amp * s;
-    };
-
-    // CHECK_EXACT by replay of the failing block (see rk4_sweep_kernel); the four lanes of a point take the branch together
-    constexpr bool REPLAY = CHECK == CHECK_EXACT;
-    double x_chk = x, y_chk = y, Er_chk = Er, Ei_chk = Ei;
-    int i_chk = 0;
-    auto checkpoint = [&](const int step) {
-        if constexpr (REPLAY) {
-            x_chk = x;
-            y_chk = y;
-            Er_chk = Er;
-            Ei_chk = Ei;
-            i_chk = step;
-        }
-    };
-    auto exact_test = [&](const int i_now) {
-        if constexpr (REPLAY) {
-            const bool newly_bad = bad < 0 && nonfinite_on(x, y);
-            if (__builtin_amdgcn_ballot_w64(newly_bad) != 0) {
-                double xx = x_chk, yy = y_chk, er = Er_chk, ei = Ei_chk;
-                int ii = i_chk;
-                while (ii < i_now) {
-                    if (ii % RESYNC == 0) seed_on(ii, er, ei);
-                    const int to_seed = RESYNC - ii % RESYNC;
-                    const int e = (i_now - ii > to_seed) ? ii + to_seed : i_now;
-#pragma nounroll
-                    for (int st = ii; st < e; ++st) {
-                        rk4_step_on(xx, yy, er, ei);
-                        if (bad < 0 && nonfinite_on(xx, yy)) bad = st;
-                    }
-                    ii = e;
-                }
-            }
-            checkpoint(i_now);
-        }
-    };
-    auto write_summary = [&]() {
+    auto step_on = [&](double (&y)[2], double &er, double &ei) { carried_step<2>(y, er, ei, K.rc, K.rs, stage); };
+    auto seed_on = [&](const int step, double &er, double &ei) { carried_seed(e_amp, dbd, K.hd, step, er, ei); };
+    auto write_summary = [&](const long long bad) {
         if (role == 2) {
             A.p_end[idx] = pe;
             A.p_max[idx] = pm;
@@ -182,90 +120,32 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_quad_kernel(const SweepArgs<d
         if constexpr (WSUM) A.p_wave_max[(long long)role * N + idx] = pm;
     };
 
-    // ---- save_every == 1 with a trajectory: every step is a saved row (the dedicated loop of rk4_sweep_kernel)
+    // ---- save_every == 1 with a trajectory: every step is a saved row
     if constexpr (TRAJ) {
-        if (se == 1) {
-            auto save_row = [&](const int r) {
-                pe = fma_(x, x, y * y);
+        if (A.save_every == 1) {
+            auto summarise = [&]() {
+                pe = fma_(a[0], a[0], a[1] * a[1]);
                 pm = pe > pm ? pe : pm;               // NaN is made to propagate after the loop (it is sticky in y)
-                if constexpr (CHECK != CHECK_NONE) {
-                    if (bad < 0 && nonfinite_on(x, y)) bad = r - 1;
-                }
-                store_traj_row(r);
             };
-            int i = 0;
-            while (i < n_run) {
-                seed_on(i, Er, Ei);
-                const int end = (n_run - i > RESYNC) ? i + RESYNC : n_run;
-                for (; i + 2 <= end; i += 2) {
-                    rk4_step();
-                    save_row(i + 1);
-                    rk4_step();
-                    save_row(i + 2);
-                }
-                if (i < end) {
-                    rk4_step();
-                    save_row(i + 1);
-                    ++i;
-                }
-            }
+            const long long bad = carried_every_step_loop<CHECK>(a, Er, Ei, A.n_steps, step_on, seed_on, nonfinite_on, summarise, store_traj_row);
             if (pe != pe) pm = pe;
             store_a_end();
-            write_summary();
+            write_summary(bad);
             return;
         }
     }
 
-    // ---- z-loop, event driven, seeds on the absolute grid i = 0, RESYNC, ... (see rk4_sweep_kernel)
-    int i = 0, row = 0;
-    int next_save = (n_rows > 0) ? se : 0x7fffffff;
-    int next_seed = 0;
-    checkpoint(0);
-    while (i < n_run) {
-        if (i == next_seed) {
-            seed_on(i, Er, Ei);
-            next_seed = (n_run - i > RESYNC) ? i + RESYNC : 0x7fffffff;
-        }
-        int end = n_run < next_seed ? n_run : next_seed;
-        end = end < next_save ? end : next_save;
-        const int m = end - i;
-        int j = 0;
-        // four steps per trip, then two, then one: with one wave per SIMD a taken back-edge is ~32 exposed cycles
-        // (tools/issue_probe.hip); four against two measured -0.5 % (config-5 shard) ... -1.2 % (4 096 points, four lanes)
-        for (; j + 4 <= m; j += 4) {
-            rk4_step();
-            rk4_step();
-            rk4_step();
-            rk4_step();
-        }
-        for (; j + 2 <= m; j += 2) {
-            rk4_step();
-            rk4_step();
-        }
-        if (j < m) rk4_step();
-        i = end;
-        if (i == next_save) {
-            ++row;
-            pe = fma_(x, x, y * y);
-            pm = (pe > pm || pe != pe) ? pe : pm;
-            if constexpr (CHECK == CHECK_BLOCK) {
-                if (bad < 0 && nonfinite_on(x, y)) bad = i - 1;
-            }
-            exact_test(i);
-            if constexpr (TRAJ) store_traj_row(row);
-            if (row == n_rows) {
-                store_a_end();
-                next_save = 0x7fffffff;
-            } else {
-                next_save += se;
-            }
-        }
-    }
-    if constexpr (CHECK == CHECK_BLOCK) {
-        if (bad < 0 && n_run > 0 && nonfinite_on(x, y)) bad = n_run - 1;
-    }
-    if (n_run > i_chk) exact_test(n_run);   // the unsaved tail (CHECK_EXACT only)
-    write_summary();
+    // ---- z-loop, event driven.  Four steps per trip, then two, then one: with one wave per SIMD a taken back-edge is ~32
+    // exposed cycles (tools/issue_probe.hip); four against two measured -0.5 % (config-5 shard) ... -1.2 % (4 096 points, four lanes)
+    auto summarise = [&]() {
+        pe = fma_(a[0], a[0], a[1] * a[1]);
+        pm = (pe > pm || pe != pe) ? pe : pm;
+    };
+    auto save_row = [&](const int row, const bool last) {
+        if constexpr (TRAJ) store_traj_row(row);
+        if (last) store_a_end();
+    };
+    write_summary(carried_event_loop<CHECK, 4>(a, Er, Ei, A.n_steps, A.save_every, step_on, seed_on, nonfinite_on, summarise, save_row));
 }
 
 // Four lanes per point: the 4-wave model's register layout only; the per-wave summary without trajectory.

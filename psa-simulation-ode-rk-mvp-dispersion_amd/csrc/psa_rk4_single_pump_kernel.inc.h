@@ -9,13 +9,10 @@
 // with a = A1 = A2 and A_p = sqrt(2) a the sideband equations coincide, but the pump's self-phase term there is
 // 3*gamma*|a|^2 = 1.5*gamma*|A_p|^2 instead of gamma*|A_p|^2.
 //
-// Layout and loop are rk4_sweep_kernel's: one sweep point per lane, the whole z-loop in the kernel, the six state components
-// in VGPRs, the fused regrouped stage (stage coefficient folded into g, tg, ha and the carried phase factor), z_i formed from
-// the integer step index, the half-step rotation re-seeded exactly on the absolute grid i = 0, RESYNC, 2*RESYNC, ..., the
-// event-driven loop, and the save / NaN semantics:  CHECK_NONE: first_bad_step = -1, NaNs propagate;  CHECK_BLOCK: the last
-// step of the first non-finite save block (or of the unsaved tail);  CHECK_EXACT: the exact step, found by replaying the
-// failing block from the last test point with a per-step test -- and if that replay should stay finite (it repeats the
-// forward pass operation for operation, so it should not), `bad` becomes the block-mode answer rather than staying -1.
+// Layout: one sweep point per lane, the whole z-loop in the kernel, the six state components in VGPRs, the fused regrouped
+// stage (stage coefficient folded into g, tg, ha and the carried phase factor).  The step, the re-seeds on the absolute
+// RESYNC grid, the event-driven loop, the save / NaN semantics and the replay that finds the exact first_bad_step are the
+// shared ones of psa_rk4_carried.inc.h (see that file); every stride, save_every == 1 included, goes through its event loop.
 // Wave-uniform control flow only: every branch is on a kernel argument, the loop counters or a ballot.
 //
 // What is carried is H = E/2, not E.  The sidebands need conj(E)/2 * A_p^2 and Im(A_p^2) = fma(x, y, y*x) = 2*RN(x*y) for every
@@ -35,7 +32,7 @@
 // Out of scope: float32, lane-pair / lane-quad layouts, RK45, chains, LDS staging, a mirrored variant, a dedicated
 // save_every == 1 trajectory loop (every stride goes through the event loop).
 #pragma once
-#include "psa_rk4_kernel.inc.h"
+#include "psa_rk4_carried.inc.h"
 
 namespace psa {
 
@@ -75,7 +72,6 @@ __device__ __forceinline__ void single_pump_stage(const double (&a)[6], const do
 
 template <int CHECK, bool TRAJ, int BLOCK, bool LOSS>
 __global__ void __launch_bounds__(BLOCK) rk4_sweep_single_pump_kernel(const SinglePumpArgs A) {
-    constexpr int RESYNC = Phase<double>::RESYNC;
     const long long idx = (long long)blockIdx.x * BLOCK + threadIdx.x;
     const long long N = A.n_points;
     if (idx >= N) return;
@@ -84,40 +80,20 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_single_pump_kernel(const Sing
 #pragma unroll
     for (int c = 0; c < 6; ++c) a[c] = A.a0[(long long)c * A.a0_ld + idx * A.a0_stride];
     const double g = A.gamma[idx * A.gamma_stride];
-    const double tg = g + g;
     const double ha = -0.5 * A.alpha[idx * A.alpha_stride];
     const double dbd = A.dbeta[idx];
-
-    const double hd = A.z_max / (double)A.n_steps;   // np.linspace step
-    const double hh = 0.5 * hd;
-    // stage coefficients folded into the physics constants: d = h/2 (stages 1, 2, 4) and h (stage 3)
-    const double g_d = hh * g, tg_d = hh * tg, ha_d = hh * ha;
-    const double g_h = hd * g, tg_h = hd * tg, ha_h = hd * ha;
-    const double third = 1.0 / 3.0;
-    const double h_amp = g_d;   // modulus of the carried H = E/2 = d*gamma*exp(i*dbeta*z)
-
-    double rc, rs, Hr = h_amp, Hi = 0.0;   // half-step rotator and the running H
-    Phase<double>::eval(dbd * (0.5 * hd), rc, rs);
+    const CarriedConsts K = carried_consts(g, ha, dbd, A.z_max, A.n_steps);
+    const double h_amp = K.g_d;   // modulus of the carried H = E/2 = d*gamma*exp(i*dbeta*z)
+    double Hr = h_amp, Hi = 0.0;
 
     double pm[3];   // np.max of |A_j|^2 over saved rows (z = 0 is one)
 #pragma unroll
     for (int j = 0; j < 3; ++j) pm[j] = fma_(a[2 * j], a[2 * j], a[2 * j + 1] * a[2 * j + 1]);
-    long long bad = -1;
-
-    const int se = A.save_every;
-    const int n_rows = A.n_steps / se;                                  // saved rows after z = 0
-    const int n_run = (CHECK != CHECK_NONE) ? A.n_steps : n_rows * se;   // the tail only matters for the check
-
     auto store_a_end = [&]() {   // the last saved row and |A_j|^2 there
 #pragma unroll
         for (int c = 0; c < 6; ++c) A.a_end[(long long)c * N + idx] = a[c];
 #pragma unroll
         for (int j = 0; j < 3; ++j) A.p_wave_end[(long long)j * N + idx] = fma_(a[2 * j], a[2 * j], a[2 * j + 1] * a[2 * j + 1]);
-    };
-    auto write_summary = [&]() {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) A.p_wave_max[(long long)j * N + idx] = pm[j];
-        A.first_bad[idx] = bad;
     };
     // trajectory rows [row][wave][ld][2]: a wave-uniform (row, wave) base and the lane's 32-bit byte offset, as in
     // rk4_sweep_kernel; the C-ABI keeps ld * 16 below 2^32 for trajectory launches
@@ -131,114 +107,31 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_single_pump_kernel(const Sing
             store_pair_nt(rowb + (long long)j * LD * (long long)sizeof(Pair), lane_off, Pair{a[2 * j], a[2 * j + 1]});
     };
     if constexpr (TRAJ) store_traj_row(0);
-    if (n_rows == 0) store_a_end();
+    if (A.n_steps / A.save_every == 0) store_a_end();   // no saved row after z = 0
 
-    // one classic RK4 step, regrouped as in rk4_sweep_kernel; (hr, hi) enters at z_step and leaves rotated to z_step + h
-    auto rk4_step_on = [&](double (&y)[6], double &hr, double &hi) {
-        double Y2[6], Y3[6], Y4[6], t[6], D[6];
-        single_pump_stage<LOSS>(y, y, hr, hi, hr + hr, hi + hi, g_d, tg_d, ha_d, Y2);      // Y2 = y + d k1
-        rotate(hr, hi, rc, rs);  // z + h/2
-        const double er = hr + hr, ei = hi + hi;
-        single_pump_stage<LOSS>(Y2, y, hr, hi, er, ei, g_d, tg_d, ha_d, Y3);               // Y3 = y + d k2
-        single_pump_stage<LOSS>(Y3, y, er, ei, er + er, ei + ei, g_h, tg_h, ha_h, Y4);     // Y4 = y + h k3: H is stage 2's E
-#pragma unroll
-        for (int c = 0; c < 6; ++c) t[c] = fma_(2.0, Y3[c], fma_(-4.0, y[c], Y2[c])) + Y4[c];
-        rotate(hr, hi, rc, rs);  // z + h
-        single_pump_stage<LOSS>(Y4, t, hr, hi, hr + hr, hi + hi, g_d, tg_d, ha_d, D);      // D = t + d k4
-#pragma unroll
-        for (int c = 0; c < 6; ++c) y[c] = fma_(D[c], third, y[c]);
+    // the adapter forms E = H + H from the factor it is handed; stage 3 is handed 2H, stage 2's E
+    auto stage = [&](auto full, const double (&y)[6], const double (&base)[6], const double hr, const double hi, double (&out)[6]) {
+        if constexpr (decltype(full)::value) single_pump_stage<LOSS>(y, base, hr, hi, hr + hr, hi + hi, K.g_h, K.tg_h, K.ha_h, out);
+        else single_pump_stage<LOSS>(y, base, hr, hi, hr + hr, hi + hi, K.g_d, K.tg_d, K.ha_d, out);
     };
-    auto rk4_step = [&]() { rk4_step_on(a, Hr, Hi); };
-    auto seed_on = [&](const int step, double &hr, double &hi) {   // exact re-seed at z = step * h
-        double c, s;
-        Phase<double>::eval(dbd * ((double)step * hd), c, s);
-        hr = h_amp * c;
-        hi = h_amp * s;
-    };
-
-    // CHECK_EXACT by replay of the failing block (see rk4_sweep_kernel): the branch is wave-uniform (a ballot)
-    constexpr bool REPLAY = CHECK == CHECK_EXACT;
-    double a_chk[REPLAY ? 6 : 1], Hr_chk = Hr, Hi_chk = Hi;
-    int i_chk = 0;
-    auto checkpoint = [&](const int step) {
-        if constexpr (REPLAY) {
+    auto step_on = [&](double (&y)[6], double &hr, double &hi) { carried_step<6>(y, hr, hi, K.rc, K.rs, stage); };
+    auto seed_on = [&](const int step, double &hr, double &hi) { carried_seed(h_amp, dbd, K.hd, step, hr, hi); };
+    auto nonfinite_on = [&](const double (&y)[6]) -> bool { return any_nonfinite<double, 6>(y); };
+    auto summarise = [&]() {
 #pragma unroll
-            for (int c = 0; c < 6; ++c) a_chk[c] = a[c];
-            Hr_chk = Hr;
-            Hi_chk = Hi;
-            i_chk = step;
+        for (int w = 0; w < 3; ++w) {
+            const double pw = fma_(a[2 * w], a[2 * w], a[2 * w + 1] * a[2 * w + 1]);
+            pm[w] = (pw > pm[w] || pw != pw) ? pw : pm[w];   // np.max propagates NaN
         }
     };
-    auto exact_test = [&](const int i_now) {   // at a test point: a is the state after step i_now - 1
-        if constexpr (REPLAY) {
-            const bool newly_bad = bad < 0 && any_nonfinite<double, 6>(a);
-            if (__builtin_amdgcn_ballot_w64(newly_bad) != 0) {
-                double yy[6], hr = Hr_chk, hi = Hi_chk;
-#pragma unroll
-                for (int c = 0; c < 6; ++c) yy[c] = a_chk[c];
-                int ii = i_chk;
-                while (ii < i_now) {
-                    if (ii % RESYNC == 0) seed_on(ii, hr, hi);   // the forward pass seeds at the same steps
-                    const int to_seed = RESYNC - ii % RESYNC;
-                    const int e = (i_now - ii > to_seed) ? ii + to_seed : i_now;
-#pragma nounroll
-                    for (int st = ii; st < e; ++st) {
-                        rk4_step_on(yy, hr, hi);
-                        if (bad < 0 && any_nonfinite<double, 6>(yy)) bad = st;
-                    }
-                    ii = e;
-                }
-                if (newly_bad && bad < 0) bad = i_now - 1;   // the replay stayed finite: the block-mode answer
-            }
-            checkpoint(i_now);
-        }
+    auto save_row = [&](const int row, const bool last) {
+        if constexpr (TRAJ) store_traj_row(row);
+        if (last) store_a_end();
     };
-
-    // ---- z-loop, event driven, seeds on the absolute grid i = 0, RESYNC, ... (see rk4_sweep_kernel)
-    int i = 0, row = 0;
-    int next_save = (n_rows > 0) ? se : 0x7fffffff;
-    int next_seed = 0;
-    checkpoint(0);
-    while (i < n_run) {
-        if (i == next_seed) {
-            seed_on(i, Hr, Hi);
-            next_seed = (n_run - i > RESYNC) ? i + RESYNC : 0x7fffffff;
-        }
-        int end = n_run < next_seed ? n_run : next_seed;
-        end = end < next_save ? end : next_save;
-        const int m = end - i;
-        int j = 0;
-        for (; j + 2 <= m; j += 2) {
-            rk4_step();
-            rk4_step();
-        }
-        if (j < m) rk4_step();
-        i = end;
-        if (i == next_save) {
-            ++row;
+    const long long bad = carried_event_loop<CHECK, 2>(a, Hr, Hi, A.n_steps, A.save_every, step_on, seed_on, nonfinite_on, summarise, save_row);
 #pragma unroll
-            for (int w = 0; w < 3; ++w) {
-                const double pw = fma_(a[2 * w], a[2 * w], a[2 * w + 1] * a[2 * w + 1]);
-                pm[w] = (pw > pm[w] || pw != pw) ? pw : pm[w];   // np.max propagates NaN
-            }
-            if constexpr (CHECK == CHECK_BLOCK) {
-                if (bad < 0 && any_nonfinite<double, 6>(a)) bad = i - 1;
-            }
-            exact_test(i);
-            if constexpr (TRAJ) store_traj_row(row);
-            if (row == n_rows) {   // the last saved row, not necessarily z_max
-                store_a_end();
-                next_save = 0x7fffffff;
-            } else {
-                next_save += se;
-            }
-        }
-    }
-    if constexpr (CHECK == CHECK_BLOCK) {   // covers the unsaved tail
-        if (bad < 0 && n_run > 0 && any_nonfinite<double, 6>(a)) bad = n_run - 1;
-    }
-    if (n_run > i_chk) exact_test(n_run);   // the unsaved tail (CHECK_EXACT only)
-    write_summary();
+    for (int j = 0; j < 3; ++j) A.p_wave_max[(long long)j * N + idx] = pm[j];
+    A.first_bad[idx] = bad;
 }
 
 }  // namespace psa

@@ -18,11 +18,12 @@
 // Values cross between the two lanes with DPP quad_perm:[1,0,3,2] moves (two v_mov_b32_dpp per double: gfx950's
 // DP ALU accepts no quad_perm, so the exchange cannot be folded into the consuming v_fma_f64).  Per RHS evaluation:
 // 4 waves 39 instructions (6 of them moves) instead of 64; 6 waves 65 (10 moves) instead of 100.
-// Same RK4 regrouping, phase recurrence, save / NaN semantics as rk4_sweep_kernel -- see that file.
+// The regrouped RK4 step, the phase recurrence, both z-loops and the save / NaN semantics (exact index by replay) are the
+// shared ones of psa_rk4_carried.inc.h -- see that file.
 // 4 waves: a wave whose points all start mirrored (A2 == A1, A4 == A3) does not run this stage at all but the mirrored z-loop of
 // rk4_sweep_kernel on its even lanes (see the kernel below).
 #pragma once
-#include "psa_rk4_kernel.inc.h"
+#include "psa_rk4_carried.inc.h"
 
 namespace psa {
 
@@ -92,7 +93,6 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_split_kernel(const SweepArgs<
     static_assert(!WSUM || !TRAJ, "the per-wave summary exists for launches without trajectory");
     constexpr int NL = NW / 2;    // waves per lane
     constexpr int NC = 2 * NL;    // real components per lane
-    constexpr int RESYNC = Phase<double>::RESYNC;
     const long long gid = (long long)blockIdx.x * BLOCK + threadIdx.x;
     const long long idx = gid >> 1;   // sweep point: lanes 2k and 2k+1 of a wave share one
     const int role = (int)(gid & 1);
@@ -140,26 +140,18 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_split_kernel(const SweepArgs<
         }
     }
     const double g = A.gamma[idx * A.gamma_stride];
-    const double tg = g + g;
     const double ha = -0.5 * A.alpha[idx * A.alpha_stride];
     // the lane's phase rate: 4 waves +dbeta (pumps) | -dbeta (sidebands: conj(E)); 6 waves the own pair's dbeta_k
     double dbd;
     if constexpr (NL == 2) dbd = role ? -A.dbeta[idx] : A.dbeta[idx];
     else dbd = role ? A.dbeta2[idx] : A.dbeta[idx];
 
-    const double hd = A.z_max / (double)A.n_steps;
-    const double hh = 0.5 * hd;
-    const double g_d = hh * g, tg_d = hh * tg, ha_d = hh * ha;
-    const double g_h = hd * g, tg_h = hd * tg, ha_h = hd * ha;
-    const double third = 1.0 / 3.0;
-    const double e_amp = tg_d;
-
-    double rc, rs, Er = e_amp, Ei = 0.0;
-    Phase<double>::eval(dbd * (0.5 * hd), rc, rs);
+    const CarriedConsts K = carried_consts(g, ha, dbd, A.z_max, A.n_steps);
+    const double e_amp = K.tg_d;
+    double Er = e_amp, Ei = 0.0;
 
     double pe = fma_(y[SIG], y[SIG], y[SIG + 1] * y[SIG + 1]);
     double pm = pe;
-    long long bad = -1;
     double pwm[WSUM ? NL : 1];     // WSUM: np.max of |A|^2 over saved rows, for each of the lane's waves
     if constexpr (WSUM) {
 #pragma unroll
@@ -173,11 +165,6 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_split_kernel(const SweepArgs<
         t += from_partner(t);
         return t != t;
     };
-    auto point_nonfinite = [&]() -> bool { return nonfinite_on(y); };
-
-    const int se = A.save_every;
-    const int n_rows = A.n_steps / se;
-    const int n_run = (CHECK != CHECK_NONE) ? A.n_steps : n_rows * se;
 
     // trajectory rows [row][wave][N][2]: the lane writes its own waves' (re, im) pairs.  wave_of[j] = U_j + role * R_j, so the
     // address splits into a wave-uniform part (row, U_j: an SGPR pair) and a per-lane constant 32-bit byte offset
@@ -213,219 +200,62 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_split_kernel(const SweepArgs<
         }
     };
     if constexpr (TRAJ) store_traj_row(0);
-    if (n_rows == 0) store_a_end();
+    if (A.n_steps / A.save_every == 0) store_a_end();   // no saved row after z = 0
 
-    // one RK4 step, regrouped exactly as rk4_step_on of rk4_sweep_kernel (integrators.py:54-59); the per-step finite test of
-    // CHECK_EXACT is not in it: the exact index comes from a replay (exact_test below), as in rk4_sweep_kernel
-    auto rk4_step_on = [&](double (&y)[NC], double &Er, double &Ei) {
-        double Y2[NC], Y3[NC], Y4[NC], t[NC], D[NC];
-        split_stage<NL, LOSS>(y, y, Er, Ei, g_d, tg_d, ha_d, Y2);
-        rotate(Er, Ei, rc, rs);  // z + h/2
-        split_stage<NL, LOSS>(Y2, y, Er, Ei, g_d, tg_d, ha_d, Y3);
-        const double E2r = Er + Er, E2i = Ei + Ei;
-        split_stage<NL, LOSS>(Y3, y, E2r, E2i, g_h, tg_h, ha_h, Y4);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) t[c] = fma_(2.0, Y3[c], fma_(-4.0, y[c], Y2[c])) + Y4[c];
-        rotate(Er, Ei, rc, rs);  // z + h
-        split_stage<NL, LOSS>(Y4, t, Er, Ei, g_d, tg_d, ha_d, D);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) y[c] = fma_(D[c], third, y[c]);
+    auto stage = [&](auto full, const double (&a)[NC], const double (&base)[NC], const double er, const double ei, double (&out)[NC]) {
+        if constexpr (decltype(full)::value) split_stage<NL, LOSS>(a, base, er, ei, K.g_h, K.tg_h, K.ha_h, out);
+        else split_stage<NL, LOSS>(a, base, er, ei, K.g_d, K.tg_d, K.ha_d, out);
     };
-    auto rk4_step = [&](const int) { rk4_step_on(y, Er, Ei); };
-    auto seed_on = [&](const int step, double &er, double &ei) {
-        double c, s;
-        Phase<double>::eval(dbd * ((double)step * hd), c, s);
-        er = e_amp * c;
-        ei = e_amp * s;
-    };
-
-    // CHECK_EXACT by replay (see rk4_sweep_kernel): state at the last test point; a wave with a newly failing point repeats
-    // the steps since then on a copy, testing after each one.  Both lanes of a point take the branch together (the test
-    // exchanges their partial sums), and the replay's own exchanges stay within the pair.
-    constexpr bool REPLAY = CHECK == CHECK_EXACT;
-    double y_chk[REPLAY ? NC : 1], Er_chk = 0.0, Ei_chk = 0.0;
-    int i_chk = 0;
-    auto checkpoint = [&](const int step) {
-        if constexpr (REPLAY) {
-#pragma unroll
-            for (int c = 0; c < NC; ++c) y_chk[c] = y[c];
-            Er_chk = Er;
-            Ei_chk = Ei;
-            i_chk = step;
+    auto step_on = [&](double (&a)[NC], double &er, double &ei) { carried_step<NC>(a, er, ei, K.rc, K.rs, stage); };
+    auto seed_on = [&](const int step, double &er, double &ei) { carried_seed(e_amp, dbd, K.hd, step, er, ei); };
+    auto write_summary = [&](const long long bad) {
+        if (owns_signal) {
+            A.p_end[idx] = pe;
+            A.p_max[idx] = pm;
         }
-    };
-    auto exact_test = [&](const int i_now) {
-        if constexpr (REPLAY) {
-            const bool newly_bad = bad < 0 && point_nonfinite();
-            if (__builtin_amdgcn_ballot_w64(newly_bad) != 0) {
-                double yy[NC], er = Er_chk, ei = Ei_chk;
+        if (role == 0) A.first_bad[idx] = bad;
+        if constexpr (WSUM) {
 #pragma unroll
-                for (int c = 0; c < NC; ++c) yy[c] = y_chk[c];
-                int ii = i_chk;
-                while (ii < i_now) {
-                    if (ii % RESYNC == 0) seed_on(ii, er, ei);            // the forward pass seeds at the same steps
-                    const int to_seed = RESYNC - ii % RESYNC;
-                    const int e = (i_now - ii > to_seed) ? ii + to_seed : i_now;
-#pragma nounroll
-                    for (int st = ii; st < e; ++st) {
-                        rk4_step_on(yy, er, ei);
-                        if (bad < 0 && nonfinite_on(yy)) bad = st;
-                    }
-                    ii = e;
-                }
-            }
-            checkpoint(i_now);
+            for (int j = 0; j < NL; ++j) A.p_wave_max[(long long)wave_of[j] * N + idx] = pwm[j];
         }
     };
 
-#ifdef PSA_SPLIT_TRAJ_SPREAD
-    // A/B hook (tools/ab_traj_stores.sh, profiles/r03_split_traj_ab.log): the same step, with the stores of the PREVIOUS row
-    // (y is unchanged until the step's last line) issued one per stage instead of as a burst after the step.  Measured
-    // SLOWER (32 768 points, every step saved: 1.71 vs 1.62 ms for 4 waves, 1.62 vs 1.54 for 6), as were default instead of
-    // non-temporal stores (1.64 / 1.56): with one wave per SIMD a store that finds the queue full stalls the only wave,
-    // wherever in the step it is issued.  Not compiled in.
-    auto store_traj_wave = [&](const int r, const int j) {
-        const char *rowb = reinterpret_cast<const char *>(A.traj) + (long long)r * NW * LD * (long long)sizeof(Pair);
-        store_pair_nt(rowb + (long long)wave_u[j] * LD * (long long)sizeof(Pair), lane_off[j], Pair{y[2 * j], y[2 * j + 1]});
-    };
-    auto rk4_step_spread = [&](const int step_index, const int r_prev) {
-        double Y2[NC], Y3[NC], Y4[NC], t[NC], D[NC];
-        split_stage<NL, LOSS>(y, y, Er, Ei, g_d, tg_d, ha_d, Y2);
-        store_traj_wave(r_prev, 0);
-        rotate(Er, Ei, rc, rs);
-        split_stage<NL, LOSS>(Y2, y, Er, Ei, g_d, tg_d, ha_d, Y3);
-        store_traj_wave(r_prev, 1);
-        const double E2r = Er + Er, E2i = Ei + Ei;
-        split_stage<NL, LOSS>(Y3, y, E2r, E2i, g_h, tg_h, ha_h, Y4);
-        if constexpr (NL == 3) store_traj_wave(r_prev, 2);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) t[c] = fma_(2.0, Y3[c], fma_(-4.0, y[c], Y2[c])) + Y4[c];
-        rotate(Er, Ei, rc, rs);
-        split_stage<NL, LOSS>(Y4, t, Er, Ei, g_d, tg_d, ha_d, D);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) y[c] = fma_(D[c], third, y[c]);
-        (void)step_index;
-    };
-#endif
-
-    // ---- save_every == 1 with a trajectory: every step is a saved row -- the dedicated loop of rk4_sweep_kernel (per row:
-    // |A_sig|^2, running maximum, block-mode finite test, the lane's NL streaming stores; two steps per trip).
+    // ---- save_every == 1 with a trajectory: every step is a saved row (per row: |A_sig|^2, running maximum, finite test, the
+    // lane's NL streaming stores).  (A/B, profiles/r03_split_traj_ab.log: issuing the stores of the previous row one per stage
+    // instead of as a burst after the step measured SLOWER, 1.71 vs 1.62 ms for 4 waves at 32 768 points, as did default
+    // instead of non-temporal stores: with one wave per SIMD a store that finds the queue full stalls the only wave.)
     if constexpr (TRAJ) {
-        if (se == 1) {
-            auto save_row = [&](const int r) {
+        if (A.save_every == 1) {
+            auto summarise = [&]() {
                 pe = fma_(y[SIG], y[SIG], y[SIG + 1] * y[SIG + 1]);
                 pm = pe > pm ? pe : pm;               // NaN is made to propagate after the loop (it is sticky in y)
-                if constexpr (CHECK != CHECK_NONE) {      // a row is a step here: exact in either mode
-                    if (bad < 0 && point_nonfinite()) bad = r - 1;
-                }
-                store_traj_row(r);
             };
-            int i = 0;
-            while (i < n_run) {
-                seed_on(i, Er, Ei);
-                const int end = (n_run - i > RESYNC) ? i + RESYNC : n_run;
-#ifdef PSA_SPLIT_TRAJ_SPREAD
-                for (; i < end; ++i) {      // row i was "saved" (summary only) after step i-1; its stores ride in step i
-                    if (i == 0) rk4_step(0); else rk4_step_spread(i, i);
-                    pe = fma_(y[SIG], y[SIG], y[SIG + 1] * y[SIG + 1]);
-                    pm = pe > pm ? pe : pm;
-                    if constexpr (CHECK != CHECK_NONE) {
-                        if (bad < 0 && point_nonfinite()) bad = i;
-                    }
-                }
-#else
-                for (; i + 2 <= end; i += 2) {
-                    rk4_step(i);
-                    save_row(i + 1);
-                    rk4_step(i + 1);
-                    save_row(i + 2);
-                }
-                if (i < end) {
-                    rk4_step(i);
-                    save_row(i + 1);
-                    ++i;
-                }
-#endif
-            }
-#ifdef PSA_SPLIT_TRAJ_SPREAD
-            if (n_run > 0) store_traj_row(n_run);
-#endif
+            const long long bad = carried_every_step_loop<CHECK>(y, Er, Ei, A.n_steps, step_on, seed_on, nonfinite_on, summarise, store_traj_row);
             if (pe != pe) pm = pe;
             store_a_end();
-            if (owns_signal) {
-                A.p_end[idx] = pe;
-                A.p_max[idx] = pm;
-            }
-            if (role == 0) A.first_bad[idx] = bad;
+            write_summary(bad);
             return;
         }
     }
 
-    // seeds on the absolute grid i = 0, RESYNC, ...: the trajectory does not depend on save_every (see rk4_sweep_kernel)
-    int i = 0, row = 0;
-    int next_save = (n_rows > 0) ? se : 0x7fffffff;
-    int next_seed = 0;
-    checkpoint(0);
-    while (i < n_run) {
-        if (i == next_seed) {
-            seed_on(i, Er, Ei);
-            next_seed = (n_run - i > RESYNC) ? i + RESYNC : 0x7fffffff;
-        }
-        int end = n_run < next_seed ? n_run : next_seed;
-        end = end < next_save ? end : next_save;
-        const int m = end - i;
-        int j = 0;
-        // four steps per trip, then two, then one: with one wave per SIMD a taken back-edge is ~32 exposed cycles
-        // (tools/issue_probe.hip); four against two measured -0.5 % (config-5 shard) ... -1.2 % (4 096 points, four lanes)
-        for (; j + 4 <= m; j += 4) {
-            rk4_step(i + j);
-            rk4_step(i + j + 1);
-            rk4_step(i + j + 2);
-            rk4_step(i + j + 3);
-        }
-        for (; j + 2 <= m; j += 2) {
-            rk4_step(i + j);
-            rk4_step(i + j + 1);
-        }
-        if (j < m) rk4_step(i + j);
-        i = end;
-        if (i == next_save) {
-            ++row;
-            pe = fma_(y[SIG], y[SIG], y[SIG + 1] * y[SIG + 1]);
-            pm = (pe > pm || pe != pe) ? pe : pm;
-            if constexpr (WSUM) {
+    // ---- z-loop, event driven.  Four steps per trip, then two, then one: with one wave per SIMD a taken back-edge is ~32
+    // exposed cycles (tools/issue_probe.hip); four against two measured -0.5 % (config-5 shard) ... -1.2 % (4 096 points, four lanes)
+    auto summarise = [&]() {
+        pe = fma_(y[SIG], y[SIG], y[SIG + 1] * y[SIG + 1]);
+        pm = (pe > pm || pe != pe) ? pe : pm;   // np.max propagates NaN
+        if constexpr (WSUM) {
 #pragma unroll
-                for (int j = 0; j < NL; ++j) {
-                    const double pj = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
-                    pwm[j] = (pj > pwm[j] || pj != pj) ? pj : pwm[j];
-                }
-            }
-            if constexpr (CHECK == CHECK_BLOCK) {
-                if (bad < 0 && point_nonfinite()) bad = i - 1;
-            }
-            exact_test(i);
-            if constexpr (TRAJ) store_traj_row(row);
-            if (row == n_rows) {
-                store_a_end();
-                next_save = 0x7fffffff;
-            } else {
-                next_save += se;
+            for (int j = 0; j < NL; ++j) {
+                const double pj = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
+                pwm[j] = (pj > pwm[j] || pj != pj) ? pj : pwm[j];
             }
         }
-    }
-    if constexpr (CHECK == CHECK_BLOCK) {
-        if (bad < 0 && n_run > 0 && point_nonfinite()) bad = n_run - 1;
-    }
-    if (n_run > i_chk) exact_test(n_run);   // the unsaved tail (CHECK_EXACT only)
-    if (owns_signal) {
-        A.p_end[idx] = pe;
-        A.p_max[idx] = pm;
-    }
-    if (role == 0) A.first_bad[idx] = bad;
-    if constexpr (WSUM) {
-#pragma unroll
-        for (int j = 0; j < NL; ++j) A.p_wave_max[(long long)wave_of[j] * N + idx] = pwm[j];
-    }
+    };
+    auto save_row = [&](const int row, const bool last) {
+        if constexpr (TRAJ) store_traj_row(row);
+        if (last) store_a_end();
+    };
+    write_summary(carried_event_loop<CHECK, 4>(y, Er, Ei, A.n_steps, A.save_every, step_on, seed_on, nonfinite_on, summarise, save_row));
 }
 
 // Two lanes per point: register layout only; the per-wave summary without trajectory.

@@ -210,6 +210,68 @@ def test_save_semantics():
     assert rel_err(r0["p_wave_end"], p) < 1e-15 and np.array_equal(r0["p_wave_end"], r0["p_wave_max"])
 
 
+@pytest.mark.parametrize("K", [3, 16])
+def test_the_stride_does_not_change_the_computed_rows(K):
+    """The re-seeds sit on the absolute step grid, so the last saved row at stride se is the state after m = 200 // se * se
+    steps whatever se is: it equals, bit for bit, the end of a run of m steps saved once (h = 0.5 m is exact in both) --
+    below, at and above RESYNC = 64; the run saved once re-seeds inside its only block.  se > n_steps: the only row is
+    z = 0."""
+    N = 37
+    rng = np.random.default_rng(40 + K)
+    dbeta = rng.uniform(-0.05, 0.05, (N, K))
+    p = np.column_stack([np.full((N, 2), 0.5), 10 ** rng.uniform(-6, -4, (N, 2 * K))])
+    a0 = np.sqrt(p) * np.exp(1j * rng.uniform(-3, 3, (N, 2 + 2 * K)))
+    kw = dict(gamma=GAMMA, alpha=ALPHA, a0=a0)
+    for se in (7, 64, 65):
+        m = 200 // se * se
+        r = nat.sweep_pairs_host(dbeta, n_steps=200, z_max=100.0, save_every=se, **kw)
+        once = nat.sweep_pairs_host(dbeta, n_steps=m, z_max=0.5 * m, save_every=m, **kw)
+        assert (r["first_bad_step"] == -1).all() and np.isfinite(r["a_end"].view(float)).all()
+        assert np.array_equal(r["a_end"], once["a_end"]), se
+        assert np.array_equal(r["p_wave_end"], once["p_wave_end"]), se
+    r = nat.sweep_pairs_host(dbeta, n_steps=200, z_max=100.0, save_every=1000, **kw)
+    assert np.array_equal(r["a_end"], a0) and (r["first_bad_step"] == -1).all()
+
+
+@functools.lru_cache(maxsize=None)
+def _graded_failures():
+    """The inputs of test_gpu_lanes' replay test at K = 3: 60 of 331 points get a graded gain and blow up at step indices
+    spread over the run.  With them the block-mode run at save_every = 1: a block is a step there, so its index is the
+    per-step index and no replay is involved."""
+    n, N = 450, 331
+    rng = np.random.default_rng(7)
+    db = rng.uniform(-0.05, 0.05, N)
+    al = np.full(N, ALPHA)
+    hot = rng.choice(N, 60, replace=False)
+    al[hot] = -np.geomspace(1.0, 60.0, hot.size)
+    a0 = np.zeros(8, complex)
+    a0[:2], a0[2:] = np.sqrt(0.5), np.sqrt(1e-5)
+    dbeta = db[:, None] * np.linspace(1.0, 0.5, 3)
+    kw = dict(n_steps=n, z_max=45.0, gamma=GAMMA, alpha=al, a0=a0)
+    per_step = nat.sweep_pairs_host(dbeta, save_every=1, exact_step=False, **kw)["first_bad_step"]
+    return dbeta, kw, per_step
+
+
+@pytest.mark.parametrize("se", [7, 64, 1024])
+def test_exact_index_equals_the_per_step_index(se):
+    """The replay of a failing block repeats the forward pass, so the index it finds is the one a test after every step finds
+    -- inside saved blocks, across the 64-step re-seeds and (se = 1024) in a run without a saved row.  Block mode names the
+    block of that index, and finite points are bit-identical in both modes."""
+    n = 450
+    dbeta, kw, per_step = _graded_failures()
+    failed = per_step >= 0
+    print(f"failing points {failed.sum()}, distinct indices {len(set(per_step[failed]))}, largest {per_step.max()}")
+    assert failed.sum() >= 40 and len(set(per_step[failed])) >= 20 and per_step.max() >= 100
+    got = nat.sweep_pairs_host(dbeta, save_every=se, exact_step=True, **kw)
+    blk = nat.sweep_pairs_host(dbeta, save_every=se, exact_step=False, **kw)
+    assert np.array_equal(got["first_bad_step"], per_step)
+    exact, last_saved = per_step[failed], n // se * se
+    assert np.array_equal(blk["first_bad_step"][failed], np.where(exact // se * se + se <= last_saved, exact // se * se + se - 1, n - 1))
+    assert (blk["first_bad_step"][~failed] == -1).all()
+    for key in ("a_end", "p_wave_end", "p_wave_max"):
+        assert np.array_equal(got[key][~failed], blk[key][~failed]), key
+
+
 def test_device_entry_and_device_split_equal_the_host_entry_bit_for_bit():
     torch = pytest.importorskip("torch")
     N, K = 37, 11

@@ -218,6 +218,67 @@ def test_trajectory_rows(save_every):
         assert np.array_equal(dense[key], r[key], equal_nan=True), key
 
 
+@functools.lru_cache(maxsize=None)
+def _every_step_run():
+    """70 points (one full wave and a ragged one), 200 steps: every row of the trajectory, computed once."""
+    dbeta, a0, gamma, alpha = _inputs(70, 31, True, True)
+    kw = dict(n_steps=200, z_max=100.0, gamma=gamma, alpha=alpha, a0=a0)
+    every = nat.single_pump_host(dbeta, save_every=1, want_traj=True, **kw)
+    assert (every["first_bad_step"] == -1).all() and np.isfinite(every["traj"].view(float)).all()
+    return dbeta, kw, every["traj"]
+
+
+@pytest.mark.parametrize("se", [2, 3, 7, 10, 31, 64, 65, 100, 200, 1000])
+def test_the_stride_only_selects_rows(se):
+    """The re-seeds sit on the absolute step grid, so which rows are saved does not change the computed trajectory: the rows
+    at any stride are the same rows of the every-step run, bit for bit -- strides below, at and above RESYNC = 64, with and
+    without an unsaved tail, the whole run as one block, and no saved row at all (a_end is a0)."""
+    n = 200
+    dbeta, kw, every = _every_step_run()
+    r = nat.single_pump_host(dbeta, save_every=se, want_traj=True, **kw)
+    assert np.array_equal(r["traj"], every[:, ::se][:, :n // se + 1])
+    assert np.array_equal(r["a_end"], every[:, n // se * se])
+    dense = nat.single_pump_host(dbeta, save_every=se, **kw)
+    for key in ("a_end", "p_wave_end", "p_wave_max"):
+        assert np.array_equal(dense[key], r[key]), key
+
+
+@functools.lru_cache(maxsize=None)
+def _graded_failures():
+    """The inputs of test_gpu_lanes' replay test for this model: 60 of 331 points get a graded gain and blow up at step
+    indices spread over the run.  With them the block-mode run at save_every = 1: a block is a step there, so its index is
+    the per-step index and no replay is involved."""
+    n, N = 450, 331
+    rng = np.random.default_rng(7)
+    db = rng.uniform(-0.05, 0.05, N)
+    al = np.full(N, ALPHA)
+    hot = rng.choice(N, 60, replace=False)
+    al[hot] = -np.geomspace(1.0, 60.0, hot.size)
+    kw = dict(n_steps=n, z_max=45.0, gamma=GAMMA, alpha=al, a0=np.sqrt([0.5, 1e-5, 1e-5]).astype(complex))
+    per_step = nat.single_pump_host(db, save_every=1, exact_step=False, **kw)["first_bad_step"]
+    return db, kw, per_step
+
+
+@pytest.mark.parametrize("se", [7, 64, 1024])
+def test_exact_index_equals_the_per_step_index(se):
+    """The replay of a failing block repeats the forward pass, so the index it finds is the one a test after every step finds
+    -- inside saved blocks, across the 64-step re-seeds and (se = 1024) in a run without a saved row.  Block mode names the
+    block of that index, and finite points are bit-identical in both modes."""
+    n = 450
+    db, kw, per_step = _graded_failures()
+    failed = per_step >= 0
+    print(f"failing points {failed.sum()}, distinct indices {len(set(per_step[failed]))}, largest {per_step.max()}")
+    assert failed.sum() >= 40 and len(set(per_step[failed])) >= 20 and per_step.max() >= 100
+    got = nat.single_pump_host(db, save_every=se, exact_step=True, **kw)
+    blk = nat.single_pump_host(db, save_every=se, exact_step=False, **kw)
+    assert np.array_equal(got["first_bad_step"], per_step)
+    exact, last_saved = per_step[failed], n // se * se
+    assert np.array_equal(blk["first_bad_step"][failed], np.where(exact // se * se + se <= last_saved, exact // se * se + se - 1, n - 1))
+    assert (blk["first_bad_step"][~failed] == -1).all()
+    for key in ("a_end", "p_wave_end", "p_wave_max"):
+        assert np.array_equal(got[key][~failed], blk[key][~failed]), key
+
+
 def _device_run(torch, dbeta, gamma, alpha, a0, *, n_steps, z_max, save_every, flags, traj_ld=None):
     """psa_rk4_single_pump_f64_dev on torch buffers -> the host entry's dictionary (traj from a [rows][3][ld][2] buffer)."""
     dev = torch.device("cuda:0")
