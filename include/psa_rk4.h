@@ -446,6 +446,59 @@ int psa_rk4_single_pump_f64_dev(void *stream, int64_t n_points, int64_t n_steps,
                                 const double *d_a0_soa, uint32_t flags, double *d_a_end_soa, double *d_p_wave_end_soa,
                                 double *d_p_wave_max_soa, int64_t *d_first_bad_step, double *d_traj_soa_or_null);
 
+/* ---- a chain of single-pump spans with mid-stage transfers (copier - mid-stage - PSA on one pump) ------------------------
+ * psa_rk4_chain_* for the three-wave model above: S = n_segments >= 1 spans, each ONE launch of the
+ * unchanged single-pump kernel, joined on the device by the chain's epilogue kernel (no host synchronisation between spans).
+ * The kernel assumes nothing about which wave is strong, so the same entry point is the signal-degenerate dual-pump PSA
+ * with the roles relabelled: the degenerate signal in slot 0, the two pumps in slots 1 and 2, dbeta = beta_1 + beta_2 -
+ * 2 beta_s.  Span s has
+ *   n_steps[s], seg_len[s]   host arrays [S]; each n_steps[s] in [1, 2^31) and a multiple of save_every (else
+ *                            PSA_E_SAVE_EVERY), each seg_len[s] positive and finite
+ *   dbeta [S][N];  gamma, alpha  [S][N], or [S] with PSA_BCAST_GAMMA / PSA_BCAST_ALPHA
+ *   a0_re_im  [N][3][2] | [1][3][2] (PSA_BCAST_A0)
+ * and between span s and s+1 the per-wave complex transfer T_s[j] (amplitude gain times e^{i phase}):
+ *   transfer_re_im  [S-1][N][3][2], or [S-1][3][2] with PSA_BCAST_TRANSFER; NULL = identity
+ * Gauge.  The physical FWM factor is e^{+-i Theta(z)}, Theta = Theta_s + dbeta_s zeta, Theta_s = sum_{k<s} dbeta_k L_k (zeta:
+ * the span's local coordinate).  With B_s = A_s e^{+i Theta_s} for the signal (wave 1) and B = A for the pump and the idler,
+ * all three equations hold in B with the plain factor e^{+-i dbeta_s zeta} (the Kerr terms are phase-blind): the kernel runs
+ * each span unchanged, a boundary is B' = T_s B with the signal also multiplied by e^{+i dbeta_s L_s}, and reported
+ * amplitudes and rows are rotated back by e^{-i Theta_s} on wave 1.  Theta is kept per point in float64.
+ * Outputs, all in the physical (A) frame:
+ *   a_end_re_im [N][3][2], p_wave_end [N][3]   the last saved row of the last span
+ *   p_wave_max  [N][3]    max over every saved row of every span (each span's z = 0 row is the post-transfer state),
+ *                         NaN-propagating
+ *   first_bad_step [N]    cumulative step index (the earlier spans' n_steps + the local index); the first failure wins
+ *   traj_or_null  [N][rows_total][3][2], rows_total = sum_s (n_steps[s]/save_every + 1); the host form pads the device
+ *                 buffer itself and brings it home in the sweep's chunks
+ * S == 1 is psa_rk4_single_pump_f64(_dev) itself, bit for bit: no workspace, no epilogue.  The host form sets
+ * PSA_OPT_LOSSLESS per span: for a broadcast alpha of 0, or (S > 1) a per-point row that is 0 everywhere.
+ * flags: the four PSA_BCAST_* bits, PSA_OPT_CHECK_NAN, PSA_OPT_EXACT_STEP, PSA_OPT_LOSSLESS, PSA_OPT_BLOCK64 and, on the
+ * `_dev` form only, PSA_OPT_TRAJ_LD; anything else is PSA_E_FLAGS.  Every rule is checked before any device call, in the
+ * order n_segments < 1 (PSA_E_NSTEPS), n_steps / seg_len NULL, the single-pump rules on the first span's grid (n_points,
+ * n_steps, seg_len, save_every, flags, pointers, a trajectory's ld * 16 < 2^32 else PSA_E_TOO_LARGE), then every span's
+ * n_steps, seg_len and save_every multiple; a trajectory that does not fit the device is PSA_E_TOO_LARGE (host form).
+ * n_points == 0 is a successful no-op.  No new error code.
+ */
+int psa_rk4_single_pump_chain_f64(int device, int64_t n_points, int n_segments, const int64_t *n_steps,
+                                  const double *seg_len, int32_t save_every, const double *dbeta, const double *gamma,
+                                  const double *alpha, const double *a0_re_im, const double *transfer_re_im, uint32_t flags,
+                                  double *a_end_re_im, double *p_wave_end, double *p_wave_max, int64_t *first_bad_step,
+                                  double *traj_or_null, double *elapsed_ms_or_null);
+/* On SoA device buffers, asynchronous on `stream`, no allocation and no synchronisation: d_dbeta [S][N], d_gamma / d_alpha
+ * [S][N] | [S], d_a0_soa [6][N | 1], d_transfer_soa [S-1][6][N] (or [S-1][6] with PSA_BCAST_TRANSFER), d_a_end_soa [6][N],
+ * d_p_wave_end_soa / d_p_wave_max_soa [3][N], d_first_bad_step [N], d_traj_soa_or_null [rows_total][3][ld][2] with ld = N, or
+ * psa_traj_ld(N, 8) with PSA_OPT_TRAJ_LD; n_steps / seg_len stay HOST arrays.  d_workspace: at least
+ * psa_rk4_single_pump_chain_workspace_bytes(n_points) bytes of device memory; NULL with S > 1 is PSA_E_NULLPTR, S == 1 needs
+ * none.  `_dev` callers pass PSA_OPT_LOSSLESS for the whole chain. */
+int psa_rk4_single_pump_chain_f64_dev(void *stream, int64_t n_points, int n_segments, const int64_t *n_steps,
+                                      const double *seg_len, int32_t save_every, const double *d_dbeta,
+                                      const double *d_gamma, const double *d_alpha, const double *d_a0_soa,
+                                      const double *d_transfer_soa, uint32_t flags, double *d_a_end_soa,
+                                      double *d_p_wave_end_soa, double *d_p_wave_max_soa, int64_t *d_first_bad_step,
+                                      double *d_traj_soa_or_null, void *d_workspace);
+/* bytes of d_workspace for a single-pump chain; -1 for n_points < 0 */
+int64_t psa_rk4_single_pump_chain_workspace_bytes(int64_t n_points);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,11 @@ _SIGS = {
     # N, n_steps, z_max, save_every, dbeta, gamma, alpha, a0, flags, a_end, p_wave_end, p_wave_max, first_bad, traj; host: elapsed_ms
     **_family("psa_rk4_single_pump", [_L, _L, _D, _I32] + [_P] * 4 + [_U32] + [_P] * 5, host=[_P],
               host_types=("f64",), dev_types=("f64",)),
+    # N, S, n_steps[S], seg_len[S], save_every, dbeta, gamma, alpha, a0, transfer, flags, a_end, p_wave_end, p_wave_max, first_bad,
+    # traj; host: elapsed_ms; dev: workspace
+    **_family("psa_rk4_single_pump_chain", [_L, _I, _P, _P, _I32] + [_P] * 5 + [_U32] + [_P] * 5, host=[_P], dev=[_P],
+              host_types=("f64",), dev_types=("f64",)),
+    "psa_rk4_single_pump_chain_workspace_bytes": (_L, [_L]),
     "psa_yaman_rhs_f64": (_I, [_I, _L] + [_P] * 9),
     # N, p_metric, first_bad, p0_sig, gain_db, gain, best_index, best_gain, n_finite; dev: workspace
     **_family("psa_gain_summary", _GAIN, dev=[_P], host_types=("f64",), dev_types=("f64",)),
@@ -411,6 +416,63 @@ def single_pump_device(*, stream: int, n_points: int, n_steps: int, z_max: float
         stream or None, int(n_points), int(n_steps), float(z_max), int(save_every), d_dbeta or None, d_gamma or None,
         d_alpha or None, d_a0_soa or None, int(flags), d_a_end_soa or None, d_p_wave_end_soa or None,
         d_p_wave_max_soa or None, d_first_bad or None, d_traj_soa or None))
+
+
+def single_pump_chain_host(dbeta, *, n_steps, seg_len, save_every: int, gamma, alpha, a0, transfers=None,
+                           check_nan: bool = True, exact_step: Optional[bool] = None, want_traj: bool = False,
+                           device: int = 0, extra_flags: int = 0) -> dict:
+    """A chain of S single-pump spans on the GPU (psa_rk4_single_pump_chain_f64; host buffers in and out, float64).
+
+    dbeta (S, N); n_steps, seg_len (S,); gamma / alpha (S,) broadcast or (S, N); a0 (3,) or (N, 3) complex; transfers None,
+    (S-1, 3) broadcast or (S-1, N, 3) complex.  Returns the keys of single_pump_host; traj is (N, n_saved_total, 3)."""
+    dbeta = np.ascontiguousarray(np.asarray(dbeta), dtype=np.float64)
+    if dbeta.ndim != 2 or dbeta.shape[0] < 1:
+        raise ValueError("dbeta must have shape (S, N)")
+    S, N = (int(x) for x in dbeta.shape)
+    steps = np.ascontiguousarray(np.asarray(n_steps), dtype=np.int64)
+    lens = np.ascontiguousarray(np.asarray(seg_len), dtype=np.float64)
+    if steps.shape != (S,) or lens.shape != (S,):
+        raise ValueError(f"n_steps and seg_len must have shape ({S},)")
+    flags, gamma, alpha, a0, _ = _point_inputs(N, np.float64, np.complex128, int(extra_flags), gamma, alpha, a0, (3,), spans=S)
+    flags |= _check_flags(check_nan, exact_step)
+    tr = None
+    if transfers is not None and S > 1:
+        tr = np.ascontiguousarray(np.asarray(transfers), dtype=np.complex128)
+        if tr.shape == (S - 1, 3):
+            flags |= BCAST_TRANSFER
+        elif tr.shape != (S - 1, N, 3):
+            raise ValueError(f"transfers must have shape ({S - 1}, 3) or ({S - 1}, {N}, 3)")
+    n_rows = int(np.sum(steps // save_every + 1)) if save_every > 0 else 0
+    a_end = np.empty((N, 3), dtype=np.complex128)
+    w_end = np.empty((N, 3), dtype=np.float64)
+    w_max = np.empty((N, 3), dtype=np.float64)
+    bad = np.empty(N, dtype=np.int64)
+    traj = np.empty((N, n_rows, 3), dtype=np.complex128) if want_traj else None
+    ms = C.c_double(0.0)
+    _check(_fn("psa_rk4_single_pump_chain")(
+        int(device), N, S, _ptr(steps), _ptr(lens), int(save_every), _ptr(dbeta), _ptr(gamma), _ptr(alpha), _ptr(a0),
+        _ptr(tr), flags, _ptr(a_end), _ptr(w_end), _ptr(w_max), _ptr(bad), _ptr(traj), C.cast(C.byref(ms), _P)))
+    return dict(a_end=a_end, p_wave_end=w_end, p_wave_max=w_max, first_bad_step=bad, traj=traj, elapsed_ms=ms.value)
+
+
+def single_pump_chain_workspace_bytes(n_points: int) -> int:
+    """Device scratch a single-pump chain of more than one span needs (psa_rk4_single_pump_chain_workspace_bytes)."""
+    return int(lib().psa_rk4_single_pump_chain_workspace_bytes(int(n_points)))
+
+
+def single_pump_chain_device(*, stream: int, n_points: int, n_steps, seg_len, save_every: int, d_dbeta: int, d_gamma: int,
+                             d_alpha: int, d_a0_soa: int, d_transfer_soa: int, flags: int, d_a_end_soa: int,
+                             d_p_wave_end_soa: int, d_p_wave_max_soa: int, d_first_bad: int, d_traj_soa: int = 0,
+                             d_workspace: int = 0) -> None:
+    """psa_rk4_single_pump_chain_f64_dev on device pointers (ints); n_steps / seg_len are host sequences of length S."""
+    steps = np.ascontiguousarray(np.asarray(n_steps), dtype=np.int64)
+    lens = np.ascontiguousarray(np.asarray(seg_len), dtype=np.float64)
+    if steps.ndim != 1 or steps.shape != lens.shape:
+        raise ValueError("n_steps and seg_len must be 1-D of equal length")
+    _check(_fn("psa_rk4_single_pump_chain", dev=True)(
+        stream or None, int(n_points), int(steps.shape[0]), _ptr(steps), _ptr(lens), int(save_every), d_dbeta or None,
+        d_gamma or None, d_alpha or None, d_a0_soa or None, d_transfer_soa or None, int(flags), d_a_end_soa or None,
+        d_p_wave_end_soa or None, d_p_wave_max_soa or None, d_first_bad or None, d_traj_soa or None, d_workspace or None))
 
 
 def chain_host(dbeta, *, n_steps, seg_len, save_every: int, gamma, alpha, a0, transfers=None, dbeta2=None,

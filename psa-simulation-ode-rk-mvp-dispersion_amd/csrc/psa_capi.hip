@@ -116,6 +116,15 @@ struct ChainCall {   // psa_rk4_chain_*
     // of 0); `_dev` callers pass PSA_OPT_LOSSLESS for the whole chain instead
     const unsigned char *lossless = nullptr;
 };
+struct SinglePumpChainCall {   // psa_rk4_single_pump_chain_f64*
+    SinglePumpCall s;           // what the spans share; its n_steps and z_max are set span by span from the arrays below
+    int n_segments;
+    const int64_t *n_steps;     // host [S]
+    const double *seg_len;      // host [S]
+    const double *transfer;
+    void *workspace;            // device scratch of more than one span (single_pump_chain_workspace_bytes)
+    const unsigned char *lossless = nullptr;   // as ChainCall's
+};
 
 // The grid rules of every fixed-step family.  lanes_per_point: named in the message when the launch limit depends on it (0: not).
 int validate_grid(int64_t n_points, long long max_points, long long lanes_per_point, int64_t n_steps, double z_max,
@@ -715,7 +724,79 @@ int64_t chain_workspace_bytes(int n_waves, int64_t n_points, size_t elem, bool w
                      2 * C::aligned(N * elem) + C::aligned(N * 8) + (waves ? 2 * C::aligned((size_t)n_waves * N * elem) : 0));
 }
 
-// argument rules of psa_rk4_chain_*; *rows_total = sum over spans of n_steps[s] / save_every + 1
+// The part of span s's epilogue record that every chain family fills alike: the frame (Theta, the rows to rotate, the
+// A-frame a_end of the last span), first_bad_step with its step offset, and the boundary to span s + 1.  The family adds its
+// wave count, the index of its signal and its summary buffers.
+template <typename T>
+struct SpanJoin {
+    int64_t n_points;
+    int n_segments;
+    uint32_t flags;          // PSA_BCAST_TRANSFER is read here
+    const T *transfer;       // the chain's [S-1] transfers or nullptr
+    size_t transfer_step;    // elements from one boundary's transfer to the next
+    T *a_end, *a0_next, *a_end_s;
+    int64_t *first_bad, *first_bad_s;
+    double *theta;
+    size_t traj_ld;
+    psa::ChainEpilogue<T> record(int s, int64_t step_offset, T *span_traj, int64_t rows, const T *dbeta, double seg_len) const {
+        const bool first = s == 0, last = s == n_segments - 1;
+        psa::ChainEpilogue<T> e;
+        e.n = n_points;
+        e.first = first;
+        e.fold = !first;
+        e.a_end_s = a_end_s;
+        e.first_bad_s = (const long long *)first_bad_s;
+        e.first_bad = (long long *)first_bad;
+        e.step_offset = step_offset;
+        e.theta = theta;
+        e.traj = span_traj;
+        e.traj_ld = (long long)traj_ld;
+        e.rows = rows;
+        e.a_end_out = last ? a_end : nullptr;
+        e.transfer = (!last && transfer) ? transfer + s * transfer_step : nullptr;
+        e.transfer_stride = (flags & PSA_BCAST_TRANSFER) ? 0 : 1;
+        e.dbeta = dbeta;
+        e.seg_len = seg_len;
+        e.a0_next = a0_next;
+        return e;
+    }
+};
+
+// The grid rules of a chain's spans (every chain family); *rows_total = sum over spans of n_steps[s] / save_every + 1
+int validate_spans(int n_segments, const int64_t *n_steps, const double *seg_len, int32_t save_every, int64_t *rows_total) {
+    int64_t rows = 0;
+    for (int s = 0; s < n_segments; ++s) {
+        if (n_steps[s] <= 0 || n_steps[s] > 2147483647LL)
+            return fail(PSA_E_NSTEPS, "n_steps[%d] must be in [1, 2^31), got %lld", s, (long long)n_steps[s]);
+        if (!(seg_len[s] > 0.0) || !std::isfinite(seg_len[s])) return fail(PSA_E_ZMAX, "seg_len[%d] must be positive", s);
+        // a_end is the last saved row: a tail after it would silently shorten the span
+        if (n_steps[s] % save_every != 0)
+            return fail(PSA_E_SAVE_EVERY, "n_steps[%d] = %lld is not a multiple of save_every = %d", s,
+                        (long long)n_steps[s], (int)save_every);
+        rows += n_steps[s] / save_every + 1;
+    }
+    *rows_total = rows;
+    return PSA_OK;
+}
+
+// The reference's alpha == 0.0 branch, span by span, for the host-buffer chains: a broadcast 0, or (S > 1, where a lossy span
+// elsewhere makes the alpha array per point) a span whose row is 0 everywhere.  One span keeps the sweep's rule: bit-identical.
+template <typename T>
+std::vector<unsigned char> lossless_spans(uint32_t flags, const T *alpha, int S, size_t N) {
+    std::vector<unsigned char> lossless((size_t)S, 0);
+    for (int s = 0; s < S; ++s) {
+        bool zero = lossless_bit(flags, alpha + s) != 0;
+        if (!(flags & PSA_BCAST_ALPHA) && S > 1) {
+            const T *a = alpha + (size_t)s * N;
+            zero = true;
+            for (size_t i = 0; i < N && zero; ++i) zero = a[i] == T(0);
+        }
+        lossless[(size_t)s] = zero;
+    }
+    return lossless;
+}
+
+// argument rules of psa_rk4_chain_*
 template <typename T>
 int validate_chain(const ChainCall<T> &c, int64_t *rows_total) {
     if (c.n_segments < 1) return fail(PSA_E_NSTEPS, "n_segments must be >= 1, got %d", c.n_segments);
@@ -725,18 +806,8 @@ int validate_chain(const ChainCall<T> &c, int64_t *rows_total) {
     first.z_max = c.seg_len[0];
     int rc = validate_common(first);
     if (rc != PSA_OK) return rc;
-    const int32_t save_every = c.s.save_every;
     int64_t rows = 0;
-    for (int s = 0; s < c.n_segments; ++s) {
-        if (c.n_steps[s] <= 0 || c.n_steps[s] > 2147483647LL)
-            return fail(PSA_E_NSTEPS, "n_steps[%d] must be in [1, 2^31), got %lld", s, (long long)c.n_steps[s]);
-        if (!(c.seg_len[s] > 0.0) || !std::isfinite(c.seg_len[s])) return fail(PSA_E_ZMAX, "seg_len[%d] must be positive", s);
-        // a_end is the last saved row: a tail after it would silently shorten the span
-        if (c.n_steps[s] % save_every != 0)
-            return fail(PSA_E_SAVE_EVERY, "n_steps[%d] = %lld is not a multiple of save_every = %d", s,
-                        (long long)c.n_steps[s], (int)save_every);
-        rows += c.n_steps[s] / save_every + 1;
-    }
+    if ((rc = validate_spans(c.n_segments, c.n_steps, c.seg_len, c.s.save_every, &rows)) != PSA_OK) return rc;
     if ((c.s.wave_end != nullptr) != (c.s.wave_max != nullptr))
         return fail(PSA_E_NULLPTR, "p_wave_end and p_wave_max are given together or not at all");
     if (c.s.wave_end && (rc = validate_waves(c.s)) != PSA_OK) return rc;
@@ -786,9 +857,10 @@ int chain_dev(void *stream, const ChainCall<T> &c) {
     const size_t ld = (flags & PSA_OPT_TRAJ_LD) ? (size_t)traj_ld_of(c.s.n_points, sizeof(T)) : N;
     const size_t g_step = (flags & PSA_BCAST_GAMMA) ? 1 : N, a_step = (flags & PSA_BCAST_ALPHA) ? 1 : N;
     const size_t t_step = (flags & PSA_BCAST_TRANSFER) ? (size_t)nc : nc * N;
+    const SpanJoin<T> join{c.s.n_points, S, flags, c.transfer, t_step, c.s.a_end, a0_next, a_end_s, c.s.first_bad, bad_s, theta, ld};
     int64_t row = 0, step_off = 0;
     for (int s = 0; s < S; ++s) {
-        const bool first = s == 0, last = s == S - 1;
+        const bool first = s == 0;
         set_span(s);
         sp.dbeta = c.s.dbeta + s * N;
         sp.dbeta2 = c.s.dbeta2 ? c.s.dbeta2 + s * N : nullptr;
@@ -804,35 +876,19 @@ int chain_dev(void *stream, const ChainCall<T> &c) {
         sp.wave_max = waves ? (first ? c.s.wave_max : wmax_s) : nullptr;
         rc = sweep_dev<T>(stream, sp);
         if (rc != PSA_OK) return rc;
-        psa::ChainEpilogue<T> e;
-        e.n = c.s.n_points;
+        psa::ChainEpilogue<T> e = join.record(s, step_off, sp.traj, sp.n_steps / sp.save_every + 1, sp.dbeta, sp.z_max);
         e.n_waves = n_waves;
-        e.first = first;
-        e.fold = !first;
-        e.a_end_s = a_end_s;
+        e.sig_wave = 2;
         e.p_end_s = p_end_s;
         e.p_max_s = p_max_s;
-        e.first_bad_s = (const long long *)bad_s;
         e.wave_end_s = wend_s;
         e.wave_max_s = wmax_s;
         e.p_end = c.s.p_end;
         e.p_max = c.s.p_max;
-        e.first_bad = (long long *)c.s.first_bad;
         e.wave_end = c.s.wave_end;
         e.wave_max = c.s.wave_max;
-        e.step_offset = step_off;
-        e.theta = theta;
         e.theta2 = theta2;
-        e.traj = sp.traj;
-        e.traj_ld = (long long)ld;
-        e.rows = sp.n_steps / sp.save_every + 1;
-        e.a_end_out = last ? c.s.a_end : nullptr;
-        e.transfer = (!last && c.transfer) ? c.transfer + s * t_step : nullptr;
-        e.transfer_stride = (flags & PSA_BCAST_TRANSFER) ? 0 : 1;
-        e.dbeta = sp.dbeta;
         e.dbeta2 = sp.dbeta2;
-        e.seg_len = sp.z_max;
-        e.a0_next = a0_next;
         hipError_t he = EpilogueLaunch<T>::fn((hipStream_t)stream, e);
         if (he != hipSuccess) return hip_fail(he, "chain epilogue launch");
         row += e.rows;
@@ -852,18 +908,7 @@ int chain_host(int device, const ChainCall<T> &c, double *elapsed_ms) {
     const int S = c.n_segments, n_waves = c.s.n_waves, nc = 2 * n_waves;
     const size_t N = (size_t)c.s.n_points;
     const uint32_t flags = c.s.flags;
-    // the reference's alpha == 0.0 branch, span by span: a broadcast 0, or (S > 1, where a lossy span elsewhere makes the
-    // alpha array per point) a span whose row is 0 everywhere.  One span keeps psa_rk4_sweep_*'s rule: bit-identical.
-    std::vector<unsigned char> lossless((size_t)S, 0);
-    for (int s = 0; s < S; ++s) {
-        bool zero = lossless_bit(flags, c.s.alpha + s) != 0;
-        if (!(flags & PSA_BCAST_ALPHA) && S > 1) {
-            const T *a = c.s.alpha + (size_t)s * N;
-            zero = true;
-            for (size_t i = 0; i < N && zero; ++i) zero = a[i] == T(0);
-        }
-        lossless[(size_t)s] = zero;
-    }
+    const std::vector<unsigned char> lossless = lossless_spans(flags, c.s.alpha, S, N);
     ChainCall<T> d = c;
     if (c.s.traj) d.s.flags |= PSA_OPT_TRAJ_LD;
     d.lossless = lossless.data();
@@ -888,6 +933,137 @@ int chain_host(int device, const ChainCall<T> &c, double *elapsed_ms) {
         d.s.traj = sg.trajectory(c.s.traj, N, (size_t)rows_total, nc);
     };
     return host_call<T>(device, "the fibre chain", elapsed_ms, layout, [&](hipStream_t st) { return chain_dev<T>(st, d); });
+}
+
+// ---- single-pump chains (psa_rk4_single_pump_chain_f64*): the chain above for the three-wave model [p, s, i] ---------------
+// The same gauge with the signal at index 1; each span is one launch of the unchanged single-pump kernel, joined by the
+// same epilogue (sig_wave = 1, no p_end / p_max: this family always writes the three per-wave columns).
+// device scratch of more than one span: Theta, the next span's a0, the span's a_end, first_bad and per-wave summary
+int64_t single_pump_chain_workspace_bytes(int64_t n_points) {
+    if (n_points < 0) return -1;
+    using C = Carver;
+    const size_t N = (size_t)n_points;
+    return (int64_t)(C::aligned(N * 8) + 2 * C::aligned(6 * N * 8) + C::aligned(N * 8) + 2 * C::aligned(3 * N * 8));
+}
+
+// validate_chain's order on top of the single-pump rules (validate_single_pump on the first span's grid)
+int validate_single_pump_chain(const SinglePumpChainCall &c, bool host_form, int64_t *rows_total) {
+    if (c.n_segments < 1) return fail(PSA_E_NSTEPS, "n_segments must be >= 1, got %d", c.n_segments);
+    if (!c.n_steps || !c.seg_len) return fail(PSA_E_NULLPTR, "n_steps / seg_len is NULL");
+    SinglePumpCall first = c.s;
+    first.n_steps = c.n_steps[0];
+    first.z_max = c.seg_len[0];
+    first.flags &= ~PSA_BCAST_TRANSFER;   // the chain's own bit
+    int rc = validate_single_pump(first, host_form);
+    if (rc != PSA_OK) return rc;
+    int64_t rows = 0;
+    if ((rc = validate_spans(c.n_segments, c.n_steps, c.seg_len, c.s.save_every, &rows)) != PSA_OK) return rc;
+    if (c.s.traj && (long double)rows * 6 * (long double)traj_ld_of(c.s.n_points, sizeof(double)) > 4.0e18L)
+        return fail(PSA_E_TOO_LARGE, "trajectory buffer too large");
+    *rows_total = rows;
+    return PSA_OK;
+}
+
+int single_pump_chain_dev(void *stream, const SinglePumpChainCall &c) {
+    int64_t rows_total = 0;
+    int rc = validate_single_pump_chain(c, false, &rows_total);
+    if (rc != PSA_OK) return rc;
+    if (c.s.n_points == 0) return PSA_OK;
+    const int S = c.n_segments;
+    const uint32_t flags = c.s.flags;
+    SinglePumpCall sp = c.s;   // the span being run
+    auto set_span = [&](int s) {
+        sp.n_steps = c.n_steps[s];
+        sp.z_max = c.seg_len[s];
+        sp.flags = flags & ~PSA_BCAST_TRANSFER;
+        if (s > 0) sp.flags &= ~PSA_BCAST_A0;                  // the next span starts from a per-point state
+        if (c.lossless && c.lossless[s]) sp.flags |= PSA_OPT_LOSSLESS;
+    };
+    if (S == 1) {   // one span IS the sweep: same launch, same outputs, bit for bit
+        set_span(0);
+        return single_pump_dev(stream, sp);
+    }
+    if (!c.workspace) return fail(PSA_E_NULLPTR, "a chain of more than one span needs d_workspace");
+
+    const size_t N = (size_t)c.s.n_points;
+    Carver ws;
+    ws.base = (char *)c.workspace;
+    double *theta = ws.take<double>(N);
+    double *a0_next = ws.take<double>(6 * N);
+    double *a_end_s = ws.take<double>(6 * N);
+    int64_t *bad_s = ws.take<int64_t>(N);
+    double *wend_s = ws.take<double>(3 * N);
+    double *wmax_s = ws.take<double>(3 * N);
+
+    const size_t ld = (flags & PSA_OPT_TRAJ_LD) ? (size_t)traj_ld_of(c.s.n_points, sizeof(double)) : N;
+    const size_t g_step = (flags & PSA_BCAST_GAMMA) ? 1 : N, a_step = (flags & PSA_BCAST_ALPHA) ? 1 : N;
+    const size_t t_step = (flags & PSA_BCAST_TRANSFER) ? (size_t)6 : 6 * N;
+    const SpanJoin<double> join{c.s.n_points, S, flags, c.transfer, t_step, c.s.a_end, a0_next, a_end_s, c.s.first_bad, bad_s, theta, ld};
+    int64_t row = 0, step_off = 0;
+    for (int s = 0; s < S; ++s) {
+        const bool first = s == 0;
+        set_span(s);
+        sp.dbeta = c.s.dbeta + s * N;
+        sp.gamma = c.s.gamma + s * g_step;
+        sp.alpha = c.s.alpha + s * a_step;
+        sp.a0 = first ? c.s.a0 : a0_next;
+        sp.a_end = a_end_s;
+        sp.wave_end = first ? c.s.wave_end : wend_s;
+        sp.wave_max = first ? c.s.wave_max : wmax_s;
+        sp.first_bad = first ? c.s.first_bad : bad_s;
+        sp.traj = c.s.traj ? c.s.traj + (size_t)row * 3 * ld * 2 : nullptr;
+        rc = single_pump_dev(stream, sp);
+        if (rc != PSA_OK) return rc;
+        psa::ChainEpilogue<double> e = join.record(s, step_off, sp.traj, sp.n_steps / sp.save_every + 1, sp.dbeta, sp.z_max);
+        e.n_waves = 3;
+        e.sig_wave = 1;
+        e.p_end_s = e.p_max_s = nullptr;   // no signal summary in this family: the three per-wave columns are the summary
+        e.p_end = e.p_max = nullptr;
+        e.wave_end_s = wend_s;
+        e.wave_max_s = wmax_s;
+        e.wave_end = c.s.wave_end;
+        e.wave_max = c.s.wave_max;
+        e.theta2 = nullptr;
+        e.dbeta2 = nullptr;
+        hipError_t he = psa::launch_chain_epilogue_f64((hipStream_t)stream, e);
+        if (he != hipSuccess) return hip_fail(he, "chain epilogue launch");
+        row += e.rows;
+        step_off += sp.n_steps;
+    }
+    return PSA_OK;
+}
+
+int single_pump_chain_host(int device, const SinglePumpChainCall &c, double *elapsed_ms) {
+    int64_t rows_total = 0;
+    int rc = validate_single_pump_chain(c, true, &rows_total);
+    if (rc != PSA_OK) return rc;
+    if (elapsed_ms) *elapsed_ms = 0.0;
+    if (c.s.n_points == 0) return PSA_OK;
+
+    const int S = c.n_segments;
+    const size_t N = (size_t)c.s.n_points;
+    const uint32_t flags = c.s.flags;
+    const std::vector<unsigned char> lossless = lossless_spans(flags, c.s.alpha, S, N);
+    SinglePumpChainCall d = c;
+    if (c.s.traj) d.s.flags |= PSA_OPT_TRAJ_LD;   // the device-side trajectory has its own leading dimension; the caller's is dense
+    d.lossless = lossless.data();
+    const double *tr = S > 1 ? c.transfer : nullptr;
+    auto layout = [&](Staging<double> &sg) {
+        d.s.dbeta = sg.input(c.s.dbeta, S * N);
+        d.s.gamma = sg.input(c.s.gamma, (flags & PSA_BCAST_GAMMA) ? (size_t)S : S * N);
+        d.s.alpha = sg.input(c.s.alpha, (flags & PSA_BCAST_ALPHA) ? (size_t)S : S * N);
+        d.s.a0 = sg.input_soa(c.s.a0, (flags & PSA_BCAST_A0) ? 1 : N, 6);
+        // [S-1][3][2] is already [S-1][6]; [S-1][N][3][2] -> [S-1][6][N]
+        d.transfer = (flags & PSA_BCAST_TRANSFER) ? sg.input(tr, (size_t)(S - 1) * 6) : sg.input_soa(tr, N, 6, S - 1);
+        d.workspace = S > 1 ? sg.template scratch<char>((size_t)single_pump_chain_workspace_bytes(c.s.n_points)) : nullptr;
+        d.s.a_end = sg.output_soa(c.s.a_end, N, 6);
+        d.s.wave_end = sg.output_soa(c.s.wave_end, N, 3);
+        d.s.wave_max = sg.output_soa(c.s.wave_max, N, 3);
+        d.s.first_bad = sg.output(c.s.first_bad, N);
+        d.s.traj = sg.trajectory(c.s.traj, N, (size_t)rows_total, 6);
+    };
+    return host_call<double>(device, "the single-pump fibre chain", elapsed_ms, layout,
+                             [&](hipStream_t st) { return single_pump_chain_dev(st, d); });
 }
 
 template <typename T> struct GainLaunch;
@@ -1396,5 +1572,26 @@ int psa_rk4_single_pump_f64_dev(void *stream, int64_t n_points, int64_t n_steps,
     return single_pump_dev(stream, {n_points, n_steps, z_max, save_every, d_dbeta, d_gamma, d_alpha, d_a0_soa, flags,
                                     d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step, d_traj_soa_or_null});
 }
+
+// the chain's record: the spans' shared part has no grid of its own (n_steps 0, z_max 0: set span by span)
+int psa_rk4_single_pump_chain_f64(int device, int64_t n_points, int n_segments, const int64_t *n_steps, const double *seg_len,
+                                  int32_t save_every, const double *dbeta, const double *gamma, const double *alpha,
+                                  const double *a0_re_im, const double *transfer_re_im, uint32_t flags, double *a_end_re_im,
+                                  double *p_wave_end, double *p_wave_max, int64_t *first_bad_step, double *traj_or_null,
+                                  double *elapsed_ms_or_null) {
+    return single_pump_chain_host(device, {{n_points, 0, 0.0, save_every, dbeta, gamma, alpha, a0_re_im, flags, a_end_re_im,
+                                            p_wave_end, p_wave_max, first_bad_step, traj_or_null}, n_segments, n_steps,
+                                           seg_len, transfer_re_im, nullptr}, elapsed_ms_or_null);
+}
+int psa_rk4_single_pump_chain_f64_dev(void *stream, int64_t n_points, int n_segments, const int64_t *n_steps,
+                                      const double *seg_len, int32_t save_every, const double *d_dbeta, const double *d_gamma,
+                                      const double *d_alpha, const double *d_a0_soa, const double *d_transfer_soa,
+                                      uint32_t flags, double *d_a_end_soa, double *d_p_wave_end_soa, double *d_p_wave_max_soa,
+                                      int64_t *d_first_bad_step, double *d_traj_soa_or_null, void *d_workspace) {
+    return single_pump_chain_dev(stream, {{n_points, 0, 0.0, save_every, d_dbeta, d_gamma, d_alpha, d_a0_soa, flags,
+                                           d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step,
+                                           d_traj_soa_or_null}, n_segments, n_steps, seg_len, d_transfer_soa, d_workspace});
+}
+int64_t psa_rk4_single_pump_chain_workspace_bytes(int64_t n_points) { return single_pump_chain_workspace_bytes(n_points); }
 
 }  // extern "C"

@@ -5,6 +5,8 @@
 // zeta}; the physical factor is e^{+-i Theta(z)}, Theta(z) = Theta_s + dbeta_s zeta, Theta_s = sum_{k<s} dbeta_k L_k.  The
 // kernels therefore integrate B with B_sig = A_sig e^{+i Theta_s} and every other wave equal to A (a3 a4 = b3 b4 e^{-i
 // Theta_s}; the Kerr terms are phase-blind).  Six waves: the signal of pair k (waves 2 and 4) takes its own Theta^(k).
+// Three waves [p, s, i] (the single-pump model, psa_rk4_single_pump_chain_*): the same rule with the signal at index 1
+// (a_s a_i = b_s b_i e^{-i Theta_s}); `sig_wave` names the index, and that family has no p_end / p_max (both null).
 // At the boundary s -> s+1 the next span starts from B'_j = T_s[j] B_j, times e^{+i dbeta_s L_s} for the signal(s);
 // reported amplitudes are brought back to A with e^{-i Theta_s}.  Theta is kept per point in float64 in HBM for both
 // precisions (the kernels form dbeta*z in float64 as well).
@@ -41,11 +43,13 @@ __global__ void __launch_bounds__(256) chain_epilogue_kernel(ChainEpilogue<T> e)
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= e.n) return;
     const long long n = e.n;
-    const int nw = e.n_waves;
+    const int nw = e.n_waves, sig = e.sig_wave;
 
     if (e.fold) {
-        nanmax_into(e.p_max[i], e.p_max_s[i]);
-        e.p_end[i] = e.p_end_s[i];
+        if (e.p_max) {
+            nanmax_into(e.p_max[i], e.p_max_s[i]);
+            e.p_end[i] = e.p_end_s[i];
+        }
         const long long b = e.first_bad_s[i];
         if (e.first_bad[i] < 0 && b >= 0) e.first_bad[i] = b + e.step_offset;
         if (e.wave_end) {
@@ -68,7 +72,7 @@ __global__ void __launch_bounds__(256) chain_epilogue_kernel(ChainEpilogue<T> e)
     if (e.traj && !e.first) {
         // rows [0, rows) of this span, (re, im) pairs at ((row * nw + w) * ld + i) * 2
         for (long long r = 0; r < e.rows; ++r) {
-            T *p = e.traj + ((r * nw + 2) * e.traj_ld + i) * 2;
+            T *p = e.traj + ((r * nw + sig) * e.traj_ld + i) * 2;
             rotate(p[0], p[1], c1, s1);
             if (nw == 6) {
                 T *q = e.traj + ((r * nw + 4) * e.traj_ld + i) * 2;
@@ -80,7 +84,7 @@ __global__ void __launch_bounds__(256) chain_epilogue_kernel(ChainEpilogue<T> e)
     if (e.a_end_out) {   // last span: the state in the A frame
         for (int c = 0; c < 2 * nw; ++c) e.a_end_out[(long long)c * n + i] = e.a_end_s[(long long)c * n + i];
         if (!e.first) {
-            rotate(e.a_end_out[4 * n + i], e.a_end_out[5 * n + i], c1, s1);
+            rotate(e.a_end_out[(long long)(2 * sig) * n + i], e.a_end_out[(long long)(2 * sig + 1) * n + i], c1, s1);
             if (nw == 6) rotate(e.a_end_out[8 * n + i], e.a_end_out[9 * n + i], c2, s2);
         }
         return;
@@ -93,9 +97,9 @@ __global__ void __launch_bounds__(256) chain_epilogue_kernel(ChainEpilogue<T> e)
     if (nw == 6) e.theta2[i] = th2 + ph2;
     for (int w = 0; w < nw; ++w) {
         T re = e.a_end_s[(long long)(2 * w) * n + i], im = e.a_end_s[(long long)(2 * w + 1) * n + i];
-        if (w == 2 || (nw == 6 && w == 4)) {
+        if (w == sig || (nw == 6 && w == 4)) {
             double sp, cp;
-            sincos(w == 2 ? ph1 : ph2, &sp, &cp);
+            sincos(w == sig ? ph1 : ph2, &sp, &cp);
             rotate(re, im, cp, sp);
         }
         if (e.transfer) {

@@ -137,13 +137,14 @@ template <typename T>
 struct ChainEpilogue {
     long long n;
     int n_waves;
+    int sig_wave;               // the wave that carries Theta: 2 (4 and 6 waves; 6 waves: wave 4 carries theta2), 1 (3 waves)
     int first;                  // span 0: Theta_0 = 0, no rotation, `theta` is initialised by the boundary
     int fold;                   // spans >= 1: fold the span's summary (the *_s buffers) into the running outputs
     const T *a_end_s;           // [2*NW][n] the span's a_end (B frame)
     const T *p_end_s, *p_max_s; // [n]
     const long long *first_bad_s;
     const T *wave_end_s, *wave_max_s;   // [NW][n] or nullptr
-    T *p_end, *p_max;           // running outputs
+    T *p_end, *p_max;           // running outputs; both nullptr for a family without a signal summary (3 waves)
     long long *first_bad;
     T *wave_end, *wave_max;     // [NW][n] or nullptr
     long long step_offset;      // steps of the spans before this one

@@ -10,6 +10,8 @@
 * ``seeded_mismatch_scan(gain_mode)``: the scenario that dead function hard-codes (:56-93), run: delta, Gs, Gi, best point.
 * ``scan_copier_psa_phase(...)``: signal gain of a copier - mid-stage - PSA chain against the mid-stage phase (optionally
   times the PSA span's dbeta) in one chain launch, with its maximum, minimum and extinction (no reference counterpart).
+* ``scan_single_pump_copier_psa_phase(...)``: the same scan for the single-pump three-wave model [p, s, i], with the
+  idler's gain next to the signal's.
 * ``scan_gain_grid(...)``: the same sweep over a 2-D (pump-2 wavelength x signal wavelength) grid in one launch
   (BASELINE config 3's shape: 1024 x 1024 points); the reference has no grid builder.
 * ``scan_six_wave_grid(...)``: BASELINE config 5's shape -- a grid over the detunings (Omega1, Omega2) of two
@@ -836,3 +838,87 @@ def scan_copier_psa_phase(*, psa_cfg: SimulationConfig, psa_delta_beta, gamma: f
     shape = (K, M) if dbp.ndim == 1 else (K,)
     return dict(phase=ph, psa_delta_beta=dbp, gain=np.asarray(gain).reshape(shape), gain_max_db=gmax, gain_min_db=gmin,
                 extinction_db=gmax - gmin, result=res)
+
+
+def scan_single_pump_copier_psa_phase(*, psa_cfg: SimulationConfig, psa_delta_beta, gamma: float, alpha: float,
+                                      p_in: Sequence[float], phase_in: Optional[Sequence[float]] = None,
+                                      copier_cfg: Optional[SimulationConfig] = None, copier_delta_beta: float = 0.0,
+                                      copier_gamma: Optional[float] = None, copier_alpha: Optional[float] = None,
+                                      mid_gain_db: Sequence[float] = (0.0, 0.0, 0.0),
+                                      mid_phase: Sequence[float] = (0.0, 0.0, 0.0), phase: Optional[Sequence[float]] = None,
+                                      phase_wave="pump", length_unit: str = "m", gain_mode: GainMode = "max",
+                                      gain_unit: str = "dB", device: Optional[int] = None,
+                                      devices: Optional[Sequence[int]] = None) -> dict:
+    """scan_copier_psa_phase for the single-pump model, waves [p, s, i] (no reference counterpart): the
+    signal and idler gain of a copier - mid-stage - PSA chain on one pump against the mid-stage phase.
+
+    An optional copier span (``copier_cfg``: length, dz; its own dbeta, gamma, alpha -- gamma / alpha default to the PSA
+    span's) makes the phase-conjugated idler; the mid-stage applies ``mid_gain_db`` / ``mid_phase`` per wave plus the
+    scanned ``phase`` (K values, default 32 over [0, 2 pi)) on ``phase_wave`` -- "pump" or a wave index 0..2; the PSA span
+    (``psa_cfg``) then amplifies phase-sensitively.  ``psa_delta_beta`` a scalar or M values: the scan runs K x M chains in
+    ONE launch per span with per-point transfers.  Without a copier the mid-stage acts on the input.  dbeta in
+    1/length_unit, gamma / alpha per length_unit; save_every and check_nan come from psa_cfg (the copier's must agree, and
+    every span's step count must be a multiple of save_every).  Sharding over a process group is out of scope here.
+
+    gain / gain_idler: (K,) or (K, M), the signal's / the idler's gain_mode metric over every saved row of the chain over
+    p_in[1], with the drivers' NaN rule for every point with first_bad_step >= 0.  Returns dict(phase, psa_delta_beta, gain,
+    gain_idler, gain_max_db, gain_min_db, extinction_db (max - min over the signal's finite gains, dB),
+    result=SinglePumpChainResult)."""
+    from .simulation import single_pump_mid_stage
+    from .sweep import FibreSpan, initial_amplitudes, rk4_chain_single_pump
+    unit = check_gain(gain_mode, gain_unit)
+    ph = np.linspace(0.0, 2.0 * np.pi, 32, endpoint=False) if phase is None else np.asarray(phase, dtype=float)
+    if ph.ndim != 1 or ph.size == 0 or not np.all(np.isfinite(ph)):
+        raise ValueError("phase must be a non-empty 1D sequence of finite values")
+    dbp = np.asarray(psa_delta_beta, dtype=float)
+    if dbp.ndim > 1 or dbp.size == 0 or not np.all(np.isfinite(dbp)):
+        raise ValueError("psa_delta_beta must be a finite scalar or a non-empty 1D sequence")
+    if isinstance(phase_wave, str) and phase_wave == "pump":
+        mask = np.eye(3)[0]
+    elif isinstance(phase_wave, (int, np.integer)) and not isinstance(phase_wave, bool) and 0 <= int(phase_wave) < 3:
+        mask = np.eye(3)[int(phase_wave)]
+    else:
+        raise ValueError("phase_wave must be 'pump' or a wave index 0..2")
+    p0 = np.asarray(list(p_in), dtype=float)
+    if p0.shape != (3,) or not np.all(np.isfinite(p0)) or np.any(p0 < 0.0):
+        raise ValueError("p_in must hold 3 finite non-negative powers [pump, signal, idler]")
+    if not p0[1] > 0.0:
+        raise ValueError("p_in[1] (signal seed) must be > 0 to define gain")
+    ph0 = None if phase_in is None else np.asarray(list(phase_in), dtype=float)
+    if ph0 is not None and (ph0.shape != (3,) or not np.all(np.isfinite(ph0))):
+        raise ValueError("phase_in must hold 3 finite phases")
+    provided = PhaseMatchingConfig(method=PhaseMatchingMethod.PROVIDED, provided_delta_beta=0.0)
+    cfgs = [psa_cfg] if copier_cfg is None else [copier_cfg, psa_cfg]
+    pres = [_prepare(c, gamma=0.0, alpha=0.0, dispersion=None, phase_matching_cfg=provided, beta_legacy=None,
+                     length_unit=length_unit) for c in cfgs]
+    if any(int(c.save_every) != int(psa_cfg.save_every) or bool(c.check_nan) != bool(psa_cfg.check_nan) for c in cfgs):
+        raise ValueError("copier_cfg and psa_cfg must share save_every and check_nan")
+    scale = pres[0]["scale"]
+    K, M = ph.size, max(dbp.size, 1)
+    db_pts = np.tile(np.atleast_1d(dbp), K) / scale                              # point k * M + m
+    T = single_pump_mid_stage(np.broadcast_to(np.asarray(mid_gain_db, dtype=float), (3,)),
+                              np.broadcast_to(np.asarray(mid_phase, dtype=float), (3,))[None, :]
+                              + ph[:, None] * mask[None, :])                     # (K, 3)
+    T = np.repeat(T, M, axis=0)                                                  # (K * M, 3)
+    a_in = initial_amplitudes(p0, ph0)
+    psa = FibreSpan(pres[-1]["fiber"].length_m, dz=pres[-1]["grid"].dz_m, dbeta=db_pts, gamma=float(gamma) / scale,
+                    alpha=float(alpha) / scale)
+    if copier_cfg is None:
+        spans, transfers, a0 = [psa], None, T * a_in[None, :]
+    else:
+        cg = gamma if copier_gamma is None else copier_gamma
+        ca = alpha if copier_alpha is None else copier_alpha
+        copier = FibreSpan(pres[0]["fiber"].length_m, dz=pres[0]["grid"].dz_m, dbeta=float(copier_delta_beta) / scale,
+                           gamma=float(cg) / scale, alpha=float(ca) / scale)
+        spans, transfers, a0 = [copier, psa], [T], a_in
+    res = rk4_chain_single_pump(spans, a0=a0, transfers=transfers, save_every=int(psa_cfg.save_every),
+                                check_nan=bool(psa_cfg.check_nan), device=(0 if device is None else int(device)),
+                                devices=devices)
+    gain_db = res.signal_gain(p0[1], mode=gain_mode, unit="dB")
+    finite = np.isfinite(gain_db)
+    gmax = float(np.max(gain_db[finite])) if finite.any() else float("nan")
+    gmin = float(np.min(gain_db[finite])) if finite.any() else float("nan")
+    shape = (K, M) if dbp.ndim == 1 else (K,)
+    return dict(phase=ph, psa_delta_beta=dbp, gain=res.signal_gain(p0[1], mode=gain_mode, unit=unit).reshape(shape),
+                gain_idler=res.idler_conversion(p0[1], mode=gain_mode, unit=unit).reshape(shape), gain_max_db=gmax,
+                gain_min_db=gmin, extinction_db=gmax - gmin, result=res)

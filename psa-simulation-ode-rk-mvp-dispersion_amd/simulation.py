@@ -19,7 +19,7 @@ from .dispersion import DispersionParams, delta_beta_from_omegas_array
 from .integrators import integrate_adaptive, integrate_interval
 from .parameters import FiberParams, PhaseMatchingParams, SimulationGrid, WavesParams, make_model_params
 from .phase_matching import PhaseMatchingConfig, PhaseMatchingMethod, PhaseMatchingResult, compute_phase_mismatch  # noqa: F401
-from .sweep import FibreSpan, initial_amplitudes, rk4_chain, rk4_sweep_single_pump
+from .sweep import FibreSpan, initial_amplitudes, rk4_chain, rk4_chain_single_pump, rk4_sweep_single_pump
 from .yaman_model import rhs_yaman_simplified
 
 _UNITS = {"m": 1.0, "km": 1000.0}
@@ -292,6 +292,84 @@ def run_concatenated_simulation(spans, *, omega: Sequence[float], p_in: Sequence
             raise ValueError(f"transfers must be {len(spans) - 1} per-wave factors of shape (4,)")
     r = rk4_chain(fibre, a0=A0, transfers=transfers, save_every=save_every, check_nan=check_nan, exact_step=True,
                   want_traj=True)
+    bad = int(r.first_bad_step[0])
+    if check_nan and bad >= 0:
+        k = int(np.searchsorted(r.step_offsets, bad, side="right")) - 1
+        raise FloatingPointError(f"NaN or Inf detected at step {bad} (span {k}, local step {bad - r.step_offsets[k]})")
+    out_unit = length_unit if return_length_unit is None else return_length_unit
+    return r.z_out / _length_scale_to_m(out_unit), r.traj[0]
+
+
+def single_pump_mid_stage(gain_db=(0.0, 0.0, 0.0), phase=(0.0, 0.0, 0.0)) -> np.ndarray:
+    """mid_stage for the single-pump model's three waves [p, s, i]: sqrt(10^(gain_db/10)) e^{i phase}.  The last axis is the
+    wave (3 entries); leading axes (one row per sweep point) broadcast."""
+    g, ph = np.broadcast_arrays(np.asarray(gain_db, dtype=float), np.asarray(phase, dtype=float))
+    if g.ndim == 0 or g.shape[-1] != 3:
+        raise ValueError("single_pump_mid_stage: gain_db / phase need one entry per wave (3)")
+    if not (np.all(np.isfinite(g)) and np.all(np.isfinite(ph))):
+        raise ValueError("single_pump_mid_stage: gain_db and phase must be finite")
+    return np.sqrt(10.0 ** (g / 10.0)) * np.exp(1j * ph)
+
+
+def run_concatenated_single_pump_simulation(spans, *, omega_pump: float, omega_signal: float, p_in: Sequence[float],
+                                            phase_in: Optional[Sequence[float]] = None, transfers=None,
+                                            length_unit: str = "m",
+                                            return_length_unit: Optional[str] = None) -> tuple[np.ndarray, np.ndarray]:
+    """run_single_pump_simulation over a chain of spans -> (z_out, A complex128 (n_saved_total, 3)), waves [p, s, i].
+
+    ``spans``: one mapping per span with ``cfg`` (SimulationConfig: length z_max, dz, save_every, check_nan), ``gamma``,
+    ``alpha`` and either ``dispersion`` (with an optional ``max_order``, default 4: dbeta = beta(w_s) + beta(w_i) -
+    2 beta(w_p) from delta_beta_from_omegas_array on [w_p, w_p, w_s, 2 w_p - w_s], as run_single_pump_simulation forms it)
+    or a ``phase_matching_cfg`` of method PROVIDED carrying the span's dbeta, all in ``length_unit``.  ``transfers``: None
+    or S-1 complex (3,) per-wave factors (single_pump_mid_stage).  The FWM phase accumulates over the spans; rows are those
+    of every span in order, each span's z = 0 row being the post-transfer state (z repeats at a boundary).  save_every and
+    check_nan must agree between spans; with check_nan a non-finite state raises FloatingPointError at the chain's step
+    index."""
+    spans = list(spans)
+    if not spans:
+        raise ValueError("spans must name at least one span")
+    _length_scale_to_m(length_unit)
+    wp, ws = _positive_omega(omega_pump, "omega_pump"), _positive_omega(omega_signal, "omega_signal")
+    wi = 2.0 * wp - ws
+    if wi <= 0.0:
+        raise ValueError("the idler frequency 2*omega_pump - omega_signal must be positive")
+    A0 = initial_amplitudes(_vec3(p_in, "p_in", what="non-negative (W)", lower=0.0),
+                            np.zeros(3) if phase_in is None else _vec3(phase_in, "phase_in", what=""))
+    fibre, cfgs = [], []
+    for k, sp in enumerate(spans):
+        sp = dict(sp)
+        unknown = set(sp) - {"cfg", "gamma", "alpha", "dispersion", "max_order", "phase_matching_cfg"}
+        if unknown or "cfg" not in sp or "gamma" not in sp or "alpha" not in sp:
+            raise ValueError(f"span {k}: needs cfg, gamma, alpha (+ dispersion / phase_matching_cfg); "
+                             f"unknown keys {sorted(unknown)}")
+        pm, disp = sp.get("phase_matching_cfg"), sp.get("dispersion")
+        if (pm is None) == (disp is None):
+            raise ValueError(f"span {k}: needs exactly one of dispersion and phase_matching_cfg")
+        if pm is not None and (not isinstance(pm, PhaseMatchingConfig) or pm.method != PhaseMatchingMethod.PROVIDED):
+            raise ValueError(f"span {k}: phase_matching_cfg must be a PhaseMatchingConfig of method PROVIDED")
+        max_order = sp.get("max_order", 4)
+        if not isinstance(max_order, int) or max_order < 0:
+            raise ValueError(f"span {k}: max_order must be a non-negative int")
+        pre = _prepare(sp["cfg"], gamma=sp["gamma"], alpha=sp["alpha"], dispersion=disp, phase_matching_cfg=pm,
+                       beta_legacy=None, length_unit=length_unit)
+        fiber, grid = pre["fiber"], pre["grid"]
+        if pm is not None:
+            dbeta = float(pre["pm"].config.provided_delta_beta)
+        else:
+            dbeta = float(delta_beta_from_omegas_array(np.array([wp, wp, ws, wi]), fiber.dispersion, max_order=max_order))
+        if not np.isfinite(dbeta):
+            raise ValueError(f"span {k}: the phase mismatch is not finite")
+        fibre.append(FibreSpan(length=fiber.length_m, dz=grid.dz_m, dbeta=dbeta, gamma=fiber.gamma_W_m, alpha=fiber.alpha_1_m))
+        cfgs.append(sp["cfg"])
+    save_every, check_nan = int(cfgs[0].save_every), bool(cfgs[0].check_nan)
+    if any(int(c.save_every) != save_every or bool(c.check_nan) != check_nan for c in cfgs):
+        raise ValueError("all spans must share save_every and check_nan")
+    if transfers is not None:
+        transfers = [np.asarray(t, dtype=np.complex128) for t in transfers]
+        if len(transfers) != len(spans) - 1 or any(t.shape != (3,) for t in transfers):
+            raise ValueError(f"transfers must be {len(spans) - 1} per-wave factors of shape (3,)")
+    r = rk4_chain_single_pump(fibre, a0=A0, transfers=transfers, save_every=save_every, check_nan=check_nan,
+                              exact_step=True, want_traj=True)
     bad = int(r.first_bad_step[0])
     if check_nan and bad >= 0:
         k = int(np.searchsorted(r.step_offsets, bad, side="right")) - 1

@@ -18,8 +18,9 @@ from . import _native
 from ._partition import CHAIN_AXES, PAIRS_AXES, SWEEP_AXES, over_devices
 from .config import AdaptiveConfig, n_steps_of
 
-__all__ = ["AdaptiveResult", "ChainResult", "FibreSpan", "PairsResult", "SinglePumpResult", "SweepResult", "check_gain",
-           "initial_amplitudes", "rk4_chain", "rk4_sweep", "rk4_sweep_pairs", "rk4_sweep_single_pump", "rk45_sweep"]
+__all__ = ["AdaptiveResult", "ChainResult", "FibreSpan", "PairsResult", "SinglePumpChainResult", "SinglePumpResult",
+           "SweepResult", "check_gain", "initial_amplitudes", "rk4_chain", "rk4_chain_single_pump", "rk4_sweep",
+           "rk4_sweep_pairs", "rk4_sweep_single_pump", "rk45_sweep"]
 
 
 def initial_amplitudes(p_in, phase_in=None) -> np.ndarray:
@@ -272,7 +273,7 @@ def rk4_sweep_single_pump(dbeta, *, z_max: float, dz: Optional[float] = None, n_
     dbeta (N,): beta(w_s) + beta(w_i) - 2 beta(w_p) per point; gamma / alpha a scalar or (N,); a0 (3,) or (N, 3) complex.
     ``dz`` gives n = int(round(z_max/dz)) as integrators.py:194; or pass ``n_steps``.  ``want_traj`` also returns every saved
     row; ``devices=[0, 1, ...]`` splits the points (and the trajectory) over several GPUs of this process.  Fixed-step
-    float64 only: no float32, chain or adaptive form."""
+    float64 only: no float32 or adaptive form; concatenated spans (copier - mid-stage - PSA) are rk4_chain_single_pump."""
     n_steps, save_every = _fixed_grid(z_max, dz, n_steps, save_every)
     db = np.atleast_1d(np.asarray(dbeta, dtype=float))
     if db.ndim != 1:
@@ -335,14 +336,10 @@ def _span_column(values, S: int, N: int, name: str, dtype) -> np.ndarray:
     return np.stack([np.broadcast_to(a, (N,)) for a in arrs]).astype(dtype)
 
 
-def rk4_chain(spans: Sequence[FibreSpan], *, a0, transfers=None, save_every: int = 10, check_nan: bool = True,
-              exact_step: Optional[bool] = None, dtype=np.float64, want_traj: bool = False, wave_summary: bool = False,
-              device: int = 0, devices: Optional[Sequence[int]] = None) -> ChainResult:
-    """Propagate N points through a chain of fibre spans (psa_rk4_chain_*): each span one launch of the sweep kernel,
-    the mismatch phase accumulated across spans, ``transfers[s]`` applied between span s and s+1.
-
-    transfers: None (identity), or S-1 entries, each (n_waves,) complex for every point or (N, n_waves) per point
-    (see simulation.mid_stage).  Every span's n_steps must be a multiple of ``save_every``."""
+def _chain_inputs(spans, a0, transfers, save_every, widths, dtype):
+    """The span, a0 and transfer rules every chain shares, in rk4_chain's order -> (spans, save_every, dtype, N, n_waves,
+    dbeta (S, N), dbeta2 (S, N) for 6 waves else None, gamma, alpha (S,) | (S, N), transfers None | (S-1, n_waves) |
+    (S-1, N, n_waves), n_steps (S,), lengths (S,))."""
     spans = list(spans)
     if not spans or not all(isinstance(s, FibreSpan) for s in spans):
         raise ValueError("spans must be a non-empty sequence of FibreSpan")
@@ -355,8 +352,8 @@ def rk4_chain(spans: Sequence[FibreSpan], *, a0, transfers=None, save_every: int
     dtype = np.dtype(dtype)
     S = len(spans)
     a0 = np.asarray(a0)
-    if a0.ndim not in (1, 2) or a0.shape[-1] not in (4, 6):
-        raise ValueError("a0 must have shape (n_waves,) or (N, n_waves) with n_waves in (4, 6)")
+    if a0.ndim not in (1, 2) or a0.shape[-1] not in widths:
+        raise ValueError(f"a0 must have shape (n_waves,) or (N, n_waves) with n_waves in {tuple(widths)}")
     nw = int(a0.shape[-1])
     sizes = {int(np.size(v)) for s in spans for v in (s.dbeta, s.gamma, s.alpha, s.dbeta2) if v is not None}
     if a0.ndim == 2:
@@ -391,18 +388,71 @@ def rk4_chain(spans: Sequence[FibreSpan], *, a0, transfers=None, save_every: int
                 tr = np.stack([np.broadcast_to(t, (N, nw)) for t in arrs])
     steps = np.array([s.n_steps for s in spans], dtype=np.int64)
     lens = np.array([float(s.length) for s in spans])
-    kw = dict(dbeta=dbeta, n_steps=steps, seg_len=lens, save_every=save_every, gamma=gamma, alpha=alpha, a0=a0,
-              transfers=tr, dbeta2=dbeta2, check_nan=check_nan, exact_step=exact_step, want_traj=want_traj,
-              dtype=dtype, wave_summary=wave_summary)
-    r = _run(_native.chain_host, CHAIN_AXES, N, kw, device, devices)
+    return spans, save_every, dtype, N, nw, dbeta, dbeta2, gamma, alpha, tr, steps, lens
+
+
+def _chain_grid(steps, lens, save_every):
+    """-> (row_offsets (S + 1,), step_offsets (S + 1,), z_out (n_saved_total,)) of a chain's saved rows."""
     rows = steps // save_every + 1
     row_off = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
     step_off = np.concatenate([[0], np.cumsum(steps)]).astype(np.int64)
     z0 = np.concatenate([[0.0], np.cumsum(lens)])
-    z_out = np.concatenate([z0[k] + np.linspace(0.0, lens[k], int(steps[k]) + 1)[::save_every] for k in range(S)])
+    z_out = np.concatenate([z0[k] + np.linspace(0.0, lens[k], int(steps[k]) + 1)[::save_every] for k in range(len(steps))])
+    return row_off, step_off, z_out
+
+
+def rk4_chain(spans: Sequence[FibreSpan], *, a0, transfers=None, save_every: int = 10, check_nan: bool = True,
+              exact_step: Optional[bool] = None, dtype=np.float64, want_traj: bool = False, wave_summary: bool = False,
+              device: int = 0, devices: Optional[Sequence[int]] = None) -> ChainResult:
+    """Propagate N points through a chain of fibre spans (psa_rk4_chain_*): each span one launch of the sweep kernel,
+    the mismatch phase accumulated across spans, ``transfers[s]`` applied between span s and s+1.
+
+    transfers: None (identity), or S-1 entries, each (n_waves,) complex for every point or (N, n_waves) per point
+    (see simulation.mid_stage).  Every span's n_steps must be a multiple of ``save_every``."""
+    spans, save_every, dtype, N, _, dbeta, dbeta2, gamma, alpha, tr, steps, lens = _chain_inputs(spans, a0, transfers,
+                                                                                                 save_every, (4, 6), dtype)
+    kw = dict(dbeta=dbeta, n_steps=steps, seg_len=lens, save_every=save_every, gamma=gamma, alpha=alpha, a0=np.asarray(a0),
+              transfers=tr, dbeta2=dbeta2, check_nan=check_nan, exact_step=exact_step, want_traj=want_traj,
+              dtype=dtype, wave_summary=wave_summary)
+    r = _run(_native.chain_host, CHAIN_AXES, N, kw, device, devices)
+    row_off, step_off, z_out = _chain_grid(steps, lens, save_every)
     return ChainResult(r["a_end"], r["p_end"], r["p_max"], r["first_bad_step"], int(step_off[-1]), save_every,
                        r["elapsed_ms"], r.get("traj"), r.get("p_wave_end"), r.get("p_wave_max"), z_out=z_out,
                        row_offsets=row_off, step_offsets=step_off)
+
+
+@dataclass
+class SinglePumpChainResult(SinglePumpResult):
+    """SinglePumpResult of a chain: rows of every span in order (each span's z = 0 row is the post-transfer state),
+    amplitudes in the physical frame, first_bad_step counted over the whole chain.  n_steps is the chain's total."""
+    z_out: Optional[np.ndarray] = None         # (n_saved_total,) absolute z of every saved row (repeats at a boundary)
+    row_offsets: Optional[np.ndarray] = None   # (S + 1,) span s owns rows [row_offsets[s], row_offsets[s + 1])
+    step_offsets: Optional[np.ndarray] = None  # (S + 1,) span s owns steps [step_offsets[s], step_offsets[s + 1])
+
+
+def rk4_chain_single_pump(spans: Sequence[FibreSpan], *, a0, transfers=None, save_every: int = 10, check_nan: bool = True,
+                          exact_step: Optional[bool] = None, want_traj: bool = False, device: int = 0,
+                          devices: Optional[Sequence[int]] = None) -> SinglePumpChainResult:
+    """Propagate N points of the single-pump model, waves [p, s, i], through a chain of fibre spans
+    (psa_rk4_single_pump_chain_f64): each span one launch of the single-pump kernel, the mismatch phase
+    accumulated across spans, ``transfers[s]`` applied between span s and s+1.  The kernel assumes nothing about which wave
+    is strong: the signal-degenerate dual-pump PSA is the same call with the degenerate signal in slot 0, the two pumps in
+    slots 1 and 2 and dbeta = beta_1 + beta_2 - 2 beta_s.
+
+    a0 (3,) or (N, 3) complex; transfers: None (identity), or S-1 entries, each (3,) complex for every point or (N, 3) per
+    point (see simulation.single_pump_mid_stage).  Every span's n_steps must be a multiple of ``save_every``; a span with
+    dbeta2 is an error.  float64 only."""
+    spans, save_every, _, N, _, dbeta, _, gamma, alpha, tr, steps, lens = _chain_inputs(spans, a0, transfers, save_every,
+                                                                                        (3,), np.float64)
+    a0 = np.asarray(a0, dtype=np.complex128)
+    kw = dict(dbeta=dbeta, n_steps=steps, seg_len=lens, save_every=save_every, gamma=gamma, alpha=alpha, a0=a0,
+              transfers=tr, check_nan=check_nan, exact_step=exact_step, want_traj=want_traj)
+    r = _run(_native.single_pump_chain_host, CHAIN_AXES, N, kw, device, devices)
+    row_off, step_off, z_out = _chain_grid(steps, lens, save_every)
+    p_in = np.abs(np.atleast_2d(a0)) ** 2
+    return SinglePumpChainResult(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"], int(step_off[-1]),
+                                 save_every, r["elapsed_ms"], p_in, r.get("traj"), z_out=z_out, row_offsets=row_off,
+                                 step_offsets=step_off)
 
 
 # ---- adaptive (RK45) sweeps ----------------------------------------------------------------------------------------
