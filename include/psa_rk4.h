@@ -417,8 +417,8 @@ int psa_rk4_sweep_pairs_f64_dev(void *stream, int n_pairs, int64_t n_points, int
  *   dA_s/dz = (-alpha/2 + i gamma (2S - P_s)) A_s + i conj(A_i) (conj(E)/2) A_p^2              (i: s <-> i)
  * This is not psa_rk4_sweep_f64 with A1 == A2: there the pump's self-phase term is 1.5 gamma |A_p|^2 (A_p = sqrt(2) A1), so
  * the phase matching is off by gamma P_p / 2.  For alpha = 0 the model conserves P_p + P_s + P_i, P_s - P_i and P_p + 2 P_s.
- * Classic fixed-step RK4 on z_i = i * z_max / n_steps with the save and NaN semantics of psa_rk4_sweep_f64; float64 only,
- * one sweep point per lane.
+ * Classic fixed-step RK4 on z_i = i * z_max / n_steps with the save and NaN semantics of psa_rk4_sweep_f64; float64 with
+ * one sweep point per lane (the float32 forms follow below).
  *   dbeta       [N]                     mismatch per point, 1/length
  *   gamma, alpha  [N] | [1]
  *   a0_re_im    [N][3][2] | [1][3][2]
@@ -445,6 +445,23 @@ int psa_rk4_single_pump_f64_dev(void *stream, int64_t n_points, int64_t n_steps,
                                 const double *d_dbeta, const double *d_gamma, const double *d_alpha,
                                 const double *d_a0_soa, uint32_t flags, double *d_a_end_soa, double *d_p_wave_end_soa,
                                 double *d_p_wave_max_soa, int64_t *d_first_bad_step, double *d_traj_soa_or_null);
+/* The same sweep in float32: every buffer float, z_max and elapsed_ms double, first_bad_step int64.  Two sweep
+ * points per lane in packed math (points 2i and 2i+1 share lane i; any N, N = 1 included); classic RK4 on the un-fused
+ * right-hand side with a compensated state, the phase factor re-seeded from a float64-reduced phase every 16 steps.  It is
+ * the one float32 layout of this model: PSA_OPT_F32_SCALAR and PSA_OPT_F32_PACKED are PSA_E_FLAGS like every other layout
+ * flag, the accepted flags are those of the _f64 forms, and PSA_OPT_LOSSLESS is a promise that selects no other kernel.
+ * PSA_OPT_EXACT_STEP tests after every step; without it first_bad_step names the last step of the failing save block.  A
+ * trajectory whose leading dimension ld (n_points, or psa_traj_ld(n_points, 4)) has ld * 8 >= 2^31 is PSA_E_TOO_LARGE, the
+ * bound of psa_rk4_sweep_f32; every other rule, code and their order are those of psa_rk4_single_pump_f64. */
+int psa_rk4_single_pump_f32(int device, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+                            const float *dbeta, const float *gamma, const float *alpha, const float *a0_re_im,
+                            uint32_t flags, float *a_end_re_im, float *p_wave_end, float *p_wave_max,
+                            int64_t *first_bad_step, float *traj_or_null, double *elapsed_ms_or_null);
+/* d_traj_soa_or_null [n_saved][3][ld][2] with ld = N, or psa_traj_ld(N, 4) with PSA_OPT_TRAJ_LD. */
+int psa_rk4_single_pump_f32_dev(void *stream, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+                                const float *d_dbeta, const float *d_gamma, const float *d_alpha,
+                                const float *d_a0_soa, uint32_t flags, float *d_a_end_soa, float *d_p_wave_end_soa,
+                                float *d_p_wave_max_soa, int64_t *d_first_bad_step, float *d_traj_soa_or_null);
 
 /* ---- a chain of single-pump spans with mid-stage transfers (copier - mid-stage - PSA on one pump) ------------------------
  * psa_rk4_chain_* for the three-wave model above: S = n_segments >= 1 spans, each ONE launch of the

@@ -81,8 +81,7 @@ _SIGS = {
     **_family("psa_rk4_sweep_pairs", [_I, _L, _L, _D, _I32] + [_P] * 4 + [_U32] + [_P] * 4, host=[_P],
               host_types=("f64",), dev_types=("f64",)),
     # N, n_steps, z_max, save_every, dbeta, gamma, alpha, a0, flags, a_end, p_wave_end, p_wave_max, first_bad, traj; host: elapsed_ms
-    **_family("psa_rk4_single_pump", [_L, _L, _D, _I32] + [_P] * 4 + [_U32] + [_P] * 5, host=[_P],
-              host_types=("f64",), dev_types=("f64",)),
+    **_family("psa_rk4_single_pump", [_L, _L, _D, _I32] + [_P] * 4 + [_U32] + [_P] * 5, host=[_P]),
     # N, S, n_steps[S], seg_len[S], save_every, dbeta, gamma, alpha, a0, transfer, flags, a_end, p_wave_end, p_wave_max, first_bad,
     # traj; host: elapsed_ms; dev: workspace
     **_family("psa_rk4_single_pump_chain", [_L, _I, _P, _P, _I32] + [_P] * 5 + [_U32] + [_P] * 5, host=[_P], dev=[_P],
@@ -381,28 +380,31 @@ def sweep_pairs_device(*, stream: int, n_pairs: int, n_points: int, n_steps: int
 
 
 def single_pump_host(dbeta, *, n_steps: int, z_max: float, save_every: int, gamma, alpha, a0, check_nan: bool = True,
-                     exact_step: Optional[bool] = None, want_traj: bool = False, device: int = 0, extra_flags: int = 0) -> dict:
-    """N independent propagations of the single-pump three-wave model on the GPU (psa_rk4_single_pump_f64; host buffers in
-    and out, float64): one pump, a signal and an idler at 2 w_p - w_s, waves [p, s, i].
+                     exact_step: Optional[bool] = None, want_traj: bool = False, device: int = 0, extra_flags: int = 0,
+                     dtype=np.float64) -> dict:
+    """N independent propagations of the single-pump three-wave model on the GPU (psa_rk4_single_pump_f64 or, with
+    ``dtype=np.float32``, psa_rk4_single_pump_f32; host buffers in and out): one pump, a signal and an idler at 2 w_p - w_s,
+    waves [p, s, i].  Inputs are converted to ``dtype`` and outputs come back in it, as in sweep_host.
 
-    dbeta (N,); gamma / alpha scalar or (N,); a0 (3,) or (N, 3) complex.  exact_step None or True: the exact first_bad_step;
-    False: the save block's last step.
+    dbeta (N,); gamma / alpha scalar or (N,); a0 (3,) or (N, 3) complex.  exact_step None or True: the exact first_bad_step
+    (both precisions: the float32 kernel tests after every step); False: the save block's last step.
     Returns a_end (N, 3) complex, p_wave_end, p_wave_max (N, 3), first_bad_step (N,) int64, traj (N, n_saved, 3) complex or
     None, elapsed_ms (kernel only)."""
-    dbeta = np.ascontiguousarray(np.atleast_1d(np.asarray(dbeta)), dtype=np.float64)
+    dtype, cdt, f64 = _dtypes(dtype)
+    dbeta = np.ascontiguousarray(np.atleast_1d(np.asarray(dbeta)), dtype=dtype)
     if dbeta.ndim != 1:
         raise ValueError("dbeta must be 1-D")
     N = int(dbeta.shape[0])
-    flags, gamma, alpha, a0, _ = _point_inputs(N, np.float64, np.complex128, int(extra_flags), gamma, alpha, a0, (3,))
+    flags, gamma, alpha, a0, _ = _point_inputs(N, dtype, cdt, int(extra_flags), gamma, alpha, a0, (3,))
     flags |= _check_flags(check_nan, exact_step)
     n_saved = int(n_steps) // int(save_every) + 1 if save_every > 0 else 0
-    a_end = np.empty((N, 3), dtype=np.complex128)
-    w_end = np.empty((N, 3), dtype=np.float64)
-    w_max = np.empty((N, 3), dtype=np.float64)
+    a_end = np.empty((N, 3), dtype=cdt)
+    w_end = np.empty((N, 3), dtype=dtype)
+    w_max = np.empty((N, 3), dtype=dtype)
     bad = np.empty(N, dtype=np.int64)
-    traj = np.empty((N, n_saved, 3), dtype=np.complex128) if want_traj else None
+    traj = np.empty((N, n_saved, 3), dtype=cdt) if want_traj else None
     ms = C.c_double(0.0)
-    _check(_fn("psa_rk4_single_pump")(int(device), N, int(n_steps), float(z_max), int(save_every), _ptr(dbeta), _ptr(gamma),
+    _check(_fn("psa_rk4_single_pump", f64)(int(device), N, int(n_steps), float(z_max), int(save_every), _ptr(dbeta), _ptr(gamma),
                                       _ptr(alpha), _ptr(a0), flags, _ptr(a_end), _ptr(w_end), _ptr(w_max), _ptr(bad),
                                       _ptr(traj), C.cast(C.byref(ms), _P)))
     return dict(a_end=a_end, p_wave_end=w_end, p_wave_max=w_max, first_bad_step=bad, traj=traj, elapsed_ms=ms.value)
@@ -410,9 +412,10 @@ def single_pump_host(dbeta, *, n_steps: int, z_max: float, save_every: int, gamm
 
 def single_pump_device(*, stream: int, n_points: int, n_steps: int, z_max: float, save_every: int, d_dbeta: int,
                        d_gamma: int, d_alpha: int, d_a0_soa: int, flags: int, d_a_end_soa: int, d_p_wave_end_soa: int,
-                       d_p_wave_max_soa: int, d_first_bad: int, d_traj_soa: int = 0) -> None:
-    """Asynchronous single-pump launch on device pointers (ints), SoA layout -- see psa_rk4_single_pump_f64_dev."""
-    _check(_fn("psa_rk4_single_pump", dev=True)(
+                       d_p_wave_max_soa: int, d_first_bad: int, d_traj_soa: int = 0, dtype=np.float64) -> None:
+    """Asynchronous single-pump launch on device pointers (ints), SoA layout -- see psa_rk4_single_pump_f64_dev; ``dtype``
+    float32 is psa_rk4_single_pump_f32_dev on float buffers."""
+    _check(_fn("psa_rk4_single_pump", _dtypes(dtype)[2], dev=True)(
         stream or None, int(n_points), int(n_steps), float(z_max), int(save_every), d_dbeta or None, d_gamma or None,
         d_alpha or None, d_a0_soa or None, int(flags), d_a_end_soa or None, d_p_wave_end_soa or None,
         d_p_wave_max_soa or None, d_first_bad or None, d_traj_soa or None))

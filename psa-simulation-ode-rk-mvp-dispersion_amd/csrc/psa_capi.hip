@@ -80,15 +80,16 @@ struct PairsCall {   // psa_rk4_sweep_pairs_f64*
     double *a_end, *wave_end, *wave_max;
     int64_t *first_bad;
 };
-struct SinglePumpCall {   // psa_rk4_single_pump_f64*
+template <typename T>
+struct SinglePumpCall {   // psa_rk4_single_pump_f64*, psa_rk4_single_pump_f32* and one span of a single-pump chain
     int64_t n_points, n_steps;
     double z_max;
     int32_t save_every;
-    const double *dbeta, *gamma, *alpha, *a0;
+    const T *dbeta, *gamma, *alpha, *a0;
     uint32_t flags;
-    double *a_end, *wave_end, *wave_max;
+    T *a_end, *wave_end, *wave_max;
     int64_t *first_bad;
-    double *traj;
+    T *traj;
 };
 struct Rk45Call {    // psa_rk45_sweep_f64*
     int n_waves;
@@ -117,7 +118,7 @@ struct ChainCall {   // psa_rk4_chain_*
     const unsigned char *lossless = nullptr;
 };
 struct SinglePumpChainCall {   // psa_rk4_single_pump_chain_f64*
-    SinglePumpCall s;           // what the spans share; its n_steps and z_max are set span by span from the arrays below
+    SinglePumpCall<double> s;   // what the spans share; its n_steps and z_max are set span by span from the arrays below
     int n_segments;
     const int64_t *n_steps;     // host [S]
     const double *seg_len;      // host [S]
@@ -644,10 +645,16 @@ int pairs_host(int device, const PairsCall &c, double *elapsed_ms) {
                              [&](hipStream_t st) { return pairs_dev(st, d); });
 }
 
-// ---- the single-pump sweep (psa_rk4_single_pump_f64*): one pump, a signal and an idler ---------------------------------
+// ---- the single-pump sweep (psa_rk4_single_pump_f64* / _f32*): one pump, a signal and an idler -------------------------
+template <typename T> struct SinglePumpLaunch;
+template <> struct SinglePumpLaunch<double> { static constexpr auto fn = psa::launch_sweep_single_pump_f64; };
+template <> struct SinglePumpLaunch<float> { static constexpr auto fn = psa::launch_sweep_single_pump_f32; };
+
 // host_form: the call as the host-buffer entry point received it (PSA_OPT_TRAJ_LD is the `_dev` form's; the host form's
-// device-side trajectory always has the padded leading dimension).  The order is validate_common's.
-int validate_single_pump(const SinglePumpCall &c, bool host_form) {
+// device-side trajectory always has the padded leading dimension).  The order is validate_common's; float32 has one layout
+// (two points per lane), so PSA_OPT_F32_SCALAR / PSA_OPT_F32_PACKED are refused like every other layout flag.
+template <typename T>
+int validate_single_pump(const SinglePumpCall<T> &c, bool host_form) {
     int rc = validate_grid(c.n_points, PSA_MAX_POINTS, 0, c.n_steps, c.z_max, c.save_every);
     if (rc != PSA_OK) return rc;
     const uint32_t accepted = PSA_BCAST_GAMMA | PSA_BCAST_ALPHA | PSA_BCAST_A0 | PSA_OPT_CHECK_NAN | PSA_OPT_EXACT_STEP |
@@ -660,41 +667,44 @@ int validate_single_pump(const SinglePumpCall &c, bool host_form) {
     if (c.traj) {
         // trajectory rows are addressed as a wave-uniform (row, wave) base + the lane's 32-bit byte offset
         const bool padded = host_form || (c.flags & PSA_OPT_TRAJ_LD);
-        const unsigned long long ld = (unsigned long long)(padded ? traj_ld_of(c.n_points, sizeof(double)) : c.n_points);
-        if (ld * 16ull >= (1ull << 32))
+        const unsigned long long ld = (unsigned long long)(padded ? traj_ld_of(c.n_points, sizeof(T)) : c.n_points);
+        // float64: one 16-byte pair per lane below 2^32; float32: the packed sweep's bound, 8-byte pairs below 2^31
+        if (ld * 2ull * sizeof(T) >= (sizeof(T) == 8 ? 1ull << 32 : 1ull << 31))
             return fail(PSA_E_TOO_LARGE, "a single-pump trajectory launch takes a leading dimension below 2^28 points, got %llu", ld);
     }
     return PSA_OK;
 }
 
-int single_pump_dev(void *stream, const SinglePumpCall &c) {
+template <typename T>
+int single_pump_dev(void *stream, const SinglePumpCall<T> &c) {
     int rc = validate_single_pump(c, false);
     if (rc != PSA_OK) return rc;
     if (c.n_points == 0) return PSA_OK;
-    psa::SinglePumpArgs a;
+    psa::SinglePumpArgs<T> a;
     fill_point_args(a, c);
     a.p_wave_end = c.wave_end;
     a.p_wave_max = c.wave_max;
     a.first_bad = (long long *)c.first_bad;
     a.traj = c.traj;
-    a.traj_ld = (c.flags & PSA_OPT_TRAJ_LD) ? traj_ld_of(c.n_points, sizeof(double)) : c.n_points;
+    a.traj_ld = (c.flags & PSA_OPT_TRAJ_LD) ? traj_ld_of(c.n_points, sizeof(T)) : c.n_points;
     a.n_steps = (int)c.n_steps;
     a.save_every = c.save_every;
-    hipError_t e = psa::launch_sweep_single_pump_f64((hipStream_t)stream, c.flags, a);
+    hipError_t e = SinglePumpLaunch<T>::fn((hipStream_t)stream, c.flags, a);
     if (e != hipSuccess) return hip_fail(e, "rk4_sweep_single_pump launch");
     return PSA_OK;
 }
 
-int single_pump_host(int device, const SinglePumpCall &c, double *elapsed_ms) {
+template <typename T>
+int single_pump_host(int device, const SinglePumpCall<T> &c, double *elapsed_ms) {
     int rc = validate_single_pump(c, true);
     if (rc != PSA_OK) return rc;
     if (elapsed_ms) *elapsed_ms = 0.0;
     if (c.n_points == 0) return PSA_OK;
     const size_t N = (size_t)c.n_points;
-    SinglePumpCall d = c;
+    SinglePumpCall<T> d = c;
     if (c.traj) d.flags |= PSA_OPT_TRAJ_LD;   // the device-side trajectory has its own leading dimension; the caller's is dense
     d.flags |= lossless_bit(c.flags, c.alpha);
-    auto layout = [&](Staging<double> &sg) {
+    auto layout = [&](Staging<T> &sg) {
         d.dbeta = sg.input(c.dbeta, N);
         d.gamma = sg.input(c.gamma, (c.flags & PSA_BCAST_GAMMA) ? 1 : N);
         d.alpha = sg.input(c.alpha, (c.flags & PSA_BCAST_ALPHA) ? 1 : N);
@@ -705,7 +715,7 @@ int single_pump_host(int device, const SinglePumpCall &c, double *elapsed_ms) {
         d.first_bad = sg.output(c.first_bad, N);
         d.traj = sg.trajectory(c.traj, N, (size_t)(c.n_steps / c.save_every + 1), 6);
     };
-    return host_call<double>(device, "the single-pump RK4 sweep", elapsed_ms, layout,
+    return host_call<T>(device, "the single-pump RK4 sweep", elapsed_ms, layout,
                              [&](hipStream_t st) { return single_pump_dev(st, d); });
 }
 
@@ -950,7 +960,7 @@ int64_t single_pump_chain_workspace_bytes(int64_t n_points) {
 int validate_single_pump_chain(const SinglePumpChainCall &c, bool host_form, int64_t *rows_total) {
     if (c.n_segments < 1) return fail(PSA_E_NSTEPS, "n_segments must be >= 1, got %d", c.n_segments);
     if (!c.n_steps || !c.seg_len) return fail(PSA_E_NULLPTR, "n_steps / seg_len is NULL");
-    SinglePumpCall first = c.s;
+    SinglePumpCall<double> first = c.s;
     first.n_steps = c.n_steps[0];
     first.z_max = c.seg_len[0];
     first.flags &= ~PSA_BCAST_TRANSFER;   // the chain's own bit
@@ -971,7 +981,7 @@ int single_pump_chain_dev(void *stream, const SinglePumpChainCall &c) {
     if (c.s.n_points == 0) return PSA_OK;
     const int S = c.n_segments;
     const uint32_t flags = c.s.flags;
-    SinglePumpCall sp = c.s;   // the span being run
+    SinglePumpCall<double> sp = c.s;   // the span being run
     auto set_span = [&](int s) {
         sp.n_steps = c.n_steps[s];
         sp.z_max = c.seg_len[s];
@@ -1562,15 +1572,33 @@ int psa_rk4_single_pump_f64(int device, int64_t n_points, int64_t n_steps, doubl
                             const double *dbeta, const double *gamma, const double *alpha, const double *a0_re_im,
                             uint32_t flags, double *a_end_re_im, double *p_wave_end, double *p_wave_max,
                             int64_t *first_bad_step, double *traj_or_null, double *elapsed_ms_or_null) {
-    return single_pump_host(device, {n_points, n_steps, z_max, save_every, dbeta, gamma, alpha, a0_re_im, flags, a_end_re_im,
-                                     p_wave_end, p_wave_max, first_bad_step, traj_or_null}, elapsed_ms_or_null);
+    return single_pump_host(device, SinglePumpCall<double>{n_points, n_steps, z_max, save_every, dbeta, gamma, alpha, a0_re_im, flags,
+                                                            a_end_re_im, p_wave_end, p_wave_max, first_bad_step, traj_or_null},
+                            elapsed_ms_or_null);
 }
 int psa_rk4_single_pump_f64_dev(void *stream, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
                                 const double *d_dbeta, const double *d_gamma, const double *d_alpha, const double *d_a0_soa,
                                 uint32_t flags, double *d_a_end_soa, double *d_p_wave_end_soa, double *d_p_wave_max_soa,
                                 int64_t *d_first_bad_step, double *d_traj_soa_or_null) {
-    return single_pump_dev(stream, {n_points, n_steps, z_max, save_every, d_dbeta, d_gamma, d_alpha, d_a0_soa, flags,
-                                    d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step, d_traj_soa_or_null});
+    return single_pump_dev(stream, SinglePumpCall<double>{n_points, n_steps, z_max, save_every, d_dbeta, d_gamma, d_alpha, d_a0_soa,
+                                                          flags, d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step,
+                                                          d_traj_soa_or_null});
+}
+int psa_rk4_single_pump_f32(int device, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+                            const float *dbeta, const float *gamma, const float *alpha, const float *a0_re_im,
+                            uint32_t flags, float *a_end_re_im, float *p_wave_end, float *p_wave_max,
+                            int64_t *first_bad_step, float *traj_or_null, double *elapsed_ms_or_null) {
+    return single_pump_host(device, SinglePumpCall<float>{n_points, n_steps, z_max, save_every, dbeta, gamma, alpha, a0_re_im, flags,
+                                                           a_end_re_im, p_wave_end, p_wave_max, first_bad_step, traj_or_null},
+                            elapsed_ms_or_null);
+}
+int psa_rk4_single_pump_f32_dev(void *stream, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+                                const float *d_dbeta, const float *d_gamma, const float *d_alpha, const float *d_a0_soa,
+                                uint32_t flags, float *d_a_end_soa, float *d_p_wave_end_soa, float *d_p_wave_max_soa,
+                                int64_t *d_first_bad_step, float *d_traj_soa_or_null) {
+    return single_pump_dev(stream, SinglePumpCall<float>{n_points, n_steps, z_max, save_every, d_dbeta, d_gamma, d_alpha, d_a0_soa,
+                                                         flags, d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step,
+                                                         d_traj_soa_or_null});
 }
 
 // the chain's record: the spans' shared part has no grid of its own (n_steps 0, z_max 0: set span by span)

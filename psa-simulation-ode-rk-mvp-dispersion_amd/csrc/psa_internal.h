@@ -69,18 +69,19 @@ struct PairsArgs {
     long long a0_ld;
 };
 
-// Everything one single-pump sweep launch needs (one pump, a signal and an idler: NW = 3 waves [p, s, i]; float64 only).
-// Strides as in SweepArgs; every output but the trajectory is always written.
+// Everything one single-pump sweep launch needs (one pump, a signal and an idler: NW = 3 waves [p, s, i]; float64 one point per
+// lane, float32 two points per lane).  Strides as in SweepArgs; every output but the trajectory is always written.
+template <typename T>
 struct SinglePumpArgs {
-    const double *dbeta;     // [N]
-    const double *gamma;     // [N] | [1]
-    const double *alpha;     // [N] | [1]
-    const double *a0;        // SoA [6][a0_ld]
-    double *a_end;           // SoA [6][N]
-    double *p_wave_end;      // SoA [3][N] |A_j|^2 at the last saved row
-    double *p_wave_max;      // SoA [3][N] max over saved rows incl. z = 0 (NaN-propagating like np.max)
+    const T *dbeta;          // [N]
+    const T *gamma;          // [N] | [1]
+    const T *alpha;          // [N] | [1]
+    const T *a0;             // SoA [6][a0_ld]
+    T *a_end;                // SoA [6][N]
+    T *p_wave_end;           // SoA [3][N] |A_j|^2 at the last saved row
+    T *p_wave_max;           // SoA [3][N] max over saved rows incl. z = 0 (NaN-propagating like np.max)
     long long *first_bad;    // [N]
-    double *traj;            // [n_saved][3][traj_ld][2] ((re, im) pairs) or nullptr
+    T *traj;                 // [n_saved][3][traj_ld][2] ((re, im) pairs) or nullptr
     long long traj_ld;       // points per (row, wave) region of traj: n_points, or padded (psa_traj_ld)
     long long n_points;
     double z_max;
@@ -103,10 +104,14 @@ hipError_t launch_sweep_f32(hipStream_t s, int n_waves, uint32_t flags, const Sw
 // validated the arguments (1 <= n_pairs <= 16, the lanes fit the launch grid).
 int pairs_lanes_per_point(int n_pairs);
 hipError_t launch_sweep_pairs_f64(hipStream_t s, uint32_t flags, const PairsArgs &a);
-// Single-pump sweep launcher (psa_rk4_single_pump.hip): one launch on s, one lane per point; nothing for n_points == 0.
-// Reads PSA_OPT_CHECK_NAN / EXACT_STEP / LOSSLESS / BLOCK64 of `flags` and takes the trajectory from a.traj being non-null;
-// the caller has validated the arguments (with a trajectory, traj_ld * 16 < 2^32).
-hipError_t launch_sweep_single_pump_f64(hipStream_t s, uint32_t flags, const SinglePumpArgs &a);
+// Single-pump sweep launchers (psa_rk4_single_pump.hip: one lane per point; psa_rk4_single_pump_f32.hip: two points per lane):
+// one launch on s, nothing for n_points == 0.  They read PSA_OPT_CHECK_NAN / EXACT_STEP / LOSSLESS / BLOCK64 of `flags` (float32
+// has one register layout: LOSSLESS selects nothing there) and take the trajectory from a.traj being non-null; the caller has
+// validated the arguments (with a trajectory, traj_ld * 16 < 2^32 in float64 and traj_ld * 8 < 2^31 in float32).
+hipError_t launch_sweep_single_pump_f64(hipStream_t s, uint32_t flags, const SinglePumpArgs<double> &a);
+hipError_t launch_sweep_single_pump_f32(hipStream_t s, uint32_t flags, const SinglePumpArgs<float> &a);
+// SIMDs (4 per CU) of the device a launch on s goes to (psa_rk4_single_pump.hip): what both launchers size their workgroups by
+int single_pump_simd_count(hipStream_t s);
 // Adaptive sweep launcher (psa_rk45.hip): one launch on s, nothing for n_points == 0; PSA_OPT_LOSSLESS is the only flag
 // it reads and the dense-output rows come from a.traj being non-null.  The caller has validated the arguments.
 hipError_t launch_rk45_sweep_f64(hipStream_t s, int n_waves, uint32_t flags, const AdaptiveArgs<double> &a);

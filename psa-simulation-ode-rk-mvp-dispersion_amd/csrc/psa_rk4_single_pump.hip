@@ -5,7 +5,7 @@
 namespace psa {
 
 // SIMDs (4 per CU) of the device the launch goes to: the stream's device, which need not be the thread's current one.
-static int single_pump_simd_count(hipStream_t s) {
+int single_pump_simd_count(hipStream_t s) {
     int dev = -1, cus = 0;
     if (s == nullptr || hipStreamGetDevice(s, &dev) != hipSuccess) {
         if (hipGetDevice(&dev) != hipSuccess) return 1024;
@@ -14,7 +14,7 @@ static int single_pump_simd_count(hipStream_t s) {
     return 4 * cus;
 }
 
-hipError_t launch_sweep_single_pump_f64(hipStream_t s, uint32_t flags, const SinglePumpArgs &a) {
+hipError_t launch_sweep_single_pump_f64(hipStream_t s, uint32_t flags, const SinglePumpArgs<double> &a) {
     if (a.n_points == 0) return hipSuccess;
     const int check = !(flags & PSA_OPT_CHECK_NAN) ? CHECK_NONE : ((flags & PSA_OPT_EXACT_STEP) ? CHECK_EXACT : CHECK_BLOCK);
     // the rule of launch_sweep_f64: 64-thread workgroups while the launch's waves fit half the SIMDs, 256 beyond
@@ -26,7 +26,7 @@ hipError_t launch_sweep_single_pump_f64(hipStream_t s, uint32_t flags, const Sin
     return with_bool(a.traj != nullptr, [&](auto traj) {
     return with_int<64, 256>(block, [&](auto b) {
     return with_bool(lossless, [&](auto ll) {
-        void *args[] = {const_cast<SinglePumpArgs *>(&a)};
+        void *args[] = {const_cast<SinglePumpArgs<double> *>(&a)};
         (void)hipLaunchKernel(reinterpret_cast<const void *>(&rk4_sweep_single_pump_kernel<chk, traj, b, !ll>), grid, blk, args, 0, s);
         return hipGetLastError();
     }); }); }); });

@@ -29,8 +29,9 @@
 // 8 (two rotations of H) + 6 (three doublings: E at z + h/2, 2E for stage 3, E at z + h) = 238 against 298 for four waves;
 // 239 as built (215 without the loss links), see the table in DESIGN.md 3.3c.
 //
-// Out of scope: float32, lane-pair / lane-quad layouts, RK45, chains, LDS staging, a mirrored variant, a dedicated
-// save_every == 1 trajectory loop (every stride goes through the event loop).
+// Out of scope: lane-pair / lane-quad layouts, RK45, chains, LDS staging, a mirrored variant, a dedicated
+// save_every == 1 trajectory loop (every stride goes through the event loop).  Float32 is
+// psa_rk4_single_pump_pk_kernel.inc.h.
 #pragma once
 #include "psa_rk4_carried.inc.h"
 
@@ -71,7 +72,7 @@ __device__ __forceinline__ void single_pump_stage(const double (&a)[6], const do
 }
 
 template <int CHECK, bool TRAJ, int BLOCK, bool LOSS>
-__global__ void __launch_bounds__(BLOCK) rk4_sweep_single_pump_kernel(const SinglePumpArgs A) {
+__global__ void __launch_bounds__(BLOCK) rk4_sweep_single_pump_kernel(const SinglePumpArgs<double> A) {
     const long long idx = (long long)blockIdx.x * BLOCK + threadIdx.x;
     const long long N = A.n_points;
     if (idx >= N) return;

@@ -714,14 +714,15 @@ def scan_single_pump_gain(*, cfg: SimulationConfig, lambda_pump_m: float, lambda
                           p_signal: float, p_idler: float = 0.0, phase_in: Optional[Sequence[float]] = None, gamma: float,
                           alpha: float, dispersion: DispersionParams, max_order: int = 4, length_unit: str = "m",
                           gain_unit: str = "dB", gain_mode: GainMode = "max", device: Optional[int] = None,
-                          devices: Optional[Sequence[int]] = None) -> dict:
+                          devices: Optional[Sequence[int]] = None, dtype=np.float64) -> dict:
     """The gain spectrum of a single-pump amplifier (no reference counterpart): waves [p, s, i], the pump at lambda_pump_m,
     sweep point k with its signal at lambda_signal_m[k] and its idler at 2 w_p - w_s, dbeta = beta(w_s) + beta(w_i) -
     2 beta(w_p) from the Taylor expansion of ``dispersion`` up to ``max_order``, formed on the host.  One launch of the
     single-pump kernel (sweep.rk4_sweep_single_pump) over the signal wavelengths on ``device``, or split over ``devices``;
     sharding over a ``torch.distributed`` process group is out of scope here -- every rank would run the whole sweep.
     A point whose plan is invalid (a wavelength that is not positive and finite, an idler frequency <= 0, a non-finite
-    dbeta) gets NaN in every output instead of an exception.
+    dbeta) gets NaN in every output instead of an exception.  ``dtype=np.float32`` runs the packed float32 kernel; dbeta is
+    still formed in float64 on the host and rounded once.
 
     Returns dict(gain (n,) of the signal over p_signal, idler (n,) the idler's power over p_signal, pump_depletion (n,),
     dbeta (n,) in 1/length_unit, first_bad_step (n,), result=SinglePumpResult)."""
@@ -760,7 +761,7 @@ def scan_single_pump_gain(*, cfg: SimulationConfig, lambda_pump_m: float, lambda
     res = rk4_sweep_single_pump(np.where(ok, db, 0.0), z_max=fiber.length_m, n_steps=n_steps_of(fiber.length_m, grid.dz_m),
                                 save_every=cfg.save_every, check_nan=bool(cfg.check_nan), gamma=fiber.gamma_W_m,
                                 alpha=fiber.alpha_1_m, a0=initial_amplitudes(p0, ph), device=(0 if device is None else int(device)),
-                                devices=devices)
+                                devices=devices, dtype=dtype)
     nan = lambda x: np.where(ok, x, np.nan)   # noqa: E731
     return dict(gain=nan(res.signal_gain(p0[1], mode=gain_mode, unit=unit)),
                 idler=nan(res.idler_conversion(p0[1], mode=gain_mode, unit=unit)), pump_depletion=nan(res.pump_depletion()),

@@ -265,24 +265,30 @@ class SinglePumpResult:
 def rk4_sweep_single_pump(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps: Optional[int] = None,
                           save_every: int = 10, check_nan: bool = True, exact_step: Optional[bool] = None, gamma, alpha, a0,
                           want_traj: bool = False, device: int = 0,
-                          devices: Optional[Sequence[int]] = None) -> SinglePumpResult:
+                          devices: Optional[Sequence[int]] = None, dtype=np.float64) -> SinglePumpResult:
     """Propagate N points of the single-pump (degenerate) model: one pump, a signal and an idler at 2 w_p - w_s, waves
     [p, s, i] (build-defined).  Not rk4_sweep with equal pumps: that system gives the pump 1.5 times the
     self-phase modulation.
 
     dbeta (N,): beta(w_s) + beta(w_i) - 2 beta(w_p) per point; gamma / alpha a scalar or (N,); a0 (3,) or (N, 3) complex.
     ``dz`` gives n = int(round(z_max/dz)) as integrators.py:194; or pass ``n_steps``.  ``want_traj`` also returns every saved
-    row; ``devices=[0, 1, ...]`` splits the points (and the trajectory) over several GPUs of this process.  Fixed-step
-    float64 only: no float32 or adaptive form; concatenated spans (copier - mid-stage - PSA) are rk4_chain_single_pump."""
+    row; ``devices=[0, 1, ...]`` splits the points (and the trajectory) over several GPUs of this process.
+    ``dtype=np.float32`` runs the packed float32 kernel (two points per lane) and returns float32 / complex64
+    arrays; any dtype but float64 and float32 is a ValueError.  Fixed-step only: no adaptive form; concatenated spans (copier
+    - mid-stage - PSA) are rk4_chain_single_pump, in float64."""
+    if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError(f"dtype must be float64 or float32, got {np.dtype(dtype)}")
     n_steps, save_every = _fixed_grid(z_max, dz, n_steps, save_every)
     db = np.atleast_1d(np.asarray(dbeta, dtype=float))
     if db.ndim != 1:
         raise ValueError(f"dbeta must be a scalar or have shape (N,), got {db.shape}")
-    a0 = np.asarray(a0, dtype=np.complex128)
+    a0 = np.asarray(a0, dtype=np.complex128 if np.dtype(dtype) == np.dtype(np.float64) else np.complex64)
     if a0.shape not in ((3,), (1, 3), (db.shape[0], 3)):
         raise ValueError(f"a0 must have shape (3,) or ({db.shape[0]}, 3), got {a0.shape}")
     kw = dict(dbeta=db, n_steps=n_steps, z_max=float(z_max), save_every=save_every, gamma=gamma, alpha=alpha, a0=a0,
               check_nan=check_nan, exact_step=exact_step, want_traj=want_traj)
+    if np.dtype(dtype) != np.dtype(np.float64):
+        kw["dtype"] = np.float32          # the float64 call stays as it was: no dtype argument
     r = _run(_native.single_pump_host, SWEEP_AXES, db.shape[0], kw, device, devices)
     p_in = np.abs(np.atleast_2d(a0)) ** 2
     return SinglePumpResult(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"], n_steps, save_every,
