@@ -689,9 +689,100 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
         }
     }
 
-    // ---- z-loop, event driven: the steps between two events (a saved row, a phase re-seed, the end) run in a
-    // branch-free 2x-unrolled inner loop.  With one wave per SIMD (65 536 points fill the chip exactly once) every
-    // taken branch is an exposed instruction refetch, so per-step `if`s cost ~6 % -- see DESIGN.md section 5.
+    // ---- z-loop by saved rows: the frame-anchored summary kernels (FRAME without trajectory) have no seed event, so the only
+    // events are the rows and the end.  One loop over blocks of steps -- n_rows of save_every, then the unsaved tail (check_nan
+    // only) through the same step text -- with no bookkeeping between the steps of a block: the odd step and the odd pair
+    // first, then trips of PSA_ROW_TRIP steps.  With one wave per SIMD every taken branch is an exposed instruction refetch
+    // (~32 cycles, profiles/r03_issue_probe.log): a row of the event loop below took nine at save_every = 10 (eleven in the general
+    // loop), this one takes three (profiles/row_loop.log; tools/isa_loop_stats.py --row walks a row through the built loop).
+    // The row itself is straight-line -- |A_sig|^2, the maxima, the block-mode test as a select -- and ONE counter, `until`,
+    // stands between it and the back-edge.  Everything rare hangs off that counter reaching zero: the exact test (REPLAY),
+    // and at the last row A[-1], the power summaries and the switch to the tail.  The tail runs as one more block whose row
+    // work is discarded: p_end / p_max (and the per-wave maxima) are already in memory, and in block mode the row's test at
+    // i = n_run is the tail's (first_bad_step = n_run - 1).
+    // The exact test need not run on every row: a non-finite component never becomes finite again (every chain of the next
+    // stage and the state update take it in; the save_every == 1 loop above relies on the same), so a lane that fails anywhere
+    // in a group of rows is still non-finite at the group's end, and the replay from the checkpoint finds the same first step
+    // whatever the distance.  The forward test, ballot and checkpoint run after every G-th row, G the largest count with
+    // G * save_every <= 64 (at least 1), after the last row and after the tail: a replay never covers more than
+    // max(save_every, 64) steps.  Groups are counted in rows from z = 0, so what is tested does not depend on the wave.
+#ifndef PSA_ROW_TRIP            // A/B hook (make EXTRA=-DPSA_ROW_TRIP=2): steps per trip of the row loop, 4 or 2
+#define PSA_ROW_TRIP 4
+#endif
+    if constexpr (FRAME && !TRAJ) {
+        static_assert(PSA_ROW_TRIP == 4 || PSA_ROW_TRIP == 2, "the row loop runs 4 or 2 steps per trip");
+        auto write_powers = [&]() {
+            A.p_end[idx] = pe;
+            A.p_max[idx] = pm;
+            if constexpr (WSUM) {
+#pragma unroll
+                for (int j = 0; j < NW; ++j) A.p_wave_max[(long long)j * N + idx] = pwm[at(2 * j) / 2];
+            }
+        };
+        const int tail = n_run - n_rows * se;
+        const int rows_per_test = se < 64 ? 64 / se : 1;
+        auto span_of = [&](const int rows) { return (REPLAY && rows > rows_per_test) ? rows_per_test : rows; };
+        int left = n_rows > 0 ? n_rows : -1;   // saved rows still ahead of the last rare stop; -1: the block is the tail
+        int m = left < 0 ? tail : se;          // steps per block, and its full trips (carried: the loop forms neither per row)
+        int trips = m / PSA_ROW_TRIP;
+        int span = left < 0 ? 1 : span_of(left);
+        [[maybe_unused]] int i_row = 0;        // block mode: the step index of the row
+        checkpoint(0);
+        if (left < 0) write_powers();          // no row after z = 0
+        if (m > 0) {
+            for (int until = span;;) {
+                if (m & 1) rk4_step_reg(0);
+                if constexpr (PSA_ROW_TRIP == 4) {
+                    if (m & 2) {
+                        rk4_step_reg(0);
+                        rk4_step_reg(0);
+                    }
+                }
+                for (int q = trips; q > 0; --q) {
+                    rk4_step_reg(0);
+                    rk4_step_reg(0);
+                    if constexpr (PSA_ROW_TRIP == 4) {
+                        rk4_step_reg(0);
+                        rk4_step_reg(0);
+                    }
+                }
+                pe = fma_(y[SIG], y[SIG], y[SIG + 1] * y[SIG + 1]);
+                pm = (pe > pm || pe != pe) ? pe : pm;  // np.max propagates NaN
+                if constexpr (WSUM) {
+#pragma unroll
+                    for (int j = 0; j < NWS; ++j) {
+                        const T pj = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
+                        pwm[j] = (pj > pwm[j] || pj != pj) ? pj : pwm[j];
+                    }
+                }
+                if constexpr (CHECK == CHECK_BLOCK) {
+                    i_row += m;
+                    if (bad < 0 && any_nonfinite<T, NS>(y)) bad = i_row - 1;
+                }
+                if (--until != 0) continue;                       // wave-uniform; the back-edge of every other row
+                if (left > 0) left -= span;
+                exact_test(left < 0 ? n_run : (n_rows - left) * se);
+                if (left < 0) break;
+                if (left > 0) {
+                    until = span = span_of(left);
+                    continue;
+                }
+                store_a_end_at(n_rows * se);   // A[-1]: the last saved row, not necessarily z_max (R8)
+                write_powers();
+                if (tail == 0) break;
+                left = -1;
+                m = tail;
+                trips = m / PSA_ROW_TRIP;
+                until = 1;
+            }
+        }
+        A.first_bad[idx] = bad;
+        return;
+    }
+
+    // ---- z-loop, event driven (trajectory, six waves, float32, LDS): the steps between two events (a saved row, a phase
+    // re-seed, the end) run in a branch-free 2x-unrolled inner loop.  With one wave per SIMD (65 536 points fill the chip
+    // exactly once) every taken branch is an exposed instruction refetch -- see DESIGN.md section 5.
     // Seeds fall on the ABSOLUTE grid i = 0, RESYNC, 2*RESYNC, ... whatever save_every is (the save_every == 1 loop above does
     // the same), so the computed trajectory does not depend on which rows are saved -- as upstream, where the stride only
     // selects rows (integrators.py:137-140): A[-1] at any stride equals the same row of the every-step run bit for bit.
