@@ -421,14 +421,13 @@ def single_pump_device(*, stream: int, n_points: int, n_steps: int, z_max: float
         d_p_wave_max_soa or None, d_first_bad or None, d_traj_soa or None))
 
 
-def single_pump_chain_host(dbeta, *, n_steps, seg_len, save_every: int, gamma, alpha, a0, transfers=None,
-                           check_nan: bool = True, exact_step: Optional[bool] = None, want_traj: bool = False,
-                           device: int = 0, extra_flags: int = 0) -> dict:
-    """A chain of S single-pump spans on the GPU (psa_rk4_single_pump_chain_f64; host buffers in and out, float64).
-
-    dbeta (S, N); n_steps, seg_len (S,); gamma / alpha (S,) broadcast or (S, N); a0 (3,) or (N, 3) complex; transfers None,
-    (S-1, 3) broadcast or (S-1, N, 3) complex.  Returns the keys of single_pump_host; traj is (N, n_saved_total, 3)."""
-    dbeta = np.ascontiguousarray(np.asarray(dbeta), dtype=np.float64)
+def _chain_host(stem: str, widths, sweep_family: bool, dbeta, *, n_steps, seg_len, save_every: int, gamma, alpha, a0,
+                transfers, dbeta2, check_nan: bool, exact_step: Optional[bool], want_traj: bool, dtype, device: int,
+                wave_summary: bool, extra_flags: int) -> dict:
+    """The host-buffer chain of either family: ``<stem>_f64`` / ``_f32`` on a0 of a width in ``widths``.  ``sweep_family``:
+    the 4/6-wave entry points, which take n_waves and dbeta2, have p_end / p_max and put the per-wave summary last."""
+    dtype, cdt, f64 = _dtypes(dtype)
+    dbeta = np.ascontiguousarray(np.asarray(dbeta), dtype=dtype)
     if dbeta.ndim != 2 or dbeta.shape[0] < 1:
         raise ValueError("dbeta must have shape (S, N)")
     S, N = (int(x) for x in dbeta.shape)
@@ -436,26 +435,57 @@ def single_pump_chain_host(dbeta, *, n_steps, seg_len, save_every: int, gamma, a
     lens = np.ascontiguousarray(np.asarray(seg_len), dtype=np.float64)
     if steps.shape != (S,) or lens.shape != (S,):
         raise ValueError(f"n_steps and seg_len must have shape ({S},)")
-    flags, gamma, alpha, a0, _ = _point_inputs(N, np.float64, np.complex128, int(extra_flags), gamma, alpha, a0, (3,), spans=S)
-    flags |= _check_flags(check_nan, exact_step)
+    flags, gamma, alpha, a0, d2 = _point_inputs(N, dtype, cdt, int(extra_flags), gamma, alpha, a0, widths,
+                                                dbeta if sweep_family else None, dbeta2, S)
+    flags |= _check_flags(check_nan, exact_step, f64)
+    nw = int(a0.shape[1])
     tr = None
     if transfers is not None and S > 1:
-        tr = np.ascontiguousarray(np.asarray(transfers), dtype=np.complex128)
-        if tr.shape == (S - 1, 3):
+        tr = np.ascontiguousarray(np.asarray(transfers), dtype=cdt)
+        if tr.shape == (S - 1, nw):
             flags |= BCAST_TRANSFER
-        elif tr.shape != (S - 1, N, 3):
-            raise ValueError(f"transfers must have shape ({S - 1}, 3) or ({S - 1}, {N}, 3)")
+        elif tr.shape != (S - 1, N, nw):
+            raise ValueError(f"transfers must have shape ({S - 1}, {nw}) or ({S - 1}, {N}, {nw})")
     n_rows = int(np.sum(steps // save_every + 1)) if save_every > 0 else 0
-    a_end = np.empty((N, 3), dtype=np.complex128)
-    w_end = np.empty((N, 3), dtype=np.float64)
-    w_max = np.empty((N, 3), dtype=np.float64)
+    out = dict(a_end=np.empty((N, nw), dtype=cdt))
+    if sweep_family:
+        out.update(p_end=np.empty(N, dtype=dtype), p_max=np.empty(N, dtype=dtype))
     bad = np.empty(N, dtype=np.int64)
-    traj = np.empty((N, n_rows, 3), dtype=np.complex128) if want_traj else None
+    traj = np.empty((N, n_rows, nw), dtype=cdt) if want_traj else None
+    w_end = np.empty((N, nw), dtype=dtype) if wave_summary else None
+    w_max = np.empty((N, nw), dtype=dtype) if wave_summary else None
     ms = C.c_double(0.0)
-    _check(_fn("psa_rk4_single_pump_chain")(
-        int(device), N, S, _ptr(steps), _ptr(lens), int(save_every), _ptr(dbeta), _ptr(gamma), _ptr(alpha), _ptr(a0),
-        _ptr(tr), flags, _ptr(a_end), _ptr(w_end), _ptr(w_max), _ptr(bad), _ptr(traj), C.cast(C.byref(ms), _P)))
-    return dict(a_end=a_end, p_wave_end=w_end, p_wave_max=w_max, first_bad_step=bad, traj=traj, elapsed_ms=ms.value)
+    grid = (N, S, _ptr(steps), _ptr(lens), int(save_every), _ptr(dbeta))
+    point = (_ptr(gamma), _ptr(alpha), _ptr(a0), _ptr(tr), flags, _ptr(out["a_end"]))
+    run = (_ptr(bad), _ptr(traj), C.cast(C.byref(ms), _P))
+    if sweep_family:
+        _check(_fn(stem, f64)(int(device), nw, *grid, _ptr(d2), *point, _ptr(out["p_end"]), _ptr(out["p_max"]), *run,
+                              _ptr(w_end), _ptr(w_max)))
+        return dict(out, first_bad_step=bad, traj=traj, elapsed_ms=ms.value, p_wave_end=w_end, p_wave_max=w_max)
+    _check(_fn(stem, f64)(int(device), *grid, *point, _ptr(w_end), _ptr(w_max), *run))
+    return dict(out, p_wave_end=w_end, p_wave_max=w_max, first_bad_step=bad, traj=traj, elapsed_ms=ms.value)
+
+
+def _chain_device(stem: str, f64: bool, stream: int, head: tuple, n_steps, seg_len, tail: tuple) -> None:
+    """``<stem>_*_dev``: ``head`` (n_waves, n_points), the span count and the two host arrays, then ``tail`` as it is."""
+    steps = np.ascontiguousarray(np.asarray(n_steps), dtype=np.int64)
+    lens = np.ascontiguousarray(np.asarray(seg_len), dtype=np.float64)
+    if steps.ndim != 1 or steps.shape != lens.shape:
+        raise ValueError("n_steps and seg_len must be 1-D of equal length")
+    _check(_fn(stem, f64, dev=True)(stream or None, *head, int(steps.shape[0]), _ptr(steps), _ptr(lens), *tail))
+
+
+def single_pump_chain_host(dbeta, *, n_steps, seg_len, save_every: int, gamma, alpha, a0, transfers=None,
+                           check_nan: bool = True, exact_step: Optional[bool] = None, want_traj: bool = False,
+                           device: int = 0, extra_flags: int = 0) -> dict:
+    """A chain of S single-pump spans on the GPU (psa_rk4_single_pump_chain_f64; host buffers in and out, float64).
+
+    dbeta (S, N); n_steps, seg_len (S,); gamma / alpha (S,) broadcast or (S, N); a0 (3,) or (N, 3) complex; transfers None,
+    (S-1, 3) broadcast or (S-1, N, 3) complex.  Returns the keys of single_pump_host; traj is (N, n_saved_total, 3)."""
+    return _chain_host("psa_rk4_single_pump_chain", (3,), False, dbeta, n_steps=n_steps, seg_len=seg_len, save_every=save_every,
+                       gamma=gamma, alpha=alpha, a0=a0, transfers=transfers, dbeta2=None, check_nan=check_nan,
+                       exact_step=exact_step, want_traj=want_traj, dtype=np.float64, device=device, wave_summary=True,
+                       extra_flags=extra_flags)
 
 
 def single_pump_chain_workspace_bytes(n_points: int) -> int:
@@ -468,14 +498,10 @@ def single_pump_chain_device(*, stream: int, n_points: int, n_steps, seg_len, sa
                              d_p_wave_end_soa: int, d_p_wave_max_soa: int, d_first_bad: int, d_traj_soa: int = 0,
                              d_workspace: int = 0) -> None:
     """psa_rk4_single_pump_chain_f64_dev on device pointers (ints); n_steps / seg_len are host sequences of length S."""
-    steps = np.ascontiguousarray(np.asarray(n_steps), dtype=np.int64)
-    lens = np.ascontiguousarray(np.asarray(seg_len), dtype=np.float64)
-    if steps.ndim != 1 or steps.shape != lens.shape:
-        raise ValueError("n_steps and seg_len must be 1-D of equal length")
-    _check(_fn("psa_rk4_single_pump_chain", dev=True)(
-        stream or None, int(n_points), int(steps.shape[0]), _ptr(steps), _ptr(lens), int(save_every), d_dbeta or None,
-        d_gamma or None, d_alpha or None, d_a0_soa or None, d_transfer_soa or None, int(flags), d_a_end_soa or None,
-        d_p_wave_end_soa or None, d_p_wave_max_soa or None, d_first_bad or None, d_traj_soa or None, d_workspace or None))
+    _chain_device("psa_rk4_single_pump_chain", True, stream, (int(n_points),), n_steps, seg_len, (
+        int(save_every), d_dbeta or None, d_gamma or None, d_alpha or None, d_a0_soa or None, d_transfer_soa or None, int(flags),
+        d_a_end_soa or None, d_p_wave_end_soa or None, d_p_wave_max_soa or None, d_first_bad or None, d_traj_soa or None,
+        d_workspace or None))
 
 
 def chain_host(dbeta, *, n_steps, seg_len, save_every: int, gamma, alpha, a0, transfers=None, dbeta2=None,
@@ -487,40 +513,10 @@ def chain_host(dbeta, *, n_steps, seg_len, save_every: int, gamma, alpha, a0, tr
     a0 (n_waves,) or (N, n_waves) complex; transfers None, (S-1, n_waves) broadcast or (S-1, N, n_waves) complex.
     Returns the keys of sweep_host; traj is (N, n_saved_total, n_waves).
     """
-    dtype, cdt, f64 = _dtypes(dtype)
-    dbeta = np.ascontiguousarray(np.asarray(dbeta), dtype=dtype)
-    if dbeta.ndim != 2 or dbeta.shape[0] < 1:
-        raise ValueError("dbeta must have shape (S, N)")
-    S, N = (int(x) for x in dbeta.shape)
-    steps = np.ascontiguousarray(np.asarray(n_steps), dtype=np.int64)
-    lens = np.ascontiguousarray(np.asarray(seg_len), dtype=np.float64)
-    if steps.shape != (S,) or lens.shape != (S,):
-        raise ValueError(f"n_steps and seg_len must have shape ({S},)")
-    flags, gamma, alpha, a0, d2 = _point_inputs(N, dtype, cdt, int(extra_flags), gamma, alpha, a0, (4, 6), dbeta, dbeta2, S)
-    flags |= _check_flags(check_nan, exact_step, f64)
-    nw = int(a0.shape[1])
-    tr = None
-    if transfers is not None and S > 1:
-        tr = np.ascontiguousarray(np.asarray(transfers), dtype=cdt)
-        if tr.shape == (S - 1, nw):
-            flags |= BCAST_TRANSFER
-        elif tr.shape != (S - 1, N, nw):
-            raise ValueError(f"transfers must have shape ({S - 1}, {nw}) or ({S - 1}, {N}, {nw})")
-    n_rows = int(np.sum(steps // save_every + 1)) if save_every > 0 else 0
-    a_end = np.empty((N, nw), dtype=cdt)
-    p_end = np.empty(N, dtype=dtype)
-    p_max = np.empty(N, dtype=dtype)
-    bad = np.empty(N, dtype=np.int64)
-    traj = np.empty((N, n_rows, nw), dtype=cdt) if want_traj else None
-    w_end = np.empty((N, nw), dtype=dtype) if wave_summary else None
-    w_max = np.empty((N, nw), dtype=dtype) if wave_summary else None
-    ms = C.c_double(0.0)
-    _check(_fn("psa_rk4_chain", f64)(
-        int(device), nw, N, S, _ptr(steps), _ptr(lens), int(save_every), _ptr(dbeta), _ptr(d2), _ptr(gamma),
-        _ptr(alpha), _ptr(a0), _ptr(tr), flags, _ptr(a_end), _ptr(p_end), _ptr(p_max), _ptr(bad), _ptr(traj),
-        C.cast(C.byref(ms), _P), _ptr(w_end), _ptr(w_max)))
-    return dict(a_end=a_end, p_end=p_end, p_max=p_max, first_bad_step=bad, traj=traj, elapsed_ms=ms.value,
-                p_wave_end=w_end, p_wave_max=w_max)
+    return _chain_host("psa_rk4_chain", (4, 6), True, dbeta, n_steps=n_steps, seg_len=seg_len, save_every=save_every,
+                       gamma=gamma, alpha=alpha, a0=a0, transfers=transfers, dbeta2=dbeta2, check_nan=check_nan,
+                       exact_step=exact_step, want_traj=want_traj, dtype=dtype, device=device, wave_summary=wave_summary,
+                       extra_flags=extra_flags)
 
 
 def chain_workspace_bytes(n_waves: int, n_points: int, dtype=np.float64, wave_summary: bool = False) -> int:
@@ -534,12 +530,7 @@ def chain_device(*, stream: int, n_waves: int, n_points: int, n_steps, seg_len, 
                  d_a_end_soa: int, d_p_end: int, d_p_max: int, d_first_bad: int, d_traj_soa: int = 0,
                  d_p_wave_end: int = 0, d_p_wave_max: int = 0, d_workspace: int = 0, dtype=np.float64) -> None:
     """psa_rk4_chain_*_dev on device pointers (ints); n_steps / seg_len are host sequences of length S."""
-    steps = np.ascontiguousarray(np.asarray(n_steps), dtype=np.int64)
-    lens = np.ascontiguousarray(np.asarray(seg_len), dtype=np.float64)
-    if steps.ndim != 1 or steps.shape != lens.shape:
-        raise ValueError("n_steps and seg_len must be 1-D of equal length")
-    _check(_fn("psa_rk4_chain", _is_f64(dtype), dev=True)(
-        stream or None, int(n_waves), int(n_points), int(steps.shape[0]), _ptr(steps), _ptr(lens),
+    _chain_device("psa_rk4_chain", _is_f64(dtype), stream, (int(n_waves), int(n_points)), n_steps, seg_len, (
         int(save_every), d_dbeta or None, d_dbeta2 or None, d_gamma or None, d_alpha or None, d_a0_soa or None,
         d_transfer_soa or None, int(flags), d_a_end_soa or None, d_p_end or None, d_p_max or None,
         d_first_bad or None, d_traj_soa or None, d_p_wave_end or None, d_p_wave_max or None, d_workspace or None))

@@ -58,6 +58,7 @@ int64_t traj_ld_of(int64_t n_points, size_t elem_size) {
 // below (validate_grid, validate_common, fill_point_args, lossless_bit).
 template <typename T>
 struct SweepCall {   // psa_rk4_sweep_*, psa_rk4_sweep_waves_* and one span of a chain
+    using Real = T;
     int n_waves;
     int64_t n_points, n_steps;
     double z_max;
@@ -82,6 +83,7 @@ struct PairsCall {   // psa_rk4_sweep_pairs_f64*
 };
 template <typename T>
 struct SinglePumpCall {   // psa_rk4_single_pump_f64*, psa_rk4_single_pump_f32* and one span of a single-pump chain
+    using Real = T;
     int64_t n_points, n_steps;
     double z_max;
     int32_t save_every;
@@ -105,26 +107,17 @@ struct Rk45Call {    // psa_rk45_sweep_f64*
     double *traj;
     int64_t traj_ld;   // leading dimension of the device rows: n_points (`_dev`), traj_ld_of (the host form's staging)
 };
-template <typename T>
-struct ChainCall {   // psa_rk4_chain_*
-    SweepCall<T> s;             // what the spans share; its n_steps and z_max are set span by span from the arrays below
+template <typename Span>
+struct ChainCall {   // psa_rk4_chain_* (Span = SweepCall<T>) and psa_rk4_single_pump_chain_f64* (Span = SinglePumpCall<double>)
+    Span s;                     // what the spans share; its n_steps and z_max are set span by span from the arrays below
     int n_segments;
     const int64_t *n_steps;     // host [S]
     const double *seg_len;      // host [S]
-    const T *transfer;
-    void *workspace;            // device scratch of more than one span (chain_workspace_bytes)
+    const typename Span::Real *transfer;
+    void *workspace;            // device scratch of more than one span (carve_chain)
     // host [S] or NULL: span s gets PSA_OPT_LOSSLESS where it is non-zero (the host-buffer entry points: a broadcast alpha
     // of 0); `_dev` callers pass PSA_OPT_LOSSLESS for the whole chain instead
     const unsigned char *lossless = nullptr;
-};
-struct SinglePumpChainCall {   // psa_rk4_single_pump_chain_f64*
-    SinglePumpCall<double> s;   // what the spans share; its n_steps and z_max are set span by span from the arrays below
-    int n_segments;
-    const int64_t *n_steps;     // host [S]
-    const double *seg_len;      // host [S]
-    const double *transfer;
-    void *workspace;            // device scratch of more than one span (single_pump_chain_workspace_bytes)
-    const unsigned char *lossless = nullptr;   // as ChainCall's
 };
 
 // The grid rules of every fixed-step family.  lanes_per_point: named in the message when the launch limit depends on it (0: not).
@@ -724,15 +717,73 @@ template <typename T> struct EpilogueLaunch;
 template <> struct EpilogueLaunch<double> { static constexpr auto fn = psa::launch_chain_epilogue_f64; };
 template <> struct EpilogueLaunch<float> { static constexpr auto fn = psa::launch_chain_epilogue_f32; };
 
-// device scratch of a chain of more than one span: Theta (float64, one per signal), the next span's a0, and the
-// span's own outputs before they are folded into the running ones
-int64_t chain_workspace_bytes(int n_waves, int64_t n_points, size_t elem, bool waves) {
-    if ((n_waves != 4 && n_waves != 6) || n_points < 0 || (elem != 4 && elem != 8)) return -1;
-    using C = Carver;
-    const size_t N = (size_t)n_points, nc = 2 * (size_t)n_waves;
-    return (int64_t)(C::aligned(N * 8) * (n_waves == 6 ? 2 : 1) + 2 * C::aligned(nc * N * elem) +
-                     2 * C::aligned(N * elem) + C::aligned(N * 8) + (waves ? 2 * C::aligned((size_t)n_waves * N * elem) : 0));
-}
+// What differs between the chain families, stated once per family: the span's record decides.
+template <typename Span> struct ChainFamily;
+template <typename T> struct ChainFamily<SweepCall<T>> {   // 4 and 6 waves [p1, p2, s, i, ...]
+    static constexpr int sig_wave = 2;
+    static constexpr bool signal_summary = true;      // p_end / p_max
+    static constexpr bool waves_optional = true;      // the per-wave summary where p_wave_end / p_wave_max are given
+    static constexpr bool second_mismatch = true;     // dbeta2 / theta2 (6 waves)
+    static constexpr const char *what = "the fibre chain";
+    static int n_waves(const SweepCall<T> &c) { return c.n_waves; }
+    static int validate_first(const SweepCall<T> &first, bool) { return validate_common(first); }
+    static int span_dev(void *stream, const SweepCall<T> &c) { return sweep_dev<T>(stream, c); }
+    static void stage_summary(Staging<T> &sg, SweepCall<T> &d, const SweepCall<T> &c, size_t N) {
+        d.p_end = sg.output(c.p_end, N);
+        d.p_max = sg.output(c.p_max, N);
+        d.first_bad = sg.output(c.first_bad, N);
+        d.wave_end = sg.output_soa(c.wave_end, N, c.n_waves);
+        d.wave_max = sg.output_soa(c.wave_max, N, c.n_waves);
+    }
+};
+template <typename T> struct ChainFamily<SinglePumpCall<T>> {   // three waves [p, s, i]: the three per-wave columns are the summary
+    static constexpr int sig_wave = 1;
+    static constexpr bool signal_summary = false, waves_optional = false, second_mismatch = false;
+    static constexpr const char *what = "the single-pump fibre chain";
+    static int n_waves(const SinglePumpCall<T> &) { return 3; }
+    static int validate_first(SinglePumpCall<T> first, bool host_form) {
+        first.flags &= ~PSA_BCAST_TRANSFER;   // the chain's own bit
+        return validate_single_pump(first, host_form);
+    }
+    static int span_dev(void *stream, const SinglePumpCall<T> &c) { return single_pump_dev(stream, c); }
+    static void stage_summary(Staging<T> &sg, SinglePumpCall<T> &d, const SinglePumpCall<T> &c, size_t N) {
+        d.wave_end = sg.output_soa(c.wave_end, N, 3);
+        d.wave_max = sg.output_soa(c.wave_max, N, 3);
+        d.first_bad = sg.output(c.first_bad, N);
+    }
+};
+
+// Device scratch of a chain of more than one span: Theta (float64, one per signal), the next span's a0, and the span's own
+// outputs before they are folded into the running ones.  Without a base it only measures (`bytes`).
+template <typename T>
+struct ChainScratch {
+    double *theta, *theta2;
+    T *a0_next, *a_end_s, *p_end_s, *p_max_s;
+    int64_t *bad_s;
+    T *wend_s, *wmax_s;
+    size_t bytes;
+    ChainScratch(void *base, size_t N, int n_waves, bool two_thetas, bool signal_summary, bool waves) {
+        Carver ws;
+        ws.base = (char *)base;
+        theta = ws.take<double>(N);
+        theta2 = two_thetas ? ws.take<double>(N) : nullptr;
+        a0_next = ws.take<T>(2 * (size_t)n_waves * N);
+        a_end_s = ws.take<T>(2 * (size_t)n_waves * N);
+        p_end_s = signal_summary ? ws.take<T>(N) : nullptr;
+        p_max_s = signal_summary ? ws.take<T>(N) : nullptr;
+        bad_s = ws.take<int64_t>(N);
+        wend_s = waves ? ws.take<T>((size_t)n_waves * N) : nullptr;
+        wmax_s = waves ? ws.take<T>((size_t)n_waves * N) : nullptr;
+        bytes = ws.used;
+    }
+    template <typename Span>
+    static ChainScratch of(void *base, const Span &c) {
+        using F = ChainFamily<Span>;
+        const int n_waves = F::n_waves(c);
+        return ChainScratch(base, (size_t)c.n_points, n_waves, F::second_mismatch && n_waves == 6, F::signal_summary,
+                            !F::waves_optional || c.wave_end != nullptr);
+    }
+};
 
 // The part of span s's epilogue record that every chain family fills alike: the frame (Theta, the rows to rotate, the
 // A-frame a_end of the last span), first_bad_step with its step offset, and the boundary to span s + 1.  The family adds its
@@ -806,36 +857,41 @@ std::vector<unsigned char> lossless_spans(uint32_t flags, const T *alpha, int S,
     return lossless;
 }
 
-// argument rules of psa_rk4_chain_*
-template <typename T>
-int validate_chain(const ChainCall<T> &c, int64_t *rows_total) {
+// argument rules of every chain: the span count, the first span's grid through the family's sweep validator, the later spans
+template <typename Span>
+int validate_chain(const ChainCall<Span> &c, bool host_form, int64_t *rows_total) {
+    using F = ChainFamily<Span>;
     if (c.n_segments < 1) return fail(PSA_E_NSTEPS, "n_segments must be >= 1, got %d", c.n_segments);
     if (!c.n_steps || !c.seg_len) return fail(PSA_E_NULLPTR, "n_steps / seg_len is NULL");
-    SweepCall<T> first = c.s;   // the sweep's rules, on the first span's grid
+    Span first = c.s;   // the sweep's rules, on the first span's grid
     first.n_steps = c.n_steps[0];
     first.z_max = c.seg_len[0];
-    int rc = validate_common(first);
+    int rc = F::validate_first(first, host_form);
     if (rc != PSA_OK) return rc;
     int64_t rows = 0;
     if ((rc = validate_spans(c.n_segments, c.n_steps, c.seg_len, c.s.save_every, &rows)) != PSA_OK) return rc;
-    if ((c.s.wave_end != nullptr) != (c.s.wave_max != nullptr))
-        return fail(PSA_E_NULLPTR, "p_wave_end and p_wave_max are given together or not at all");
-    if (c.s.wave_end && (rc = validate_waves(c.s)) != PSA_OK) return rc;
-    if (c.s.traj && (long double)rows * 2 * c.s.n_waves * (long double)traj_ld_of(c.s.n_points, sizeof(T)) > 4.0e18L)
+    if constexpr (F::waves_optional) {
+        if ((c.s.wave_end != nullptr) != (c.s.wave_max != nullptr))
+            return fail(PSA_E_NULLPTR, "p_wave_end and p_wave_max are given together or not at all");
+        if (c.s.wave_end && (rc = validate_waves(c.s)) != PSA_OK) return rc;
+    }
+    if (c.s.traj && (long double)rows * 2 * F::n_waves(c.s) * (long double)traj_ld_of(c.s.n_points, sizeof(typename Span::Real)) > 4.0e18L)
         return fail(PSA_E_TOO_LARGE, "trajectory buffer too large");
     *rows_total = rows;
     return PSA_OK;
 }
 
-template <typename T>
-int chain_dev(void *stream, const ChainCall<T> &c) {
+template <typename Span>
+int chain_dev(void *stream, const ChainCall<Span> &c) {
+    using F = ChainFamily<Span>;
+    using T = typename Span::Real;
     int64_t rows_total = 0;
-    int rc = validate_chain(c, &rows_total);
+    int rc = validate_chain(c, false, &rows_total);
     if (rc != PSA_OK) return rc;
     if (c.s.n_points == 0) return PSA_OK;
-    const int S = c.n_segments, n_waves = c.s.n_waves;
+    const int S = c.n_segments, n_waves = F::n_waves(c.s);
     const uint32_t flags = c.s.flags;
-    SweepCall<T> sp = c.s;   // the span being run
+    Span sp = c.s;   // the span being run
     auto set_span = [&](int s) {
         sp.n_steps = c.n_steps[s];
         sp.z_max = c.seg_len[s];
@@ -845,60 +901,54 @@ int chain_dev(void *stream, const ChainCall<T> &c) {
     };
     if (S == 1) {   // one span IS the sweep: same launch, same outputs, bit for bit
         set_span(0);
-        return sweep_dev<T>(stream, sp);
+        return F::span_dev(stream, sp);
     }
     if (!c.workspace) return fail(PSA_E_NULLPTR, "a chain of more than one span needs d_workspace");
 
     const size_t N = (size_t)c.s.n_points;
     const int nc = 2 * n_waves;
-    const bool waves = c.s.wave_end != nullptr;
-    Carver ws;
-    ws.base = (char *)c.workspace;
-    double *theta = ws.take<double>(N);
-    double *theta2 = n_waves == 6 ? ws.take<double>(N) : nullptr;
-    T *a0_next = ws.take<T>(nc * N);
-    T *a_end_s = ws.take<T>(nc * N);
-    T *p_end_s = ws.take<T>(N);
-    T *p_max_s = ws.take<T>(N);
-    int64_t *bad_s = ws.take<int64_t>(N);
-    T *wend_s = waves ? ws.take<T>(n_waves * N) : nullptr;
-    T *wmax_s = waves ? ws.take<T>(n_waves * N) : nullptr;
-
+    const auto w = ChainScratch<T>::of(c.workspace, c.s);
     const size_t ld = (flags & PSA_OPT_TRAJ_LD) ? (size_t)traj_ld_of(c.s.n_points, sizeof(T)) : N;
     const size_t g_step = (flags & PSA_BCAST_GAMMA) ? 1 : N, a_step = (flags & PSA_BCAST_ALPHA) ? 1 : N;
     const size_t t_step = (flags & PSA_BCAST_TRANSFER) ? (size_t)nc : nc * N;
-    const SpanJoin<T> join{c.s.n_points, S, flags, c.transfer, t_step, c.s.a_end, a0_next, a_end_s, c.s.first_bad, bad_s, theta, ld};
+    const SpanJoin<T> join{c.s.n_points, S, flags, c.transfer, t_step, c.s.a_end, w.a0_next, w.a_end_s, c.s.first_bad, w.bad_s, w.theta, ld};
     int64_t row = 0, step_off = 0;
     for (int s = 0; s < S; ++s) {
         const bool first = s == 0;
         set_span(s);
         sp.dbeta = c.s.dbeta + s * N;
-        sp.dbeta2 = c.s.dbeta2 ? c.s.dbeta2 + s * N : nullptr;
         sp.gamma = c.s.gamma + s * g_step;
         sp.alpha = c.s.alpha + s * a_step;
-        sp.a0 = first ? c.s.a0 : a0_next;
-        sp.a_end = a_end_s;
-        sp.p_end = first ? c.s.p_end : p_end_s;
-        sp.p_max = first ? c.s.p_max : p_max_s;
-        sp.first_bad = first ? c.s.first_bad : bad_s;
+        sp.a0 = first ? c.s.a0 : w.a0_next;
+        sp.a_end = w.a_end_s;
+        sp.first_bad = first ? c.s.first_bad : w.bad_s;
         sp.traj = c.s.traj ? c.s.traj + (size_t)row * n_waves * ld * 2 : nullptr;
-        sp.wave_end = waves ? (first ? c.s.wave_end : wend_s) : nullptr;
-        sp.wave_max = waves ? (first ? c.s.wave_max : wmax_s) : nullptr;
-        rc = sweep_dev<T>(stream, sp);
+        sp.wave_end = w.wend_s ? (first ? c.s.wave_end : w.wend_s) : nullptr;
+        sp.wave_max = w.wmax_s ? (first ? c.s.wave_max : w.wmax_s) : nullptr;
+        if constexpr (F::signal_summary) {
+            sp.p_end = first ? c.s.p_end : w.p_end_s;
+            sp.p_max = first ? c.s.p_max : w.p_max_s;
+        }
+        if constexpr (F::second_mismatch) sp.dbeta2 = c.s.dbeta2 ? c.s.dbeta2 + s * N : nullptr;
+        rc = F::span_dev(stream, sp);
         if (rc != PSA_OK) return rc;
         psa::ChainEpilogue<T> e = join.record(s, step_off, sp.traj, sp.n_steps / sp.save_every + 1, sp.dbeta, sp.z_max);
         e.n_waves = n_waves;
-        e.sig_wave = 2;
-        e.p_end_s = p_end_s;
-        e.p_max_s = p_max_s;
-        e.wave_end_s = wend_s;
-        e.wave_max_s = wmax_s;
-        e.p_end = c.s.p_end;
-        e.p_max = c.s.p_max;
+        e.sig_wave = F::sig_wave;
+        e.p_end_s = w.p_end_s;
+        e.p_max_s = w.p_max_s;
+        e.wave_end_s = w.wend_s;
+        e.wave_max_s = w.wmax_s;
         e.wave_end = c.s.wave_end;
         e.wave_max = c.s.wave_max;
-        e.theta2 = theta2;
-        e.dbeta2 = sp.dbeta2;
+        e.theta2 = w.theta2;
+        e.p_end = e.p_max = nullptr;   // a family without the signal summary, without a second mismatch
+        e.dbeta2 = nullptr;
+        if constexpr (F::signal_summary) {
+            e.p_end = c.s.p_end;
+            e.p_max = c.s.p_max;
+        }
+        if constexpr (F::second_mismatch) e.dbeta2 = sp.dbeta2;
         hipError_t he = EpilogueLaunch<T>::fn((hipStream_t)stream, e);
         if (he != hipSuccess) return hip_fail(he, "chain epilogue launch");
         row += e.rows;
@@ -907,173 +957,49 @@ int chain_dev(void *stream, const ChainCall<T> &c) {
     return PSA_OK;
 }
 
-template <typename T>
-int chain_host(int device, const ChainCall<T> &c, double *elapsed_ms) {
+template <typename Span>
+int chain_host(int device, const ChainCall<Span> &c, double *elapsed_ms) {
+    using F = ChainFamily<Span>;
+    using T = typename Span::Real;
     int64_t rows_total = 0;
-    int rc = validate_chain(c, &rows_total);
+    int rc = validate_chain(c, true, &rows_total);
     if (rc != PSA_OK) return rc;
     if (elapsed_ms) *elapsed_ms = 0.0;
     if (c.s.n_points == 0) return PSA_OK;
 
-    const int S = c.n_segments, n_waves = c.s.n_waves, nc = 2 * n_waves;
+    const int S = c.n_segments, nc = 2 * F::n_waves(c.s);
     const size_t N = (size_t)c.s.n_points;
     const uint32_t flags = c.s.flags;
     const std::vector<unsigned char> lossless = lossless_spans(flags, c.s.alpha, S, N);
-    ChainCall<T> d = c;
-    if (c.s.traj) d.s.flags |= PSA_OPT_TRAJ_LD;
+    ChainCall<Span> d = c;
+    if (c.s.traj) d.s.flags |= PSA_OPT_TRAJ_LD;   // the device-side trajectory has its own leading dimension; the caller's is dense
     d.lossless = lossless.data();
     const T *tr = S > 1 ? c.transfer : nullptr;
     auto layout = [&](Staging<T> &sg) {
         d.s.dbeta = sg.input(c.s.dbeta, S * N);
-        d.s.dbeta2 = sg.input(c.s.dbeta2, S * N);
+        if constexpr (F::second_mismatch) d.s.dbeta2 = sg.input(c.s.dbeta2, S * N);
         d.s.gamma = sg.input(c.s.gamma, (flags & PSA_BCAST_GAMMA) ? (size_t)S : S * N);
         d.s.alpha = sg.input(c.s.alpha, (flags & PSA_BCAST_ALPHA) ? (size_t)S : S * N);
         d.s.a0 = sg.input_soa(c.s.a0, (flags & PSA_BCAST_A0) ? 1 : N, nc);
         // [S-1][n_waves][2] is already [S-1][2*n_waves]; [S-1][N][n_waves][2] -> [S-1][2*n_waves][N]
         d.transfer = (flags & PSA_BCAST_TRANSFER) ? sg.input(tr, (size_t)(S - 1) * nc) : sg.input_soa(tr, N, nc, S - 1);
-        d.workspace = S > 1 ? sg.template scratch<char>((size_t)chain_workspace_bytes(n_waves, c.s.n_points, sizeof(T),
-                                                                                      c.s.wave_end != nullptr))
-                            : nullptr;
+        d.workspace = S > 1 ? sg.template scratch<char>(ChainScratch<T>::of(nullptr, c.s).bytes) : nullptr;
         d.s.a_end = sg.output_soa(c.s.a_end, N, nc);
-        d.s.p_end = sg.output(c.s.p_end, N);
-        d.s.p_max = sg.output(c.s.p_max, N);
-        d.s.first_bad = sg.output(c.s.first_bad, N);
-        d.s.wave_end = sg.output_soa(c.s.wave_end, N, n_waves);
-        d.s.wave_max = sg.output_soa(c.s.wave_max, N, n_waves);
+        F::stage_summary(sg, d.s, c.s, N);
         d.s.traj = sg.trajectory(c.s.traj, N, (size_t)rows_total, nc);
     };
-    return host_call<T>(device, "the fibre chain", elapsed_ms, layout, [&](hipStream_t st) { return chain_dev<T>(st, d); });
+    return host_call<T>(device, F::what, elapsed_ms, layout, [&](hipStream_t st) { return chain_dev(st, d); });
 }
 
-// ---- single-pump chains (psa_rk4_single_pump_chain_f64*): the chain above for the three-wave model [p, s, i] ---------------
-// The same gauge with the signal at index 1; each span is one launch of the unchanged single-pump kernel, joined by the
-// same epilogue (sig_wave = 1, no p_end / p_max: this family always writes the three per-wave columns).
-// device scratch of more than one span: Theta, the next span's a0, the span's a_end, first_bad and per-wave summary
-int64_t single_pump_chain_workspace_bytes(int64_t n_points) {
-    if (n_points < 0) return -1;
-    using C = Carver;
+// the two exported sizes: the same carve, measured; -1 for a call no chain takes
+int64_t chain_workspace_bytes(int n_waves, int64_t n_points, size_t elem, bool waves) {
+    if ((n_waves != 4 && n_waves != 6) || n_points < 0 || (elem != 4 && elem != 8)) return -1;
     const size_t N = (size_t)n_points;
-    return (int64_t)(C::aligned(N * 8) + 2 * C::aligned(6 * N * 8) + C::aligned(N * 8) + 2 * C::aligned(3 * N * 8));
+    return (int64_t)(elem == 8 ? ChainScratch<double>(nullptr, N, n_waves, n_waves == 6, true, waves).bytes
+                               : ChainScratch<float>(nullptr, N, n_waves, n_waves == 6, true, waves).bytes);
 }
-
-// validate_chain's order on top of the single-pump rules (validate_single_pump on the first span's grid)
-int validate_single_pump_chain(const SinglePumpChainCall &c, bool host_form, int64_t *rows_total) {
-    if (c.n_segments < 1) return fail(PSA_E_NSTEPS, "n_segments must be >= 1, got %d", c.n_segments);
-    if (!c.n_steps || !c.seg_len) return fail(PSA_E_NULLPTR, "n_steps / seg_len is NULL");
-    SinglePumpCall<double> first = c.s;
-    first.n_steps = c.n_steps[0];
-    first.z_max = c.seg_len[0];
-    first.flags &= ~PSA_BCAST_TRANSFER;   // the chain's own bit
-    int rc = validate_single_pump(first, host_form);
-    if (rc != PSA_OK) return rc;
-    int64_t rows = 0;
-    if ((rc = validate_spans(c.n_segments, c.n_steps, c.seg_len, c.s.save_every, &rows)) != PSA_OK) return rc;
-    if (c.s.traj && (long double)rows * 6 * (long double)traj_ld_of(c.s.n_points, sizeof(double)) > 4.0e18L)
-        return fail(PSA_E_TOO_LARGE, "trajectory buffer too large");
-    *rows_total = rows;
-    return PSA_OK;
-}
-
-int single_pump_chain_dev(void *stream, const SinglePumpChainCall &c) {
-    int64_t rows_total = 0;
-    int rc = validate_single_pump_chain(c, false, &rows_total);
-    if (rc != PSA_OK) return rc;
-    if (c.s.n_points == 0) return PSA_OK;
-    const int S = c.n_segments;
-    const uint32_t flags = c.s.flags;
-    SinglePumpCall<double> sp = c.s;   // the span being run
-    auto set_span = [&](int s) {
-        sp.n_steps = c.n_steps[s];
-        sp.z_max = c.seg_len[s];
-        sp.flags = flags & ~PSA_BCAST_TRANSFER;
-        if (s > 0) sp.flags &= ~PSA_BCAST_A0;                  // the next span starts from a per-point state
-        if (c.lossless && c.lossless[s]) sp.flags |= PSA_OPT_LOSSLESS;
-    };
-    if (S == 1) {   // one span IS the sweep: same launch, same outputs, bit for bit
-        set_span(0);
-        return single_pump_dev(stream, sp);
-    }
-    if (!c.workspace) return fail(PSA_E_NULLPTR, "a chain of more than one span needs d_workspace");
-
-    const size_t N = (size_t)c.s.n_points;
-    Carver ws;
-    ws.base = (char *)c.workspace;
-    double *theta = ws.take<double>(N);
-    double *a0_next = ws.take<double>(6 * N);
-    double *a_end_s = ws.take<double>(6 * N);
-    int64_t *bad_s = ws.take<int64_t>(N);
-    double *wend_s = ws.take<double>(3 * N);
-    double *wmax_s = ws.take<double>(3 * N);
-
-    const size_t ld = (flags & PSA_OPT_TRAJ_LD) ? (size_t)traj_ld_of(c.s.n_points, sizeof(double)) : N;
-    const size_t g_step = (flags & PSA_BCAST_GAMMA) ? 1 : N, a_step = (flags & PSA_BCAST_ALPHA) ? 1 : N;
-    const size_t t_step = (flags & PSA_BCAST_TRANSFER) ? (size_t)6 : 6 * N;
-    const SpanJoin<double> join{c.s.n_points, S, flags, c.transfer, t_step, c.s.a_end, a0_next, a_end_s, c.s.first_bad, bad_s, theta, ld};
-    int64_t row = 0, step_off = 0;
-    for (int s = 0; s < S; ++s) {
-        const bool first = s == 0;
-        set_span(s);
-        sp.dbeta = c.s.dbeta + s * N;
-        sp.gamma = c.s.gamma + s * g_step;
-        sp.alpha = c.s.alpha + s * a_step;
-        sp.a0 = first ? c.s.a0 : a0_next;
-        sp.a_end = a_end_s;
-        sp.wave_end = first ? c.s.wave_end : wend_s;
-        sp.wave_max = first ? c.s.wave_max : wmax_s;
-        sp.first_bad = first ? c.s.first_bad : bad_s;
-        sp.traj = c.s.traj ? c.s.traj + (size_t)row * 3 * ld * 2 : nullptr;
-        rc = single_pump_dev(stream, sp);
-        if (rc != PSA_OK) return rc;
-        psa::ChainEpilogue<double> e = join.record(s, step_off, sp.traj, sp.n_steps / sp.save_every + 1, sp.dbeta, sp.z_max);
-        e.n_waves = 3;
-        e.sig_wave = 1;
-        e.p_end_s = e.p_max_s = nullptr;   // no signal summary in this family: the three per-wave columns are the summary
-        e.p_end = e.p_max = nullptr;
-        e.wave_end_s = wend_s;
-        e.wave_max_s = wmax_s;
-        e.wave_end = c.s.wave_end;
-        e.wave_max = c.s.wave_max;
-        e.theta2 = nullptr;
-        e.dbeta2 = nullptr;
-        hipError_t he = psa::launch_chain_epilogue_f64((hipStream_t)stream, e);
-        if (he != hipSuccess) return hip_fail(he, "chain epilogue launch");
-        row += e.rows;
-        step_off += sp.n_steps;
-    }
-    return PSA_OK;
-}
-
-int single_pump_chain_host(int device, const SinglePumpChainCall &c, double *elapsed_ms) {
-    int64_t rows_total = 0;
-    int rc = validate_single_pump_chain(c, true, &rows_total);
-    if (rc != PSA_OK) return rc;
-    if (elapsed_ms) *elapsed_ms = 0.0;
-    if (c.s.n_points == 0) return PSA_OK;
-
-    const int S = c.n_segments;
-    const size_t N = (size_t)c.s.n_points;
-    const uint32_t flags = c.s.flags;
-    const std::vector<unsigned char> lossless = lossless_spans(flags, c.s.alpha, S, N);
-    SinglePumpChainCall d = c;
-    if (c.s.traj) d.s.flags |= PSA_OPT_TRAJ_LD;   // the device-side trajectory has its own leading dimension; the caller's is dense
-    d.lossless = lossless.data();
-    const double *tr = S > 1 ? c.transfer : nullptr;
-    auto layout = [&](Staging<double> &sg) {
-        d.s.dbeta = sg.input(c.s.dbeta, S * N);
-        d.s.gamma = sg.input(c.s.gamma, (flags & PSA_BCAST_GAMMA) ? (size_t)S : S * N);
-        d.s.alpha = sg.input(c.s.alpha, (flags & PSA_BCAST_ALPHA) ? (size_t)S : S * N);
-        d.s.a0 = sg.input_soa(c.s.a0, (flags & PSA_BCAST_A0) ? 1 : N, 6);
-        // [S-1][3][2] is already [S-1][6]; [S-1][N][3][2] -> [S-1][6][N]
-        d.transfer = (flags & PSA_BCAST_TRANSFER) ? sg.input(tr, (size_t)(S - 1) * 6) : sg.input_soa(tr, N, 6, S - 1);
-        d.workspace = S > 1 ? sg.template scratch<char>((size_t)single_pump_chain_workspace_bytes(c.s.n_points)) : nullptr;
-        d.s.a_end = sg.output_soa(c.s.a_end, N, 6);
-        d.s.wave_end = sg.output_soa(c.s.wave_end, N, 3);
-        d.s.wave_max = sg.output_soa(c.s.wave_max, N, 3);
-        d.s.first_bad = sg.output(c.s.first_bad, N);
-        d.s.traj = sg.trajectory(c.s.traj, N, (size_t)rows_total, 6);
-    };
-    return host_call<double>(device, "the single-pump fibre chain", elapsed_ms, layout,
-                             [&](hipStream_t st) { return single_pump_chain_dev(st, d); });
+int64_t single_pump_chain_workspace_bytes(int64_t n_points) {
+    return n_points < 0 ? -1 : (int64_t)ChainScratch<double>(nullptr, (size_t)n_points, 3, false, false, true).bytes;
 }
 
 template <typename T> struct GainLaunch;
@@ -1494,7 +1420,7 @@ int psa_rk4_chain_f64(int device, int n_waves, int64_t n_points, int n_segments,
                       const double *seg_len, int32_t save_every, const double *dbeta, const double *dbeta2, const double *gamma,
                       const double *alpha, const double *a0, const double *transfer, uint32_t flags, double *a_end, double *p_end,
                       double *p_max, int64_t *first_bad, double *traj, double *elapsed_ms, double *p_wave_end, double *p_wave_max) {
-    return chain_host<double>(device, {{n_waves, n_points, 0, 0.0, save_every, dbeta, dbeta2, gamma, alpha, a0, flags, a_end,
+    return chain_host<SweepCall<double>>(device, {{n_waves, n_points, 0, 0.0, save_every, dbeta, dbeta2, gamma, alpha, a0, flags, a_end,
                                        p_end, p_max, first_bad, traj, p_wave_end, p_wave_max}, n_segments, n_steps, seg_len,
                                        transfer, nullptr}, elapsed_ms);
 }
@@ -1504,7 +1430,7 @@ int psa_rk4_chain_f64_dev(void *stream, int n_waves, int64_t n_points, int n_seg
                           const double *d_gamma, const double *d_alpha, const double *d_a0_soa, const double *d_transfer_soa,
                           uint32_t flags, double *d_a_end_soa, double *d_p_end, double *d_p_max, int64_t *d_first_bad,
                           double *d_traj_soa, double *d_p_wave_end_soa, double *d_p_wave_max_soa, void *d_workspace) {
-    return chain_dev<double>(stream, {{n_waves, n_points, 0, 0.0, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha, d_a0_soa,
+    return chain_dev<SweepCall<double>>(stream, {{n_waves, n_points, 0, 0.0, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha, d_a0_soa,
                                       flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa, d_p_wave_end_soa,
                                       d_p_wave_max_soa}, n_segments, n_steps, seg_len, d_transfer_soa, d_workspace});
 }
@@ -1513,7 +1439,7 @@ int psa_rk4_chain_f32(int device, int n_waves, int64_t n_points, int n_segments,
                       const double *seg_len, int32_t save_every, const float *dbeta, const float *dbeta2, const float *gamma,
                       const float *alpha, const float *a0, const float *transfer, uint32_t flags, float *a_end, float *p_end,
                       float *p_max, int64_t *first_bad, float *traj, double *elapsed_ms, float *p_wave_end, float *p_wave_max) {
-    return chain_host<float>(device, {{n_waves, n_points, 0, 0.0, save_every, dbeta, dbeta2, gamma, alpha, a0, flags, a_end,
+    return chain_host<SweepCall<float>>(device, {{n_waves, n_points, 0, 0.0, save_every, dbeta, dbeta2, gamma, alpha, a0, flags, a_end,
                                       p_end, p_max, first_bad, traj, p_wave_end, p_wave_max}, n_segments, n_steps, seg_len,
                                       transfer, nullptr}, elapsed_ms);
 }
@@ -1523,7 +1449,7 @@ int psa_rk4_chain_f32_dev(void *stream, int n_waves, int64_t n_points, int n_seg
                           const float *d_gamma, const float *d_alpha, const float *d_a0_soa, const float *d_transfer_soa,
                           uint32_t flags, float *d_a_end_soa, float *d_p_end, float *d_p_max, int64_t *d_first_bad,
                           float *d_traj_soa, float *d_p_wave_end_soa, float *d_p_wave_max_soa, void *d_workspace) {
-    return chain_dev<float>(stream, {{n_waves, n_points, 0, 0.0, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha, d_a0_soa,
+    return chain_dev<SweepCall<float>>(stream, {{n_waves, n_points, 0, 0.0, save_every, d_dbeta, d_dbeta2, d_gamma, d_alpha, d_a0_soa,
                                      flags, d_a_end_soa, d_p_end, d_p_max, d_first_bad, d_traj_soa, d_p_wave_end_soa,
                                      d_p_wave_max_soa}, n_segments, n_steps, seg_len, d_transfer_soa, d_workspace});
 }
@@ -1607,7 +1533,7 @@ int psa_rk4_single_pump_chain_f64(int device, int64_t n_points, int n_segments, 
                                   const double *a0_re_im, const double *transfer_re_im, uint32_t flags, double *a_end_re_im,
                                   double *p_wave_end, double *p_wave_max, int64_t *first_bad_step, double *traj_or_null,
                                   double *elapsed_ms_or_null) {
-    return single_pump_chain_host(device, {{n_points, 0, 0.0, save_every, dbeta, gamma, alpha, a0_re_im, flags, a_end_re_im,
+    return chain_host<SinglePumpCall<double>>(device, {{n_points, 0, 0.0, save_every, dbeta, gamma, alpha, a0_re_im, flags, a_end_re_im,
                                             p_wave_end, p_wave_max, first_bad_step, traj_or_null}, n_segments, n_steps,
                                            seg_len, transfer_re_im, nullptr}, elapsed_ms_or_null);
 }
@@ -1616,7 +1542,7 @@ int psa_rk4_single_pump_chain_f64_dev(void *stream, int64_t n_points, int n_segm
                                       const double *d_alpha, const double *d_a0_soa, const double *d_transfer_soa,
                                       uint32_t flags, double *d_a_end_soa, double *d_p_wave_end_soa, double *d_p_wave_max_soa,
                                       int64_t *d_first_bad_step, double *d_traj_soa_or_null, void *d_workspace) {
-    return single_pump_chain_dev(stream, {{n_points, 0, 0.0, save_every, d_dbeta, d_gamma, d_alpha, d_a0_soa, flags,
+    return chain_dev<SinglePumpCall<double>>(stream, {{n_points, 0, 0.0, save_every, d_dbeta, d_gamma, d_alpha, d_a0_soa, flags,
                                            d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step,
                                            d_traj_soa_or_null}, n_segments, n_steps, seg_len, d_transfer_soa, d_workspace});
 }

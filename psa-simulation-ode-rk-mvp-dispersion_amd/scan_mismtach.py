@@ -768,6 +768,54 @@ def scan_single_pump_gain(*, cfg: SimulationConfig, lambda_pump_m: float, lambda
                 dbeta=nan(db) * pre["scale"], first_bad_step=res.first_bad_step, result=res)
 
 
+def _phase_scan_axes(phase, psa_delta_beta):
+    """The rules both copier - PSA scans share for their two axes -> (phase (K,), psa_delta_beta () or (M,))."""
+    ph = np.linspace(0.0, 2.0 * np.pi, 32, endpoint=False) if phase is None else np.asarray(phase, dtype=float)
+    if ph.ndim != 1 or ph.size == 0 or not np.all(np.isfinite(ph)):
+        raise ValueError("phase must be a non-empty 1D sequence of finite values")
+    dbp = np.asarray(psa_delta_beta, dtype=float)
+    if dbp.ndim > 1 or dbp.size == 0 or not np.all(np.isfinite(dbp)):
+        raise ValueError("psa_delta_beta must be a finite scalar or a non-empty 1D sequence")
+    return ph, dbp
+
+
+def _copier_psa_chain(ph, dbp, mask, transfer_of, a_in, *, psa_cfg, copier_cfg, gamma, alpha, copier_delta_beta, copier_gamma,
+                      copier_alpha, length_unit):
+    """The K x M chains of a copier - PSA scan, point k * M + m -> (spans, transfers, a0) for the family's chain driver.
+    ``mask``: the waves that take the scanned phase; ``transfer_of``: the family's mid-stage on (K, n_waves) scanned phases;
+    ``a_in``: the input amplitudes (n_waves,)."""
+    from .sweep import FibreSpan
+    provided = PhaseMatchingConfig(method=PhaseMatchingMethod.PROVIDED, provided_delta_beta=0.0)
+    cfgs = [psa_cfg] if copier_cfg is None else [copier_cfg, psa_cfg]
+    pres = [_prepare(c, gamma=0.0, alpha=0.0, dispersion=None, phase_matching_cfg=provided, beta_legacy=None,
+                     length_unit=length_unit) for c in cfgs]
+    if any(int(c.save_every) != int(psa_cfg.save_every) or bool(c.check_nan) != bool(psa_cfg.check_nan) for c in cfgs):
+        raise ValueError("copier_cfg and psa_cfg must share save_every and check_nan")
+    scale = pres[0]["scale"]
+    K, M = ph.size, max(dbp.size, 1)
+    db_pts = np.tile(np.atleast_1d(dbp), K) / scale
+    T = np.repeat(transfer_of(ph[:, None] * mask[None, :]), M, axis=0)           # (K * M, n_waves)
+    psa = FibreSpan(pres[-1]["fiber"].length_m, dz=pres[-1]["grid"].dz_m, dbeta=db_pts, gamma=float(gamma) / scale,
+                    alpha=float(alpha) / scale)
+    if copier_cfg is None:
+        return [psa], None, T * a_in[None, :]
+    cg = gamma if copier_gamma is None else copier_gamma
+    ca = alpha if copier_alpha is None else copier_alpha
+    copier = FibreSpan(pres[0]["fiber"].length_m, dz=pres[0]["grid"].dz_m, dbeta=float(copier_delta_beta) / scale,
+                       gamma=float(cg) / scale, alpha=float(ca) / scale)
+    return [copier, psa], [T], a_in
+
+
+def _phase_scan_result(ph, dbp, gain_db, res, **gains) -> dict:
+    """The scans' returned dict: the axes, ``gains`` as (K,) or (K, M), the extremes of the finite ``gain_db`` and their
+    distance, the chain's result."""
+    finite = np.isfinite(gain_db)
+    gmax = float(np.max(gain_db[finite])) if finite.any() else float("nan")
+    gmin = float(np.min(gain_db[finite])) if finite.any() else float("nan")
+    return dict(phase=ph, psa_delta_beta=dbp, **{k: np.asarray(g).reshape((ph.size,) + dbp.shape) for k, g in gains.items()},
+                gain_max_db=gmax, gain_min_db=gmin, extinction_db=gmax - gmin, result=res)
+
+
 def scan_copier_psa_phase(*, psa_cfg: SimulationConfig, psa_delta_beta, gamma: float, alpha: float, p_in: Sequence[float],
                           phase_in: Optional[Sequence[float]] = None, copier_cfg: Optional[SimulationConfig] = None,
                           copier_delta_beta: float = 0.0, copier_gamma: Optional[float] = None,
@@ -790,14 +838,9 @@ def scan_copier_psa_phase(*, psa_cfg: SimulationConfig, psa_delta_beta, gamma: f
     NaN rules (a point that went non-finite is NaN, scan_mismtach.py:391-392).  Returns dict(phase, psa_delta_beta, gain,
     gain_max_db, gain_min_db, extinction_db (max - min over the finite gains, dB), result=ChainResult)."""
     from .simulation import mid_stage
-    from .sweep import FibreSpan, rk4_chain
+    from .sweep import rk4_chain
     unit = check_gain(gain_mode, gain_unit)
-    ph = np.linspace(0.0, 2.0 * np.pi, 32, endpoint=False) if phase is None else np.asarray(phase, dtype=float)
-    if ph.ndim != 1 or ph.size == 0 or not np.all(np.isfinite(ph)):
-        raise ValueError("phase must be a non-empty 1D sequence of finite values")
-    dbp = np.asarray(psa_delta_beta, dtype=float)
-    if dbp.ndim > 1 or dbp.size == 0 or not np.all(np.isfinite(dbp)):
-        raise ValueError("psa_delta_beta must be a finite scalar or a non-empty 1D sequence")
+    ph, dbp = _phase_scan_axes(phase, psa_delta_beta)
     if phase_wave == "pumps":
         mask = np.array([1.0, 1.0, 0.0, 0.0])
     elif isinstance(phase_wave, (int, np.integer)) and 0 <= int(phase_wave) < 4:
@@ -805,40 +848,16 @@ def scan_copier_psa_phase(*, psa_cfg: SimulationConfig, psa_delta_beta, gamma: f
     else:
         raise ValueError("phase_wave must be 'pumps' or a wave index 0..3")
     _, p0, ph0 = _check_sweep_inputs([1.0], p_in, phase_in)
-    provided = PhaseMatchingConfig(method=PhaseMatchingMethod.PROVIDED, provided_delta_beta=0.0)
-    cfgs = [psa_cfg] if copier_cfg is None else [copier_cfg, psa_cfg]
-    pres = [_prepare(c, gamma=0.0, alpha=0.0, dispersion=None, phase_matching_cfg=provided, beta_legacy=None,
-                     length_unit=length_unit) for c in cfgs]
-    if any(int(c.save_every) != int(psa_cfg.save_every) or bool(c.check_nan) != bool(psa_cfg.check_nan) for c in cfgs):
-        raise ValueError("copier_cfg and psa_cfg must share save_every and check_nan")
-    scale = pres[0]["scale"]
-    K, M = ph.size, max(dbp.size, 1)
-    db_pts = np.tile(np.atleast_1d(dbp), K) / scale                              # point k * M + m
-    T = mid_stage(np.broadcast_to(np.asarray(mid_gain_db, dtype=float), (4,)),
-                  np.asarray(mid_phase, dtype=float)[None, :] + ph[:, None] * mask[None, :])   # (K, 4)
-    T = np.repeat(T, M, axis=0)                                                  # (K * M, 4)
-    a_in = make_initial_amplitudes(p0, ph0)
-    psa = FibreSpan(pres[-1]["fiber"].length_m, dz=pres[-1]["grid"].dz_m, dbeta=db_pts, gamma=float(gamma) / scale,
-                    alpha=float(alpha) / scale)
-    if copier_cfg is None:
-        spans, transfers, a0 = [psa], None, T * a_in[None, :]
-    else:
-        cg = gamma if copier_gamma is None else copier_gamma
-        ca = alpha if copier_alpha is None else copier_alpha
-        copier = FibreSpan(pres[0]["fiber"].length_m, dz=pres[0]["grid"].dz_m, dbeta=float(copier_delta_beta) / scale,
-                           gamma=float(cg) / scale, alpha=float(ca) / scale)
-        spans, transfers, a0 = [copier, psa], [T], a_in
+    spans, transfers, a0 = _copier_psa_chain(
+        ph, dbp, mask, lambda scanned: mid_stage(np.broadcast_to(np.asarray(mid_gain_db, dtype=float), (4,)),
+                                                 np.asarray(mid_phase, dtype=float)[None, :] + scanned),
+        make_initial_amplitudes(p0, ph0), psa_cfg=psa_cfg, copier_cfg=copier_cfg, gamma=gamma, alpha=alpha,
+        copier_delta_beta=copier_delta_beta, copier_gamma=copier_gamma, copier_alpha=copier_alpha, length_unit=length_unit)
     dev = 0 if device is None else int(device)
     res = rk4_chain(spans, a0=a0, transfers=transfers, save_every=int(psa_cfg.save_every),
                     check_nan=bool(psa_cfg.check_nan), dtype=dtype, device=dev, devices=devices)
     gain_db = res.gain(p0[2], mode=gain_mode, unit="dB", device=(dev if not devices else int(devices[0])))
-    gain = gain_db if unit == "db" else 10.0 ** (gain_db / 10.0)
-    finite = np.isfinite(gain_db)
-    gmax = float(np.max(gain_db[finite])) if finite.any() else float("nan")
-    gmin = float(np.min(gain_db[finite])) if finite.any() else float("nan")
-    shape = (K, M) if dbp.ndim == 1 else (K,)
-    return dict(phase=ph, psa_delta_beta=dbp, gain=np.asarray(gain).reshape(shape), gain_max_db=gmax, gain_min_db=gmin,
-                extinction_db=gmax - gmin, result=res)
+    return _phase_scan_result(ph, dbp, gain_db, res, gain=gain_db if unit == "db" else 10.0 ** (gain_db / 10.0))
 
 
 def scan_single_pump_copier_psa_phase(*, psa_cfg: SimulationConfig, psa_delta_beta, gamma: float, alpha: float,
@@ -866,14 +885,9 @@ def scan_single_pump_copier_psa_phase(*, psa_cfg: SimulationConfig, psa_delta_be
     gain_idler, gain_max_db, gain_min_db, extinction_db (max - min over the signal's finite gains, dB),
     result=SinglePumpChainResult)."""
     from .simulation import single_pump_mid_stage
-    from .sweep import FibreSpan, initial_amplitudes, rk4_chain_single_pump
+    from .sweep import initial_amplitudes, rk4_chain_single_pump
     unit = check_gain(gain_mode, gain_unit)
-    ph = np.linspace(0.0, 2.0 * np.pi, 32, endpoint=False) if phase is None else np.asarray(phase, dtype=float)
-    if ph.ndim != 1 or ph.size == 0 or not np.all(np.isfinite(ph)):
-        raise ValueError("phase must be a non-empty 1D sequence of finite values")
-    dbp = np.asarray(psa_delta_beta, dtype=float)
-    if dbp.ndim > 1 or dbp.size == 0 or not np.all(np.isfinite(dbp)):
-        raise ValueError("psa_delta_beta must be a finite scalar or a non-empty 1D sequence")
+    ph, dbp = _phase_scan_axes(phase, psa_delta_beta)
     if isinstance(phase_wave, str) and phase_wave == "pump":
         mask = np.eye(3)[0]
     elif isinstance(phase_wave, (int, np.integer)) and not isinstance(phase_wave, bool) and 0 <= int(phase_wave) < 3:
@@ -888,38 +902,15 @@ def scan_single_pump_copier_psa_phase(*, psa_cfg: SimulationConfig, psa_delta_be
     ph0 = None if phase_in is None else np.asarray(list(phase_in), dtype=float)
     if ph0 is not None and (ph0.shape != (3,) or not np.all(np.isfinite(ph0))):
         raise ValueError("phase_in must hold 3 finite phases")
-    provided = PhaseMatchingConfig(method=PhaseMatchingMethod.PROVIDED, provided_delta_beta=0.0)
-    cfgs = [psa_cfg] if copier_cfg is None else [copier_cfg, psa_cfg]
-    pres = [_prepare(c, gamma=0.0, alpha=0.0, dispersion=None, phase_matching_cfg=provided, beta_legacy=None,
-                     length_unit=length_unit) for c in cfgs]
-    if any(int(c.save_every) != int(psa_cfg.save_every) or bool(c.check_nan) != bool(psa_cfg.check_nan) for c in cfgs):
-        raise ValueError("copier_cfg and psa_cfg must share save_every and check_nan")
-    scale = pres[0]["scale"]
-    K, M = ph.size, max(dbp.size, 1)
-    db_pts = np.tile(np.atleast_1d(dbp), K) / scale                              # point k * M + m
-    T = single_pump_mid_stage(np.broadcast_to(np.asarray(mid_gain_db, dtype=float), (3,)),
-                              np.broadcast_to(np.asarray(mid_phase, dtype=float), (3,))[None, :]
-                              + ph[:, None] * mask[None, :])                     # (K, 3)
-    T = np.repeat(T, M, axis=0)                                                  # (K * M, 3)
-    a_in = initial_amplitudes(p0, ph0)
-    psa = FibreSpan(pres[-1]["fiber"].length_m, dz=pres[-1]["grid"].dz_m, dbeta=db_pts, gamma=float(gamma) / scale,
-                    alpha=float(alpha) / scale)
-    if copier_cfg is None:
-        spans, transfers, a0 = [psa], None, T * a_in[None, :]
-    else:
-        cg = gamma if copier_gamma is None else copier_gamma
-        ca = alpha if copier_alpha is None else copier_alpha
-        copier = FibreSpan(pres[0]["fiber"].length_m, dz=pres[0]["grid"].dz_m, dbeta=float(copier_delta_beta) / scale,
-                           gamma=float(cg) / scale, alpha=float(ca) / scale)
-        spans, transfers, a0 = [copier, psa], [T], a_in
+    spans, transfers, a0 = _copier_psa_chain(
+        ph, dbp, mask, lambda scanned: single_pump_mid_stage(np.broadcast_to(np.asarray(mid_gain_db, dtype=float), (3,)),
+                                                             np.broadcast_to(np.asarray(mid_phase, dtype=float), (3,))[None, :]
+                                                             + scanned),
+        initial_amplitudes(p0, ph0), psa_cfg=psa_cfg, copier_cfg=copier_cfg, gamma=gamma, alpha=alpha,
+        copier_delta_beta=copier_delta_beta, copier_gamma=copier_gamma, copier_alpha=copier_alpha, length_unit=length_unit)
     res = rk4_chain_single_pump(spans, a0=a0, transfers=transfers, save_every=int(psa_cfg.save_every),
                                 check_nan=bool(psa_cfg.check_nan), device=(0 if device is None else int(device)),
                                 devices=devices)
-    gain_db = res.signal_gain(p0[1], mode=gain_mode, unit="dB")
-    finite = np.isfinite(gain_db)
-    gmax = float(np.max(gain_db[finite])) if finite.any() else float("nan")
-    gmin = float(np.min(gain_db[finite])) if finite.any() else float("nan")
-    shape = (K, M) if dbp.ndim == 1 else (K,)
-    return dict(phase=ph, psa_delta_beta=dbp, gain=res.signal_gain(p0[1], mode=gain_mode, unit=unit).reshape(shape),
-                gain_idler=res.idler_conversion(p0[1], mode=gain_mode, unit=unit).reshape(shape), gain_max_db=gmax,
-                gain_min_db=gmin, extinction_db=gmax - gmin, result=res)
+    return _phase_scan_result(ph, dbp, res.signal_gain(p0[1], mode=gain_mode, unit="dB"), res,
+                              gain=res.signal_gain(p0[1], mode=gain_mode, unit=unit),
+                              gain_idler=res.idler_conversion(p0[1], mode=gain_mode, unit=unit))

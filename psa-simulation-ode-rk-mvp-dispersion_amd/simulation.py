@@ -237,15 +237,38 @@ def run_single_pump_simulation(cfg: SimulationConfig, *, gamma: float, alpha: fl
 
 
 # ---- concatenated spans (copier - mid-stage - PSA chains) ------------------------------------------------------------
+def _mid_stage(name: str, widths, gain_db, phase) -> np.ndarray:
+    g, ph = np.broadcast_arrays(np.asarray(gain_db, dtype=float), np.asarray(phase, dtype=float))
+    if g.ndim == 0 or g.shape[-1] not in widths:
+        raise ValueError(f"{name}: gain_db / phase need one entry per wave ({' or '.join(map(str, widths))})")
+    if not (np.all(np.isfinite(g)) and np.all(np.isfinite(ph))):
+        raise ValueError(f"{name}: gain_db and phase must be finite")
+    return np.sqrt(10.0 ** (g / 10.0)) * np.exp(1j * ph)
+
+
 def mid_stage(gain_db=(0.0, 0.0, 0.0, 0.0), phase=(0.0, 0.0, 0.0, 0.0)) -> np.ndarray:
     """Per-wave transfer of a mid-stage (pump recovery, attenuator, phase shifter): sqrt(10^(gain_db/10)) e^{i phase}.
     The last axis is the wave (4 or 6); leading axes (one row per sweep point) broadcast."""
-    g, ph = np.broadcast_arrays(np.asarray(gain_db, dtype=float), np.asarray(phase, dtype=float))
-    if g.ndim == 0 or g.shape[-1] not in (4, 6):
-        raise ValueError("mid_stage: gain_db / phase need one entry per wave (4 or 6)")
-    if not (np.all(np.isfinite(g)) and np.all(np.isfinite(ph))):
-        raise ValueError("mid_stage: gain_db and phase must be finite")
-    return np.sqrt(10.0 ** (g / 10.0)) * np.exp(1j * ph)
+    return _mid_stage("mid_stage", (4, 6), gain_db, phase)
+
+
+def _run_spans(chain, fibre, cfgs, A0, transfers, length_unit, return_length_unit):
+    """The end of both run_concatenated_* functions: the rules the spans' configs and the transfers share, the chain call
+    (``chain``: rk4_chain or rk4_chain_single_pump, on A0's waves), the failure and the unit of z_out."""
+    save_every, check_nan = int(cfgs[0].save_every), bool(cfgs[0].check_nan)
+    if any(int(c.save_every) != save_every or bool(c.check_nan) != check_nan for c in cfgs):
+        raise ValueError("all spans must share save_every and check_nan")
+    if transfers is not None:
+        transfers = [np.asarray(t, dtype=np.complex128) for t in transfers]
+        if len(transfers) != len(fibre) - 1 or any(t.shape != A0.shape for t in transfers):
+            raise ValueError(f"transfers must be {len(fibre) - 1} per-wave factors of shape ({A0.shape[0]},)")
+    r = chain(fibre, a0=A0, transfers=transfers, save_every=save_every, check_nan=check_nan, exact_step=True, want_traj=True)
+    bad = int(r.first_bad_step[0])
+    if check_nan and bad >= 0:
+        k = int(np.searchsorted(r.step_offsets, bad, side="right")) - 1
+        raise FloatingPointError(f"NaN or Inf detected at step {bad} (span {k}, local step {bad - r.step_offsets[k]})")
+    out_unit = length_unit if return_length_unit is None else return_length_unit
+    return r.z_out / _length_scale_to_m(out_unit), r.traj[0]
 
 
 def run_concatenated_simulation(spans, *, omega: Sequence[float], p_in: Sequence[float],
@@ -283,32 +306,13 @@ def run_concatenated_simulation(spans, *, omega: Sequence[float], p_in: Sequence
         fibre.append(FibreSpan(length=params.fiber.length_m, dz=params.grid.dz_m, dbeta=float(res.delta_beta),
                                gamma=params.fiber.gamma_W_m, alpha=params.fiber.alpha_1_m))
         cfgs.append(cfg)
-    save_every, check_nan = int(cfgs[0].save_every), bool(cfgs[0].check_nan)
-    if any(int(c.save_every) != save_every or bool(c.check_nan) != check_nan for c in cfgs):
-        raise ValueError("all spans must share save_every and check_nan")
-    if transfers is not None:
-        transfers = [np.asarray(t, dtype=np.complex128) for t in transfers]
-        if len(transfers) != len(spans) - 1 or any(t.shape != (4,) for t in transfers):
-            raise ValueError(f"transfers must be {len(spans) - 1} per-wave factors of shape (4,)")
-    r = rk4_chain(fibre, a0=A0, transfers=transfers, save_every=save_every, check_nan=check_nan, exact_step=True,
-                  want_traj=True)
-    bad = int(r.first_bad_step[0])
-    if check_nan and bad >= 0:
-        k = int(np.searchsorted(r.step_offsets, bad, side="right")) - 1
-        raise FloatingPointError(f"NaN or Inf detected at step {bad} (span {k}, local step {bad - r.step_offsets[k]})")
-    out_unit = length_unit if return_length_unit is None else return_length_unit
-    return r.z_out / _length_scale_to_m(out_unit), r.traj[0]
+    return _run_spans(rk4_chain, fibre, cfgs, A0, transfers, length_unit, return_length_unit)
 
 
 def single_pump_mid_stage(gain_db=(0.0, 0.0, 0.0), phase=(0.0, 0.0, 0.0)) -> np.ndarray:
     """mid_stage for the single-pump model's three waves [p, s, i]: sqrt(10^(gain_db/10)) e^{i phase}.  The last axis is the
     wave (3 entries); leading axes (one row per sweep point) broadcast."""
-    g, ph = np.broadcast_arrays(np.asarray(gain_db, dtype=float), np.asarray(phase, dtype=float))
-    if g.ndim == 0 or g.shape[-1] != 3:
-        raise ValueError("single_pump_mid_stage: gain_db / phase need one entry per wave (3)")
-    if not (np.all(np.isfinite(g)) and np.all(np.isfinite(ph))):
-        raise ValueError("single_pump_mid_stage: gain_db and phase must be finite")
-    return np.sqrt(10.0 ** (g / 10.0)) * np.exp(1j * ph)
+    return _mid_stage("single_pump_mid_stage", (3,), gain_db, phase)
 
 
 def run_concatenated_single_pump_simulation(spans, *, omega_pump: float, omega_signal: float, p_in: Sequence[float],
@@ -361,21 +365,7 @@ def run_concatenated_single_pump_simulation(spans, *, omega_pump: float, omega_s
             raise ValueError(f"span {k}: the phase mismatch is not finite")
         fibre.append(FibreSpan(length=fiber.length_m, dz=grid.dz_m, dbeta=dbeta, gamma=fiber.gamma_W_m, alpha=fiber.alpha_1_m))
         cfgs.append(sp["cfg"])
-    save_every, check_nan = int(cfgs[0].save_every), bool(cfgs[0].check_nan)
-    if any(int(c.save_every) != save_every or bool(c.check_nan) != check_nan for c in cfgs):
-        raise ValueError("all spans must share save_every and check_nan")
-    if transfers is not None:
-        transfers = [np.asarray(t, dtype=np.complex128) for t in transfers]
-        if len(transfers) != len(spans) - 1 or any(t.shape != (3,) for t in transfers):
-            raise ValueError(f"transfers must be {len(spans) - 1} per-wave factors of shape (3,)")
-    r = rk4_chain_single_pump(fibre, a0=A0, transfers=transfers, save_every=save_every, check_nan=check_nan,
-                              exact_step=True, want_traj=True)
-    bad = int(r.first_bad_step[0])
-    if check_nan and bad >= 0:
-        k = int(np.searchsorted(r.step_offsets, bad, side="right")) - 1
-        raise FloatingPointError(f"NaN or Inf detected at step {bad} (span {k}, local step {bad - r.step_offsets[k]})")
-    out_unit = length_unit if return_length_unit is None else return_length_unit
-    return r.z_out / _length_scale_to_m(out_unit), r.traj[0]
+    return _run_spans(rk4_chain_single_pump, fibre, cfgs, A0, transfers, length_unit, return_length_unit)
 
 
 # ---- the reference's two ready-made scenarios (simulation.py:371-447), km-unit path -----------------------

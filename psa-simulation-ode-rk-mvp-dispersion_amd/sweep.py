@@ -323,12 +323,17 @@ class FibreSpan:
 
 
 @dataclass
-class ChainResult(SweepResult):
-    """SweepResult of a chain: rows of every span in order (each span's z = 0 row is the post-transfer state), amplitudes
-    in the physical frame, first_bad_step counted over the whole chain.  n_steps is the chain's total."""
+class _ChainGrid:
+    """The grid of a chain's result, after the fields of the family's own result."""
     z_out: Optional[np.ndarray] = None         # (n_saved_total,) absolute z of every saved row (repeats at a boundary)
     row_offsets: Optional[np.ndarray] = None   # (S + 1,) span s owns rows [row_offsets[s], row_offsets[s + 1])
     step_offsets: Optional[np.ndarray] = None  # (S + 1,) span s owns steps [step_offsets[s], step_offsets[s + 1])
+
+
+@dataclass
+class ChainResult(_ChainGrid, SweepResult):
+    """SweepResult of a chain: rows of every span in order (each span's z = 0 row is the post-transfer state), amplitudes
+    in the physical frame, first_bad_step counted over the whole chain.  n_steps is the chain's total."""
 
 
 def _span_column(values, S: int, N: int, name: str, dtype) -> np.ndarray:
@@ -397,14 +402,23 @@ def _chain_inputs(spans, a0, transfers, save_every, widths, dtype):
     return spans, save_every, dtype, N, nw, dbeta, dbeta2, gamma, alpha, tr, steps, lens
 
 
-def _chain_grid(steps, lens, save_every):
-    """-> (row_offsets (S + 1,), step_offsets (S + 1,), z_out (n_saved_total,)) of a chain's saved rows."""
+def _run_chain(host_name: str, widths, spans, a0, transfers, save_every, dtype, a0_dtype, device, devices, **options):
+    """What every chain driver does: the shared input rules, the family's host call (looked up in _native when called) over
+    the devices, and the grid of the saved rows -> (outputs, save_every, a0 as passed on, the _ChainGrid fields)."""
+    spans, save_every, dtype, N, nw, dbeta, dbeta2, gamma, alpha, tr, steps, lens = _chain_inputs(spans, a0, transfers,
+                                                                                                  save_every, widths, dtype)
+    a0 = np.asarray(a0, dtype=a0_dtype)
+    kw = dict(dbeta=dbeta, n_steps=steps, seg_len=lens, save_every=save_every, gamma=gamma, alpha=alpha, a0=a0,
+              transfers=tr, **options)
+    if 6 in widths:
+        kw.update(dbeta2=dbeta2, dtype=dtype)
+    r = _run(getattr(_native, host_name), CHAIN_AXES, N, kw, device, devices)
     rows = steps // save_every + 1
-    row_off = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
-    step_off = np.concatenate([[0], np.cumsum(steps)]).astype(np.int64)
     z0 = np.concatenate([[0.0], np.cumsum(lens)])
     z_out = np.concatenate([z0[k] + np.linspace(0.0, lens[k], int(steps[k]) + 1)[::save_every] for k in range(len(steps))])
-    return row_off, step_off, z_out
+    grid = dict(z_out=z_out, row_offsets=np.concatenate([[0], np.cumsum(rows)]).astype(np.int64),
+                step_offsets=np.concatenate([[0], np.cumsum(steps)]).astype(np.int64))
+    return r, save_every, a0, grid
 
 
 def rk4_chain(spans: Sequence[FibreSpan], *, a0, transfers=None, save_every: int = 10, check_nan: bool = True,
@@ -415,25 +429,17 @@ def rk4_chain(spans: Sequence[FibreSpan], *, a0, transfers=None, save_every: int
 
     transfers: None (identity), or S-1 entries, each (n_waves,) complex for every point or (N, n_waves) per point
     (see simulation.mid_stage).  Every span's n_steps must be a multiple of ``save_every``."""
-    spans, save_every, dtype, N, _, dbeta, dbeta2, gamma, alpha, tr, steps, lens = _chain_inputs(spans, a0, transfers,
-                                                                                                 save_every, (4, 6), dtype)
-    kw = dict(dbeta=dbeta, n_steps=steps, seg_len=lens, save_every=save_every, gamma=gamma, alpha=alpha, a0=np.asarray(a0),
-              transfers=tr, dbeta2=dbeta2, check_nan=check_nan, exact_step=exact_step, want_traj=want_traj,
-              dtype=dtype, wave_summary=wave_summary)
-    r = _run(_native.chain_host, CHAIN_AXES, N, kw, device, devices)
-    row_off, step_off, z_out = _chain_grid(steps, lens, save_every)
-    return ChainResult(r["a_end"], r["p_end"], r["p_max"], r["first_bad_step"], int(step_off[-1]), save_every,
-                       r["elapsed_ms"], r.get("traj"), r.get("p_wave_end"), r.get("p_wave_max"), z_out=z_out,
-                       row_offsets=row_off, step_offsets=step_off)
+    r, save_every, _, grid = _run_chain("chain_host", (4, 6), spans, a0, transfers, save_every, dtype, None, device, devices,
+                                        check_nan=check_nan, exact_step=exact_step, want_traj=want_traj,
+                                        wave_summary=wave_summary)
+    return ChainResult(r["a_end"], r["p_end"], r["p_max"], r["first_bad_step"], int(grid["step_offsets"][-1]), save_every,
+                       r["elapsed_ms"], r.get("traj"), r.get("p_wave_end"), r.get("p_wave_max"), **grid)
 
 
 @dataclass
-class SinglePumpChainResult(SinglePumpResult):
+class SinglePumpChainResult(_ChainGrid, SinglePumpResult):
     """SinglePumpResult of a chain: rows of every span in order (each span's z = 0 row is the post-transfer state),
     amplitudes in the physical frame, first_bad_step counted over the whole chain.  n_steps is the chain's total."""
-    z_out: Optional[np.ndarray] = None         # (n_saved_total,) absolute z of every saved row (repeats at a boundary)
-    row_offsets: Optional[np.ndarray] = None   # (S + 1,) span s owns rows [row_offsets[s], row_offsets[s + 1])
-    step_offsets: Optional[np.ndarray] = None  # (S + 1,) span s owns steps [step_offsets[s], step_offsets[s + 1])
 
 
 def rk4_chain_single_pump(spans: Sequence[FibreSpan], *, a0, transfers=None, save_every: int = 10, check_nan: bool = True,
@@ -448,17 +454,12 @@ def rk4_chain_single_pump(spans: Sequence[FibreSpan], *, a0, transfers=None, sav
     a0 (3,) or (N, 3) complex; transfers: None (identity), or S-1 entries, each (3,) complex for every point or (N, 3) per
     point (see simulation.single_pump_mid_stage).  Every span's n_steps must be a multiple of ``save_every``; a span with
     dbeta2 is an error.  float64 only."""
-    spans, save_every, _, N, _, dbeta, _, gamma, alpha, tr, steps, lens = _chain_inputs(spans, a0, transfers, save_every,
-                                                                                        (3,), np.float64)
-    a0 = np.asarray(a0, dtype=np.complex128)
-    kw = dict(dbeta=dbeta, n_steps=steps, seg_len=lens, save_every=save_every, gamma=gamma, alpha=alpha, a0=a0,
-              transfers=tr, check_nan=check_nan, exact_step=exact_step, want_traj=want_traj)
-    r = _run(_native.single_pump_chain_host, CHAIN_AXES, N, kw, device, devices)
-    row_off, step_off, z_out = _chain_grid(steps, lens, save_every)
-    p_in = np.abs(np.atleast_2d(a0)) ** 2
-    return SinglePumpChainResult(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"], int(step_off[-1]),
-                                 save_every, r["elapsed_ms"], p_in, r.get("traj"), z_out=z_out, row_offsets=row_off,
-                                 step_offsets=step_off)
+    r, save_every, a0, grid = _run_chain("single_pump_chain_host", (3,), spans, a0, transfers, save_every, np.float64,
+                                         np.complex128, device, devices, check_nan=check_nan, exact_step=exact_step,
+                                         want_traj=want_traj)
+    return SinglePumpChainResult(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"],
+                                 int(grid["step_offsets"][-1]), save_every, r["elapsed_ms"], np.abs(np.atleast_2d(a0)) ** 2,
+                                 r.get("traj"), **grid)
 
 
 # ---- adaptive (RK45) sweeps ----------------------------------------------------------------------------------------

@@ -41,6 +41,9 @@ RK45 = dict(n_waves=4, n_points=8, z_max=1.0, rtol=1e-8, atol=1e-12, h_max=INF, 
 PAIRS = dict(n_pairs=3, n_points=8, n_steps=10, z_max=1.0, save_every=1, dbeta=P, gamma=P, alpha=P, a0=P, flags=0, a_end=P,
              p_wave_end=P, p_wave_max=P, first_bad=P)
 WAVES = dict(p_wave_end=P, p_wave_max=P)
+SP_CHAIN = dict(n_points=8, n_segments=2, n_steps=_STEPS, seg_len=_LENS, save_every=5, dbeta=P, gamma=P, alpha=P, a0=P,
+                transfer=None, flags=0, a_end=P, p_wave_end=P, p_wave_max=P, first_bad=P, traj=None)
+BCAST_ALL, CHECKS, LOSSLESS = 0b1111, 3 << 8, 1 << 14
 
 
 def _entry(base, *, dev, tail=None, dev_tail=None):
@@ -118,6 +121,34 @@ def _chain_cases(f32, dev):
     return c
 
 
+def _single_pump_chain_cases(dev):
+    """The calls of tests/test_single_pump_chain_host.py (every argument error, the flags and the workspace of the two forms)."""
+    arr = lambda a, dt: np.array(a, dt)  # noqa: E731
+    steps, lens = (lambda *a: dict(n_steps=arr(a, np.int64))), (lambda *a: dict(seg_len=arr(a, float)))
+    null = dict(dbeta=None) if dev else dict(p_wave_max=None)
+    ok = BCAST_ALL | CHECKS | LOSSLESS | BLOCK64
+    c = {"n_segments_zero": dict(n_segments=0), "n_segments_negative": dict(n_segments=-1), "null_n_steps": dict(n_steps=None),
+         "null_seg_len": dict(seg_len=None), "n_points_negative": dict(n_points=-1), "n_points_launch_limit": dict(n_points=MAX_POINTS + 1),
+         "first_span_n_steps_zero": steps(0, 20), "second_span_n_steps_zero": steps(10, 0), "second_span_n_steps_2^31": steps(10, 5 * 2**29),
+         "save_every_zero": dict(save_every=0), "second_span_not_a_multiple": steps(10, 21), "first_span_not_a_multiple": steps(11, 20),
+         "null_buffer": null, "two:n_segments_zero+n_points_negative": dict(n_segments=0, n_points=-1),
+         "two:n_points_negative+flag+null": dict(n_points=-1, flags=ONE_LANE, **null), "two:flag+null": dict(flags=ONE_LANE, **null),
+         "two:null+not_a_multiple": dict(null, **steps(10, 21)), "traj_launch_limit": dict(n_points=2**28, traj=P),
+         "no_traj_at_the_limit": dict(null, n_points=2**28), "traj_below_the_limit": dict(null, n_points=2**28 - 1, traj=P),
+         "every_accepted_flag": dict(null, flags=ok | (TRAJ_LD if dev else 0)),
+         "empty": dict(n_points=0)}
+    for name, bad in (("zero", 0.0), ("negative", -1.0), ("inf", INF), ("nan", NAN)):
+        c[f"first_span_seg_len_{name}"], c[f"second_span_seg_len_{name}"] = lens(bad, 2.0), lens(1.0, bad)
+    for name, bit in (("one_lane", ONE_LANE), ("split", SPLIT), ("quad", QUAD), ("f32_scalar", F32_SCALAR), ("f32_packed", F32_PACKED),
+                      ("lds", LDS), ("bit19", 1 << 19), ("bit30", 1 << 30)):
+        c[f"flag_{name}"] = dict(flags=bit | CHECK_NAN)
+    if dev:   # rejected after validation and before the first launch
+        c.update({"two_spans_without_workspace": dict(d_workspace=None), "empty_without_workspace": dict(n_points=0, d_workspace=None)})
+    else:     # the padded leading dimension belongs to the device form
+        c.update({"host_traj_ld": dict(flags=TRAJ_LD), "host_traj_ld_with_traj": dict(flags=TRAJ_LD, traj=P)})
+    return c
+
+
 def _rk45_cases():
     c = _common(grid=False)
     c.update(_nulls(["status", "z_end", "n_accepted", "n_rejected"]))
@@ -161,6 +192,8 @@ def cases() -> dict:
         sfx = "_dev" if dev else ""
         out[f"psa_rk45_sweep_f64{sfx}"] = (_entry(RK45, dev=dev), _rk45_cases())
         out[f"psa_rk4_sweep_pairs_f64{sfx}"] = (_entry(PAIRS, dev=dev), _pairs_cases())
+        out[f"psa_rk4_single_pump_chain_f64{sfx}"] = (_entry(SP_CHAIN, dev=dev, dev_tail=dict(d_workspace=P)),
+                                                      _single_pump_chain_cases(dev))
     return out
 
 

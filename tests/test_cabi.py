@@ -164,6 +164,24 @@ def test_header_is_valid_c99_and_a_c_program_links_and_gets_the_documented_codes
     assert "abi_client ok" in out.stdout
 
 
+def test_the_chain_argument_client_gets_the_documented_codes(tmp_path):
+    """tests/c/chain_args_client.c (the program tools/chain_host_sanitize.sh runs under the host sanitizers) against the
+    library under test: every chain entry point with invalid arguments and with n_points = 0 -- no GPU needed."""
+    import shutil
+    import subprocess
+    gcc = shutil.which("gcc")
+    if gcc is None:
+        pytest.skip("gcc not available")
+    libdir = os.path.dirname(nat.LIB_PATH)
+    exe = str(tmp_path / "chain_args_client")
+    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", "c", "chain_args_client.c"), "-o", exe, "-L", libdir, "-lpsa_hip",
+                    f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib", "-lm"], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr
+    assert "chain_args_client ok" in out.stdout
+
+
 def test_dbeta_producer_validates_its_model_before_any_launch():
     """psa_dbeta_grid_*_dev / psa_dbeta_pairs_*_dev: bad method / orders / beta count / block -> negative codes, no launch."""
     L = nat.lib()
