@@ -397,7 +397,8 @@ int psa_rk45_sweep_f64_dev(void *stream, int n_waves, int64_t n_points, double z
  * PSA_OPT_LOSSLESS (set by the host form itself for a broadcast alpha == 0) and PSA_OPT_BLOCK64; anything else (a layout,
  * float32 or LDS flag) is PSA_E_FLAGS.  n_pairs outside 1..PSA_MAX_PAIRS: PSA_E_NPAIRS; L * n_points beyond the launch
  * grid (2 * PSA_MAX_POINTS lanes): PSA_E_TOO_LARGE; the other codes as psa_rk4_sweep_f64.  All of it is checked before
- * any device call; n_points == 0 is a successful no-op.  No trajectory rows, chains or adaptive form.
+ * any device call; n_points == 0 is a successful no-op.  Saved rows and chains of spans are psa_rk4_pairs_chain_f64 below
+ * (one span with a trajectory is this sweep's trajectory form); there is no adaptive form.
  */
 int psa_rk4_sweep_pairs_f64(int device, int n_pairs, int64_t n_points, int64_t n_steps, double z_max,
                             int32_t save_every, const double *dbeta, const double *gamma, const double *alpha,
@@ -515,6 +516,63 @@ int psa_rk4_single_pump_chain_f64_dev(void *stream, int64_t n_points, int n_segm
                                       double *d_traj_soa_or_null, void *d_workspace);
 /* bytes of d_workspace for a single-pump chain; -1 for n_points < 0 */
 int64_t psa_rk4_single_pump_chain_workspace_bytes(int64_t n_points);
+
+/* ---- a chain of multi-channel spans with mid-stage transfers (the WDM copier - mid-stage - PSA link) ----------------------
+ * psa_rk4_single_pump_chain_f64 for the multi-channel model above: S = n_segments >= 1 spans of two pumps
+ * and K = n_pairs signal/idler pairs, NW = 2 + 2K, each span ONE launch of the multi-channel kernel, joined on the device by
+ * the chain's epilogue kernel (no host synchronisation between spans).  Span s has
+ *   n_steps[s], seg_len[s]   host arrays [S]; each n_steps[s] in [1, 2^31) and a multiple of save_every (else
+ *                            PSA_E_SAVE_EVERY), each seg_len[s] positive and finite
+ *   dbeta [S][N][K];  gamma, alpha  [S][N], or [S] with PSA_BCAST_GAMMA / PSA_BCAST_ALPHA
+ *   a0_re_im  [N][NW][2] | [1][NW][2] (PSA_BCAST_A0)
+ * and between span s and s+1 the per-wave complex transfer T_s[j] (amplitude gain times e^{i phase}):
+ *   transfer_re_im  [S-1][N][NW][2], or [S-1][NW][2] with PSA_BCAST_TRANSFER; NULL = identity
+ * Gauge.  Pair k's physical FWM factor is e^{+-i Theta_k(z)}, Theta_k = Theta_{s,k} + dbeta_{s,k} zeta, Theta_{s,k} =
+ * sum_{j<s} dbeta_{j,k} L_j.  With B_sk = A_sk e^{+i Theta_{s,k}} for the signal of every pair (wave 2 + 2k) and B = A for the
+ * pumps and the idlers, every equation holds in B with the plain factor e^{+-i dbeta_{s,k} zeta}: in the pumps' sum over the
+ * pairs each pair's phase cancels in its own term, and the Kerr terms are phase-blind.  The kernel runs each span unchanged,
+ * a boundary is B' = T_s B with signal k also multiplied by e^{+i dbeta_{s,k} L_s}, and reported amplitudes and rows are
+ * rotated back by e^{-i Theta_{s,k}} on wave 2 + 2k.  Theta is kept per point and pair in float64.
+ * Outputs, all in the physical (A) frame:
+ *   a_end_re_im [N][NW][2], p_wave_end [N][NW]   the last saved row of the last span
+ *   p_wave_max  [N][NW]   max over every saved row of every span (each span's z = 0 row is the post-transfer state),
+ *                         NaN-propagating
+ *   first_bad_step [N]    cumulative step index (the earlier spans' n_steps + the local index); the first failure wins
+ *   traj_or_null  [N][rows_total][NW][2], rows_total = sum_s (n_steps[s]/save_every + 1); the host form pads the device
+ *                 buffer itself and brings it home in the sweep's chunks
+ * S == 1 without a trajectory is psa_rk4_sweep_pairs_f64(_dev) itself, bit for bit: no workspace, no epilogue; S == 1 with
+ * one is that sweep's trajectory form, its summaries the same bits.
+ * One deliberate difference from psa_rk4_single_pump_chain_f64: a chain of ONE span keeps the sweep's rule for save_every,
+ * not the chain's.  n_steps[0] need not be a multiple of save_every; a_end is the last saved row and the trajectory has
+ * n_steps[0] / save_every + 1 rows, as for psa_rk4_sweep_pairs_f64.  With S > 1 every span's n_steps must be a multiple.
+ * The host form sets PSA_OPT_LOSSLESS per span: for a broadcast alpha of 0, or (S > 1) a per-point row that is 0 everywhere.
+ * flags: the four PSA_BCAST_* bits, PSA_OPT_CHECK_NAN, PSA_OPT_EXACT_STEP, PSA_OPT_LOSSLESS, PSA_OPT_BLOCK64 (rows are
+ * written by 256-thread workgroups whatever it says) and, on the `_dev` form only, PSA_OPT_TRAJ_LD; anything else is
+ * PSA_E_FLAGS.  Every rule is checked before any device call, in the order n_segments < 1 (PSA_E_NSTEPS), n_steps / seg_len
+ * NULL, the multi-channel rules on the first span's grid (n_pairs: PSA_E_NPAIRS; n_points and the launch grid, n_steps,
+ * seg_len, save_every, flags, pointers, a trajectory's ld * 16 < 2^32 else PSA_E_TOO_LARGE), then every span's n_steps,
+ * seg_len and save_every multiple; a trajectory that does not fit the device is PSA_E_TOO_LARGE (host form).
+ * n_points == 0 is a successful no-op.  No new error code.
+ */
+int psa_rk4_pairs_chain_f64(int device, int n_pairs, int64_t n_points, int n_segments, const int64_t *n_steps,
+                            const double *seg_len, int32_t save_every, const double *dbeta, const double *gamma,
+                            const double *alpha, const double *a0_re_im, const double *transfer_re_im, uint32_t flags,
+                            double *a_end_re_im, double *p_wave_end, double *p_wave_max, int64_t *first_bad_step,
+                            double *traj_or_null, double *elapsed_ms_or_null);
+/* On SoA device buffers, asynchronous on `stream`, no allocation and no synchronisation: d_dbeta_soa [S][K][N], d_gamma /
+ * d_alpha [S][N] | [S], d_a0_soa [2*NW][N | 1], d_transfer_soa [S-1][2*NW][N] (or [S-1][2*NW] with PSA_BCAST_TRANSFER),
+ * d_a_end_soa [2*NW][N], d_p_wave_end_soa / d_p_wave_max_soa [NW][N], d_first_bad_step [N], d_traj_soa_or_null
+ * [rows_total][NW][ld][2] with ld = N, or psa_traj_ld(N, 8) with PSA_OPT_TRAJ_LD; n_steps / seg_len stay HOST arrays.
+ * d_workspace: at least psa_rk4_pairs_chain_workspace_bytes(n_pairs, n_points) bytes of device memory; NULL with S > 1 is
+ * PSA_E_NULLPTR, S == 1 needs none.  `_dev` callers pass PSA_OPT_LOSSLESS for the whole chain. */
+int psa_rk4_pairs_chain_f64_dev(void *stream, int n_pairs, int64_t n_points, int n_segments, const int64_t *n_steps,
+                                const double *seg_len, int32_t save_every, const double *d_dbeta_soa,
+                                const double *d_gamma, const double *d_alpha, const double *d_a0_soa,
+                                const double *d_transfer_soa, uint32_t flags, double *d_a_end_soa,
+                                double *d_p_wave_end_soa, double *d_p_wave_max_soa, int64_t *d_first_bad_step,
+                                double *d_traj_soa_or_null, void *d_workspace);
+/* bytes of d_workspace for a multi-channel chain; -1 for n_pairs outside 1..PSA_MAX_PAIRS or n_points < 0 */
+int64_t psa_rk4_pairs_chain_workspace_bytes(int n_pairs, int64_t n_points);
 
 #ifdef __cplusplus
 }

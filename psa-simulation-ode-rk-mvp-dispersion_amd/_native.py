@@ -87,6 +87,10 @@ _SIGS = {
     **_family("psa_rk4_single_pump_chain", [_L, _I, _P, _P, _I32] + [_P] * 5 + [_U32] + [_P] * 5, host=[_P], dev=[_P],
               host_types=("f64",), dev_types=("f64",)),
     "psa_rk4_single_pump_chain_workspace_bytes": (_L, [_L]),
+    # n_pairs, then the arguments of psa_rk4_single_pump_chain
+    **_family("psa_rk4_pairs_chain", [_I, _L, _I, _P, _P, _I32] + [_P] * 5 + [_U32] + [_P] * 5, host=[_P], dev=[_P],
+              host_types=("f64",), dev_types=("f64",)),
+    "psa_rk4_pairs_chain_workspace_bytes": (_L, [_I, _L]),
     "psa_yaman_rhs_f64": (_I, [_I, _L] + [_P] * 9),
     # N, p_metric, first_bad, p0_sig, gain_db, gain, best_index, best_gain, n_finite; dev: workspace
     **_family("psa_gain_summary", _GAIN, dev=[_P], host_types=("f64",), dev_types=("f64",)),
@@ -423,14 +427,19 @@ def single_pump_device(*, stream: int, n_points: int, n_steps: int, z_max: float
 
 def _chain_host(stem: str, widths, sweep_family: bool, dbeta, *, n_steps, seg_len, save_every: int, gamma, alpha, a0,
                 transfers, dbeta2, check_nan: bool, exact_step: Optional[bool], want_traj: bool, dtype, device: int,
-                wave_summary: bool, extra_flags: int) -> dict:
-    """The host-buffer chain of either family: ``<stem>_f64`` / ``_f32`` on a0 of a width in ``widths``.  ``sweep_family``:
-    the 4/6-wave entry points, which take n_waves and dbeta2, have p_end / p_max and put the per-wave summary last."""
+                wave_summary: bool, extra_flags: int, pairs: bool = False) -> dict:
+    """The host-buffer chain of a family: ``<stem>_f64`` / ``_f32`` on a0 of a width in ``widths``.  ``sweep_family``:
+    the 4/6-wave entry points, which take n_waves and dbeta2, have p_end / p_max and put the per-wave summary last.
+    ``pairs``: the multi-channel entry point, whose dbeta is (S, N, K) and which takes K in front; K fixes the width."""
     dtype, cdt, f64 = _dtypes(dtype)
     dbeta = np.ascontiguousarray(np.asarray(dbeta), dtype=dtype)
-    if dbeta.ndim != 2 or dbeta.shape[0] < 1:
+    if pairs:
+        if dbeta.ndim != 3 or dbeta.shape[0] < 1 or not 1 <= dbeta.shape[2] <= MAX_PAIRS:
+            raise ValueError(f"dbeta must have shape (S, N, K) with 1 <= K <= {MAX_PAIRS}, got {dbeta.shape}")
+        widths = (2 + 2 * int(dbeta.shape[2]),)
+    elif dbeta.ndim != 2 or dbeta.shape[0] < 1:
         raise ValueError("dbeta must have shape (S, N)")
-    S, N = (int(x) for x in dbeta.shape)
+    S, N = (int(x) for x in dbeta.shape[:2])
     steps = np.ascontiguousarray(np.asarray(n_steps), dtype=np.int64)
     lens = np.ascontiguousarray(np.asarray(seg_len), dtype=np.float64)
     if steps.shape != (S,) or lens.shape != (S,):
@@ -462,7 +471,7 @@ def _chain_host(stem: str, widths, sweep_family: bool, dbeta, *, n_steps, seg_le
         _check(_fn(stem, f64)(int(device), nw, *grid, _ptr(d2), *point, _ptr(out["p_end"]), _ptr(out["p_max"]), *run,
                               _ptr(w_end), _ptr(w_max)))
         return dict(out, first_bad_step=bad, traj=traj, elapsed_ms=ms.value, p_wave_end=w_end, p_wave_max=w_max)
-    _check(_fn(stem, f64)(int(device), *grid, *point, _ptr(w_end), _ptr(w_max), *run))
+    _check(_fn(stem, f64)(int(device), *((int(dbeta.shape[2]),) if pairs else ()), *grid, *point, _ptr(w_end), _ptr(w_max), *run))
     return dict(out, p_wave_end=w_end, p_wave_max=w_max, first_bad_step=bad, traj=traj, elapsed_ms=ms.value)
 
 
@@ -502,6 +511,36 @@ def single_pump_chain_device(*, stream: int, n_points: int, n_steps, seg_len, sa
         int(save_every), d_dbeta or None, d_gamma or None, d_alpha or None, d_a0_soa or None, d_transfer_soa or None, int(flags),
         d_a_end_soa or None, d_p_wave_end_soa or None, d_p_wave_max_soa or None, d_first_bad or None, d_traj_soa or None,
         d_workspace or None))
+
+
+def pairs_chain_host(dbeta, *, n_steps, seg_len, save_every: int, gamma, alpha, a0, transfers=None, check_nan: bool = True,
+                     exact_step: Optional[bool] = None, want_traj: bool = False, device: int = 0, extra_flags: int = 0) -> dict:
+    """A chain of S multi-channel spans on the GPU (psa_rk4_pairs_chain_f64; host buffers in and out, float64): two pumps
+    and K signal/idler pairs, waves [p1, p2, s_1, i_1, ..., s_K, i_K], NW = 2 + 2K.
+
+    dbeta (S, N, K) with 1 <= K <= 16; n_steps, seg_len (S,); gamma / alpha (S,) broadcast or (S, N); a0 (NW,) or (N, NW)
+    complex; transfers None, (S-1, NW) broadcast or (S-1, N, NW) complex.  One span with want_traj is the multi-channel
+    sweep's trajectory form.  Returns the keys of sweep_pairs_host and traj (N, n_saved_total, NW) or None."""
+    return _chain_host("psa_rk4_pairs_chain", None, False, dbeta, n_steps=n_steps, seg_len=seg_len, save_every=save_every,
+                       gamma=gamma, alpha=alpha, a0=a0, transfers=transfers, dbeta2=None, check_nan=check_nan,
+                       exact_step=exact_step, want_traj=want_traj, dtype=np.float64, device=device, wave_summary=True,
+                       extra_flags=extra_flags, pairs=True)
+
+
+def pairs_chain_workspace_bytes(n_pairs: int, n_points: int) -> int:
+    """Device scratch a multi-channel chain of more than one span needs (psa_rk4_pairs_chain_workspace_bytes)."""
+    return int(lib().psa_rk4_pairs_chain_workspace_bytes(int(n_pairs), int(n_points)))
+
+
+def pairs_chain_device(*, stream: int, n_pairs: int, n_points: int, n_steps, seg_len, save_every: int, d_dbeta_soa: int,
+                       d_gamma: int, d_alpha: int, d_a0_soa: int, d_transfer_soa: int, flags: int, d_a_end_soa: int,
+                       d_p_wave_end_soa: int, d_p_wave_max_soa: int, d_first_bad: int, d_traj_soa: int = 0,
+                       d_workspace: int = 0) -> None:
+    """psa_rk4_pairs_chain_f64_dev on device pointers (ints); n_steps / seg_len are host sequences of length S."""
+    _chain_device("psa_rk4_pairs_chain", True, stream, (int(n_pairs), int(n_points)), n_steps, seg_len, (
+        int(save_every), d_dbeta_soa or None, d_gamma or None, d_alpha or None, d_a0_soa or None, d_transfer_soa or None,
+        int(flags), d_a_end_soa or None, d_p_wave_end_soa or None, d_p_wave_max_soa or None, d_first_bad or None,
+        d_traj_soa or None, d_workspace or None))
 
 
 def chain_host(dbeta, *, n_steps, seg_len, save_every: int, gamma, alpha, a0, transfers=None, dbeta2=None,

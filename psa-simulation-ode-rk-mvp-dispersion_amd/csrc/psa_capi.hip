@@ -71,7 +71,8 @@ struct SweepCall {   // psa_rk4_sweep_*, psa_rk4_sweep_waves_* and one span of a
     T *wave_end = nullptr, *wave_max = nullptr;   // the per-wave summary (on the device SoA [n_waves][N]); launched where set
     bool waves = false;                           // psa_rk4_sweep_waves_*: the summary is required, its rules are checked first
 };
-struct PairsCall {   // psa_rk4_sweep_pairs_f64*
+struct PairsCall {   // psa_rk4_sweep_pairs_f64* and one span of a multi-channel chain
+    using Real = double;
     int n_pairs;
     int64_t n_points, n_steps;
     double z_max;
@@ -80,6 +81,7 @@ struct PairsCall {   // psa_rk4_sweep_pairs_f64*
     uint32_t flags;
     double *a_end, *wave_end, *wave_max;
     int64_t *first_bad;
+    double *traj = nullptr;   // a chain's rows (psa_rk4_pairs_chain_f64*); the sweep's entry points have none
 };
 template <typename T>
 struct SinglePumpCall {   // psa_rk4_single_pump_f64*, psa_rk4_single_pump_f32* and one span of a single-pump chain
@@ -108,7 +110,7 @@ struct Rk45Call {    // psa_rk45_sweep_f64*
     int64_t traj_ld;   // leading dimension of the device rows: n_points (`_dev`), traj_ld_of (the host form's staging)
 };
 template <typename Span>
-struct ChainCall {   // psa_rk4_chain_* (Span = SweepCall<T>) and psa_rk4_single_pump_chain_f64* (Span = SinglePumpCall<double>)
+struct ChainCall {   // psa_rk4_chain_* (Span = SweepCall<T>), psa_rk4_single_pump_chain_f64* (SinglePumpCall<double>), psa_rk4_pairs_chain_f64* (PairsCall)
     Span s;                     // what the spans share; its n_steps and z_max are set span by span from the arrays below
     int n_segments;
     const int64_t *n_steps;     // host [S]
@@ -581,7 +583,8 @@ int sweep_host(int device, const SweepCall<T> &c, double *elapsed_ms) {
 }
 
 // ---- the multi-channel sweep (psa_rk4_sweep_pairs_f64*): two pumps and n_pairs signal/idler pairs -----------------------
-int validate_pairs(const PairsCall &c) {
+// chain: the call is (a span of) psa_rk4_pairs_chain_f64*, which has rows; host_form as in validate_single_pump
+int validate_pairs(const PairsCall &c, bool chain = false, bool host_form = false) {
     if (c.n_pairs < 1 || c.n_pairs > PSA_MAX_PAIRS)
         return fail(PSA_E_NPAIRS, "n_pairs must be in [1, %d], got %d", PSA_MAX_PAIRS, c.n_pairs);
     // a launch is at most 2^32 - 1 threads in x and a point takes L of them: the power of two >= n_pairs (at least 2)
@@ -589,17 +592,27 @@ int validate_pairs(const PairsCall &c) {
     int rc = validate_grid(c.n_points, 2 * PSA_MAX_POINTS / lanes_per_point, lanes_per_point, c.n_steps, c.z_max, c.save_every);
     if (rc != PSA_OK) return rc;
     const uint32_t accepted = PSA_BCAST_GAMMA | PSA_BCAST_ALPHA | PSA_BCAST_A0 | PSA_OPT_CHECK_NAN | PSA_OPT_EXACT_STEP |
-                              PSA_OPT_LOSSLESS | PSA_OPT_BLOCK64;
+                              PSA_OPT_LOSSLESS | PSA_OPT_BLOCK64 | ((chain && !host_form) ? PSA_OPT_TRAJ_LD : 0u);
     if (c.flags & ~accepted)
-        return fail(PSA_E_FLAGS, "the multi-channel sweep takes the BCAST bits, CHECK_NAN, EXACT_STEP, LOSSLESS and BLOCK64 "
-                                 "only (no layout, float32 or LDS flag): 0x%x", (unsigned)(c.flags & ~accepted));
+        return fail(PSA_E_FLAGS, chain ? "the multi-channel chain takes the BCAST bits, CHECK_NAN, EXACT_STEP, LOSSLESS, BLOCK64 "
+                                         "and (its _dev form) TRAJ_LD only (no layout, float32 or LDS flag): 0x%x"
+                                       : "the multi-channel sweep takes the BCAST bits, CHECK_NAN, EXACT_STEP, LOSSLESS and BLOCK64 "
+                                         "only (no layout, float32 or LDS flag): 0x%x", (unsigned)(c.flags & ~accepted));
     if (c.n_points > 0 && (!c.dbeta || !c.gamma || !c.alpha || !c.a0 || !c.a_end || !c.wave_end || !c.wave_max || !c.first_bad))
         return fail(PSA_E_NULLPTR, "a required buffer pointer is NULL");
+    if (c.traj) {
+        // the bound of every float64 row launch, kept for parity between the families: this kernel addresses its rows with a
+        // 64-bit address per lane and would not need it
+        const bool padded = host_form || (c.flags & PSA_OPT_TRAJ_LD);
+        const unsigned long long ld = (unsigned long long)(padded ? traj_ld_of(c.n_points, sizeof(double)) : c.n_points);
+        if (ld * 16ull >= (1ull << 32))
+            return fail(PSA_E_TOO_LARGE, "a multi-channel trajectory launch takes a leading dimension below 2^28 points, got %llu", ld);
+    }
     return PSA_OK;
 }
 
-int pairs_dev(void *stream, const PairsCall &c) {
-    int rc = validate_pairs(c);
+int pairs_dev(void *stream, const PairsCall &c, bool chain = false) {
+    int rc = validate_pairs(c, chain);
     if (rc != PSA_OK) return rc;
     if (c.n_points == 0) return PSA_OK;
     psa::PairsArgs a;
@@ -610,6 +623,8 @@ int pairs_dev(void *stream, const PairsCall &c) {
     a.n_steps = (int)c.n_steps;
     a.save_every = c.save_every;
     a.n_pairs = c.n_pairs;
+    a.traj = c.traj;
+    a.traj_ld = (c.flags & PSA_OPT_TRAJ_LD) ? traj_ld_of(c.n_points, sizeof(double)) : c.n_points;
     hipError_t e = psa::launch_sweep_pairs_f64((hipStream_t)stream, c.flags, a);
     if (e != hipSuccess) return hip_fail(e, "rk4_sweep_pairs launch");
     return PSA_OK;
@@ -724,8 +739,12 @@ template <typename T> struct ChainFamily<SweepCall<T>> {   // 4 and 6 waves [p1,
     static constexpr bool signal_summary = true;      // p_end / p_max
     static constexpr bool waves_optional = true;      // the per-wave summary where p_wave_end / p_wave_max are given
     static constexpr bool second_mismatch = true;     // dbeta2 / theta2 (6 waves)
+    static constexpr bool sweep_tail = false;         // one span, too, must end on a saved row
     static constexpr const char *what = "the fibre chain";
     static int n_waves(const SweepCall<T> &c) { return c.n_waves; }
+    static int n_signals(const SweepCall<T> &c) { return c.n_waves == 6 ? 2 : 1; }
+    static int dbeta_rows(const SweepCall<T> &) { return 1; }   // rows of [N] a span's dbeta holds
+    static const T *stage_dbeta(Staging<T> &sg, const SweepCall<T> &c, int S, size_t N) { return sg.input(c.dbeta, S * N); }
     static int validate_first(const SweepCall<T> &first, bool) { return validate_common(first); }
     static int span_dev(void *stream, const SweepCall<T> &c) { return sweep_dev<T>(stream, c); }
     static void stage_summary(Staging<T> &sg, SweepCall<T> &d, const SweepCall<T> &c, size_t N) {
@@ -738,9 +757,12 @@ template <typename T> struct ChainFamily<SweepCall<T>> {   // 4 and 6 waves [p1,
 };
 template <typename T> struct ChainFamily<SinglePumpCall<T>> {   // three waves [p, s, i]: the three per-wave columns are the summary
     static constexpr int sig_wave = 1;
-    static constexpr bool signal_summary = false, waves_optional = false, second_mismatch = false;
+    static constexpr bool signal_summary = false, waves_optional = false, second_mismatch = false, sweep_tail = false;
     static constexpr const char *what = "the single-pump fibre chain";
     static int n_waves(const SinglePumpCall<T> &) { return 3; }
+    static int n_signals(const SinglePumpCall<T> &) { return 1; }
+    static int dbeta_rows(const SinglePumpCall<T> &) { return 1; }
+    static const T *stage_dbeta(Staging<T> &sg, const SinglePumpCall<T> &c, int S, size_t N) { return sg.input(c.dbeta, S * N); }
     static int validate_first(SinglePumpCall<T> first, bool host_form) {
         first.flags &= ~PSA_BCAST_TRANSFER;   // the chain's own bit
         return validate_single_pump(first, host_form);
@@ -749,6 +771,29 @@ template <typename T> struct ChainFamily<SinglePumpCall<T>> {   // three waves [
     static void stage_summary(Staging<T> &sg, SinglePumpCall<T> &d, const SinglePumpCall<T> &c, size_t N) {
         d.wave_end = sg.output_soa(c.wave_end, N, 3);
         d.wave_max = sg.output_soa(c.wave_max, N, 3);
+        d.first_bad = sg.output(c.first_bad, N);
+    }
+};
+template <> struct ChainFamily<PairsCall> {   // two pumps and K pairs [p1, p2, s_1, i_1, ..., s_K, i_K]: K signals, K mismatches
+    static constexpr int sig_wave = 2;
+    static constexpr bool signal_summary = false, waves_optional = false, second_mismatch = false;
+    // one span is the sweep's trajectory form and keeps the sweep's rule: A[-1] is the last SAVED row, a tail may follow it
+    static constexpr bool sweep_tail = true;
+    static constexpr const char *what = "the multi-channel fibre chain";
+    static int n_waves(const PairsCall &c) { return 2 + 2 * c.n_pairs; }
+    static int n_signals(const PairsCall &c) { return c.n_pairs; }
+    static int dbeta_rows(const PairsCall &c) { return c.n_pairs; }   // a span's dbeta is SoA [K][N]
+    static int validate_first(PairsCall first, bool host_form) {
+        first.flags &= ~PSA_BCAST_TRANSFER;   // the chain's own bit
+        return validate_pairs(first, true, host_form);
+    }
+    static int span_dev(void *stream, const PairsCall &c) { return pairs_dev(stream, c, true); }
+    static const double *stage_dbeta(Staging<double> &sg, const PairsCall &c, int S, size_t N) {
+        return sg.input_soa(c.dbeta, N, c.n_pairs, S);                 // [S][N][K] -> [S][K][N]
+    }
+    static void stage_summary(Staging<double> &sg, PairsCall &d, const PairsCall &c, size_t N) {
+        d.wave_end = sg.output_soa(c.wave_end, N, n_waves(c));
+        d.wave_max = sg.output_soa(c.wave_max, N, n_waves(c));
         d.first_bad = sg.output(c.first_bad, N);
     }
 };
@@ -762,11 +807,13 @@ struct ChainScratch {
     int64_t *bad_s;
     T *wend_s, *wmax_s;
     size_t bytes;
-    ChainScratch(void *base, size_t N, int n_waves, bool two_thetas, bool signal_summary, bool waves) {
+    // theta_rows: the Theta of that many signals in ONE block [theta_rows][N] (the multi-channel model's K; theta2 is its
+    // second row); two_thetas: a second signal's Theta in a block of its own (6 waves)
+    ChainScratch(void *base, size_t N, int n_waves, bool two_thetas, bool signal_summary, bool waves, int theta_rows = 1) {
         Carver ws;
         ws.base = (char *)base;
-        theta = ws.take<double>(N);
-        theta2 = two_thetas ? ws.take<double>(N) : nullptr;
+        theta = ws.take<double>((size_t)theta_rows * N);
+        theta2 = two_thetas ? ws.take<double>(N) : (theta_rows > 1 && theta ? theta + N : nullptr);
         a0_next = ws.take<T>(2 * (size_t)n_waves * N);
         a_end_s = ws.take<T>(2 * (size_t)n_waves * N);
         p_end_s = signal_summary ? ws.take<T>(N) : nullptr;
@@ -781,7 +828,7 @@ struct ChainScratch {
         using F = ChainFamily<Span>;
         const int n_waves = F::n_waves(c);
         return ChainScratch(base, (size_t)c.n_points, n_waves, F::second_mismatch && n_waves == 6, F::signal_summary,
-                            !F::waves_optional || c.wave_end != nullptr);
+                            !F::waves_optional || c.wave_end != nullptr, F::second_mismatch ? 1 : F::n_signals(c));
     }
 };
 
@@ -823,15 +870,17 @@ struct SpanJoin {
     }
 };
 
-// The grid rules of a chain's spans (every chain family); *rows_total = sum over spans of n_steps[s] / save_every + 1
-int validate_spans(int n_segments, const int64_t *n_steps, const double *seg_len, int32_t save_every, int64_t *rows_total) {
+// The grid rules of a chain's spans (every chain family); *rows_total = sum over spans of n_steps[s] / save_every + 1.
+// tail_ok: this span count may end behind its last saved row, as a sweep may (ChainFamily::sweep_tail: one span alone)
+int validate_spans(int n_segments, const int64_t *n_steps, const double *seg_len, int32_t save_every, int64_t *rows_total,
+                   bool tail_ok = false) {
     int64_t rows = 0;
     for (int s = 0; s < n_segments; ++s) {
         if (n_steps[s] <= 0 || n_steps[s] > 2147483647LL)
             return fail(PSA_E_NSTEPS, "n_steps[%d] must be in [1, 2^31), got %lld", s, (long long)n_steps[s]);
         if (!(seg_len[s] > 0.0) || !std::isfinite(seg_len[s])) return fail(PSA_E_ZMAX, "seg_len[%d] must be positive", s);
         // a_end is the last saved row: a tail after it would silently shorten the span
-        if (n_steps[s] % save_every != 0)
+        if (n_steps[s] % save_every != 0 && !tail_ok)
             return fail(PSA_E_SAVE_EVERY, "n_steps[%d] = %lld is not a multiple of save_every = %d", s,
                         (long long)n_steps[s], (int)save_every);
         rows += n_steps[s] / save_every + 1;
@@ -869,7 +918,8 @@ int validate_chain(const ChainCall<Span> &c, bool host_form, int64_t *rows_total
     int rc = F::validate_first(first, host_form);
     if (rc != PSA_OK) return rc;
     int64_t rows = 0;
-    if ((rc = validate_spans(c.n_segments, c.n_steps, c.seg_len, c.s.save_every, &rows)) != PSA_OK) return rc;
+    if ((rc = validate_spans(c.n_segments, c.n_steps, c.seg_len, c.s.save_every, &rows, F::sweep_tail && c.n_segments == 1)) != PSA_OK)
+        return rc;
     if constexpr (F::waves_optional) {
         if ((c.s.wave_end != nullptr) != (c.s.wave_max != nullptr))
             return fail(PSA_E_NULLPTR, "p_wave_end and p_wave_max are given together or not at all");
@@ -916,7 +966,7 @@ int chain_dev(void *stream, const ChainCall<Span> &c) {
     for (int s = 0; s < S; ++s) {
         const bool first = s == 0;
         set_span(s);
-        sp.dbeta = c.s.dbeta + s * N;
+        sp.dbeta = c.s.dbeta + s * (F::dbeta_rows(c.s) * N);
         sp.gamma = c.s.gamma + s * g_step;
         sp.alpha = c.s.alpha + s * a_step;
         sp.a0 = first ? c.s.a0 : w.a0_next;
@@ -941,14 +991,16 @@ int chain_dev(void *stream, const ChainCall<Span> &c) {
         e.wave_max_s = w.wmax_s;
         e.wave_end = c.s.wave_end;
         e.wave_max = c.s.wave_max;
+        e.n_sig = F::n_signals(c.s);
         e.theta2 = w.theta2;
-        e.p_end = e.p_max = nullptr;   // a family without the signal summary, without a second mismatch
-        e.dbeta2 = nullptr;
+        e.sig_ld = (long long)N;
+        e.p_end = e.p_max = nullptr;   // a family without the signal summary
+        e.dbeta2 = e.n_sig > 1 ? sp.dbeta + N : nullptr;   // the rows of one [K][N] block, or ...
         if constexpr (F::signal_summary) {
             e.p_end = c.s.p_end;
             e.p_max = c.s.p_max;
         }
-        if constexpr (F::second_mismatch) e.dbeta2 = sp.dbeta2;
+        if constexpr (F::second_mismatch) e.dbeta2 = sp.dbeta2;   // ... the second mismatch's own array
         hipError_t he = EpilogueLaunch<T>::fn((hipStream_t)stream, e);
         if (he != hipSuccess) return hip_fail(he, "chain epilogue launch");
         row += e.rows;
@@ -976,7 +1028,7 @@ int chain_host(int device, const ChainCall<Span> &c, double *elapsed_ms) {
     d.lossless = lossless.data();
     const T *tr = S > 1 ? c.transfer : nullptr;
     auto layout = [&](Staging<T> &sg) {
-        d.s.dbeta = sg.input(c.s.dbeta, S * N);
+        d.s.dbeta = F::stage_dbeta(sg, c.s, S, N);
         if constexpr (F::second_mismatch) d.s.dbeta2 = sg.input(c.s.dbeta2, S * N);
         d.s.gamma = sg.input(c.s.gamma, (flags & PSA_BCAST_GAMMA) ? (size_t)S : S * N);
         d.s.alpha = sg.input(c.s.alpha, (flags & PSA_BCAST_ALPHA) ? (size_t)S : S * N);
@@ -1000,6 +1052,10 @@ int64_t chain_workspace_bytes(int n_waves, int64_t n_points, size_t elem, bool w
 }
 int64_t single_pump_chain_workspace_bytes(int64_t n_points) {
     return n_points < 0 ? -1 : (int64_t)ChainScratch<double>(nullptr, (size_t)n_points, 3, false, false, true).bytes;
+}
+int64_t pairs_chain_workspace_bytes(int n_pairs, int64_t n_points) {
+    if (n_pairs < 1 || n_pairs > PSA_MAX_PAIRS || n_points < 0) return -1;
+    return (int64_t)ChainScratch<double>(nullptr, (size_t)n_points, 2 + 2 * n_pairs, false, false, true, n_pairs).bytes;
 }
 
 template <typename T> struct GainLaunch;
@@ -1547,5 +1603,25 @@ int psa_rk4_single_pump_chain_f64_dev(void *stream, int64_t n_points, int n_segm
                                            d_traj_soa_or_null}, n_segments, n_steps, seg_len, d_transfer_soa, d_workspace});
 }
 int64_t psa_rk4_single_pump_chain_workspace_bytes(int64_t n_points) { return single_pump_chain_workspace_bytes(n_points); }
+
+int psa_rk4_pairs_chain_f64(int device, int n_pairs, int64_t n_points, int n_segments, const int64_t *n_steps, const double *seg_len,
+                            int32_t save_every, const double *dbeta, const double *gamma, const double *alpha,
+                            const double *a0_re_im, const double *transfer_re_im, uint32_t flags, double *a_end_re_im,
+                            double *p_wave_end, double *p_wave_max, int64_t *first_bad_step, double *traj_or_null,
+                            double *elapsed_ms_or_null) {
+    return chain_host<PairsCall>(device, {{n_pairs, n_points, 0, 0.0, save_every, dbeta, gamma, alpha, a0_re_im, flags, a_end_re_im,
+                                          p_wave_end, p_wave_max, first_bad_step, traj_or_null},
+                                         n_segments, n_steps, seg_len, transfer_re_im, nullptr}, elapsed_ms_or_null);
+}
+int psa_rk4_pairs_chain_f64_dev(void *stream, int n_pairs, int64_t n_points, int n_segments, const int64_t *n_steps,
+                                const double *seg_len, int32_t save_every, const double *d_dbeta_soa, const double *d_gamma,
+                                const double *d_alpha, const double *d_a0_soa, const double *d_transfer_soa, uint32_t flags,
+                                double *d_a_end_soa, double *d_p_wave_end_soa, double *d_p_wave_max_soa,
+                                int64_t *d_first_bad_step, double *d_traj_soa_or_null, void *d_workspace) {
+    return chain_dev<PairsCall>(stream, {{n_pairs, n_points, 0, 0.0, save_every, d_dbeta_soa, d_gamma, d_alpha, d_a0_soa, flags,
+                                         d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step, d_traj_soa_or_null},
+                                        n_segments, n_steps, seg_len, d_transfer_soa, d_workspace});
+}
+int64_t psa_rk4_pairs_chain_workspace_bytes(int n_pairs, int64_t n_points) { return pairs_chain_workspace_bytes(n_pairs, n_points); }
 
 }  // extern "C"

@@ -7,6 +7,10 @@
 // Theta_s}; the Kerr terms are phase-blind).  Six waves: the signal of pair k (waves 2 and 4) takes its own Theta^(k).
 // Three waves [p, s, i] (the single-pump model, psa_rk4_single_pump_chain_*): the same rule with the signal at index 1
 // (a_s a_i = b_s b_i e^{-i Theta_s}); `sig_wave` names the index, and that family has no p_end / p_max (both null).
+// K signals (the multi-channel model, psa_rk4_pairs_chain_*): the six-wave rule for every pair, signal k at wave 2 + 2k with
+// its own Theta^(k) = sum_{j<s} dbeta_{j,k} L_j; in the pumps' sum_k E_k A_sk A_ik every pair's phase cancels in its own term.
+// In general: `n_sig` signals at waves sig_wave + 2k, signal 0 with (theta, dbeta), signal k >= 1 with row k - 1 of
+// (theta2, dbeta2), rows `sig_ld` elements apart.
 // At the boundary s -> s+1 the next span starts from B'_j = T_s[j] B_j, times e^{+i dbeta_s L_s} for the signal(s);
 // reported amplitudes are brought back to A with e^{-i Theta_s}.  Theta is kept per point in float64 in HBM for both
 // precisions (the kernels form dbeta*z in float64 as well).
@@ -60,53 +64,49 @@ __global__ void __launch_bounds__(256) chain_epilogue_kernel(ChainEpilogue<T> e)
         }
     }
 
-    // Theta_s of this span's signal(s): 0 for the first span (the `theta` buffers are not read there)
-    const double th1 = e.first ? 0.0 : e.theta[i];
-    const double th2 = (nw == 6) ? (e.first ? 0.0 : e.theta2[i]) : 0.0;
-    double c1 = 1.0, s1 = 0.0, c2 = 1.0, s2 = 0.0;
-    if (!e.first) {
-        sincos(-th1, &s1, &c1);
-        if (nw == 6) sincos(-th2, &s2, &c2);
-    }
+    // signal k: wave sig + 2k, its Theta and its mismatch
+    auto theta_of = [&](const int k) -> double * { return k == 0 ? e.theta + i : e.theta2 + (long long)(k - 1) * e.sig_ld + i; };
+    auto dbeta_of = [&](const int k) -> double {
+        return (double)(k == 0 ? e.dbeta[i] : e.dbeta2[(long long)(k - 1) * e.sig_ld + i]);
+    };
 
-    if (e.traj && !e.first) {
-        // rows [0, rows) of this span, (re, im) pairs at ((row * nw + w) * ld + i) * 2
-        for (long long r = 0; r < e.rows; ++r) {
-            T *p = e.traj + ((r * nw + sig) * e.traj_ld + i) * 2;
-            rotate(p[0], p[1], c1, s1);
-            if (nw == 6) {
-                T *q = e.traj + ((r * nw + 4) * e.traj_ld + i) * 2;
-                rotate(q[0], q[1], c2, s2);
-            }
-        }
-    }
-
-    if (e.a_end_out) {   // last span: the state in the A frame
+    if (e.a_end_out)   // last span: the state, brought to the A frame below
         for (int c = 0; c < 2 * nw; ++c) e.a_end_out[(long long)c * n + i] = e.a_end_s[(long long)c * n + i];
-        if (!e.first) {
-            rotate(e.a_end_out[(long long)(2 * sig) * n + i], e.a_end_out[(long long)(2 * sig + 1) * n + i], c1, s1);
-            if (nw == 6) rotate(e.a_end_out[8 * n + i], e.a_end_out[9 * n + i], c2, s2);
-        }
-        return;
-    }
 
-    // boundary s -> s+1: B' = T_s B, signal(s) times e^{+i dbeta_s L_s}; Theta += dbeta_s L_s
-    const double ph1 = (double)e.dbeta[i] * e.seg_len;
-    const double ph2 = (nw == 6) ? (double)e.dbeta2[i] * e.seg_len : 0.0;
-    e.theta[i] = th1 + ph1;
-    if (nw == 6) e.theta2[i] = th2 + ph2;
+    if (!e.first) {   // Theta_s = 0 in the first span: nothing to rotate (the `theta` buffers are not read there)
+        for (int k = 0; k < e.n_sig; ++k) {
+            const int w = sig + 2 * k;
+            double c, s;
+            sincos(-*theta_of(k), &s, &c);
+            if (e.traj) {
+                // rows [0, rows) of this span, (re, im) pairs at ((row * nw + w) * ld + i) * 2
+                for (long long r = 0; r < e.rows; ++r) {
+                    T *p = e.traj + ((r * nw + w) * e.traj_ld + i) * 2;
+                    rotate(p[0], p[1], c, s);
+                }
+            }
+            if (e.a_end_out) rotate(e.a_end_out[(long long)(2 * w) * n + i], e.a_end_out[(long long)(2 * w + 1) * n + i], c, s);
+        }
+    }
+    if (e.a_end_out) return;
+
+    // boundary s -> s+1: B' = T_s B, signal k times e^{+i dbeta_s,k L_s}; Theta^(k) += dbeta_s,k L_s
     for (int w = 0; w < nw; ++w) {
         T re = e.a_end_s[(long long)(2 * w) * n + i], im = e.a_end_s[(long long)(2 * w + 1) * n + i];
-        if (w == sig || (nw == 6 && w == 4)) {
+        const int k = (w - sig) / 2;
+        if (w >= sig && (w - sig) % 2 == 0 && k < e.n_sig) {
+            double *th = theta_of(k);
+            const double ph = dbeta_of(k) * e.seg_len;
+            *th = (e.first ? 0.0 : *th) + ph;
             double sp, cp;
-            sincos(w == sig ? ph1 : ph2, &sp, &cp);
+            sincos(ph, &sp, &cp);
             rotate(re, im, cp, sp);
         }
         if (e.transfer) {
-            const long long k = e.transfer_stride ? i : 0;
+            const long long j = e.transfer_stride ? i : 0;
             const long long ld = e.transfer_stride ? n : 1;
-            const double tr = (double)e.transfer[(long long)(2 * w) * ld + k];
-            const double ti = (double)e.transfer[(long long)(2 * w + 1) * ld + k];
+            const double tr = (double)e.transfer[(long long)(2 * w) * ld + j];
+            const double ti = (double)e.transfer[(long long)(2 * w + 1) * ld + j];
             const double r = (double)re, m = (double)im;
             re = (T)(tr * r - ti * m);
             im = (T)(tr * m + ti * r);

@@ -50,7 +50,7 @@ struct AdaptiveArgs {
 };
 
 // Everything one multi-channel sweep launch needs (two pumps and n_pairs signal/idler pairs, NW = 2 + 2*n_pairs waves
-// [p1, p2, s_1, i_1, ..., s_K, i_K]; float64 only).  Strides as in SweepArgs; every output is always written.
+// [p1, p2, s_1, i_1, ..., s_K, i_K]; float64 only).  Strides as in SweepArgs; every output but the trajectory is always written.
 struct PairsArgs {
     const double *dbeta;     // SoA [n_pairs][N]
     const double *gamma;     // [N] | [1]
@@ -67,6 +67,8 @@ struct PairsArgs {
     int n_pairs;             // 1..16
     int gamma_stride, alpha_stride, a0_stride;  // 0 | 1
     long long a0_ld;
+    double *traj;            // [n_saved][NW][traj_ld][2] ((re, im) pairs) or nullptr
+    long long traj_ld;       // points per (row, wave) region of traj: n_points, or padded (psa_traj_ld)
 };
 
 // Everything one single-pump sweep launch needs (one pump, a signal and an idler: NW = 3 waves [p, s, i]; float64 one point per
@@ -100,8 +102,9 @@ enum CheckMode : int { CHECK_NONE = 0, CHECK_BLOCK = 1, CHECK_EXACT = 2 };
 hipError_t launch_sweep_f64(hipStream_t s, int n_waves, uint32_t flags, const SweepArgs<double> &a);
 hipError_t launch_sweep_f32(hipStream_t s, int n_waves, uint32_t flags, const SweepArgs<float> &a);
 // Multi-channel sweep launcher (psa_rk4_pairs.hip): one launch on s of L * n_points lanes, L = pairs_lanes_per_point;
-// nothing for n_points == 0.  Reads PSA_OPT_CHECK_NAN / EXACT_STEP / LOSSLESS / BLOCK64 of `flags`; the caller has
-// validated the arguments (1 <= n_pairs <= 16, the lanes fit the launch grid).
+// nothing for n_points == 0.  Reads PSA_OPT_CHECK_NAN / EXACT_STEP / LOSSLESS / BLOCK64 of `flags` and takes the trajectory
+// from a.traj being non-null; the caller has validated the arguments (1 <= n_pairs <= 16, the lanes fit the launch grid, with
+// a trajectory traj_ld * 16 < 2^32).
 int pairs_lanes_per_point(int n_pairs);
 hipError_t launch_sweep_pairs_f64(hipStream_t s, uint32_t flags, const PairsArgs &a);
 // Single-pump sweep launchers (psa_rk4_single_pump.hip: one lane per point; psa_rk4_single_pump_f32.hip: two points per lane):
@@ -142,7 +145,8 @@ template <typename T>
 struct ChainEpilogue {
     long long n;
     int n_waves;
-    int sig_wave;               // the wave that carries Theta: 2 (4 and 6 waves; 6 waves: wave 4 carries theta2), 1 (3 waves)
+    int sig_wave;               // the first wave that carries a Theta: 2 (two pumps in front), 1 (3 waves)
+    int n_sig;                  // signals, at waves sig_wave + 2k: 1 (3 and 4 waves), 2 (6 waves), K (the multi-channel model)
     int first;                  // span 0: Theta_0 = 0, no rotation, `theta` is initialised by the boundary
     int fold;                   // spans >= 1: fold the span's summary (the *_s buffers) into the running outputs
     const T *a_end_s;           // [2*NW][n] the span's a_end (B frame)
@@ -153,13 +157,14 @@ struct ChainEpilogue {
     long long *first_bad;
     T *wave_end, *wave_max;     // [NW][n] or nullptr
     long long step_offset;      // steps of the spans before this one
-    double *theta, *theta2;     // [n] float64 accumulated mismatch phase (theta2: 6 waves)
+    double *theta, *theta2;     // float64 accumulated mismatch phase: [n] of signal 0, [n_sig - 1][sig_ld] of the others
+    long long sig_ld;           // elements between the rows of theta2 and of dbeta2 (n where n_sig > 2 packs them)
     T *traj;                    // first row of this span in [rows][NW][traj_ld][2], or nullptr
     long long traj_ld, rows;
     T *a_end_out;               // last span: [2*NW][n] A-frame a_end; nullptr otherwise
     const T *transfer;          // boundary: [2*NW][n] (stride 1) or [2*NW] (stride 0); nullptr = identity
     int transfer_stride;
-    const T *dbeta, *dbeta2;    // this span's [n]
+    const T *dbeta, *dbeta2;    // this span's: [n] of signal 0, [n_sig - 1][sig_ld] of the others
     double seg_len;
     T *a0_next;                 // [2*NW][n]
 };

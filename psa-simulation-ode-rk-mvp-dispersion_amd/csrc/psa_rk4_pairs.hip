@@ -27,19 +27,24 @@ hipError_t launch_sweep_pairs_f64(hipStream_t s, uint32_t flags, const PairsArgs
     const int lanes_per_point = pairs_lanes_per_point(a.n_pairs);
     const long long lanes = (long long)lanes_per_point * a.n_points;
     const int check = !(flags & PSA_OPT_CHECK_NAN) ? CHECK_NONE : ((flags & PSA_OPT_EXACT_STEP) ? CHECK_EXACT : CHECK_BLOCK);
-    // the rule of launch_sweep_f64: 64-thread workgroups while the launch's waves fit half the SIMDs, 256 beyond
+    // the rule of launch_sweep_f64: 64-thread workgroups while the launch's waves fit half the SIMDs, 256 beyond.  Rows exist
+    // with 256-thread workgroups only: the block size changes the speed and no number, and a launch that saves rows is bound
+    // by its stores (PSA_OPT_BLOCK64 selects nothing there).
     const long long waves = (lanes + 63) / 64;
-    const int block = ((flags & PSA_OPT_BLOCK64) || 2 * waves <= (long long)pairs_simd_count(s)) ? 64 : 256;
+    const bool traj = a.traj != nullptr;
+    const int block = (!traj && ((flags & PSA_OPT_BLOCK64) || 2 * waves <= (long long)pairs_simd_count(s))) ? 64 : 256;
     const bool lossless = (flags & PSA_OPT_LOSSLESS) != 0;
     const dim3 grid((unsigned)((lanes + block - 1) / block)), blk(block);
     return with_int<2, 4, 8, 16>(lanes_per_point, [&](auto l) {
     return with_int<CHECK_NONE, CHECK_BLOCK, CHECK_EXACT>(check, [&](auto chk) {
-    return with_int<64, 256>(block, [&](auto b) {
     return with_bool(lossless, [&](auto ll) {
         void *args[] = {const_cast<PairsArgs *>(&a)};
-        (void)hipLaunchKernel(reinterpret_cast<const void *>(&rk4_sweep_pairs_kernel<l, chk, b, !ll>), grid, blk, args, 0, s);
+        const void *k = block == 64 ? reinterpret_cast<const void *>(&rk4_sweep_pairs_kernel<l, chk, 64, !ll, false>)
+                        : traj      ? reinterpret_cast<const void *>(&rk4_sweep_pairs_kernel<l, chk, 256, !ll, true>)
+                                    : reinterpret_cast<const void *>(&rk4_sweep_pairs_kernel<l, chk, 256, !ll, false>);
+        (void)hipLaunchKernel(k, grid, blk, args, 0, s);
         return hipGetLastError();
-    }); }); }); });
+    }); }); });
 }
 
 }  // namespace psa

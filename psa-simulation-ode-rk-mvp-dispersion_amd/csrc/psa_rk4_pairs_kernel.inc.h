@@ -39,7 +39,12 @@
 // file).  `bad` and the non-finite test's result are the same in the L lanes of a point, so no exchange runs with part of
 // a point masked off.
 //
-// Out of scope: trajectory rows, float32, LDS staging, RK45, chains.
+// Saved rows (TRAJ): row 0 is z = 0, then one row per save, [row][wave][ld] (re, im) pairs like every other family.  Lane 0
+// stores the two pumps, lane r < K its pair's waves 2 + 2r and 3 + 2r, a padding lane nothing: one 16-byte store per wave, so
+// of a wave's 64 lanes 64/L write CONSECUTIVE points of one wave region.  The stores sit where the
+// summary stores sit, outside every exchange.  Chains of spans are joined outside the kernel (psa_chain.hip).
+//
+// Out of scope: float32, LDS staging, RK45, a dedicated save_every == 1 loop.
 #pragma once
 #include "psa_rk4_carried.inc.h"
 #include "psa_rk4_quad_kernel.inc.h"
@@ -99,7 +104,7 @@ __device__ __forceinline__ void pairs_stage(const double (&a)[8], const double (
     out[7] = fma_(xs, Fsr, fma_(ys, Fsi, link(gj[3], xi, 7)));
 }
 
-template <int L, int CHECK, int BLOCK, bool LOSS>
+template <int L, int CHECK, int BLOCK, bool LOSS, bool TRAJ>
 __global__ void __launch_bounds__(BLOCK) rk4_sweep_pairs_kernel(const PairsArgs A) {
     const long long gid = (long long)blockIdx.x * BLOCK + threadIdx.x;
     const long long idx = gid / L;          // sweep point: its L lanes share one
@@ -152,6 +157,28 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_pairs_kernel(const PairsArgs 
                 A.p_wave_end[(long long)(2 * r + j) * N + idx] = fma_(a[2 * j], a[2 * j], a[2 * j + 1] * a[2 * j + 1]);
         }
     };
+    // trajectory rows [row][wave][ld][2].  The wave a lane stores depends on the lane, so the (row, wave) base is not
+    // wave-uniform as it is in the one-lane kernels: each lane keeps the 64-bit address of its first wave's pair in row 0
+    // and steps it by whole rows; plain C++ stores, so the compiler sees the 16-byte store hazard itself.  The C-ABI keeps
+    // ld * 16 below 2^32, the bound of every float64 row launch.
+    using Pair = typename PairOf<double>::type;
+    const long long LD = A.traj_ld;
+    const long long row_pairs = (long long)(2 + 2 * A.n_pairs) * LD;
+    Pair *const pump_row0 = reinterpret_cast<Pair *>(A.traj) + idx;                       // wave 0; wave 1 is LD further
+    Pair *const pair_row0 = pump_row0 + (long long)(2 + 2 * rr) * LD;                     // wave 2 + 2r; 3 + 2r is LD further
+    auto store_traj_row = [&](const int row) {
+        if (r == 0) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                __builtin_nontemporal_store(Pair{a[2 * j], a[2 * j + 1]}, pump_row0 + (long long)row * row_pairs + (long long)j * LD);
+        }
+        if (lit) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                __builtin_nontemporal_store(Pair{a[4 + 2 * j], a[5 + 2 * j]}, pair_row0 + (long long)row * row_pairs + (long long)j * LD);
+        }
+    };
+    if constexpr (TRAJ) store_traj_row(0);
     if (A.n_steps / A.save_every == 0) store_a_end();   // no saved row after z = 0
 
     auto stage = [&](auto full, const double (&y)[8], const double (&base)[8], const double er, const double ei, double (&out)[8]) {
@@ -167,7 +194,8 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_pairs_kernel(const PairsArgs 
             pm[w] = (pw > pm[w] || pw != pw) ? pw : pm[w];   // np.max propagates NaN
         }
     };
-    auto save_row = [&](const int, const bool last) {
+    auto save_row = [&](const int row, const bool last) {
+        if constexpr (TRAJ) store_traj_row(row);
         if (last) store_a_end();
     };
     const long long bad = carried_event_loop<CHECK, 2>(a, Er, Ei, A.n_steps, A.save_every, step_on, seed_on, nonfinite_on, summarise, save_row);

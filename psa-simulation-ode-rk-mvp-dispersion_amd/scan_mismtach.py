@@ -914,3 +914,96 @@ def scan_single_pump_copier_psa_phase(*, psa_cfg: SimulationConfig, psa_delta_be
     return _phase_scan_result(ph, dbp, res.signal_gain(p0[1], mode=gain_mode, unit="dB"), res,
                               gain=res.signal_gain(p0[1], mode=gain_mode, unit=unit),
                               gain_idler=res.idler_conversion(p0[1], mode=gain_mode, unit=unit))
+
+
+def scan_wdm_copier_psa_phase(*, psa_cfg: SimulationConfig, copier_cfg: Optional[SimulationConfig] = None, lambda_p1_m: float,
+                              lambda_p2_m: float, Omega: Sequence[float], p_pump: Sequence[float], p_signal, p_idler=0.0,
+                              gamma: float, alpha: float, dispersion: DispersionParams,
+                              copier_dispersion: Optional[DispersionParams] = None, copier_gamma: Optional[float] = None,
+                              copier_alpha: Optional[float] = None, mid_gain_db=0.0, mid_phase=0.0,
+                              phase: Optional[Sequence[float]] = None, phase_wave: str = "pumps",
+                              even_orders: Tuple[int, ...] = (2, 4), length_unit: str = "m", gain_mode: GainMode = "max",
+                              gain_unit: str = "dB", device: Optional[int] = None,
+                              devices: Optional[Sequence[int]] = None) -> dict:
+    """scan_copier_psa_phase for the multi-channel model (no reference counterpart): the gain of every
+    channel of a WDM copier - mid-stage - PSA link on two pumps against the mid-stage phase.  Waves
+    [p1, p2, s_1, i_1, ..., s_K, i_K], channel k at omega_c +- Omega_k; per span dbeta_k = delta_beta_symmetric(omega_d,
+    Omega_k) from that span's dispersion, as scan_wdm_gain forms it.  The channels couple through pump depletion and
+    SPM/XPM; signal-signal FWM is not modelled.
+
+    An optional copier span (``copier_cfg``: length, dz; ``copier_dispersion`` / ``copier_gamma`` / ``copier_alpha`` default
+    to the PSA span's) generates the K idlers; the mid-stage applies ``mid_gain_db`` / ``mid_phase`` (a scalar or NW = 2 + 2K
+    values) plus the scanned ``phase`` (F values, default 32 over [0, 2 pi)) on ``phase_wave`` -- "pumps", "signals" or
+    "idlers"; the PSA span (``psa_cfg``) then amplifies all channels phase-sensitively from the same two pumps.  The F
+    phase points are the sweep points: ONE launch per span (sweep.rk4_chain_pairs) with per-point transfers, on ``device``
+    or split over ``devices``.  Without a copier the mid-stage acts on the input.  p_pump (2,), p_signal (K,) > 0, p_idler a
+    scalar or (K,); gamma / alpha per length_unit; save_every and check_nan come from psa_cfg (the copier's must agree, and
+    every span's step count must be a multiple of save_every).  Sharding over a process group is out of scope here.
+
+    Returns dict(phase (F,), gain (F, K) of every signal over its seed, idler (F, K) every idler's power over its signal's
+    seed, gain_max_db, gain_min_db, extinction_db (K,): per channel over the finite gains, dbeta (S, K) in 1/length_unit,
+    first_bad_step (F,), result=PairsChainResult)."""
+    from .frequency_plan import omega_from_lambda
+    from .simulation import wdm_mid_stage
+    from .sweep import FibreSpan, initial_amplitudes, rk4_chain_pairs
+    unit = check_gain(gain_mode, gain_unit)
+    ph, _ = _phase_scan_axes(phase, 0.0)
+    Om = np.asarray(list(Omega), dtype=float)
+    if Om.ndim != 1 or not 1 <= Om.size <= 16 or not np.all(np.isfinite(Om)):
+        raise ValueError("Omega must be a 1D sequence of 1..16 finite detunings (rad/s)")
+    K = int(Om.size)
+    nw = 2 + 2 * K
+    pp = np.asarray(list(p_pump), dtype=float)
+    if pp.shape != (2,) or not np.all(np.isfinite(pp)) or np.any(pp < 0.0):
+        raise ValueError("p_pump must hold two finite non-negative powers [p1, p2]")
+    ps = np.asarray(p_signal, dtype=float)
+    if ps.shape != (K,) or not np.all(np.isfinite(ps)) or np.any(ps <= 0.0):
+        raise ValueError(f"p_signal (the seed powers) must have shape ({K},), finite and > 0 to define gain")
+    pi = np.asarray(p_idler, dtype=float)
+    if pi.shape not in ((), (K,)) or not np.all(np.isfinite(pi)) or np.any(pi < 0.0):
+        raise ValueError(f"p_idler must be a scalar or ({K},) of finite non-negative powers")
+    masks = {"pumps": (slice(0, 2),), "signals": (slice(2, None, 2),), "idlers": (slice(3, None, 2),)}
+    if not isinstance(phase_wave, str) or phase_wave not in masks:
+        raise ValueError("phase_wave must be 'pumps', 'signals' or 'idlers'")
+    mask = np.zeros(nw)
+    mask[masks[phase_wave]] = 1.0
+    mg, mp = np.asarray(mid_gain_db, dtype=float), np.asarray(mid_phase, dtype=float)
+    if mg.shape not in ((), (nw,)) or mp.shape not in ((), (nw,)):
+        raise ValueError(f"mid_gain_db and mid_phase must be a scalar or hold {nw} values")
+    if dispersion is None:
+        raise ValueError("dispersion must be provided")
+    w1, w2 = omega_from_lambda(lambda_p1_m), omega_from_lambda(lambda_p2_m)
+    wc, wd = 0.5 * (w1 + w2), 0.5 * (w1 - w2)
+    if np.any(np.abs(Om) >= wc):
+        raise ValueError("|Omega| must stay below omega_c (sideband frequencies must be positive)")
+    fibres = [(psa_cfg, gamma, alpha, dispersion)]
+    if copier_cfg is not None:
+        fibres.insert(0, (copier_cfg, gamma if copier_gamma is None else copier_gamma,
+                          alpha if copier_alpha is None else copier_alpha,
+                          dispersion if copier_dispersion is None else copier_dispersion))
+        if int(copier_cfg.save_every) != int(psa_cfg.save_every) or bool(copier_cfg.check_nan) != bool(psa_cfg.check_nan):
+            raise ValueError("copier_cfg and psa_cfg must share save_every and check_nan")
+    spans, dbs = [], []
+    for cfg, g, a, d in fibres:
+        pre = _prepare(cfg, gamma=g, alpha=a, dispersion=d, phase_matching_cfg=None, beta_legacy=None, length_unit=length_unit)
+        fiber = pre["fiber"]
+        db = delta_beta_symmetric_array(wd, Om, fiber.dispersion, even_orders=even_orders)      # per metre
+        dbs.append(db * pre["scale"])
+        # per point: the F phase points are the sweep points, and a chain takes its point count from the spans and a0
+        spans.append(FibreSpan(fiber.length_m, dz=pre["grid"].dz_m, dbeta=np.broadcast_to(db, (ph.size, K)), gamma=fiber.gamma_W_m,
+                               alpha=fiber.alpha_1_m))
+    p_all = np.empty(nw)
+    p_all[:2], p_all[2::2], p_all[3::2] = pp, ps, np.broadcast_to(pi, (K,))
+    a_in = initial_amplitudes(p_all)
+    T = wdm_mid_stage(np.broadcast_to(mg, (nw,)), np.broadcast_to(mp, (nw,))[None, :] + ph[:, None] * mask[None, :])   # (F, NW)
+    a0, transfers = (T * a_in[None, :], None) if copier_cfg is None else (a_in, [T])
+    res = rk4_chain_pairs(spans, a0=a0, transfers=transfers, save_every=int(psa_cfg.save_every),
+                          check_nan=bool(psa_cfg.check_nan), device=(0 if device is None else int(device)), devices=devices)
+    gain_db = res.channel_gain(ps, mode=gain_mode, unit="dB")
+    with np.errstate(all="ignore"):
+        some = np.isfinite(gain_db).any(axis=0)
+        gmax = np.where(some, np.max(np.where(np.isfinite(gain_db), gain_db, -np.inf), axis=0), np.nan)
+        gmin = np.where(some, np.min(np.where(np.isfinite(gain_db), gain_db, np.inf), axis=0), np.nan)
+    return dict(phase=ph, gain=gain_db if unit == "db" else res.channel_gain(ps, mode=gain_mode, unit=unit),
+                idler=res.idler_conversion(ps, mode=gain_mode, unit=unit), gain_max_db=gmax, gain_min_db=gmin,
+                extinction_db=gmax - gmin, dbeta=np.stack(dbs), first_bad_step=res.first_bad_step, result=res)

@@ -252,6 +252,13 @@ def mid_stage(gain_db=(0.0, 0.0, 0.0, 0.0), phase=(0.0, 0.0, 0.0, 0.0)) -> np.nd
     return _mid_stage("mid_stage", (4, 6), gain_db, phase)
 
 
+def wdm_mid_stage(gain_db, phase) -> np.ndarray:
+    """mid_stage for the multi-channel model's NW = 2 + 2K waves [p1, p2, s_1, i_1, ..., s_K, i_K], K = 1..16:
+    sqrt(10^(gain_db/10)) e^{i phase}.  The last axis is the wave (4, 6, ..., 34 entries); leading axes (one row per sweep
+    point) broadcast."""
+    return _mid_stage("wdm_mid_stage", tuple(range(4, 36, 2)), gain_db, phase)
+
+
 def _run_spans(chain, fibre, cfgs, A0, transfers, length_unit, return_length_unit):
     """The end of both run_concatenated_* functions: the rules the spans' configs and the transfers share, the chain call
     (``chain``: rk4_chain or rk4_chain_single_pump, on A0's waves), the failure and the unit of z_out."""

@@ -15,12 +15,12 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _native
-from ._partition import CHAIN_AXES, PAIRS_AXES, SWEEP_AXES, over_devices
+from ._partition import CHAIN_AXES, PAIRS_AXES, PAIRS_CHAIN_AXES, SWEEP_AXES, over_devices
 from .config import AdaptiveConfig, n_steps_of
 
-__all__ = ["AdaptiveResult", "ChainResult", "FibreSpan", "PairsResult", "SinglePumpChainResult", "SinglePumpResult",
-           "SweepResult", "check_gain", "initial_amplitudes", "rk4_chain", "rk4_chain_single_pump", "rk4_sweep",
-           "rk4_sweep_pairs", "rk4_sweep_single_pump", "rk45_sweep"]
+__all__ = ["AdaptiveResult", "ChainResult", "FibreSpan", "PairsChainResult", "PairsResult", "SinglePumpChainResult",
+           "SinglePumpResult", "SweepResult", "check_gain", "initial_amplitudes", "rk4_chain", "rk4_chain_pairs",
+           "rk4_chain_single_pump", "rk4_sweep", "rk4_sweep_pairs", "rk4_sweep_single_pump", "rk45_sweep"]
 
 
 def initial_amplitudes(p_in, phase_in=None) -> np.ndarray:
@@ -141,6 +141,7 @@ class PairsResult:
     save_every: int
     elapsed_ms: float            # kernel time (hipEvents)
     p_wave_in: Optional[np.ndarray] = None   # (1 | N, NW) |A_j(0)|^2: what pump_depletion compares with
+    traj: Optional[np.ndarray] = None        # (N, n_saved, NW) complex when requested
 
     @property
     def n_pairs(self) -> int:
@@ -186,7 +187,7 @@ class PairsResult:
 
 def rk4_sweep_pairs(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps: Optional[int] = None,
                     save_every: int = 10, check_nan: bool = True, exact_step: Optional[bool] = None, gamma, alpha, a0,
-                    device: int = 0, devices: Optional[Sequence[int]] = None) -> PairsResult:
+                    device: int = 0, devices: Optional[Sequence[int]] = None, want_traj: bool = False) -> PairsResult:
     """Propagate N points of the multi-channel model: two pumps and K = 1..16 signal/idler pairs, waves
     [p1, p2, s_1, i_1, ..., s_K, i_K] (build-defined; K = 1 is the reference's 4-wave system, K = 2 the
     6-wave model).  All channels draw on the same two pumps and shift each other's phase matching through SPM/XPM; FWM
@@ -194,7 +195,9 @@ def rk4_sweep_pairs(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps:
 
     dbeta (N, K): the mismatch of every pair; gamma / alpha a scalar or (N,); a0 (NW,) or (N, NW) complex, NW = 2 + 2K.
     ``dz`` gives n = int(round(z_max/dz)) as integrators.py:194; or pass ``n_steps``.  ``devices=[0, 1, ...]`` splits the
-    points over several GPUs of this process.  Fixed-step float64 only: no trajectory, float32, chain or adaptive form."""
+    points over several GPUs of this process.  ``want_traj`` also returns every saved row (the chain's entry point with one
+    span: the summaries are the same bits).  Fixed-step float64 only: no float32 or adaptive form; concatenated spans
+    (copier - mid-stage - PSA) are rk4_chain_pairs."""
     n_steps, save_every = _fixed_grid(z_max, dz, n_steps, save_every)
     db = np.asarray(dbeta, dtype=float)
     if db.ndim != 2 or not 1 <= db.shape[1] <= _native.MAX_PAIRS:
@@ -205,10 +208,16 @@ def rk4_sweep_pairs(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps:
         raise ValueError(f"a0 must have shape ({nw},) or ({db.shape[0]}, {nw}) for {db.shape[1]} pairs, got {a0.shape}")
     kw = dict(dbeta=db, n_steps=n_steps, z_max=float(z_max), save_every=save_every, gamma=gamma, alpha=alpha, a0=a0,
               check_nan=check_nan, exact_step=exact_step)
-    r = _run(_native.sweep_pairs_host, PAIRS_AXES, db.shape[0], kw, device, devices)
+    if want_traj:   # one span of the chain's entry point: dbeta (1, N, K), gamma / alpha (1,) or (1, N)
+        N = int(db.shape[0])
+        kw.update(dbeta=db[None], n_steps=[kw.pop("n_steps")], seg_len=[kw.pop("z_max")], want_traj=True,
+                  gamma=_span_column([gamma], 1, N, "gamma", np.float64), alpha=_span_column([alpha], 1, N, "alpha", np.float64))
+        r = _run(_native.pairs_chain_host, PAIRS_CHAIN_AXES, N, kw, device, devices)
+    else:
+        r = _run(_native.sweep_pairs_host, PAIRS_AXES, db.shape[0], kw, device, devices)
     p_in = np.abs(np.atleast_2d(a0)) ** 2
     return PairsResult(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"], n_steps, save_every,
-                       r["elapsed_ms"], p_in)
+                       r["elapsed_ms"], p_in, r.get("traj"))
 
 
 # ---- single-pump (degenerate) sweeps: one pump, a signal and an idler ---------------------------------------------------
@@ -347,10 +356,11 @@ def _span_column(values, S: int, N: int, name: str, dtype) -> np.ndarray:
     return np.stack([np.broadcast_to(a, (N,)) for a in arrs]).astype(dtype)
 
 
-def _chain_inputs(spans, a0, transfers, save_every, widths, dtype):
+def _chain_inputs(spans, a0, transfers, save_every, widths, dtype, pairs=False):
     """The span, a0 and transfer rules every chain shares, in rk4_chain's order -> (spans, save_every, dtype, N, n_waves,
     dbeta (S, N), dbeta2 (S, N) for 6 waves else None, gamma, alpha (S,) | (S, N), transfers None | (S-1, n_waves) |
-    (S-1, N, n_waves), n_steps (S,), lengths (S,))."""
+    (S-1, N, n_waves), n_steps (S,), lengths (S,)).  ``pairs``: the multi-channel model, K = (n_waves - 2) / 2 mismatches per
+    span: a span's dbeta is (K,) for every point or (N, K), the returned dbeta (S, N, K), and dbeta2 is an error."""
     spans = list(spans)
     if not spans or not all(isinstance(s, FibreSpan) for s in spans):
         raise ValueError("spans must be a non-empty sequence of FibreSpan")
@@ -366,16 +376,34 @@ def _chain_inputs(spans, a0, transfers, save_every, widths, dtype):
     if a0.ndim not in (1, 2) or a0.shape[-1] not in widths:
         raise ValueError(f"a0 must have shape (n_waves,) or (N, n_waves) with n_waves in {tuple(widths)}")
     nw = int(a0.shape[-1])
-    sizes = {int(np.size(v)) for s in spans for v in (s.dbeta, s.gamma, s.alpha, s.dbeta2) if v is not None}
+    sizes = {int(np.size(v)) for s in spans for v in (s.gamma, s.alpha) + (() if pairs else (s.dbeta, s.dbeta2)) if v is not None}
+    if pairs:
+        K = (nw - 2) // 2
+        if any(s.dbeta2 is not None for s in spans):
+            raise ValueError("the multi-channel model takes its K mismatches in dbeta: dbeta2 must be None")
+        for k, s in enumerate(spans):
+            shape = np.shape(s.dbeta)
+            if len(shape) not in (1, 2) or shape[-1] != K:
+                raise ValueError(f"span {k}: dbeta must have shape ({K},) or (N, {K}) for {K} pairs, got {shape}")
+            if len(shape) == 2:
+                sizes.add(int(shape[0]))
     if a0.ndim == 2:
         sizes.add(int(a0.shape[0]))
     sizes.discard(1)
     if len(sizes) > 1:
         raise ValueError(f"per-point arguments disagree on the number of points: {sorted(sizes)}")
     N = sizes.pop() if sizes else 1
-    dbeta = np.stack([np.broadcast_to(np.asarray(s.dbeta, dtype=dtype).reshape(-1), (N,)) for s in spans])
+    if pairs:
+        for k, s in enumerate(spans):
+            if np.ndim(s.dbeta) == 2 and np.shape(s.dbeta)[0] != N:   # a single (1, K) row among N points
+                raise ValueError(f"span {k}: dbeta must have shape ({K},) or ({N}, {K}), got {np.shape(s.dbeta)}")
+        dbeta = np.stack([np.broadcast_to(np.asarray(s.dbeta, dtype=dtype), (N, K)) for s in spans])
+    else:
+        dbeta = np.stack([np.broadcast_to(np.asarray(s.dbeta, dtype=dtype).reshape(-1), (N,)) for s in spans])
     dbeta2 = None
-    if nw == 6:
+    if pairs:
+        pass
+    elif nw == 6:
         if any(s.dbeta2 is None for s in spans):
             raise ValueError("6 waves: every span needs dbeta2")
         dbeta2 = np.stack([np.broadcast_to(np.asarray(s.dbeta2, dtype=dtype).reshape(-1), (N,)) for s in spans])
@@ -402,17 +430,20 @@ def _chain_inputs(spans, a0, transfers, save_every, widths, dtype):
     return spans, save_every, dtype, N, nw, dbeta, dbeta2, gamma, alpha, tr, steps, lens
 
 
-def _run_chain(host_name: str, widths, spans, a0, transfers, save_every, dtype, a0_dtype, device, devices, **options):
+def _run_chain(host_name: str, widths, spans, a0, transfers, save_every, dtype, a0_dtype, device, devices, pairs=False,
+               **options):
     """What every chain driver does: the shared input rules, the family's host call (looked up in _native when called) over
-    the devices, and the grid of the saved rows -> (outputs, save_every, a0 as passed on, the _ChainGrid fields)."""
-    spans, save_every, dtype, N, nw, dbeta, dbeta2, gamma, alpha, tr, steps, lens = _chain_inputs(spans, a0, transfers,
-                                                                                                  save_every, widths, dtype)
+    the devices, and the grid of the saved rows -> (outputs, save_every, a0 as passed on, the _ChainGrid fields).  ``pairs``:
+    the multi-channel family (_chain_inputs' rules for it, PAIRS_CHAIN_AXES); otherwise the family is the 4/6-wave one where
+    6 is among ``widths`` and the single-pump one where it is not."""
+    spans, save_every, dtype, N, nw, dbeta, dbeta2, gamma, alpha, tr, steps, lens = _chain_inputs(
+        spans, a0, transfers, save_every, widths, dtype, pairs=pairs)
     a0 = np.asarray(a0, dtype=a0_dtype)
     kw = dict(dbeta=dbeta, n_steps=steps, seg_len=lens, save_every=save_every, gamma=gamma, alpha=alpha, a0=a0,
               transfers=tr, **options)
-    if 6 in widths:
+    if 6 in widths and not pairs:   # the 4/6-wave family
         kw.update(dbeta2=dbeta2, dtype=dtype)
-    r = _run(getattr(_native, host_name), CHAIN_AXES, N, kw, device, devices)
+    r = _run(getattr(_native, host_name), PAIRS_CHAIN_AXES if pairs else CHAIN_AXES, N, kw, device, devices)
     rows = steps // save_every + 1
     z0 = np.concatenate([[0.0], np.cumsum(lens)])
     z_out = np.concatenate([z0[k] + np.linspace(0.0, lens[k], int(steps[k]) + 1)[::save_every] for k in range(len(steps))])
@@ -460,6 +491,31 @@ def rk4_chain_single_pump(spans: Sequence[FibreSpan], *, a0, transfers=None, sav
     return SinglePumpChainResult(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"],
                                  int(grid["step_offsets"][-1]), save_every, r["elapsed_ms"], np.abs(np.atleast_2d(a0)) ** 2,
                                  r.get("traj"), **grid)
+
+
+@dataclass
+class PairsChainResult(_ChainGrid, PairsResult):
+    """PairsResult of a chain: rows of every span in order (each span's z = 0 row is the post-transfer state), amplitudes
+    in the physical frame, first_bad_step counted over the whole chain.  n_steps is the chain's total."""
+
+
+def rk4_chain_pairs(spans: Sequence[FibreSpan], *, a0, transfers=None, save_every: int = 10, check_nan: bool = True,
+                    exact_step: Optional[bool] = None, want_traj: bool = False, device: int = 0,
+                    devices: Optional[Sequence[int]] = None) -> PairsChainResult:
+    """Propagate N points of the multi-channel model, waves [p1, p2, s_1, i_1, ..., s_K, i_K], through a chain of fibre
+    spans (psa_rk4_pairs_chain_f64): each span one launch of the multi-channel kernel, every pair's
+    mismatch phase accumulated across spans, ``transfers[s]`` applied between span s and s+1 -- the WDM copier - mid-stage -
+    PSA link, whose channels couple through pump depletion and SPM/XPM.
+
+    a0 (NW,) or (N, NW) complex fixes K = (NW - 2) / 2 in 1..16; a span's dbeta is (K,) for every point or (N, K); transfers:
+    None (identity), or S-1 entries, each (NW,) complex for every point or (N, NW) per point (see
+    simulation.wdm_mid_stage).  Every span's n_steps must be a multiple of ``save_every``; a span with dbeta2 is an error.
+    float64 only."""
+    r, save_every, a0, grid = _run_chain("pairs_chain_host", tuple(range(4, 2 * _native.MAX_PAIRS + 3, 2)), spans, a0, transfers,
+                                         save_every, np.float64, np.complex128, device, devices, pairs=True,
+                                         check_nan=check_nan, exact_step=exact_step, want_traj=want_traj)
+    return PairsChainResult(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"], int(grid["step_offsets"][-1]),
+                            save_every, r["elapsed_ms"], np.abs(np.atleast_2d(a0)) ** 2, r.get("traj"), **grid)
 
 
 # ---- adaptive (RK45) sweeps ----------------------------------------------------------------------------------------

@@ -54,10 +54,10 @@ def static_counts(unit="psa_rk4_pairs.hip", pattern="rk4_sweep_pairs_kernel"):
 def print_static():
     print("# static: VGPRs, scratch, VALU instructions per RK4 step (DPP moves among them) from the gfx950 assembly")
     for name, (vgpr, scratch, valu, dpp) in sorted(static_counts().items()):
-        m = re.search(r"ILi(\d+)ELi(\d)ELi(\d+)ELb([01])E", name)
+        m = re.search(r"ILi(\d+)ELi(\d)ELi(\d+)ELb([01])ELb([01])E", name)
         lanes, check, block, loss = int(m.group(1)), "none block exact".split()[int(m.group(2))], int(m.group(3)), m.group(4) == "1"
         print(f"L={lanes:2d} check={check:5s} block={block:3d} {'lossy   ' if loss else 'lossless'}  VGPRs {vgpr:3d}  scratch {scratch}  "
-              f"VALU/step {valu:6.1f}  (DPP {dpp:5.1f})")
+              f"VALU/step {valu:6.1f}  (DPP {dpp:5.1f}){'  rows' if m.group(5) == '1' else ''}")
     ref = static_counts("psa_rk4_f64.hip", "rk4_sweep_kernelIdLi4ELi2ELb0ELi256ELb0ELb1ELb0E")
     for name, (vgpr, scratch, valu, dpp) in ref.items():
         print(f"4-wave one-lane (check=exact block=256 lossy)  VGPRs {vgpr}  scratch {scratch}  VALU/step {valu:.1f}")
