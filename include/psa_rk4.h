@@ -56,6 +56,8 @@ extern "C" {
 #define PSA_E_TOL        -12  /* psa_rk45_*: rtol < 100*DBL_EPSILON or not finite, atol <= 0 or not finite, h_max <= 0,
                                  first_step < 0 or not finite, max_steps < 1, n_out < 0 */
 #define PSA_E_NPAIRS     -13  /* psa_rk4_sweep_pairs_*: n_pairs outside 1..PSA_MAX_PAIRS */
+#define PSA_E_NLINES     (-14) /* psa_rk4_comb_*: n_lines outside 3..PSA_MAX_LINES (in parentheses, as a negative macro
+                                   value should be; the thirteen above keep the spelling their tests read) */
 
 /* The most points one launch takes: a launch has at most 2^32 - 1 threads in x and the two-lane float64 layout uses two
  * per point.  (2^31 - 256 float64 records are 189 GB: a 288 GB MI355X holds them, so the limit is stated, not theoretical.) */
@@ -63,6 +65,9 @@ extern "C" {
 /* The most signal/idler pairs of the multi-channel sweep (psa_rk4_sweep_pairs_*): one lane per pair, a point within one
  * 16-lane DPP row. */
 #define PSA_MAX_PAIRS    16
+/* The most lines of the multi-line ("comb") sweep (psa_rk4_comb_*): one point per lane with the whole state in registers;
+ * 12 lines are the most that every instantiation holds without scratch memory. */
+#define PSA_MAX_LINES    12
 
 /* ---- flags ----------------------------------------------------------------- */
 /* broadcast: the array has ONE entry used for every sweep point */
@@ -383,7 +388,8 @@ int psa_rk45_sweep_f64_dev(void *stream, int n_waves, int64_t n_points, double z
  *   dA_p1/dz = (-alpha/2 + i gamma (2S - P_p1)) A_p1 + i conj(A_p2) sum_k E_k A_sk A_ik        (p2: p1 <-> p2)
  *   dA_sk/dz = (-alpha/2 + i gamma (2S - P_sk)) A_sk + i conj(A_ik) conj(E_k) A_p1 A_p2        (ik: sk <-> ik)
  * K = 1 is the reference's system (yaman_model.py:123-186), K = 2 the 6-wave model of psa_rk4_sweep_f64.  The channels
- * couple through pump depletion and SPM/XPM only: FWM products between channels (signal-signal mixing) are NOT modelled.
+ * couple through pump depletion and SPM/XPM only: FWM products between channels (signal-signal mixing) are NOT modelled
+ * here, where the detunings are arbitrary; on a uniform frequency grid psa_rk4_comb_f64 below models every one of them.
  * Classic fixed-step RK4 on z_i = i * z_max / n_steps with the save and NaN semantics of psa_rk4_sweep_f64; float64 only.
  * One lane per pair, L = the power of two >= K (at least 2) lanes per point: K = 5 pays for 8 lanes.
  *   dbeta       [N][n_pairs]            mismatch of every pair, 1/length
@@ -463,6 +469,46 @@ int psa_rk4_single_pump_f32_dev(void *stream, int64_t n_points, int64_t n_steps,
                                 const float *d_dbeta, const float *d_gamma, const float *d_alpha,
                                 const float *d_a0_soa, uint32_t flags, float *d_a_end_soa, float *d_p_wave_end_soa,
                                 float *d_p_wave_max_soa, int64_t *d_first_bad_step, float *d_traj_soa_or_null);
+
+/* ---- the multi-line ("frequency comb") sweep: M = n_lines equally spaced lines and EVERY FWM product among them ----------
+ * Build-defined, no reference counterpart: lines m = 0..M-1 at w_0 + m dw, ascending in frequency,
+ * 3 <= M <= PSA_MAX_LINES, the field of line m being A_m e^{i kappa_m z}.  With u_m(z) = exp(i kappa_m z), B_m = A_m u_m,
+ *   C_d = sum_n B_{n+d} conj(B_n)      (both indices inside 0..M-1; C_{-d} = conj(C_d), C_0 = sum |B|^2)
+ *   S_m = sum_l B_l C_{m-l}            (= sum over every ordered triple k + l - n = m of B_k B_l conj(B_n))
+ *   dA_m/dz = -alpha/2 A_m + i gamma conj(u_m) S_m
+ * S_m holds SPM/XPM ((2 sum_j P_j - P_m) B_m), pump-pump, pump-signal and signal-signal mixing; products that fall outside
+ * the grid are dropped.  kappa_m is the line's propagation constant in any gauge: kappa_m + a + b m is the same system, only
+ * kappa_k + kappa_l - kappa_n - kappa_m ever acts.  For alpha = 0 the model conserves sum P_m and sum m P_m.  M = 3 is
+ * psa_rk4_single_pump_f64 with lines [0, 1, 2] = waves [s, p, i] and kappa_0 + kappa_2 - 2 kappa_1 = dbeta.
+ * Classic fixed-step RK4 on z_i = i * z_max / n_steps with the save semantics of psa_rk4_sweep_f64; float64, one sweep
+ * point per lane.
+ *   kappa       [N][M]                  propagation constant of every line, 1/length
+ *   gamma, alpha  [N] | [1]
+ *   a0_re_im    [N][M][2] | [1][M][2]
+ *   a_end_re_im [N][M][2]   state at the last saved row
+ *   p_wave_end  [N][M]      |A_m|^2 at that row
+ *   p_wave_max  [N][M]      max of |A_m|^2 over the saved rows incl. z = 0, NaN-propagating like np.max
+ *   first_bad_step [N]      with PSA_OPT_CHECK_NAN the EXACT index of the first step that left the point non-finite (the
+ *                           point is tested after every step; PSA_OPT_EXACT_STEP is accepted and changes nothing), else -1
+ *   traj_or_null [N][n_saved][M][2]  every saved row, or NULL
+ * The four summary outputs are always written.  flags: PSA_BCAST_GAMMA / ALPHA / A0, PSA_OPT_CHECK_NAN, PSA_OPT_EXACT_STEP,
+ * PSA_OPT_LOSSLESS (set by the host form itself for a broadcast alpha == 0), PSA_OPT_BLOCK64 and, on the `_dev` form only,
+ * PSA_OPT_TRAJ_LD; anything else (a layout, float32 or LDS flag) is PSA_E_FLAGS.  n_lines outside 3..PSA_MAX_LINES:
+ * PSA_E_NLINES, checked first; then the rules, codes and order of psa_rk4_single_pump_f64 with M in place of 3 (a trajectory
+ * whose leading dimension ld has ld * 16 >= 2^32, or that does not fit the device's free memory: PSA_E_TOO_LARGE).  All of it
+ * is checked before any device call; n_points == 0 is a successful no-op.  There is no float32, adaptive or chain form.
+ */
+int psa_rk4_comb_f64(int device, int n_lines, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+                     const double *kappa, const double *gamma, const double *alpha, const double *a0_re_im,
+                     uint32_t flags, double *a_end_re_im, double *p_wave_end, double *p_wave_max,
+                     int64_t *first_bad_step, double *traj_or_null, double *elapsed_ms_or_null);
+/* On device buffers, asynchronous on `stream`, no allocation and no synchronisation: d_kappa_soa [M][N], d_a0_soa
+ * [2M][N | 1], d_a_end_soa [2M][N], d_p_wave_end_soa / d_p_wave_max_soa [M][N], d_first_bad_step [N], d_traj_soa_or_null
+ * [n_saved][M][ld][2] with ld = N, or psa_traj_ld(N, 8) with PSA_OPT_TRAJ_LD. */
+int psa_rk4_comb_f64_dev(void *stream, int n_lines, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+                         const double *d_kappa_soa, const double *d_gamma, const double *d_alpha,
+                         const double *d_a0_soa, uint32_t flags, double *d_a_end_soa, double *d_p_wave_end_soa,
+                         double *d_p_wave_max_soa, int64_t *d_first_bad_step, double *d_traj_soa_or_null);
 
 /* ---- a chain of single-pump spans with mid-stage transfers (copier - mid-stage - PSA on one pump) ------------------------
  * psa_rk4_chain_* for the three-wave model above: S = n_segments >= 1 spans, each ONE launch of the

@@ -41,6 +41,7 @@ OPT_TRAJ_LD = 1 << 17
 OPT_QUAD_POINT = 1 << 18
 MAX_POINTS = 2**31 - 256          # PSA_MAX_POINTS: the most points one launch takes
 MAX_PAIRS = 16                    # PSA_MAX_PAIRS: the most signal/idler pairs of the multi-channel sweep
+MAX_LINES = 12                    # PSA_MAX_LINES: the most lines of the multi-line ("comb") sweep
 
 # every symbol the header declares, with (restype, argtypes)
 _P, _I, _L, _D, _I32, _U32 = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_int32, C.c_uint32
@@ -82,6 +83,8 @@ _SIGS = {
               host_types=("f64",), dev_types=("f64",)),
     # N, n_steps, z_max, save_every, dbeta, gamma, alpha, a0, flags, a_end, p_wave_end, p_wave_max, first_bad, traj; host: elapsed_ms
     **_family("psa_rk4_single_pump", [_L, _L, _D, _I32] + [_P] * 4 + [_U32] + [_P] * 5, host=[_P]),
+    # n_lines, N, n_steps, z_max, save_every, kappa, gamma, alpha, a0, flags, a_end, p_wave_end, p_wave_max, first_bad, traj; host: elapsed_ms
+    **_family("psa_rk4_comb", [_I, _L, _L, _D, _I32] + [_P] * 4 + [_U32] + [_P] * 5, host=[_P], host_types=("f64",), dev_types=("f64",)),
     # N, S, n_steps[S], seg_len[S], save_every, dbeta, gamma, alpha, a0, transfer, flags, a_end, p_wave_end, p_wave_max, first_bad,
     # traj; host: elapsed_ms; dev: workspace
     **_family("psa_rk4_single_pump_chain", [_L, _I, _P, _P, _I32] + [_P] * 5 + [_U32] + [_P] * 5, host=[_P], dev=[_P],
@@ -350,7 +353,8 @@ def sweep_waves_device(*, stream: int, n_waves: int, n_points: int, n_steps: int
 def sweep_pairs_host(dbeta, *, n_steps: int, z_max: float, save_every: int, gamma, alpha, a0, check_nan: bool = True,
                      exact_step: Optional[bool] = None, device: int = 0, extra_flags: int = 0) -> dict:
     """N independent propagations of two pumps and K signal/idler pairs on the GPU (psa_rk4_sweep_pairs_f64; host buffers
-    in and out, float64).  The channels couple through pump depletion and SPM/XPM; signal-signal FWM is not modelled.
+    in and out, float64).  The channels couple through pump depletion and SPM/XPM; signal-signal FWM is not modelled
+    here (on a uniform frequency grid, comb_host models every product).
 
     dbeta (N, K) with 1 <= K <= 16; gamma / alpha scalar or (N,); a0 (NW,) or (N, NW) complex, NW = 2 + 2K, waves
     [p1, p2, s_1, i_1, ..., s_K, i_K].  exact_step None or True: the exact first_bad_step; False: the save block's last step.
@@ -422,6 +426,44 @@ def single_pump_device(*, stream: int, n_points: int, n_steps: int, z_max: float
     _check(_fn("psa_rk4_single_pump", _dtypes(dtype)[2], dev=True)(
         stream or None, int(n_points), int(n_steps), float(z_max), int(save_every), d_dbeta or None, d_gamma or None,
         d_alpha or None, d_a0_soa or None, int(flags), d_a_end_soa or None, d_p_wave_end_soa or None,
+        d_p_wave_max_soa or None, d_first_bad or None, d_traj_soa or None))
+
+
+def comb_host(kappa, *, n_steps: int, z_max: float, save_every: int, gamma, alpha, a0, check_nan: bool = True,
+              want_traj: bool = False, device: int = 0, extra_flags: int = 0) -> dict:
+    """N independent propagations of the multi-line ("comb") model on the GPU (psa_rk4_comb_f64; host buffers in and out,
+    float64): M equally spaced lines, ascending in frequency, with every FWM product among them that falls on the grid.
+
+    kappa (N, M) with 3 <= M <= 12, the lines' propagation constants in any gauge; gamma / alpha scalar or (N,); a0 (M,) or
+    (N, M) complex.  With check_nan first_bad_step is the exact step index (the point is tested after every step).
+    Returns a_end (N, M) complex, p_wave_end, p_wave_max (N, M), first_bad_step (N,) int64, traj (N, n_saved, M) complex or
+    None, elapsed_ms (kernel only)."""
+    kappa = np.ascontiguousarray(np.asarray(kappa), dtype=np.float64)
+    if kappa.ndim != 2 or not 3 <= kappa.shape[1] <= MAX_LINES:
+        raise ValueError(f"kappa must have shape (N, M) with 3 <= M <= {MAX_LINES}, got {kappa.shape}")
+    N, M = (int(x) for x in kappa.shape)
+    flags, gamma, alpha, a0, _ = _point_inputs(N, np.float64, np.complex128, int(extra_flags), gamma, alpha, a0, (M,))
+    flags |= _check_flags(check_nan, None)
+    n_saved = int(n_steps) // int(save_every) + 1 if save_every > 0 else 0
+    a_end = np.empty((N, M), dtype=np.complex128)
+    w_end = np.empty((N, M), dtype=np.float64)
+    w_max = np.empty((N, M), dtype=np.float64)
+    bad = np.empty(N, dtype=np.int64)
+    traj = np.empty((N, n_saved, M), dtype=np.complex128) if want_traj else None
+    ms = C.c_double(0.0)
+    _check(_fn("psa_rk4_comb")(int(device), M, N, int(n_steps), float(z_max), int(save_every), _ptr(kappa), _ptr(gamma),
+                               _ptr(alpha), _ptr(a0), flags, _ptr(a_end), _ptr(w_end), _ptr(w_max), _ptr(bad), _ptr(traj),
+                               C.cast(C.byref(ms), _P)))
+    return dict(a_end=a_end, p_wave_end=w_end, p_wave_max=w_max, first_bad_step=bad, traj=traj, elapsed_ms=ms.value)
+
+
+def comb_device(*, stream: int, n_lines: int, n_points: int, n_steps: int, z_max: float, save_every: int, d_kappa_soa: int,
+                d_gamma: int, d_alpha: int, d_a0_soa: int, flags: int, d_a_end_soa: int, d_p_wave_end_soa: int,
+                d_p_wave_max_soa: int, d_first_bad: int, d_traj_soa: int = 0) -> None:
+    """Asynchronous multi-line launch on device pointers (ints), SoA layout -- see psa_rk4_comb_f64_dev."""
+    _check(_fn("psa_rk4_comb", dev=True)(
+        stream or None, int(n_lines), int(n_points), int(n_steps), float(z_max), int(save_every), d_kappa_soa or None,
+        d_gamma or None, d_alpha or None, d_a0_soa or None, int(flags), d_a_end_soa or None, d_p_wave_end_soa or None,
         d_p_wave_max_soa or None, d_first_bad or None, d_traj_soa or None))
 
 

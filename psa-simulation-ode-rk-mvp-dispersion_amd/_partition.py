@@ -11,6 +11,7 @@ import numpy as np
 # Per-point arguments of each entry point: name -> (axis of the points, ndim of the per-point form).
 SWEEP_AXES = {"dbeta": (0, 1), "dbeta2": (0, 1), "gamma": (0, 1), "alpha": (0, 1), "a0": (0, 2)}
 PAIRS_AXES = {"dbeta": (0, 2), "gamma": (0, 1), "alpha": (0, 1), "a0": (0, 2)}
+COMB_AXES = {"kappa": (0, 2), "gamma": (0, 1), "alpha": (0, 1), "a0": (0, 2)}
 CHAIN_AXES = {"dbeta": (1, 2), "dbeta2": (1, 2), "gamma": (1, 2), "alpha": (1, 2), "a0": (0, 2), "transfers": (1, 3)}
 PAIRS_CHAIN_AXES = {"dbeta": (1, 3), "gamma": (1, 2), "alpha": (1, 2), "a0": (0, 2), "transfers": (1, 3)}
 

@@ -95,6 +95,17 @@ struct SinglePumpCall {   // psa_rk4_single_pump_f64*, psa_rk4_single_pump_f32* 
     int64_t *first_bad;
     T *traj;
 };
+struct CombCall {    // psa_rk4_comb_f64*
+    int n_lines;
+    int64_t n_points, n_steps;
+    double z_max;
+    int32_t save_every;
+    const double *kappa, *gamma, *alpha, *a0;
+    uint32_t flags;
+    double *a_end, *wave_end, *wave_max;
+    int64_t *first_bad;
+    double *traj;
+};
 struct Rk45Call {    // psa_rk45_sweep_f64*
     int n_waves;
     int64_t n_points;
@@ -185,11 +196,10 @@ int validate_common(const SweepCall<T> &c) {
     return PSA_OK;
 }
 
-// What SweepArgs, AdaptiveArgs and PairsArgs share (they agree on the field names): the per-point inputs with the strides the
-// PSA_BCAST_* bits select, a_end, n_points and z_max.
+// What the argument structs of every family share (they agree on the field names): gamma, alpha and a0 with the strides the
+// PSA_BCAST_* bits select, a_end, n_points and z_max ...
 template <typename Args, typename Call>
-void fill_point_args(Args &a, const Call &c) {
-    a.dbeta = c.dbeta;
+void fill_shared_args(Args &a, const Call &c) {
     a.gamma = c.gamma;
     a.alpha = c.alpha;
     a.a0 = c.a0;
@@ -200,6 +210,12 @@ void fill_point_args(Args &a, const Call &c) {
     a.alpha_stride = (c.flags & PSA_BCAST_ALPHA) ? 0 : 1;
     a.a0_stride = (c.flags & PSA_BCAST_A0) ? 0 : 1;
     a.a0_ld = (c.flags & PSA_BCAST_A0) ? 1 : c.n_points;
+}
+// ... and, for SweepArgs, AdaptiveArgs, PairsArgs and SinglePumpArgs, the mismatch
+template <typename Args, typename Call>
+void fill_point_args(Args &a, const Call &c) {
+    a.dbeta = c.dbeta;
+    fill_shared_args(a, c);
 }
 
 // The reference's alpha == 0.0 branch: a broadcast alpha (host pointer) of 0 selects PSA_OPT_LOSSLESS.
@@ -725,6 +741,74 @@ int single_pump_host(int device, const SinglePumpCall<T> &c, double *elapsed_ms)
     };
     return host_call<T>(device, "the single-pump RK4 sweep", elapsed_ms, layout,
                              [&](hipStream_t st) { return single_pump_dev(st, d); });
+}
+
+// ---- the multi-line ("comb") sweep (psa_rk4_comb_f64*): n_lines equally spaced lines, every FWM product among them ------
+// host_form as in validate_single_pump, whose order this is with n_lines in front.
+int validate_comb(const CombCall &c, bool host_form) {
+    if (c.n_lines < 3 || c.n_lines > PSA_MAX_LINES)
+        return fail(PSA_E_NLINES, "n_lines must be in [3, %d], got %d", PSA_MAX_LINES, c.n_lines);
+    int rc = validate_grid(c.n_points, PSA_MAX_POINTS, 0, c.n_steps, c.z_max, c.save_every);
+    if (rc != PSA_OK) return rc;
+    const uint32_t accepted = PSA_BCAST_GAMMA | PSA_BCAST_ALPHA | PSA_BCAST_A0 | PSA_OPT_CHECK_NAN | PSA_OPT_EXACT_STEP |
+                              PSA_OPT_LOSSLESS | PSA_OPT_BLOCK64 | (host_form ? 0u : PSA_OPT_TRAJ_LD);
+    if (c.flags & ~accepted)
+        return fail(PSA_E_FLAGS, "the multi-line sweep takes the BCAST bits, CHECK_NAN, EXACT_STEP, LOSSLESS, BLOCK64 and (its "
+                                 "_dev form) TRAJ_LD only (no layout, float32 or LDS flag): 0x%x", (unsigned)(c.flags & ~accepted));
+    if (c.n_points > 0 && (!c.kappa || !c.gamma || !c.alpha || !c.a0 || !c.a_end || !c.wave_end || !c.wave_max || !c.first_bad))
+        return fail(PSA_E_NULLPTR, "a required buffer pointer is NULL");
+    if (c.traj) {
+        // trajectory rows are addressed as a wave-uniform (row, line) base + the lane's 32-bit byte offset
+        const bool padded = host_form || (c.flags & PSA_OPT_TRAJ_LD);
+        const unsigned long long ld = (unsigned long long)(padded ? traj_ld_of(c.n_points, sizeof(double)) : c.n_points);
+        if (ld * 16ull >= (1ull << 32))
+            return fail(PSA_E_TOO_LARGE, "a multi-line trajectory launch takes a leading dimension below 2^28 points, got %llu", ld);
+    }
+    return PSA_OK;
+}
+
+int comb_dev(void *stream, const CombCall &c) {
+    int rc = validate_comb(c, false);
+    if (rc != PSA_OK) return rc;
+    if (c.n_points == 0) return PSA_OK;
+    psa::CombArgs a;
+    fill_shared_args(a, c);
+    a.kappa = c.kappa;
+    a.p_wave_end = c.wave_end;
+    a.p_wave_max = c.wave_max;
+    a.first_bad = (long long *)c.first_bad;
+    a.traj = c.traj;
+    a.traj_ld = (c.flags & PSA_OPT_TRAJ_LD) ? traj_ld_of(c.n_points, sizeof(double)) : c.n_points;
+    a.n_steps = (int)c.n_steps;
+    a.save_every = c.save_every;
+    a.n_lines = c.n_lines;
+    hipError_t e = psa::launch_sweep_comb_f64((hipStream_t)stream, c.flags, a);
+    if (e != hipSuccess) return hip_fail(e, "rk4_sweep_comb launch");
+    return PSA_OK;
+}
+
+int comb_host(int device, const CombCall &c, double *elapsed_ms) {
+    int rc = validate_comb(c, true);
+    if (rc != PSA_OK) return rc;
+    if (elapsed_ms) *elapsed_ms = 0.0;
+    if (c.n_points == 0) return PSA_OK;
+    const int M = c.n_lines;
+    const size_t N = (size_t)c.n_points;
+    CombCall d = c;
+    if (c.traj) d.flags |= PSA_OPT_TRAJ_LD;   // the device-side trajectory has its own leading dimension; the caller's is dense
+    d.flags |= lossless_bit(c.flags, c.alpha);
+    auto layout = [&](Staging<double> &sg) {
+        d.kappa = sg.input_soa(c.kappa, N, M);                      // [N][M] -> [M][N]
+        d.gamma = sg.input(c.gamma, (c.flags & PSA_BCAST_GAMMA) ? 1 : N);
+        d.alpha = sg.input(c.alpha, (c.flags & PSA_BCAST_ALPHA) ? 1 : N);
+        d.a0 = sg.input_soa(c.a0, (c.flags & PSA_BCAST_A0) ? 1 : N, 2 * M);
+        d.a_end = sg.output_soa(c.a_end, N, 2 * M);
+        d.wave_end = sg.output_soa(c.wave_end, N, M);
+        d.wave_max = sg.output_soa(c.wave_max, N, M);
+        d.first_bad = sg.output(c.first_bad, N);
+        d.traj = sg.trajectory(c.traj, N, (size_t)(c.n_steps / c.save_every + 1), 2 * M);
+    };
+    return host_call<double>(device, "the multi-line RK4 sweep", elapsed_ms, layout, [&](hipStream_t st) { return comb_dev(st, d); });
 }
 
 // ---- fibre chains: S spans, one sweep launch + one epilogue (psa_chain.hip) each ------------------------------------
@@ -1623,5 +1707,20 @@ int psa_rk4_pairs_chain_f64_dev(void *stream, int n_pairs, int64_t n_points, int
                                         n_segments, n_steps, seg_len, d_transfer_soa, d_workspace});
 }
 int64_t psa_rk4_pairs_chain_workspace_bytes(int n_pairs, int64_t n_points) { return pairs_chain_workspace_bytes(n_pairs, n_points); }
+
+int psa_rk4_comb_f64(int device, int n_lines, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+                     const double *kappa, const double *gamma, const double *alpha, const double *a0_re_im, uint32_t flags,
+                     double *a_end_re_im, double *p_wave_end, double *p_wave_max, int64_t *first_bad_step, double *traj_or_null,
+                     double *elapsed_ms_or_null) {
+    return comb_host(device, {n_lines, n_points, n_steps, z_max, save_every, kappa, gamma, alpha, a0_re_im, flags, a_end_re_im,
+                              p_wave_end, p_wave_max, first_bad_step, traj_or_null}, elapsed_ms_or_null);
+}
+int psa_rk4_comb_f64_dev(void *stream, int n_lines, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+                         const double *d_kappa_soa, const double *d_gamma, const double *d_alpha, const double *d_a0_soa,
+                         uint32_t flags, double *d_a_end_soa, double *d_p_wave_end_soa, double *d_p_wave_max_soa,
+                         int64_t *d_first_bad_step, double *d_traj_soa_or_null) {
+    return comb_dev(stream, {n_lines, n_points, n_steps, z_max, save_every, d_kappa_soa, d_gamma, d_alpha, d_a0_soa, flags,
+                             d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step, d_traj_soa_or_null});
+}
 
 }  // extern "C"

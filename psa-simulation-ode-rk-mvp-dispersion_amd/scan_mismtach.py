@@ -656,7 +656,8 @@ def scan_wdm_gain(*, cfg: SimulationConfig, lambda_p1_m: float, lambda_p2_m: flo
     """A dual-pump amplifier carrying K = 1..16 channels at once (no reference counterpart): waves
     [p1, p2, s_1, i_1, ..., s_K, i_K], channel k at omega_c +- Omega_k with dbeta_k = delta_beta_symmetric(omega_d, Omega_k)
     as scan_six_wave_grid computes its two.  All channels draw on the same two pumps and shift each other's phase matching
-    through XPM; FWM products between channels (signal-signal mixing) are not modelled.
+    through XPM; FWM products between channels (signal-signal mixing) are not modelled here (scan_comb_gain models them on
+    a uniform frequency grid).
 
     The N sweep points are input-power settings: p_signal (K,) is one point, (N, K) is N of them; p_idler a scalar, (K,)
     or (N, K); p_pump (2,); phase_in None or NW = 2 + 2K phases.  One launch of the multi-channel kernel
@@ -766,6 +767,43 @@ def scan_single_pump_gain(*, cfg: SimulationConfig, lambda_pump_m: float, lambda
     return dict(gain=nan(res.signal_gain(p0[1], mode=gain_mode, unit=unit)),
                 idler=nan(res.idler_conversion(p0[1], mode=gain_mode, unit=unit)), pump_depletion=nan(res.pump_depletion()),
                 dbeta=nan(db) * pre["scale"], first_bad_step=res.first_bad_step, result=res)
+
+
+def scan_comb_gain(*, cfg: SimulationConfig, lambda_center_m: float, line_spacing: float, p_lines,
+                   phase_in: Optional[Sequence[float]] = None, gamma: float, alpha: float, dispersion: DispersionParams,
+                   max_order: int = 4, length_unit: str = "m", gain_unit: str = "dB", gain_mode: GainMode = "max",
+                   device: Optional[int] = None, devices: Optional[Sequence[int]] = None) -> dict:
+    """A multi-line ("comb") parametric amplifier (no reference counterpart): M = 3..12 lines at omega_c + (m - (M-1)/2) *
+    line_spacing (rad/s), omega_c from lambda_center_m, ascending in frequency, coupled by EVERY four-wave-mixing product
+    that falls on the grid: inter-channel crosstalk, the cascaded pump products at 2 w_1 - w_2 and 2 w_2 - w_1, higher-order
+    idlers.  b_m is the Taylor sum of ``dispersion`` over the orders 2..max_order at line m and kappa_m = b_m - [b_0 +
+    (b_{M-1} - b_0) * m / (M-1)] (simulation.comb_lines): the large beta_1 phase never reaches a sincos.
+
+    The N sweep points are input-power settings: p_lines (M,) is one point, (N, M) is N of them (a dark line is 0 W);
+    phase_in None or M phases.  One launch of the multi-line kernel (sweep.rk4_sweep_comb) on ``device``, or split over
+    ``devices``; sharding over a ``torch.distributed`` process group is out of scope here -- every rank would run the whole
+    sweep -- and so are float32, RK45, chains and non-uniform grids.
+
+    Returns dict(gain (N, M) of every line over its input power -- NaN for a line with zero input --, p_end, p_max (N, M),
+    kappa (M,) in 1/length_unit, omega (M,), first_bad_step (N,), result=CombResult)."""
+    from .frequency_plan import omega_from_lambda
+    from .simulation import _comb_phases, _comb_powers, comb_lines
+    from .sweep import initial_amplitudes, rk4_sweep_comb
+    unit = check_gain(gain_mode, gain_unit)
+    p = np.atleast_2d(_comb_powers(p_lines, "p_lines"))
+    N, M = (int(x) for x in p.shape)
+    ph = _comb_phases(phase_in, M)
+    if dispersion is None:
+        raise ValueError("dispersion must be provided")
+    pre = _prepare(cfg, gamma=gamma, alpha=alpha, dispersion=dispersion, phase_matching_cfg=None, beta_legacy=None,
+                   length_unit=length_unit)
+    fiber, grid = pre["fiber"], pre["grid"]
+    omega, kappa, _ = comb_lines(omega_from_lambda(lambda_center_m), line_spacing, M, fiber.dispersion, max_order=max_order)
+    res = rk4_sweep_comb(np.broadcast_to(kappa, (N, M)), z_max=fiber.length_m, n_steps=n_steps_of(fiber.length_m, grid.dz_m),
+                         save_every=cfg.save_every, check_nan=bool(cfg.check_nan), gamma=fiber.gamma_W_m, alpha=fiber.alpha_1_m,
+                         a0=initial_amplitudes(p, ph), device=(0 if device is None else int(device)), devices=devices)
+    return dict(gain=res.line_gain(p, mode=gain_mode, unit=unit), p_end=res.p_wave_end, p_max=res.p_wave_max,
+                kappa=kappa * pre["scale"], omega=omega, first_bad_step=res.first_bad_step, result=res)
 
 
 def _phase_scan_axes(phase, psa_delta_beta):

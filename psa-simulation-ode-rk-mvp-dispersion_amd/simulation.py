@@ -13,13 +13,14 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import constants
+from ._native import MAX_LINES
 from .config import (AdaptiveConfig, SimulationConfig, custom_simulation_config, default_simulation_config,  # noqa: F401
                      n_steps_of, validate_config)
 from .dispersion import DispersionParams, delta_beta_from_omegas_array
 from .integrators import integrate_adaptive, integrate_interval
 from .parameters import FiberParams, PhaseMatchingParams, SimulationGrid, WavesParams, make_model_params
 from .phase_matching import PhaseMatchingConfig, PhaseMatchingMethod, PhaseMatchingResult, compute_phase_mismatch  # noqa: F401
-from .sweep import FibreSpan, initial_amplitudes, rk4_chain, rk4_chain_single_pump, rk4_sweep_single_pump
+from .sweep import FibreSpan, initial_amplitudes, rk4_chain, rk4_chain_single_pump, rk4_sweep_comb, rk4_sweep_single_pump
 from .yaman_model import rhs_yaman_simplified
 
 _UNITS = {"m": 1.0, "km": 1000.0}
@@ -234,6 +235,91 @@ def run_single_pump_simulation(cfg: SimulationConfig, *, gamma: float, alpha: fl
         raise FloatingPointError(f"NaN or Inf detected at step {bad}, z = {z_m[bad]}")
     out_unit = length_unit if return_length_unit is None else return_length_unit
     return z_m[::int(cfg.save_every)] / _length_scale_to_m(out_unit), r.traj[0]
+
+
+# ---- multi-line ("comb") amplifier: M equally spaced lines, every FWM product among them ------------------------------------
+def comb_lines(omega_center: float, line_spacing: float, n_lines: int, dispersion: DispersionParams, *,
+               max_order: int = 4) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The lines of a comb -> (omega (M,), kappa (M,), b (M,)): line m at omega_center + (m - (M-1)/2) * line_spacing, b_m the
+    Taylor sum of ``dispersion`` over the orders 2..max_order at that frequency and kappa_m = b_m - [b_0 + (b_{M-1} - b_0) *
+    m / (M-1)], the same propagation constants in the gauge where the two outer lines have none.  beta_0 and beta_1 cancel in
+    every product k + l - n = m, so they are left out rather than cancelled: the large beta_1 phase never reaches a sincos."""
+    from math import factorial
+    M = int(n_lines)
+    if not 3 <= M <= MAX_LINES:
+        raise ValueError(f"a comb has 3..{MAX_LINES} lines, got {M}")
+    wc, dw = _positive_omega(omega_center, "omega_center"), float(line_spacing)
+    if not np.isfinite(dw) or dw <= 0.0:
+        raise ValueError("line_spacing must be positive and finite (rad/s)")
+    if not isinstance(max_order, int):
+        raise TypeError("max_order must be int")
+    if max_order < 2:
+        raise ValueError("max_order must be >= 2")
+    if dispersion is None:
+        raise ValueError("dispersion must be provided")
+    m = np.arange(M, dtype=float)
+    omega = wc + (m - 0.5 * (M - 1)) * dw
+    if omega[0] <= 0.0:
+        raise ValueError("the lowest line's frequency must be positive")
+    x = omega - dispersion.omega_ref
+    b = np.zeros(M)
+    for n in range(2, max_order + 1):
+        bn = dispersion.get_beta_n(n)
+        if bn != 0.0:
+            b = b + bn * (x**n) / float(factorial(n))
+    kappa = b - (b[0] + (b[-1] - b[0]) * m / (M - 1))
+    if not np.all(np.isfinite(kappa)):
+        raise ValueError("the lines' propagation constants are not finite")
+    return omega, kappa, b
+
+
+def _comb_powers(p, name: str) -> np.ndarray:
+    arr = np.asarray(p, dtype=float)
+    if arr.ndim not in (1, 2) or arr.size == 0 or not 3 <= arr.shape[-1] <= MAX_LINES:
+        raise ValueError(f"{name} must have shape (M,) or (N, M) with 3 <= M <= {MAX_LINES}, got {arr.shape}")
+    if not np.all(np.isfinite(arr)) or np.any(arr < 0.0):
+        raise ValueError(f"{name} must hold finite non-negative powers (W)")
+    return arr
+
+
+def _comb_phases(phase_in, M: int) -> Optional[np.ndarray]:
+    if phase_in is None:
+        return None
+    ph = np.asarray(phase_in, dtype=float)
+    if ph.shape != (M,) or not np.all(np.isfinite(ph)):
+        raise ValueError(f"phase_in must hold {M} finite phases")
+    return ph
+
+
+def run_comb_simulation(cfg: SimulationConfig, *, gamma: float, alpha: float, omega_center: float, line_spacing: float,
+                        p_in: Sequence[float], phase_in: Optional[Sequence[float]] = None, dispersion: DispersionParams,
+                        max_order: int = 4, length_unit: str = "m") -> tuple[np.ndarray, np.ndarray]:
+    """One propagation of the multi-line ("comb") model on the GPU -> (z_out in ``length_unit``, A complex128 (n_saved, M)):
+    M = len(p_in) = 3..12 lines at omega_center + (m - (M-1)/2) * line_spacing (rad/s), ascending in frequency, with every
+    FWM product among them (no reference counterpart; see comb_lines for the propagation constants).
+    Validation, units and the failure behaviour are run_single_simulation's: with cfg.check_nan a non-finite state raises
+    FloatingPointError at its step."""
+    validate_config(cfg)
+    _length_scale_to_m(length_unit)
+    p = _comb_powers(p_in, "p_in")
+    if p.ndim != 1:
+        raise ValueError(f"p_in must have shape (M,), got {p.shape}")
+    M = int(p.shape[0])
+    A0 = initial_amplitudes(p, _comb_phases(phase_in, M))
+    if dispersion is None:
+        raise ValueError("dispersion must be provided")
+    pre = _prepare(cfg, gamma=gamma, alpha=alpha, dispersion=dispersion, phase_matching_cfg=None, beta_legacy=None,
+                   length_unit=length_unit)
+    fiber, grid = pre["fiber"], pre["grid"]
+    _, kappa, _ = comb_lines(omega_center, line_spacing, M, fiber.dispersion, max_order=max_order)
+    n_steps = n_steps_of(fiber.length_m, grid.dz_m)
+    r = rk4_sweep_comb(kappa[None, :], z_max=fiber.length_m, n_steps=n_steps, save_every=int(cfg.save_every),
+                       check_nan=bool(cfg.check_nan), gamma=fiber.gamma_W_m, alpha=fiber.alpha_1_m, a0=A0, want_traj=True)
+    z_m = np.linspace(0.0, fiber.length_m, n_steps + 1)
+    bad = int(r.first_bad_step[0])
+    if cfg.check_nan and bad >= 0:
+        raise FloatingPointError(f"NaN or Inf detected at step {bad}, z = {z_m[bad]}")
+    return z_m[::int(cfg.save_every)] / pre["scale"], r.traj[0]
 
 
 # ---- concatenated spans (copier - mid-stage - PSA chains) ------------------------------------------------------------

@@ -15,12 +15,12 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _native
-from ._partition import CHAIN_AXES, PAIRS_AXES, PAIRS_CHAIN_AXES, SWEEP_AXES, over_devices
+from ._partition import CHAIN_AXES, COMB_AXES, PAIRS_AXES, PAIRS_CHAIN_AXES, SWEEP_AXES, over_devices
 from .config import AdaptiveConfig, n_steps_of
 
-__all__ = ["AdaptiveResult", "ChainResult", "FibreSpan", "PairsChainResult", "PairsResult", "SinglePumpChainResult",
+__all__ = ["AdaptiveResult", "ChainResult", "CombResult", "FibreSpan", "PairsChainResult", "PairsResult", "SinglePumpChainResult",
            "SinglePumpResult", "SweepResult", "check_gain", "initial_amplitudes", "rk4_chain", "rk4_chain_pairs",
-           "rk4_chain_single_pump", "rk4_sweep", "rk4_sweep_pairs", "rk4_sweep_single_pump", "rk45_sweep"]
+           "rk4_chain_single_pump", "rk4_sweep", "rk4_sweep_comb", "rk4_sweep_pairs", "rk4_sweep_single_pump", "rk45_sweep"]
 
 
 def initial_amplitudes(p_in, phase_in=None) -> np.ndarray:
@@ -191,7 +191,8 @@ def rk4_sweep_pairs(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps:
     """Propagate N points of the multi-channel model: two pumps and K = 1..16 signal/idler pairs, waves
     [p1, p2, s_1, i_1, ..., s_K, i_K] (build-defined; K = 1 is the reference's 4-wave system, K = 2 the
     6-wave model).  All channels draw on the same two pumps and shift each other's phase matching through SPM/XPM; FWM
-    products between channels (signal-signal mixing) are NOT modelled.
+    products between channels (signal-signal mixing) are NOT modelled here, where the detunings are arbitrary: on a uniform
+    frequency grid rk4_sweep_comb models every one of them.
 
     dbeta (N, K): the mismatch of every pair; gamma / alpha a scalar or (N,); a0 (NW,) or (N, NW) complex, NW = 2 + 2K.
     ``dz`` gives n = int(round(z_max/dz)) as integrators.py:194; or pass ``n_steps``.  ``devices=[0, 1, ...]`` splits the
@@ -302,6 +303,72 @@ def rk4_sweep_single_pump(dbeta, *, z_max: float, dz: Optional[float] = None, n_
     p_in = np.abs(np.atleast_2d(a0)) ** 2
     return SinglePumpResult(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"], n_steps, save_every,
                             r["elapsed_ms"], p_in, r.get("traj"))
+
+
+# ---- multi-line ("comb") sweeps: M equally spaced lines, every FWM product among them ----------------------------------------
+@dataclass
+class CombResult:
+    """Outcome of a multi-line sweep; lines 0..M-1 ascending in frequency, M columns."""
+    a_end: np.ndarray            # (N, M) complex: state at the last SAVED row
+    p_wave_end: np.ndarray       # (N, M) |A_m|^2 there
+    p_wave_max: np.ndarray       # (N, M) max over saved rows (z = 0 included), NaN-propagating
+    first_bad_step: np.ndarray   # (N,) int64, -1 = finite everywhere (or check_nan off); otherwise the exact step
+    n_steps: int
+    save_every: int
+    elapsed_ms: float            # kernel time (hipEvents)
+    p_wave_in: Optional[np.ndarray] = None   # (1 | N, M) |A_m(0)|^2
+    traj: Optional[np.ndarray] = None        # (N, n_saved, M) complex when requested
+
+    def line_gain(self, p0, *, mode: str = "max", unit: str = "dB") -> np.ndarray:
+        """(N, M): every line's power over its input power p0 (M,) or (N, M); gain_mode "end" | "max".  The drivers' NaN
+        rule per line (scan_mismtach.py:376-392): a point with first_bad_step >= 0, a non-positive or non-finite input
+        power (a dark line), a non-finite or non-positive ratio give NaN."""
+        u = check_gain(mode, unit)
+        N, M = (int(x) for x in self.p_wave_end.shape)
+        p0 = np.asarray(p0, dtype=float)
+        if p0.shape not in ((M,), (N, M)):
+            raise ValueError(f"p0 must have shape ({M},) or ({N}, {M}), got {p0.shape}")
+        p0 = np.broadcast_to(p0, (N, M))
+        metric = self.p_wave_max if mode == "max" else self.p_wave_end
+        with np.errstate(all="ignore"):
+            ok = (p0 > 0.0) & np.isfinite(p0) & (np.asarray(self.first_bad_step) < 0)[:, None]
+            g = metric / np.where(ok, p0, 1.0)
+            ok &= np.isfinite(g) & (g > 0.0)
+            return np.where(ok, g if u == "linear" else 10.0 * np.log10(np.where(ok, g, 1.0)), np.nan)
+
+    def total_power(self) -> np.ndarray:
+        """(N,): sum of the lines' powers at the last saved row (conserved for alpha = 0); NaN for a failed point."""
+        with np.errstate(all="ignore"):
+            return np.where(np.asarray(self.first_bad_step) < 0, self.p_wave_end.sum(axis=1), np.nan)
+
+
+def rk4_sweep_comb(kappa, *, z_max: float, dz: Optional[float] = None, n_steps: Optional[int] = None, save_every: int = 10,
+                   check_nan: bool = True, gamma, alpha, a0, want_traj: bool = False, device: int = 0,
+                   devices: Optional[Sequence[int]] = None) -> CombResult:
+    """Propagate N points of the CW multi-line ("frequency comb") model: M = 3..12 lines at w_0 + m dw, ascending in
+    frequency, coupled by EVERY four-wave-mixing product k + l - n = m that falls on the grid -- SPM, XPM, pump-pump,
+    pump-signal and signal-signal mixing (build-defined).  It is what the multi-channel model of
+    rk4_sweep_pairs leaves out and needs the uniform grid that model does not have.  M = 3 is rk4_sweep_single_pump with
+    lines [0, 1, 2] = waves [s, p, i].
+
+    kappa (N, M): the lines' propagation constants in any gauge (kappa + a + b*m is the same system);  gamma / alpha a scalar
+    or (N,); a0 (M,) or (N, M) complex.  ``dz`` gives n = int(round(z_max/dz)) as integrators.py:194; or pass ``n_steps``.
+    With ``check_nan`` first_bad_step is the exact step.  ``want_traj`` also returns every saved row; ``devices=[0, 1, ...]``
+    splits the points over several GPUs of this process.  Fixed-step float64 on a uniform grid only: no float32, RK45, chain
+    or process-group form."""
+    n_steps, save_every = _fixed_grid(z_max, dz, n_steps, save_every)
+    kp = np.asarray(kappa, dtype=float)
+    if kp.ndim != 2 or not 3 <= kp.shape[1] <= _native.MAX_LINES:
+        raise ValueError(f"kappa must have shape (N, M) with 3 <= M <= {_native.MAX_LINES}, got {kp.shape}")
+    N, M = (int(x) for x in kp.shape)
+    a0 = np.asarray(a0, dtype=np.complex128)
+    if a0.shape not in ((M,), (1, M), (N, M)):
+        raise ValueError(f"a0 must have shape ({M},) or ({N}, {M}) for {M} lines, got {a0.shape}")
+    kw = dict(kappa=kp, n_steps=n_steps, z_max=float(z_max), save_every=save_every, gamma=gamma, alpha=alpha, a0=a0,
+              check_nan=check_nan, want_traj=want_traj)
+    r = _run(_native.comb_host, COMB_AXES, N, kw, device, devices)
+    return CombResult(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"], n_steps, save_every, r["elapsed_ms"],
+                      np.abs(np.atleast_2d(a0)) ** 2, r.get("traj"))
 
 
 # ---- chains of fibre spans ------------------------------------------------------------------------------------------
