@@ -13,6 +13,9 @@ Python face of the CPU oracle:
 Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s cpu_baseline
 leg may import this module.  Parity status: PINNED by golden vectors generated
 from the reference itself (tests/golden/gen_golden.py, tests/test_oracle_golden.py).
+A disagreement with a golden is the distance between two float64 runs: whose
+rounding it is is measured against the 80-bit RK4 of tests/truth_ld.py
+(tests/test_truth_host.py).
 """
 from __future__ import annotations
 

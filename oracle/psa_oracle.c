@@ -10,7 +10,11 @@
  * Parity status: PINNED.  Checked against golden vectors G1-G9, G11 produced
  * by importing the reference itself (tests/golden/gen_golden.py) -- see
  * tests/test_oracle_golden.py.  Agreement is at the level of libm-vs-NumPy
- * ulp differences (<= 1e-13 relative on A_end at 45 dB gain).
+ * ulp differences (<= 1e-13 relative on A_end at 45 dB gain).  What is left
+ * against a golden is the distance between two float64 runs, not this port's
+ * error: against an 80-bit run of the same scheme (tests/truth_ld.py) golden G8
+ * at 1e4 steps is off by 3.8e-13 of a point's largest wave (9.3e-12 element by
+ * element, alpha = 0) and this port by the same 3.8e-13 (6.6e-12).
  *
  * Every function cites the reference file:line it restates (paths are into
  * the upstream repo Alxkov/PSA-simulation-ODE-RK-MVP-Dispersion).  Evaluation

@@ -1,0 +1,253 @@
+"""Every sweep kernel against the 80-bit RK4 yardstick (tests/truth_ld.py), through the C-ABI host entries of _native.
+
+The other GPU parity tests hold a kernel within RTOL_F64 = 1e-9 of a float64 twin while the kernels sit at 1e-12..1e-13 of
+theirs: three decimal digits in which a kernel can get worse unseen, and no way to say whose error a disagreement is.  Here
+kernel and twin are both measured against the same discrete scheme run 2 000 times finer than float64, and the bar is "no
+worse than a plain float64 RK4 by more than a stated factor":
+
+    median(e_gpu) <= max(4 median(e_twin), floor)   and   max(e_gpu) <= max(8 max(e_twin), floor)
+
+over the N points, e = point_err against the yardstick, on a_end, on the power summaries and on the rows where a case has
+them.  The factors are about three times the spread between two plain float64 statements of the scheme (medians within 1.3x,
+maxima within 2.4x of each other: tests/test_truth_host.py measures it); the floor 2e-14 is the drift budget psa_rk4_kernel.inc.h states
+for the carried phase (1.4e-14) plus rounding, 2e-6 the same budget in float32 against a plain float32 RK4.  Neither comes
+from a kernel's own figures.  The RTOL_F64 / RTOL_F32 assertion against the twin is kept alongside.
+
+Where a documented design choice makes an output miss the bar, the strict xfail expects BarMissed for that output alone: the
+other outputs, the twin at RTOL_F64, first_bad_step and a band -- the bar plus the drift the kernel's header states for the
+choice -- are asserted as in every other case, and failing any of them fails the test.
+
+Inputs, shapes and the cached 80-bit runs: tests/truth_cases.py.  Each case prints one line of the record
+(profiles/truth_errors.txt)."""
+import functools
+
+import numpy as np
+import pytest
+
+import truth_cases as TC
+import truth_ld as T
+from conftest import RTOL_F32, RTOL_F64
+
+import psa_amd._native as nat
+
+pytestmark = pytest.mark.gpu
+
+
+class BarMissed(AssertionError):
+    """An output misses the bar.  The strict xfails below expect this and nothing else: every other assertion of such a case
+    -- first_bad_step, the twin at RTOL_F64, the outputs that are not known to miss, the band on those that are -- fails it."""
+
+
+def check(family, case, got, inputs, floor=TC.FLOOR_F64, rtol=RTOL_F64, known=(), budget=0.0):
+    """Every assertion of a case but the last.  ``known``: the outputs a documented design choice lets miss the bar; each of
+    them stays within the bar plus ``budget``, the drift the kernel's header states for that choice (never a figure measured
+    on the kernel).  -> the outputs that miss the bar; the caller raises BarMissed for them."""
+    assert (got["first_bad_step"] == -1).all()
+    missed = TC.judge(family, case, got, inputs, floor)
+    # the bar of record: against the float64 twin, and in float32 (whose twin is no reference) against the yardstick
+    for key, e in TC.errors(got, inputs["twin" if rtol == RTOL_F64 else "truth"]).items():
+        assert e.max() < rtol, (key, e.max())
+    assert set(missed) <= set(known), "\n".join(missed[k][0] for k in missed if k not in known)
+    for key, (line, med, mx, tmed, tmx) in missed.items():
+        assert med <= max(4.0 * tmed, floor) + budget and mx <= max(8.0 * tmx, floor) + budget, f"beyond the stated drift: {line}"
+    return missed
+
+
+def meets_the_bar(missed):
+    if missed:
+        raise BarMissed("\n".join(line for line, *_ in missed.values()))
+
+
+def sweep_kw(inputs):
+    return {k: inputs[k] for k in ("n_steps", "z_max", "save_every", "gamma", "alpha", "a0")}
+
+
+# ---- findings at HEAD: strict xfails on BarMissed alone, each a consequence of a documented design choice -----
+R_OFF_UNIT = 5.5e-17      # psa_rk4_kernel.inc.h: "the modulus of the rounded r, <= 5.5e-17 off one, now accumulates in the sidebands"
+CARRIED_BUDGET = 1.4e-14  # psa_rk4_kernel.inc.h: "drift <= 128 multiplications ~1.4e-14" between two seeds of a carried factor
+FRAME_DRIFT = (
+    "the one-lane float64 4-wave step is frame-anchored (psa_rk4_kernel.inc.h, rk4_step_on): after every step the sidebands are "
+    "multiplied by the rounded r = exp(i dbeta h/2), and |r| - 1 is a lane constant of ONE sign, up to 5.5e-17, so the sidebands' "
+    "moduli drift by n (|r| - 1) -- up to 8e-14 of themselves after 1 500 steps, 5.5e-13 after 10 000 -- where a plain RK4's "
+    "random-walk.  The kernel header states the choice (5e-12 after 1e5 steps for 10 instructions per step).  This mark stands "
+    "in for a fix that has not been made.  Measured: ")
+CARRIED_U = (
+    "the comb kernel carries u_m = exp(i kappa_m z) by two rotations per step between exact seeds 64 steps apart "
+    "(psa_rk4_comb_kernel.inc.h): up to 128 roundings of one sign in |u_m| and in its angle, the 1.4e-14 drift budget "
+    "psa_rk4_kernel.inc.h states, on every line -- the pumps included from M = 4 on.  Every case with M >= 4 has an a_end median "
+    "3.9x..6.3x the twin's (1.5e-14..2.3e-14), AT the 2e-14 floor: which of them land above it is a matter of 1-2 %, so the "
+    "family is one finding with one mark.  This mark stands in for a fix that has not been made.")
+
+
+def xfail(why, figures=""):
+    return pytest.mark.xfail(strict=True, raises=BarMissed, reason=why + figures)
+
+
+# ---- four waves, float64 ---------------------------------------------------------------------------------------------------
+LAYOUTS = dict(one_lane=nat.OPT_ONE_LANE, split=nat.OPT_SPLIT_POINT, quad=nat.OPT_QUAD_POINT, lds=nat.OPT_LDS_STAGING)
+SIGNAL_POWER = ("p_end", "p_max")     # what the frame's drift moves at 1 500 steps: a_end, scaled to the pumps, stays inside the bar
+WAVES4 = [
+    pytest.param("one_lane", False, True, marks=xfail(FRAME_DRIFT, "p_end median 8.5e-16 (33x the twin's), max 3.1e-14 (24x)")),
+    ("one_lane", False, False),
+    pytest.param("one_lane", True, True, marks=xfail(FRAME_DRIFT, "p_end median 2.1e-16 (17x the twin's), max 4.8e-14 (31x)")),
+    pytest.param("one_lane", True, False, marks=xfail(FRAME_DRIFT, "p_end median 4.6e-16 (21x the twin's), max 2.5e-14 (17x)")),
+    ("split", False, True), ("split", False, False), ("quad", False, True), ("quad", False, False), ("lds", False, True)]
+
+
+@pytest.mark.parametrize("layout,mirrored,lossy", WAVES4)
+def test_four_waves(layout, mirrored, lossy):
+    """In the one-lane layout the signal's power may miss the bar by the frame's stated drift, n (|r| - 1), and no more; a_end,
+    the twin at RTOL_F64 and first_bad_step hold in every case, xfailed or not."""
+    inputs = TC.waves4(mirrored, lossy)
+    got = nat.sweep_host(inputs["dbeta"], extra_flags=LAYOUTS[layout], **sweep_kw(inputs))
+    if mirrored:      # mirrored inputs give mirrored outputs bit for bit (in the mirrored loop and in the general one alike)
+        assert np.array_equal(got["a_end"][:, 1], got["a_end"][:, 0]) and np.array_equal(got["a_end"][:, 3], got["a_end"][:, 2])
+    frame = layout == "one_lane"
+    meets_the_bar(check("waves4", f"{layout}-{'mirrored' if mirrored else 'general'}-{'lossy' if lossy else 'lossless'}", got, inputs,
+                        known=SIGNAL_POWER if frame else (), budget=inputs["n_steps"] * R_OFF_UNIT if frame else 0.0))
+
+
+@pytest.mark.parametrize("mirrored", [False, True])
+def test_four_waves_one_lane_without_mismatch(mirrored):
+    """The contrast that places the finding above: dbeta = 0 makes r = 1 exactly, and the same layout on the same fibre
+    meets the bar.  (The two- and four-lane layouts and LDS staging, which carry the phase factor instead, meet it too.)"""
+    inputs = TC.waves4_without_mismatch(mirrored)
+    got = nat.sweep_host(inputs["dbeta"], extra_flags=nat.OPT_ONE_LANE, **sweep_kw(inputs))
+    meets_the_bar(check("waves4", f"one_lane-{'mirrored' if mirrored else 'general'}-lossy-dbeta0", got, inputs))
+
+
+G8_DRIFT = xfail(FRAME_DRIFT, "a_end max 1.7e-12 (8.7x the twin's), p_end median 3.3e-15 (16x..21x), p_max median 9.5e-16 (20x)")
+
+
+@pytest.mark.parametrize("mirrored,alpha_i", [(False, 0), pytest.param(False, 1, marks=G8_DRIFT), (True, 0),
+                                              pytest.param(True, 1, marks=G8_DRIFT)])
+def test_four_waves_at_10000_steps_on_the_g8_inputs(mirrored, alpha_i):
+    """10 000 steps of drift reach a_end as well (its maximum, at the points whose sidebands have grown to the pumps' scale):
+    every output may miss by the stated drift and no more."""
+    inputs = TC.g8(mirrored, alpha_i)
+    got = nat.sweep_host(inputs["dbeta"], extra_flags=nat.OPT_ONE_LANE, **sweep_kw(inputs))
+    if mirrored:      # the split of the figure the parity tests quote against the golden: whose error it is, element by element
+        truth, golden = inputs["truth"]["a_end"], inputs["golden"]
+        print(f"\ntruth | waves4-g8 | golden-split-a{alpha_i} | elementwise: kernel against the golden "
+              f"{T.elementwise_err(got['a_end'], golden):.2e}, kernel against the yardstick {T.elementwise_err(got['a_end'], truth):.2e}"
+              f", golden against the yardstick {T.elementwise_err(golden, truth):.2e}")
+    meets_the_bar(check("waves4-g8", f"one_lane-{'mirrored' if mirrored else 'general'}-a{alpha_i}", got, inputs,
+                        known=("a_end",) + SIGNAL_POWER, budget=inputs["n_steps"] * R_OFF_UNIT))
+
+
+@pytest.mark.parametrize("layout", ["one_lane", "split"])
+def test_six_waves(layout):
+    inputs = TC.waves6()
+    got = nat.sweep_host(inputs["dbeta"], dbeta2=inputs["dbeta2"], extra_flags=LAYOUTS[layout], **sweep_kw(inputs))
+    meets_the_bar(check("waves6", layout, got, inputs))
+
+
+def test_per_wave_summary():
+    """psa_rk4_sweep_waves_f64 in the layout a driver's call gets: every wave's end and maximum power."""
+    inputs = TC.waves4(False, True)
+    got = nat.sweep_host(inputs["dbeta"], wave_summary=True, **sweep_kw(inputs))
+    assert got["p_wave_end"].shape == (TC.N, 4)
+    meets_the_bar(check("waves4", "per-wave-summary", got, inputs))
+
+
+# ---- K pairs, single pump, comb --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("K", [1, 2, 3, 5, 8, 16])
+def test_pairs(K):
+    inputs = TC.pairs(K)
+    meets_the_bar(check("pairs", f"K{K}", nat.sweep_pairs_host(inputs["dbeta"], **sweep_kw(inputs)), inputs))
+
+
+def test_pairs_rows():
+    """The multi-channel sweep's trajectory form: one span through psa_rk4_pairs_chain_f64."""
+    inputs = TC.pairs(3)
+    got = nat.pairs_chain_host(inputs["dbeta"][None], n_steps=[inputs["n_steps"]], seg_len=[inputs["z_max"]],
+                               save_every=inputs["save_every"], gamma=inputs["gamma"][None], alpha=inputs["alpha"][None],
+                               a0=inputs["a0"], want_traj=True)
+    assert got["traj"].shape == inputs["truth"]["rows"].shape
+    meets_the_bar(check("pairs", "K3-rows", got, inputs))
+
+
+@pytest.mark.parametrize("lossy", [True, False])
+def test_single_pump(lossy):
+    inputs = TC.at_stride(TC.single_pump(lossy), TC.SAVE_EVERY)
+    meets_the_bar(check("single_pump", "lossy" if lossy else "lossless", nat.single_pump_host(inputs["dbeta"], **sweep_kw(inputs)), inputs))
+
+
+def test_single_pump_rows_at_every_step():
+    inputs = TC.at_stride(TC.single_pump(True), 1)
+    got = nat.single_pump_host(inputs["dbeta"], want_traj=True, **sweep_kw(inputs))
+    assert got["traj"].shape == (TC.N, TC.N_STEPS + 1, 3)
+    meets_the_bar(check("single_pump", "rows-save_every-1", got, inputs))
+
+
+COMB = [(M, True) for M in range(3, 13)] + [(M, False) for M in (3, 7, 10, 12)]
+
+
+@functools.lru_cache(maxsize=None)
+def _comb(M, lossy):
+    """-> the outputs of the case that miss the bar (one launch and one record line per case, whichever test asks first).
+    From M = 4 on a_end may miss, by the carried factor's stated budget and no more."""
+    inputs = TC.comb(M, lossy)
+    got = nat.comb_host(inputs["kappa"], **sweep_kw(inputs))
+    return check("comb", f"M{M}-{'lossy' if lossy else 'lossless'}", got, inputs, known=("a_end",) if M >= 4 else (),
+                 budget=CARRIED_BUDGET if M >= 4 else 0.0)
+
+
+@pytest.mark.parametrize("M,lossy", COMB)
+def test_comb(M, lossy):
+    """Every instantiation: first_bad_step, the twin at RTOL_F64, the power summaries at the bar, and a_end at the bar (M = 3,
+    whose pump line has kappa = 0) or within the bar plus the carried factor's stated drift (M >= 4; the bar itself for
+    these is test_comb_family_meets_the_bar)."""
+    missed = _comb(M, lossy)
+    if M < 4:
+        meets_the_bar(missed)
+
+
+@xfail(CARRIED_U)
+def test_comb_family_meets_the_bar():
+    """The bar on a_end for every comb case with M >= 4, as one finding."""
+    missed = {}
+    for M, lossy in COMB:
+        if M >= 4:
+            missed.update({f"M{M}-{'lossy' if lossy else 'lossless'} {k}": v for k, v in _comb(M, lossy).items()})
+    meets_the_bar(missed)
+
+
+def test_comb_without_dispersion():
+    """The contrast that places the finding above: kappa = 0 leaves u_m = 1 and every rotator (1, 0), nothing carried can
+    drift, and M = 7 -- over the floor with dispersion -- sits with the twin."""
+    inputs = TC.comb_without_dispersion(7)
+    meets_the_bar(check("comb", "M7-lossy-kappa0", nat.comb_host(inputs["kappa"], **sweep_kw(inputs)), inputs))
+
+
+# ---- chains ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("family", ["waves", "single_pump", "pairs"])
+def test_chain(family):
+    inputs = TC.chain(family)
+    kw = TC.chain_arrays(inputs)
+    dbeta = kw.pop("dbeta")
+    if family == "waves":
+        got = nat.chain_host(dbeta, want_traj=True, **kw)
+    elif family == "single_pump":
+        got = nat.single_pump_chain_host(dbeta, want_traj=True, **kw)
+    else:
+        got = nat.pairs_chain_host(dbeta, want_traj=True, **kw)
+    assert got["traj"].shape == inputs["truth"]["rows"].shape
+    meets_the_bar(check("chain", family, got, inputs))
+
+
+# ---- float32 ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("layout,mirrored", [("packed", False), ("packed", True), ("scalar", False)])
+def test_four_waves_float32(layout, mirrored):
+    inputs = TC.waves4_f32(mirrored)
+    got = nat.sweep_host(inputs["dbeta"], dtype=np.float32, extra_flags=dict(packed=nat.OPT_F32_PACKED, scalar=nat.OPT_F32_SCALAR)[layout],
+                         **sweep_kw(inputs))
+    assert got["a_end"].dtype == np.complex64
+    meets_the_bar(check("waves4-f32", f"{layout}-{'mirrored' if mirrored else 'general'}", got, inputs, TC.FLOOR_F32, RTOL_F32))
+
+
+def test_single_pump_float32():
+    inputs = TC.single_pump_f32()
+    got = nat.single_pump_host(inputs["dbeta"], dtype=np.float32, **sweep_kw(inputs))
+    assert got["a_end"].dtype == np.complex64
+    meets_the_bar(check("single_pump-f32", "packed", got, inputs, TC.FLOOR_F32, RTOL_F32))

@@ -1,0 +1,372 @@
+"""The input sets of tests/test_truth_host.py and tests/test_gpu_truth.py, each with its 80-bit run (truth_ld) and its twin's
+run, computed once per process; the float32 twins; and the bar both files apply.
+
+Shapes: N = 67 points (one full wave and a ragged one with one lane per point, an odd count for two points per lane, four full
+waves and a ragged one with four lanes per point), 1 500 steps over 300 m (not a multiple of the 64-step seed grid: 23
+re-seeds), rows every 7 steps (a tail of 2 behind the last row).  Per-point gamma, alpha and amplitudes with random phases.
+
+Every result is a dict in one form: a_end (N, NW), p_wave_end, p_wave_max (N, NW), rows (N, n_saved, NW) or None.
+"""
+import functools
+import os
+
+import numpy as np
+
+import comb_np
+import pairs_chain_np
+import pairs_np
+import single_pump_chain_np
+import single_pump_np
+import truth_ld as T
+
+N, N_STEPS, Z_MAX, SAVE_EVERY = 67, 1500, 300.0, 7
+GAMMA, ALPHA = 0.0115, 1.15e-4
+CHAIN_STEPS, CHAIN_LENGTHS, CHAIN_SAVE_EVERY = (700, 800), (140.0, 200.0), 20   # a chain's spans end on a saved row: 20 | 700, 800
+FLOOR_F64, FLOOR_F32 = 2e-14, 2e-6
+TWIN_CONDITION = 1e-11                 # every float64 input set: the twin's largest point_err stays below this
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def from_rows(rows):
+    """Saved rows (N, n_saved, NW) -> the result dict."""
+    rows = np.asarray(rows)
+    p = rows.real ** 2 + rows.imag ** 2
+    return dict(a_end=rows[:, -1], p_wave_end=p[:, -1], p_wave_max=p.max(axis=1), rows=rows)
+
+
+def strided(res, save_every):
+    """The result of a run that saved every step, read at a save stride."""
+    return from_rows(res["rows"][:, ::save_every])
+
+
+# ---- the bar ---------------------------------------------------------------------------------------------------------------
+def errors(got, truth):
+    """Per-point errors against the yardstick of everything ``got`` holds: a_end, the power summaries as moduli against the
+    point's largest modulus (p_end / p_max are wave 2's), the rows.  -> {key: (N,) float64}."""
+    out = dict(a_end=T.point_err(got["a_end"], truth["a_end"]))
+    for key, one in (("p_wave_end", "p_end"), ("p_wave_max", "p_max")):
+        mod = np.sqrt(truth[key])
+        scale = mod.max(axis=1)
+        if got.get(key) is not None:
+            out[key] = T.point_err(np.sqrt(T.ld(got[key])), mod)
+        elif got.get(one) is not None:
+            out[one] = np.asarray(np.abs(np.sqrt(T.ld(got[one])) - mod[:, 2]) / scale, dtype=np.float64)
+    rows = got.get("rows") if got.get("rows") is not None else got.get("traj")
+    if rows is not None and truth["rows"] is not None:
+        out["rows"] = T.point_err(rows, truth["rows"])
+    return out
+
+
+def like(got, twin):
+    """The twin's result in the form of ``got``: wave 2's p_end / p_max where the entry point returns those alone."""
+    if got.get("p_wave_end") is None and got.get("p_end") is not None:
+        return dict(a_end=twin["a_end"], p_end=twin["p_wave_end"][:, 2], p_max=twin["p_wave_max"][:, 2], rows=twin["rows"])
+    return twin
+
+
+def bar(e_got, e_twin, floor):
+    """The assertion of every case: no worse than the plain twin by more than a stated factor, on the aggregates over the
+    points.  -> (passes, median ratio, max ratio)."""
+    med, mx = float(np.median(e_got)), float(np.max(e_got))
+    tmed, tmx = float(np.median(e_twin)), float(np.max(e_twin))
+    ok = med <= max(4.0 * tmed, floor) and mx <= max(8.0 * tmx, floor)
+    return ok, med / tmed if tmed > 0 else float("inf"), mx / tmx if tmx > 0 else float("inf")
+
+
+def judge(family, case, got, inputs, floor=FLOOR_F64):
+    """Print the case's line of the record (and one more for every output that misses the bar) and -> the outputs that miss
+    it: {key: (its figures as a readable line, kernel median, kernel max, twin median, twin max)}."""
+    e_got, e_twin = errors(got, inputs["truth"]), errors(like(got, inputs["twin"]), inputs["truth"])
+    missed, worst = {}, None
+    for key, e in e_got.items():
+        ok, r_med, r_max = bar(e, e_twin[key], floor)
+        line = (f"{key}: kernel median {np.median(e):.2e} max {e.max():.2e}, twin median {np.median(e_twin[key]):.2e} "
+                f"max {e_twin[key].max():.2e}, ratio {r_med:.2f} / {r_max:.2f}")
+        if not ok:
+            missed[key] = (line, float(np.median(e)), float(e.max()), float(np.median(e_twin[key])), float(e_twin[key].max()))
+        if worst is None or max(r_med / 4.0, r_max / 8.0) > worst[0]:
+            worst = (max(r_med / 4.0, r_max / 8.0), key, r_med, r_max)
+    a, t = e_got["a_end"], e_twin["a_end"]
+    print(f"\ntruth | {family} | {case} | a_end kernel {np.median(a):.2e} {a.max():.2e} twin {np.median(t):.2e} {t.max():.2e} "
+          f"ratio {np.median(a) / np.median(t):.2f} {a.max() / t.max():.2f} | worst {worst[1]} {worst[2]:.2f} {worst[3]:.2f}", end="")
+    for line, *_ in missed.values():
+        print(f"\ntruth | {family} | {case} | misses the bar | {line}", end="")
+    print()
+    return missed
+
+
+# ---- four and six waves ----------------------------------------------------------------------------------------------------
+def _oracle_rows(a0, dbeta, dbeta2, gamma, alpha, z_max, n, save_every):
+    """The C oracle point by point, with its saved rows."""
+    import oracle
+    n_pts = dbeta.shape[0]
+    gamma, alpha = np.broadcast_to(gamma, (n_pts,)), np.broadcast_to(alpha, (n_pts,))
+    rows = []
+    for j in range(n_pts):
+        _, A, bad = oracle.integrate(a0[j], z_max=z_max, n=n, save_every=save_every, gamma=gamma[j], alpha=alpha[j],
+                                     dbeta=dbeta[j], dbeta2=0.0 if dbeta2 is None else dbeta2[j])
+        assert bad < 0
+        rows.append(A)
+    return np.stack(rows)
+
+
+def _amplitudes(rng, n_pts, pumps, sidebands):
+    """Pumps 0.2-0.6 W each, sidebands 1e-7..1e-3 W, every phase random."""
+    p = np.column_stack([rng.uniform(0.2, 0.6, (n_pts, pumps)), 10 ** rng.uniform(-7.0, -3.0, (n_pts, sidebands))])
+    return np.sqrt(p) * np.exp(1j * rng.uniform(-3.0, 3.0, p.shape))
+
+
+def _fibre(rng, n_pts, lossy):
+    return GAMMA * rng.uniform(0.9, 1.1, n_pts), (ALPHA * rng.uniform(0.5, 1.5, n_pts) if lossy else 0.0)
+
+
+def _waves_set(inp):
+    rate = inp["dbeta"] if inp.get("dbeta2") is None else np.column_stack([inp["dbeta"], inp["dbeta2"]])
+    kw = dict(z_max=inp["z_max"], n=inp["n_steps"], save_every=inp["save_every"])
+    truth = T.integrate(T.rhs_waves, inp["a0"], rate, gamma=inp["gamma"], alpha=inp["alpha"], want_rows=True, **kw)
+    twin = from_rows(_oracle_rows(inp["a0"], inp["dbeta"], inp.get("dbeta2"), inp["gamma"], inp["alpha"], **kw))
+    return dict(inp, truth=truth, twin=twin)
+
+
+@functools.lru_cache(maxsize=None)
+def waves4(mirrored, lossy):
+    """General amplitudes (A2 != A1, A4 != A3) or mirrored ones (A2 == A1 and A4 == A3 bit for bit in every lane: the loop
+    the headline benchmark runs)."""
+    rng = np.random.default_rng(4100 + 2 * mirrored + lossy)
+    a0 = _amplitudes(rng, N, 2, 2)
+    if mirrored:
+        a0[:, 1], a0[:, 3] = a0[:, 0], a0[:, 2]
+    gamma, alpha = _fibre(rng, N, lossy)
+    return _waves_set(dict(dbeta=rng.uniform(-0.05, 0.05, N), gamma=gamma, alpha=alpha, a0=a0, z_max=Z_MAX, n_steps=N_STEPS,
+                           save_every=SAVE_EVERY))
+
+
+@functools.lru_cache(maxsize=None)
+def waves4_without_mismatch(mirrored):
+    """The lossy set with dbeta = 0: no phase to carry, and the one-lane step's frame rotation is the identity."""
+    inp = {k: v for k, v in waves4(mirrored, True).items() if k not in ("truth", "twin")}
+    return _waves_set(dict(inp, dbeta=np.zeros(N)))
+
+
+def g8_inputs(alpha_i):
+    """Every 4th of golden G8's first 256 mismatches (64 points: one wave), its fibre and powers, 10 000 steps over 1000 m."""
+    g = np.load(os.path.join(GOLDEN, "G8.npz"))
+    pick = np.arange(0, 256, 4)
+    a0 = np.repeat(np.sqrt(g["p_in"]).astype(complex)[None, :], 64, axis=0)
+    return dict(dbeta=g["dbeta257"][pick], gamma=float(g["gamma"]), alpha=float(g["alphas"][alpha_i]), a0=a0,
+                z_max=float(g["z_max"]), n_steps=10_000, save_every=int(g["save_every"]),
+                golden=g[f"n1e4_a{alpha_i}_A_end"][pick])
+
+
+@functools.lru_cache(maxsize=None)
+def g8(mirrored, alpha_i):
+    """G8's powers are mirrored.  The general loop runs the same fibre with A2 one ulp off A1 in lane 5 -- a wave leaves the
+    mirrored loop when one live lane does -- and A4 = 1.5 A3 in lane 40."""
+    inp = g8_inputs(alpha_i)
+    if not mirrored:
+        inp["a0"][5, 1] = complex(np.nextafter(inp["a0"][5, 0].real, np.inf), inp["a0"][5, 0].imag)
+        inp["a0"][40, 3] = 1.5 * inp["a0"][40, 2]
+    return _waves_set(inp)
+
+
+@functools.lru_cache(maxsize=None)
+def waves6():
+    rng = np.random.default_rng(4600)
+    gamma, alpha = _fibre(rng, N, True)
+    return _waves_set(dict(dbeta=rng.uniform(-0.05, 0.05, N), dbeta2=rng.uniform(-0.05, 0.05, N), gamma=gamma, alpha=alpha,
+                           a0=_amplitudes(rng, N, 2, 4), z_max=Z_MAX, n_steps=N_STEPS, save_every=SAVE_EVERY))
+
+
+# ---- K pairs, single pump, comb --------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def pairs(K):
+    """K = 1, 2, 3, 5, 8, 16: every lane-group width (2, 2, 4, 8, 8, 16), a padded group at 1, 3 and 5.  K = 3 keeps the rows."""
+    rng = np.random.default_rng(4200 + K)
+    gamma, alpha = _fibre(rng, N, True)
+    inp = dict(dbeta=rng.uniform(-0.05, 0.05, (N, K)), gamma=gamma, alpha=alpha, a0=_amplitudes(rng, N, 2, 2 * K), z_max=Z_MAX,
+               n_steps=N_STEPS, save_every=SAVE_EVERY)
+    kw = dict(z_max=Z_MAX, n=N_STEPS, save_every=SAVE_EVERY, gamma=gamma, alpha=alpha)
+    truth = T.integrate(T.rhs_pairs, inp["a0"], inp["dbeta"], want_rows=(K == 3), **kw)
+    if K == 3:
+        twin = from_rows(pairs_chain_np.integrate(inp["a0"], inp["dbeta"], **kw)["traj"])
+    else:
+        twin = dict(pairs_np.integrate(inp["a0"], inp["dbeta"], **kw), rows=None)
+    return dict(inp, truth=truth, twin=twin)
+
+
+@functools.lru_cache(maxsize=None)
+def single_pump(lossy):
+    """Every step is saved: the rows case reads them all, the summary cases every 7th (``strided``)."""
+    rng = np.random.default_rng(4300 + lossy)
+    gamma, alpha = _fibre(rng, N, lossy)
+    inp = dict(dbeta=rng.uniform(-4.5, 0.5, N) * GAMMA * 0.5, gamma=gamma, alpha=alpha, a0=_amplitudes(rng, N, 1, 2),
+               z_max=Z_MAX, n_steps=N_STEPS)
+    kw = dict(z_max=Z_MAX, n=N_STEPS, save_every=1, gamma=gamma, alpha=alpha)
+    truth = T.integrate(T.rhs_single_pump, inp["a0"], inp["dbeta"], want_rows=True, **kw)
+    twin = from_rows(single_pump_np.integrate(inp["a0"], inp["dbeta"], want_traj=True, **kw)["traj"])
+    return dict(inp, truth=truth, twin=twin)
+
+
+def at_stride(inputs, save_every):
+    return dict(inputs, save_every=save_every, truth=strided(inputs["truth"], save_every), twin=strided(inputs["twin"], save_every))
+
+
+@functools.lru_cache(maxsize=None)
+def comb(M, lossy):
+    kappa, a0, gamma, alpha = comb_np.random_inputs(N, M, 4400 + 2 * M + lossy, per_point=True, lossy=lossy)
+    kw = dict(z_max=Z_MAX, n=N_STEPS, save_every=SAVE_EVERY, gamma=gamma, alpha=alpha)
+    truth = T.integrate(T.rhs_comb, a0, kappa, **kw)
+    twin = dict(comb_np.integrate(a0, kappa, **kw), rows=None)
+    return dict(kappa=kappa, a0=a0, gamma=gamma, alpha=alpha, z_max=Z_MAX, n_steps=N_STEPS, save_every=SAVE_EVERY,
+                truth=truth, twin=twin)
+
+
+@functools.lru_cache(maxsize=None)
+def comb_without_dispersion(M):
+    """The lossy set with kappa = 0: u_m = 1 and every rotator is (1, 0), so nothing carried can drift."""
+    inp = {k: v for k, v in comb(M, True).items() if k not in ("truth", "twin")}
+    kappa = np.zeros_like(inp["kappa"])
+    kw = dict(z_max=Z_MAX, n=N_STEPS, save_every=SAVE_EVERY, gamma=inp["gamma"], alpha=inp["alpha"])
+    return dict(inp, kappa=kappa, truth=T.integrate(T.rhs_comb, inp["a0"], kappa, **kw),
+                twin=dict(comb_np.integrate(inp["a0"], kappa, **kw), rows=None))
+
+
+# ---- chains ----------------------------------------------------------------------------------------------------------------
+def _mid_stage(rng, shape):
+    """One mid-stage transfer per point with gain (-3..1 dB) and phase on every wave."""
+    return np.sqrt(10.0 ** (rng.uniform(-3.0, 1.0, shape) / 10.0)) * np.exp(1j * rng.uniform(-np.pi, np.pi, shape))
+
+
+def _chain_spans(rng, dbeta_shape, scale):
+    return [(L, n, rng.uniform(-1.0, 1.0, dbeta_shape) * scale, GAMMA * rng.uniform(0.8, 1.6, N), ALPHA * rng.uniform(0.5, 2.0, N))
+            for L, n in zip(CHAIN_LENGTHS, CHAIN_STEPS)]
+
+
+@functools.lru_cache(maxsize=None)
+def chain(family):
+    """Two spans of 700 and 800 steps (h = 0.2 and 0.25 m) with different per-point dbeta, gamma and alpha and one per-point
+    mid-stage transfer.  family: "waves" (4 waves), "single_pump", "pairs" (K = 3)."""
+    rng = np.random.default_rng(dict(waves=4500, single_pump=4501, pairs=4502)[family])
+    if family == "waves":
+        import test_chain_host
+        a0, spans = _amplitudes(rng, N, 2, 2), _chain_spans(rng, N, 0.05)
+        transfers = [_mid_stage(rng, (N, 4))]
+        twin = np.stack([test_chain_host._oracle_chain(a0[j], [(L, n, db[j], g[j], al[j]) for L, n, db, g, al in spans],
+                                                       [transfers[0][j]], CHAIN_SAVE_EVERY) for j in range(N)])
+        f = T.rhs_waves
+    elif family == "single_pump":
+        a0, spans = _amplitudes(rng, N, 1, 2), _chain_spans(rng, N, 2.5 * GAMMA * 0.5)
+        transfers = [_mid_stage(rng, (N, 3))]
+        twin = single_pump_chain_np.chain(a0, spans, transfers, CHAIN_SAVE_EVERY)["rows"]
+        f = T.rhs_single_pump
+    else:
+        a0, spans = _amplitudes(rng, N, 2, 6), _chain_spans(rng, (N, 3), 0.05)
+        transfers = [_mid_stage(rng, (N, 8))]
+        twin = pairs_chain_np.chain(a0, spans, transfers, CHAIN_SAVE_EVERY)["rows"]
+        f = T.rhs_pairs
+    truth = T.chain(f, a0, spans, transfers, CHAIN_SAVE_EVERY)
+    return dict(a0=a0, spans=spans, transfers=transfers, save_every=CHAIN_SAVE_EVERY, truth=truth, twin=from_rows(twin))
+
+
+def chain_arrays(inputs):
+    """The spans of a chain as the C entry points take them."""
+    spans = inputs["spans"]
+    return dict(dbeta=np.stack([s[2] for s in spans]), n_steps=[s[1] for s in spans], seg_len=[s[0] for s in spans],
+                gamma=np.stack([s[3] for s in spans]), alpha=np.stack([s[4] for s in spans]), a0=inputs["a0"],
+                transfers=np.stack(inputs["transfers"]), save_every=inputs["save_every"])
+
+
+# ---- float32: the twin is a plain float32 classic RK4 ------------------------------------------------------------------------
+F32, C64 = np.float32, np.complex64
+
+
+def _expi32(dbeta32, z):
+    """exp(i dbeta z) in float32: the phase is formed and reduced to [-pi, pi] in float64, then a float32 cos / sin, as
+    psa_rk4_kernel.inc.h says the float32 kernels do."""
+    ph = dbeta32.astype(np.float64) * z
+    r = (ph - 2.0 * np.pi * np.rint(ph / (2.0 * np.pi))).astype(F32)
+    return (np.cos(r) + 1j * np.sin(r)).astype(C64)
+
+
+def _rhs32_waves(e, a, g, al):
+    P = a.real * a.real + a.imag * a.imag
+    kerr = P + F32(2) * (P.sum(axis=1, keepdims=True) - P)
+    e = e[:, None]
+    M = np.concatenate([np.conj(a[:, 1:2]) * a[:, 2:3] * a[:, 3:4] * e, np.conj(a[:, 0:1]) * a[:, 2:3] * a[:, 3:4] * e,
+                        np.conj(a[:, 3:4]) * a[:, 0:1] * a[:, 1:2] * np.conj(e),
+                        np.conj(a[:, 2:3]) * a[:, 0:1] * a[:, 1:2] * np.conj(e)], axis=1)
+    return (F32(-0.5) * al) * a + C64(1j) * (g * kerr * a) + C64(2j) * (g * M)
+
+
+def _rhs32_single_pump(e, a, g, al):
+    P = a.real * a.real + a.imag * a.imag
+    kerr = F32(2) * P.sum(axis=1, keepdims=True) - P
+    e = e[:, None]
+    p, s, i = a[:, 0:1], a[:, 1:2], a[:, 2:3]
+    M = np.concatenate([F32(2) * np.conj(p) * s * i * e, np.conj(i) * p * p * np.conj(e), np.conj(s) * p * p * np.conj(e)],
+                       axis=1)
+    return (F32(-0.5) * al) * a + C64(1j) * (g * kerr * a) + C64(1j) * (g * M)
+
+
+def rk4_f32(rhs, a0, dbeta, *, z_max, n, save_every, gamma, alpha):
+    """State and arithmetic in float32 / complex64; z = i h in float64 for the phase alone."""
+    dbeta = np.asarray(dbeta, dtype=F32)
+    n_pts = dbeta.shape[0]
+    y = np.array(np.broadcast_to(np.asarray(a0, dtype=C64), (n_pts, np.shape(a0)[-1])))
+    g = np.broadcast_to(np.asarray(gamma, dtype=F32), (n_pts,))[:, None]
+    al = np.broadcast_to(np.asarray(alpha, dtype=F32), (n_pts,))[:, None]
+    h64 = z_max / n
+    h, half, sixth = F32(h64), F32(0.5 * h64), F32(h64 / 6.0)
+    rows = [y]
+    for i in range(n):
+        e0, em, e1 = _expi32(dbeta, i * h64), _expi32(dbeta, (i + 0.5) * h64), _expi32(dbeta, (i + 1) * h64)
+        k1 = rhs(e0, y, g, al)
+        k2 = rhs(em, y + half * k1, g, al)
+        k3 = rhs(em, y + half * k2, g, al)
+        k4 = rhs(e1, y + h * k3, g, al)
+        y = y + sixth * (k1 + F32(2) * k2 + F32(2) * k3 + k4)
+        assert y.dtype == C64
+        if (i + 1) % save_every == 0:
+            rows.append(y)
+    return from_rows(np.stack(rows, axis=1))
+
+
+def _rounded(inp):
+    """The inputs as the float32 entry points see them: what the yardstick integrates."""
+    out = dict(inp)
+    for k in ("dbeta", "gamma", "alpha"):
+        out[k] = np.asarray(inp[k], dtype=F32)
+    out["a0"] = np.asarray(inp["a0"], dtype=C64)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def waves4_f32(mirrored):
+    inp = _rounded({k: v for k, v in waves4(mirrored, True).items() if k not in ("truth", "twin")})
+    kw = dict(z_max=Z_MAX, n=N_STEPS, save_every=SAVE_EVERY, gamma=inp["gamma"], alpha=inp["alpha"])
+    truth = T.integrate(T.rhs_waves, inp["a0"], inp["dbeta"], **kw)
+    return dict(inp, truth=truth, twin=rk4_f32(_rhs32_waves, inp["a0"], inp["dbeta"], **kw))
+
+
+@functools.lru_cache(maxsize=None)
+def single_pump_f32():
+    inp = _rounded({k: v for k, v in single_pump(True).items() if k not in ("truth", "twin")})
+    kw = dict(z_max=Z_MAX, n=N_STEPS, save_every=SAVE_EVERY, gamma=inp["gamma"], alpha=inp["alpha"])
+    truth = T.integrate(T.rhs_single_pump, inp["a0"], inp["dbeta"], **kw)
+    return dict(inp, save_every=SAVE_EVERY, truth=truth, twin=rk4_f32(_rhs32_single_pump, inp["a0"], inp["dbeta"], **kw))
+
+
+# ---- every float64 input set, for the CPU test that pins the twins ---------------------------------------------------------
+F64_SETS = ([(f"waves4-{'mirrored' if m else 'general'}-{'lossy' if l else 'lossless'}", lambda m=m, l=l: waves4(m, l))
+             for m in (False, True) for l in (True, False)]
+            + [(f"g8-{'mirrored' if m else 'general'}-a{a}", lambda m=m, a=a: g8(m, a)) for m in (False, True) for a in (0, 1)]
+            + [("waves6", waves6)]
+            + [(f"pairs-K{K}", lambda K=K: pairs(K)) for K in (1, 2, 3, 5, 8, 16)]
+            + [(f"single_pump-{'lossy' if l else 'lossless'}", lambda l=l: single_pump(l)) for l in (True, False)]
+            + [(f"comb-M{M}-lossy", lambda M=M: comb(M, True)) for M in range(3, 13)]
+            + [(f"comb-M{M}-lossless", lambda M=M: comb(M, False)) for M in (3, 7, 10, 12)]
+            + [(f"chain-{f}", lambda f=f: chain(f)) for f in ("waves", "single_pump", "pairs")]
+            + [(f"waves4-{'mirrored' if m else 'general'}-dbeta0", lambda m=m: waves4_without_mismatch(m)) for m in (False, True)]
+            + [("comb-M7-kappa0", lambda: comb_without_dispersion(7))])
+F32_SETS = [("waves4_f32-general", lambda: waves4_f32(False)), ("waves4_f32-mirrored", lambda: waves4_f32(True)),
+            ("single_pump_f32", single_pump_f32)]
