@@ -65,7 +65,11 @@ hipError_t launch_sweep_f64(hipStream_t s, int n_waves, uint32_t flags, const Sw
         else if (flags & PSA_OPT_SPLIT_POINT) lanes = 2;
         else lanes = best_lanes_per_point(n_waves, a.n_points, simds);
     }
-    if (lanes == 1) return launch_family<OneLane<double>>(s, p, a);
+    if (lanes == 1) {
+        // the row-driven z-loop (4 waves, register layout, no trajectory) compiled for the row length, where a row exists
+        if (n_waves == 4 && !p.traj && !p.lds && a.save_every == PSA_FIXED_ROW && a.n_steps >= PSA_FIXED_ROW) p.row = PSA_FIXED_ROW;
+        return launch_family<OneLane<double>>(s, p, a);
+    }
     // 64-thread workgroups while the sweep's waves fit half the SIMDs (a sweep of few waves is spread over as many CUs as
     // it has waves), 256 beyond (four waves per workgroup land on the four SIMDs of one CU: the placement that gives every
     // wave its own SIMD when the sweep fills the chip -- 1 024 single-wave workgroups measured 12 % slower at N = 32 768

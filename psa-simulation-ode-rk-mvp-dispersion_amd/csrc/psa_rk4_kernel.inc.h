@@ -266,9 +266,13 @@ __device__ __forceinline__ bool any_nonfinite(const T (&y)[NC]) {
 // idler seeds, zero phases).  The step, the rotations, the re-seeds, the event loop, the checkpoint and replay, the block
 // test and the tail are the one text below for both; the outputs are the full record, waves 2 and 4 written from the
 // registers of waves 1 and 3.  144 DP instructions per step instead of 288 (32 + 30 + 30 + 32 stages, 12 + 4, 4 to move the frame).
-template <typename T, int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS, bool LOSS, bool WSUM, bool MIRROR>
+//
+// ROW > 0 (the frame-anchored summary kernels only) is the same body for launches whose save_every IS ROW, known when the
+// kernel is compiled: a saved row of the z-loop is then ROW steps in straight line (see "z-loop by saved rows" below).
+template <typename T, int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS, bool LOSS, bool WSUM, bool MIRROR, int ROW = 0>
 __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long long idx, T (&y)[MIRROR ? NW : 2 * NW]) {
     static_assert(!MIRROR || (sizeof(T) == 8 && NW == 4 && !LDS), "the mirrored body exists for the fused float64 4-wave step");
+    static_assert(ROW == 0 || (sizeof(T) == 8 && NW == 4 && !LDS && !TRAJ), "a fixed row length exists for the row-driven z-loop");
     constexpr int NC = 2 * NW;                  // components of the record
     constexpr int NS = MIRROR ? NW : NC;        // components of the state this lane carries
     constexpr int NWS = NS / 2;                 // waves of that state
@@ -727,10 +731,52 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
         int trips = m / PSA_ROW_TRIP;
         int span = left < 0 ? 1 : span_of(left);
         [[maybe_unused]] int i_row = 0;        // block mode: the step index of the row
+        auto row_work = [&](const int steps) {   // the row after a block of `steps` steps
+            pe = fma_(y[SIG], y[SIG], y[SIG + 1] * y[SIG + 1]);
+            pm = (pe > pm || pe != pe) ? pe : pm;  // np.max propagates NaN
+            if constexpr (WSUM) {
+#pragma unroll
+                for (int j = 0; j < NWS; ++j) {
+                    const T pj = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
+                    pwm[j] = (pj > pwm[j] || pj != pj) ? pj : pwm[j];
+                }
+            }
+            if constexpr (CHECK == CHECK_BLOCK) {
+                i_row += steps;
+                if (bad < 0 && any_nonfinite<T, NS>(y)) bad = i_row - 1;
+            }
+        };
         checkpoint(0);
         if (left < 0) write_powers();          // no row after z = 0
+        int until = span;
+        // ROW > 0: the saved rows of a launch whose save_every is ROW.  The block is ROW steps in straight line, the row work
+        // and the counter: one basic block, nothing to pick, count or skip -- 10 instructions outside the steps and one taken
+        // branch per row, where the run-time loop below has 23 and three at save_every = 10 (profiles/fixed_rows.log).
+        // The same steps, the same row work, the same test points: no bit depends on which loop ran the rows.  What is rare
+        // hangs off `until` as below; after the last row the tail, if any, is one block of the run-time loop.  The host picks
+        // this instantiation for save_every == ROW only (launch_sweep_f64); any other stride takes the run-time loop here too.
+        if constexpr (ROW > 0) {
+            if (se == ROW && left > 0) {
+                for (;;) {
+#pragma unroll
+                    for (int q = 0; q < ROW; ++q) rk4_step_reg(0);
+                    row_work(ROW);
+                    if (--until != 0) continue;                   // wave-uniform; the back-edge of every other row
+                    left -= span;
+                    exact_test((n_rows - left) * ROW);
+                    if (left == 0) break;
+                    until = span = span_of(left);
+                }
+                store_a_end_at(n_rows * ROW);  // A[-1]: the last saved row, not necessarily z_max (R8)
+                write_powers();
+                left = -1;
+                m = tail;
+                trips = m / PSA_ROW_TRIP;
+                until = 1;
+            }
+        }
         if (m > 0) {
-            for (int until = span;;) {
+            for (;;) {
                 if (m & 1) rk4_step_reg(0);
                 if constexpr (PSA_ROW_TRIP == 4) {
                     if (m & 2) {
@@ -746,19 +792,7 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
                         rk4_step_reg(0);
                     }
                 }
-                pe = fma_(y[SIG], y[SIG], y[SIG + 1] * y[SIG + 1]);
-                pm = (pe > pm || pe != pe) ? pe : pm;  // np.max propagates NaN
-                if constexpr (WSUM) {
-#pragma unroll
-                    for (int j = 0; j < NWS; ++j) {
-                        const T pj = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
-                        pwm[j] = (pj > pwm[j] || pj != pj) ? pj : pwm[j];
-                    }
-                }
-                if constexpr (CHECK == CHECK_BLOCK) {
-                    i_row += m;
-                    if (bad < 0 && any_nonfinite<T, NS>(y)) bad = i_row - 1;
-                }
+                row_work(m);
                 if (--until != 0) continue;                       // wave-uniform; the back-edge of every other row
                 if (left > 0) left -= span;
                 exact_test(left < 0 ? n_run : (n_rows - left) * se);
@@ -866,7 +900,7 @@ __device__ __forceinline__ bool wave_starts_mirrored(const double (&y)[8]) {
     return __builtin_amdgcn_ballot_w64(objects) == 0;
 }
 
-template <typename T, int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS = false, bool LOSS = true, bool WSUM = false>
+template <typename T, int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS = false, bool LOSS = true, bool WSUM = false, int ROW = 0>
 __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(const SweepArgs<T> A) {
     static_assert(!WSUM || (!TRAJ && !LDS), "the per-wave summary exists for the register layout without trajectory");
     constexpr int NC = 2 * NW;
@@ -889,22 +923,24 @@ __global__ void __launch_bounds__(BLOCK) PSA_SWEEP_KERNEL_ATTR rk4_sweep_kernel(
             T ym[NW];
 #pragma unroll
             for (int c = 0; c < NW; ++c) ym[c] = A.a0[(long long)(c < 2 ? c : c + 2) * A.a0_ld + idx_m * A.a0_stride];
-            sweep_point<T, NW, CHECK, TRAJ, BLOCK, LDS, LOSS, WSUM, true>(A, idx_m, ym);
+            sweep_point<T, NW, CHECK, TRAJ, BLOCK, LDS, LOSS, WSUM, true, ROW>(A, idx_m, ym);
             return;
         }
     }
-    sweep_point<T, NW, CHECK, TRAJ, BLOCK, LDS, LOSS, WSUM, false>(A, idx, y);
+    sweep_point<T, NW, CHECK, TRAJ, BLOCK, LDS, LOSS, WSUM, false, ROW>(A, idx, y);
 }
 
 // One lane per point.  LDS staging (an A/B variant: 5 * 2*NW * 64 * sizeof(T) bytes of LDS, 20 KB for f64 with 4 waves)
 // is one 64-thread wave per workgroup with the loss links; the per-wave summary is register-only, without trajectory,
-// in 256-thread workgroups.
+// in 256-thread workgroups.  A fixed row length (ROW, Pick::row) exists for the row-driven z-loop alone: float64, 4 waves,
+// register layout, no trajectory.
 template <typename T> struct OneLane {
     static long long lanes(long long n_points) { return n_points; }
-    template <int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS, bool LOSS, bool WSUM>
+    template <int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS, bool LOSS, bool WSUM, int ROW = 0>
     static constexpr auto kernel() {
         if constexpr ((WSUM && (TRAJ || LDS || BLOCK != 256)) || (LDS && (BLOCK != 64 || !LOSS))) return nullptr;
-        else return rk4_sweep_kernel<T, NW, CHECK, TRAJ, BLOCK, LDS, LOSS, WSUM>;
+        else if constexpr (ROW != 0 && (sizeof(T) != 8 || NW != 4 || TRAJ || LDS)) return nullptr;
+        else return rk4_sweep_kernel<T, NW, CHECK, TRAJ, BLOCK, LDS, LOSS, WSUM, ROW>;
     }
 };
 
@@ -915,7 +951,9 @@ template <typename T> struct OneLane {
 struct Pick {
     int n_waves, check, block;  // 4 | 6, CheckMode, 64 | 256
     bool traj, lds, lossless, wsum;
+    int row;                    // 0, or the save_every the kernel is compiled for (PSA_FIXED_ROW; launch_sweep_f64 sets it)
 };
+constexpr int PSA_FIXED_ROW = 10;   // the stride of the headline, of every driver default and of the goldens
 
 // What every layout shares, filled for one lane per point: the check mode, trajectory and per-wave summary (from the
 // buffers), LDS staging and BLOCK64 (LDS staging is always 64 threads; BLOCK64 is rejected with the per-wave summary,
@@ -931,6 +969,7 @@ static Pick pick_one_lane(int n_waves, uint32_t flags, const SweepArgs<T> &a) {
     p.lds = (flags & PSA_OPT_LDS_STAGING) != 0;
     p.lossless = (flags & PSA_OPT_LOSSLESS) && !p.lds;
     p.block = (p.lds || (flags & PSA_OPT_BLOCK64)) ? 64 : 256;
+    p.row = 0;
     return p;
 }
 
@@ -954,7 +993,8 @@ static hipError_t launch_family(hipStream_t s, const Pick &p, const SweepArgs<T>
     return with_bool(p.lds, [&](auto lds) {
     return with_bool(p.lossless, [&](auto lossless) {
     return with_bool(p.wsum, [&](auto wsum) {
-        constexpr auto k = Family::template kernel<nw, check, traj, blk, lds, !lossless, wsum>();
+    return with_int<PSA_FIXED_ROW, 0>(p.row, [&](auto row) {
+        constexpr auto k = Family::template kernel<nw, check, traj, blk, lds, !lossless, wsum, row>();
         if constexpr (std::is_null_pointer_v<std::remove_const_t<decltype(k)>>) {
             return hipErrorInvalidDeviceFunction;   // no such instantiation: the layout choice never picks one
         } else {   // by the kernel's address: a <<< >>> call through a pointer is lost in the host-sanitizer build
@@ -962,7 +1002,7 @@ static hipError_t launch_family(hipStream_t s, const Pick &p, const SweepArgs<T>
             (void)hipLaunchKernel(reinterpret_cast<const void *>(k), grid, block, args, 0, s);
             return hipGetLastError();
         }
-    }); }); }); }); }); }); });
+    }); }); }); }); }); }); }); });
 }
 
 }  // namespace psa

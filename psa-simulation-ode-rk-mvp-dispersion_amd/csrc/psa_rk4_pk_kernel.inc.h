@@ -99,9 +99,9 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_pk_kernel(const SweepArgs<flo
 // without trajectory, in 256-thread workgroups.
 struct PackedPoints {
     static long long lanes(long long n_points) { return (n_points + 1) / 2; }
-    template <int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS, bool LOSS, bool WSUM>
+    template <int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS, bool LOSS, bool WSUM, int ROW = 0>
     static constexpr auto kernel() {
-        if constexpr (LDS || !LOSS || (WSUM && (TRAJ || BLOCK != 256))) return nullptr;
+        if constexpr (ROW != 0 || LDS || !LOSS || (WSUM && (TRAJ || BLOCK != 256))) return nullptr;
         else return rk4_sweep_pk_kernel<NW, CHECK, TRAJ, BLOCK, WSUM>;
     }
 };

@@ -151,9 +151,9 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_quad_kernel(const SweepArgs<d
 // Four lanes per point: the 4-wave model's register layout only; the per-wave summary without trajectory.
 struct QuadLanes {
     static long long lanes(long long n_points) { return 4 * n_points; }
-    template <int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS, bool LOSS, bool WSUM>
+    template <int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS, bool LOSS, bool WSUM, int ROW = 0>
     static constexpr auto kernel() {
-        if constexpr (NW != 4 || LDS || (WSUM && TRAJ)) return nullptr;
+        if constexpr (ROW != 0 || NW != 4 || LDS || (WSUM && TRAJ)) return nullptr;
         else return rk4_sweep_quad_kernel<CHECK, TRAJ, BLOCK, LOSS, WSUM>;
     }
 };

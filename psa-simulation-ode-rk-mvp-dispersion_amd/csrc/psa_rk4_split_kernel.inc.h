@@ -123,7 +123,8 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_split_kernel(const SweepArgs<
     // of each point, the odd lane leaves.  The z-loop is issue-bound, so what counts is the wave's instruction stream, not
     // how many of its lanes work: 144 instructions per step instead of this kernel's 183.6.  And the record is then the
     // one-lane kernel's in every bit, whatever layout a sweep's size selects (the stage below pairs the products as
-    // A_u * A_v per lane, the one-lane kernel crosswise: on other points the two layouts agree to rounding).
+    // A_u * A_v per lane, the one-lane kernel crosswise: on other points the two layouts agree to rounding).  With the
+    // run-time row loop (ROW = 0) at every stride: the fixed-row form is the one-lane launch's, and moves no bit.
     if constexpr (NL == 2) {
         const bool same = __builtin_bit_cast(long long, y[0]) == __builtin_bit_cast(long long, y[2]) &&
                           __builtin_bit_cast(long long, y[1]) == __builtin_bit_cast(long long, y[3]);
@@ -261,9 +262,9 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_split_kernel(const SweepArgs<
 // Two lanes per point: register layout only; the per-wave summary without trajectory.
 struct SplitLanes {
     static long long lanes(long long n_points) { return 2 * n_points; }
-    template <int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS, bool LOSS, bool WSUM>
+    template <int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS, bool LOSS, bool WSUM, int ROW = 0>
     static constexpr auto kernel() {
-        if constexpr (LDS || (WSUM && TRAJ)) return nullptr;
+        if constexpr (ROW != 0 || LDS || (WSUM && TRAJ)) return nullptr;
         else return rk4_sweep_split_kernel<NW, CHECK, TRAJ, BLOCK, LOSS, WSUM>;
     }
 };

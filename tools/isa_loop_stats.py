@@ -6,7 +6,7 @@ mirrored).  For the float32 unit:  SRC=psa_rk4_f32.hi
 tools/isa_loop_stats.py /tmp/f32.s --top=2 rk4_sweep_pk_kernel  (valu = packed instructions per two-step trip and point pair).
 --row=SE --step=S [--trips=1,2,4] [--via=LABEL,...] walks ONE SAVED ROW of SE steps through the kernel's control flow instead: S the vector
 instructions of a step (144 mirrored loop, 288 general), --trips the steps per step block in the order a row runs them, the
-largest repeated (the row loop: 1,2,4; the event loop: 2,1).  Prints the instructions executed, those outside the steps, the
+largest repeated (the row loop: 1,2,4; the event loop: 2,1; the fixed-row loop, one block of SE steps: --trips=SE).  Prints the instructions executed, those outside the steps, the
 branches taken and the path (profiles/row_loop.log)."""
 import re, sys
 from collections import Counter
@@ -75,7 +75,9 @@ def row_walk(name, body, se, step, trips, via=()):
             if nd[4] and k + 1 < len(nodes):
                 succ.append((k + 1, 0))
             for n, tk in succ:
-                if n == s0 and done == len(seq) and v == len(via) and k != s0:   # back at the start, not by the trip's own back-edge: a row was passed
+                # back at the start, not by the trip's own back-edge: a row was passed (a row that is ONE block -- the fixed-row
+                # loop, --trips=SE -- closes on that block's own back-edge)
+                if n == s0 and done == len(seq) and v == len(via) and (k != s0 or len(seq) == 1):
                     cand = (ins, taken + tk, path)
                     best = min(best, cand) if best else cand
                     continue
