@@ -496,7 +496,8 @@ int psa_rk4_single_pump_f32_dev(void *stream, int64_t n_points, int64_t n_steps,
  * PSA_OPT_TRAJ_LD; anything else (a layout, float32 or LDS flag) is PSA_E_FLAGS.  n_lines outside 3..PSA_MAX_LINES:
  * PSA_E_NLINES, checked first; then the rules, codes and order of psa_rk4_single_pump_f64 with M in place of 3 (a trajectory
  * whose leading dimension ld has ld * 16 >= 2^32, or that does not fit the device's free memory: PSA_E_TOO_LARGE).  All of it
- * is checked before any device call; n_points == 0 is a successful no-op.  There is no float32, adaptive or chain form.
+ * is checked before any device call; n_points == 0 is a successful no-op.  Chains of spans are psa_rk4_comb_chain_f64 below;
+ * there is no float32 or adaptive form.
  */
 int psa_rk4_comb_f64(int device, int n_lines, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
                      const double *kappa, const double *gamma, const double *alpha, const double *a0_re_im,
@@ -619,6 +620,62 @@ int psa_rk4_pairs_chain_f64_dev(void *stream, int n_pairs, int64_t n_points, int
                                 double *d_traj_soa_or_null, void *d_workspace);
 /* bytes of d_workspace for a multi-channel chain; -1 for n_pairs outside 1..PSA_MAX_PAIRS or n_points < 0 */
 int64_t psa_rk4_pairs_chain_workspace_bytes(int n_pairs, int64_t n_points);
+
+/* ---- a chain of multi-line ("frequency comb") spans with mid-stage transfers (copier - mid-stage - PSA with every product) --
+ * psa_rk4_single_pump_chain_f64 for the multi-line model above: S = n_segments >= 1 spans of M = n_lines
+ * equally spaced lines, each span ONE launch of the unchanged multi-line kernel, joined on the device by the chain's epilogue
+ * kernel (no host synchronisation between spans).  Span s has
+ *   n_steps[s], seg_len[s]   host arrays [S]; each n_steps[s] in [1, 2^31) and a multiple of save_every (else
+ *                            PSA_E_SAVE_EVERY), each seg_len[s] positive and finite
+ *   kappa [S][N][M];  gamma, alpha  [S][N], or [S] with PSA_BCAST_GAMMA / PSA_BCAST_ALPHA
+ *   a0_re_im  [N][M][2] | [1][M][2] (PSA_BCAST_A0)
+ * and between span s and s+1 the per-line complex transfer T_s[m] (amplitude gain times e^{i phase}):
+ *   transfer_re_im  [S-1][N][M][2], or [S-1][M][2] with PSA_BCAST_TRANSFER; NULL = identity
+ * Gauge.  The field of line m is A_m e^{i Phi_m(z)}, Phi_m = Phi_{s,m} + kappa_{s,m} zeta on the span's local coordinate zeta,
+ * Phi_{s,m} = sum_{j<s} kappa_{j,m} L_j.  With B_m = A_m e^{+i Phi_{s,m}} for EVERY line, A_m e^{i Phi_m} = B_m e^{i kappa_{s,m}
+ * zeta}: the equations hold in B with the plain factors e^{+-i kappa_{s,m} zeta}, which is what the kernel integrates.  The kernel
+ * runs each span unchanged, a boundary is B'_m = T_s[m] B_m e^{+i kappa_{s,m} L_s}, and reported amplitudes and rows are rotated
+ * back by e^{-i Phi_{s,m}} on every line; powers need nothing.  Phi is kept per point and line in float64.  A span's kappa may
+ * be given in any gauge kappa + a_s + b_s m (another one per span): only kappa_k + kappa_l - kappa_n - kappa_m acts on A, so
+ * neither the powers nor the reported amplitudes depend on it.
+ * Outputs, all in the physical (A) frame:
+ *   a_end_re_im [N][M][2], p_wave_end [N][M]   the last saved row of the last span
+ *   p_wave_max  [N][M]    max over every saved row of every span (each span's z = 0 row is the post-transfer state),
+ *                         NaN-propagating
+ *   first_bad_step [N]    cumulative step index (the earlier spans' n_steps + the local index); the first failure wins
+ *   traj_or_null  [N][rows_total][M][2], rows_total = sum_s (n_steps[s]/save_every + 1); the host form pads the device
+ *                 buffer itself and brings it home in the sweep's chunks
+ * S == 1 is psa_rk4_comb_f64(_dev) itself, bit for bit: no workspace, no epilogue.  The host form sets PSA_OPT_LOSSLESS per
+ * span: for a broadcast alpha of 0, or (S > 1) a per-point row that is 0 everywhere.
+ * flags: the four PSA_BCAST_* bits, PSA_OPT_CHECK_NAN, PSA_OPT_EXACT_STEP, PSA_OPT_LOSSLESS, PSA_OPT_BLOCK64 and, on the
+ * `_dev` form only, PSA_OPT_TRAJ_LD; anything else (a layout, float32 or LDS flag) is PSA_E_FLAGS.  Every rule is checked
+ * before any device call, in the order n_segments < 1 (PSA_E_NSTEPS), n_steps / seg_len NULL, the multi-line rules on the
+ * first span's grid (n_lines: PSA_E_NLINES, the first of them; n_points, n_steps, seg_len, save_every, flags, pointers, a
+ * trajectory's ld * 16 < 2^32 else PSA_E_TOO_LARGE), then every span's n_steps, seg_len and save_every multiple; a trajectory
+ * that does not fit the device is PSA_E_TOO_LARGE (host form).  n_points == 0 is a successful no-op.  No new error code.
+ * There is no float32 or adaptive form.
+ */
+int psa_rk4_comb_chain_f64(int device, int n_lines, int64_t n_points, int n_segments, const int64_t *n_steps,
+                           const double *seg_len, int32_t save_every, const double *kappa, const double *gamma,
+                           const double *alpha, const double *a0_re_im, const double *transfer_re_im, uint32_t flags,
+                           double *a_end_re_im, double *p_wave_end, double *p_wave_max, int64_t *first_bad_step,
+                           double *traj_or_null, double *elapsed_ms_or_null);
+/* On SoA device buffers, asynchronous on `stream`, no allocation and no synchronisation: d_kappa_soa [S][M][N], d_gamma /
+ * d_alpha [S][N] | [S], d_a0_soa [2M][N | 1], d_transfer_soa [S-1][2M][N] (or [S-1][2M] with PSA_BCAST_TRANSFER),
+ * d_a_end_soa [2M][N], d_p_wave_end_soa / d_p_wave_max_soa [M][N], d_first_bad_step [N], d_traj_soa_or_null
+ * [rows_total][M][ld][2] with ld = N, or psa_traj_ld(N, 8) with PSA_OPT_TRAJ_LD; n_steps / seg_len stay HOST arrays.
+ * d_workspace: at least psa_rk4_comb_chain_workspace_bytes(n_lines, n_points) bytes of device memory (Phi 8 M N, the span's
+ * first_bad_step 8 N, the next a0 and the span's a_end 16 M N each, the span's two summaries 8 M N each, every slice rounded
+ * up to 256 B); NULL with S > 1 is PSA_E_NULLPTR, S == 1 needs none.  `_dev` callers pass PSA_OPT_LOSSLESS for the whole
+ * chain. */
+int psa_rk4_comb_chain_f64_dev(void *stream, int n_lines, int64_t n_points, int n_segments, const int64_t *n_steps,
+                               const double *seg_len, int32_t save_every, const double *d_kappa_soa,
+                               const double *d_gamma, const double *d_alpha, const double *d_a0_soa,
+                               const double *d_transfer_soa, uint32_t flags, double *d_a_end_soa,
+                               double *d_p_wave_end_soa, double *d_p_wave_max_soa, int64_t *d_first_bad_step,
+                               double *d_traj_soa_or_null, void *d_workspace);
+/* bytes of d_workspace for a multi-line chain; -1 for n_lines outside 3..PSA_MAX_LINES or n_points < 0 */
+int64_t psa_rk4_comb_chain_workspace_bytes(int n_lines, int64_t n_points);
 
 #ifdef __cplusplus
 }

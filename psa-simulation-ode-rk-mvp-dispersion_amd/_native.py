@@ -94,6 +94,10 @@ _SIGS = {
     **_family("psa_rk4_pairs_chain", [_I, _L, _I, _P, _P, _I32] + [_P] * 5 + [_U32] + [_P] * 5, host=[_P], dev=[_P],
               host_types=("f64",), dev_types=("f64",)),
     "psa_rk4_pairs_chain_workspace_bytes": (_L, [_I, _L]),
+    # n_lines, then the arguments of psa_rk4_single_pump_chain
+    **_family("psa_rk4_comb_chain", [_I, _L, _I, _P, _P, _I32] + [_P] * 5 + [_U32] + [_P] * 5, host=[_P], dev=[_P],
+              host_types=("f64",), dev_types=("f64",)),
+    "psa_rk4_comb_chain_workspace_bytes": (_L, [_I, _L]),
     "psa_yaman_rhs_f64": (_I, [_I, _L] + [_P] * 9),
     # N, p_metric, first_bad, p0_sig, gain_db, gain, best_index, best_gain, n_finite; dev: workspace
     **_family("psa_gain_summary", _GAIN, dev=[_P], host_types=("f64",), dev_types=("f64",)),
@@ -469,13 +473,18 @@ def comb_device(*, stream: int, n_lines: int, n_points: int, n_steps: int, z_max
 
 def _chain_host(stem: str, widths, sweep_family: bool, dbeta, *, n_steps, seg_len, save_every: int, gamma, alpha, a0,
                 transfers, dbeta2, check_nan: bool, exact_step: Optional[bool], want_traj: bool, dtype, device: int,
-                wave_summary: bool, extra_flags: int, pairs: bool = False) -> dict:
+                wave_summary: bool, extra_flags: int, pairs: bool = False, lines: bool = False) -> dict:
     """The host-buffer chain of a family: ``<stem>_f64`` / ``_f32`` on a0 of a width in ``widths``.  ``sweep_family``:
     the 4/6-wave entry points, which take n_waves and dbeta2, have p_end / p_max and put the per-wave summary last.
-    ``pairs``: the multi-channel entry point, whose dbeta is (S, N, K) and which takes K in front; K fixes the width."""
+    ``pairs``: the multi-channel entry point, whose dbeta is (S, N, K) and which takes K in front; K fixes the width.
+    ``lines``: the multi-line entry point, whose dbeta is (S, N, M), the lines' propagation constants, with M in front."""
     dtype, cdt, f64 = _dtypes(dtype)
     dbeta = np.ascontiguousarray(np.asarray(dbeta), dtype=dtype)
-    if pairs:
+    if lines:
+        if dbeta.ndim != 3 or dbeta.shape[0] < 1 or not 3 <= dbeta.shape[2] <= MAX_LINES:
+            raise ValueError(f"kappa must have shape (S, N, M) with 3 <= M <= {MAX_LINES}, got {dbeta.shape}")
+        widths = (int(dbeta.shape[2]),)
+    elif pairs:
         if dbeta.ndim != 3 or dbeta.shape[0] < 1 or not 1 <= dbeta.shape[2] <= MAX_PAIRS:
             raise ValueError(f"dbeta must have shape (S, N, K) with 1 <= K <= {MAX_PAIRS}, got {dbeta.shape}")
         widths = (2 + 2 * int(dbeta.shape[2]),)
@@ -513,7 +522,7 @@ def _chain_host(stem: str, widths, sweep_family: bool, dbeta, *, n_steps, seg_le
         _check(_fn(stem, f64)(int(device), nw, *grid, _ptr(d2), *point, _ptr(out["p_end"]), _ptr(out["p_max"]), *run,
                               _ptr(w_end), _ptr(w_max)))
         return dict(out, first_bad_step=bad, traj=traj, elapsed_ms=ms.value, p_wave_end=w_end, p_wave_max=w_max)
-    _check(_fn(stem, f64)(int(device), *((int(dbeta.shape[2]),) if pairs else ()), *grid, *point, _ptr(w_end), _ptr(w_max), *run))
+    _check(_fn(stem, f64)(int(device), *((int(dbeta.shape[2]),) if pairs or lines else ()), *grid, *point, _ptr(w_end), _ptr(w_max), *run))
     return dict(out, p_wave_end=w_end, p_wave_max=w_max, first_bad_step=bad, traj=traj, elapsed_ms=ms.value)
 
 
@@ -581,6 +590,36 @@ def pairs_chain_device(*, stream: int, n_pairs: int, n_points: int, n_steps, seg
     """psa_rk4_pairs_chain_f64_dev on device pointers (ints); n_steps / seg_len are host sequences of length S."""
     _chain_device("psa_rk4_pairs_chain", True, stream, (int(n_pairs), int(n_points)), n_steps, seg_len, (
         int(save_every), d_dbeta_soa or None, d_gamma or None, d_alpha or None, d_a0_soa or None, d_transfer_soa or None,
+        int(flags), d_a_end_soa or None, d_p_wave_end_soa or None, d_p_wave_max_soa or None, d_first_bad or None,
+        d_traj_soa or None, d_workspace or None))
+
+
+def comb_chain_host(dbeta, *, n_steps, seg_len, save_every: int, gamma, alpha, a0, transfers=None, check_nan: bool = True,
+                    exact_step: Optional[bool] = None, want_traj: bool = False, device: int = 0, extra_flags: int = 0) -> dict:
+    """A chain of S multi-line ("comb") spans on the GPU (psa_rk4_comb_chain_f64; host buffers in and out, float64): M equally
+    spaced lines with every FWM product among them, every line's phase accumulated across the spans.
+
+    dbeta (S, N, M) with 3 <= M <= 12: the lines' propagation constants kappa of every span, under the name every chain
+    wrapper gives its per-span array; n_steps, seg_len (S,); gamma / alpha (S,) broadcast or (S, N); a0 (M,) or (N, M) complex;
+    transfers None, (S-1, M) broadcast or (S-1, N, M) complex.  Returns the keys of comb_host; traj is (N, n_saved_total, M)."""
+    return _chain_host("psa_rk4_comb_chain", None, False, dbeta, n_steps=n_steps, seg_len=seg_len, save_every=save_every,
+                       gamma=gamma, alpha=alpha, a0=a0, transfers=transfers, dbeta2=None, check_nan=check_nan,
+                       exact_step=exact_step, want_traj=want_traj, dtype=np.float64, device=device, wave_summary=True,
+                       extra_flags=extra_flags, lines=True)
+
+
+def comb_chain_workspace_bytes(n_lines: int, n_points: int) -> int:
+    """Device scratch a multi-line chain of more than one span needs (psa_rk4_comb_chain_workspace_bytes)."""
+    return int(lib().psa_rk4_comb_chain_workspace_bytes(int(n_lines), int(n_points)))
+
+
+def comb_chain_device(*, stream: int, n_lines: int, n_points: int, n_steps, seg_len, save_every: int, d_kappa_soa: int,
+                      d_gamma: int, d_alpha: int, d_a0_soa: int, d_transfer_soa: int, flags: int, d_a_end_soa: int,
+                      d_p_wave_end_soa: int, d_p_wave_max_soa: int, d_first_bad: int, d_traj_soa: int = 0,
+                      d_workspace: int = 0) -> None:
+    """psa_rk4_comb_chain_f64_dev on device pointers (ints); n_steps / seg_len are host sequences of length S."""
+    _chain_device("psa_rk4_comb_chain", True, stream, (int(n_lines), int(n_points)), n_steps, seg_len, (
+        int(save_every), d_kappa_soa or None, d_gamma or None, d_alpha or None, d_a0_soa or None, d_transfer_soa or None,
         int(flags), d_a_end_soa or None, d_p_wave_end_soa or None, d_p_wave_max_soa or None, d_first_bad or None,
         d_traj_soa or None, d_workspace or None))
 

@@ -95,7 +95,8 @@ struct SinglePumpCall {   // psa_rk4_single_pump_f64*, psa_rk4_single_pump_f32* 
     int64_t *first_bad;
     T *traj;
 };
-struct CombCall {    // psa_rk4_comb_f64*
+struct CombCall {    // psa_rk4_comb_f64* and one span of a multi-line chain
+    using Real = double;
     int n_lines;
     int64_t n_points, n_steps;
     double z_max;
@@ -121,7 +122,8 @@ struct Rk45Call {    // psa_rk45_sweep_f64*
     int64_t traj_ld;   // leading dimension of the device rows: n_points (`_dev`), traj_ld_of (the host form's staging)
 };
 template <typename Span>
-struct ChainCall {   // psa_rk4_chain_* (Span = SweepCall<T>), psa_rk4_single_pump_chain_f64* (SinglePumpCall<double>), psa_rk4_pairs_chain_f64* (PairsCall)
+struct ChainCall {   // psa_rk4_chain_* (Span = SweepCall<T>), psa_rk4_single_pump_chain_f64* (SinglePumpCall<double>),
+                     // psa_rk4_pairs_chain_f64* (PairsCall), psa_rk4_comb_chain_f64* (CombCall)
     Span s;                     // what the spans share; its n_steps and z_max are set span by span from the arrays below
     int n_segments;
     const int64_t *n_steps;     // host [S]
@@ -818,8 +820,12 @@ template <> struct EpilogueLaunch<float> { static constexpr auto fn = psa::launc
 
 // What differs between the chain families, stated once per family: the span's record decides.
 template <typename Span> struct ChainFamily;
+// The array of a span's record whose values the gauge accumulates: dbeta, or the multi-line model's kappa.
+template <typename Span> auto mismatch_of(Span &c) -> decltype((c.dbeta)) { return c.dbeta; }
+inline const double *&mismatch_of(CombCall &c) { return c.kappa; }
+inline const double *mismatch_of(const CombCall &c) { return c.kappa; }
 template <typename T> struct ChainFamily<SweepCall<T>> {   // 4 and 6 waves [p1, p2, s, i, ...]
-    static constexpr int sig_wave = 2;
+    static constexpr int sig_wave = 2, sig_stride = 2;
     static constexpr bool signal_summary = true;      // p_end / p_max
     static constexpr bool waves_optional = true;      // the per-wave summary where p_wave_end / p_wave_max are given
     static constexpr bool second_mismatch = true;     // dbeta2 / theta2 (6 waves)
@@ -840,7 +846,7 @@ template <typename T> struct ChainFamily<SweepCall<T>> {   // 4 and 6 waves [p1,
     }
 };
 template <typename T> struct ChainFamily<SinglePumpCall<T>> {   // three waves [p, s, i]: the three per-wave columns are the summary
-    static constexpr int sig_wave = 1;
+    static constexpr int sig_wave = 1, sig_stride = 2;
     static constexpr bool signal_summary = false, waves_optional = false, second_mismatch = false, sweep_tail = false;
     static constexpr const char *what = "the single-pump fibre chain";
     static int n_waves(const SinglePumpCall<T> &) { return 3; }
@@ -859,7 +865,7 @@ template <typename T> struct ChainFamily<SinglePumpCall<T>> {   // three waves [
     }
 };
 template <> struct ChainFamily<PairsCall> {   // two pumps and K pairs [p1, p2, s_1, i_1, ..., s_K, i_K]: K signals, K mismatches
-    static constexpr int sig_wave = 2;
+    static constexpr int sig_wave = 2, sig_stride = 2;
     static constexpr bool signal_summary = false, waves_optional = false, second_mismatch = false;
     // one span is the sweep's trajectory form and keeps the sweep's rule: A[-1] is the last SAVED row, a tail may follow it
     static constexpr bool sweep_tail = true;
@@ -878,6 +884,28 @@ template <> struct ChainFamily<PairsCall> {   // two pumps and K pairs [p1, p2, 
     static void stage_summary(Staging<double> &sg, PairsCall &d, const PairsCall &c, size_t N) {
         d.wave_end = sg.output_soa(c.wave_end, N, n_waves(c));
         d.wave_max = sg.output_soa(c.wave_max, N, n_waves(c));
+        d.first_bad = sg.output(c.first_bad, N);
+    }
+};
+
+template <> struct ChainFamily<CombCall> {   // M lines, every one with its own accumulated phase: M "signals" at waves 0..M-1
+    static constexpr int sig_wave = 0, sig_stride = 1;
+    static constexpr bool signal_summary = false, waves_optional = false, second_mismatch = false, sweep_tail = false;
+    static constexpr const char *what = "the multi-line fibre chain";
+    static int n_waves(const CombCall &c) { return c.n_lines; }
+    static int n_signals(const CombCall &c) { return c.n_lines; }
+    static int dbeta_rows(const CombCall &c) { return c.n_lines; }   // a span's kappa is SoA [M][N]
+    static int validate_first(CombCall first, bool host_form) {
+        first.flags &= ~PSA_BCAST_TRANSFER;   // the chain's own bit
+        return validate_comb(first, host_form);
+    }
+    static int span_dev(void *stream, const CombCall &c) { return comb_dev(stream, c); }
+    static const double *stage_dbeta(Staging<double> &sg, const CombCall &c, int S, size_t N) {
+        return sg.input_soa(c.kappa, N, c.n_lines, S);                 // [S][N][M] -> [S][M][N]
+    }
+    static void stage_summary(Staging<double> &sg, CombCall &d, const CombCall &c, size_t N) {
+        d.wave_end = sg.output_soa(c.wave_end, N, c.n_lines);
+        d.wave_max = sg.output_soa(c.wave_max, N, c.n_lines);
         d.first_bad = sg.output(c.first_bad, N);
     }
 };
@@ -1050,7 +1078,8 @@ int chain_dev(void *stream, const ChainCall<Span> &c) {
     for (int s = 0; s < S; ++s) {
         const bool first = s == 0;
         set_span(s);
-        sp.dbeta = c.s.dbeta + s * (F::dbeta_rows(c.s) * N);
+        const T *const dbeta = mismatch_of(c.s) + s * (F::dbeta_rows(c.s) * N);
+        mismatch_of(sp) = dbeta;
         sp.gamma = c.s.gamma + s * g_step;
         sp.alpha = c.s.alpha + s * a_step;
         sp.a0 = first ? c.s.a0 : w.a0_next;
@@ -1066,9 +1095,10 @@ int chain_dev(void *stream, const ChainCall<Span> &c) {
         if constexpr (F::second_mismatch) sp.dbeta2 = c.s.dbeta2 ? c.s.dbeta2 + s * N : nullptr;
         rc = F::span_dev(stream, sp);
         if (rc != PSA_OK) return rc;
-        psa::ChainEpilogue<T> e = join.record(s, step_off, sp.traj, sp.n_steps / sp.save_every + 1, sp.dbeta, sp.z_max);
+        psa::ChainEpilogue<T> e = join.record(s, step_off, sp.traj, sp.n_steps / sp.save_every + 1, dbeta, sp.z_max);
         e.n_waves = n_waves;
         e.sig_wave = F::sig_wave;
+        e.sig_stride = F::sig_stride;
         e.p_end_s = w.p_end_s;
         e.p_max_s = w.p_max_s;
         e.wave_end_s = w.wend_s;
@@ -1079,7 +1109,7 @@ int chain_dev(void *stream, const ChainCall<Span> &c) {
         e.theta2 = w.theta2;
         e.sig_ld = (long long)N;
         e.p_end = e.p_max = nullptr;   // a family without the signal summary
-        e.dbeta2 = e.n_sig > 1 ? sp.dbeta + N : nullptr;   // the rows of one [K][N] block, or ...
+        e.dbeta2 = e.n_sig > 1 ? dbeta + N : nullptr;   // the rows of one [K][N] block, or ...
         if constexpr (F::signal_summary) {
             e.p_end = c.s.p_end;
             e.p_max = c.s.p_max;
@@ -1112,7 +1142,7 @@ int chain_host(int device, const ChainCall<Span> &c, double *elapsed_ms) {
     d.lossless = lossless.data();
     const T *tr = S > 1 ? c.transfer : nullptr;
     auto layout = [&](Staging<T> &sg) {
-        d.s.dbeta = F::stage_dbeta(sg, c.s, S, N);
+        mismatch_of(d.s) = F::stage_dbeta(sg, c.s, S, N);
         if constexpr (F::second_mismatch) d.s.dbeta2 = sg.input(c.s.dbeta2, S * N);
         d.s.gamma = sg.input(c.s.gamma, (flags & PSA_BCAST_GAMMA) ? (size_t)S : S * N);
         d.s.alpha = sg.input(c.s.alpha, (flags & PSA_BCAST_ALPHA) ? (size_t)S : S * N);
@@ -1140,6 +1170,10 @@ int64_t single_pump_chain_workspace_bytes(int64_t n_points) {
 int64_t pairs_chain_workspace_bytes(int n_pairs, int64_t n_points) {
     if (n_pairs < 1 || n_pairs > PSA_MAX_PAIRS || n_points < 0) return -1;
     return (int64_t)ChainScratch<double>(nullptr, (size_t)n_points, 2 + 2 * n_pairs, false, false, true, n_pairs).bytes;
+}
+int64_t comb_chain_workspace_bytes(int n_lines, int64_t n_points) {
+    if (n_lines < 3 || n_lines > PSA_MAX_LINES || n_points < 0) return -1;
+    return (int64_t)ChainScratch<double>(nullptr, (size_t)n_points, n_lines, false, false, true, n_lines).bytes;
 }
 
 template <typename T> struct GainLaunch;
@@ -1722,5 +1756,25 @@ int psa_rk4_comb_f64_dev(void *stream, int n_lines, int64_t n_points, int64_t n_
     return comb_dev(stream, {n_lines, n_points, n_steps, z_max, save_every, d_kappa_soa, d_gamma, d_alpha, d_a0_soa, flags,
                              d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step, d_traj_soa_or_null});
 }
+
+int psa_rk4_comb_chain_f64(int device, int n_lines, int64_t n_points, int n_segments, const int64_t *n_steps, const double *seg_len,
+                           int32_t save_every, const double *kappa, const double *gamma, const double *alpha,
+                           const double *a0_re_im, const double *transfer_re_im, uint32_t flags, double *a_end_re_im,
+                           double *p_wave_end, double *p_wave_max, int64_t *first_bad_step, double *traj_or_null,
+                           double *elapsed_ms_or_null) {
+    return chain_host<CombCall>(device, {{n_lines, n_points, 0, 0.0, save_every, kappa, gamma, alpha, a0_re_im, flags, a_end_re_im,
+                                         p_wave_end, p_wave_max, first_bad_step, traj_or_null},
+                                        n_segments, n_steps, seg_len, transfer_re_im, nullptr}, elapsed_ms_or_null);
+}
+int psa_rk4_comb_chain_f64_dev(void *stream, int n_lines, int64_t n_points, int n_segments, const int64_t *n_steps,
+                               const double *seg_len, int32_t save_every, const double *d_kappa_soa, const double *d_gamma,
+                               const double *d_alpha, const double *d_a0_soa, const double *d_transfer_soa, uint32_t flags,
+                               double *d_a_end_soa, double *d_p_wave_end_soa, double *d_p_wave_max_soa,
+                               int64_t *d_first_bad_step, double *d_traj_soa_or_null, void *d_workspace) {
+    return chain_dev<CombCall>(stream, {{n_lines, n_points, 0, 0.0, save_every, d_kappa_soa, d_gamma, d_alpha, d_a0_soa, flags,
+                                        d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step, d_traj_soa_or_null},
+                                       n_segments, n_steps, seg_len, d_transfer_soa, d_workspace});
+}
+int64_t psa_rk4_comb_chain_workspace_bytes(int n_lines, int64_t n_points) { return comb_chain_workspace_bytes(n_lines, n_points); }
 
 }  // extern "C"

@@ -9,8 +9,12 @@
 // (a_s a_i = b_s b_i e^{-i Theta_s}); `sig_wave` names the index, and that family has no p_end / p_max (both null).
 // K signals (the multi-channel model, psa_rk4_pairs_chain_*): the six-wave rule for every pair, signal k at wave 2 + 2k with
 // its own Theta^(k) = sum_{j<s} dbeta_{j,k} L_j; in the pumps' sum_k E_k A_sk A_ik every pair's phase cancels in its own term.
-// In general: `n_sig` signals at waves sig_wave + 2k, signal 0 with (theta, dbeta), signal k >= 1 with row k - 1 of
-// (theta2, dbeta2), rows `sig_ld` elements apart.
+// M lines (the multi-line model, psa_rk4_comb_chain_*): the field of line m is A_m e^{i Phi_m(z)}, Phi_m = Phi_{s,m} + kappa_{s,m}
+// zeta, Phi_{s,m} = sum_{j<s} kappa_{j,m} L_j, and EVERY line takes its own phase: B_m = A_m e^{+i Phi_{s,m}} turns the span's
+// equations into the kernel's (A o U = B o e^{i kappa_s zeta}).  That is the K-signal rule with M "signals" at consecutive waves
+// 0..M-1, kappa in the place of dbeta.
+// In general: `n_sig` signals at waves sig_wave + sig_stride * k (stride 2: an idler after every signal; 1: the comb), signal 0
+// with (theta, dbeta), signal k >= 1 with row k - 1 of (theta2, dbeta2), rows `sig_ld` elements apart.
 // At the boundary s -> s+1 the next span starts from B'_j = T_s[j] B_j, times e^{+i dbeta_s L_s} for the signal(s);
 // reported amplitudes are brought back to A with e^{-i Theta_s}.  Theta is kept per point in float64 in HBM for both
 // precisions (the kernels form dbeta*z in float64 as well).
@@ -47,7 +51,7 @@ __global__ void __launch_bounds__(256) chain_epilogue_kernel(ChainEpilogue<T> e)
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= e.n) return;
     const long long n = e.n;
-    const int nw = e.n_waves, sig = e.sig_wave;
+    const int nw = e.n_waves, sig = e.sig_wave, stride = e.sig_stride;
 
     if (e.fold) {
         if (e.p_max) {
@@ -64,7 +68,7 @@ __global__ void __launch_bounds__(256) chain_epilogue_kernel(ChainEpilogue<T> e)
         }
     }
 
-    // signal k: wave sig + 2k, its Theta and its mismatch
+    // signal k: wave sig + stride * k, its Theta and its mismatch
     auto theta_of = [&](const int k) -> double * { return k == 0 ? e.theta + i : e.theta2 + (long long)(k - 1) * e.sig_ld + i; };
     auto dbeta_of = [&](const int k) -> double {
         return (double)(k == 0 ? e.dbeta[i] : e.dbeta2[(long long)(k - 1) * e.sig_ld + i]);
@@ -75,7 +79,7 @@ __global__ void __launch_bounds__(256) chain_epilogue_kernel(ChainEpilogue<T> e)
 
     if (!e.first) {   // Theta_s = 0 in the first span: nothing to rotate (the `theta` buffers are not read there)
         for (int k = 0; k < e.n_sig; ++k) {
-            const int w = sig + 2 * k;
+            const int w = sig + stride * k;
             double c, s;
             sincos(-*theta_of(k), &s, &c);
             if (e.traj) {
@@ -93,8 +97,8 @@ __global__ void __launch_bounds__(256) chain_epilogue_kernel(ChainEpilogue<T> e)
     // boundary s -> s+1: B' = T_s B, signal k times e^{+i dbeta_s,k L_s}; Theta^(k) += dbeta_s,k L_s
     for (int w = 0; w < nw; ++w) {
         T re = e.a_end_s[(long long)(2 * w) * n + i], im = e.a_end_s[(long long)(2 * w + 1) * n + i];
-        const int k = (w - sig) / 2;
-        if (w >= sig && (w - sig) % 2 == 0 && k < e.n_sig) {
+        const int k = (w - sig) / stride;
+        if (w >= sig && (w - sig) % stride == 0 && k < e.n_sig) {
             double *th = theta_of(k);
             const double ph = dbeta_of(k) * e.seg_len;
             *th = (e.first ? 0.0 : *th) + ph;

@@ -172,8 +172,10 @@ template <typename T>
 struct ChainEpilogue {
     long long n;
     int n_waves;
-    int sig_wave;               // the first wave that carries a Theta: 2 (two pumps in front), 1 (3 waves)
-    int n_sig;                  // signals, at waves sig_wave + 2k: 1 (3 and 4 waves), 2 (6 waves), K (the multi-channel model)
+    int sig_wave;               // the first wave that carries a Theta: 2 (two pumps in front), 1 (3 waves), 0 (the comb)
+    int sig_stride;             // waves from one Theta-carrying wave to the next: 2 (an idler in between), 1 (the comb: every line)
+    int n_sig;                  // signals, at waves sig_wave + sig_stride * k: 1 (3 and 4 waves), 2 (6 waves), K (the multi-channel
+                                // model), M (the comb)
     int first;                  // span 0: Theta_0 = 0, no rotation, `theta` is initialised by the boundary
     int fold;                   // spans >= 1: fold the span's summary (the *_s buffers) into the running outputs
     const T *a_end_s;           // [2*NW][n] the span's a_end (B frame)

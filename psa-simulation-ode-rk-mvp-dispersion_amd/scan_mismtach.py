@@ -782,7 +782,7 @@ def scan_comb_gain(*, cfg: SimulationConfig, lambda_center_m: float, line_spacin
     The N sweep points are input-power settings: p_lines (M,) is one point, (N, M) is N of them (a dark line is 0 W);
     phase_in None or M phases.  One launch of the multi-line kernel (sweep.rk4_sweep_comb) on ``device``, or split over
     ``devices``; sharding over a ``torch.distributed`` process group is out of scope here -- every rank would run the whole
-    sweep -- and so are float32, RK45, chains and non-uniform grids.
+    sweep -- and so are float32, RK45 and non-uniform grids; the copier - PSA link is scan_comb_copier_psa_phase.
 
     Returns dict(gain (N, M) of every line over its input power -- NaN for a line with zero input --, p_end, p_max (N, M),
     kappa (M,) in 1/length_unit, omega (M,), first_bad_step (N,), result=CombResult)."""
@@ -1045,3 +1045,85 @@ def scan_wdm_copier_psa_phase(*, psa_cfg: SimulationConfig, copier_cfg: Optional
     return dict(phase=ph, gain=gain_db if unit == "db" else res.channel_gain(ps, mode=gain_mode, unit=unit),
                 idler=res.idler_conversion(ps, mode=gain_mode, unit=unit), gain_max_db=gmax, gain_min_db=gmin,
                 extinction_db=gmax - gmin, dbeta=np.stack(dbs), first_bad_step=res.first_bad_step, result=res)
+
+
+def scan_comb_copier_psa_phase(*, psa_cfg: SimulationConfig, copier_cfg: Optional[SimulationConfig] = None, lambda_center_m: float,
+                               line_spacing: float, p_lines, phase_in: Optional[Sequence[float]] = None, gamma: float,
+                               alpha: float, dispersion: DispersionParams, copier_dispersion: Optional[DispersionParams] = None,
+                               copier_gamma: Optional[float] = None, copier_alpha: Optional[float] = None, mid_gain_db=0.0,
+                               mid_phase=0.0, phase: Optional[Sequence[float]] = None, phase_lines: Sequence[int] = (),
+                               max_order: int = 4, length_unit: str = "m", gain_mode: GainMode = "max", gain_unit: str = "dB",
+                               device: Optional[int] = None, devices: Optional[Sequence[int]] = None) -> dict:
+    """scan_copier_psa_phase for the multi-line ("comb") model (no reference counterpart): the gain of every
+    line of a copier - mid-stage - PSA link against the mid-stage phase, with EVERY four-wave-mixing product on the grid --
+    what scan_wdm_copier_psa_phase leaves out: signal-signal crosstalk, the cascaded pump products, higher-order idlers.
+    M = 3..12 lines at omega_c + (m - (M-1)/2) * line_spacing (rad/s), omega_c from lambda_center_m, ascending in frequency;
+    per span kappa_m comes from simulation.comb_lines on that span's dispersion, as scan_comb_gain forms it.
+
+    An optional copier span (``copier_cfg``: length, dz; ``copier_dispersion`` / ``copier_gamma`` / ``copier_alpha`` default
+    to the PSA span's) generates the idlers; the mid-stage applies ``mid_gain_db`` / ``mid_phase`` (a scalar or M values) plus
+    the scanned ``phase`` (F values, default 32 over [0, 2 pi)) on the lines ``phase_lines`` (distinct indices 0..M-1, at
+    least one: the pumps, say); the PSA span (``psa_cfg``) then amplifies phase-sensitively.  The F phase points are the
+    sweep points: ONE launch per span (sweep.rk4_chain_comb) with a per-point transfer, on ``device`` or split over
+    ``devices``.  Without a copier the mid-stage acts on the input.  p_lines (M,) in W, a dark line is 0; phase_in None or M
+    phases; gamma / alpha per length_unit; save_every and check_nan come from psa_cfg (the copier's must agree, and every
+    span's step count must be a multiple of save_every).  Sharding over a process group is out of scope here.
+
+    Returns dict(phase (F,), gain (F, M) of every line over its input power -- NaN for a line with zero input, as
+    CombResult.line_gain --, p_out (F, M) the lines' powers at the end of the link, gain_max_db, gain_min_db, extinction_db
+    (M,): per line over the finite gains, kappa (S, M) in 1/length_unit, omega (M,), first_bad_step (F,),
+    result=CombChainResult)."""
+    from .frequency_plan import omega_from_lambda
+    from .simulation import _comb_phases, _comb_powers, comb_lines, comb_mid_stage
+    from .sweep import FibreSpan, initial_amplitudes, rk4_chain_comb
+    unit = check_gain(gain_mode, gain_unit)
+    ph, _ = _phase_scan_axes(phase, 0.0)
+    p = _comb_powers(p_lines, "p_lines")
+    if p.ndim != 1:
+        raise ValueError(f"p_lines must have shape (M,), got {p.shape}")
+    M = int(p.shape[0])
+    ph0 = _comb_phases(phase_in, M)
+    try:
+        lines = list(phase_lines)
+    except TypeError:
+        lines = []
+    if not lines or not all(isinstance(m, (int, np.integer)) and not isinstance(m, bool) and 0 <= m < M for m in lines) \
+            or len(set(int(m) for m in lines)) != len(lines):
+        raise ValueError(f"phase_lines must name at least one of the lines 0..{M - 1}, each once")
+    mask = np.zeros(M)
+    mask[lines] = 1.0
+    mg, mp = np.asarray(mid_gain_db, dtype=float), np.asarray(mid_phase, dtype=float)
+    if mg.shape not in ((), (M,)) or mp.shape not in ((), (M,)):
+        raise ValueError(f"mid_gain_db and mid_phase must be a scalar or hold {M} values")
+    if dispersion is None:
+        raise ValueError("dispersion must be provided")
+    wc = omega_from_lambda(lambda_center_m)
+    fibres = [(psa_cfg, gamma, alpha, dispersion)]
+    if copier_cfg is not None:
+        fibres.insert(0, (copier_cfg, gamma if copier_gamma is None else copier_gamma,
+                          alpha if copier_alpha is None else copier_alpha,
+                          dispersion if copier_dispersion is None else copier_dispersion))
+        if int(copier_cfg.save_every) != int(psa_cfg.save_every) or bool(copier_cfg.check_nan) != bool(psa_cfg.check_nan):
+            raise ValueError("copier_cfg and psa_cfg must share save_every and check_nan")
+    spans, kappas, omega = [], [], None
+    for cfg, g, a, d in fibres:
+        pre = _prepare(cfg, gamma=g, alpha=a, dispersion=d, phase_matching_cfg=None, beta_legacy=None, length_unit=length_unit)
+        fiber = pre["fiber"]
+        omega, kappa, _ = comb_lines(wc, line_spacing, M, fiber.dispersion, max_order=max_order)      # per metre
+        kappas.append(kappa * pre["scale"])
+        # per point: the F phase points are the sweep points, and a chain takes its point count from the spans and a0
+        spans.append(FibreSpan(fiber.length_m, dz=pre["grid"].dz_m, dbeta=np.broadcast_to(kappa, (ph.size, M)), gamma=fiber.gamma_W_m,
+                               alpha=fiber.alpha_1_m))
+    a_in = initial_amplitudes(p, ph0)
+    T = comb_mid_stage(np.broadcast_to(mg, (M,)), np.broadcast_to(mp, (M,))[None, :] + ph[:, None] * mask[None, :])   # (F, M)
+    a0, transfers = (T * a_in[None, :], None) if copier_cfg is None else (a_in, [T])
+    res = rk4_chain_comb(spans, a0=a0, transfers=transfers, save_every=int(psa_cfg.save_every),
+                         check_nan=bool(psa_cfg.check_nan), device=(0 if device is None else int(device)), devices=devices)
+    gain_db = res.line_gain(p, mode=gain_mode, unit="dB")
+    with np.errstate(all="ignore"):
+        some = np.isfinite(gain_db).any(axis=0)
+        gmax = np.where(some, np.max(np.where(np.isfinite(gain_db), gain_db, -np.inf), axis=0), np.nan)
+        gmin = np.where(some, np.min(np.where(np.isfinite(gain_db), gain_db, np.inf), axis=0), np.nan)
+    return dict(phase=ph, gain=gain_db if unit == "db" else res.line_gain(p, mode=gain_mode, unit=unit), p_out=res.p_wave_end,
+                gain_max_db=gmax, gain_min_db=gmin, extinction_db=gmax - gmin, kappa=np.stack(kappas), omega=omega,
+                first_bad_step=res.first_bad_step, result=res)

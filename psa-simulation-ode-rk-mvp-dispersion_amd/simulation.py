@@ -20,7 +20,8 @@ from .dispersion import DispersionParams, delta_beta_from_omegas_array
 from .integrators import integrate_adaptive, integrate_interval
 from .parameters import FiberParams, PhaseMatchingParams, SimulationGrid, WavesParams, make_model_params
 from .phase_matching import PhaseMatchingConfig, PhaseMatchingMethod, PhaseMatchingResult, compute_phase_mismatch  # noqa: F401
-from .sweep import FibreSpan, initial_amplitudes, rk4_chain, rk4_chain_single_pump, rk4_sweep_comb, rk4_sweep_single_pump
+from .sweep import (FibreSpan, initial_amplitudes, rk4_chain, rk4_chain_comb, rk4_chain_single_pump, rk4_sweep_comb,
+                    rk4_sweep_single_pump)
 from .yaman_model import rhs_yaman_simplified
 
 _UNITS = {"m": 1.0, "km": 1000.0}
@@ -346,8 +347,8 @@ def wdm_mid_stage(gain_db, phase) -> np.ndarray:
 
 
 def _run_spans(chain, fibre, cfgs, A0, transfers, length_unit, return_length_unit):
-    """The end of both run_concatenated_* functions: the rules the spans' configs and the transfers share, the chain call
-    (``chain``: rk4_chain or rk4_chain_single_pump, on A0's waves), the failure and the unit of z_out."""
+    """The end of every run_concatenated_* function: the rules the spans' configs and the transfers share, the chain call
+    (``chain``: rk4_chain, rk4_chain_single_pump or rk4_chain_comb, on A0's waves), the failure and the unit of z_out."""
     save_every, check_nan = int(cfgs[0].save_every), bool(cfgs[0].check_nan)
     if any(int(c.save_every) != save_every or bool(c.check_nan) != check_nan for c in cfgs):
         raise ValueError("all spans must share save_every and check_nan")
@@ -459,6 +460,47 @@ def run_concatenated_single_pump_simulation(spans, *, omega_pump: float, omega_s
         fibre.append(FibreSpan(length=fiber.length_m, dz=grid.dz_m, dbeta=dbeta, gamma=fiber.gamma_W_m, alpha=fiber.alpha_1_m))
         cfgs.append(sp["cfg"])
     return _run_spans(rk4_chain_single_pump, fibre, cfgs, A0, transfers, length_unit, return_length_unit)
+
+
+def comb_mid_stage(gain_db, phase) -> np.ndarray:
+    """mid_stage for the multi-line model's M = 3..12 lines, ascending in frequency: sqrt(10^(gain_db/10)) e^{i phase}.  The
+    last axis is the line (3..12 entries); leading axes (one row per sweep point) broadcast."""
+    return _mid_stage("comb_mid_stage", tuple(range(3, MAX_LINES + 1)), gain_db, phase)
+
+
+def run_concatenated_comb_simulation(spans, *, omega_center: float, line_spacing: float, p_in: Sequence[float],
+                                     phase_in: Optional[Sequence[float]] = None, transfers=None, length_unit: str = "m",
+                                     return_length_unit: Optional[str] = None) -> tuple[np.ndarray, np.ndarray]:
+    """run_comb_simulation over a chain of spans -> (z_out, A complex128 (n_saved_total, M)), lines ascending in frequency.
+
+    ``spans``: one mapping per span with ``cfg`` (SimulationConfig: length z_max, dz, save_every, check_nan), ``gamma``,
+    ``alpha`` and ``dispersion`` (with an optional ``max_order``, default 4), all in ``length_unit``; the span's propagation
+    constants are comb_lines' kappa on that span's dispersion.  ``transfers``: None or S-1 complex (M,) per-line factors
+    (comb_mid_stage).  Every line's phase accumulates over the spans; rows are those of every span in order, each span's
+    z = 0 row being the post-transfer state (z repeats at a boundary).  save_every and check_nan must agree between spans;
+    with check_nan a non-finite state raises FloatingPointError at the chain's step index."""
+    spans = list(spans)
+    if not spans:
+        raise ValueError("spans must name at least one span")
+    _length_scale_to_m(length_unit)
+    p = _comb_powers(p_in, "p_in")
+    if p.ndim != 1:
+        raise ValueError(f"p_in must have shape (M,), got {p.shape}")
+    M = int(p.shape[0])
+    A0 = initial_amplitudes(p, _comb_phases(phase_in, M))
+    fibre, cfgs = [], []
+    for k, sp in enumerate(spans):
+        sp = dict(sp)
+        unknown = set(sp) - {"cfg", "gamma", "alpha", "dispersion", "max_order"}
+        if unknown or "cfg" not in sp or "gamma" not in sp or "alpha" not in sp or sp.get("dispersion") is None:
+            raise ValueError(f"span {k}: needs cfg, gamma, alpha and dispersion (+ max_order); unknown keys {sorted(unknown)}")
+        pre = _prepare(sp["cfg"], gamma=sp["gamma"], alpha=sp["alpha"], dispersion=sp["dispersion"], phase_matching_cfg=None,
+                       beta_legacy=None, length_unit=length_unit)
+        fiber, grid = pre["fiber"], pre["grid"]
+        _, kappa, _ = comb_lines(omega_center, line_spacing, M, fiber.dispersion, max_order=sp.get("max_order", 4))
+        fibre.append(FibreSpan(length=fiber.length_m, dz=grid.dz_m, dbeta=kappa, gamma=fiber.gamma_W_m, alpha=fiber.alpha_1_m))
+        cfgs.append(sp["cfg"])
+    return _run_spans(rk4_chain_comb, fibre, cfgs, A0, transfers, length_unit, return_length_unit)
 
 
 # ---- the reference's two ready-made scenarios (simulation.py:371-447), km-unit path -----------------------

@@ -18,9 +18,10 @@ from . import _native
 from ._partition import CHAIN_AXES, COMB_AXES, PAIRS_AXES, PAIRS_CHAIN_AXES, SWEEP_AXES, over_devices
 from .config import AdaptiveConfig, n_steps_of
 
-__all__ = ["AdaptiveResult", "ChainResult", "CombResult", "FibreSpan", "PairsChainResult", "PairsResult", "SinglePumpChainResult",
-           "SinglePumpResult", "SweepResult", "check_gain", "initial_amplitudes", "rk4_chain", "rk4_chain_pairs",
-           "rk4_chain_single_pump", "rk4_sweep", "rk4_sweep_comb", "rk4_sweep_pairs", "rk4_sweep_single_pump", "rk45_sweep"]
+__all__ = ["AdaptiveResult", "ChainResult", "CombChainResult", "CombResult", "FibreSpan", "PairsChainResult", "PairsResult",
+           "SinglePumpChainResult", "SinglePumpResult", "SweepResult", "check_gain", "initial_amplitudes", "rk4_chain",
+           "rk4_chain_comb", "rk4_chain_pairs", "rk4_chain_single_pump", "rk4_sweep", "rk4_sweep_comb", "rk4_sweep_pairs",
+           "rk4_sweep_single_pump", "rk45_sweep"]
 
 
 def initial_amplitudes(p_in, phase_in=None) -> np.ndarray:
@@ -354,8 +355,8 @@ def rk4_sweep_comb(kappa, *, z_max: float, dz: Optional[float] = None, n_steps: 
     kappa (N, M): the lines' propagation constants in any gauge (kappa + a + b*m is the same system);  gamma / alpha a scalar
     or (N,); a0 (M,) or (N, M) complex.  ``dz`` gives n = int(round(z_max/dz)) as integrators.py:194; or pass ``n_steps``.
     With ``check_nan`` first_bad_step is the exact step.  ``want_traj`` also returns every saved row; ``devices=[0, 1, ...]``
-    splits the points over several GPUs of this process.  Fixed-step float64 on a uniform grid only: no float32, RK45, chain
-    or process-group form."""
+    splits the points over several GPUs of this process.  Fixed-step float64 on a uniform grid only: no float32, RK45 or
+    process-group form; chains of spans are rk4_chain_comb."""
     n_steps, save_every = _fixed_grid(z_max, dz, n_steps, save_every)
     kp = np.asarray(kappa, dtype=float)
     if kp.ndim != 2 or not 3 <= kp.shape[1] <= _native.MAX_LINES:
@@ -423,11 +424,12 @@ def _span_column(values, S: int, N: int, name: str, dtype) -> np.ndarray:
     return np.stack([np.broadcast_to(a, (N,)) for a in arrs]).astype(dtype)
 
 
-def _chain_inputs(spans, a0, transfers, save_every, widths, dtype, pairs=False):
+def _chain_inputs(spans, a0, transfers, save_every, widths, dtype, pairs=False, lines=False):
     """The span, a0 and transfer rules every chain shares, in rk4_chain's order -> (spans, save_every, dtype, N, n_waves,
     dbeta (S, N), dbeta2 (S, N) for 6 waves else None, gamma, alpha (S,) | (S, N), transfers None | (S-1, n_waves) |
     (S-1, N, n_waves), n_steps (S,), lengths (S,)).  ``pairs``: the multi-channel model, K = (n_waves - 2) / 2 mismatches per
-    span: a span's dbeta is (K,) for every point or (N, K), the returned dbeta (S, N, K), and dbeta2 is an error."""
+    span: a span's dbeta is (K,) for every point or (N, K), the returned dbeta (S, N, K), and dbeta2 is an error.  ``lines``: the
+    multi-line model, the same rules with K = n_waves: a span's dbeta holds the propagation constant of every line."""
     spans = list(spans)
     if not spans or not all(isinstance(s, FibreSpan) for s in spans):
         raise ValueError("spans must be a non-empty sequence of FibreSpan")
@@ -443,15 +445,18 @@ def _chain_inputs(spans, a0, transfers, save_every, widths, dtype, pairs=False):
     if a0.ndim not in (1, 2) or a0.shape[-1] not in widths:
         raise ValueError(f"a0 must have shape (n_waves,) or (N, n_waves) with n_waves in {tuple(widths)}")
     nw = int(a0.shape[-1])
+    what = "lines" if lines else "pairs"
+    pairs = pairs or lines   # from here on: a span's dbeta has K columns
     sizes = {int(np.size(v)) for s in spans for v in (s.gamma, s.alpha) + (() if pairs else (s.dbeta, s.dbeta2)) if v is not None}
     if pairs:
-        K = (nw - 2) // 2
+        K = nw if lines else (nw - 2) // 2
         if any(s.dbeta2 is not None for s in spans):
-            raise ValueError("the multi-channel model takes its K mismatches in dbeta: dbeta2 must be None")
+            raise ValueError("the multi-line model takes its M propagation constants in dbeta: dbeta2 must be None" if lines else
+                             "the multi-channel model takes its K mismatches in dbeta: dbeta2 must be None")
         for k, s in enumerate(spans):
             shape = np.shape(s.dbeta)
             if len(shape) not in (1, 2) or shape[-1] != K:
-                raise ValueError(f"span {k}: dbeta must have shape ({K},) or (N, {K}) for {K} pairs, got {shape}")
+                raise ValueError(f"span {k}: dbeta must have shape ({K},) or (N, {K}) for {K} {what}, got {shape}")
             if len(shape) == 2:
                 sizes.add(int(shape[0]))
     if a0.ndim == 2:
@@ -498,16 +503,17 @@ def _chain_inputs(spans, a0, transfers, save_every, widths, dtype, pairs=False):
 
 
 def _run_chain(host_name: str, widths, spans, a0, transfers, save_every, dtype, a0_dtype, device, devices, pairs=False,
-               **options):
+               lines=False, **options):
     """What every chain driver does: the shared input rules, the family's host call (looked up in _native when called) over
     the devices, and the grid of the saved rows -> (outputs, save_every, a0 as passed on, the _ChainGrid fields).  ``pairs``:
-    the multi-channel family (_chain_inputs' rules for it, PAIRS_CHAIN_AXES); otherwise the family is the 4/6-wave one where
-    6 is among ``widths`` and the single-pump one where it is not."""
+    the multi-channel family (_chain_inputs' rules for it, PAIRS_CHAIN_AXES), ``lines``: the multi-line family (the same
+    axes); otherwise the family is the 4/6-wave one where 6 is among ``widths`` and the single-pump one where it is not."""
     spans, save_every, dtype, N, nw, dbeta, dbeta2, gamma, alpha, tr, steps, lens = _chain_inputs(
-        spans, a0, transfers, save_every, widths, dtype, pairs=pairs)
+        spans, a0, transfers, save_every, widths, dtype, pairs=pairs, lines=lines)
     a0 = np.asarray(a0, dtype=a0_dtype)
     kw = dict(dbeta=dbeta, n_steps=steps, seg_len=lens, save_every=save_every, gamma=gamma, alpha=alpha, a0=a0,
               transfers=tr, **options)
+    pairs = pairs or lines
     if 6 in widths and not pairs:   # the 4/6-wave family
         kw.update(dbeta2=dbeta2, dtype=dtype)
     r = _run(getattr(_native, host_name), PAIRS_CHAIN_AXES if pairs else CHAIN_AXES, N, kw, device, devices)
@@ -583,6 +589,32 @@ def rk4_chain_pairs(spans: Sequence[FibreSpan], *, a0, transfers=None, save_ever
                                          check_nan=check_nan, exact_step=exact_step, want_traj=want_traj)
     return PairsChainResult(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"], int(grid["step_offsets"][-1]),
                             save_every, r["elapsed_ms"], np.abs(np.atleast_2d(a0)) ** 2, r.get("traj"), **grid)
+
+
+@dataclass
+class CombChainResult(_ChainGrid, CombResult):
+    """CombResult of a chain: rows of every span in order (each span's z = 0 row is the post-transfer state), amplitudes in
+    the physical frame, first_bad_step counted over the whole chain.  n_steps is the chain's total."""
+
+
+def rk4_chain_comb(spans: Sequence[FibreSpan], *, a0, transfers=None, save_every: int = 10, check_nan: bool = True,
+                   exact_step: Optional[bool] = None, want_traj: bool = False, device: int = 0,
+                   devices: Optional[Sequence[int]] = None) -> CombChainResult:
+    """Propagate N points of the multi-line ("frequency comb") model, lines 0..M-1 ascending in frequency, through a chain of
+    fibre spans (psa_rk4_comb_chain_f64): each span one launch of the multi-line kernel, EVERY line's phase
+    kappa_{s,m} L_s accumulated across spans, ``transfers[s]`` applied between span s and s+1 -- the copier - mid-stage - PSA
+    link with every FWM product on the grid: WDM crosstalk, cascaded pump products, higher-order idlers.
+
+    a0 (M,) or (N, M) complex fixes M in 3..12; a span's propagation constants go in ``FibreSpan.dbeta`` as (M,) for every
+    point or (N, M), in any gauge kappa + a_s + b_s*m per span (no output depends on it); transfers: None (identity),
+    or S-1 entries, each (M,) complex for every point or (N, M) per point (see simulation.comb_mid_stage).  Every span's
+    n_steps must be a multiple of ``save_every``; a span with dbeta2 is an error.  first_bad_step is the exact step
+    (``exact_step`` changes nothing).  float64 only."""
+    r, save_every, a0, grid = _run_chain("comb_chain_host", tuple(range(3, _native.MAX_LINES + 1)), spans, a0, transfers,
+                                         save_every, np.float64, np.complex128, device, devices, lines=True,
+                                         check_nan=check_nan, exact_step=exact_step, want_traj=want_traj)
+    return CombChainResult(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"], int(grid["step_offsets"][-1]),
+                           save_every, r["elapsed_ms"], np.abs(np.atleast_2d(a0)) ** 2, r.get("traj"), **grid)
 
 
 # ---- adaptive (RK45) sweeps ----------------------------------------------------------------------------------------
