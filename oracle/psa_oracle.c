@@ -266,8 +266,10 @@ int psa_oracle_sweep(int n_waves, int64_t n_points, double z_max, int64_t n_step
                      double *a_end, double *p_end, double *p_max, int64_t *first_bad_step, int n_threads) {
     if ((n_waves != 4 && n_waves != 6) || n_points < 0 || n_steps <= 0 || save_every <= 0) return -1;
 #ifdef _OPENMP
-    if (n_threads > 0) omp_set_num_threads(n_threads);
-#pragma omp parallel for schedule(dynamic, 4)
+    /* the request holds for this call alone: omp_set_num_threads would change the thread count of every later parallel
+     * region of the process (the other oracle library's runs went from 16 threads to 3 behind a sweep that asked for 3) */
+    const int threads = n_threads > 0 ? n_threads : omp_get_max_threads();
+#pragma omp parallel for schedule(dynamic, 4) num_threads(threads)
 #endif
     for (int64_t p = 0; p < n_points; ++p) {
         rhs_par par = {n_waves, gamma[p * gamma_stride], alpha[p * alpha_stride], dbeta[p],

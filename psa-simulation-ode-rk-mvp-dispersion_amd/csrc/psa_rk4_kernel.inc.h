@@ -474,8 +474,14 @@ __device__ __forceinline__ void sweep_point(const SweepArgs<T> &A, const long lo
     // middle -- and nothing is carried or re-seeded.  Moving
     // from the frame of one step to the next multiplies the sidebands by r = exp(i*dbeta*d), the same expression for both
     // (so the exchange of the members still permutes the outputs bit for bit).  Between steps the map is linear and exact:
-    // method, grid and truncation error are the reference's, only rounding moves (the modulus of the rounded r, <= 5.5e-17
-    // off one, now accumulates in the sidebands: ~5e-12 after 1e5 steps).  The record leaves the frame by conj(F(step)).
+    // method, grid and truncation error are the reference's, only rounding moves: the modulus of the rounded r, <= 5.5e-17
+    // off one, now accumulates in the sidebands -- ONE rotation per step, so their moduli are off by n (|r| - 1) of themselves,
+    // <= 5.5e-12 after 1e5 steps, as long as the pumps are undepleted (the equations are then linear in the sidebands).  That
+    // product is NOT a bound on the result: |r| - 1 acts as a gain error on both sidebands, and where they have grown to the
+    // pumps' scale the propagation carries it further.  Measured against an 80-bit run on G8's 64 mismatches at 1e5 steps:
+    // a_end off by up to 1.5e-11 of the point's largest wave, 2.7 n (|r| - 1); a scaling by each lane's own |r| planted into
+    // the 80-bit run gives 1.46e-11, by 1 + 5.5e-17 in every lane 2.1e-11 (tests/test_gpu_truth.py,
+    // tests/truth_cases.g8_long_frame_drift).  The record leaves the frame by conj(F(step)).
     auto rk4_step_on = [&](T (&y)[NS], T (&Er)[NP], T (&Ei)[NP]) {
         T Y2[NS], Y3[NS], Y4[NS], t[NS], D[NS];
         if constexpr (FRAME) {

@@ -17,6 +17,10 @@ Where a documented design choice makes an output miss the bar, the strict xfail 
 other outputs, the twin at RTOL_F64, first_bad_step and a band -- the bar plus the drift the kernel's header states for the
 choice -- are asserted as in every other case, and failing any of them fails the test.
 
+The cases at 100 000 steps (float64) and at 1e5 / 1e6 steps (float32) take yardstick and twins from a compiled plain RK4
+(oracle/plain_rk4.py, pinned in tests/test_truth_long_host.py); float32 has a second bar there, against a compensated float32
+twin of the kernel's kind, with no floor.
+
 Inputs, shapes and the cached 80-bit runs: tests/truth_cases.py.  Each case prints one line of the record
 (profiles/truth_errors.txt)."""
 import functools
@@ -49,7 +53,8 @@ def check(family, case, got, inputs, floor=TC.FLOOR_F64, rtol=RTOL_F64, known=()
         assert e.max() < rtol, (key, e.max())
     assert set(missed) <= set(known), "\n".join(missed[k][0] for k in missed if k not in known)
     for key, (line, med, mx, tmed, tmx) in missed.items():
-        assert med <= max(4.0 * tmed, floor) + budget and mx <= max(8.0 * tmx, floor) + budget, f"beyond the stated drift: {line}"
+        b_med, b_max = budget[key] if isinstance(budget, dict) else (budget, budget)   # one budget, or (median, max) per output
+        assert med <= max(4.0 * tmed, floor) + b_med and mx <= max(8.0 * tmx, floor) + b_max, f"beyond the stated drift: {line}"
     return missed
 
 
@@ -69,7 +74,7 @@ FRAME_DRIFT = (
     "the one-lane float64 4-wave step is frame-anchored (psa_rk4_kernel.inc.h, rk4_step_on): after every step the sidebands are "
     "multiplied by the rounded r = exp(i dbeta h/2), and |r| - 1 is a lane constant of ONE sign, up to 5.5e-17, so the sidebands' "
     "moduli drift by n (|r| - 1) -- up to 8e-14 of themselves after 1 500 steps, 5.5e-13 after 10 000 -- where a plain RK4's "
-    "random-walk.  The kernel header states the choice (5e-12 after 1e5 steps for 10 instructions per step).  This mark stands "
+    "random-walk.  The kernel header states the choice (5.5e-12 of the sidebands after 1e5 steps, for 10 instructions per step).  This mark stands "
     "in for a fix that has not been made.  Measured: ")
 CARRIED_U = (
     "the comb kernel carries u_m = exp(i kappa_m z) by two rotations per step between exact seeds 64 steps apart "
@@ -181,6 +186,7 @@ def test_single_pump_rows_at_every_step():
 
 
 COMB = [(M, True) for M in range(3, 13)] + [(M, False) for M in (3, 7, 10, 12)]
+COMB_LONG = [4, 7]                    # the same family at 100 000 steps (further down)
 
 
 @functools.lru_cache(maxsize=None)
@@ -210,6 +216,8 @@ def test_comb_family_meets_the_bar():
     for M, lossy in COMB:
         if M >= 4:
             missed.update({f"M{M}-{'lossy' if lossy else 'lossless'} {k}": v for k, v in _comb(M, lossy).items()})
+    for M in COMB_LONG:
+        missed.update({f"M{M}-lossy at 100 000 steps {k}": v for k, v in _comb_long(M).items()})
     meets_the_bar(missed)
 
 
@@ -220,8 +228,92 @@ def test_comb_without_dispersion():
     meets_the_bar(check("comb", "M7-lossy-kappa0", nat.comb_host(inputs["kappa"], **sweep_kw(inputs)), inputs))
 
 
+# ---- 100 000 steps, float64: the step count the headline runs --------------------------------------------------------------
+# 64 points (one wave of every lane layout; K = 16: 32 points, eight waves of its 16-lane groups) over 1000 m, the compiled
+# 80-bit run as the yardstick and its double instantiation as the twin (oracle/plain_rk4.py, pinned in
+# tests/test_truth_long_host.py).  The step count is what is under test: what a kernel carries between seeds must not accumulate.
+EVERY_OUTPUT = ("a_end",) + SIGNAL_POWER
+REGROUPING = 1e-13        # psa_rk4_kernel.inc.h: "the regrouping costs ~1 ulp(y) of rounding noise per step, ~1e-13 after 1e5 steps"
+G8_LONG_A0 = xfail(FRAME_DRIFT, "at 1e5 steps a_end max 1.50e-11 (25x the twin's), p_end median 2.9e-14 (32x) max 1.1e-12 (9.7x), "
+                                "p_max median 1.9e-14 (98x)")
+G8_LONG_A1 = xfail(FRAME_DRIFT, "at 1e5 steps a_end max 1.40e-11 (19x the twin's; median 4.5x..4.8x), p_end median 2.9e-14 (49x) max 1.5e-12 (11x), "
+                                "p_max median 5.7e-15..6.9e-15 (27x..33x); a_end's median by the fused step's regrouping, inside the "
+                                "header's 1e-13 for it")
+G8_LONG = [pytest.param("one_lane", False, 0, 10, marks=G8_LONG_A0), pytest.param("one_lane", False, 1, 10, marks=G8_LONG_A1),
+           pytest.param("one_lane", True, 0, 10, marks=G8_LONG_A0), pytest.param("one_lane", True, 1, 10, marks=G8_LONG_A1),
+           pytest.param("one_lane", True, 1, 7, marks=G8_LONG_A1),
+           ("split", False, 0, 10), ("split", False, 1, 10), ("quad", False, 0, 10), ("quad", False, 1, 10),
+           ("lds", False, 0, 10), ("lds", False, 1, 10)]
+
+
+@pytest.mark.parametrize("layout,mirrored,alpha_i,save_every", G8_LONG)
+def test_four_waves_at_100000_steps_on_the_g8_inputs(layout, mirrored, alpha_i, save_every):
+    """save_every = 10 in the one-lane layout is the straight-line ten-step-row loop the benchmark runs, 7 the run-time row loop.
+    The layouts that carry the phase factor between 64-step seeds meet the bar as they do at 1 500 steps: nothing accumulates
+    across seeds.  The one-lane cases miss by the frame's drift, and the band on them is that drift EVALUATED: the kernel header's
+    own |r| - 1 <= 5.5e-17 per step, planted into the 80-bit run of the same inputs (truth_cases.g8_long_frame_drift).  The plain
+    product n (|r| - 1) = 5.5e-12, which the header used to quote as the effect after 1e5 steps, holds for the sidebands' moduli
+    while the pumps are undepleted; on the points of this set where the sidebands have reached a tenth of the pumps the
+    propagation carries the same drift to 1.5e-11 of the largest wave (the kernel: 1.50e-11 / 1.40e-11 at alpha = 0 / > 0; each
+    lane's own |r| planted on the CPU: 1.46e-11 / 1.33e-11; the bound 5.5e-17 in every lane, the band: 2.07e-11 / 1.75e-11).
+    The band on a MEDIAN is the planted run's median (4.7e-14..6.0e-14 on a_end), not its maximum.  That drift does not carry
+    a_end's median at alpha > 0 (6.6e-13, 4.5x..4.8x the twin's 1.4e-13): half the points have no sidebands to speak of.  What
+    does is the fused step's regrouping, for which the same header states ~1e-13 after 1e5 steps; a_end's band has both."""
+    inputs = TC.g8_long(mirrored, alpha_i, save_every)
+    got = nat.sweep_host(inputs["dbeta"], extra_flags=LAYOUTS[layout], **sweep_kw(inputs))
+    if mirrored:
+        assert np.array_equal(got["a_end"][:, 1], got["a_end"][:, 0]) and np.array_equal(got["a_end"][:, 3], got["a_end"][:, 2])
+    frame = layout == "one_lane"
+    case = f"{layout}-{'mirrored' if mirrored else 'general'}-a{alpha_i}" + ("" if save_every == 10 else f"-save_every-{save_every}")
+    budget = TC.g8_long_frame_drift(mirrored, alpha_i, save_every, R_OFF_UNIT) if frame else 0.0
+    if frame:
+        print(f"\ntruth | waves4-g8-1e5 | {case} | the stated |r| - 1 = {R_OFF_UNIT:.1e} per step planted into the 80-bit run: "
+              + ", ".join(f"{k} median {v[0]:.2e} max {v[1]:.2e}" for k, v in budget.items())
+              + f" (n (|r| - 1) = {inputs['n_steps'] * R_OFF_UNIT:.1e}); a_end's band adds the regrouping's {REGROUPING:.0e}", end="")
+        budget = dict(budget, a_end=tuple(b + REGROUPING for b in budget["a_end"]))
+    meets_the_bar(check("waves4-g8-1e5", case, got, inputs, known=EVERY_OUTPUT if frame else (), budget=budget))
+
+
+@pytest.mark.parametrize("layout", ["one_lane", "split"])
+def test_six_waves_at_100000_steps(layout):
+    inputs = TC.waves6_long()
+    got = nat.sweep_host(inputs["dbeta"], dbeta2=inputs["dbeta2"], extra_flags=LAYOUTS[layout], **sweep_kw(inputs))
+    meets_the_bar(check("waves6-1e5", layout, got, inputs))
+
+
+@pytest.mark.parametrize("K", [3, 16])
+def test_pairs_at_100000_steps(K):
+    """K = 3: a padded group of four lanes; K = 16: the widest group."""
+    inputs = TC.pairs_long(K)
+    meets_the_bar(check("pairs-1e5", f"K{K}", nat.sweep_pairs_host(inputs["dbeta"], **sweep_kw(inputs)), inputs))
+
+
+def test_single_pump_at_100000_steps():
+    inputs = TC.single_pump_long()
+    meets_the_bar(check("single_pump-1e5", "lossy", nat.single_pump_host(inputs["dbeta"], **sweep_kw(inputs)), inputs))
+
+
+@functools.lru_cache(maxsize=None)
+def _comb_long(M):
+    inputs = TC.comb_long(M)
+    return check("comb-1e5", f"M{M}-lossy", nat.comb_host(inputs["kappa"], **sweep_kw(inputs)), inputs)
+
+
+@pytest.mark.parametrize("M", COMB_LONG)
+def test_comb_at_100000_steps(M):
+    """Every output at the bar, a_end included: the carried factor's drift between two seeds (1.4e-14) does not grow with the
+    number of seeds and is far inside a plain RK4's own 1e-13 here, so these cases need no band (M4 2.1x / 0.9x, M7 1.8x / 2.0x
+    of the twin).  They are still listed in the family's test, where they add nothing to what it expects."""
+    meets_the_bar(_comb_long(M))
+
+
+def test_comb_without_dispersion_at_100000_steps():
+    inputs = TC.comb_long(7, False)
+    meets_the_bar(check("comb-1e5", "M7-lossy-kappa0", nat.comb_host(inputs["kappa"], **sweep_kw(inputs)), inputs))
+
+
 # ---- chains ----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("family", ["waves", "single_pump", "pairs"])
+@pytest.mark.parametrize("family", ["waves", "single_pump", "pairs", "comb"])
 def test_chain(family):
     inputs = TC.chain(family)
     kw = TC.chain_arrays(inputs)
@@ -230,6 +322,8 @@ def test_chain(family):
         got = nat.chain_host(dbeta, want_traj=True, **kw)
     elif family == "single_pump":
         got = nat.single_pump_chain_host(dbeta, want_traj=True, **kw)
+    elif family == "comb":
+        got = nat.comb_chain_host(dbeta, want_traj=True, **kw)
     else:
         got = nat.pairs_chain_host(dbeta, want_traj=True, **kw)
     assert got["traj"].shape == inputs["truth"]["rows"].shape
@@ -237,11 +331,36 @@ def test_chain(family):
 
 
 # ---- float32 ---------------------------------------------------------------------------------------------------------------
+# Two bars.  The first, as above: no worse than a PLAIN float32 RK4 (floor 2e-6), with RTOL_F32 against the yardstick beside it.
+# The kernels sit 12x..30x below that twin, so it cannot see a compensated state that got lost.  The second holds the kernel to
+# the compensated float32 statement of its own kind -- Kahan for the scalar kernel, base + offset with a fold every 16 steps for
+# the packed ones (oracle/psa_plain_rk4.c) -- with NO floor, by the factors 4 and 8 on a_end and on every wave's power and by
+# 9.71 and 8 on wave 2's power alone, three times what the two compensated statements themselves differ by there
+# (truth_cases.bar_compensated; factors and planted defects: tests/test_truth_long_host.py).  The yardstick of the long cases is the compiled double run of the rounded inputs.
+F32_LAYOUTS = dict(packed=(nat.OPT_F32_PACKED, "base_offset"), scalar=(nat.OPT_F32_SCALAR, "kahan"))
+
+
+def check_float32(family, case, got, inputs, kind, plain_launch=None):
+    """Both float32 bars, every assertion of check included; the second on a_end and on every wave's end and maximum power.
+    ``plain_launch``: the same sweep without the per-wave summary (the instantiation the benchmark runs): its a_end and wave
+    2's p_end / p_max are held to the second bar too, the latter two by the factors of one wave alone
+    (truth_cases.factors_compensated).  Raises BarMissed for what misses either bar."""
+    assert got["a_end"].dtype == np.complex64 and got["p_wave_end"] is not None
+    missed = check(family, case, got, inputs, TC.FLOOR_F32, RTOL_F32)
+    second = TC.judge_compensated(family, case, got, inputs, kind)
+    if plain_launch is not None:
+        assert (plain_launch["first_bad_step"] == -1).all()
+        second.update({f"{k} without the per-wave summary": v for k, v in
+                       TC.judge_compensated(family, case + "-plain-launch", {k: plain_launch[k] for k in ("a_end", "p_end", "p_max")},
+                                            inputs, kind).items()})
+    meets_the_bar(missed)
+    meets_the_bar({f"{k} against the {kind} twin": v for k, v in second.items()})
+
+
 @pytest.mark.parametrize("layout,mirrored", [("packed", False), ("packed", True), ("scalar", False)])
 def test_four_waves_float32(layout, mirrored):
     inputs = TC.waves4_f32(mirrored)
-    got = nat.sweep_host(inputs["dbeta"], dtype=np.float32, extra_flags=dict(packed=nat.OPT_F32_PACKED, scalar=nat.OPT_F32_SCALAR)[layout],
-                         **sweep_kw(inputs))
+    got = nat.sweep_host(inputs["dbeta"], dtype=np.float32, extra_flags=F32_LAYOUTS[layout][0], **sweep_kw(inputs))
     assert got["a_end"].dtype == np.complex64
     meets_the_bar(check("waves4-f32", f"{layout}-{'mirrored' if mirrored else 'general'}", got, inputs, TC.FLOOR_F32, RTOL_F32))
 
@@ -251,3 +370,51 @@ def test_single_pump_float32():
     got = nat.single_pump_host(inputs["dbeta"], dtype=np.float32, **sweep_kw(inputs))
     assert got["a_end"].dtype == np.complex64
     meets_the_bar(check("single_pump-f32", "packed", got, inputs, TC.FLOOR_F32, RTOL_F32))
+
+
+def _sweep_f32(inputs, flags, wave_summary):
+    return nat.sweep_host(inputs["dbeta"], dbeta2=inputs.get("dbeta2"), dtype=np.float32, extra_flags=flags, wave_summary=wave_summary,
+                          **sweep_kw(inputs))
+
+
+@pytest.mark.parametrize("layout,mirrored", [("packed", False), ("packed", True), ("scalar", False)])
+def test_four_waves_float32_against_the_compensated_twin(layout, mirrored):
+    """The 1 500-step sets above under both bars, in a launch with the per-wave summary and in one without.  On the general set
+    the kernels' p_max sits at 4.0x..4.6x of the twin's median, inside the 9.71 that the two compensated statements' own spread
+    on one wave's power sets: the float32 kernels carry the phase factor between 16-step seeds where the twins take cosf / sinf
+    at every stage."""
+    inputs = TC.waves4_f32_compensated(mirrored)
+    flags, kind = F32_LAYOUTS[layout]
+    check_float32("waves4-f32", f"{layout}-{'mirrored' if mirrored else 'general'}", _sweep_f32(inputs, flags, True), inputs, kind,
+                  plain_launch=_sweep_f32(inputs, flags, False))
+
+
+def test_single_pump_float32_against_the_compensated_twin():
+    inputs = TC.single_pump_f32_compensated()
+    got = nat.single_pump_host(inputs["dbeta"], dtype=np.float32, **sweep_kw(inputs))
+    check_float32("single_pump-f32", "packed", got, inputs, "base_offset")
+
+
+CONFIG4 = [("mirrored", 100_000, "packed"), ("mirrored", 1_000_000, "packed"), ("general", 100_000, "packed"),
+           ("general", 1_000_000, "packed"), ("general", 100_000, "scalar"), ("strong", 100_000, "packed"), ("six", 100_000, "packed")]
+
+
+@pytest.mark.parametrize("powers,n_steps,layout", CONFIG4)
+def test_float32_config4_shaped(powers, n_steps, layout):
+    """17 points (8 packed lanes and the odd tail), dbeta from -0.02 to 0.02 over 1000 m, rows every 10 steps: config 4's powers
+    (the mirrored loop) at its 1e6 steps and at 1e5, the general loop on (0.1, 0.08, 1e-7, 1e-7), the scalar kernel, 0.5 / 0.4 W
+    pumps with 1e-5 W sidebands, and six waves.  Two launches: with the per-wave summary, and the benchmark's own without."""
+    inputs = TC.config4_f32(powers, n_steps)
+    flags, kind = F32_LAYOUTS[layout]
+    got, plain = _sweep_f32(inputs, flags, True), _sweep_f32(inputs, flags, False)
+    if powers == "mirrored":
+        for g in (got, plain):
+            assert np.array_equal(g["a_end"][:, 1], g["a_end"][:, 0]) and np.array_equal(g["a_end"][:, 3], g["a_end"][:, 2])
+    check_float32("config4-f32", f"{layout}-{powers}-{n_steps}", got, inputs, kind, plain_launch=plain)
+
+
+@pytest.mark.parametrize("n_steps", [100_000, 1_000_000])
+def test_single_pump_float32_long(n_steps):
+    inputs = TC.single_pump_f32_long(n_steps)
+    got = nat.single_pump_host(inputs["dbeta"], dtype=np.float32, **sweep_kw(inputs))
+    check_float32("single_pump-f32", f"packed-{n_steps}", got, inputs, "base_offset")
