@@ -65,8 +65,9 @@ extern "C" {
 /* The most signal/idler pairs of the multi-channel sweep (psa_rk4_sweep_pairs_*): one lane per pair, a point within one
  * 16-lane DPP row. */
 #define PSA_MAX_PAIRS    16
-/* The most lines of the multi-line ("comb") sweep (psa_rk4_comb_*): one point per lane with the whole state in registers;
- * 12 lines are the most that every instantiation holds without scratch memory. */
+/* The most lines of the multi-line ("comb") sweep (psa_rk4_comb_*): one point per lane (float64) or two (float32) with the
+ * whole state in registers and LDS; 12 lines are the most that every instantiation holds without scratch memory
+ * (DESIGN.md 3.3e, 3.3f). */
 #define PSA_MAX_LINES    12
 
 /* ---- flags ----------------------------------------------------------------- */
@@ -496,8 +497,8 @@ int psa_rk4_single_pump_f32_dev(void *stream, int64_t n_points, int64_t n_steps,
  * PSA_OPT_TRAJ_LD; anything else (a layout, float32 or LDS flag) is PSA_E_FLAGS.  n_lines outside 3..PSA_MAX_LINES:
  * PSA_E_NLINES, checked first; then the rules, codes and order of psa_rk4_single_pump_f64 with M in place of 3 (a trajectory
  * whose leading dimension ld has ld * 16 >= 2^32, or that does not fit the device's free memory: PSA_E_TOO_LARGE).  All of it
- * is checked before any device call; n_points == 0 is a successful no-op.  Chains of spans are psa_rk4_comb_chain_f64 below;
- * there is no float32 or adaptive form.
+ * is checked before any device call; n_points == 0 is a successful no-op.  Chains of spans are psa_rk4_comb_chain_f64 below
+ * (float64 only); psa_rk4_comb_f32 is the float32 form; there is no adaptive form.
  */
 int psa_rk4_comb_f64(int device, int n_lines, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
                      const double *kappa, const double *gamma, const double *alpha, const double *a0_re_im,
@@ -510,6 +511,24 @@ int psa_rk4_comb_f64_dev(void *stream, int n_lines, int64_t n_points, int64_t n_
                          const double *d_kappa_soa, const double *d_gamma, const double *d_alpha,
                          const double *d_a0_soa, uint32_t flags, double *d_a_end_soa, double *d_p_wave_end_soa,
                          double *d_p_wave_max_soa, int64_t *d_first_bad_step, double *d_traj_soa_or_null);
+/* The same sweep in float32: every buffer float, z_max and elapsed_ms double, first_bad_step int64.  Two sweep
+ * points per lane in packed math (points 2i and 2i+1 share lane i; any N, N = 1 included), every M = 3..PSA_MAX_LINES; classic
+ * RK4 on the un-fused right-hand side with a compensated state, u_m re-seeded from a float64-reduced phase every 16 steps
+ * (kappa is widened to double there, z is formed in double).  It is the one float32 layout of this model: PSA_OPT_F32_SCALAR
+ * and PSA_OPT_F32_PACKED are PSA_E_FLAGS like every other layout flag, the accepted flags are those of the _f64 forms, and
+ * PSA_OPT_LOSSLESS is a promise that selects no other kernel.  With PSA_OPT_CHECK_NAN first_bad_step is exact per point, as in
+ * float64.  A trajectory whose leading dimension ld (n_points, or psa_traj_ld(n_points, 4)) has ld * 8 >= 2^31 is
+ * PSA_E_TOO_LARGE, the bound of psa_rk4_sweep_f32; every other rule, code and their order are those of psa_rk4_comb_f64.
+ * Float32 pays from sweeps that fill the chip with two points per lane (DESIGN.md 3.3f has the measured rates per M). */
+int psa_rk4_comb_f32(int device, int n_lines, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+                     const float *kappa, const float *gamma, const float *alpha, const float *a0_re_im,
+                     uint32_t flags, float *a_end_re_im, float *p_wave_end, float *p_wave_max,
+                     int64_t *first_bad_step, float *traj_or_null, double *elapsed_ms_or_null);
+/* d_traj_soa_or_null [n_saved][M][ld][2] with ld = N, or psa_traj_ld(N, 4) with PSA_OPT_TRAJ_LD. */
+int psa_rk4_comb_f32_dev(void *stream, int n_lines, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+                         const float *d_kappa_soa, const float *d_gamma, const float *d_alpha,
+                         const float *d_a0_soa, uint32_t flags, float *d_a_end_soa, float *d_p_wave_end_soa,
+                         float *d_p_wave_max_soa, int64_t *d_first_bad_step, float *d_traj_soa_or_null);
 
 /* ---- a chain of single-pump spans with mid-stage transfers (copier - mid-stage - PSA on one pump) ------------------------
  * psa_rk4_chain_* for the three-wave model above: S = n_segments >= 1 spans, each ONE launch of the

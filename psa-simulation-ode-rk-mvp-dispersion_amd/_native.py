@@ -84,7 +84,7 @@ _SIGS = {
     # N, n_steps, z_max, save_every, dbeta, gamma, alpha, a0, flags, a_end, p_wave_end, p_wave_max, first_bad, traj; host: elapsed_ms
     **_family("psa_rk4_single_pump", [_L, _L, _D, _I32] + [_P] * 4 + [_U32] + [_P] * 5, host=[_P]),
     # n_lines, N, n_steps, z_max, save_every, kappa, gamma, alpha, a0, flags, a_end, p_wave_end, p_wave_max, first_bad, traj; host: elapsed_ms
-    **_family("psa_rk4_comb", [_I, _L, _L, _D, _I32] + [_P] * 4 + [_U32] + [_P] * 5, host=[_P], host_types=("f64",), dev_types=("f64",)),
+    **_family("psa_rk4_comb", [_I, _L, _L, _D, _I32] + [_P] * 4 + [_U32] + [_P] * 5, host=[_P]),
     # N, S, n_steps[S], seg_len[S], save_every, dbeta, gamma, alpha, a0, transfer, flags, a_end, p_wave_end, p_wave_max, first_bad,
     # traj; host: elapsed_ms; dev: workspace
     **_family("psa_rk4_single_pump_chain", [_L, _I, _P, _P, _I32] + [_P] * 5 + [_U32] + [_P] * 5, host=[_P], dev=[_P],
@@ -434,38 +434,41 @@ def single_pump_device(*, stream: int, n_points: int, n_steps: int, z_max: float
 
 
 def comb_host(kappa, *, n_steps: int, z_max: float, save_every: int, gamma, alpha, a0, check_nan: bool = True,
-              want_traj: bool = False, device: int = 0, extra_flags: int = 0) -> dict:
-    """N independent propagations of the multi-line ("comb") model on the GPU (psa_rk4_comb_f64; host buffers in and out,
-    float64): M equally spaced lines, ascending in frequency, with every FWM product among them that falls on the grid.
+              want_traj: bool = False, device: int = 0, extra_flags: int = 0, dtype=np.float64) -> dict:
+    """N independent propagations of the multi-line ("comb") model on the GPU (psa_rk4_comb_f64 or, with ``dtype=np.float32``,
+    psa_rk4_comb_f32; host buffers in and out): M equally spaced lines, ascending in frequency, with every FWM product among
+    them that falls on the grid.  Inputs are converted to ``dtype`` once and outputs come back in it, as in single_pump_host.
 
     kappa (N, M) with 3 <= M <= 12, the lines' propagation constants in any gauge; gamma / alpha scalar or (N,); a0 (M,) or
     (N, M) complex.  With check_nan first_bad_step is the exact step index (the point is tested after every step).
     Returns a_end (N, M) complex, p_wave_end, p_wave_max (N, M), first_bad_step (N,) int64, traj (N, n_saved, M) complex or
     None, elapsed_ms (kernel only)."""
-    kappa = np.ascontiguousarray(np.asarray(kappa), dtype=np.float64)
+    dtype, cdt, f64 = _dtypes(dtype)
+    kappa = np.ascontiguousarray(np.asarray(kappa), dtype=dtype)
     if kappa.ndim != 2 or not 3 <= kappa.shape[1] <= MAX_LINES:
         raise ValueError(f"kappa must have shape (N, M) with 3 <= M <= {MAX_LINES}, got {kappa.shape}")
     N, M = (int(x) for x in kappa.shape)
-    flags, gamma, alpha, a0, _ = _point_inputs(N, np.float64, np.complex128, int(extra_flags), gamma, alpha, a0, (M,))
-    flags |= _check_flags(check_nan, None)
+    flags, gamma, alpha, a0, _ = _point_inputs(N, dtype, cdt, int(extra_flags), gamma, alpha, a0, (M,))
+    flags |= _check_flags(check_nan, None, f64)   # float32 goes without PSA_OPT_EXACT_STEP: the kernel tests after every step anyway
     n_saved = int(n_steps) // int(save_every) + 1 if save_every > 0 else 0
-    a_end = np.empty((N, M), dtype=np.complex128)
-    w_end = np.empty((N, M), dtype=np.float64)
-    w_max = np.empty((N, M), dtype=np.float64)
+    a_end = np.empty((N, M), dtype=cdt)
+    w_end = np.empty((N, M), dtype=dtype)
+    w_max = np.empty((N, M), dtype=dtype)
     bad = np.empty(N, dtype=np.int64)
-    traj = np.empty((N, n_saved, M), dtype=np.complex128) if want_traj else None
+    traj = np.empty((N, n_saved, M), dtype=cdt) if want_traj else None
     ms = C.c_double(0.0)
-    _check(_fn("psa_rk4_comb")(int(device), M, N, int(n_steps), float(z_max), int(save_every), _ptr(kappa), _ptr(gamma),
-                               _ptr(alpha), _ptr(a0), flags, _ptr(a_end), _ptr(w_end), _ptr(w_max), _ptr(bad), _ptr(traj),
-                               C.cast(C.byref(ms), _P)))
+    _check(_fn("psa_rk4_comb", f64)(int(device), M, N, int(n_steps), float(z_max), int(save_every), _ptr(kappa), _ptr(gamma),
+                                    _ptr(alpha), _ptr(a0), flags, _ptr(a_end), _ptr(w_end), _ptr(w_max), _ptr(bad), _ptr(traj),
+                                    C.cast(C.byref(ms), _P)))
     return dict(a_end=a_end, p_wave_end=w_end, p_wave_max=w_max, first_bad_step=bad, traj=traj, elapsed_ms=ms.value)
 
 
 def comb_device(*, stream: int, n_lines: int, n_points: int, n_steps: int, z_max: float, save_every: int, d_kappa_soa: int,
                 d_gamma: int, d_alpha: int, d_a0_soa: int, flags: int, d_a_end_soa: int, d_p_wave_end_soa: int,
-                d_p_wave_max_soa: int, d_first_bad: int, d_traj_soa: int = 0) -> None:
-    """Asynchronous multi-line launch on device pointers (ints), SoA layout -- see psa_rk4_comb_f64_dev."""
-    _check(_fn("psa_rk4_comb", dev=True)(
+                d_p_wave_max_soa: int, d_first_bad: int, d_traj_soa: int = 0, dtype=np.float64) -> None:
+    """Asynchronous multi-line launch on device pointers (ints), SoA layout -- see psa_rk4_comb_f64_dev; ``dtype`` float32 is
+    psa_rk4_comb_f32_dev on float buffers."""
+    _check(_fn("psa_rk4_comb", _dtypes(dtype)[2], dev=True)(
         stream or None, int(n_lines), int(n_points), int(n_steps), float(z_max), int(save_every), d_kappa_soa or None,
         d_gamma or None, d_alpha or None, d_a0_soa or None, int(flags), d_a_end_soa or None, d_p_wave_end_soa or None,
         d_p_wave_max_soa or None, d_first_bad or None, d_traj_soa or None))

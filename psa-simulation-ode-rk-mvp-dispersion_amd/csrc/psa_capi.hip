@@ -95,17 +95,18 @@ struct SinglePumpCall {   // psa_rk4_single_pump_f64*, psa_rk4_single_pump_f32* 
     int64_t *first_bad;
     T *traj;
 };
-struct CombCall {    // psa_rk4_comb_f64* and one span of a multi-line chain
-    using Real = double;
+template <typename T>
+struct CombCall {    // psa_rk4_comb_f64*, psa_rk4_comb_f32* and one span of a multi-line chain
+    using Real = T;
     int n_lines;
     int64_t n_points, n_steps;
     double z_max;
     int32_t save_every;
-    const double *kappa, *gamma, *alpha, *a0;
+    const T *kappa, *gamma, *alpha, *a0;
     uint32_t flags;
-    double *a_end, *wave_end, *wave_max;
+    T *a_end, *wave_end, *wave_max;
     int64_t *first_bad;
-    double *traj;
+    T *traj;
 };
 struct Rk45Call {    // psa_rk45_sweep_f64*
     int n_waves;
@@ -123,7 +124,7 @@ struct Rk45Call {    // psa_rk45_sweep_f64*
 };
 template <typename Span>
 struct ChainCall {   // psa_rk4_chain_* (Span = SweepCall<T>), psa_rk4_single_pump_chain_f64* (SinglePumpCall<double>),
-                     // psa_rk4_pairs_chain_f64* (PairsCall), psa_rk4_comb_chain_f64* (CombCall)
+                     // psa_rk4_pairs_chain_f64* (PairsCall), psa_rk4_comb_chain_f64* (CombCall<double>)
     Span s;                     // what the spans share; its n_steps and z_max are set span by span from the arrays below
     int n_segments;
     const int64_t *n_steps;     // host [S]
@@ -745,9 +746,15 @@ int single_pump_host(int device, const SinglePumpCall<T> &c, double *elapsed_ms)
                              [&](hipStream_t st) { return single_pump_dev(st, d); });
 }
 
-// ---- the multi-line ("comb") sweep (psa_rk4_comb_f64*): n_lines equally spaced lines, every FWM product among them ------
-// host_form as in validate_single_pump, whose order this is with n_lines in front.
-int validate_comb(const CombCall &c, bool host_form) {
+// ---- the multi-line ("comb") sweep (psa_rk4_comb_f64* / _f32*): n_lines equally spaced lines, every FWM product among them
+template <typename T> struct CombLaunch;
+template <> struct CombLaunch<double> { static constexpr auto fn = psa::launch_sweep_comb_f64; };
+template <> struct CombLaunch<float> { static constexpr auto fn = psa::launch_sweep_comb_f32; };
+
+// host_form as in validate_single_pump, whose order this is with n_lines in front; float32 has one layout (two points per
+// lane), so PSA_OPT_F32_SCALAR / PSA_OPT_F32_PACKED are refused like every other layout flag.
+template <typename T>
+int validate_comb(const CombCall<T> &c, bool host_form) {
     if (c.n_lines < 3 || c.n_lines > PSA_MAX_LINES)
         return fail(PSA_E_NLINES, "n_lines must be in [3, %d], got %d", PSA_MAX_LINES, c.n_lines);
     int rc = validate_grid(c.n_points, PSA_MAX_POINTS, 0, c.n_steps, c.z_max, c.save_every);
@@ -762,44 +769,47 @@ int validate_comb(const CombCall &c, bool host_form) {
     if (c.traj) {
         // trajectory rows are addressed as a wave-uniform (row, line) base + the lane's 32-bit byte offset
         const bool padded = host_form || (c.flags & PSA_OPT_TRAJ_LD);
-        const unsigned long long ld = (unsigned long long)(padded ? traj_ld_of(c.n_points, sizeof(double)) : c.n_points);
-        if (ld * 16ull >= (1ull << 32))
+        const unsigned long long ld = (unsigned long long)(padded ? traj_ld_of(c.n_points, sizeof(T)) : c.n_points);
+        // float64: one 16-byte pair per lane below 2^32; float32: the packed sweep's bound, 8-byte pairs below 2^31
+        if (ld * 2ull * sizeof(T) >= (sizeof(T) == 8 ? 1ull << 32 : 1ull << 31))
             return fail(PSA_E_TOO_LARGE, "a multi-line trajectory launch takes a leading dimension below 2^28 points, got %llu", ld);
     }
     return PSA_OK;
 }
 
-int comb_dev(void *stream, const CombCall &c) {
+template <typename T>
+int comb_dev(void *stream, const CombCall<T> &c) {
     int rc = validate_comb(c, false);
     if (rc != PSA_OK) return rc;
     if (c.n_points == 0) return PSA_OK;
-    psa::CombArgs a;
+    psa::CombArgs<T> a;
     fill_shared_args(a, c);
     a.kappa = c.kappa;
     a.p_wave_end = c.wave_end;
     a.p_wave_max = c.wave_max;
     a.first_bad = (long long *)c.first_bad;
     a.traj = c.traj;
-    a.traj_ld = (c.flags & PSA_OPT_TRAJ_LD) ? traj_ld_of(c.n_points, sizeof(double)) : c.n_points;
+    a.traj_ld = (c.flags & PSA_OPT_TRAJ_LD) ? traj_ld_of(c.n_points, sizeof(T)) : c.n_points;
     a.n_steps = (int)c.n_steps;
     a.save_every = c.save_every;
     a.n_lines = c.n_lines;
-    hipError_t e = psa::launch_sweep_comb_f64((hipStream_t)stream, c.flags, a);
+    hipError_t e = CombLaunch<T>::fn((hipStream_t)stream, c.flags, a);
     if (e != hipSuccess) return hip_fail(e, "rk4_sweep_comb launch");
     return PSA_OK;
 }
 
-int comb_host(int device, const CombCall &c, double *elapsed_ms) {
+template <typename T>
+int comb_host(int device, const CombCall<T> &c, double *elapsed_ms) {
     int rc = validate_comb(c, true);
     if (rc != PSA_OK) return rc;
     if (elapsed_ms) *elapsed_ms = 0.0;
     if (c.n_points == 0) return PSA_OK;
     const int M = c.n_lines;
     const size_t N = (size_t)c.n_points;
-    CombCall d = c;
+    CombCall<T> d = c;
     if (c.traj) d.flags |= PSA_OPT_TRAJ_LD;   // the device-side trajectory has its own leading dimension; the caller's is dense
     d.flags |= lossless_bit(c.flags, c.alpha);
-    auto layout = [&](Staging<double> &sg) {
+    auto layout = [&](Staging<T> &sg) {
         d.kappa = sg.input_soa(c.kappa, N, M);                      // [N][M] -> [M][N]
         d.gamma = sg.input(c.gamma, (c.flags & PSA_BCAST_GAMMA) ? 1 : N);
         d.alpha = sg.input(c.alpha, (c.flags & PSA_BCAST_ALPHA) ? 1 : N);
@@ -810,7 +820,7 @@ int comb_host(int device, const CombCall &c, double *elapsed_ms) {
         d.first_bad = sg.output(c.first_bad, N);
         d.traj = sg.trajectory(c.traj, N, (size_t)(c.n_steps / c.save_every + 1), 2 * M);
     };
-    return host_call<double>(device, "the multi-line RK4 sweep", elapsed_ms, layout, [&](hipStream_t st) { return comb_dev(st, d); });
+    return host_call<T>(device, "the multi-line RK4 sweep", elapsed_ms, layout, [&](hipStream_t st) { return comb_dev(st, d); });
 }
 
 // ---- fibre chains: S spans, one sweep launch + one epilogue (psa_chain.hip) each ------------------------------------
@@ -822,8 +832,8 @@ template <> struct EpilogueLaunch<float> { static constexpr auto fn = psa::launc
 template <typename Span> struct ChainFamily;
 // The array of a span's record whose values the gauge accumulates: dbeta, or the multi-line model's kappa.
 template <typename Span> auto mismatch_of(Span &c) -> decltype((c.dbeta)) { return c.dbeta; }
-inline const double *&mismatch_of(CombCall &c) { return c.kappa; }
-inline const double *mismatch_of(const CombCall &c) { return c.kappa; }
+inline const double *&mismatch_of(CombCall<double> &c) { return c.kappa; }
+inline const double *mismatch_of(const CombCall<double> &c) { return c.kappa; }
 template <typename T> struct ChainFamily<SweepCall<T>> {   // 4 and 6 waves [p1, p2, s, i, ...]
     static constexpr int sig_wave = 2, sig_stride = 2;
     static constexpr bool signal_summary = true;      // p_end / p_max
@@ -888,22 +898,22 @@ template <> struct ChainFamily<PairsCall> {   // two pumps and K pairs [p1, p2, 
     }
 };
 
-template <> struct ChainFamily<CombCall> {   // M lines, every one with its own accumulated phase: M "signals" at waves 0..M-1
+template <> struct ChainFamily<CombCall<double>> {   // M lines, every one with its own accumulated phase: M "signals" at waves 0..M-1
     static constexpr int sig_wave = 0, sig_stride = 1;
     static constexpr bool signal_summary = false, waves_optional = false, second_mismatch = false, sweep_tail = false;
     static constexpr const char *what = "the multi-line fibre chain";
-    static int n_waves(const CombCall &c) { return c.n_lines; }
-    static int n_signals(const CombCall &c) { return c.n_lines; }
-    static int dbeta_rows(const CombCall &c) { return c.n_lines; }   // a span's kappa is SoA [M][N]
-    static int validate_first(CombCall first, bool host_form) {
+    static int n_waves(const CombCall<double> &c) { return c.n_lines; }
+    static int n_signals(const CombCall<double> &c) { return c.n_lines; }
+    static int dbeta_rows(const CombCall<double> &c) { return c.n_lines; }   // a span's kappa is SoA [M][N]
+    static int validate_first(CombCall<double> first, bool host_form) {
         first.flags &= ~PSA_BCAST_TRANSFER;   // the chain's own bit
         return validate_comb(first, host_form);
     }
-    static int span_dev(void *stream, const CombCall &c) { return comb_dev(stream, c); }
-    static const double *stage_dbeta(Staging<double> &sg, const CombCall &c, int S, size_t N) {
+    static int span_dev(void *stream, const CombCall<double> &c) { return comb_dev(stream, c); }
+    static const double *stage_dbeta(Staging<double> &sg, const CombCall<double> &c, int S, size_t N) {
         return sg.input_soa(c.kappa, N, c.n_lines, S);                 // [S][N][M] -> [S][M][N]
     }
-    static void stage_summary(Staging<double> &sg, CombCall &d, const CombCall &c, size_t N) {
+    static void stage_summary(Staging<double> &sg, CombCall<double> &d, const CombCall<double> &c, size_t N) {
         d.wave_end = sg.output_soa(c.wave_end, N, c.n_lines);
         d.wave_max = sg.output_soa(c.wave_max, N, c.n_lines);
         d.first_bad = sg.output(c.first_bad, N);
@@ -1746,15 +1756,31 @@ int psa_rk4_comb_f64(int device, int n_lines, int64_t n_points, int64_t n_steps,
                      const double *kappa, const double *gamma, const double *alpha, const double *a0_re_im, uint32_t flags,
                      double *a_end_re_im, double *p_wave_end, double *p_wave_max, int64_t *first_bad_step, double *traj_or_null,
                      double *elapsed_ms_or_null) {
-    return comb_host(device, {n_lines, n_points, n_steps, z_max, save_every, kappa, gamma, alpha, a0_re_im, flags, a_end_re_im,
-                              p_wave_end, p_wave_max, first_bad_step, traj_or_null}, elapsed_ms_or_null);
+    return comb_host(device, CombCall<double>{n_lines, n_points, n_steps, z_max, save_every, kappa, gamma, alpha, a0_re_im, flags,
+                                              a_end_re_im, p_wave_end, p_wave_max, first_bad_step, traj_or_null}, elapsed_ms_or_null);
 }
 int psa_rk4_comb_f64_dev(void *stream, int n_lines, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
                          const double *d_kappa_soa, const double *d_gamma, const double *d_alpha, const double *d_a0_soa,
                          uint32_t flags, double *d_a_end_soa, double *d_p_wave_end_soa, double *d_p_wave_max_soa,
                          int64_t *d_first_bad_step, double *d_traj_soa_or_null) {
-    return comb_dev(stream, {n_lines, n_points, n_steps, z_max, save_every, d_kappa_soa, d_gamma, d_alpha, d_a0_soa, flags,
-                             d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step, d_traj_soa_or_null});
+    return comb_dev(stream, CombCall<double>{n_lines, n_points, n_steps, z_max, save_every, d_kappa_soa, d_gamma, d_alpha, d_a0_soa,
+                                             flags, d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step,
+                                             d_traj_soa_or_null});
+}
+int psa_rk4_comb_f32(int device, int n_lines, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+                     const float *kappa, const float *gamma, const float *alpha, const float *a0_re_im, uint32_t flags,
+                     float *a_end_re_im, float *p_wave_end, float *p_wave_max, int64_t *first_bad_step, float *traj_or_null,
+                     double *elapsed_ms_or_null) {
+    return comb_host(device, CombCall<float>{n_lines, n_points, n_steps, z_max, save_every, kappa, gamma, alpha, a0_re_im, flags,
+                                             a_end_re_im, p_wave_end, p_wave_max, first_bad_step, traj_or_null}, elapsed_ms_or_null);
+}
+int psa_rk4_comb_f32_dev(void *stream, int n_lines, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
+                         const float *d_kappa_soa, const float *d_gamma, const float *d_alpha, const float *d_a0_soa,
+                         uint32_t flags, float *d_a_end_soa, float *d_p_wave_end_soa, float *d_p_wave_max_soa,
+                         int64_t *d_first_bad_step, float *d_traj_soa_or_null) {
+    return comb_dev(stream, CombCall<float>{n_lines, n_points, n_steps, z_max, save_every, d_kappa_soa, d_gamma, d_alpha, d_a0_soa,
+                                            flags, d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step,
+                                            d_traj_soa_or_null});
 }
 
 int psa_rk4_comb_chain_f64(int device, int n_lines, int64_t n_points, int n_segments, const int64_t *n_steps, const double *seg_len,
@@ -1762,7 +1788,7 @@ int psa_rk4_comb_chain_f64(int device, int n_lines, int64_t n_points, int n_segm
                            const double *a0_re_im, const double *transfer_re_im, uint32_t flags, double *a_end_re_im,
                            double *p_wave_end, double *p_wave_max, int64_t *first_bad_step, double *traj_or_null,
                            double *elapsed_ms_or_null) {
-    return chain_host<CombCall>(device, {{n_lines, n_points, 0, 0.0, save_every, kappa, gamma, alpha, a0_re_im, flags, a_end_re_im,
+    return chain_host<CombCall<double>>(device, {{n_lines, n_points, 0, 0.0, save_every, kappa, gamma, alpha, a0_re_im, flags, a_end_re_im,
                                          p_wave_end, p_wave_max, first_bad_step, traj_or_null},
                                         n_segments, n_steps, seg_len, transfer_re_im, nullptr}, elapsed_ms_or_null);
 }
@@ -1771,7 +1797,7 @@ int psa_rk4_comb_chain_f64_dev(void *stream, int n_lines, int64_t n_points, int 
                                const double *d_alpha, const double *d_a0_soa, const double *d_transfer_soa, uint32_t flags,
                                double *d_a_end_soa, double *d_p_wave_end_soa, double *d_p_wave_max_soa,
                                int64_t *d_first_bad_step, double *d_traj_soa_or_null, void *d_workspace) {
-    return chain_dev<CombCall>(stream, {{n_lines, n_points, 0, 0.0, save_every, d_kappa_soa, d_gamma, d_alpha, d_a0_soa, flags,
+    return chain_dev<CombCall<double>>(stream, {{n_lines, n_points, 0, 0.0, save_every, d_kappa_soa, d_gamma, d_alpha, d_a0_soa, flags,
                                         d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step, d_traj_soa_or_null},
                                        n_segments, n_steps, seg_len, d_transfer_soa, d_workspace});
 }

@@ -93,18 +93,19 @@ struct SinglePumpArgs {
     long long a0_ld;
 };
 
-// Everything one multi-line ("comb") sweep launch needs (n_lines equally spaced lines, ascending in frequency; float64, one
-// point per lane).  Strides as in SweepArgs; every output but the trajectory is always written.
+// Everything one multi-line ("comb") sweep launch needs (n_lines equally spaced lines, ascending in frequency; float64 one
+// point per lane, float32 two points per lane).  Strides as in SweepArgs; every output but the trajectory is always written.
+template <typename T>
 struct CombArgs {
-    const double *kappa;     // SoA [n_lines][N] propagation constant of every line, 1/length
-    const double *gamma;     // [N] | [1]
-    const double *alpha;     // [N] | [1]
-    const double *a0;        // SoA [2*n_lines][a0_ld]
-    double *a_end;           // SoA [2*n_lines][N]
-    double *p_wave_end;      // SoA [n_lines][N] |A_m|^2 at the last saved row
-    double *p_wave_max;      // SoA [n_lines][N] max over saved rows incl. z = 0 (NaN-propagating like np.max)
+    const T *kappa;          // SoA [n_lines][N] propagation constant of every line, 1/length
+    const T *gamma;          // [N] | [1]
+    const T *alpha;          // [N] | [1]
+    const T *a0;             // SoA [2*n_lines][a0_ld]
+    T *a_end;                // SoA [2*n_lines][N]
+    T *p_wave_end;           // SoA [n_lines][N] |A_m|^2 at the last saved row
+    T *p_wave_max;           // SoA [n_lines][N] max over saved rows incl. z = 0 (NaN-propagating like np.max)
     long long *first_bad;    // [N]
-    double *traj;            // [n_saved][n_lines][traj_ld][2] ((re, im) pairs) or nullptr
+    T *traj;                 // [n_saved][n_lines][traj_ld][2] ((re, im) pairs) or nullptr
     long long traj_ld;       // points per (row, line) region of traj: n_points, or padded (psa_traj_ld)
     long long n_points;
     double z_max;
@@ -137,11 +138,13 @@ hipError_t launch_sweep_single_pump_f64(hipStream_t s, uint32_t flags, const Sin
 hipError_t launch_sweep_single_pump_f32(hipStream_t s, uint32_t flags, const SinglePumpArgs<float> &a);
 // SIMDs (4 per CU) of the device a launch on s goes to (psa_rk4_single_pump.hip): what both launchers size their workgroups by
 int single_pump_simd_count(hipStream_t s);
-// Multi-line sweep launcher (psa_rk4_comb.hip): one launch on s, nothing for n_points == 0.  Reads PSA_OPT_CHECK_NAN (the test
-// runs after every step: PSA_OPT_EXACT_STEP selects nothing), LOSSLESS and BLOCK64 of `flags` and takes the trajectory from
-// a.traj being non-null; the caller has validated the arguments (3 <= n_lines <= PSA_MAX_LINES, with a trajectory
-// traj_ld * 16 < 2^32).
-hipError_t launch_sweep_comb_f64(hipStream_t s, uint32_t flags, const CombArgs &a);
+// Multi-line sweep launchers (psa_rk4_comb.hip: one lane per point; psa_rk4_comb_f32.hip: two points per lane): one launch on
+// s, nothing for n_points == 0.  They read PSA_OPT_CHECK_NAN (the test runs after every step: PSA_OPT_EXACT_STEP selects
+// nothing), LOSSLESS (float32 has one register layout: it selects nothing there) and BLOCK64 of `flags` and take the trajectory
+// from a.traj being non-null; the caller has validated the arguments (3 <= n_lines <= PSA_MAX_LINES, with a trajectory
+// traj_ld * 16 < 2^32 in float64 and traj_ld * 8 < 2^31 in float32).
+hipError_t launch_sweep_comb_f64(hipStream_t s, uint32_t flags, const CombArgs<double> &a);
+hipError_t launch_sweep_comb_f32(hipStream_t s, uint32_t flags, const CombArgs<float> &a);
 // Adaptive sweep launcher (psa_rk45.hip): one launch on s, nothing for n_points == 0; PSA_OPT_LOSSLESS is the only flag
 // it reads and the dense-output rows come from a.traj being non-null.  The caller has validated the arguments.
 hipError_t launch_rk45_sweep_f64(hipStream_t s, int n_waves, uint32_t flags, const AdaptiveArgs<double> &a);

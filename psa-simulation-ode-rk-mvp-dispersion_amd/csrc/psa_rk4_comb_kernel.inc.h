@@ -33,7 +33,7 @@
 // Per stage 6 M^2 + 10 M DP instructions (B: 4M, C_0: 2M, C_d: 2M(M-1), S: 4M^2 - 2M, conj(u) S: 4M, the links: 4M; 2M
 // fewer without loss), per step 4 stages + 6M (t) + 2M (update) + 8M (two rotations) = 24 M^2 + 56 M.
 //
-// Out of scope: float32, RK45, chains and transfers, lane-group layouts, process-group sharding, non-uniform grids.
+// Out of scope: RK45, lane-group layouts, process-group sharding, non-uniform grids.  (Float32: psa_rk4_comb_pk_kernel.inc.h.)
 #pragma once
 #include "psa_rk4_kernel.inc.h"
 
@@ -143,7 +143,7 @@ __device__ __forceinline__ void comb_step(double (&y)[2 * M], double (&ur)[M], d
 
 // The block size is the launch's (64 or 256 threads); both run this one instantiation.
 template <int M, bool CHECK, bool LOSS>
-__global__ void __launch_bounds__(256) rk4_sweep_comb_kernel(const CombArgs A) {
+__global__ void __launch_bounds__(256) rk4_sweep_comb_kernel(const CombArgs<double> A) {
     constexpr int NC = 2 * M;
     constexpr int RESYNC = Phase<double>::RESYNC;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -772,7 +772,7 @@ def scan_single_pump_gain(*, cfg: SimulationConfig, lambda_pump_m: float, lambda
 def scan_comb_gain(*, cfg: SimulationConfig, lambda_center_m: float, line_spacing: float, p_lines,
                    phase_in: Optional[Sequence[float]] = None, gamma: float, alpha: float, dispersion: DispersionParams,
                    max_order: int = 4, length_unit: str = "m", gain_unit: str = "dB", gain_mode: GainMode = "max",
-                   device: Optional[int] = None, devices: Optional[Sequence[int]] = None) -> dict:
+                   device: Optional[int] = None, devices: Optional[Sequence[int]] = None, dtype=np.float64) -> dict:
     """A multi-line ("comb") parametric amplifier (no reference counterpart): M = 3..12 lines at omega_c + (m - (M-1)/2) *
     line_spacing (rad/s), omega_c from lambda_center_m, ascending in frequency, coupled by EVERY four-wave-mixing product
     that falls on the grid: inter-channel crosstalk, the cascaded pump products at 2 w_1 - w_2 and 2 w_2 - w_1, higher-order
@@ -782,7 +782,10 @@ def scan_comb_gain(*, cfg: SimulationConfig, lambda_center_m: float, line_spacin
     The N sweep points are input-power settings: p_lines (M,) is one point, (N, M) is N of them (a dark line is 0 W);
     phase_in None or M phases.  One launch of the multi-line kernel (sweep.rk4_sweep_comb) on ``device``, or split over
     ``devices``; sharding over a ``torch.distributed`` process group is out of scope here -- every rank would run the whole
-    sweep -- and so are float32, RK45 and non-uniform grids; the copier - PSA link is scan_comb_copier_psa_phase.
+    sweep -- and so are RK45 and non-uniform grids; the copier - PSA link is scan_comb_copier_psa_phase (float64).
+    ``dtype=np.float32`` runs the packed float32 kernel (sweep.rk4_sweep_comb has from what N it pays): kappa is still formed
+    in float64 here, in the gauge kappa_0 = kappa_{M-1} = 0 that keeps |kappa| smallest, and rounded once; the outputs come back
+    in float32.  Any other dtype is a ValueError.
 
     Returns dict(gain (N, M) of every line over its input power -- NaN for a line with zero input --, p_end, p_max (N, M),
     kappa (M,) in 1/length_unit, omega (M,), first_bad_step (N,), result=CombResult)."""
@@ -790,6 +793,8 @@ def scan_comb_gain(*, cfg: SimulationConfig, lambda_center_m: float, line_spacin
     from .simulation import _comb_phases, _comb_powers, comb_lines
     from .sweep import initial_amplitudes, rk4_sweep_comb
     unit = check_gain(gain_mode, gain_unit)
+    if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError(f"dtype must be float64 or float32, got {np.dtype(dtype)}")
     p = np.atleast_2d(_comb_powers(p_lines, "p_lines"))
     N, M = (int(x) for x in p.shape)
     ph = _comb_phases(phase_in, M)
@@ -801,7 +806,8 @@ def scan_comb_gain(*, cfg: SimulationConfig, lambda_center_m: float, line_spacin
     omega, kappa, _ = comb_lines(omega_from_lambda(lambda_center_m), line_spacing, M, fiber.dispersion, max_order=max_order)
     res = rk4_sweep_comb(np.broadcast_to(kappa, (N, M)), z_max=fiber.length_m, n_steps=n_steps_of(fiber.length_m, grid.dz_m),
                          save_every=cfg.save_every, check_nan=bool(cfg.check_nan), gamma=fiber.gamma_W_m, alpha=fiber.alpha_1_m,
-                         a0=initial_amplitudes(p, ph), device=(0 if device is None else int(device)), devices=devices)
+                         a0=initial_amplitudes(p, ph), device=(0 if device is None else int(device)), devices=devices,
+                         dtype=dtype)
     return dict(gain=res.line_gain(p, mode=gain_mode, unit=unit), p_end=res.p_wave_end, p_max=res.p_wave_max,
                 kappa=kappa * pre["scale"], omega=omega, first_bad_step=res.first_bad_step, result=res)
 

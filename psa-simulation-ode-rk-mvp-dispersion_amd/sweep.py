@@ -345,7 +345,7 @@ class CombResult:
 
 def rk4_sweep_comb(kappa, *, z_max: float, dz: Optional[float] = None, n_steps: Optional[int] = None, save_every: int = 10,
                    check_nan: bool = True, gamma, alpha, a0, want_traj: bool = False, device: int = 0,
-                   devices: Optional[Sequence[int]] = None) -> CombResult:
+                   devices: Optional[Sequence[int]] = None, dtype=np.float64) -> CombResult:
     """Propagate N points of the CW multi-line ("frequency comb") model: M = 3..12 lines at w_0 + m dw, ascending in
     frequency, coupled by EVERY four-wave-mixing product k + l - n = m that falls on the grid -- SPM, XPM, pump-pump,
     pump-signal and signal-signal mixing (build-defined).  It is what the multi-channel model of
@@ -355,18 +355,26 @@ def rk4_sweep_comb(kappa, *, z_max: float, dz: Optional[float] = None, n_steps: 
     kappa (N, M): the lines' propagation constants in any gauge (kappa + a + b*m is the same system);  gamma / alpha a scalar
     or (N,); a0 (M,) or (N, M) complex.  ``dz`` gives n = int(round(z_max/dz)) as integrators.py:194; or pass ``n_steps``.
     With ``check_nan`` first_bad_step is the exact step.  ``want_traj`` also returns every saved row; ``devices=[0, 1, ...]``
-    splits the points over several GPUs of this process.  Fixed-step float64 on a uniform grid only: no float32, RK45 or
-    process-group form; chains of spans are rk4_chain_comb."""
+    splits the points over several GPUs of this process.
+    ``dtype=np.float32`` runs the packed float32 kernel (two points per lane) and returns float32 / complex64
+    arrays; kappa is rounded to float32 once, so pass it in a gauge that keeps |kappa| small.  It pays from sweeps that fill
+    the chip with two points per lane (131 072 points on one device; DESIGN.md 3.3f has the rates per M) and gains nothing on
+    smaller ones.  Any dtype but float64 and float32 is a ValueError.  Fixed-step on a uniform grid only: no RK45 or
+    process-group form; chains of spans are rk4_chain_comb, in float64."""
+    if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError(f"dtype must be float64 or float32, got {np.dtype(dtype)}")
     n_steps, save_every = _fixed_grid(z_max, dz, n_steps, save_every)
     kp = np.asarray(kappa, dtype=float)
     if kp.ndim != 2 or not 3 <= kp.shape[1] <= _native.MAX_LINES:
         raise ValueError(f"kappa must have shape (N, M) with 3 <= M <= {_native.MAX_LINES}, got {kp.shape}")
     N, M = (int(x) for x in kp.shape)
-    a0 = np.asarray(a0, dtype=np.complex128)
+    a0 = np.asarray(a0, dtype=np.complex128 if np.dtype(dtype) == np.dtype(np.float64) else np.complex64)
     if a0.shape not in ((M,), (1, M), (N, M)):
         raise ValueError(f"a0 must have shape ({M},) or ({N}, {M}) for {M} lines, got {a0.shape}")
     kw = dict(kappa=kp, n_steps=n_steps, z_max=float(z_max), save_every=save_every, gamma=gamma, alpha=alpha, a0=a0,
               check_nan=check_nan, want_traj=want_traj)
+    if np.dtype(dtype) != np.dtype(np.float64):
+        kw["dtype"] = np.float32          # the float64 call stays as it was: no dtype argument
     r = _run(_native.comb_host, COMB_AXES, N, kw, device, devices)
     return CombResult(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"], n_steps, save_every, r["elapsed_ms"],
                       np.abs(np.atleast_2d(a0)) ** 2, r.get("traj"))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Resources and timing of the multi-line ("comb") sweep kernels (psa_rk4_comb_f64) for DESIGN.md 3.3e.
+"""Resources and timing of the multi-line ("comb") sweep kernels (psa_rk4_comb_f64, psa_rk4_comb_f32) for DESIGN.md 3.3e, 3.3f.
 
   python tools/comb_timing.py --static   no GPU: compiles csrc/psa_rk4_comb.hip to gfx950 assembly with the Makefile's flags
       and prints, per instantiation, VGPRs, AGPRs, scratch, waves per SIMD and the VALU instructions of one RK4 step (the hot
@@ -9,6 +9,15 @@
       M in 3, 4, 6, 7, 9, 12 and the single-pump kernel at the same size, in one process: a warm-up launch of every candidate,
       then best of 3 of the kernel time the host entry reports (hipEvents on the launch stream); with the static counts the
       implied VALU issue rate next to the single-pump kernel's
+  python tools/comb_timing.py --f32 --static   the same counts for csrc/psa_rk4_comb_f32.hip (two points per lane), with the
+      static expectation of its time per point-step over the float64 kernel's, I_pk / (2 I_f64)
+  python tools/comb_timing.py --f32      on one MI355X, per M and in one process: (a) the float64 kernel at 65 536 points, (b) the
+      float32 kernel at 131 072 points (the same lanes), (c) the float32 kernel at 65 536 points; milliseconds, ps per
+      point-step and (b)/(a) per point-step beside the static expectation.  Then the accuracy pass on the parity tests' lossy
+      inputs (tests/comb_np.random_inputs, rounded to float32): worst |a_end(float32 kernel) - a_end(float64 kernel)| over the
+      point's largest line at 1 500, 10 000 and 100 000 steps.  PSA_HIP_LIB selects another build of the library for the same
+      run: EXTRA=-DPSA_COMB_F32_PLAIN (the plain y += inc state update), EXTRA=-DPSA_COMB_F32_RESYNC=8 (a shorter seed interval),
+      EXTRA=-DPSA_COMB_F32_NORENORM (u_m carried without the per-step renormalisation).
 """
 import argparse
 import os
@@ -80,6 +89,84 @@ def print_static(remarks):
     print(f"# worst scratch over the comb instantiations: {worst}")
 
 
+def comb_f32_static(remarks=None):
+    """{(M, check): counts} of every float32 comb instantiation."""
+    out = {}
+    for name, c in static_counts("psa_rk4_comb_f32.hip", "rk4_sweep_comb_pk_kernel", remarks).items():
+        m = re.search(r"ILi(\d+)ELb([01])E", name)
+        out[int(m.group(1)), m.group(2) == "1"] = c
+    return out
+
+
+def print_static_f32(remarks):
+    print("# static, float32 (two points per lane): registers, scratch, waves per SIMD and the VALU instructions of one RK4 step;")
+    print("# 24 M^2 + 69 M is the step's packed arithmetic for two points, + 2 M for the test; expectation = I_pk / (2 I_f64) as built")
+    f64 = comb_static()
+    worst = 0
+    for (M, check), c in sorted(comb_f32_static(remarks).items()):
+        worst = max(worst, c["scratch"])
+        print(f"M={M:2d} check={int(check)}  VGPRs {c['vgpr']:3d}  AGPRs {c['agpr']:3d}  scratch {c['scratch']}  waves/SIMD {c['occupancy']}  "
+              f"VALU/step {c['valu']:5d}  of them AGPR moves {c['acc']:4d}  (24 M^2 + 69 M = {24 * M * M + 69 * M})  "
+              f"expectation {c['valu'] / (2.0 * f64[M, check, True]['valu']):.3f}")
+    print(f"# worst scratch over the float32 comb instantiations: {worst}")
+
+
+def run_f32(args):
+    import numpy as np
+    import psa_amd._native as nat
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import comb_np
+    N, n_steps = args.points, args.steps
+    rng = np.random.default_rng(1)
+    grid = dict(n_steps=n_steps, z_max=0.1 * n_steps, save_every=10, gamma=0.0115, alpha=1.15e-4)
+
+    def comb(M, n, dtype):
+        x = np.arange(M) - 0.5 * (M - 1)
+        kappa = x ** 2 * rng.uniform(-2e-3, 5e-4, (n, 1)) + x ** 3 * rng.uniform(-1e-4, 1e-4, (n, 1))
+        p = np.full(M, 1e-5)
+        p[1] = p[M - 2] = 0.3
+        return lambda: nat.comb_host(kappa, a0=np.sqrt(p).astype(complex), dtype=dtype, **grid)
+
+    cands = {}
+    for M in args.lines:
+        cands[M, "a"] = comb(M, N, np.float64)
+        cands[M, "b"] = comb(M, 2 * N, np.float32)
+        cands[M, "c"] = comb(M, N, np.float32)
+    print(f"# {nat.version()} ({nat.LIB_PATH}); {n_steps} steps, save_every 10, check on, lossy, broadcast gamma / alpha / a0; (a) float64 "
+          f"{N} points, (b) float32 {2 * N} points, (c) float32 {N} points", flush=True)
+    times = {k: [] for k in cands}
+    for rep in range(args.repeats + 1):
+        for (M, which), fn in cands.items():
+            r = fn()
+            assert (r["first_bad_step"] == -1).all(), (M, which)
+            if rep:
+                times[M, which].append(r["elapsed_ms"])
+            print(f"  M={M} ({which}): launch {rep} {r['elapsed_ms']:9.3f} ms{'  (warm-up)' if not rep else ''}", flush=True)
+    f64, f32 = (None, None) if args.no_static else (comb_static(), comb_f32_static())
+    for M in args.lines:
+        best = {w: min(times[M, w]) for w in "abc"}
+        spread = {w: (max(times[M, w]) - best[w]) / best[w] for w in "abc"}
+        pts = dict(a=N, b=2 * N, c=N)
+        ps = {w: best[w] * 1e9 / n_steps / pts[w] for w in "abc"}
+        print(f"RESULT M={M}: (a) {best['a']:.3f} ms {ps['a']:.2f} ps/point-step (spread {spread['a']:.2%}); (b) {best['b']:.3f} ms "
+              f"{ps['b']:.2f} ps (spread {spread['b']:.2%}); (c) {best['c']:.3f} ms {ps['c']:.2f} ps (spread {spread['c']:.2%}); "
+              f"(b)/(a) per point-step {ps['b'] / ps['a']:.3f}; (c)/(a) {ps['c'] / ps['a']:.3f}"
+              + ("" if f32 is None else f"; static expectation {f32[M, True]['valu'] / (2.0 * f64[M, True, True]['valu']):.3f} (VALU/step "
+                 f"{f32[M, True]['valu']} of them AGPR moves {f32[M, True]['acc']}, float64 {f64[M, True, True]['valu']} / {f64[M, True, True]['acc']})"))
+    # accuracy: the float32 kernel against the float64 kernel on the same rounded inputs
+    for M in args.lines:
+        kappa, a0, gamma, alpha = comb_np.random_inputs(203, M, 100 * M + 3)
+        kappa, a0, gamma, alpha = kappa.astype(np.float32), a0.astype(np.complex64), gamma.astype(np.float32), alpha.astype(np.float32)
+        for steps in (1_500, 10_000, 100_000):
+            z_max = 300.0 if steps == 1_500 else 1000.0         # the fibres of the truth tests
+            kw = dict(n_steps=steps, z_max=z_max, save_every=10, gamma=gamma, alpha=alpha, a0=a0)
+            lo, hi = nat.comb_host(kappa, dtype=np.float32, **kw), nat.comb_host(kappa, **kw)
+            assert (lo["first_bad_step"] == -1).all() and (hi["first_bad_step"] == -1).all()
+            e = np.max(np.abs(lo["a_end"].astype(complex) - hi["a_end"]), axis=1) / np.max(np.abs(hi["a_end"]), axis=1)
+            print(f"ACCURACY M={M} {steps} steps over {z_max:g} m: a_end float32 against float64 kernel, median {np.median(e):.2e} "
+                  f"worst {e.max():.2e}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--static", action="store_true")
@@ -87,9 +174,15 @@ def main():
     ap.add_argument("--steps", type=int, default=STEPS)
     ap.add_argument("--points", type=int, default=POINTS)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--f32", action="store_true", help="the float32 kernel (two points per lane) beside the float64 one")
+    ap.add_argument("--lines", type=int, nargs="+", default=list(LINES), help="with --f32: the M to run")
+    ap.add_argument("--no-static", action="store_true", help="with --f32: leave the static expectation out (no compiler run)")
     args = ap.parse_args()
     if args.static:
-        print_static(args.remarks)
+        (print_static_f32 if args.f32 else print_static)(args.remarks)
+        return
+    if args.f32:
+        run_f32(args)
         return
     import numpy as np
     import psa_amd._native as nat
