@@ -156,7 +156,7 @@ def gain_from_summary(p_max, first_bad_step, p0_sig, unit="db"):
 # --------------------------------------------------------------------------
 def np_rhs(z, a, gamma, alpha, dbeta):
     """yaman_model.py:10-52 with 4-element arrays (same expression order)."""
-    lin = np.zeros_like(a) if alpha == 0.0 else (-0.5 * alpha) * a
+    lin = np.zeros_like(a) if np.ndim(alpha) == 0 and alpha == 0.0 else (-0.5 * alpha) * a
     p = np.abs(a) ** 2
     f = np.array([p[0] + 2.0 * (p[1] + p[2] + p[3]), p[1] + 2.0 * (p[0] + p[2] + p[3]),
                   p[2] + 2.0 * (p[0] + p[1] + p[3]), p[3] + 2.0 * (p[0] + p[1] + p[2])])

@@ -5,9 +5,10 @@ its own for every point, plus what the kernel adds: the max_steps cap (status 2)
 rows at np.linspace(0, z_max, n_out + 1).  Test infrastructure: no scipy, not imported by the package.  The right-hand
 sides are the oracle's NumPy statements (oracle.np_rhs, oracle.np_rhs6).
 
-    rk45(rhs, y0, z_max, rtol=..., atol=...) -> dict(a_end, p_end, p_max, status, z_end, n_accepted, n_rejected, traj)
+    rk45(rhs, y0, z_max, rtol=..., atol=...) -> dict(a_end, p_end, p_max, status, z_end, n_accepted, n_rejected, traj, steps)
 
-rhs(z[m], y[n, m], idx[m]) -> dy/dz [n, m] for the points idx (m of them); y0 is (n, N) complex.
+rhs(z[m], y[n, m], idx[m]) -> dy/dz [n, m] for the points idx (m of them); y0 is (n, N) complex.  steps: the accepted
+(z, h) pairs of the point ``record``, or None.
 """
 from __future__ import annotations
 
@@ -42,12 +43,21 @@ def _comb(K, w):
     return s
 
 
+def _alpha_of(alpha):
+    """alpha one scalar for all points (0.0 keeps the oracle's lossless branch) or (N,) -> idx -> the points' alpha."""
+    if np.ndim(alpha) == 0:
+        return lambda idx: float(alpha)
+    alpha = np.asarray(alpha, dtype=float)
+    return lambda idx: alpha[idx]
+
+
 def rhs4(dbeta, gamma, alpha):
-    """Four waves: oracle.np_rhs on (4, m) columns; alpha one scalar for all points."""
+    """Four waves: oracle.np_rhs on (4, m) columns; alpha a scalar or per point."""
     import oracle as O
     dbeta = np.asarray(dbeta, dtype=float)
     gamma = np.broadcast_to(np.asarray(gamma, dtype=float), dbeta.shape)
-    return lambda z, y, idx: O.np_rhs(z, y, gamma[idx], float(alpha), dbeta[idx])
+    al = _alpha_of(alpha)
+    return lambda z, y, idx: O.np_rhs(z, y, gamma[idx], al(idx), dbeta[idx])
 
 
 def rhs6(dbeta1, dbeta2, gamma, alpha):
@@ -55,13 +65,14 @@ def rhs6(dbeta1, dbeta2, gamma, alpha):
     import oracle as O
     d1, d2 = np.asarray(dbeta1, dtype=float), np.asarray(dbeta2, dtype=float)
     g = np.broadcast_to(np.asarray(gamma, dtype=float), d1.shape)
+    al = _alpha_of(alpha)
 
     def f(z, y, idx):
-        return np.stack([O.np_rhs6(z[k], y[:, k], g[i], float(alpha), d1[i], d2[i]) for k, i in enumerate(idx)], axis=1)
+        return np.stack([O.np_rhs6(z[k], y[:, k], g[i], al(i), d1[i], d2[i]) for k, i in enumerate(idx)], axis=1)
     return f
 
 
-def rk45(rhs, y0, z_max, *, rtol, atol, h_max=np.inf, first_step=0.0, max_steps=1_000_000, n_out=0):
+def rk45(rhs, y0, z_max, *, rtol, atol, h_max=np.inf, first_step=0.0, max_steps=1_000_000, n_out=0, record=None):
     y = np.array(y0, dtype=np.complex128)
     n, N = y.shape
     z = np.zeros(N)
@@ -75,6 +86,7 @@ def rk45(rhs, y0, z_max, *, rtol, atol, h_max=np.inf, first_step=0.0, max_steps=
         traj[:, 0] = y.T
         t_eval = np.linspace(0.0, z_max, n_out + 1)
     next_row = np.ones(N, dtype=np.int64)
+    steps = [] if record is not None else None
     active = np.isfinite(y).all(0)
     status[~active] = 1
     all_idx = np.arange(N)
@@ -136,6 +148,8 @@ def rk45(rhs, y0, z_max, *, rtol, atol, h_max=np.inf, first_step=0.0, max_steps=
                         p = np.cumprod(np.full(4, x))
                         traj[i, next_row[i]] = h[k] * np.dot(Q, p) + ya[:, k]
                         next_row[i] += 1
+            if steps is not None and acc[ia == record].any():
+                steps.append((float(t[ia == record][0]), float(h[ia == record][0])))
             ai = ia[acc]
             y[:, ai] = y_new[:, acc]
             f[:, ai] = K[6][:, acc]
@@ -154,4 +168,4 @@ def rk45(rhs, y0, z_max, *, rtol, atol, h_max=np.inf, first_step=0.0, max_steps=
             ha = h_abs[ai]
             h_abs[ai] = np.where(ha > h_max, h_max, np.where(ha < ms, ms, ha))
     return dict(a_end=y.T.copy(), p_end=np.abs(y[2]) ** 2, p_max=pm, status=status, z_end=z, n_accepted=n_acc,
-                n_rejected=n_rej, traj=traj)
+                n_rejected=n_rej, traj=traj, steps=steps)

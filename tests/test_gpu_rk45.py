@@ -1,5 +1,6 @@
 """The adaptive (RK45) sweep on the GPU: G18 (scipy's RK45 on the reference's RHS) through the three call levels, a seeded
-random sweep against the NumPy restatement (tests/rk45_np.py), accuracy against a converged RK4 sweep, lane independence,
+random sweep against the NumPy restatement (tests/rk45_np.py), accuracy against a converged RK4 sweep and against an 80-bit
+plain RK4 that is none of the project's GPU code, lane independence,
 the failure statuses, the device form (also replayed from a captured graph), the dense rows and the lossless path."""
 import os
 from types import SimpleNamespace
@@ -9,6 +10,7 @@ import pytest
 
 import psa_amd._native as nat
 import rk45_np
+from truth_cases import rk45_random_points as _random_points
 from psa_amd.config import AdaptiveConfig, custom_simulation_config
 from psa_amd.integrators import integrate_adaptive
 from psa_amd.phase_matching import PhaseMatchingConfig, PhaseMatchingMethod
@@ -160,16 +162,6 @@ def test_g18_through_integrate_adaptive(name):
         assert np.max(np.abs(rows - g["rows"]) / np.max(np.abs(g["rows"]), axis=0)) < 1e-10
 
 
-def _random_points(n, seed, six=False):
-    rng = np.random.default_rng(seed)
-    db = rng.uniform(-0.1, 0.1, n)
-    gamma = rng.uniform(5e-3, 2e-2, n)
-    pp = rng.uniform(0.05, 1.0, (n, 2))
-    nw = 6 if six else 4
-    p = np.concatenate([pp, np.full((n, nw - 2), 1e-5)], axis=1)
-    return db, gamma, np.sqrt(p).astype(complex), (rng.uniform(-0.1, 0.1, n) if six else None)
-
-
 def _compare_to_numpy(r, ref, rtol):
     same = (r.n_accepted == ref["n_accepted"]) & (r.n_rejected == ref["n_rejected"])
     assert np.mean(same) >= 0.95, np.mean(same)
@@ -202,6 +194,20 @@ def _config2(n):
     return np.linspace(-0.05, 0.05, n), np.full(n, 0.0115), np.repeat(np.sqrt(P_C2).astype(complex)[None, :], n, axis=0)
 
 
+ARBITER_POINTS = 17
+
+
+def _independent_arbiter(db, gamma, a0, n, n_out=1):
+    """The global error's second arbiter, none of the project's GPU code: 17 of the points spread over the sweep through the
+    compiled plain RK4 in 80 bits (oracle/plain_rk4.py) at the 4e5 steps of the GPU one, rows at the dense grid.
+    -> (the points picked, its rows (17, n_out + 1, 4) as complex128)."""
+    import plain_rk4
+    pick = np.linspace(0, n - 1, ARBITER_POINTS).astype(int)
+    ld = plain_rk4.integrate("pairs", a0[pick], db[pick], z_max=1000.0, n=400_000, save_every=400_000 // n_out,
+                             gamma=gamma[pick], alpha=1.15e-4, precision="ld", want_rows=True)
+    return pick, ld["rows"].astype(np.complex128)
+
+
 def test_accuracy_against_converged_rk4():
     # rtol bounds the local error per step, not the global one: on config-2 inputs the global error stays within
     # 100 * rtol; at gamma * P * L ~ 20 rad (the random set above) it reaches ~2e-7 at rtol 1e-9 (DESIGN.md 3.7)
@@ -211,6 +217,8 @@ def test_accuracy_against_converged_rk4():
     truth = rk4_sweep(db, z_max=1000.0, n_steps=400_000, save_every=400_000, gamma=gamma, alpha=1.15e-4, a0=a0)
     assert np.all(r.status == 0)
     assert np.max(rel_rows(r.a_end, truth.a_end)) < 100 * rtol
+    pick, rows = _independent_arbiter(db, gamma, a0, n)
+    assert np.max(rel_rows(r.a_end[pick], rows[:, -1])) < 100 * rtol
 
 
 def test_lane_independence():
@@ -311,6 +319,9 @@ def test_dense_rows():
     assert fixed.traj.shape == r.traj.shape
     scale = np.max(np.abs(fixed.traj), axis=2, keepdims=True)
     assert np.max(np.abs(r.traj - fixed.traj) / scale) < 100 * rtol
+    pick, rows = _independent_arbiter(db, gamma, a0, n, n_out)
+    assert rows.shape == r.traj[pick].shape
+    assert np.max(np.abs(r.traj[pick] - rows) / np.max(np.abs(rows), axis=2, keepdims=True)) < 100 * rtol
 
 
 def test_lossless_path_equals_lossy_instantiation():

@@ -6,6 +6,9 @@ waves and a ragged one with four lanes per point), 1 500 steps over 300 m (not a
 re-seeds), rows every 7 steps (a tail of 2 behind the last row).  Per-point gamma, alpha and amplitudes with random phases.
 
 Every result is a dict in one form: a_end (N, NW), p_wave_end, p_wave_max (N, NW), rows (N, n_saved, NW) or None.
+
+At the end, the sets of the adaptive sweep (tests/test_truth_rk45_host.py, tests/test_gpu_rk45_truth.py): the same 67 points and
+fibre draws, each with the 80-bit run of Dormand-Prince 5(4) and its controller (truth_rk45_ld) and the twin's (rk45_np).
 """
 import functools
 import os
@@ -60,7 +63,7 @@ def errors(got, truth):
 
 def like(got, twin):
     """The twin's result in the form of ``got``: wave 2's p_end / p_max where the entry point returns those alone."""
-    if got.get("p_wave_end") is None and got.get("p_end") is not None:
+    if got.get("p_wave_end") is None and got.get("p_end") is not None and twin.get("p_end") is None:
         return dict(a_end=twin["a_end"], p_end=twin["p_wave_end"][:, 2], p_max=twin["p_wave_max"][:, 2], rows=twin["rows"])
     return twin
 
@@ -585,3 +588,113 @@ F64_SETS = ([(f"waves4-{'mirrored' if m else 'general'}-{'lossy' if l else 'loss
             + [("comb-M7-kappa0", lambda: comb_without_dispersion(7))])
 F32_SETS = [("waves4_f32-general", lambda: waves4_f32(False)), ("waves4_f32-mirrored", lambda: waves4_f32(True)),
             ("single_pump_f32", single_pump_f32)]
+
+
+# ---- the adaptive sweep: Dormand-Prince 5(4) against the 80-bit run of its own scheme (truth_rk45_ld) ------------------------
+# The yardstick is of the kernel's discrete scheme only where its controller takes the kernel's steps: twin (tests/rk45_np.py)
+# and yardstick have identical status, n_accepted and n_rejected at every point of every set below (asserted in
+# tests/test_truth_rk45_host.py; a set that ever fails it gets another seed).  atol = 1e-3 rtol unless a set says otherwise; rows
+# at linspace(0, z_max, 44) -- 43 divides neither length, so no row but the last lies on a step end.
+# The floor of this bar is NOT FLOOR_F64: that is the drift budget of a carried phase, and the adaptive kernel takes an exact sincos
+# at every stage.  It is zero: two plain float64 statements meet the bar against each other on every set and every output without
+# one (test_truth_rk45_host.test_spread_between_two_plain_statements).
+RK45_N_OUT = 43
+FLOOR_RK45 = 0.0
+RK45_TWIN_RTOL = 1e-10                 # what tests/test_gpu_rk45.py holds kernel and twin to; kept beside the bar
+RK45_KEYS = ("a_end", "p_end", "p_max", "p_wave_end", "p_wave_max", "status", "z_end", "n_accepted", "n_rejected", "rows")
+
+
+def rk45_random_points(n, seed, six=False):
+    """The seeded random sweep of tests/test_gpu_rk45.py: -> dbeta, gamma, a0 (n, 4 or 6), dbeta2 or None.  The strong set
+    below is its first 67 points, so the draws stay as they are."""
+    rng = np.random.default_rng(seed)
+    db = rng.uniform(-0.1, 0.1, n)
+    gamma = rng.uniform(5e-3, 2e-2, n)
+    pp = rng.uniform(0.05, 1.0, (n, 2))
+    nw = 6 if six else 4
+    p = np.concatenate([pp, np.full((n, nw - 2), 1e-5)], axis=1)
+    return db, gamma, np.sqrt(p).astype(complex), (rng.uniform(-0.1, 0.1, n) if six else None)
+
+
+def rk45_form(result, rows=True):
+    """A run of rk45_np.rk45 or nat.rk45_sweep_host in the yardstick's form: the outputs above, its dense rows ("traj" there)
+    under "rows"; rows = False leaves them out, as a launch with n_out = 0 does."""
+    out = {k: result[k] for k in RK45_KEYS[:-1] if result.get(k) is not None}
+    out["rows"] = (result.get("rows") if result.get("rows") is not None else result.get("traj")) if rows else None
+    return out
+
+
+def _rk45_set(inp):
+    import rk45_np
+    import truth_rk45_ld
+    inp = dict(dict(rtol=1e-9, h_max=np.inf, first_step=0.0, n_out=RK45_N_OUT, z_max=Z_MAX), **inp)
+    inp.setdefault("atol", 1e-3 * inp["rtol"])
+    tol = {k: inp[k] for k in ("z_max", "rtol", "atol", "h_max", "first_step", "n_out")}
+    truth = truth_rk45_ld.integrate(inp["a0"], _rate2(inp), gamma=inp["gamma"], alpha=inp["alpha"], **tol)
+    rhs = (rk45_np.rhs4(inp["dbeta"], inp["gamma"], inp["alpha"]) if inp.get("dbeta2") is None
+           else rk45_np.rhs6(inp["dbeta"], inp["dbeta2"], inp["gamma"], inp["alpha"]))
+    return dict(inp, truth=truth, twin=rk45_form(rk45_np.rk45(rhs, inp["a0"].T, **tol)))
+
+
+def _rk45_lossy_inputs():
+    rng = np.random.default_rng(4700)
+    gamma, alpha = _fibre(rng, N, True)
+    return dict(dbeta=rng.uniform(-0.05, 0.05, N), gamma=gamma, alpha=alpha, a0=_amplitudes(rng, N, 2, 2))
+
+
+def _rk45_six_inputs(lossy):
+    rng = np.random.default_rng(4760 + lossy)
+    gamma, alpha = _fibre(rng, N, lossy)
+    return dict(dbeta=rng.uniform(-0.05, 0.05, N), dbeta2=rng.uniform(-0.05, 0.05, N), gamma=gamma, alpha=alpha,
+                a0=_amplitudes(rng, N, 2, 4))
+
+
+def _rk45_strong_inputs():
+    """The first 67 points of the 4 096-point random sweep of tests/test_gpu_rk45.py over its 1000 m: gamma P L up to ~20 rad,
+    up to ~1 600 steps, one alpha for all points."""
+    db, gamma, a0, _ = rk45_random_points(4096, 20261016)
+    return dict(dbeta=db[:N], gamma=gamma[:N], alpha=ALPHA, a0=a0[:N], z_max=1000.0, rtol=1e-9, atol=1e-12)
+
+
+def _rk45_lossless_inputs():
+    rng = np.random.default_rng(4710)
+    gamma, alpha = _fibre(rng, N, False)                   # the scalar 0.0: the LOSSLESS instantiation
+    return dict(dbeta=rng.uniform(-0.05, 0.05, N), gamma=gamma, alpha=alpha, a0=_amplitudes(rng, N, 2, 2))
+
+
+RK45_INPUTS = {
+    "lossy-r9": lambda: _rk45_lossy_inputs(),                                        # per-point gamma and alpha, ~150 steps
+    "lossless-r9": _rk45_lossless_inputs,
+    "lossy-r6": lambda: dict(_rk45_lossy_inputs(), rtol=1e-6),                       # the tolerance ends: ~20 steps ...
+    "lossy-r11": lambda: dict(_rk45_lossy_inputs(), rtol=1e-11),                     # ... and ~500
+    "lossy-dbeta0": lambda: dict(_rk45_lossy_inputs(), dbeta=np.zeros(N)),
+    "strong-r9": _rk45_strong_inputs,
+    "six-lossy-r9": lambda: _rk45_six_inputs(True),                                  # the instantiations that use AGPRs
+    "six-lossless-r9": lambda: _rk45_six_inputs(False),
+    # the controller's other branches: rejections (1..3 per point, then factor <= 1), the h_max clamp on every step, both
+    "first_step50-r4": lambda: dict(_rk45_lossy_inputs(), first_step=50.0, rtol=1e-4, atol=1e-9),
+    "h_max1.3-r9": lambda: dict(_rk45_lossy_inputs(), h_max=1.3),
+    "first_step100-h_max7-r7": lambda: dict(_rk45_lossy_inputs(), first_step=100.0, h_max=7.0, rtol=1e-7),
+}
+RK45_SETS = tuple(RK45_INPUTS)
+
+
+@functools.lru_cache(maxsize=None)
+def rk45(name):
+    """One input set of the adaptive sweep with its 80-bit run and its twin's, both in the kernel's output form."""
+    return _rk45_set(RK45_INPUTS[name]())
+
+
+def rk45_tolerances(inputs):
+    """The set's controller settings as nat.rk45_sweep_host and rk45_np.rk45 take them."""
+    return {k: inputs[k] for k in ("z_max", "rtol", "atol", "h_max", "first_step")}
+
+
+def rk45_same_steps(got, truth):
+    """The points where ``got`` took the yardstick's accepted and rejected attempts: where the two are one discrete scheme."""
+    return (np.asarray(got["n_accepted"]) == truth["n_accepted"]) & (np.asarray(got["n_rejected"]) == truth["n_rejected"])
+
+
+def rk45_at(result, mask):
+    """The arrays of a result in the yardstick's form (rk45_form) at the points of ``mask``."""
+    return {k: (None if result.get(k) is None else np.asarray(result[k])[mask]) for k in RK45_KEYS if k in result}
