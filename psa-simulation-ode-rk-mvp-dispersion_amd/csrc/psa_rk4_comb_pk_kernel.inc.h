@@ -2,17 +2,15 @@
 // lane (packed math), gfx950.  The equations and the discretisation are those of psa_rk4_comb_kernel.inc.h, the
 // layout and the arithmetic those of psa_rk4_single_pump_pk_kernel.inc.h; DESIGN.md 3.3f.
 //
-//   layout   lane i holds points 2i and 2i+1 in the halves of an f32x2, lanes = (N + 1) / 2; the odd tail's slot 1 repeats slot 0
-//            and is never stored; a wave whose lanes all hold two real points (wave_full, wave-uniform) moves the adjacent pair
-//            with 8-byte accesses at float alignment and a trajectory row with one 16-byte store per line, the one other wave
-//            goes element by element.  N = 1 runs here too: there is no scalar float32 kernel for this model.
+//   layout   two points per lane as psa_rk4_pk_frame.inc.h lays them out (PkLane); a trajectory row is one 16-byte store per line
+//            in a full wave.  N = 1 runs here too: there is no scalar float32 kernel for this model.
 //   step     classic low-storage RK4 (y, y_stage, accumulator) on the UN-FUSED right-hand side k = dA/dz: the stage
 //            coefficient is an operand of the stage-input FMA and is not folded into gamma and alpha, which float32 would
 //            round.  u_m = exp(i kappa_m z) is carried by two half-step rotations per step and re-seeded every
 //            COMB_PK_RESYNC steps on the absolute grid from a float64-reduced phase; kappa_m is read again from memory there.
 //            Once per step |u_m| is brought back to one (a Newton step): what is carried must not keep a modulus offset.
-//   state    compensated: y = yb + dl, the increments collect in the small offset dl, which is folded into yb with its
-//            rounding residue (Fast2Sum) where the phases are re-seeded.
+//   state    compensated: y = yb + dl, the increments collect in the small offset dl, which is folded into yb (pk_fold, through
+//            the accessors that know where a component lives) where the phases are re-seeded.
 //   loss     one register layout, with the loss links; PSA_OPT_LOSSLESS is accepted as a promise and runs this instantiation.
 //   check    CHECK tests every half after every step (no block mode, no replay): first_bad_step is exact per point.
 //
@@ -26,6 +24,10 @@
 // column (comb_pk_lds_vectors): the half-step rotators, then dl, then yb; sched_barrier fences keep the stages apart there.
 // Control flow is wave-uniform: branches on kernel arguments, loop counters, wave_full or nothing; lane-dependent branches hold
 // loads and stores only, and no lane reads another lane's data.
+//
+// From psa_rk4_pk_frame.inc.h: the lane's points with load2 / store2 / pin_points, the finite test, the fold, |A|^2.  This
+// kernel's own, as in the single-pump kernel: the row maxima, the stores of a row, of the last one and of first_bad, and the
+// event loop (DESIGN.md 3.3d says what each of them compiled to as a shared function).
 //
 // Out of scope: a lossless instantiation, a scalar (one point per lane) kernel, chains, RK45, lane-group layouts.
 #pragma once
@@ -99,38 +101,15 @@ __global__ void __launch_bounds__(256) rk4_sweep_comb_pk_kernel(const CombArgs<f
     using V = f32x2;
     constexpr int NC = 2 * M;
     constexpr int RESYNC = COMB_PK_RESYNC;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long N = A.n_points;
-    long long pt[2] = {2 * idx, (2 * idx + 1 < N) ? 2 * idx + 1 : 2 * idx};  // odd tail: slot 1 repeats slot 0
-    if (pt[0] >= N) return;
-    const bool live1 = 2 * idx + 1 < N;  // slot 1 holds a real point (else computed but never stored)
-
-    // wave-uniform: every lane of this wave holds two real points (see rk4_sweep_pk_kernel)
-    const bool wave_full = __builtin_amdgcn_readfirstlane((int)(2 * (idx | 63) + 1 < N)) != 0;
-    typedef float f32x2_u __attribute__((ext_vector_type(2), aligned(4)));   // an 8-B access at float alignment (odd N rows)
-    auto load2 = [&](const float *base, const int stride) -> V {   // base[pt0 * stride], base[pt1 * stride]
-        if (stride == 0) return splat2(base[0]);
-        if (wave_full) return *reinterpret_cast<const f32x2_u *>(base + pt[0]);
-        return (V){base[pt[0]], base[pt[1]]};
-    };
-    // Called where the z-loop loads or stores per point: the indices pass through an empty asm there, so the 2M-fold addresses
-    // formed from them stay inside that block.  Hoisted out of the loop as invariants they would be held in registers across
-    // every step, and from M = 11 spilled to scratch memory.
-    auto pin_points = [&]() { asm volatile("" : "+v"(pt[0]), "+v"(pt[1])); };
-    auto store2 = [&](float *base, const V v) {   // base[pt0], base[pt1]
-        if (wave_full) {
-            *reinterpret_cast<f32x2_u *>(base + pt[0]) = v;
-        } else {
-            base[pt[0]] = v.x;
-            if (live1) base[pt[1]] = v.y;
-        }
-    };
+    PkLane L;   // pin_points() is called where the z-loop loads or stores per point
+    if (!L.init((long long)blockIdx.x * blockDim.x + threadIdx.x, A.n_points)) return;
+    const long long N = L.N;
 
     V y[NC];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) y[c] = load2(A.a0 + (long long)c * A.a0_ld, A.a0_stride);
-    const V g = load2(A.gamma, A.gamma_stride);
-    const V ha = splat2(-0.5f) * load2(A.alpha, A.alpha_stride);
+    for (int c = 0; c < NC; ++c) y[c] = L.load2(A.a0 + (long long)c * A.a0_ld, A.a0_stride);
+    const V g = L.load2(A.gamma, A.gamma_stride);
+    const V ha = splat2(-0.5f) * L.load2(A.alpha, A.alpha_stride);
     const double hd = A.z_max / (double)A.n_steps;   // np.linspace step
     const V h = splat2((float)hd), hh = splat2((float)(0.5 * hd)), h6 = splat2((float)(hd / 6.0));
     const V two = splat2(2.0f);
@@ -144,7 +123,7 @@ __global__ void __launch_bounds__(256) rk4_sweep_comb_pk_kernel(const CombArgs<f
     auto lds_at = [&](const int vec, const int c) -> V & { return lds[(unsigned)(vec * NC + c) * lds_ld]; };
 
     auto eval2 = [&](const int m, const double z, V &c, V &s) {   // exp(i kappa_m z) of both halves; kappa_m from memory
-        const V kap = load2(A.kappa + (long long)m * N, 1);
+        const V kap = L.load2(A.kappa + (long long)m * N, 1);
         float c0, s0, c1, s1;
         Phase<float>::eval((double)kap.x * z, c0, s0);
         Phase<float>::eval((double)kap.y * z, c1, s1);
@@ -181,7 +160,7 @@ __global__ void __launch_bounds__(256) rk4_sweep_comb_pk_kernel(const CombArgs<f
         }
     };
     auto seed = [&](const int step) {   // exact u_m at z = step * h
-        pin_points();
+        L.pin_points();
         const double z = (double)step * hd;
 #pragma unroll
         for (int m = 0; m < M; ++m) eval2(m, z, ur[m], ui[m]);
@@ -196,33 +175,18 @@ __global__ void __launch_bounds__(256) rk4_sweep_comb_pk_kernel(const CombArgs<f
         yb_at(c) = y[c];
         dl_at(c) = V{};
     }
-    auto fold = [&]() {
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const V b = yb_at(c), d = dl_at(c);
-            const V sum = b + d;
-            dl_at(c) = d - (sum - b);
-            yb_at(c) = sum;
-            y[c] = sum;
-        }
-    };
+    auto fold = [&]() { pk_fold(y, yb_at, dl_at); };
     int bad[2] = {-1, -1};   // step indices are below 2^31: widened where they are stored
     V pm[M];   // np.max of |A_m|^2 over saved rows (z = 0 is one)
 #pragma unroll
-    for (int m = 0; m < M; ++m) pm[m] = fma_(y[2 * m], y[2 * m], y[2 * m + 1] * y[2 * m + 1]);
-    auto track = [&](const int step) {  // sum_c 0*y_c is NaN exactly for a non-finite component, per packed half
-        V t = V{};
-#pragma unroll
-        for (int c = 0; c < NC; ++c) t = fma_(y[c], V{}, t);
-        if (bad[0] < 0 && t.x != t.x) bad[0] = step;
-        if (bad[1] < 0 && t.y != t.y) bad[1] = step;
-    };
+    for (int m = 0; m < M; ++m) pm[m] = pk_abs2(y[2 * m], y[2 * m + 1]);
+    auto track = [&](const int step) { pk_track(y, step, bad); };
     auto store_a_end = [&]() {   // the last saved row and |A_m|^2 there
-        pin_points();
+        L.pin_points();
 #pragma unroll
-        for (int c = 0; c < NC; ++c) store2(A.a_end + (long long)c * N, y[c]);
+        for (int c = 0; c < NC; ++c) L.store2(A.a_end + (long long)c * N, y[c]);
 #pragma unroll
-        for (int m = 0; m < M; ++m) store2(A.p_wave_end + (long long)m * N, fma_(y[2 * m], y[2 * m], y[2 * m + 1] * y[2 * m + 1]));
+        for (int m = 0; m < M; ++m) L.store2(A.p_wave_end + (long long)m * N, pk_abs2(y[2 * m], y[2 * m + 1]));
     };
 
     const int se = A.save_every;
@@ -233,10 +197,10 @@ __global__ void __launch_bounds__(256) rk4_sweep_comb_pk_kernel(const CombArgs<f
     // trajectory launches), as in rk4_sweep_pk_kernel
     const bool traj = A.traj != nullptr;
     const long long LD = A.traj_ld;
-    const unsigned lane_off = (unsigned)idx * 16u;
+    const unsigned lane_off = (unsigned)L.idx * 16u;
     auto store_traj_row = [&](const int r) {
         const char *rowb = reinterpret_cast<const char *>(A.traj) + (long long)r * M * LD * 8;
-        if (wave_full) {
+        if (L.wave_full) {
 #pragma unroll
             for (int m = 0; m < M; ++m)
                 store_quad_nt(rowb + (long long)m * LD * 8, lane_off, (f32x4){y[2 * m].x, y[2 * m + 1].x, y[2 * m].y, y[2 * m + 1].y});
@@ -245,7 +209,7 @@ __global__ void __launch_bounds__(256) rk4_sweep_comb_pk_kernel(const CombArgs<f
             for (int m = 0; m < M; ++m) {
                 const char *wb = rowb + (long long)m * LD * 8;
                 store_pair_nt(wb, lane_off, (f32x2){y[2 * m].x, y[2 * m + 1].x});
-                if (live1) store_pair_nt(wb, lane_off + 8u, (f32x2){y[2 * m].y, y[2 * m + 1].y});
+                if (L.live1) store_pair_nt(wb, lane_off + 8u, (f32x2){y[2 * m].y, y[2 * m + 1].y});
             }
         }
     };
@@ -318,8 +282,8 @@ __global__ void __launch_bounds__(256) rk4_sweep_comb_pk_kernel(const CombArgs<f
         if (i == next_save) {
             ++row;
 #pragma unroll
-            for (int m = 0; m < M; ++m) {
-                const V pw = fma_(y[2 * m], y[2 * m], y[2 * m + 1] * y[2 * m + 1]);
+            for (int m = 0; m < M; ++m) {   // pk_row_max(y, pm) in its place moves one instruction of the unchecked M = 10 kernel
+                const V pw = pk_abs2(y[2 * m], y[2 * m + 1]);
                 pm[m].x = (pw.x > pm[m].x || pw.x != pw.x) ? pw.x : pm[m].x;   // np.max propagates NaN
                 pm[m].y = (pw.y > pm[m].y || pw.y != pw.y) ? pw.y : pm[m].y;
             }
@@ -333,9 +297,9 @@ __global__ void __launch_bounds__(256) rk4_sweep_comb_pk_kernel(const CombArgs<f
         }
     }
 #pragma unroll
-    for (int m = 0; m < M; ++m) store2(A.p_wave_max + (long long)m * N, pm[m]);
-    A.first_bad[pt[0]] = bad[0];
-    if (live1) A.first_bad[pt[1]] = bad[1];
+    for (int m = 0; m < M; ++m) L.store2(A.p_wave_max + (long long)m * N, pm[m]);
+    A.first_bad[L.pt[0]] = bad[0];
+    if (L.live1) A.first_bad[L.pt[1]] = bad[1];
 }
 
 }  // namespace psa

@@ -64,15 +64,7 @@
         yb[c] = y[c];
         dl[c] = V{};
     }
-    auto fold = [&]() {
-#pragma unroll
-        for (int c = 0; c < NS; ++c) {
-            const V sum = yb[c] + dl[c];
-            dl[c] = dl[c] - (sum - yb[c]);
-            yb[c] = sum;
-            y[c] = sum;
-        }
-    };
+    auto fold = [&]() { pk_fold(y, [&](const int c) -> V & { return yb[c]; }, [&](const int c) -> V & { return dl[c]; }); };
     V pe = fma_(y[SIG], y[SIG], y[SIG + 1] * y[SIG + 1]);
     V pm = pe;
     long long bad[2] = {-1, -1};
@@ -81,13 +73,7 @@
 #pragma unroll
         for (int j = 0; j < NWS; ++j) pwm[j] = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
     }
-    auto track = [&](const int step) {  // sum_c 0*y_c is NaN exactly for a non-finite component, per packed half
-        V t = V{};
-#pragma unroll
-        for (int c = 0; c < NS; ++c) t = fma_(y[c], V{}, t);
-        if (bad[0] < 0 && t.x != t.x) bad[0] = step;
-        if (bad[1] < 0 && t.y != t.y) bad[1] = step;
-    };
+    auto track = [&](const int step) { pk_track(y, step, bad); };
     auto store_rows = [&](float *base) {  // base[c * N + point]
 #pragma unroll
         for (int c = 0; c < NC; ++c) {

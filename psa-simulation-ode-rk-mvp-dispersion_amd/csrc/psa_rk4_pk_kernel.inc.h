@@ -8,12 +8,15 @@
 // config 4's per-GPU shard -- and 140-147 with four or more).  Same algorithm and arithmetic as the scalar float32 kernel
 // (classic low-storage RK4 on the un-fused RHS with a compensated state update, phase factor re-seeded from a
 // float64-reduced sincos every 16 steps), so the two agree to rounding.
+//
+// Of psa_rk4_pk_frame.inc.h this kernel and its body use the finite test, the fold, splat2 and the f32x2_u type: with the lane
+// record (PkLane) or its load2 / store2 in place of the spelled-out prologue and lambdas, 24 of the unit's instantiations compile
+// to other code (store2 as a method: 2 VGPRs more in every one), and this unit's device code is held to the text it had before
+// the frame existed.
 #pragma once
-#include "psa_rk4_kernel.inc.h"
+#include "psa_rk4_pk_frame.inc.h"
 
 namespace psa {
-
-__device__ __forceinline__ f32x2 splat2(float x) { return (f32x2){x, x}; }
 
 // Does every live lane of this wave start MIRRORED in both of its points?  As wave_starts_mirrored: A2 == A1 and A4 == A3
 // as bit patterns -- one 64-bit compare per packed pair, so both halves must agree, +0 and -0 differ -- and all eight
@@ -53,7 +56,6 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_pk_kernel(const SweepArgs<flo
     // wave-uniform: every lane of this wave holds two real points -> 8-B loads / stores of the adjacent pair, 16-B trajectory
     // stores; the (at most one) wave with the odd tail or past-the-end lanes takes the element-wise path
     const bool wave_full = __builtin_amdgcn_readfirstlane((int)(2 * (idx | 63) + 1 < N)) != 0;
-    typedef float f32x2_u __attribute__((ext_vector_type(2), aligned(4)));   // an 8-B access at float alignment (odd N rows)
     auto load2 = [&](const float *base, const int stride) -> V {   // base[pt0 * stride], base[pt1 * stride]
         if (stride == 0) return splat2(base[0]);
         if (wave_full) return *reinterpret_cast<const f32x2_u *>(base + pt[0]);

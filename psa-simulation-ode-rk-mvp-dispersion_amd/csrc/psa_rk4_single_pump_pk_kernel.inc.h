@@ -2,10 +2,8 @@
 // lane (packed math), gfx950.  The equations are those of psa_rk4_single_pump_kernel.inc.h, the layout and the
 // arithmetic those of rk4_sweep_pk_kernel (psa_rk4_pk_kernel.inc.h, psa_rk4_pk_body.inc.h):
 //
-//   layout   lane i holds points 2i and 2i+1 in the halves of an f32x2, lanes = (N + 1) / 2; the odd tail's slot 1 repeats slot 0
-//            and is never stored; a wave whose lanes all hold two real points (wave_full, wave-uniform) moves the adjacent pair
-//            with 8-byte accesses at float alignment and a trajectory row with one 16-byte store per wave of the model, the one
-//            other wave goes element by element.  N = 1 runs here too: there is no scalar float32 kernel for this model.
+//   layout   two points per lane as psa_rk4_pk_frame.inc.h lays them out (PkLane); a trajectory row is one 16-byte store per wave
+//            of the model in a full wave.  N = 1 runs here too: there is no scalar float32 kernel for this model.
 //   step     classic low-storage RK4 (y, y_stage, accumulator) on the UN-FUSED right-hand side: the fused regrouped stage of the
 //            float64 kernel needs the stage coefficient folded into five constants per stage kind, which float32 rounds
 //            (DESIGN.md 5.1).  E = 2*gamma*exp(i*dbeta*z) is carried by the half-step rotation and re-seeded every
@@ -22,9 +20,12 @@
 // 4 * 51 + 30 (stage inputs and accumulator) + 18 (sum, offset, state) + 8 (two rotations) = 260 for two points, plus the
 // per-step finite test of CHECK_EXACT (6) and 18 / RESYNC for the fold; as built, tools/single_pump_timing.py --static.
 //
-// The body is its own text and not psa_rk4_pk_body.inc.h with a third stage: that body's VGPR counts depend on how it is
+// Shared with the other packed kernels (psa_rk4_pk_frame.inc.h): the lane's points with load2 / store2, the finite test, the
+// fold and the row maxima.  Still this kernel's own text, as in rk4_sweep_comb_pk_kernel and psa_rk4_pk_body.inc.h: the stores
+// of a saved row, of the last one and of first_bad, and the event loop -- as shared functions they compile to other code
+// (DESIGN.md 3.3d).  The body is not psa_rk4_pk_body.inc.h with a third stage: that body's VGPR counts depend on how it is
 // included (see its head), and the three-wave model has neither a signal summary (p_end / p_max) nor a dbeta2 nor a mirrored
-// form, so most of the shared text would sit behind switches.  Control flow is wave-uniform: branches on kernel arguments, loop
+// form, so most of that text would sit behind switches.  Control flow is wave-uniform: branches on kernel arguments, loop
 // counters, wave_full or nothing; lane-dependent branches hold loads and stores only.  Check modes as the packed kernel: per
 // packed half, exact = a test after every step (no replay), block = at saved rows and after the last step.
 //
@@ -66,38 +67,19 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_single_pump_pk_kernel(const S
     using V = f32x2;
     constexpr int NW = 3, NC = 6;
     constexpr int RESYNC = Phase<float>::RESYNC;
-    const long long idx = (long long)blockIdx.x * BLOCK + threadIdx.x;
-    const long long N = A.n_points;
-    const long long pt[2] = {2 * idx, (2 * idx + 1 < N) ? 2 * idx + 1 : 2 * idx};  // odd tail: slot 1 repeats slot 0
-    if (pt[0] >= N) return;
-    const bool live1 = 2 * idx + 1 < N;  // slot 1 holds a real point (else computed but never stored)
-
-    // wave-uniform: every lane of this wave holds two real points (see rk4_sweep_pk_kernel)
-    const bool wave_full = __builtin_amdgcn_readfirstlane((int)(2 * (idx | 63) + 1 < N)) != 0;
-    typedef float f32x2_u __attribute__((ext_vector_type(2), aligned(4)));   // an 8-B access at float alignment (odd N rows)
-    auto load2 = [&](const float *base, const int stride) -> V {   // base[pt0 * stride], base[pt1 * stride]
-        if (stride == 0) return splat2(base[0]);
-        if (wave_full) return *reinterpret_cast<const f32x2_u *>(base + pt[0]);
-        return (V){base[pt[0]], base[pt[1]]};
-    };
-    auto store2 = [&](float *base, const V v) {   // base[pt0], base[pt1]
-        if (wave_full) {
-            *reinterpret_cast<f32x2_u *>(base + pt[0]) = v;
-        } else {
-            base[pt[0]] = v.x;
-            if (live1) base[pt[1]] = v.y;
-        }
-    };
+    PkLane L;
+    if (!L.init((long long)blockIdx.x * BLOCK + threadIdx.x, A.n_points)) return;
+    const long long N = L.N;
 
     V y[NC];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) y[c] = load2(A.a0 + (long long)c * A.a0_ld, A.a0_stride);
-    const V g = load2(A.gamma, A.gamma_stride);
+    for (int c = 0; c < NC; ++c) y[c] = L.load2(A.a0 + (long long)c * A.a0_ld, A.a0_stride);
+    const V g = L.load2(A.gamma, A.gamma_stride);
     const V tg = g + g;
-    const V ha = splat2(-0.5f) * load2(A.alpha, A.alpha_stride);
+    const V ha = splat2(-0.5f) * L.load2(A.alpha, A.alpha_stride);
     double dbd[2];
     {
-        const V d0 = load2(A.dbeta, 1);
+        const V d0 = L.load2(A.dbeta, 1);
         dbd[0] = (double)d0.x;
         dbd[1] = (double)d0.y;
     }
@@ -123,31 +105,17 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_single_pump_pk_kernel(const S
         yb[c] = y[c];
         dl[c] = V{};
     }
-    auto fold = [&]() {
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const V sum = yb[c] + dl[c];
-            dl[c] = dl[c] - (sum - yb[c]);
-            yb[c] = sum;
-            y[c] = sum;
-        }
-    };
+    auto fold = [&]() { pk_fold(y, [&](const int c) -> V & { return yb[c]; }, [&](const int c) -> V & { return dl[c]; }); };
     int bad[2] = {-1, -1};   // step indices are below 2^31: widened where they are stored
     V pm[NW];   // np.max of |A_j|^2 over saved rows (z = 0 is one)
 #pragma unroll
-    for (int j = 0; j < NW; ++j) pm[j] = fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]);
-    auto track = [&](const int step) {  // sum_c 0*y_c is NaN exactly for a non-finite component, per packed half
-        V t = V{};
-#pragma unroll
-        for (int c = 0; c < NC; ++c) t = fma_(y[c], V{}, t);
-        if (bad[0] < 0 && t.x != t.x) bad[0] = step;
-        if (bad[1] < 0 && t.y != t.y) bad[1] = step;
-    };
+    for (int j = 0; j < NW; ++j) pm[j] = pk_abs2(y[2 * j], y[2 * j + 1]);
+    auto track = [&](const int step) { pk_track(y, step, bad); };
     auto store_a_end = [&]() {   // the last saved row and |A_j|^2 there
 #pragma unroll
-        for (int c = 0; c < NC; ++c) store2(A.a_end + (long long)c * N, y[c]);
+        for (int c = 0; c < NC; ++c) L.store2(A.a_end + (long long)c * N, y[c]);
 #pragma unroll
-        for (int j = 0; j < NW; ++j) store2(A.p_wave_end + (long long)j * N, fma_(y[2 * j], y[2 * j], y[2 * j + 1] * y[2 * j + 1]));
+        for (int j = 0; j < NW; ++j) L.store2(A.p_wave_end + (long long)j * N, pk_abs2(y[2 * j], y[2 * j + 1]));
     };
 
     const int se = A.save_every;
@@ -157,10 +125,10 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_single_pump_pk_kernel(const S
     // store per lane; the (row, wave) base stays in SGPRs and the lane adds a 32-bit byte offset (the C-ABI keeps ld * 8 B below
     // 2^31 for trajectory launches), as in rk4_sweep_pk_kernel
     const long long LD = A.traj_ld;
-    const unsigned lane_off = (unsigned)idx * 16u;
+    const unsigned lane_off = (unsigned)L.idx * 16u;
     auto store_traj_row = [&](const int r) {
         const char *rowb = reinterpret_cast<const char *>(A.traj) + (long long)r * NW * LD * 8;
-        if (wave_full) {
+        if (L.wave_full) {
 #pragma unroll
             for (int j = 0; j < NW; ++j)
                 store_quad_nt(rowb + (long long)j * LD * 8, lane_off, (f32x4){y[2 * j].x, y[2 * j + 1].x, y[2 * j].y, y[2 * j + 1].y});
@@ -169,7 +137,7 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_single_pump_pk_kernel(const S
             for (int j = 0; j < NW; ++j) {
                 const char *wb = rowb + (long long)j * LD * 8;
                 store_pair_nt(wb, lane_off, (f32x2){y[2 * j].x, y[2 * j + 1].x});
-                if (live1) store_pair_nt(wb, lane_off + 8u, (f32x2){y[2 * j].y, y[2 * j + 1].y});
+                if (L.live1) store_pair_nt(wb, lane_off + 8u, (f32x2){y[2 * j].y, y[2 * j + 1].y});
             }
         }
     };
@@ -227,12 +195,7 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_single_pump_pk_kernel(const S
         i = end;
         if (i == next_save) {
             ++row;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                const V pw = fma_(y[2 * w], y[2 * w], y[2 * w + 1] * y[2 * w + 1]);
-                pm[w].x = (pw.x > pm[w].x || pw.x != pw.x) ? pw.x : pm[w].x;   // np.max propagates NaN
-                pm[w].y = (pw.y > pm[w].y || pw.y != pw.y) ? pw.y : pm[w].y;
-            }
+            pk_row_max(y, pm);
             if constexpr (CHECK == CHECK_BLOCK) track(i - 1);
             if constexpr (TRAJ) store_traj_row(row);
             if (row == n_rows) {
@@ -247,9 +210,9 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_single_pump_pk_kernel(const S
         if (n_run > 0) track(n_run - 1);
     }
 #pragma unroll
-    for (int j = 0; j < NW; ++j) store2(A.p_wave_max + (long long)j * N, pm[j]);
-    A.first_bad[pt[0]] = bad[0];
-    if (live1) A.first_bad[pt[1]] = bad[1];
+    for (int j = 0; j < NW; ++j) L.store2(A.p_wave_max + (long long)j * N, pm[j]);
+    A.first_bad[L.pt[0]] = bad[0];
+    if (L.live1) A.first_bad[L.pt[1]] = bad[1];
 }
 
 }  // namespace psa
