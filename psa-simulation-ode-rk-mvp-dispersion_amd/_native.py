@@ -354,6 +354,39 @@ def sweep_waves_device(*, stream: int, n_waves: int, n_points: int, n_steps: int
         d_p_wave_end_soa or None, d_p_wave_max_soa or None))
 
 
+def _wave_host(stem: str, dtypes, mismatch: np.ndarray, head: tuple, nw: int, check: int, rows: bool, n_steps, z_max,
+               save_every, gamma, alpha, a0, want_traj: bool, device: int, extra_flags: int) -> dict:
+    """The host-buffer sweep of a wave-summary family (multi-channel, single-pump, multi-line): ``<stem>_f64`` / ``_f32`` with
+    ``head`` (the family's count, or nothing) in front of N.  ``dtypes``: _dtypes' answer; ``mismatch``: the family's checked
+    and converted array, N its first axis; ``nw``: the columns of a0; ``check``: _check_flags' answer; ``rows``: the entry point
+    takes a trajectory, and the result has the key traj."""
+    dtype, cdt, f64 = dtypes
+    N = int(mismatch.shape[0])
+    flags, gamma, alpha, a0, _ = _point_inputs(N, dtype, cdt, int(extra_flags), gamma, alpha, a0, (nw,))
+    a_end = np.empty((N, nw), dtype=cdt)
+    w_end = np.empty((N, nw), dtype=dtype)
+    w_max = np.empty((N, nw), dtype=dtype)
+    bad = np.empty(N, dtype=np.int64)
+    ms = C.c_double(0.0)
+    out = dict(a_end=a_end, p_wave_end=w_end, p_wave_max=w_max, first_bad_step=bad)
+    tail = ()
+    if rows:
+        n_saved = int(n_steps) // int(save_every) + 1 if save_every > 0 else 0
+        out["traj"] = np.empty((N, n_saved, nw), dtype=cdt) if want_traj else None
+        tail = (_ptr(out["traj"]),)
+    _check(_fn(stem, f64)(int(device), *head, N, int(n_steps), float(z_max), int(save_every), _ptr(mismatch), _ptr(gamma),
+                          _ptr(alpha), _ptr(a0), flags | check, _ptr(a_end), _ptr(w_end), _ptr(w_max), _ptr(bad), *tail,
+                          C.cast(C.byref(ms), _P)))
+    out["elapsed_ms"] = ms.value
+    return out
+
+
+def _wave_device(stem: str, f64: bool, stream: int, head: tuple, inputs: tuple, flags: int, outputs: tuple) -> None:
+    """``<stem>_*_dev``: ``head`` ([the family's count,] n_points, n_steps, z_max, save_every) as the caller converted it, then
+    the device pointers (ints, 0 for NULL) with the flags between the inputs and the outputs."""
+    _check(_fn(stem, f64, dev=True)(stream or None, *head, *(p or None for p in inputs), int(flags), *(p or None for p in outputs)))
+
+
 def sweep_pairs_host(dbeta, *, n_steps: int, z_max: float, save_every: int, gamma, alpha, a0, check_nan: bool = True,
                      exact_step: Optional[bool] = None, device: int = 0, extra_flags: int = 0) -> dict:
     """N independent propagations of two pumps and K signal/idler pairs on the GPU (psa_rk4_sweep_pairs_f64; host buffers
@@ -366,29 +399,17 @@ def sweep_pairs_host(dbeta, *, n_steps: int, z_max: float, save_every: int, gamm
     dbeta = np.ascontiguousarray(np.asarray(dbeta), dtype=np.float64)
     if dbeta.ndim != 2 or not 1 <= dbeta.shape[1] <= MAX_PAIRS:
         raise ValueError(f"dbeta must have shape (N, K) with 1 <= K <= {MAX_PAIRS}, got {dbeta.shape}")
-    N, K = (int(x) for x in dbeta.shape)
-    nw = 2 + 2 * K
-    flags, gamma, alpha, a0, _ = _point_inputs(N, np.float64, np.complex128, int(extra_flags), gamma, alpha, a0, (nw,))
-    flags |= _check_flags(check_nan, exact_step)
-    a_end = np.empty((N, nw), dtype=np.complex128)
-    w_end = np.empty((N, nw), dtype=np.float64)
-    w_max = np.empty((N, nw), dtype=np.float64)
-    bad = np.empty(N, dtype=np.int64)
-    ms = C.c_double(0.0)
-    _check(_fn("psa_rk4_sweep_pairs")(int(device), K, N, int(n_steps), float(z_max), int(save_every), _ptr(dbeta),
-                                      _ptr(gamma), _ptr(alpha), _ptr(a0), flags, _ptr(a_end), _ptr(w_end), _ptr(w_max),
-                                      _ptr(bad), C.cast(C.byref(ms), _P)))
-    return dict(a_end=a_end, p_wave_end=w_end, p_wave_max=w_max, first_bad_step=bad, elapsed_ms=ms.value)
+    K = int(dbeta.shape[1])
+    return _wave_host("psa_rk4_sweep_pairs", (np.float64, np.complex128, True), dbeta, (K,), 2 + 2 * K,
+                      _check_flags(check_nan, exact_step), False, n_steps, z_max, save_every, gamma, alpha, a0, False, device, extra_flags)
 
 
 def sweep_pairs_device(*, stream: int, n_pairs: int, n_points: int, n_steps: int, z_max: float, save_every: int,
                        d_dbeta_soa: int, d_gamma: int, d_alpha: int, d_a0_soa: int, flags: int, d_a_end_soa: int,
                        d_p_wave_end_soa: int, d_p_wave_max_soa: int, d_first_bad: int) -> None:
     """Asynchronous multi-channel launch on device pointers (ints), SoA layout -- see psa_rk4_sweep_pairs_f64_dev."""
-    _check(_fn("psa_rk4_sweep_pairs", dev=True)(
-        stream or None, int(n_pairs), int(n_points), int(n_steps), float(z_max), int(save_every), d_dbeta_soa or None,
-        d_gamma or None, d_alpha or None, d_a0_soa or None, int(flags), d_a_end_soa or None, d_p_wave_end_soa or None,
-        d_p_wave_max_soa or None, d_first_bad or None))
+    _wave_device("psa_rk4_sweep_pairs", True, stream, (int(n_pairs), int(n_points), int(n_steps), float(z_max), int(save_every)),
+                 (d_dbeta_soa, d_gamma, d_alpha, d_a0_soa), flags, (d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad))
 
 
 def single_pump_host(dbeta, *, n_steps: int, z_max: float, save_every: int, gamma, alpha, a0, check_nan: bool = True,
@@ -402,24 +423,12 @@ def single_pump_host(dbeta, *, n_steps: int, z_max: float, save_every: int, gamm
     (both precisions: the float32 kernel tests after every step); False: the save block's last step.
     Returns a_end (N, 3) complex, p_wave_end, p_wave_max (N, 3), first_bad_step (N,) int64, traj (N, n_saved, 3) complex or
     None, elapsed_ms (kernel only)."""
-    dtype, cdt, f64 = _dtypes(dtype)
-    dbeta = np.ascontiguousarray(np.atleast_1d(np.asarray(dbeta)), dtype=dtype)
+    dtypes = _dtypes(dtype)
+    dbeta = np.ascontiguousarray(np.atleast_1d(np.asarray(dbeta)), dtype=dtypes[0])
     if dbeta.ndim != 1:
         raise ValueError("dbeta must be 1-D")
-    N = int(dbeta.shape[0])
-    flags, gamma, alpha, a0, _ = _point_inputs(N, dtype, cdt, int(extra_flags), gamma, alpha, a0, (3,))
-    flags |= _check_flags(check_nan, exact_step)
-    n_saved = int(n_steps) // int(save_every) + 1 if save_every > 0 else 0
-    a_end = np.empty((N, 3), dtype=cdt)
-    w_end = np.empty((N, 3), dtype=dtype)
-    w_max = np.empty((N, 3), dtype=dtype)
-    bad = np.empty(N, dtype=np.int64)
-    traj = np.empty((N, n_saved, 3), dtype=cdt) if want_traj else None
-    ms = C.c_double(0.0)
-    _check(_fn("psa_rk4_single_pump", f64)(int(device), N, int(n_steps), float(z_max), int(save_every), _ptr(dbeta), _ptr(gamma),
-                                      _ptr(alpha), _ptr(a0), flags, _ptr(a_end), _ptr(w_end), _ptr(w_max), _ptr(bad),
-                                      _ptr(traj), C.cast(C.byref(ms), _P)))
-    return dict(a_end=a_end, p_wave_end=w_end, p_wave_max=w_max, first_bad_step=bad, traj=traj, elapsed_ms=ms.value)
+    return _wave_host("psa_rk4_single_pump", dtypes, dbeta, (), 3, _check_flags(check_nan, exact_step), True, n_steps, z_max,
+                      save_every, gamma, alpha, a0, want_traj, device, extra_flags)
 
 
 def single_pump_device(*, stream: int, n_points: int, n_steps: int, z_max: float, save_every: int, d_dbeta: int,
@@ -427,10 +436,9 @@ def single_pump_device(*, stream: int, n_points: int, n_steps: int, z_max: float
                        d_p_wave_max_soa: int, d_first_bad: int, d_traj_soa: int = 0, dtype=np.float64) -> None:
     """Asynchronous single-pump launch on device pointers (ints), SoA layout -- see psa_rk4_single_pump_f64_dev; ``dtype``
     float32 is psa_rk4_single_pump_f32_dev on float buffers."""
-    _check(_fn("psa_rk4_single_pump", _dtypes(dtype)[2], dev=True)(
-        stream or None, int(n_points), int(n_steps), float(z_max), int(save_every), d_dbeta or None, d_gamma or None,
-        d_alpha or None, d_a0_soa or None, int(flags), d_a_end_soa or None, d_p_wave_end_soa or None,
-        d_p_wave_max_soa or None, d_first_bad or None, d_traj_soa or None))
+    _wave_device("psa_rk4_single_pump", _dtypes(dtype)[2], stream, (int(n_points), int(n_steps), float(z_max), int(save_every)),
+                 (d_dbeta, d_gamma, d_alpha, d_a0_soa), flags,
+                 (d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad, d_traj_soa))
 
 
 def comb_host(kappa, *, n_steps: int, z_max: float, save_every: int, gamma, alpha, a0, check_nan: bool = True,
@@ -443,24 +451,14 @@ def comb_host(kappa, *, n_steps: int, z_max: float, save_every: int, gamma, alph
     (N, M) complex.  With check_nan first_bad_step is the exact step index (the point is tested after every step).
     Returns a_end (N, M) complex, p_wave_end, p_wave_max (N, M), first_bad_step (N,) int64, traj (N, n_saved, M) complex or
     None, elapsed_ms (kernel only)."""
-    dtype, cdt, f64 = _dtypes(dtype)
-    kappa = np.ascontiguousarray(np.asarray(kappa), dtype=dtype)
+    dtypes = _dtypes(dtype)
+    kappa = np.ascontiguousarray(np.asarray(kappa), dtype=dtypes[0])
     if kappa.ndim != 2 or not 3 <= kappa.shape[1] <= MAX_LINES:
         raise ValueError(f"kappa must have shape (N, M) with 3 <= M <= {MAX_LINES}, got {kappa.shape}")
-    N, M = (int(x) for x in kappa.shape)
-    flags, gamma, alpha, a0, _ = _point_inputs(N, dtype, cdt, int(extra_flags), gamma, alpha, a0, (M,))
-    flags |= _check_flags(check_nan, None, f64)   # float32 goes without PSA_OPT_EXACT_STEP: the kernel tests after every step anyway
-    n_saved = int(n_steps) // int(save_every) + 1 if save_every > 0 else 0
-    a_end = np.empty((N, M), dtype=cdt)
-    w_end = np.empty((N, M), dtype=dtype)
-    w_max = np.empty((N, M), dtype=dtype)
-    bad = np.empty(N, dtype=np.int64)
-    traj = np.empty((N, n_saved, M), dtype=cdt) if want_traj else None
-    ms = C.c_double(0.0)
-    _check(_fn("psa_rk4_comb", f64)(int(device), M, N, int(n_steps), float(z_max), int(save_every), _ptr(kappa), _ptr(gamma),
-                                    _ptr(alpha), _ptr(a0), flags, _ptr(a_end), _ptr(w_end), _ptr(w_max), _ptr(bad), _ptr(traj),
-                                    C.cast(C.byref(ms), _P)))
-    return dict(a_end=a_end, p_wave_end=w_end, p_wave_max=w_max, first_bad_step=bad, traj=traj, elapsed_ms=ms.value)
+    M = int(kappa.shape[1])
+    # float32 goes without PSA_OPT_EXACT_STEP: the kernel tests after every step anyway
+    return _wave_host("psa_rk4_comb", dtypes, kappa, (M,), M, _check_flags(check_nan, None, dtypes[2]), True, n_steps, z_max,
+                      save_every, gamma, alpha, a0, want_traj, device, extra_flags)
 
 
 def comb_device(*, stream: int, n_lines: int, n_points: int, n_steps: int, z_max: float, save_every: int, d_kappa_soa: int,
@@ -468,10 +466,9 @@ def comb_device(*, stream: int, n_lines: int, n_points: int, n_steps: int, z_max
                 d_p_wave_max_soa: int, d_first_bad: int, d_traj_soa: int = 0, dtype=np.float64) -> None:
     """Asynchronous multi-line launch on device pointers (ints), SoA layout -- see psa_rk4_comb_f64_dev; ``dtype`` float32 is
     psa_rk4_comb_f32_dev on float buffers."""
-    _check(_fn("psa_rk4_comb", _dtypes(dtype)[2], dev=True)(
-        stream or None, int(n_lines), int(n_points), int(n_steps), float(z_max), int(save_every), d_kappa_soa or None,
-        d_gamma or None, d_alpha or None, d_a0_soa or None, int(flags), d_a_end_soa or None, d_p_wave_end_soa or None,
-        d_p_wave_max_soa or None, d_first_bad or None, d_traj_soa or None))
+    _wave_device("psa_rk4_comb", _dtypes(dtype)[2], stream, (int(n_lines), int(n_points), int(n_steps), float(z_max), int(save_every)),
+                 (d_kappa_soa, d_gamma, d_alpha, d_a0_soa), flags,
+                 (d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad, d_traj_soa))
 
 
 def _chain_host(stem: str, widths, sweep_family: bool, dbeta, *, n_steps, seg_len, save_every: int, gamma, alpha, a0,

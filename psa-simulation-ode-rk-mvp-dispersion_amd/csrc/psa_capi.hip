@@ -54,8 +54,10 @@ int64_t traj_ld_of(int64_t n_points, size_t elem_size) {
 // What one call of a sweep family asks for, fields in the order of its C arguments.  The extern "C" function builds the record
 // once; validation, the `_dev` path and the host path take it by reference.  The host path copies it, has its layout function
 // put device pointers (Staging) in place of the copy's buffer pointers and hands the copy to the same `_dev` function.  A new
-// family brings its record, its validator, its `_dev` function and its layout; the rules the families share are stated once
-// below (validate_grid, validate_common, fill_point_args, lossless_bit).
+// family with the wave summary (a_end, p_wave_end, p_wave_max, first_bad_step, optional rows) brings its record and its
+// Family<> and is served by validate_wave, wave_dev, wave_host and the chain functions; a family with other outputs or rules
+// (SweepCall, Rk45Call) brings its own validator, `_dev` function and layout on top of the shared rules (validate_grid,
+// fill_shared_args, lossless_bit).
 template <typename T>
 struct SweepCall {   // psa_rk4_sweep_*, psa_rk4_sweep_waves_* and one span of a chain
     using Real = T;
@@ -214,7 +216,7 @@ void fill_shared_args(Args &a, const Call &c) {
     a.a0_stride = (c.flags & PSA_BCAST_A0) ? 0 : 1;
     a.a0_ld = (c.flags & PSA_BCAST_A0) ? 1 : c.n_points;
 }
-// ... and, for SweepArgs, AdaptiveArgs, PairsArgs and SinglePumpArgs, the mismatch
+// ... and, for SweepArgs and AdaptiveArgs, the mismatch
 template <typename Args, typename Call>
 void fill_point_args(Args &a, const Call &c) {
     a.dbeta = c.dbeta;
@@ -601,250 +603,127 @@ int sweep_host(int device, const SweepCall<T> &c, double *elapsed_ms) {
     return host_call<T>(device, "the RK4 sweep", elapsed_ms, layout, [&](hipStream_t st) { return sweep_dev<T>(st, d); });
 }
 
-// ---- the multi-channel sweep (psa_rk4_sweep_pairs_f64*): two pumps and n_pairs signal/idler pairs -----------------------
-// chain: the call is (a span of) psa_rk4_pairs_chain_f64*, which has rows; host_form as in validate_single_pump
-int validate_pairs(const PairsCall &c, bool chain = false, bool host_form = false) {
-    if (c.n_pairs < 1 || c.n_pairs > PSA_MAX_PAIRS)
-        return fail(PSA_E_NPAIRS, "n_pairs must be in [1, %d], got %d", PSA_MAX_PAIRS, c.n_pairs);
-    // a launch is at most 2^32 - 1 threads in x and a point takes L of them: the power of two >= n_pairs (at least 2)
-    const long long lanes_per_point = psa::pairs_lanes_per_point(c.n_pairs);
-    int rc = validate_grid(c.n_points, 2 * PSA_MAX_POINTS / lanes_per_point, lanes_per_point, c.n_steps, c.z_max, c.save_every);
-    if (rc != PSA_OK) return rc;
-    const uint32_t accepted = PSA_BCAST_GAMMA | PSA_BCAST_ALPHA | PSA_BCAST_A0 | PSA_OPT_CHECK_NAN | PSA_OPT_EXACT_STEP |
-                              PSA_OPT_LOSSLESS | PSA_OPT_BLOCK64 | ((chain && !host_form) ? PSA_OPT_TRAJ_LD : 0u);
-    if (c.flags & ~accepted)
-        return fail(PSA_E_FLAGS, chain ? "the multi-channel chain takes the BCAST bits, CHECK_NAN, EXACT_STEP, LOSSLESS, BLOCK64 "
-                                         "and (its _dev form) TRAJ_LD only (no layout, float32 or LDS flag): 0x%x"
-                                       : "the multi-channel sweep takes the BCAST bits, CHECK_NAN, EXACT_STEP, LOSSLESS and BLOCK64 "
-                                         "only (no layout, float32 or LDS flag): 0x%x", (unsigned)(c.flags & ~accepted));
-    if (c.n_points > 0 && (!c.dbeta || !c.gamma || !c.alpha || !c.a0 || !c.a_end || !c.wave_end || !c.wave_max || !c.first_bad))
-        return fail(PSA_E_NULLPTR, "a required buffer pointer is NULL");
-    if (c.traj) {
-        // the bound of every float64 row launch, kept for parity between the families: this kernel addresses its rows with a
-        // 64-bit address per lane and would not need it
-        const bool padded = host_form || (c.flags & PSA_OPT_TRAJ_LD);
-        const unsigned long long ld = (unsigned long long)(padded ? traj_ld_of(c.n_points, sizeof(double)) : c.n_points);
-        if (ld * 16ull >= (1ull << 32))
-            return fail(PSA_E_TOO_LARGE, "a multi-channel trajectory launch takes a leading dimension below 2^28 points, got %llu", ld);
-    }
-    return PSA_OK;
-}
-
-int pairs_dev(void *stream, const PairsCall &c, bool chain = false) {
-    int rc = validate_pairs(c, chain);
-    if (rc != PSA_OK) return rc;
-    if (c.n_points == 0) return PSA_OK;
-    psa::PairsArgs a;
-    fill_point_args(a, c);
-    a.p_wave_end = c.wave_end;
-    a.p_wave_max = c.wave_max;
-    a.first_bad = (long long *)c.first_bad;
-    a.n_steps = (int)c.n_steps;
-    a.save_every = c.save_every;
-    a.n_pairs = c.n_pairs;
-    a.traj = c.traj;
-    a.traj_ld = (c.flags & PSA_OPT_TRAJ_LD) ? traj_ld_of(c.n_points, sizeof(double)) : c.n_points;
-    hipError_t e = psa::launch_sweep_pairs_f64((hipStream_t)stream, c.flags, a);
-    if (e != hipSuccess) return hip_fail(e, "rk4_sweep_pairs launch");
-    return PSA_OK;
-}
-
-int pairs_host(int device, const PairsCall &c, double *elapsed_ms) {
-    int rc = validate_pairs(c);
-    if (rc != PSA_OK) return rc;
-    if (elapsed_ms) *elapsed_ms = 0.0;
-    if (c.n_points == 0) return PSA_OK;
-    const int nw = 2 + 2 * c.n_pairs;
-    const size_t N = (size_t)c.n_points;
-    PairsCall d = c;
-    d.flags |= lossless_bit(c.flags, c.alpha);
-    auto layout = [&](Staging<double> &sg) {
-        d.dbeta = sg.input_soa(c.dbeta, N, c.n_pairs);             // [N][n_pairs] -> [n_pairs][N]
-        d.gamma = sg.input(c.gamma, (c.flags & PSA_BCAST_GAMMA) ? 1 : N);
-        d.alpha = sg.input(c.alpha, (c.flags & PSA_BCAST_ALPHA) ? 1 : N);
-        d.a0 = sg.input_soa(c.a0, (c.flags & PSA_BCAST_A0) ? 1 : N, 2 * nw);
-        d.a_end = sg.output_soa(c.a_end, N, 2 * nw);
-        d.wave_end = sg.output_soa(c.wave_end, N, nw);
-        d.wave_max = sg.output_soa(c.wave_max, N, nw);
-        d.first_bad = sg.output(c.first_bad, N);
-    };
-    return host_call<double>(device, "the multi-channel RK4 sweep", elapsed_ms, layout,
-                             [&](hipStream_t st) { return pairs_dev(st, d); });
-}
-
-// ---- the single-pump sweep (psa_rk4_single_pump_f64* / _f32*): one pump, a signal and an idler -------------------------
-template <typename T> struct SinglePumpLaunch;
-template <> struct SinglePumpLaunch<double> { static constexpr auto fn = psa::launch_sweep_single_pump_f64; };
-template <> struct SinglePumpLaunch<float> { static constexpr auto fn = psa::launch_sweep_single_pump_f32; };
+// ---- the wave-summary families: multi-channel (psa_rk4_sweep_pairs_f64*), single-pump (psa_rk4_single_pump_*) and multi-line
+// ("comb", psa_rk4_comb_*) -----------------------------------------------------------------------------------------------
+// Three models with one surface: a_end, the end and the maximum power of every wave, first_bad_step and optional rows.  One
+// validator, one `_dev` function and one host function serve them, as sweeps and as the spans of their chains; what differs
+// between them -- and between them and the 4/6-wave sweep as a chain's span -- is stated once per record, in Family<> below.
+template <typename Span> struct Family;
+// The array of a record whose values a chain's gauge accumulates: dbeta, or the multi-line model's kappa.
+template <typename Span> auto mismatch_of(Span &c) -> decltype((c.dbeta)) { return c.dbeta; }
+template <typename T> const T *&mismatch_of(CombCall<T> &c) { return c.kappa; }
+template <typename T> const T *mismatch_of(const CombCall<T> &c) { return c.kappa; }
 
 // host_form: the call as the host-buffer entry point received it (PSA_OPT_TRAJ_LD is the `_dev` form's; the host form's
-// device-side trajectory always has the padded leading dimension).  The order is validate_common's; float32 has one layout
-// (two points per lane), so PSA_OPT_F32_SCALAR / PSA_OPT_F32_PACKED are refused like every other layout flag.
-template <typename T>
-int validate_single_pump(const SinglePumpCall<T> &c, bool host_form) {
-    int rc = validate_grid(c.n_points, PSA_MAX_POINTS, 0, c.n_steps, c.z_max, c.save_every);
+// device-side trajectory always has the padded leading dimension); chain: the call is (a span of) the family's chain.  The
+// order is validate_common's with the family's count in front; float32 has one layout (two points per lane), so
+// PSA_OPT_F32_SCALAR / PSA_OPT_F32_PACKED are refused like every other layout flag.
+template <typename Call>
+int validate_wave(const Call &c, bool host_form, bool chain = false) {
+    using F = Family<Call>;
+    using T = typename Call::Real;
+    int rc = F::check_count(c);
     if (rc != PSA_OK) return rc;
+    // a launch is at most 2^32 - 1 threads in x, two of which the limit allows per point; a family that spends more says so
+    const long long lanes = F::lanes_per_point(c);
+    rc = validate_grid(c.n_points, lanes ? 2 * PSA_MAX_POINTS / lanes : PSA_MAX_POINTS, lanes, c.n_steps, c.z_max, c.save_every);
+    if (rc != PSA_OK) return rc;
+    const bool rows = F::sweep_rows || chain;   // a sweep without rows has them as one span of its chain, and says "chain" there
     const uint32_t accepted = PSA_BCAST_GAMMA | PSA_BCAST_ALPHA | PSA_BCAST_A0 | PSA_OPT_CHECK_NAN | PSA_OPT_EXACT_STEP |
-                              PSA_OPT_LOSSLESS | PSA_OPT_BLOCK64 | (host_form ? 0u : PSA_OPT_TRAJ_LD);
+                              PSA_OPT_LOSSLESS | PSA_OPT_BLOCK64 | ((rows && !host_form) ? PSA_OPT_TRAJ_LD : 0u);
     if (c.flags & ~accepted)
-        return fail(PSA_E_FLAGS, "the single-pump sweep takes the BCAST bits, CHECK_NAN, EXACT_STEP, LOSSLESS, BLOCK64 and (its "
-                                 "_dev form) TRAJ_LD only (no layout, float32 or LDS flag): 0x%x", (unsigned)(c.flags & ~accepted));
-    if (c.n_points > 0 && (!c.dbeta || !c.gamma || !c.alpha || !c.a0 || !c.a_end || !c.wave_end || !c.wave_max || !c.first_bad))
+        return fail(PSA_E_FLAGS, rows ? "the %s %s takes the BCAST bits, CHECK_NAN, EXACT_STEP, LOSSLESS, BLOCK64 and (its _dev form) "
+                                        "TRAJ_LD only (no layout, float32 or LDS flag): 0x%x"
+                                      : "the %s %s takes the BCAST bits, CHECK_NAN, EXACT_STEP, LOSSLESS and BLOCK64 only (no layout, "
+                                        "float32 or LDS flag): 0x%x",
+                    F::name, (chain && !F::sweep_rows) ? "chain" : "sweep", (unsigned)(c.flags & ~accepted));
+    if (c.n_points > 0 && (!mismatch_of(c) || !c.gamma || !c.alpha || !c.a0 || !c.a_end || !c.wave_end || !c.wave_max || !c.first_bad))
         return fail(PSA_E_NULLPTR, "a required buffer pointer is NULL");
     if (c.traj) {
-        // trajectory rows are addressed as a wave-uniform (row, wave) base + the lane's 32-bit byte offset
+        // trajectory rows are addressed as a wave-uniform (row, wave) base + the lane's 32-bit byte offset (the multi-channel
+        // kernel addresses its rows with 64 bits per lane and keeps the bound for parity between the families)
         const bool padded = host_form || (c.flags & PSA_OPT_TRAJ_LD);
         const unsigned long long ld = (unsigned long long)(padded ? traj_ld_of(c.n_points, sizeof(T)) : c.n_points);
         // float64: one 16-byte pair per lane below 2^32; float32: the packed sweep's bound, 8-byte pairs below 2^31
         if (ld * 2ull * sizeof(T) >= (sizeof(T) == 8 ? 1ull << 32 : 1ull << 31))
-            return fail(PSA_E_TOO_LARGE, "a single-pump trajectory launch takes a leading dimension below 2^28 points, got %llu", ld);
+            return fail(PSA_E_TOO_LARGE, "a %s trajectory launch takes a leading dimension below 2^28 points, got %llu", F::name, ld);
     }
     return PSA_OK;
 }
 
-template <typename T>
-int single_pump_dev(void *stream, const SinglePumpCall<T> &c) {
-    int rc = validate_single_pump(c, false);
+// every pointer of c is a device pointer (SoA: a mismatch of several rows, a0, a_end, the summaries and the rows)
+template <typename Call>
+int wave_dev(void *stream, const Call &c, bool chain = false) {
+    using F = Family<Call>;
+    int rc = validate_wave(c, false, chain);
     if (rc != PSA_OK) return rc;
     if (c.n_points == 0) return PSA_OK;
-    psa::SinglePumpArgs<T> a;
-    fill_point_args(a, c);
-    a.p_wave_end = c.wave_end;
-    a.p_wave_max = c.wave_max;
-    a.first_bad = (long long *)c.first_bad;
-    a.traj = c.traj;
-    a.traj_ld = (c.flags & PSA_OPT_TRAJ_LD) ? traj_ld_of(c.n_points, sizeof(T)) : c.n_points;
-    a.n_steps = (int)c.n_steps;
-    a.save_every = c.save_every;
-    hipError_t e = SinglePumpLaunch<T>::fn((hipStream_t)stream, c.flags, a);
-    if (e != hipSuccess) return hip_fail(e, "rk4_sweep_single_pump launch");
-    return PSA_OK;
-}
-
-template <typename T>
-int single_pump_host(int device, const SinglePumpCall<T> &c, double *elapsed_ms) {
-    int rc = validate_single_pump(c, true);
-    if (rc != PSA_OK) return rc;
-    if (elapsed_ms) *elapsed_ms = 0.0;
-    if (c.n_points == 0) return PSA_OK;
-    const size_t N = (size_t)c.n_points;
-    SinglePumpCall<T> d = c;
-    if (c.traj) d.flags |= PSA_OPT_TRAJ_LD;   // the device-side trajectory has its own leading dimension; the caller's is dense
-    d.flags |= lossless_bit(c.flags, c.alpha);
-    auto layout = [&](Staging<T> &sg) {
-        d.dbeta = sg.input(c.dbeta, N);
-        d.gamma = sg.input(c.gamma, (c.flags & PSA_BCAST_GAMMA) ? 1 : N);
-        d.alpha = sg.input(c.alpha, (c.flags & PSA_BCAST_ALPHA) ? 1 : N);
-        d.a0 = sg.input_soa(c.a0, (c.flags & PSA_BCAST_A0) ? 1 : N, 6);
-        d.a_end = sg.output_soa(c.a_end, N, 6);
-        d.wave_end = sg.output_soa(c.wave_end, N, 3);
-        d.wave_max = sg.output_soa(c.wave_max, N, 3);
-        d.first_bad = sg.output(c.first_bad, N);
-        d.traj = sg.trajectory(c.traj, N, (size_t)(c.n_steps / c.save_every + 1), 6);
-    };
-    return host_call<T>(device, "the single-pump RK4 sweep", elapsed_ms, layout,
-                             [&](hipStream_t st) { return single_pump_dev(st, d); });
-}
-
-// ---- the multi-line ("comb") sweep (psa_rk4_comb_f64* / _f32*): n_lines equally spaced lines, every FWM product among them
-template <typename T> struct CombLaunch;
-template <> struct CombLaunch<double> { static constexpr auto fn = psa::launch_sweep_comb_f64; };
-template <> struct CombLaunch<float> { static constexpr auto fn = psa::launch_sweep_comb_f32; };
-
-// host_form as in validate_single_pump, whose order this is with n_lines in front; float32 has one layout (two points per
-// lane), so PSA_OPT_F32_SCALAR / PSA_OPT_F32_PACKED are refused like every other layout flag.
-template <typename T>
-int validate_comb(const CombCall<T> &c, bool host_form) {
-    if (c.n_lines < 3 || c.n_lines > PSA_MAX_LINES)
-        return fail(PSA_E_NLINES, "n_lines must be in [3, %d], got %d", PSA_MAX_LINES, c.n_lines);
-    int rc = validate_grid(c.n_points, PSA_MAX_POINTS, 0, c.n_steps, c.z_max, c.save_every);
-    if (rc != PSA_OK) return rc;
-    const uint32_t accepted = PSA_BCAST_GAMMA | PSA_BCAST_ALPHA | PSA_BCAST_A0 | PSA_OPT_CHECK_NAN | PSA_OPT_EXACT_STEP |
-                              PSA_OPT_LOSSLESS | PSA_OPT_BLOCK64 | (host_form ? 0u : PSA_OPT_TRAJ_LD);
-    if (c.flags & ~accepted)
-        return fail(PSA_E_FLAGS, "the multi-line sweep takes the BCAST bits, CHECK_NAN, EXACT_STEP, LOSSLESS, BLOCK64 and (its "
-                                 "_dev form) TRAJ_LD only (no layout, float32 or LDS flag): 0x%x", (unsigned)(c.flags & ~accepted));
-    if (c.n_points > 0 && (!c.kappa || !c.gamma || !c.alpha || !c.a0 || !c.a_end || !c.wave_end || !c.wave_max || !c.first_bad))
-        return fail(PSA_E_NULLPTR, "a required buffer pointer is NULL");
-    if (c.traj) {
-        // trajectory rows are addressed as a wave-uniform (row, line) base + the lane's 32-bit byte offset
-        const bool padded = host_form || (c.flags & PSA_OPT_TRAJ_LD);
-        const unsigned long long ld = (unsigned long long)(padded ? traj_ld_of(c.n_points, sizeof(T)) : c.n_points);
-        // float64: one 16-byte pair per lane below 2^32; float32: the packed sweep's bound, 8-byte pairs below 2^31
-        if (ld * 2ull * sizeof(T) >= (sizeof(T) == 8 ? 1ull << 32 : 1ull << 31))
-            return fail(PSA_E_TOO_LARGE, "a multi-line trajectory launch takes a leading dimension below 2^28 points, got %llu", ld);
-    }
-    return PSA_OK;
-}
-
-template <typename T>
-int comb_dev(void *stream, const CombCall<T> &c) {
-    int rc = validate_comb(c, false);
-    if (rc != PSA_OK) return rc;
-    if (c.n_points == 0) return PSA_OK;
-    psa::CombArgs<T> a;
+    typename F::Args a;
     fill_shared_args(a, c);
-    a.kappa = c.kappa;
     a.p_wave_end = c.wave_end;
     a.p_wave_max = c.wave_max;
     a.first_bad = (long long *)c.first_bad;
     a.traj = c.traj;
-    a.traj_ld = (c.flags & PSA_OPT_TRAJ_LD) ? traj_ld_of(c.n_points, sizeof(T)) : c.n_points;
+    a.traj_ld = (c.flags & PSA_OPT_TRAJ_LD) ? traj_ld_of(c.n_points, sizeof(typename Call::Real)) : c.n_points;
     a.n_steps = (int)c.n_steps;
     a.save_every = c.save_every;
-    a.n_lines = c.n_lines;
-    hipError_t e = CombLaunch<T>::fn((hipStream_t)stream, c.flags, a);
-    if (e != hipSuccess) return hip_fail(e, "rk4_sweep_comb launch");
+    hipError_t e = F::launch((hipStream_t)stream, a, c);   // sets the mismatch and the family's count
+    if (e != hipSuccess) return hip_fail(e, F::launch_what);
     return PSA_OK;
 }
 
-template <typename T>
-int comb_host(int device, const CombCall<T> &c, double *elapsed_ms) {
-    int rc = validate_comb(c, true);
+// The mismatch of S spans (a sweep: one) on the device: [S][N] as it is, or [S][N][rows] -> [S][rows][N]
+template <typename Span>
+auto stage_mismatch(Staging<typename Span::Real> &sg, const Span &c, int S, size_t N) {
+    return Family<Span>::mismatch_soa ? sg.input_soa(mismatch_of(c), N, Family<Span>::dbeta_rows(c), S) : sg.input(mismatch_of(c), S * N);
+}
+// The summary of a wave-summary family, sweep or chain
+template <typename Call>
+void stage_wave_summary(Staging<typename Call::Real> &sg, Call &d, const Call &c, size_t N) {
+    d.wave_end = sg.output_soa(c.wave_end, N, Family<Call>::n_waves(c));
+    d.wave_max = sg.output_soa(c.wave_max, N, Family<Call>::n_waves(c));
+    d.first_bad = sg.output(c.first_bad, N);
+}
+
+template <typename Call>
+int wave_host(int device, const Call &c, double *elapsed_ms) {
+    using F = Family<Call>;
+    using T = typename Call::Real;
+    int rc = validate_wave(c, true);
     if (rc != PSA_OK) return rc;
     if (elapsed_ms) *elapsed_ms = 0.0;
     if (c.n_points == 0) return PSA_OK;
-    const int M = c.n_lines;
+    const int nc = 2 * F::n_waves(c);
     const size_t N = (size_t)c.n_points;
-    CombCall<T> d = c;
+    Call d = c;
     if (c.traj) d.flags |= PSA_OPT_TRAJ_LD;   // the device-side trajectory has its own leading dimension; the caller's is dense
     d.flags |= lossless_bit(c.flags, c.alpha);
     auto layout = [&](Staging<T> &sg) {
-        d.kappa = sg.input_soa(c.kappa, N, M);                      // [N][M] -> [M][N]
+        mismatch_of(d) = stage_mismatch(sg, c, 1, N);
         d.gamma = sg.input(c.gamma, (c.flags & PSA_BCAST_GAMMA) ? 1 : N);
         d.alpha = sg.input(c.alpha, (c.flags & PSA_BCAST_ALPHA) ? 1 : N);
-        d.a0 = sg.input_soa(c.a0, (c.flags & PSA_BCAST_A0) ? 1 : N, 2 * M);
-        d.a_end = sg.output_soa(c.a_end, N, 2 * M);
-        d.wave_end = sg.output_soa(c.wave_end, N, M);
-        d.wave_max = sg.output_soa(c.wave_max, N, M);
-        d.first_bad = sg.output(c.first_bad, N);
-        d.traj = sg.trajectory(c.traj, N, (size_t)(c.n_steps / c.save_every + 1), 2 * M);
+        d.a0 = sg.input_soa(c.a0, (c.flags & PSA_BCAST_A0) ? 1 : N, nc);
+        d.a_end = sg.output_soa(c.a_end, N, nc);
+        stage_wave_summary(sg, d, c, N);
+        d.traj = sg.trajectory(c.traj, N, (size_t)(c.n_steps / c.save_every + 1), nc);   // a sweep without rows: NULL in, NULL out
     };
-    return host_call<T>(device, "the multi-line RK4 sweep", elapsed_ms, layout, [&](hipStream_t st) { return comb_dev(st, d); });
+    return host_call<T>(device, F::sweep_what, elapsed_ms, layout, [&](hipStream_t st) { return wave_dev(st, d); });
 }
 
-// ---- fibre chains: S spans, one sweep launch + one epilogue (psa_chain.hip) each ------------------------------------
-template <typename T> struct EpilogueLaunch;
-template <> struct EpilogueLaunch<double> { static constexpr auto fn = psa::launch_chain_epilogue_f64; };
-template <> struct EpilogueLaunch<float> { static constexpr auto fn = psa::launch_chain_epilogue_f32; };
-
-// What differs between the chain families, stated once per family: the span's record decides.
-template <typename Span> struct ChainFamily;
-// The array of a span's record whose values the gauge accumulates: dbeta, or the multi-line model's kappa.
-template <typename Span> auto mismatch_of(Span &c) -> decltype((c.dbeta)) { return c.dbeta; }
-inline const double *&mismatch_of(CombCall<double> &c) { return c.kappa; }
-inline const double *mismatch_of(const CombCall<double> &c) { return c.kappa; }
-template <typename T> struct ChainFamily<SweepCall<T>> {   // 4 and 6 waves [p1, p2, s, i, ...]
+// What differs between the families, stated once per family: the record decides.  As a chain's span every family states the
+// index and stride of its signals (whose phase the gauge accumulates), its summary, and whether one span alone may end behind
+// its last saved row; a wave-summary family adds what validate_wave, wave_dev and wave_host read.
+template <typename T> struct Family<SweepCall<T>> {   // 4 and 6 waves [p1, p2, s, i, ...]
     static constexpr int sig_wave = 2, sig_stride = 2;
     static constexpr bool signal_summary = true;      // p_end / p_max
     static constexpr bool waves_optional = true;      // the per-wave summary where p_wave_end / p_wave_max are given
     static constexpr bool second_mismatch = true;     // dbeta2 / theta2 (6 waves)
     static constexpr bool sweep_tail = false;         // one span, too, must end on a saved row
+    static constexpr bool mismatch_soa = false;
     static constexpr const char *what = "the fibre chain";
     static int n_waves(const SweepCall<T> &c) { return c.n_waves; }
     static int n_signals(const SweepCall<T> &c) { return c.n_waves == 6 ? 2 : 1; }
     static int dbeta_rows(const SweepCall<T> &) { return 1; }   // rows of [N] a span's dbeta holds
-    static const T *stage_dbeta(Staging<T> &sg, const SweepCall<T> &c, int S, size_t N) { return sg.input(c.dbeta, S * N); }
     static int validate_first(const SweepCall<T> &first, bool) { return validate_common(first); }
     static int span_dev(void *stream, const SweepCall<T> &c) { return sweep_dev<T>(stream, c); }
     static void stage_summary(Staging<T> &sg, SweepCall<T> &d, const SweepCall<T> &c, size_t N) {
@@ -855,70 +734,87 @@ template <typename T> struct ChainFamily<SweepCall<T>> {   // 4 and 6 waves [p1,
         d.wave_max = sg.output_soa(c.wave_max, N, c.n_waves);
     }
 };
-template <typename T> struct ChainFamily<SinglePumpCall<T>> {   // three waves [p, s, i]: the three per-wave columns are the summary
-    static constexpr int sig_wave = 1, sig_stride = 2;
-    static constexpr bool signal_summary = false, waves_optional = false, second_mismatch = false, sweep_tail = false;
-    static constexpr const char *what = "the single-pump fibre chain";
-    static int n_waves(const SinglePumpCall<T> &) { return 3; }
-    static int n_signals(const SinglePumpCall<T> &) { return 1; }
-    static int dbeta_rows(const SinglePumpCall<T> &) { return 1; }
-    static const T *stage_dbeta(Staging<T> &sg, const SinglePumpCall<T> &c, int S, size_t N) { return sg.input(c.dbeta, S * N); }
-    static int validate_first(SinglePumpCall<T> first, bool host_form) {
+// A wave-summary family as a chain's span: the per-wave columns are the summary, and the sweep's own functions run the span.
+template <typename Call> struct WaveSpan {
+    static constexpr bool signal_summary = false, waves_optional = false, second_mismatch = false;
+    static int validate_first(Call first, bool host_form) {
         first.flags &= ~PSA_BCAST_TRANSFER;   // the chain's own bit
-        return validate_single_pump(first, host_form);
+        return validate_wave(first, host_form, true);
     }
-    static int span_dev(void *stream, const SinglePumpCall<T> &c) { return single_pump_dev(stream, c); }
-    static void stage_summary(Staging<T> &sg, SinglePumpCall<T> &d, const SinglePumpCall<T> &c, size_t N) {
-        d.wave_end = sg.output_soa(c.wave_end, N, 3);
-        d.wave_max = sg.output_soa(c.wave_max, N, 3);
-        d.first_bad = sg.output(c.first_bad, N);
+    static int span_dev(void *stream, const Call &c) { return wave_dev(stream, c, true); }
+    static void stage_summary(Staging<typename Call::Real> &sg, Call &d, const Call &c, size_t N) { stage_wave_summary(sg, d, c, N); }
+};
+template <typename T> struct Family<SinglePumpCall<T>> : WaveSpan<SinglePumpCall<T>> {   // three waves [p, s, i]
+    using Call = SinglePumpCall<T>;
+    using Args = psa::SinglePumpArgs<T>;
+    static constexpr int sig_wave = 1, sig_stride = 2;
+    static constexpr bool sweep_tail = false, sweep_rows = true, mismatch_soa = false;
+    static constexpr const char *name = "single-pump", *sweep_what = "the single-pump RK4 sweep", *what = "the single-pump fibre chain",
+                                 *launch_what = "rk4_sweep_single_pump launch";
+    static int n_waves(const Call &) { return 3; }
+    static int n_signals(const Call &) { return 1; }
+    static int dbeta_rows(const Call &) { return 1; }
+    static int check_count(const Call &) { return PSA_OK; }
+    static long long lanes_per_point(const Call &) { return 0; }   // one, or half a lane: PSA_MAX_POINTS holds, no lanes in the message
+    static hipError_t launch(hipStream_t st, Args &a, const Call &c) {
+        a.dbeta = c.dbeta;
+        if constexpr (sizeof(T) == 8) return psa::launch_sweep_single_pump_f64(st, c.flags, a);
+        else return psa::launch_sweep_single_pump_f32(st, c.flags, a);
     }
 };
-template <> struct ChainFamily<PairsCall> {   // two pumps and K pairs [p1, p2, s_1, i_1, ..., s_K, i_K]: K signals, K mismatches
+template <> struct Family<PairsCall> : WaveSpan<PairsCall> {   // two pumps and K pairs [p1, p2, s_1, i_1, ..., s_K, i_K]: K signals, K mismatches
+    using Call = PairsCall;
+    using Args = psa::PairsArgs;
     static constexpr int sig_wave = 2, sig_stride = 2;
-    static constexpr bool signal_summary = false, waves_optional = false, second_mismatch = false;
     // one span is the sweep's trajectory form and keeps the sweep's rule: A[-1] is the last SAVED row, a tail may follow it
     static constexpr bool sweep_tail = true;
-    static constexpr const char *what = "the multi-channel fibre chain";
-    static int n_waves(const PairsCall &c) { return 2 + 2 * c.n_pairs; }
-    static int n_signals(const PairsCall &c) { return c.n_pairs; }
-    static int dbeta_rows(const PairsCall &c) { return c.n_pairs; }   // a span's dbeta is SoA [K][N]
-    static int validate_first(PairsCall first, bool host_form) {
-        first.flags &= ~PSA_BCAST_TRANSFER;   // the chain's own bit
-        return validate_pairs(first, true, host_form);
+    static constexpr bool sweep_rows = false;    // psa_rk4_sweep_pairs_f64* stages no rows and takes no PSA_OPT_TRAJ_LD: the chain does
+    static constexpr bool mismatch_soa = true;   // a span's dbeta is SoA [K][N]
+    static constexpr const char *name = "multi-channel", *sweep_what = "the multi-channel RK4 sweep", *what = "the multi-channel fibre chain",
+                                 *launch_what = "rk4_sweep_pairs launch";
+    static int n_waves(const Call &c) { return 2 + 2 * c.n_pairs; }
+    static int n_signals(const Call &c) { return c.n_pairs; }
+    static int dbeta_rows(const Call &c) { return c.n_pairs; }
+    static int check_count(const Call &c) {
+        if (c.n_pairs >= 1 && c.n_pairs <= PSA_MAX_PAIRS) return PSA_OK;
+        return fail(PSA_E_NPAIRS, "n_pairs must be in [1, %d], got %d", PSA_MAX_PAIRS, c.n_pairs);
     }
-    static int span_dev(void *stream, const PairsCall &c) { return pairs_dev(stream, c, true); }
-    static const double *stage_dbeta(Staging<double> &sg, const PairsCall &c, int S, size_t N) {
-        return sg.input_soa(c.dbeta, N, c.n_pairs, S);                 // [S][N][K] -> [S][K][N]
+    // a point takes L lanes: the power of two >= n_pairs (at least 2)
+    static long long lanes_per_point(const Call &c) { return psa::pairs_lanes_per_point(c.n_pairs); }
+    static hipError_t launch(hipStream_t st, Args &a, const Call &c) {
+        a.dbeta = c.dbeta;
+        a.n_pairs = c.n_pairs;
+        return psa::launch_sweep_pairs_f64(st, c.flags, a);
     }
-    static void stage_summary(Staging<double> &sg, PairsCall &d, const PairsCall &c, size_t N) {
-        d.wave_end = sg.output_soa(c.wave_end, N, n_waves(c));
-        d.wave_max = sg.output_soa(c.wave_max, N, n_waves(c));
-        d.first_bad = sg.output(c.first_bad, N);
+};
+template <typename T> struct Family<CombCall<T>> : WaveSpan<CombCall<T>> {   // M lines, every one with its own accumulated phase: M "signals" at waves 0..M-1
+    using Call = CombCall<T>;
+    using Args = psa::CombArgs<T>;
+    static constexpr int sig_wave = 0, sig_stride = 1;
+    static constexpr bool sweep_tail = false, sweep_rows = true;
+    static constexpr bool mismatch_soa = true;   // a span's kappa is SoA [M][N]
+    static constexpr const char *name = "multi-line", *sweep_what = "the multi-line RK4 sweep", *what = "the multi-line fibre chain",
+                                 *launch_what = "rk4_sweep_comb launch";
+    static int n_waves(const Call &c) { return c.n_lines; }
+    static int n_signals(const Call &c) { return c.n_lines; }
+    static int dbeta_rows(const Call &c) { return c.n_lines; }
+    static int check_count(const Call &c) {
+        if (c.n_lines >= 3 && c.n_lines <= PSA_MAX_LINES) return PSA_OK;
+        return fail(PSA_E_NLINES, "n_lines must be in [3, %d], got %d", PSA_MAX_LINES, c.n_lines);
+    }
+    static long long lanes_per_point(const Call &) { return 0; }
+    static hipError_t launch(hipStream_t st, Args &a, const Call &c) {
+        a.kappa = c.kappa;
+        a.n_lines = c.n_lines;
+        if constexpr (sizeof(T) == 8) return psa::launch_sweep_comb_f64(st, c.flags, a);
+        else return psa::launch_sweep_comb_f32(st, c.flags, a);
     }
 };
 
-template <> struct ChainFamily<CombCall<double>> {   // M lines, every one with its own accumulated phase: M "signals" at waves 0..M-1
-    static constexpr int sig_wave = 0, sig_stride = 1;
-    static constexpr bool signal_summary = false, waves_optional = false, second_mismatch = false, sweep_tail = false;
-    static constexpr const char *what = "the multi-line fibre chain";
-    static int n_waves(const CombCall<double> &c) { return c.n_lines; }
-    static int n_signals(const CombCall<double> &c) { return c.n_lines; }
-    static int dbeta_rows(const CombCall<double> &c) { return c.n_lines; }   // a span's kappa is SoA [M][N]
-    static int validate_first(CombCall<double> first, bool host_form) {
-        first.flags &= ~PSA_BCAST_TRANSFER;   // the chain's own bit
-        return validate_comb(first, host_form);
-    }
-    static int span_dev(void *stream, const CombCall<double> &c) { return comb_dev(stream, c); }
-    static const double *stage_dbeta(Staging<double> &sg, const CombCall<double> &c, int S, size_t N) {
-        return sg.input_soa(c.kappa, N, c.n_lines, S);                 // [S][N][M] -> [S][M][N]
-    }
-    static void stage_summary(Staging<double> &sg, CombCall<double> &d, const CombCall<double> &c, size_t N) {
-        d.wave_end = sg.output_soa(c.wave_end, N, c.n_lines);
-        d.wave_max = sg.output_soa(c.wave_max, N, c.n_lines);
-        d.first_bad = sg.output(c.first_bad, N);
-    }
-};
+// ---- fibre chains: S spans, one sweep launch + one epilogue (psa_chain.hip) each ------------------------------------
+template <typename T> struct EpilogueLaunch;
+template <> struct EpilogueLaunch<double> { static constexpr auto fn = psa::launch_chain_epilogue_f64; };
+template <> struct EpilogueLaunch<float> { static constexpr auto fn = psa::launch_chain_epilogue_f32; };
 
 // Device scratch of a chain of more than one span: Theta (float64, one per signal), the next span's a0, and the span's own
 // outputs before they are folded into the running ones.  Without a base it only measures (`bytes`).
@@ -947,7 +843,7 @@ struct ChainScratch {
     }
     template <typename Span>
     static ChainScratch of(void *base, const Span &c) {
-        using F = ChainFamily<Span>;
+        using F = Family<Span>;
         const int n_waves = F::n_waves(c);
         return ChainScratch(base, (size_t)c.n_points, n_waves, F::second_mismatch && n_waves == 6, F::signal_summary,
                             !F::waves_optional || c.wave_end != nullptr, F::second_mismatch ? 1 : F::n_signals(c));
@@ -993,7 +889,7 @@ struct SpanJoin {
 };
 
 // The grid rules of a chain's spans (every chain family); *rows_total = sum over spans of n_steps[s] / save_every + 1.
-// tail_ok: this span count may end behind its last saved row, as a sweep may (ChainFamily::sweep_tail: one span alone)
+// tail_ok: this span count may end behind its last saved row, as a sweep may (Family::sweep_tail: one span alone)
 int validate_spans(int n_segments, const int64_t *n_steps, const double *seg_len, int32_t save_every, int64_t *rows_total,
                    bool tail_ok = false) {
     int64_t rows = 0;
@@ -1031,7 +927,7 @@ std::vector<unsigned char> lossless_spans(uint32_t flags, const T *alpha, int S,
 // argument rules of every chain: the span count, the first span's grid through the family's sweep validator, the later spans
 template <typename Span>
 int validate_chain(const ChainCall<Span> &c, bool host_form, int64_t *rows_total) {
-    using F = ChainFamily<Span>;
+    using F = Family<Span>;
     if (c.n_segments < 1) return fail(PSA_E_NSTEPS, "n_segments must be >= 1, got %d", c.n_segments);
     if (!c.n_steps || !c.seg_len) return fail(PSA_E_NULLPTR, "n_steps / seg_len is NULL");
     Span first = c.s;   // the sweep's rules, on the first span's grid
@@ -1055,7 +951,7 @@ int validate_chain(const ChainCall<Span> &c, bool host_form, int64_t *rows_total
 
 template <typename Span>
 int chain_dev(void *stream, const ChainCall<Span> &c) {
-    using F = ChainFamily<Span>;
+    using F = Family<Span>;
     using T = typename Span::Real;
     int64_t rows_total = 0;
     int rc = validate_chain(c, false, &rows_total);
@@ -1135,7 +1031,7 @@ int chain_dev(void *stream, const ChainCall<Span> &c) {
 
 template <typename Span>
 int chain_host(int device, const ChainCall<Span> &c, double *elapsed_ms) {
-    using F = ChainFamily<Span>;
+    using F = Family<Span>;
     using T = typename Span::Real;
     int64_t rows_total = 0;
     int rc = validate_chain(c, true, &rows_total);
@@ -1152,7 +1048,7 @@ int chain_host(int device, const ChainCall<Span> &c, double *elapsed_ms) {
     d.lossless = lossless.data();
     const T *tr = S > 1 ? c.transfer : nullptr;
     auto layout = [&](Staging<T> &sg) {
-        mismatch_of(d.s) = F::stage_dbeta(sg, c.s, S, N);
+        mismatch_of(d.s) = stage_mismatch(sg, c.s, S, N);
         if constexpr (F::second_mismatch) d.s.dbeta2 = sg.input(c.s.dbeta2, S * N);
         d.s.gamma = sg.input(c.s.gamma, (flags & PSA_BCAST_GAMMA) ? (size_t)S : S * N);
         d.s.alpha = sg.input(c.s.alpha, (flags & PSA_BCAST_ALPHA) ? (size_t)S : S * N);
@@ -1666,14 +1562,14 @@ int psa_rk4_sweep_pairs_f64(int device, int n_pairs, int64_t n_points, int64_t n
                             const double *dbeta, const double *gamma, const double *alpha, const double *a0_re_im,
                             uint32_t flags, double *a_end_re_im, double *p_wave_end, double *p_wave_max,
                             int64_t *first_bad_step, double *elapsed_ms_or_null) {
-    return pairs_host(device, {n_pairs, n_points, n_steps, z_max, save_every, dbeta, gamma, alpha, a0_re_im, flags, a_end_re_im,
+    return wave_host(device, PairsCall{n_pairs, n_points, n_steps, z_max, save_every, dbeta, gamma, alpha, a0_re_im, flags, a_end_re_im,
                                p_wave_end, p_wave_max, first_bad_step}, elapsed_ms_or_null);
 }
 int psa_rk4_sweep_pairs_f64_dev(void *stream, int n_pairs, int64_t n_points, int64_t n_steps, double z_max,
                                 int32_t save_every, const double *d_dbeta_soa, const double *d_gamma, const double *d_alpha,
                                 const double *d_a0_soa, uint32_t flags, double *d_a_end_soa, double *d_p_wave_end_soa,
                                 double *d_p_wave_max_soa, int64_t *d_first_bad_step) {
-    return pairs_dev(stream, {n_pairs, n_points, n_steps, z_max, save_every, d_dbeta_soa, d_gamma, d_alpha, d_a0_soa, flags,
+    return wave_dev(stream, PairsCall{n_pairs, n_points, n_steps, z_max, save_every, d_dbeta_soa, d_gamma, d_alpha, d_a0_soa, flags,
                               d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step});
 }
 
@@ -1682,7 +1578,7 @@ int psa_rk4_single_pump_f64(int device, int64_t n_points, int64_t n_steps, doubl
                             const double *dbeta, const double *gamma, const double *alpha, const double *a0_re_im,
                             uint32_t flags, double *a_end_re_im, double *p_wave_end, double *p_wave_max,
                             int64_t *first_bad_step, double *traj_or_null, double *elapsed_ms_or_null) {
-    return single_pump_host(device, SinglePumpCall<double>{n_points, n_steps, z_max, save_every, dbeta, gamma, alpha, a0_re_im, flags,
+    return wave_host(device, SinglePumpCall<double>{n_points, n_steps, z_max, save_every, dbeta, gamma, alpha, a0_re_im, flags,
                                                             a_end_re_im, p_wave_end, p_wave_max, first_bad_step, traj_or_null},
                             elapsed_ms_or_null);
 }
@@ -1690,7 +1586,7 @@ int psa_rk4_single_pump_f64_dev(void *stream, int64_t n_points, int64_t n_steps,
                                 const double *d_dbeta, const double *d_gamma, const double *d_alpha, const double *d_a0_soa,
                                 uint32_t flags, double *d_a_end_soa, double *d_p_wave_end_soa, double *d_p_wave_max_soa,
                                 int64_t *d_first_bad_step, double *d_traj_soa_or_null) {
-    return single_pump_dev(stream, SinglePumpCall<double>{n_points, n_steps, z_max, save_every, d_dbeta, d_gamma, d_alpha, d_a0_soa,
+    return wave_dev(stream, SinglePumpCall<double>{n_points, n_steps, z_max, save_every, d_dbeta, d_gamma, d_alpha, d_a0_soa,
                                                           flags, d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step,
                                                           d_traj_soa_or_null});
 }
@@ -1698,7 +1594,7 @@ int psa_rk4_single_pump_f32(int device, int64_t n_points, int64_t n_steps, doubl
                             const float *dbeta, const float *gamma, const float *alpha, const float *a0_re_im,
                             uint32_t flags, float *a_end_re_im, float *p_wave_end, float *p_wave_max,
                             int64_t *first_bad_step, float *traj_or_null, double *elapsed_ms_or_null) {
-    return single_pump_host(device, SinglePumpCall<float>{n_points, n_steps, z_max, save_every, dbeta, gamma, alpha, a0_re_im, flags,
+    return wave_host(device, SinglePumpCall<float>{n_points, n_steps, z_max, save_every, dbeta, gamma, alpha, a0_re_im, flags,
                                                            a_end_re_im, p_wave_end, p_wave_max, first_bad_step, traj_or_null},
                             elapsed_ms_or_null);
 }
@@ -1706,7 +1602,7 @@ int psa_rk4_single_pump_f32_dev(void *stream, int64_t n_points, int64_t n_steps,
                                 const float *d_dbeta, const float *d_gamma, const float *d_alpha, const float *d_a0_soa,
                                 uint32_t flags, float *d_a_end_soa, float *d_p_wave_end_soa, float *d_p_wave_max_soa,
                                 int64_t *d_first_bad_step, float *d_traj_soa_or_null) {
-    return single_pump_dev(stream, SinglePumpCall<float>{n_points, n_steps, z_max, save_every, d_dbeta, d_gamma, d_alpha, d_a0_soa,
+    return wave_dev(stream, SinglePumpCall<float>{n_points, n_steps, z_max, save_every, d_dbeta, d_gamma, d_alpha, d_a0_soa,
                                                          flags, d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step,
                                                          d_traj_soa_or_null});
 }
@@ -1756,14 +1652,14 @@ int psa_rk4_comb_f64(int device, int n_lines, int64_t n_points, int64_t n_steps,
                      const double *kappa, const double *gamma, const double *alpha, const double *a0_re_im, uint32_t flags,
                      double *a_end_re_im, double *p_wave_end, double *p_wave_max, int64_t *first_bad_step, double *traj_or_null,
                      double *elapsed_ms_or_null) {
-    return comb_host(device, CombCall<double>{n_lines, n_points, n_steps, z_max, save_every, kappa, gamma, alpha, a0_re_im, flags,
+    return wave_host(device, CombCall<double>{n_lines, n_points, n_steps, z_max, save_every, kappa, gamma, alpha, a0_re_im, flags,
                                               a_end_re_im, p_wave_end, p_wave_max, first_bad_step, traj_or_null}, elapsed_ms_or_null);
 }
 int psa_rk4_comb_f64_dev(void *stream, int n_lines, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
                          const double *d_kappa_soa, const double *d_gamma, const double *d_alpha, const double *d_a0_soa,
                          uint32_t flags, double *d_a_end_soa, double *d_p_wave_end_soa, double *d_p_wave_max_soa,
                          int64_t *d_first_bad_step, double *d_traj_soa_or_null) {
-    return comb_dev(stream, CombCall<double>{n_lines, n_points, n_steps, z_max, save_every, d_kappa_soa, d_gamma, d_alpha, d_a0_soa,
+    return wave_dev(stream, CombCall<double>{n_lines, n_points, n_steps, z_max, save_every, d_kappa_soa, d_gamma, d_alpha, d_a0_soa,
                                              flags, d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step,
                                              d_traj_soa_or_null});
 }
@@ -1771,14 +1667,14 @@ int psa_rk4_comb_f32(int device, int n_lines, int64_t n_points, int64_t n_steps,
                      const float *kappa, const float *gamma, const float *alpha, const float *a0_re_im, uint32_t flags,
                      float *a_end_re_im, float *p_wave_end, float *p_wave_max, int64_t *first_bad_step, float *traj_or_null,
                      double *elapsed_ms_or_null) {
-    return comb_host(device, CombCall<float>{n_lines, n_points, n_steps, z_max, save_every, kappa, gamma, alpha, a0_re_im, flags,
+    return wave_host(device, CombCall<float>{n_lines, n_points, n_steps, z_max, save_every, kappa, gamma, alpha, a0_re_im, flags,
                                              a_end_re_im, p_wave_end, p_wave_max, first_bad_step, traj_or_null}, elapsed_ms_or_null);
 }
 int psa_rk4_comb_f32_dev(void *stream, int n_lines, int64_t n_points, int64_t n_steps, double z_max, int32_t save_every,
                          const float *d_kappa_soa, const float *d_gamma, const float *d_alpha, const float *d_a0_soa,
                          uint32_t flags, float *d_a_end_soa, float *d_p_wave_end_soa, float *d_p_wave_max_soa,
                          int64_t *d_first_bad_step, float *d_traj_soa_or_null) {
-    return comb_dev(stream, CombCall<float>{n_lines, n_points, n_steps, z_max, save_every, d_kappa_soa, d_gamma, d_alpha, d_a0_soa,
+    return wave_dev(stream, CombCall<float>{n_lines, n_points, n_steps, z_max, save_every, d_kappa_soa, d_gamma, d_alpha, d_a0_soa,
                                             flags, d_a_end_soa, d_p_wave_end_soa, d_p_wave_max_soa, d_first_bad_step,
                                             d_traj_soa_or_null});
 }

@@ -130,60 +130,106 @@ def rk4_sweep(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps: Optio
                        r["elapsed_ms"], r.get("traj"), r.get("p_wave_end"), r.get("p_wave_max"))
 
 
-# ---- multi-channel sweeps: two pumps and K signal/idler pairs ----------------------------------------------------------
+# ---- the wave-summary families: multi-channel, single-pump and multi-line sweeps ------------------------------------------
 @dataclass
-class PairsResult:
-    """Outcome of a multi-channel sweep; waves [p1, p2, s_1, i_1, ..., s_K, i_K], NW = 2 + 2K columns."""
-    a_end: np.ndarray            # (N, NW) complex: state at the last SAVED row
-    p_wave_end: np.ndarray       # (N, NW) |A_j|^2 there
-    p_wave_max: np.ndarray       # (N, NW) max over saved rows (z = 0 included), NaN-propagating
+class _WaveResult:
+    """What the results of the three families share: the fields, and the drivers' NaN rules for a power over a seed power."""
+    a_end: np.ndarray            # (N, n_waves) complex: state at the last SAVED row
+    p_wave_end: np.ndarray       # (N, n_waves) |A_j|^2 there
+    p_wave_max: np.ndarray       # (N, n_waves) max over saved rows (z = 0 included), NaN-propagating
     first_bad_step: np.ndarray   # (N,) int64, -1 = finite everywhere (or check_nan off)
     n_steps: int
     save_every: int
     elapsed_ms: float            # kernel time (hipEvents)
-    p_wave_in: Optional[np.ndarray] = None   # (1 | N, NW) |A_j(0)|^2: what pump_depletion compares with
-    traj: Optional[np.ndarray] = None        # (N, n_saved, NW) complex when requested
+    p_wave_in: Optional[np.ndarray] = None   # (1 | N, n_waves) |A_j(0)|^2: what pump_depletion compares with
+    traj: Optional[np.ndarray] = None        # (N, n_saved, n_waves) complex when requested
+
+    def _over_seed(self, cols, p0, mode: str, unit: str) -> np.ndarray:
+        """The metric columns ``cols`` over the seed power p0 with the drivers' NaN rule (scan_mismtach.py:376-392): a point
+        with first_bad_step >= 0, a non-positive or non-finite seed power, a non-finite or non-positive ratio give NaN.  One
+        column (an int) gives (N,) and takes p0 as a scalar or (N,); C columns (a slice) give (N, C) and take (C,) or (N, C)."""
+        u = check_gain(mode, unit)
+        metric = (self.p_wave_max if mode == "max" else self.p_wave_end)[:, cols]
+        N = int(self.p_wave_end.shape[0])
+        p0 = np.asarray(p0, dtype=float)
+        if metric.ndim == 1:
+            if p0.shape not in ((), (1,), (N,)):
+                raise ValueError(f"p0 must be a scalar or have shape ({N},), got {p0.shape}")
+        elif p0.shape not in (metric.shape[1:], metric.shape):
+            raise ValueError(f"p0 must have shape ({metric.shape[1]},) or ({N}, {metric.shape[1]}), got {p0.shape}")
+        p0 = np.broadcast_to(p0, metric.shape)
+        finite = np.asarray(self.first_bad_step) < 0
+        with np.errstate(all="ignore"):
+            ok = (p0 > 0.0) & np.isfinite(p0) & (finite if metric.ndim == 1 else finite[:, None])
+            g = metric / np.where(ok, p0, 1.0)
+            ok &= np.isfinite(g) & (g > 0.0)
+            return np.where(ok, g if u == "linear" else 10.0 * np.log10(np.where(ok, g, 1.0)), np.nan)
+
+    def _depletion(self, pumps: slice, driver: str) -> np.ndarray:
+        """(N,): the fraction of the input power of the columns ``pumps`` that is gone at the last saved row; NaN for a
+        failed point or dark pumps."""
+        if self.p_wave_in is None:
+            raise ValueError(f"pump_depletion needs p_wave_in (set by {driver})")
+        N = int(self.p_wave_end.shape[0])
+        p_in = np.broadcast_to(self.p_wave_in[:, pumps].sum(axis=1), (N,))
+        with np.errstate(all="ignore"):
+            ok = (p_in > 0.0) & np.isfinite(p_in) & (np.asarray(self.first_bad_step) < 0)
+            d = 1.0 - self.p_wave_end[:, pumps].sum(axis=1) / np.where(ok, p_in, 1.0)
+            return np.where(ok & np.isfinite(d), d, np.nan)
+
+
+def _mismatch_columns(x, name: str, letter: str, low: int, high: int) -> np.ndarray:
+    """A mismatch of several columns, (N, C) with low <= C <= high, as float64."""
+    x = np.asarray(x, dtype=float)
+    if x.ndim != 2 or not low <= x.shape[1] <= high:
+        raise ValueError(f"{name} must have shape (N, {letter}) with {low} <= {letter} <= {high}, got {x.shape}")
+    return x
+
+
+def _sweep_waves(result, host_fn, axes, key: str, checked, *, z_max, dz, n_steps, save_every, a0, dtype, device, devices,
+                 reroute=None, **options):
+    """The driver of a wave-summary family: the dtype and grid rules, ``checked()`` -> (the mismatch (N, ...), the columns of
+    a0, what the a0 error says they are for), the a0 rule, host_fn(**{key: mismatch}, ...) over the devices, and the family's
+    ``result``.  ``reroute(kw, N)`` -> (host_fn, axes, kw) sends the call elsewhere once its arguments stand."""
+    f64 = np.dtype(dtype) == np.dtype(np.float64)
+    if not f64 and np.dtype(dtype) != np.dtype(np.float32):
+        raise ValueError(f"dtype must be float64 or float32, got {np.dtype(dtype)}")
+    n_steps, save_every = _fixed_grid(z_max, dz, n_steps, save_every)
+    mismatch, nw, what = checked()
+    N = int(mismatch.shape[0])
+    a0 = np.asarray(a0, dtype=np.complex128 if f64 else np.complex64)
+    if a0.shape not in ((nw,), (1, nw), (N, nw)):
+        raise ValueError(f"a0 must have shape ({nw},) or ({N}, {nw}){what}, got {a0.shape}")
+    kw = dict({key: mismatch}, n_steps=n_steps, z_max=float(z_max), save_every=save_every, a0=a0, **options)
+    if not f64:
+        kw["dtype"] = np.float32          # the float64 call stays as it was: no dtype argument
+    if reroute is not None:
+        host_fn, axes, kw = reroute(kw, N)
+    r = _run(host_fn, axes, N, kw, device, devices)
+    return result(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"], n_steps, save_every, r["elapsed_ms"],
+                  np.abs(np.atleast_2d(a0)) ** 2, r.get("traj"))
+
+
+@dataclass
+class PairsResult(_WaveResult):
+    """Outcome of a multi-channel sweep; waves [p1, p2, s_1, i_1, ..., s_K, i_K], NW = 2 + 2K columns."""
 
     @property
     def n_pairs(self) -> int:
         return (int(self.p_wave_end.shape[1]) - 2) // 2
 
-    def _ratio(self, first_wave: int, p0, mode: str, unit: str) -> np.ndarray:
-        """metric of waves first_wave, first_wave + 2, ... over the seed powers p0, with the drivers' NaN rule
-        (scan_mismtach.py:376-392): a point with first_bad_step >= 0, a non-positive seed power, a non-finite or
-        non-positive ratio give NaN."""
-        u = check_gain(mode, unit)
-        N, K = int(self.p_wave_end.shape[0]), self.n_pairs
-        p0 = np.asarray(p0, dtype=float)
-        if p0.shape not in ((K,), (N, K)):
-            raise ValueError(f"p0 must have shape ({K},) or ({N}, {K}), got {p0.shape}")
-        p0 = np.broadcast_to(p0, (N, K))
-        metric = (self.p_wave_max if mode == "max" else self.p_wave_end)[:, first_wave::2][:, :K]
-        with np.errstate(all="ignore"):
-            ok = (p0 > 0.0) & np.isfinite(p0) & (np.asarray(self.first_bad_step) < 0)[:, None]
-            g = metric / np.where(ok, p0, 1.0)
-            ok &= np.isfinite(g) & (g > 0.0)
-            return np.where(ok, g if u == "linear" else 10.0 * np.log10(np.where(ok, g, 1.0)), np.nan)
-
     def channel_gain(self, p0, *, mode: str = "max", unit: str = "dB") -> np.ndarray:
         """(N, K): every signal's gain over its seed power p0 (K,) or (N, K); gain_mode "end" | "max"."""
-        return self._ratio(2, p0, mode, unit)
+        return self._over_seed(slice(2, None, 2), p0, mode, unit)
 
     def idler_conversion(self, p0, *, mode: str = "max", unit: str = "dB") -> np.ndarray:
         """(N, K): every idler's power over the SIGNAL's seed power p0 (K,) or (N, K): the conversion efficiency."""
-        return self._ratio(3, p0, mode, unit)
+        return self._over_seed(slice(3, None, 2), p0, mode, unit)
 
     def pump_depletion(self) -> np.ndarray:
         """(N,): the fraction of the two pumps' input power that is gone at the last saved row,
         1 - (P_p1 + P_p2)_end / (P_p1 + P_p2)_in (fibre loss included); NaN for a failed point or dark pumps."""
-        if self.p_wave_in is None:
-            raise ValueError("pump_depletion needs p_wave_in (set by rk4_sweep_pairs)")
-        N = int(self.p_wave_end.shape[0])
-        p_in = np.broadcast_to(self.p_wave_in[:, :2].sum(axis=1), (N,))
-        with np.errstate(all="ignore"):
-            ok = (p_in > 0.0) & np.isfinite(p_in) & (np.asarray(self.first_bad_step) < 0)
-            d = 1.0 - self.p_wave_end[:, :2].sum(axis=1) / np.where(ok, p_in, 1.0)
-            return np.where(ok & np.isfinite(d), d, np.nan)
+        return self._depletion(slice(0, 2), "rk4_sweep_pairs")
 
 
 def rk4_sweep_pairs(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps: Optional[int] = None,
@@ -200,77 +246,36 @@ def rk4_sweep_pairs(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps:
     points over several GPUs of this process.  ``want_traj`` also returns every saved row (the chain's entry point with one
     span: the summaries are the same bits).  Fixed-step float64 only: no float32 or adaptive form; concatenated spans
     (copier - mid-stage - PSA) are rk4_chain_pairs."""
-    n_steps, save_every = _fixed_grid(z_max, dz, n_steps, save_every)
-    db = np.asarray(dbeta, dtype=float)
-    if db.ndim != 2 or not 1 <= db.shape[1] <= _native.MAX_PAIRS:
-        raise ValueError(f"dbeta must have shape (N, K) with 1 <= K <= {_native.MAX_PAIRS}, got {db.shape}")
-    nw = 2 + 2 * int(db.shape[1])
-    a0 = np.asarray(a0, dtype=np.complex128)
-    if a0.shape not in ((nw,), (1, nw), (db.shape[0], nw)):
-        raise ValueError(f"a0 must have shape ({nw},) or ({db.shape[0]}, {nw}) for {db.shape[1]} pairs, got {a0.shape}")
-    kw = dict(dbeta=db, n_steps=n_steps, z_max=float(z_max), save_every=save_every, gamma=gamma, alpha=alpha, a0=a0,
-              check_nan=check_nan, exact_step=exact_step)
-    if want_traj:   # one span of the chain's entry point: dbeta (1, N, K), gamma / alpha (1,) or (1, N)
-        N = int(db.shape[0])
-        kw.update(dbeta=db[None], n_steps=[kw.pop("n_steps")], seg_len=[kw.pop("z_max")], want_traj=True,
+    def checked():
+        db = _mismatch_columns(dbeta, "dbeta", "K", 1, _native.MAX_PAIRS)
+        return db, 2 + 2 * int(db.shape[1]), f" for {db.shape[1]} pairs"
+
+    def one_span(kw, N):   # one span of the chain's entry point: dbeta (1, N, K), gamma / alpha (1,) or (1, N)
+        kw.update(dbeta=kw["dbeta"][None], n_steps=[kw.pop("n_steps")], seg_len=[kw.pop("z_max")], want_traj=True,
                   gamma=_span_column([gamma], 1, N, "gamma", np.float64), alpha=_span_column([alpha], 1, N, "alpha", np.float64))
-        r = _run(_native.pairs_chain_host, PAIRS_CHAIN_AXES, N, kw, device, devices)
-    else:
-        r = _run(_native.sweep_pairs_host, PAIRS_AXES, db.shape[0], kw, device, devices)
-    p_in = np.abs(np.atleast_2d(a0)) ** 2
-    return PairsResult(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"], n_steps, save_every,
-                       r["elapsed_ms"], p_in, r.get("traj"))
+        return _native.pairs_chain_host, PAIRS_CHAIN_AXES, kw
+
+    return _sweep_waves(PairsResult, _native.sweep_pairs_host, PAIRS_AXES, "dbeta", checked, z_max=z_max, dz=dz, n_steps=n_steps,
+                        save_every=save_every, a0=a0, dtype=np.float64, device=device, devices=devices,
+                        reroute=one_span if want_traj else None, gamma=gamma, alpha=alpha, check_nan=check_nan, exact_step=exact_step)
 
 
-# ---- single-pump (degenerate) sweeps: one pump, a signal and an idler ---------------------------------------------------
 @dataclass
-class SinglePumpResult:
+class SinglePumpResult(_WaveResult):
     """Outcome of a single-pump sweep; waves [p, s, i], 3 columns."""
-    a_end: np.ndarray            # (N, 3) complex: state at the last SAVED row
-    p_wave_end: np.ndarray       # (N, 3) |A_j|^2 there
-    p_wave_max: np.ndarray       # (N, 3) max over saved rows (z = 0 included), NaN-propagating
-    first_bad_step: np.ndarray   # (N,) int64, -1 = finite everywhere (or check_nan off)
-    n_steps: int
-    save_every: int
-    elapsed_ms: float            # kernel time (hipEvents)
-    p_wave_in: Optional[np.ndarray] = None   # (1 | N, 3) |A_j(0)|^2: what pump_depletion compares with
-    traj: Optional[np.ndarray] = None        # (N, n_saved, 3) complex when requested
-
-    def _ratio(self, wave: int, p0, mode: str, unit: str) -> np.ndarray:
-        """metric of ``wave`` over the seed power p0, with PairsResult._ratio's NaN rule: a point with first_bad_step >= 0, a
-        non-positive or non-finite seed power, a non-finite or non-positive ratio give NaN."""
-        u = check_gain(mode, unit)
-        N = int(self.p_wave_end.shape[0])
-        p0 = np.asarray(p0, dtype=float)
-        if p0.shape not in ((), (1,), (N,)):
-            raise ValueError(f"p0 must be a scalar or have shape ({N},), got {p0.shape}")
-        p0 = np.broadcast_to(p0, (N,))
-        metric = (self.p_wave_max if mode == "max" else self.p_wave_end)[:, wave]
-        with np.errstate(all="ignore"):
-            ok = (p0 > 0.0) & np.isfinite(p0) & (np.asarray(self.first_bad_step) < 0)
-            g = metric / np.where(ok, p0, 1.0)
-            ok &= np.isfinite(g) & (g > 0.0)
-            return np.where(ok, g if u == "linear" else 10.0 * np.log10(np.where(ok, g, 1.0)), np.nan)
 
     def signal_gain(self, p0, *, mode: str = "max", unit: str = "dB") -> np.ndarray:
         """(N,): the signal's gain over its seed power p0, a scalar or (N,); gain_mode "end" | "max"."""
-        return self._ratio(1, p0, mode, unit)
+        return self._over_seed(1, p0, mode, unit)
 
     def idler_conversion(self, p0, *, mode: str = "max", unit: str = "dB") -> np.ndarray:
         """(N,): the idler's power over the SIGNAL's seed power p0, a scalar or (N,): the conversion efficiency."""
-        return self._ratio(2, p0, mode, unit)
+        return self._over_seed(2, p0, mode, unit)
 
     def pump_depletion(self) -> np.ndarray:
         """(N,): the fraction of the pump's input power that is gone at the last saved row, 1 - P_p_end / P_p_in (fibre
         loss included); NaN for a failed point or a dark pump."""
-        if self.p_wave_in is None:
-            raise ValueError("pump_depletion needs p_wave_in (set by rk4_sweep_single_pump)")
-        N = int(self.p_wave_end.shape[0])
-        p_in = np.broadcast_to(self.p_wave_in[:, 0], (N,))
-        with np.errstate(all="ignore"):
-            ok = (p_in > 0.0) & np.isfinite(p_in) & (np.asarray(self.first_bad_step) < 0)
-            d = 1.0 - self.p_wave_end[:, 0] / np.where(ok, p_in, 1.0)
-            return np.where(ok & np.isfinite(d), d, np.nan)
+        return self._depletion(slice(0, 1), "rk4_sweep_single_pump")
 
 
 def rk4_sweep_single_pump(dbeta, *, z_max: float, dz: Optional[float] = None, n_steps: Optional[int] = None,
@@ -287,55 +292,26 @@ def rk4_sweep_single_pump(dbeta, *, z_max: float, dz: Optional[float] = None, n_
     ``dtype=np.float32`` runs the packed float32 kernel (two points per lane) and returns float32 / complex64
     arrays; any dtype but float64 and float32 is a ValueError.  Fixed-step only: no adaptive form; concatenated spans (copier
     - mid-stage - PSA) are rk4_chain_single_pump, in float64."""
-    if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
-        raise ValueError(f"dtype must be float64 or float32, got {np.dtype(dtype)}")
-    n_steps, save_every = _fixed_grid(z_max, dz, n_steps, save_every)
-    db = np.atleast_1d(np.asarray(dbeta, dtype=float))
-    if db.ndim != 1:
-        raise ValueError(f"dbeta must be a scalar or have shape (N,), got {db.shape}")
-    a0 = np.asarray(a0, dtype=np.complex128 if np.dtype(dtype) == np.dtype(np.float64) else np.complex64)
-    if a0.shape not in ((3,), (1, 3), (db.shape[0], 3)):
-        raise ValueError(f"a0 must have shape (3,) or ({db.shape[0]}, 3), got {a0.shape}")
-    kw = dict(dbeta=db, n_steps=n_steps, z_max=float(z_max), save_every=save_every, gamma=gamma, alpha=alpha, a0=a0,
-              check_nan=check_nan, exact_step=exact_step, want_traj=want_traj)
-    if np.dtype(dtype) != np.dtype(np.float64):
-        kw["dtype"] = np.float32          # the float64 call stays as it was: no dtype argument
-    r = _run(_native.single_pump_host, SWEEP_AXES, db.shape[0], kw, device, devices)
-    p_in = np.abs(np.atleast_2d(a0)) ** 2
-    return SinglePumpResult(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"], n_steps, save_every,
-                            r["elapsed_ms"], p_in, r.get("traj"))
+    def checked():
+        db = np.atleast_1d(np.asarray(dbeta, dtype=float))
+        if db.ndim != 1:
+            raise ValueError(f"dbeta must be a scalar or have shape (N,), got {db.shape}")
+        return db, 3, ""
+
+    return _sweep_waves(SinglePumpResult, _native.single_pump_host, SWEEP_AXES, "dbeta", checked, z_max=z_max, dz=dz,
+                        n_steps=n_steps, save_every=save_every, a0=a0, dtype=dtype, device=device, devices=devices, gamma=gamma,
+                        alpha=alpha, check_nan=check_nan, exact_step=exact_step, want_traj=want_traj)
 
 
-# ---- multi-line ("comb") sweeps: M equally spaced lines, every FWM product among them ----------------------------------------
 @dataclass
-class CombResult:
+class CombResult(_WaveResult):
     """Outcome of a multi-line sweep; lines 0..M-1 ascending in frequency, M columns."""
-    a_end: np.ndarray            # (N, M) complex: state at the last SAVED row
-    p_wave_end: np.ndarray       # (N, M) |A_m|^2 there
-    p_wave_max: np.ndarray       # (N, M) max over saved rows (z = 0 included), NaN-propagating
-    first_bad_step: np.ndarray   # (N,) int64, -1 = finite everywhere (or check_nan off); otherwise the exact step
-    n_steps: int
-    save_every: int
-    elapsed_ms: float            # kernel time (hipEvents)
-    p_wave_in: Optional[np.ndarray] = None   # (1 | N, M) |A_m(0)|^2
-    traj: Optional[np.ndarray] = None        # (N, n_saved, M) complex when requested
 
     def line_gain(self, p0, *, mode: str = "max", unit: str = "dB") -> np.ndarray:
         """(N, M): every line's power over its input power p0 (M,) or (N, M); gain_mode "end" | "max".  The drivers' NaN
         rule per line (scan_mismtach.py:376-392): a point with first_bad_step >= 0, a non-positive or non-finite input
         power (a dark line), a non-finite or non-positive ratio give NaN."""
-        u = check_gain(mode, unit)
-        N, M = (int(x) for x in self.p_wave_end.shape)
-        p0 = np.asarray(p0, dtype=float)
-        if p0.shape not in ((M,), (N, M)):
-            raise ValueError(f"p0 must have shape ({M},) or ({N}, {M}), got {p0.shape}")
-        p0 = np.broadcast_to(p0, (N, M))
-        metric = self.p_wave_max if mode == "max" else self.p_wave_end
-        with np.errstate(all="ignore"):
-            ok = (p0 > 0.0) & np.isfinite(p0) & (np.asarray(self.first_bad_step) < 0)[:, None]
-            g = metric / np.where(ok, p0, 1.0)
-            ok &= np.isfinite(g) & (g > 0.0)
-            return np.where(ok, g if u == "linear" else 10.0 * np.log10(np.where(ok, g, 1.0)), np.nan)
+        return self._over_seed(slice(None), p0, mode, unit)
 
     def total_power(self) -> np.ndarray:
         """(N,): sum of the lines' powers at the last saved row (conserved for alpha = 0); NaN for a failed point."""
@@ -361,23 +337,13 @@ def rk4_sweep_comb(kappa, *, z_max: float, dz: Optional[float] = None, n_steps: 
     the chip with two points per lane (131 072 points on one device; DESIGN.md 3.3f has the rates per M) and gains nothing on
     smaller ones.  Any dtype but float64 and float32 is a ValueError.  Fixed-step on a uniform grid only: no RK45 or
     process-group form; chains of spans are rk4_chain_comb, in float64."""
-    if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
-        raise ValueError(f"dtype must be float64 or float32, got {np.dtype(dtype)}")
-    n_steps, save_every = _fixed_grid(z_max, dz, n_steps, save_every)
-    kp = np.asarray(kappa, dtype=float)
-    if kp.ndim != 2 or not 3 <= kp.shape[1] <= _native.MAX_LINES:
-        raise ValueError(f"kappa must have shape (N, M) with 3 <= M <= {_native.MAX_LINES}, got {kp.shape}")
-    N, M = (int(x) for x in kp.shape)
-    a0 = np.asarray(a0, dtype=np.complex128 if np.dtype(dtype) == np.dtype(np.float64) else np.complex64)
-    if a0.shape not in ((M,), (1, M), (N, M)):
-        raise ValueError(f"a0 must have shape ({M},) or ({N}, {M}) for {M} lines, got {a0.shape}")
-    kw = dict(kappa=kp, n_steps=n_steps, z_max=float(z_max), save_every=save_every, gamma=gamma, alpha=alpha, a0=a0,
-              check_nan=check_nan, want_traj=want_traj)
-    if np.dtype(dtype) != np.dtype(np.float64):
-        kw["dtype"] = np.float32          # the float64 call stays as it was: no dtype argument
-    r = _run(_native.comb_host, COMB_AXES, N, kw, device, devices)
-    return CombResult(r["a_end"], r["p_wave_end"], r["p_wave_max"], r["first_bad_step"], n_steps, save_every, r["elapsed_ms"],
-                      np.abs(np.atleast_2d(a0)) ** 2, r.get("traj"))
+    def checked():
+        kp = _mismatch_columns(kappa, "kappa", "M", 3, _native.MAX_LINES)
+        return kp, int(kp.shape[1]), f" for {kp.shape[1]} lines"
+
+    return _sweep_waves(CombResult, _native.comb_host, COMB_AXES, "kappa", checked, z_max=z_max, dz=dz, n_steps=n_steps,
+                        save_every=save_every, a0=a0, dtype=dtype, device=device, devices=devices, gamma=gamma, alpha=alpha,
+                        check_nan=check_nan, want_traj=want_traj)
 
 
 # ---- chains of fibre spans ------------------------------------------------------------------------------------------

@@ -44,6 +44,14 @@ WAVES = dict(p_wave_end=P, p_wave_max=P)
 SP_CHAIN = dict(n_points=8, n_segments=2, n_steps=_STEPS, seg_len=_LENS, save_every=5, dbeta=P, gamma=P, alpha=P, a0=P,
                 transfer=None, flags=0, a_end=P, p_wave_end=P, p_wave_max=P, first_bad=P, traj=None)
 BCAST_ALL, CHECKS, LOSSLESS = 0b1111, 3 << 8, 1 << 14
+# the three wave-summary families: the single-pump and multi-line sweeps, and the multi-channel and multi-line chains
+SINGLE_PUMP = dict(n_points=8, n_steps=10, z_max=1.0, save_every=1, dbeta=P, gamma=P, alpha=P, a0=P, flags=0, a_end=P,
+                   p_wave_end=P, p_wave_max=P, first_bad=P, traj=None)
+COMB = dict(n_lines=5, **{("kappa" if k == "dbeta" else k): v for k, v in SINGLE_PUMP.items()})
+PAIRS_CHAIN = dict(n_pairs=3, **SP_CHAIN)
+COMB_CHAIN = dict(n_lines=5, **{("kappa" if k == "dbeta" else k): v for k, v in SP_CHAIN.items()})
+REFUSED_BITS = (("one_lane", ONE_LANE), ("split", SPLIT), ("quad", QUAD), ("f32_scalar", F32_SCALAR), ("f32_packed", F32_PACKED),
+                ("lds", LDS), ("bit19", 1 << 19), ("bit30", 1 << 30))
 
 
 def _entry(base, *, dev, tail=None, dev_tail=None):
@@ -177,6 +185,76 @@ def _pairs_cases():
     return c
 
 
+def _wave_family_cases(base, dev, count=None):
+    """One call per rule of a wave-summary family's validator, in its order: the single-pump and multi-line sweeps, and the
+    multi-channel and multi-line chains (``base`` with n_segments).  count: (argument, below, above) of n_pairs / n_lines."""
+    arr = lambda a, dt: np.array(a, dt)  # noqa: E731
+    chain, pairs = "n_segments" in base, "n_pairs" in base
+    steps, lens = (lambda *a: dict(n_steps=arr(a, np.int64))), (lambda *a: dict(seg_len=arr(a, float)))
+    mismatch = "kappa" if "kappa" in base else "dbeta"
+    null = {mismatch: None} if dev else dict(p_wave_max=None)
+    ok = (BCAST_ALL if chain else 0b0111) | CHECKS | LOSSLESS | BLOCK64
+    c = {}
+    if chain:
+        c.update({"n_segments_zero": dict(n_segments=0), "n_segments_negative": dict(n_segments=-1), "null_n_steps": dict(n_steps=None),
+                  "null_seg_len": dict(seg_len=None)})
+    if count:
+        name, low, high = count
+        c.update({f"{name}_{low}": {name: low}, f"{name}_{high}": {name: high}})
+    c["n_points_negative"] = dict(n_points=-1)
+    if pairs:
+        c.update({"launch_limit_2_lanes": dict(n_pairs=1, n_points=MAX_POINTS + 1), "launch_limit_4_lanes": dict(n_points=MAX_POINTS // 2 + 1),
+                  "launch_limit_16_lanes": dict(n_pairs=16, n_points=2**31)})
+    else:
+        c["n_points_launch_limit"] = dict(n_points=MAX_POINTS + 1)
+    if chain:
+        c.update({"first_span_n_steps_zero": steps(0, 20), "first_span_n_steps_2^31": steps(5 * 2**29, 20),
+                  "second_span_n_steps_zero": steps(10, 0), "second_span_n_steps_2^31": steps(10, 5 * 2**29)})
+        for name, bad in (("zero", 0.0), ("negative", -1.0), ("inf", INF), ("nan", NAN)):
+            c[f"first_span_seg_len_{name}"], c[f"second_span_seg_len_{name}"] = lens(bad, 2.0), lens(1.0, bad)
+    else:
+        c.update({"n_steps_zero": dict(n_steps=0), "n_steps_2^31": dict(n_steps=2**31), "z_max_zero": dict(z_max=0.0),
+                  "z_max_negative": dict(z_max=-1.0), "z_max_nan": dict(z_max=NAN), "z_max_inf": dict(z_max=INF)})
+    c["save_every_zero"] = dict(save_every=0)
+    for name, bit in REFUSED_BITS:
+        c[f"flag_{name}"] = dict(flags=bit | CHECK_NAN)
+    if not chain:   # the chain's own bit
+        c["flag_bcast_transfer"] = dict(flags=1 << 3)
+    if dev:         # accepted: the call fails at a later rule
+        c.update({"dev_traj_ld_then_null": dict(null, flags=TRAJ_LD), "dev_traj_ld_with_traj_then_null": dict(null, flags=TRAJ_LD, traj=P)})
+    else:           # the padded leading dimension belongs to the device form
+        c.update({"host_traj_ld": dict(flags=TRAJ_LD), "host_traj_ld_with_traj": dict(flags=TRAJ_LD, traj=P)})
+    c["every_accepted_flag"] = dict(null, flags=ok | (TRAJ_LD if dev else 0))
+    c.update(_nulls([k for k, v in base.items() if v is P]))
+    # the row bound: refused at 2^28 points with rows, not one point below it, and not without rows
+    c["traj_launch_limit"] = dict(n_points=2**28, traj=P)
+    if dev:
+        c["traj_launch_limit_padded"] = dict(n_points=2**28, traj=P, flags=TRAJ_LD)
+    later = steps(10, 21) if chain else null   # a chain has rules after the row bound; a sweep is stopped in front of it
+    c.update({"traj_below_the_limit": dict(later, n_points=2**28 - 1, traj=P), "no_traj_at_the_limit": dict(later, n_points=2**28)})
+    if chain:
+        c.update({"first_span_not_a_multiple": steps(11, 20), "second_span_not_a_multiple": steps(10, 21),
+                  "two:n_segments_zero+n_points_negative": dict(n_segments=0, n_points=-1),
+                  "two:null+not_a_multiple": dict(null, **steps(10, 21)),
+                  "two:traj_launch_limit+not_a_multiple": dict(n_points=2**28, traj=P, **steps(10, 21))})
+        if not pairs:   # one span of the multi-channel chain is the sweep's trajectory form, which may end behind its last row
+            c["one_span_not_a_multiple"] = dict(n_segments=1, **steps(11, 20))
+        if dev:   # rejected after validation and before the first launch
+            c.update({"two_spans_without_workspace": dict(d_workspace=None), "empty_without_workspace": dict(n_points=0, d_workspace=None)})
+    if count:
+        name, low, _ = count
+        c[f"two:{name}+n_points_negative"] = {name: low, "n_points": -1}
+        c[f"two:{name}+flag+null"] = dict(null, flags=ONE_LANE, **{name: low})
+        if chain:
+            c[f"two:null_n_steps+{name}"] = {"n_steps": None, name: low}
+    c.update({"two:n_points_negative+save_every_zero": dict(n_points=-1, save_every=0),
+              "two:save_every_zero+flag": dict(save_every=0, flags=ONE_LANE), "two:flag+null": dict(flags=ONE_LANE, **null),
+              "two:null+traj_launch_limit": dict(null, n_points=2**28, traj=P),
+              "empty": _empty(base), "empty_with_traj": dict(_empty(base), traj=P),
+              "empty_with_refused_flag": dict(_empty(base), flags=ONE_LANE)})
+    return c
+
+
 def cases() -> dict:
     """{symbol: (default arguments in call order, {case: overrides})} for every sweep-family entry point, both faces."""
     out = {}
@@ -194,6 +272,14 @@ def cases() -> dict:
         out[f"psa_rk4_sweep_pairs_f64{sfx}"] = (_entry(PAIRS, dev=dev), _pairs_cases())
         out[f"psa_rk4_single_pump_chain_f64{sfx}"] = (_entry(SP_CHAIN, dev=dev, dev_tail=dict(d_workspace=P)),
                                                       _single_pump_chain_cases(dev))
+        ws = dict(d_workspace=P)
+        out[f"psa_rk4_pairs_chain_f64{sfx}"] = (_entry(PAIRS_CHAIN, dev=dev, dev_tail=ws),
+                                                _wave_family_cases(PAIRS_CHAIN, dev, ("n_pairs", 0, 17)))
+        out[f"psa_rk4_comb_chain_f64{sfx}"] = (_entry(COMB_CHAIN, dev=dev, dev_tail=ws),
+                                               _wave_family_cases(COMB_CHAIN, dev, ("n_lines", 2, 13)))
+        for t in ("f64", "f32"):   # both precisions share one validator and one row bound: "below 2^28 points"
+            out[f"psa_rk4_single_pump_{t}{sfx}"] = (_entry(SINGLE_PUMP, dev=dev), _wave_family_cases(SINGLE_PUMP, dev))
+            out[f"psa_rk4_comb_{t}{sfx}"] = (_entry(COMB, dev=dev), _wave_family_cases(COMB, dev, ("n_lines", 2, 13)))
     return out
 
 
