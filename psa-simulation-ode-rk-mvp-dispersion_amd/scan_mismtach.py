@@ -49,6 +49,7 @@ from .simulation import _prepare, make_initial_amplitudes
 from .sweep import SweepResult, check_gain, rk4_sweep
 
 GainMode = Literal["end", "max"]
+_PROVIDED = PhaseMatchingConfig(method=PhaseMatchingMethod.PROVIDED, provided_delta_beta=0.0)
 
 
 def _select_power_metric(Pz: np.ndarray, mode: GainMode) -> float:
@@ -648,6 +649,32 @@ def scan_six_wave_grid(*, cfg: SimulationConfig, lambda_p1_m: float, lambda_p2_m
                 a_end=res.a_end.reshape(shape + (6,)), first_bad_step=res.first_bad_step.reshape(shape), result=res)
 
 
+def _wdm_channels(Omega, p_pump):
+    """The channels and the pumps of a multi-channel scan -> (Omega (K,), K, p_pump (2,))."""
+    Om = np.asarray(list(Omega), dtype=float)
+    if Om.ndim != 1 or not 1 <= Om.size <= 16 or not np.all(np.isfinite(Om)):
+        raise ValueError("Omega must be a 1D sequence of 1..16 finite detunings (rad/s)")
+    pp = np.asarray(list(p_pump), dtype=float)
+    if pp.shape != (2,) or not np.all(np.isfinite(pp)) or np.any(pp < 0.0):
+        raise ValueError("p_pump must hold two finite non-negative powers [p1, p2]")
+    return Om, int(Om.size), pp
+
+
+def _wdm_plan(Om, lambda_p1_m, lambda_p2_m, dispersion, pp, ps, pi):
+    """The frequency plan of a multi-channel scan, once its powers stand -> (omega_d, the powers [p1, p2, s_1, i_1, ...] of
+    ps's leading shape): a dispersion, the pumps at omega_c +- omega_d, every sideband omega_c +- Omega_k positive."""
+    from .frequency_plan import omega_from_lambda
+    if dispersion is None:
+        raise ValueError("dispersion must be provided")
+    w1, w2 = omega_from_lambda(lambda_p1_m), omega_from_lambda(lambda_p2_m)
+    wc, wd = 0.5 * (w1 + w2), 0.5 * (w1 - w2)
+    if np.any(np.abs(Om) >= wc):
+        raise ValueError("|Omega| must stay below omega_c (sideband frequencies must be positive)")
+    p_all = np.empty(ps.shape[:-1] + (2 + 2 * Om.size,))
+    p_all[..., :2], p_all[..., 2::2], p_all[..., 3::2] = pp, ps, np.broadcast_to(pi, ps.shape)
+    return wd, p_all
+
+
 def scan_wdm_gain(*, cfg: SimulationConfig, lambda_p1_m: float, lambda_p2_m: float, Omega: Sequence[float],
                   p_pump: Sequence[float], p_signal, p_idler=0.0, phase_in: Optional[Sequence[float]] = None, gamma: float,
                   alpha: float, dispersion: DispersionParams, even_orders: Tuple[int, ...] = (2, 4), length_unit: str = "m",
@@ -666,16 +693,9 @@ def scan_wdm_gain(*, cfg: SimulationConfig, lambda_p1_m: float, lambda_p2_m: flo
 
     Returns dict(gain (N, K) of every signal over its seed, idler (N, K) every idler's power over its signal's seed,
     pump_depletion (N,), dbeta (K,) in 1/length_unit, first_bad_step (N,), result=PairsResult)."""
-    from .frequency_plan import omega_from_lambda
     from .sweep import initial_amplitudes, rk4_sweep_pairs
     unit = check_gain(gain_mode, gain_unit)
-    Om = np.asarray(list(Omega), dtype=float)
-    if Om.ndim != 1 or not 1 <= Om.size <= 16 or not np.all(np.isfinite(Om)):
-        raise ValueError("Omega must be a 1D sequence of 1..16 finite detunings (rad/s)")
-    K = int(Om.size)
-    pp = np.asarray(list(p_pump), dtype=float)
-    if pp.shape != (2,) or not np.all(np.isfinite(pp)) or np.any(pp < 0.0):
-        raise ValueError("p_pump must hold two finite non-negative powers [p1, p2]")
+    Om, K, pp = _wdm_channels(Omega, p_pump)
     ps = np.asarray(p_signal, dtype=float)
     if ps.ndim not in (1, 2) or ps.shape[-1] != K or ps.size == 0:
         raise ValueError(f"p_signal must have shape ({K},) or (N, {K})")
@@ -689,20 +709,11 @@ def scan_wdm_gain(*, cfg: SimulationConfig, lambda_p1_m: float, lambda_p2_m: flo
     ph = None if phase_in is None else np.asarray(list(phase_in), dtype=float)
     if ph is not None and (ph.shape != (2 + 2 * K,) or not np.all(np.isfinite(ph))):
         raise ValueError(f"phase_in must hold {2 + 2 * K} finite phases")
-    if dispersion is None:
-        raise ValueError("dispersion must be provided")
-    w1, w2 = omega_from_lambda(lambda_p1_m), omega_from_lambda(lambda_p2_m)
-    wc, wd = 0.5 * (w1 + w2), 0.5 * (w1 - w2)
-    if np.any(np.abs(Om) >= wc):
-        raise ValueError("|Omega| must stay below omega_c (sideband frequencies must be positive)")
+    wd, p_all = _wdm_plan(Om, lambda_p1_m, lambda_p2_m, dispersion, pp, ps, pi)
     pre = _prepare(cfg, gamma=gamma, alpha=alpha, dispersion=dispersion, phase_matching_cfg=None, beta_legacy=None,
                    length_unit=length_unit)
     fiber, grid = pre["fiber"], pre["grid"]
     db = delta_beta_symmetric_array(wd, Om, fiber.dispersion, even_orders=even_orders)      # per metre
-    p_all = np.empty((N, 2 + 2 * K))
-    p_all[:, :2] = pp
-    p_all[:, 2::2] = ps
-    p_all[:, 3::2] = np.broadcast_to(pi, (N, K))
     res = rk4_sweep_pairs(np.broadcast_to(db, (N, K)), z_max=fiber.length_m, n_steps=n_steps_of(fiber.length_m, grid.dz_m),
                           save_every=cfg.save_every, check_nan=bool(cfg.check_nan), gamma=fiber.gamma_W_m,
                           alpha=fiber.alpha_1_m, a0=initial_amplitudes(p_all, ph), device=(0 if device is None else int(device)),
@@ -727,8 +738,8 @@ def scan_single_pump_gain(*, cfg: SimulationConfig, lambda_pump_m: float, lambda
 
     Returns dict(gain (n,) of the signal over p_signal, idler (n,) the idler's power over p_signal, pump_depletion (n,),
     dbeta (n,) in 1/length_unit, first_bad_step (n,), result=SinglePumpResult)."""
-    from .dispersion import delta_beta_from_omegas_array
     from .frequency_plan import omega_from_lambda, omega_from_lambda_array
+    from .simulation import _single_pump_mismatch
     from .sweep import initial_amplitudes, rk4_sweep_single_pump
     unit = check_gain(gain_mode, gain_unit)
     lam = np.asarray(lambda_signal_m, dtype=float)
@@ -750,14 +761,12 @@ def scan_single_pump_gain(*, cfg: SimulationConfig, lambda_pump_m: float, lambda
     pre = _prepare(cfg, gamma=gamma, alpha=alpha, dispersion=dispersion, phase_matching_cfg=None, beta_legacy=None,
                    length_unit=length_unit)
     fiber, grid = pre["fiber"], pre["grid"]
-    n = int(lam.size)
     with np.errstate(all="ignore"):
         ok = np.isfinite(lam) & (lam > 0.0)
         ws = omega_from_lambda_array(np.where(ok, lam, 1.0))
         wi = 2.0 * wp - ws
         ok &= np.isfinite(ws) & (wi > 0.0)
-        om = np.stack([np.full(n, wp), np.full(n, wp), np.where(ok, ws, wp), np.where(ok, wi, wp)], axis=-1)
-        db = delta_beta_from_omegas_array(om, fiber.dispersion, max_order=max_order)      # per metre
+        db = _single_pump_mismatch(wp, np.where(ok, ws, wp), np.where(ok, wi, wp), fiber.dispersion, max_order)   # per metre
         ok &= np.isfinite(db)
     res = rk4_sweep_single_pump(np.where(ok, db, 0.0), z_max=fiber.length_m, n_steps=n_steps_of(fiber.length_m, grid.dz_m),
                                 save_every=cfg.save_every, check_nan=bool(cfg.check_nan), gamma=fiber.gamma_W_m,
@@ -790,14 +799,13 @@ def scan_comb_gain(*, cfg: SimulationConfig, lambda_center_m: float, line_spacin
     Returns dict(gain (N, M) of every line over its input power -- NaN for a line with zero input --, p_end, p_max (N, M),
     kappa (M,) in 1/length_unit, omega (M,), first_bad_step (N,), result=CombResult)."""
     from .frequency_plan import omega_from_lambda
-    from .simulation import _comb_phases, _comb_powers, comb_lines
-    from .sweep import initial_amplitudes, rk4_sweep_comb
+    from .simulation import _comb_input, comb_lines
+    from .sweep import rk4_sweep_comb
     unit = check_gain(gain_mode, gain_unit)
     if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
         raise ValueError(f"dtype must be float64 or float32, got {np.dtype(dtype)}")
-    p = np.atleast_2d(_comb_powers(p_lines, "p_lines"))
+    p, a0 = _comb_input(p_lines, "p_lines", phase_in, points=True)
     N, M = (int(x) for x in p.shape)
-    ph = _comb_phases(phase_in, M)
     if dispersion is None:
         raise ValueError("dispersion must be provided")
     pre = _prepare(cfg, gamma=gamma, alpha=alpha, dispersion=dispersion, phase_matching_cfg=None, beta_legacy=None,
@@ -806,14 +814,13 @@ def scan_comb_gain(*, cfg: SimulationConfig, lambda_center_m: float, line_spacin
     omega, kappa, _ = comb_lines(omega_from_lambda(lambda_center_m), line_spacing, M, fiber.dispersion, max_order=max_order)
     res = rk4_sweep_comb(np.broadcast_to(kappa, (N, M)), z_max=fiber.length_m, n_steps=n_steps_of(fiber.length_m, grid.dz_m),
                          save_every=cfg.save_every, check_nan=bool(cfg.check_nan), gamma=fiber.gamma_W_m, alpha=fiber.alpha_1_m,
-                         a0=initial_amplitudes(p, ph), device=(0 if device is None else int(device)), devices=devices,
-                         dtype=dtype)
+                         a0=a0, device=(0 if device is None else int(device)), devices=devices, dtype=dtype)
     return dict(gain=res.line_gain(p, mode=gain_mode, unit=unit), p_end=res.p_wave_end, p_max=res.p_wave_max,
                 kappa=kappa * pre["scale"], omega=omega, first_bad_step=res.first_bad_step, result=res)
 
 
 def _phase_scan_axes(phase, psa_delta_beta):
-    """The rules both copier - PSA scans share for their two axes -> (phase (K,), psa_delta_beta () or (M,))."""
+    """The rules the copier - PSA scans share for their axes -> (phase (K,), psa_delta_beta () or (M,))."""
     ph = np.linspace(0.0, 2.0 * np.pi, 32, endpoint=False) if phase is None else np.asarray(phase, dtype=float)
     if ph.ndim != 1 or ph.size == 0 or not np.all(np.isfinite(ph)):
         raise ValueError("phase must be a non-empty 1D sequence of finite values")
@@ -823,41 +830,60 @@ def _phase_scan_axes(phase, psa_delta_beta):
     return ph, dbp
 
 
-def _copier_psa_chain(ph, dbp, mask, transfer_of, a_in, *, psa_cfg, copier_cfg, gamma, alpha, copier_delta_beta, copier_gamma,
-                      copier_alpha, length_unit):
-    """The K x M chains of a copier - PSA scan, point k * M + m -> (spans, transfers, a0) for the family's chain driver.
-    ``mask``: the waves that take the scanned phase; ``transfer_of``: the family's mid-stage on (K, n_waves) scanned phases;
-    ``a_in``: the input amplitudes (n_waves,)."""
+def _copier_psa_link(chain, transfer_of, a_in, gain_db_of, *, psa_cfg, copier_cfg, gamma, alpha, copier_gamma, copier_alpha,
+                     psa_x, copier_x, length_unit, device, devices, mismatch_of=None, **chain_kw):
+    """The copier - mid-stage - PSA link under the four scan_*_copier_psa_phase functions -> (the chain's result, what
+    ``mismatch_of`` kept of every span, gain_db, its extremes as the scans return them).
+
+    The spans are the PSA's (psa_cfg, gamma, alpha, psa_x) and, with a copier_cfg, the copier's in front, whose gamma and alpha
+    default to the PSA's; the two configs share save_every and check_nan.  ``mismatch_of(x, prepared)`` -> (the span's
+    per-metre mismatch as FibreSpan takes it, something to keep) forms it from the span's dispersion x, scaled by _prepare.
+    Without it x is the mismatch itself in 1/length_unit, psa_x per point and copier_x a scalar (the 4-wave and single-pump
+    scans): a span is then prepared without gamma, alpha or a dispersion, so none of FiberParams' rules applies to them, and
+    the configs are compared after the spans are prepared, not before -- the order those two scans always had.
+    ``transfer_of()`` is the mid-stage (points, n_waves) with the scanned phase in it; without a copier it acts on the input
+    ``a_in``.  One call of ``chain`` (the family's rk4_chain_*), then ``gain_db_of(result)``: (points,) has its extremes taken
+    over all points, as floats, (points, columns) per column; NaN where no gain is finite."""
     from .sweep import FibreSpan
-    provided = PhaseMatchingConfig(method=PhaseMatchingMethod.PROVIDED, provided_delta_beta=0.0)
-    cfgs = [psa_cfg] if copier_cfg is None else [copier_cfg, psa_cfg]
-    pres = [_prepare(c, gamma=0.0, alpha=0.0, dispersion=None, phase_matching_cfg=provided, beta_legacy=None,
-                     length_unit=length_unit) for c in cfgs]
-    if any(int(c.save_every) != int(psa_cfg.save_every) or bool(c.check_nan) != bool(psa_cfg.check_nan) for c in cfgs):
-        raise ValueError("copier_cfg and psa_cfg must share save_every and check_nan")
-    scale = pres[0]["scale"]
-    K, M = ph.size, max(dbp.size, 1)
-    db_pts = np.tile(np.atleast_1d(dbp), K) / scale
-    T = np.repeat(transfer_of(ph[:, None] * mask[None, :]), M, axis=0)           # (K * M, n_waves)
-    psa = FibreSpan(pres[-1]["fiber"].length_m, dz=pres[-1]["grid"].dz_m, dbeta=db_pts, gamma=float(gamma) / scale,
-                    alpha=float(alpha) / scale)
-    if copier_cfg is None:
-        return [psa], None, T * a_in[None, :]
-    cg = gamma if copier_gamma is None else copier_gamma
-    ca = alpha if copier_alpha is None else copier_alpha
-    copier = FibreSpan(pres[0]["fiber"].length_m, dz=pres[0]["grid"].dz_m, dbeta=float(copier_delta_beta) / scale,
-                       gamma=float(cg) / scale, alpha=float(ca) / scale)
-    return [copier, psa], [T], a_in
+    provided = mismatch_of is None
+    fibres = [(psa_cfg, gamma, alpha, psa_x)]
+    if copier_cfg is not None:
+        fibres.insert(0, (copier_cfg, gamma if copier_gamma is None else copier_gamma,
+                          alpha if copier_alpha is None else copier_alpha, copier_x))
 
+    def shared():
+        if any(int(c.save_every) != int(psa_cfg.save_every) or bool(c.check_nan) != bool(psa_cfg.check_nan) for c, *_ in fibres):
+            raise ValueError("copier_cfg and psa_cfg must share save_every and check_nan")
 
-def _phase_scan_result(ph, dbp, gain_db, res, **gains) -> dict:
-    """The scans' returned dict: the axes, ``gains`` as (K,) or (K, M), the extremes of the finite ``gain_db`` and their
-    distance, the chain's result."""
-    finite = np.isfinite(gain_db)
-    gmax = float(np.max(gain_db[finite])) if finite.any() else float("nan")
-    gmin = float(np.min(gain_db[finite])) if finite.any() else float("nan")
-    return dict(phase=ph, psa_delta_beta=dbp, **{k: np.asarray(g).reshape((ph.size,) + dbp.shape) for k, g in gains.items()},
-                gain_max_db=gmax, gain_min_db=gmin, extinction_db=gmax - gmin, result=res)
+    if not provided:
+        shared()
+    pres, mismatches, kept = [], [], []
+    for cfg, g, a, x in fibres:
+        if provided:
+            pre = _prepare(cfg, gamma=0.0, alpha=0.0, dispersion=None, phase_matching_cfg=_PROVIDED, beta_legacy=None,
+                           length_unit=length_unit)
+            m, keep = (x if x is psa_x else float(x)) / pre["scale"], None
+        else:
+            pre = _prepare(cfg, gamma=g, alpha=a, dispersion=x, phase_matching_cfg=None, beta_legacy=None, length_unit=length_unit)
+            m, keep = mismatch_of(x, pre)
+        pres.append(pre), mismatches.append(m), kept.append(keep)
+    if provided:
+        shared()
+    T = transfer_of()
+    spans = [FibreSpan(pre["fiber"].length_m, dz=pre["grid"].dz_m, dbeta=m, gamma=float(g) / pre["scale"],
+                       alpha=float(a) / pre["scale"]) for (_, g, a, _), pre, m in zip(fibres, pres, mismatches)]
+    a0, transfers = (T * a_in[None, :], None) if copier_cfg is None else (a_in, [T])
+    res = chain(spans, a0=a0, transfers=transfers, save_every=int(psa_cfg.save_every), check_nan=bool(psa_cfg.check_nan),
+                device=(0 if device is None else int(device)), devices=devices, **chain_kw)
+    gain_db = gain_db_of(res)
+    with np.errstate(all="ignore"):
+        finite = np.isfinite(gain_db)
+        some = finite.any(axis=0)
+        gmax = np.where(some, np.max(np.where(finite, gain_db, -np.inf), axis=0), np.nan)
+        gmin = np.where(some, np.min(np.where(finite, gain_db, np.inf), axis=0), np.nan)
+    if gain_db.ndim == 1:
+        gmax, gmin = float(gmax), float(gmin)
+    return res, kept, gain_db, dict(gain_max_db=gmax, gain_min_db=gmin, extinction_db=gmax - gmin)
 
 
 def scan_copier_psa_phase(*, psa_cfg: SimulationConfig, psa_delta_beta, gamma: float, alpha: float, p_in: Sequence[float],
@@ -892,16 +918,20 @@ def scan_copier_psa_phase(*, psa_cfg: SimulationConfig, psa_delta_beta, gamma: f
     else:
         raise ValueError("phase_wave must be 'pumps' or a wave index 0..3")
     _, p0, ph0 = _check_sweep_inputs([1.0], p_in, phase_in)
-    spans, transfers, a0 = _copier_psa_chain(
-        ph, dbp, mask, lambda scanned: mid_stage(np.broadcast_to(np.asarray(mid_gain_db, dtype=float), (4,)),
-                                                 np.asarray(mid_phase, dtype=float)[None, :] + scanned),
-        make_initial_amplitudes(p0, ph0), psa_cfg=psa_cfg, copier_cfg=copier_cfg, gamma=gamma, alpha=alpha,
-        copier_delta_beta=copier_delta_beta, copier_gamma=copier_gamma, copier_alpha=copier_alpha, length_unit=length_unit)
-    dev = 0 if device is None else int(device)
-    res = rk4_chain(spans, a0=a0, transfers=transfers, save_every=int(psa_cfg.save_every),
-                    check_nan=bool(psa_cfg.check_nan), dtype=dtype, device=dev, devices=devices)
-    gain_db = res.gain(p0[2], mode=gain_mode, unit="dB", device=(dev if not devices else int(devices[0])))
-    return _phase_scan_result(ph, dbp, gain_db, res, gain=gain_db if unit == "db" else 10.0 ** (gain_db / 10.0))
+    M = max(dbp.size, 1)                  # point k * M + m: phase k, mismatch m
+    res, _, gain_db, extremes = _copier_psa_link(
+        rk4_chain,
+        lambda: np.repeat(mid_stage(np.broadcast_to(np.asarray(mid_gain_db, dtype=float), (4,)),
+                                    np.asarray(mid_phase, dtype=float)[None, :] + ph[:, None] * mask[None, :]), M, axis=0),
+        make_initial_amplitudes(p0, ph0),
+        lambda r: r.gain(p0[2], mode=gain_mode, unit="dB",
+                         device=(int(devices[0]) if devices else 0 if device is None else int(device))),
+        psa_cfg=psa_cfg, copier_cfg=copier_cfg, gamma=gamma, alpha=alpha, copier_gamma=copier_gamma, copier_alpha=copier_alpha,
+        psa_x=np.tile(np.atleast_1d(dbp), ph.size), copier_x=copier_delta_beta, length_unit=length_unit, device=device,
+        devices=devices, dtype=dtype)
+    shape = (ph.size,) + dbp.shape
+    return dict(phase=ph, psa_delta_beta=dbp, gain=(gain_db if unit == "db" else 10.0 ** (gain_db / 10.0)).reshape(shape),
+                **extremes, result=res)
 
 
 def scan_single_pump_copier_psa_phase(*, psa_cfg: SimulationConfig, psa_delta_beta, gamma: float, alpha: float,
@@ -946,18 +976,20 @@ def scan_single_pump_copier_psa_phase(*, psa_cfg: SimulationConfig, psa_delta_be
     ph0 = None if phase_in is None else np.asarray(list(phase_in), dtype=float)
     if ph0 is not None and (ph0.shape != (3,) or not np.all(np.isfinite(ph0))):
         raise ValueError("phase_in must hold 3 finite phases")
-    spans, transfers, a0 = _copier_psa_chain(
-        ph, dbp, mask, lambda scanned: single_pump_mid_stage(np.broadcast_to(np.asarray(mid_gain_db, dtype=float), (3,)),
-                                                             np.broadcast_to(np.asarray(mid_phase, dtype=float), (3,))[None, :]
-                                                             + scanned),
-        initial_amplitudes(p0, ph0), psa_cfg=psa_cfg, copier_cfg=copier_cfg, gamma=gamma, alpha=alpha,
-        copier_delta_beta=copier_delta_beta, copier_gamma=copier_gamma, copier_alpha=copier_alpha, length_unit=length_unit)
-    res = rk4_chain_single_pump(spans, a0=a0, transfers=transfers, save_every=int(psa_cfg.save_every),
-                                check_nan=bool(psa_cfg.check_nan), device=(0 if device is None else int(device)),
-                                devices=devices)
-    return _phase_scan_result(ph, dbp, res.signal_gain(p0[1], mode=gain_mode, unit="dB"), res,
-                              gain=res.signal_gain(p0[1], mode=gain_mode, unit=unit),
-                              gain_idler=res.idler_conversion(p0[1], mode=gain_mode, unit=unit))
+    M = max(dbp.size, 1)                  # point k * M + m: phase k, mismatch m
+    res, _, _, extremes = _copier_psa_link(
+        rk4_chain_single_pump,
+        lambda: np.repeat(single_pump_mid_stage(np.broadcast_to(np.asarray(mid_gain_db, dtype=float), (3,)),
+                                                np.broadcast_to(np.asarray(mid_phase, dtype=float), (3,))[None, :]
+                                                + ph[:, None] * mask[None, :]), M, axis=0),
+        initial_amplitudes(p0, ph0), lambda r: r.signal_gain(p0[1], mode=gain_mode, unit="dB"),
+        psa_cfg=psa_cfg, copier_cfg=copier_cfg, gamma=gamma, alpha=alpha, copier_gamma=copier_gamma, copier_alpha=copier_alpha,
+        psa_x=np.tile(np.atleast_1d(dbp), ph.size), copier_x=copier_delta_beta, length_unit=length_unit, device=device,
+        devices=devices)
+    shape = (ph.size,) + dbp.shape
+    return dict(phase=ph, psa_delta_beta=dbp, gain=np.asarray(res.signal_gain(p0[1], mode=gain_mode, unit=unit)).reshape(shape),
+                gain_idler=np.asarray(res.idler_conversion(p0[1], mode=gain_mode, unit=unit)).reshape(shape), **extremes,
+                result=res)
 
 
 def scan_wdm_copier_psa_phase(*, psa_cfg: SimulationConfig, copier_cfg: Optional[SimulationConfig] = None, lambda_p1_m: float,
@@ -987,19 +1019,12 @@ def scan_wdm_copier_psa_phase(*, psa_cfg: SimulationConfig, copier_cfg: Optional
     Returns dict(phase (F,), gain (F, K) of every signal over its seed, idler (F, K) every idler's power over its signal's
     seed, gain_max_db, gain_min_db, extinction_db (K,): per channel over the finite gains, dbeta (S, K) in 1/length_unit,
     first_bad_step (F,), result=PairsChainResult)."""
-    from .frequency_plan import omega_from_lambda
     from .simulation import wdm_mid_stage
-    from .sweep import FibreSpan, initial_amplitudes, rk4_chain_pairs
+    from .sweep import initial_amplitudes, rk4_chain_pairs
     unit = check_gain(gain_mode, gain_unit)
     ph, _ = _phase_scan_axes(phase, 0.0)
-    Om = np.asarray(list(Omega), dtype=float)
-    if Om.ndim != 1 or not 1 <= Om.size <= 16 or not np.all(np.isfinite(Om)):
-        raise ValueError("Omega must be a 1D sequence of 1..16 finite detunings (rad/s)")
-    K = int(Om.size)
+    Om, K, pp = _wdm_channels(Omega, p_pump)
     nw = 2 + 2 * K
-    pp = np.asarray(list(p_pump), dtype=float)
-    if pp.shape != (2,) or not np.all(np.isfinite(pp)) or np.any(pp < 0.0):
-        raise ValueError("p_pump must hold two finite non-negative powers [p1, p2]")
     ps = np.asarray(p_signal, dtype=float)
     if ps.shape != (K,) or not np.all(np.isfinite(ps)) or np.any(ps <= 0.0):
         raise ValueError(f"p_signal (the seed powers) must have shape ({K},), finite and > 0 to define gain")
@@ -1014,43 +1039,22 @@ def scan_wdm_copier_psa_phase(*, psa_cfg: SimulationConfig, copier_cfg: Optional
     mg, mp = np.asarray(mid_gain_db, dtype=float), np.asarray(mid_phase, dtype=float)
     if mg.shape not in ((), (nw,)) or mp.shape not in ((), (nw,)):
         raise ValueError(f"mid_gain_db and mid_phase must be a scalar or hold {nw} values")
-    if dispersion is None:
-        raise ValueError("dispersion must be provided")
-    w1, w2 = omega_from_lambda(lambda_p1_m), omega_from_lambda(lambda_p2_m)
-    wc, wd = 0.5 * (w1 + w2), 0.5 * (w1 - w2)
-    if np.any(np.abs(Om) >= wc):
-        raise ValueError("|Omega| must stay below omega_c (sideband frequencies must be positive)")
-    fibres = [(psa_cfg, gamma, alpha, dispersion)]
-    if copier_cfg is not None:
-        fibres.insert(0, (copier_cfg, gamma if copier_gamma is None else copier_gamma,
-                          alpha if copier_alpha is None else copier_alpha,
-                          dispersion if copier_dispersion is None else copier_dispersion))
-        if int(copier_cfg.save_every) != int(psa_cfg.save_every) or bool(copier_cfg.check_nan) != bool(psa_cfg.check_nan):
-            raise ValueError("copier_cfg and psa_cfg must share save_every and check_nan")
-    spans, dbs = [], []
-    for cfg, g, a, d in fibres:
-        pre = _prepare(cfg, gamma=g, alpha=a, dispersion=d, phase_matching_cfg=None, beta_legacy=None, length_unit=length_unit)
-        fiber = pre["fiber"]
-        db = delta_beta_symmetric_array(wd, Om, fiber.dispersion, even_orders=even_orders)      # per metre
-        dbs.append(db * pre["scale"])
-        # per point: the F phase points are the sweep points, and a chain takes its point count from the spans and a0
-        spans.append(FibreSpan(fiber.length_m, dz=pre["grid"].dz_m, dbeta=np.broadcast_to(db, (ph.size, K)), gamma=fiber.gamma_W_m,
-                               alpha=fiber.alpha_1_m))
-    p_all = np.empty(nw)
-    p_all[:2], p_all[2::2], p_all[3::2] = pp, ps, np.broadcast_to(pi, (K,))
-    a_in = initial_amplitudes(p_all)
-    T = wdm_mid_stage(np.broadcast_to(mg, (nw,)), np.broadcast_to(mp, (nw,))[None, :] + ph[:, None] * mask[None, :])   # (F, NW)
-    a0, transfers = (T * a_in[None, :], None) if copier_cfg is None else (a_in, [T])
-    res = rk4_chain_pairs(spans, a0=a0, transfers=transfers, save_every=int(psa_cfg.save_every),
-                          check_nan=bool(psa_cfg.check_nan), device=(0 if device is None else int(device)), devices=devices)
-    gain_db = res.channel_gain(ps, mode=gain_mode, unit="dB")
-    with np.errstate(all="ignore"):
-        some = np.isfinite(gain_db).any(axis=0)
-        gmax = np.where(some, np.max(np.where(np.isfinite(gain_db), gain_db, -np.inf), axis=0), np.nan)
-        gmin = np.where(some, np.min(np.where(np.isfinite(gain_db), gain_db, np.inf), axis=0), np.nan)
+    wd, p_all = _wdm_plan(Om, lambda_p1_m, lambda_p2_m, dispersion, pp, ps, pi)
+
+    def mismatch_of(d, pre):     # per point: the F phase points are the sweep points, and a chain counts them in the spans and a0
+        db = delta_beta_symmetric_array(wd, Om, pre["fiber"].dispersion, even_orders=even_orders)      # per metre
+        return np.broadcast_to(db, (ph.size, K)), db * pre["scale"]
+
+    res, dbs, gain_db, extremes = _copier_psa_link(
+        rk4_chain_pairs, lambda: wdm_mid_stage(np.broadcast_to(mg, (nw,)), np.broadcast_to(mp, (nw,))[None, :]
+                                               + ph[:, None] * mask[None, :]),       # (F, NW)
+        initial_amplitudes(p_all), lambda r: r.channel_gain(ps, mode=gain_mode, unit="dB"), mismatch_of=mismatch_of,
+        psa_cfg=psa_cfg, copier_cfg=copier_cfg, gamma=gamma, alpha=alpha, copier_gamma=copier_gamma, copier_alpha=copier_alpha,
+        psa_x=dispersion, copier_x=dispersion if copier_dispersion is None else copier_dispersion, length_unit=length_unit,
+        device=device, devices=devices)
     return dict(phase=ph, gain=gain_db if unit == "db" else res.channel_gain(ps, mode=gain_mode, unit=unit),
-                idler=res.idler_conversion(ps, mode=gain_mode, unit=unit), gain_max_db=gmax, gain_min_db=gmin,
-                extinction_db=gmax - gmin, dbeta=np.stack(dbs), first_bad_step=res.first_bad_step, result=res)
+                idler=res.idler_conversion(ps, mode=gain_mode, unit=unit), **extremes, dbeta=np.stack(dbs),
+                first_bad_step=res.first_bad_step, result=res)
 
 
 def scan_comb_copier_psa_phase(*, psa_cfg: SimulationConfig, copier_cfg: Optional[SimulationConfig] = None, lambda_center_m: float,
@@ -1080,15 +1084,12 @@ def scan_comb_copier_psa_phase(*, psa_cfg: SimulationConfig, copier_cfg: Optiona
     (M,): per line over the finite gains, kappa (S, M) in 1/length_unit, omega (M,), first_bad_step (F,),
     result=CombChainResult)."""
     from .frequency_plan import omega_from_lambda
-    from .simulation import _comb_phases, _comb_powers, comb_lines, comb_mid_stage
-    from .sweep import FibreSpan, initial_amplitudes, rk4_chain_comb
+    from .simulation import _comb_input, comb_lines, comb_mid_stage
+    from .sweep import rk4_chain_comb
     unit = check_gain(gain_mode, gain_unit)
     ph, _ = _phase_scan_axes(phase, 0.0)
-    p = _comb_powers(p_lines, "p_lines")
-    if p.ndim != 1:
-        raise ValueError(f"p_lines must have shape (M,), got {p.shape}")
+    p, a_in = _comb_input(p_lines, "p_lines", phase_in)
     M = int(p.shape[0])
-    ph0 = _comb_phases(phase_in, M)
     try:
         lines = list(phase_lines)
     except TypeError:
@@ -1104,32 +1105,17 @@ def scan_comb_copier_psa_phase(*, psa_cfg: SimulationConfig, copier_cfg: Optiona
     if dispersion is None:
         raise ValueError("dispersion must be provided")
     wc = omega_from_lambda(lambda_center_m)
-    fibres = [(psa_cfg, gamma, alpha, dispersion)]
-    if copier_cfg is not None:
-        fibres.insert(0, (copier_cfg, gamma if copier_gamma is None else copier_gamma,
-                          alpha if copier_alpha is None else copier_alpha,
-                          dispersion if copier_dispersion is None else copier_dispersion))
-        if int(copier_cfg.save_every) != int(psa_cfg.save_every) or bool(copier_cfg.check_nan) != bool(psa_cfg.check_nan):
-            raise ValueError("copier_cfg and psa_cfg must share save_every and check_nan")
-    spans, kappas, omega = [], [], None
-    for cfg, g, a, d in fibres:
-        pre = _prepare(cfg, gamma=g, alpha=a, dispersion=d, phase_matching_cfg=None, beta_legacy=None, length_unit=length_unit)
-        fiber = pre["fiber"]
-        omega, kappa, _ = comb_lines(wc, line_spacing, M, fiber.dispersion, max_order=max_order)      # per metre
-        kappas.append(kappa * pre["scale"])
-        # per point: the F phase points are the sweep points, and a chain takes its point count from the spans and a0
-        spans.append(FibreSpan(fiber.length_m, dz=pre["grid"].dz_m, dbeta=np.broadcast_to(kappa, (ph.size, M)), gamma=fiber.gamma_W_m,
-                               alpha=fiber.alpha_1_m))
-    a_in = initial_amplitudes(p, ph0)
-    T = comb_mid_stage(np.broadcast_to(mg, (M,)), np.broadcast_to(mp, (M,))[None, :] + ph[:, None] * mask[None, :])   # (F, M)
-    a0, transfers = (T * a_in[None, :], None) if copier_cfg is None else (a_in, [T])
-    res = rk4_chain_comb(spans, a0=a0, transfers=transfers, save_every=int(psa_cfg.save_every),
-                         check_nan=bool(psa_cfg.check_nan), device=(0 if device is None else int(device)), devices=devices)
-    gain_db = res.line_gain(p, mode=gain_mode, unit="dB")
-    with np.errstate(all="ignore"):
-        some = np.isfinite(gain_db).any(axis=0)
-        gmax = np.where(some, np.max(np.where(np.isfinite(gain_db), gain_db, -np.inf), axis=0), np.nan)
-        gmin = np.where(some, np.min(np.where(np.isfinite(gain_db), gain_db, np.inf), axis=0), np.nan)
+
+    def mismatch_of(d, pre):     # per point: the F phase points are the sweep points, and a chain counts them in the spans and a0
+        omega, kappa, _ = comb_lines(wc, line_spacing, M, pre["fiber"].dispersion, max_order=max_order)      # per metre
+        return np.broadcast_to(kappa, (ph.size, M)), (kappa * pre["scale"], omega)
+
+    res, kept, gain_db, extremes = _copier_psa_link(
+        rk4_chain_comb, lambda: comb_mid_stage(np.broadcast_to(mg, (M,)), np.broadcast_to(mp, (M,))[None, :]
+                                               + ph[:, None] * mask[None, :]),       # (F, M)
+        a_in, lambda r: r.line_gain(p, mode=gain_mode, unit="dB"), mismatch_of=mismatch_of,
+        psa_cfg=psa_cfg, copier_cfg=copier_cfg, gamma=gamma, alpha=alpha, copier_gamma=copier_gamma, copier_alpha=copier_alpha,
+        psa_x=dispersion, copier_x=dispersion if copier_dispersion is None else copier_dispersion, length_unit=length_unit,
+        device=device, devices=devices)
     return dict(phase=ph, gain=gain_db if unit == "db" else res.line_gain(p, mode=gain_mode, unit=unit), p_out=res.p_wave_end,
-                gain_max_db=gmax, gain_min_db=gmin, extinction_db=gmax - gmin, kappa=np.stack(kappas), omega=omega,
-                first_bad_step=res.first_bad_step, result=res)
+                **extremes, kappa=np.stack([k for k, _ in kept]), omega=kept[-1][1], first_bad_step=res.first_bad_step, result=res)

@@ -34,10 +34,10 @@ def _length_scale_to_m(length_unit: str) -> float:
         raise ValueError(f"Unsupported length_unit={length_unit!r}. Use 'm' or 'km'.") from None
 
 
-def _vec4(x, name: str, *, what: str, lower: Optional[float] = None, strict: bool = False) -> np.ndarray:
+def _vec(x, name: str, *, what: str, lower: Optional[float] = None, strict: bool = False, n: int = 4) -> np.ndarray:
     arr = np.asarray(list(x), dtype=float)
-    if arr.shape != (4,):
-        raise ValueError(f"{name} must have shape (4,), got {arr.shape}")
+    if arr.shape != (n,):
+        raise ValueError(f"{name} must have shape ({n},), got {arr.shape}")
     if not np.all(np.isfinite(arr)):
         raise ValueError(f"{name} must be finite")
     if lower is not None and np.any(arr <= lower if strict else arr < lower):
@@ -46,15 +46,15 @@ def _vec4(x, name: str, *, what: str, lower: Optional[float] = None, strict: boo
 
 
 def _to_omega_array(omega) -> np.ndarray:
-    return _vec4(omega, "omega", what="positive (rad/s)", lower=0.0, strict=True)
+    return _vec(omega, "omega", what="positive (rad/s)", lower=0.0, strict=True)
 
 
 def _to_power_array(p_in) -> np.ndarray:
-    return _vec4(p_in, "p_in", what="non-negative (W)", lower=0.0)
+    return _vec(p_in, "p_in", what="non-negative (W)", lower=0.0)
 
 
 def _to_phase_array(phase_in) -> np.ndarray:
-    return np.zeros(4) if phase_in is None else _vec4(phase_in, "phase_in", what="")
+    return np.zeros(4) if phase_in is None else _vec(phase_in, "phase_in", what="")
 
 
 def make_initial_amplitudes(p_in: Sequence[float], phase_in: Optional[Sequence[float]] = None) -> np.ndarray:
@@ -177,17 +177,6 @@ def run_single_simulation_adaptive(cfg: SimulationConfig, *, tol: AdaptiveConfig
 
 
 # ---- single-pump (degenerate) amplifier: one pump, a signal, an idler at 2 w_p - w_s ---------------------------------------
-def _vec3(x, name: str, *, what: str, lower: Optional[float] = None) -> np.ndarray:
-    arr = np.asarray(list(x), dtype=float)
-    if arr.shape != (3,):
-        raise ValueError(f"{name} must have shape (3,), got {arr.shape}")
-    if not np.all(np.isfinite(arr)):
-        raise ValueError(f"{name} must be finite")
-    if lower is not None and np.any(arr < lower):
-        raise ValueError(f"{name} must be {what}")
-    return arr
-
-
 def _positive_omega(x, name: str) -> float:
     v = float(x)
     if not np.isfinite(v):
@@ -195,6 +184,39 @@ def _positive_omega(x, name: str) -> float:
     if v <= 0.0:
         raise ValueError(f"{name} must be positive (rad/s)")
     return v
+
+
+def _single_pump_plan(omega_pump, omega_signal, p_in, phase_in) -> tuple[tuple[float, float, float], np.ndarray]:
+    """The frequency plan and the input of the single-pump model -> ((w_p, w_s, w_i), A0 (3,)): both frequencies and the idler's
+    2 w_p - w_s positive, three finite non-negative powers and three finite phases [pump, signal, idler]."""
+    wp, ws = _positive_omega(omega_pump, "omega_pump"), _positive_omega(omega_signal, "omega_signal")
+    wi = 2.0 * wp - ws
+    if wi <= 0.0:
+        raise ValueError("the idler frequency 2*omega_pump - omega_signal must be positive")
+    return (wp, ws, wi), initial_amplitudes(_vec(p_in, "p_in", what="non-negative (W)", lower=0.0, n=3),
+                                            np.zeros(3) if phase_in is None else _vec(phase_in, "phase_in", what="", n=3))
+
+
+def _single_pump_mismatch(wp, ws, wi, dispersion: DispersionParams, max_order: int):
+    """dbeta = beta(w_s) + beta(w_i) - 2 beta(w_p) of the single-pump model from the Taylor expansion of ``dispersion`` up to
+    ``max_order``: delta_beta_from_omegas_array on [w_p, w_p, w_s, w_i].  Scalars give a scalar; w_s, w_i (n,) give (n,)."""
+    om = np.empty(np.shape(ws) + (4,))
+    om[..., 0], om[..., 1], om[..., 2], om[..., 3] = wp, wp, ws, wi
+    return delta_beta_from_omegas_array(om, dispersion, max_order=max_order)
+
+
+def _run_one(sweep, mismatch, cfg, pre, A0, out_unit, **options):
+    """The end of the single-run functions of the wave-summary families: one point through ``sweep`` (rk4_sweep_single_pump or
+    rk4_sweep_comb) with its saved rows, the failure at its step, and z_out in ``out_unit``."""
+    fiber = pre["fiber"]
+    n_steps = n_steps_of(fiber.length_m, pre["grid"].dz_m)
+    r = sweep(mismatch, z_max=fiber.length_m, n_steps=n_steps, save_every=int(cfg.save_every), check_nan=bool(cfg.check_nan),
+              gamma=fiber.gamma_W_m, alpha=fiber.alpha_1_m, a0=A0, want_traj=True, **options)
+    z_m = np.linspace(0.0, fiber.length_m, n_steps + 1)
+    bad = int(r.first_bad_step[0])
+    if cfg.check_nan and bad >= 0:
+        raise FloatingPointError(f"NaN or Inf detected at step {bad}, z = {z_m[bad]}")
+    return z_m[::int(cfg.save_every)] / _length_scale_to_m(out_unit), r.traj[0]
 
 
 def run_single_pump_simulation(cfg: SimulationConfig, *, gamma: float, alpha: float, omega_pump: float, omega_signal: float,
@@ -208,12 +230,7 @@ def run_single_pump_simulation(cfg: SimulationConfig, *, gamma: float, alpha: fl
     run_single_simulation's: with cfg.check_nan a non-finite state raises FloatingPointError at its step."""
     validate_config(cfg)
     _length_scale_to_m(length_unit)
-    wp, ws = _positive_omega(omega_pump, "omega_pump"), _positive_omega(omega_signal, "omega_signal")
-    wi = 2.0 * wp - ws
-    if wi <= 0.0:
-        raise ValueError("the idler frequency 2*omega_pump - omega_signal must be positive")
-    A0 = initial_amplitudes(_vec3(p_in, "p_in", what="non-negative (W)", lower=0.0),
-                            np.zeros(3) if phase_in is None else _vec3(phase_in, "phase_in", what=""))
+    plan, A0 = _single_pump_plan(omega_pump, omega_signal, p_in, phase_in)
     if dispersion is None:
         raise ValueError("dispersion must be provided")
     if not isinstance(max_order, int):
@@ -222,20 +239,11 @@ def run_single_pump_simulation(cfg: SimulationConfig, *, gamma: float, alpha: fl
         raise ValueError("max_order must be >= 0")
     pre = _prepare(cfg, gamma=gamma, alpha=alpha, dispersion=dispersion, phase_matching_cfg=None, beta_legacy=None,
                    length_unit=length_unit)
-    fiber, grid = pre["fiber"], pre["grid"]
-    dbeta = float(delta_beta_from_omegas_array(np.array([wp, wp, ws, wi]), fiber.dispersion, max_order=max_order))
+    dbeta = float(_single_pump_mismatch(*plan, pre["fiber"].dispersion, max_order))
     if not np.isfinite(dbeta):
         raise ValueError("the phase mismatch is not finite")
-    n_steps = n_steps_of(fiber.length_m, grid.dz_m)
-    r = rk4_sweep_single_pump([dbeta], z_max=fiber.length_m, n_steps=n_steps, save_every=int(cfg.save_every),
-                              check_nan=bool(cfg.check_nan), exact_step=True, gamma=fiber.gamma_W_m, alpha=fiber.alpha_1_m,
-                              a0=A0, want_traj=True)
-    z_m = np.linspace(0.0, fiber.length_m, n_steps + 1)
-    bad = int(r.first_bad_step[0])
-    if cfg.check_nan and bad >= 0:
-        raise FloatingPointError(f"NaN or Inf detected at step {bad}, z = {z_m[bad]}")
-    out_unit = length_unit if return_length_unit is None else return_length_unit
-    return z_m[::int(cfg.save_every)] / _length_scale_to_m(out_unit), r.traj[0]
+    return _run_one(rk4_sweep_single_pump, [dbeta], cfg, pre, A0, length_unit if return_length_unit is None else return_length_unit,
+                    exact_step=True)
 
 
 # ---- multi-line ("comb") amplifier: M equally spaced lines, every FWM product among them ------------------------------------
@@ -274,22 +282,26 @@ def comb_lines(omega_center: float, line_spacing: float, n_lines: int, dispersio
     return omega, kappa, b
 
 
-def _comb_powers(p, name: str) -> np.ndarray:
-    arr = np.asarray(p, dtype=float)
-    if arr.ndim not in (1, 2) or arr.size == 0 or not 3 <= arr.shape[-1] <= MAX_LINES:
-        raise ValueError(f"{name} must have shape (M,) or (N, M) with 3 <= M <= {MAX_LINES}, got {arr.shape}")
-    if not np.all(np.isfinite(arr)) or np.any(arr < 0.0):
+def _comb_input(p, name: str, phase_in, *, points: bool = False) -> tuple[np.ndarray, np.ndarray]:
+    """The input of the multi-line model -> (the powers, A0 of their shape): ``p`` (called ``name``) finite non-negative powers
+    of M = 3..MAX_LINES lines, (M,) -- or, where the sweep points are power settings (``points``), (M,) or (N, M), returned as
+    (N, M) --, phase_in None or M finite phases."""
+    p = np.asarray(p, dtype=float)
+    if p.ndim not in (1, 2) or p.size == 0 or not 3 <= p.shape[-1] <= MAX_LINES:
+        raise ValueError(f"{name} must have shape (M,) or (N, M) with 3 <= M <= {MAX_LINES}, got {p.shape}")
+    if not np.all(np.isfinite(p)) or np.any(p < 0.0):
         raise ValueError(f"{name} must hold finite non-negative powers (W)")
-    return arr
-
-
-def _comb_phases(phase_in, M: int) -> Optional[np.ndarray]:
-    if phase_in is None:
-        return None
-    ph = np.asarray(phase_in, dtype=float)
-    if ph.shape != (M,) or not np.all(np.isfinite(ph)):
-        raise ValueError(f"phase_in must hold {M} finite phases")
-    return ph
+    if points:
+        p = np.atleast_2d(p)
+    elif p.ndim != 1:
+        raise ValueError(f"{name} must have shape (M,), got {p.shape}")
+    M = int(p.shape[-1])
+    ph = None
+    if phase_in is not None:
+        ph = np.asarray(phase_in, dtype=float)
+        if ph.shape != (M,) or not np.all(np.isfinite(ph)):
+            raise ValueError(f"phase_in must hold {M} finite phases")
+    return p, initial_amplitudes(p, ph)
 
 
 def run_comb_simulation(cfg: SimulationConfig, *, gamma: float, alpha: float, omega_center: float, line_spacing: float,
@@ -302,25 +314,13 @@ def run_comb_simulation(cfg: SimulationConfig, *, gamma: float, alpha: float, om
     FloatingPointError at its step."""
     validate_config(cfg)
     _length_scale_to_m(length_unit)
-    p = _comb_powers(p_in, "p_in")
-    if p.ndim != 1:
-        raise ValueError(f"p_in must have shape (M,), got {p.shape}")
-    M = int(p.shape[0])
-    A0 = initial_amplitudes(p, _comb_phases(phase_in, M))
+    p, A0 = _comb_input(p_in, "p_in", phase_in)
     if dispersion is None:
         raise ValueError("dispersion must be provided")
     pre = _prepare(cfg, gamma=gamma, alpha=alpha, dispersion=dispersion, phase_matching_cfg=None, beta_legacy=None,
                    length_unit=length_unit)
-    fiber, grid = pre["fiber"], pre["grid"]
-    _, kappa, _ = comb_lines(omega_center, line_spacing, M, fiber.dispersion, max_order=max_order)
-    n_steps = n_steps_of(fiber.length_m, grid.dz_m)
-    r = rk4_sweep_comb(kappa[None, :], z_max=fiber.length_m, n_steps=n_steps, save_every=int(cfg.save_every),
-                       check_nan=bool(cfg.check_nan), gamma=fiber.gamma_W_m, alpha=fiber.alpha_1_m, a0=A0, want_traj=True)
-    z_m = np.linspace(0.0, fiber.length_m, n_steps + 1)
-    bad = int(r.first_bad_step[0])
-    if cfg.check_nan and bad >= 0:
-        raise FloatingPointError(f"NaN or Inf detected at step {bad}, z = {z_m[bad]}")
-    return z_m[::int(cfg.save_every)] / pre["scale"], r.traj[0]
+    _, kappa, _ = comb_lines(omega_center, line_spacing, int(p.shape[0]), pre["fiber"].dispersion, max_order=max_order)
+    return _run_one(rk4_sweep_comb, kappa[None, :], cfg, pre, A0, length_unit)
 
 
 # ---- concatenated spans (copier - mid-stage - PSA chains) ------------------------------------------------------------
@@ -365,6 +365,39 @@ def _run_spans(chain, fibre, cfgs, A0, transfers, length_unit, return_length_uni
     return r.z_out / _length_scale_to_m(out_unit), r.traj[0]
 
 
+def _span_list(spans, length_unit) -> list:
+    """What every run_concatenated_* function checks before its frequency plan: at least one span and a known unit."""
+    spans = list(spans)
+    if not spans:
+        raise ValueError("spans must name at least one span")
+    _length_scale_to_m(length_unit)
+    return spans
+
+
+def _run_span_maps(chain, spans, A0, transfers, length_unit, return_length_unit, *, optional, needs, mismatch_of, required=(),
+                   rules=None):
+    """The span loop of every run_concatenated_* function, then _run_spans: each mapping of ``spans`` holds cfg, gamma, alpha,
+    the keys ``required`` (present and not None) and any of ``optional``, or the error names what it ``needs``;
+    ``rules(k, span)`` are the family's own rules on the mapping, _prepare scales the span to metres, and
+    ``mismatch_of(k, span, prepared)`` is its per-metre mismatch (a scalar, or the lines' propagation constants)."""
+    fibre, cfgs, known = [], [], {"cfg", "gamma", "alpha", *required, *optional}
+    for k, sp in enumerate(spans):
+        sp = dict(sp)
+        unknown = set(sp) - known
+        if unknown or "cfg" not in sp or "gamma" not in sp or "alpha" not in sp or any(sp.get(key) is None for key in required):
+            raise ValueError(f"span {k}: needs cfg, gamma, alpha{needs}; unknown keys {sorted(unknown)}")
+        if rules is not None:
+            rules(k, sp)
+        pre = _prepare(sp["cfg"], gamma=sp["gamma"], alpha=sp["alpha"], dispersion=sp.get("dispersion"),
+                       phase_matching_cfg=sp.get("phase_matching_cfg"), beta_legacy=sp.get("beta_legacy"),
+                       length_unit=length_unit)
+        fiber = pre["fiber"]
+        fibre.append(FibreSpan(length=fiber.length_m, dz=pre["grid"].dz_m, dbeta=mismatch_of(k, sp, pre), gamma=fiber.gamma_W_m,
+                               alpha=fiber.alpha_1_m))
+        cfgs.append(sp["cfg"])
+    return _run_spans(chain, fibre, cfgs, A0, transfers, length_unit, return_length_unit)
+
+
 def run_concatenated_simulation(spans, *, omega: Sequence[float], p_in: Sequence[float],
                                 phase_in: Optional[Sequence[float]] = None, transfers=None, length_unit: str = "m",
                                 return_length_unit: Optional[str] = None) -> tuple[np.ndarray, np.ndarray]:
@@ -376,31 +409,19 @@ def run_concatenated_simulation(spans, *, omega: Sequence[float], p_in: Sequence
     (4,) per-wave factors (mid_stage).  The FWM phase accumulates over the spans; rows are those of every span in order,
     each span's z = 0 row being the post-transfer state (z repeats at a boundary).  save_every and check_nan must agree
     between spans; with check_nan a non-finite state raises FloatingPointError at the chain's step index."""
-    spans = list(spans)
-    if not spans:
-        raise ValueError("spans must name at least one span")
-    _length_scale_to_m(length_unit)
+    spans = _span_list(spans, length_unit)
     om = _to_omega_array(omega)
     A0 = make_initial_amplitudes(_to_power_array(p_in), phase_in)
-    fibre, cfgs = [], []
-    for k, sp in enumerate(spans):
-        sp = dict(sp)
-        unknown = set(sp) - {"cfg", "gamma", "alpha", "dispersion", "phase_matching_cfg", "beta_legacy"}
-        if unknown or "cfg" not in sp or "gamma" not in sp or "alpha" not in sp:
-            raise ValueError(f"span {k}: needs cfg, gamma, alpha (+ dispersion / phase_matching_cfg / beta_legacy); "
-                             f"unknown keys {sorted(unknown)}")
-        cfg = sp["cfg"]
-        pre = _prepare(cfg, gamma=sp["gamma"], alpha=sp["alpha"], dispersion=sp.get("dispersion"),
-                       phase_matching_cfg=sp.get("phase_matching_cfg"), beta_legacy=sp.get("beta_legacy"),
-                       length_unit=length_unit)
+
+    def mismatch_of(k, sp, pre):
         params = make_model_params(waves=WavesParams(omega=om, symmetric=None), fiber=pre["fiber"], grid=pre["grid"],
                                    phase_matching=pre["pm"])
-        res = compute_phase_mismatch(params.waves.omega, params.fiber.dispersion, params.phase_matching.config,
-                                     symmetric_hint=params.waves.symmetric)
-        fibre.append(FibreSpan(length=params.fiber.length_m, dz=params.grid.dz_m, dbeta=float(res.delta_beta),
-                               gamma=params.fiber.gamma_W_m, alpha=params.fiber.alpha_1_m))
-        cfgs.append(cfg)
-    return _run_spans(rk4_chain, fibre, cfgs, A0, transfers, length_unit, return_length_unit)
+        return float(compute_phase_mismatch(params.waves.omega, params.fiber.dispersion, params.phase_matching.config,
+                                            symmetric_hint=params.waves.symmetric).delta_beta)
+
+    return _run_span_maps(rk4_chain, spans, A0, transfers, length_unit, return_length_unit,
+                          optional=("dispersion", "phase_matching_cfg", "beta_legacy"),
+                          needs=" (+ dispersion / phase_matching_cfg / beta_legacy)", mismatch_of=mismatch_of)
 
 
 def single_pump_mid_stage(gain_db=(0.0, 0.0, 0.0), phase=(0.0, 0.0, 0.0)) -> np.ndarray:
@@ -423,43 +444,31 @@ def run_concatenated_single_pump_simulation(spans, *, omega_pump: float, omega_s
     of every span in order, each span's z = 0 row being the post-transfer state (z repeats at a boundary).  save_every and
     check_nan must agree between spans; with check_nan a non-finite state raises FloatingPointError at the chain's step
     index."""
-    spans = list(spans)
-    if not spans:
-        raise ValueError("spans must name at least one span")
-    _length_scale_to_m(length_unit)
-    wp, ws = _positive_omega(omega_pump, "omega_pump"), _positive_omega(omega_signal, "omega_signal")
-    wi = 2.0 * wp - ws
-    if wi <= 0.0:
-        raise ValueError("the idler frequency 2*omega_pump - omega_signal must be positive")
-    A0 = initial_amplitudes(_vec3(p_in, "p_in", what="non-negative (W)", lower=0.0),
-                            np.zeros(3) if phase_in is None else _vec3(phase_in, "phase_in", what=""))
-    fibre, cfgs = [], []
-    for k, sp in enumerate(spans):
-        sp = dict(sp)
-        unknown = set(sp) - {"cfg", "gamma", "alpha", "dispersion", "max_order", "phase_matching_cfg"}
-        if unknown or "cfg" not in sp or "gamma" not in sp or "alpha" not in sp:
-            raise ValueError(f"span {k}: needs cfg, gamma, alpha (+ dispersion / phase_matching_cfg); "
-                             f"unknown keys {sorted(unknown)}")
-        pm, disp = sp.get("phase_matching_cfg"), sp.get("dispersion")
-        if (pm is None) == (disp is None):
+    spans = _span_list(spans, length_unit)
+    plan, A0 = _single_pump_plan(omega_pump, omega_signal, p_in, phase_in)
+
+    def rules(k, sp):
+        pm = sp.get("phase_matching_cfg")
+        if (pm is None) == (sp.get("dispersion") is None):
             raise ValueError(f"span {k}: needs exactly one of dispersion and phase_matching_cfg")
         if pm is not None and (not isinstance(pm, PhaseMatchingConfig) or pm.method != PhaseMatchingMethod.PROVIDED):
             raise ValueError(f"span {k}: phase_matching_cfg must be a PhaseMatchingConfig of method PROVIDED")
         max_order = sp.get("max_order", 4)
         if not isinstance(max_order, int) or max_order < 0:
             raise ValueError(f"span {k}: max_order must be a non-negative int")
-        pre = _prepare(sp["cfg"], gamma=sp["gamma"], alpha=sp["alpha"], dispersion=disp, phase_matching_cfg=pm,
-                       beta_legacy=None, length_unit=length_unit)
-        fiber, grid = pre["fiber"], pre["grid"]
-        if pm is not None:
+
+    def mismatch_of(k, sp, pre):
+        if sp.get("phase_matching_cfg") is not None:
             dbeta = float(pre["pm"].config.provided_delta_beta)
         else:
-            dbeta = float(delta_beta_from_omegas_array(np.array([wp, wp, ws, wi]), fiber.dispersion, max_order=max_order))
+            dbeta = float(_single_pump_mismatch(*plan, pre["fiber"].dispersion, sp.get("max_order", 4)))
         if not np.isfinite(dbeta):
             raise ValueError(f"span {k}: the phase mismatch is not finite")
-        fibre.append(FibreSpan(length=fiber.length_m, dz=grid.dz_m, dbeta=dbeta, gamma=fiber.gamma_W_m, alpha=fiber.alpha_1_m))
-        cfgs.append(sp["cfg"])
-    return _run_spans(rk4_chain_single_pump, fibre, cfgs, A0, transfers, length_unit, return_length_unit)
+        return dbeta
+
+    return _run_span_maps(rk4_chain_single_pump, spans, A0, transfers, length_unit, return_length_unit,
+                          optional=("dispersion", "max_order", "phase_matching_cfg"), needs=" (+ dispersion / phase_matching_cfg)",
+                          rules=rules, mismatch_of=mismatch_of)
 
 
 def comb_mid_stage(gain_db, phase) -> np.ndarray:
@@ -479,28 +488,12 @@ def run_concatenated_comb_simulation(spans, *, omega_center: float, line_spacing
     (comb_mid_stage).  Every line's phase accumulates over the spans; rows are those of every span in order, each span's
     z = 0 row being the post-transfer state (z repeats at a boundary).  save_every and check_nan must agree between spans;
     with check_nan a non-finite state raises FloatingPointError at the chain's step index."""
-    spans = list(spans)
-    if not spans:
-        raise ValueError("spans must name at least one span")
-    _length_scale_to_m(length_unit)
-    p = _comb_powers(p_in, "p_in")
-    if p.ndim != 1:
-        raise ValueError(f"p_in must have shape (M,), got {p.shape}")
-    M = int(p.shape[0])
-    A0 = initial_amplitudes(p, _comb_phases(phase_in, M))
-    fibre, cfgs = [], []
-    for k, sp in enumerate(spans):
-        sp = dict(sp)
-        unknown = set(sp) - {"cfg", "gamma", "alpha", "dispersion", "max_order"}
-        if unknown or "cfg" not in sp or "gamma" not in sp or "alpha" not in sp or sp.get("dispersion") is None:
-            raise ValueError(f"span {k}: needs cfg, gamma, alpha and dispersion (+ max_order); unknown keys {sorted(unknown)}")
-        pre = _prepare(sp["cfg"], gamma=sp["gamma"], alpha=sp["alpha"], dispersion=sp["dispersion"], phase_matching_cfg=None,
-                       beta_legacy=None, length_unit=length_unit)
-        fiber, grid = pre["fiber"], pre["grid"]
-        _, kappa, _ = comb_lines(omega_center, line_spacing, M, fiber.dispersion, max_order=sp.get("max_order", 4))
-        fibre.append(FibreSpan(length=fiber.length_m, dz=grid.dz_m, dbeta=kappa, gamma=fiber.gamma_W_m, alpha=fiber.alpha_1_m))
-        cfgs.append(sp["cfg"])
-    return _run_spans(rk4_chain_comb, fibre, cfgs, A0, transfers, length_unit, return_length_unit)
+    spans = _span_list(spans, length_unit)
+    p, A0 = _comb_input(p_in, "p_in", phase_in)
+    return _run_span_maps(rk4_chain_comb, spans, A0, transfers, length_unit, return_length_unit, required=("dispersion",),
+                          optional=("max_order",), needs=" and dispersion (+ max_order)",
+                          mismatch_of=lambda k, sp, pre: comb_lines(omega_center, line_spacing, int(p.shape[0]),
+                                                                    pre["fiber"].dispersion, max_order=sp.get("max_order", 4))[1])
 
 
 # ---- the reference's two ready-made scenarios (simulation.py:371-447), km-unit path -----------------------
