@@ -330,6 +330,55 @@ def test_chain(family):
     meets_the_bar(check("chain", family, got, inputs))
 
 
+# Three spans of the 4/6-wave chain entry point (truth_cases.chain3*): both pairs' gauge (theta2 / dbeta2 of the epilogue) under
+# transfers on every wave, the forced lane layouts, the per-wave summary, and a middle span that ends before the first re-seed.
+# Two launches per case: the trajectory (a_end, p_end, p_max, rows) and the per-wave summary (a_end, p_wave_end, p_wave_max).
+def _chain3_launches(inputs, flags, dtype=np.float64):
+    kw = TC.chain_arrays(inputs)
+    dbeta = kw.pop("dbeta")                                     # (S, N, K): column 0 the first pair's, column 1 the second's
+    kw.update(dtype=dtype, extra_flags=flags, dbeta2=np.ascontiguousarray(dbeta[:, :, 1]) if dbeta.shape[2] == 2 else None)
+    dbeta = np.ascontiguousarray(dbeta[:, :, 0])
+    rows, waves = nat.chain_host(dbeta, want_traj=True, **kw), nat.chain_host(dbeta, wave_summary=True, **kw)
+    assert rows["traj"].shape == inputs["truth"]["rows"].shape and waves["p_wave_end"].shape == inputs["a0"].shape
+    return {k: rows[k] for k in ("a_end", "p_end", "p_max", "traj", "first_bad_step")}, \
+           {k: waves[k] for k in ("a_end", "p_wave_end", "p_wave_max", "first_bad_step")}
+
+
+def _pump_powers_meet_the_bar(got, inputs, floor):
+    """The per-wave powers of the two pumps alone (truth_cases.pump_power_errors): under the bar itself."""
+    e_got, e_twin = TC.pump_power_errors(got, inputs["truth"]), TC.pump_power_errors(inputs["twin"], inputs["truth"])
+    for key in e_got:
+        assert TC.bar(e_got[key], e_twin[key], floor)[0], f"{key} of the pumps misses the bar"
+
+
+CHAIN3_F64 = [(4, False, "one_lane"), (4, False, "split"), (4, False, "quad"), (4, True, "one_lane"), (6, False, "one_lane"),
+              (6, False, "split")]
+
+
+@pytest.mark.parametrize("n_waves,mirrored,layout", CHAIN3_F64)
+def test_chain_of_three_spans(n_waves, mirrored, layout):
+    """Float64, 460 + 40 + 1000 steps.  Mirrored: span 0 runs the mirrored loop, spans 1 and 2 the general one.
+
+    The one-lane four-wave step is frame-anchored (FRAME_DRIFT above), in a chain as in a sweep: in those two cases the signal's
+    power -- p_end / p_max, and the per-wave powers where waves 2 and 3 carry them past the bar -- is held to the band
+    test_four_waves holds it to, the bar plus 1 500 (|r| - 1) by the header's figure; a_end, the rows and the pumps' powers are
+    held to the bar itself, and nothing lies beyond the band.  (Measured: neither case needs the band.  p_end is 15x and
+    8.5x the twin's median and, at 4e-16, under the floor.)"""
+    inputs = TC.chain3(n_waves, mirrored)
+    rows, waves = _chain3_launches(inputs, LAYOUTS[layout])
+    case = f"{TC.chain3_name(n_waves, mirrored)}-{layout}"
+    frame = layout == "one_lane" and n_waves == 4
+    budget = sum(s[1] for s in inputs["spans"]) * R_OFF_UNIT if frame else 0.0
+    missed = check("chain3", case + "-rows", rows, inputs, known=SIGNAL_POWER if frame else (), budget=budget)
+    missed_w = check("chain3", case + "-per-wave", waves, inputs, known=("p_wave_end", "p_wave_max") if frame else (), budget=budget)
+    if missed_w:
+        _pump_powers_meet_the_bar(waves, inputs, TC.FLOOR_F64)
+        print(f"truth | chain3 | {case}-per-wave | {', '.join(missed_w)} between the bar and the band by waves 2 and 3 (the frame's drift, "
+              f"budget {budget:.2e}); the pumps' own meet the bar")
+    if not frame:
+        meets_the_bar(dict(missed, **missed_w))
+
+
 # ---- float32 ---------------------------------------------------------------------------------------------------------------
 # Two bars.  The first, as above: no worse than a PLAIN float32 RK4 (floor 2e-6), with RTOL_F32 against the yardstick beside it.
 # The kernels sit 12x..30x below that twin, so it cannot see a compensated state that got lost.  The second holds the kernel to
@@ -340,19 +389,39 @@ def test_chain(family):
 F32_LAYOUTS = dict(packed=(nat.OPT_F32_PACKED, "base_offset"), scalar=(nat.OPT_F32_SCALAR, "kahan"))
 
 
-def check_float32(family, case, got, inputs, kind, plain_launch=None):
+def check_float32(family, case, got, inputs, kind, plain_launch=None, known=(), budget=None):
     """Both float32 bars, every assertion of check included; the second on a_end and on every wave's end and maximum power.
     ``plain_launch``: the same sweep without the per-wave summary (the instantiation the benchmark runs): its a_end and wave
     2's p_end / p_max are held to the second bar too, the latter two by the factors of one wave alone
-    (truth_cases.factors_compensated).  Raises BarMissed for what misses either bar."""
+    (truth_cases.factors_compensated).  A ``plain_launch`` with a trajectory (a chain's) goes through check as well, and its
+    rows are judged under both bars.  Raises BarMissed for what misses either bar.
+
+    ``known`` (with ``budget``, {output: (median, maximum)}): the outputs of the PLAIN launch a documented design choice lets miss
+    the SECOND bar.  Then BarMissed can carry these outputs and nothing else: everything else -- the first bar of both launches,
+    the second bar of the whole per-wave launch and of the plain launch's other outputs, and the band on the known ones, that bar
+    plus the budget (from the kernel header's figure, never a kernel's) -- fails with a plain AssertionError, which a strict xfail
+    on BarMissed does not accept.  Without ``known`` nothing changes: every miss of either bar is a BarMissed."""
     assert got["a_end"].dtype == np.complex64 and got["p_wave_end"] is not None
     missed = check(family, case, got, inputs, TC.FLOOR_F32, RTOL_F32)
     second = TC.judge_compensated(family, case, got, inputs, kind)
     if plain_launch is not None:
         assert (plain_launch["first_bad_step"] == -1).all()
-        second.update({f"{k} without the per-wave summary": v for k, v in
-                       TC.judge_compensated(family, case + "-plain-launch", {k: plain_launch[k] for k in ("a_end", "p_end", "p_max")},
-                                            inputs, kind).items()})
+        keys = ("a_end", "p_end", "p_max")
+        if plain_launch.get("traj") is not None:
+            keys += ("traj",)
+            missed.update({f"{k} of the trajectory launch": v for k, v in
+                           check(family, case + "-plain-launch", plain_launch, inputs, TC.FLOOR_F32, RTOL_F32).items()})
+        second_plain = TC.judge_compensated(family, case + "-plain-launch", {k: plain_launch[k] for k in keys}, inputs, kind)
+        if known:
+            assert not missed, "the first bar: " + "\n".join(line for line, *_ in missed.values())
+            assert not second, "the second bar, per-wave launch: " + "\n".join(line for line, *_ in second.values())
+            assert set(second_plain) <= set(known), "\n".join(second_plain[k][0] for k in second_plain if k not in known)
+            for key, (line, med, mx, tmed, tmx) in second_plain.items():
+                f_med, f_max = TC.factors_compensated(key)
+                assert med <= f_med * tmed + budget[key][0] and mx <= f_max * tmx + budget[key][1], f"beyond the stated drift: {line}"
+        second.update({f"{k} without the per-wave summary": v for k, v in second_plain.items()})
+    else:
+        assert not known
     meets_the_bar(missed)
     meets_the_bar({f"{k} against the {kind} twin": v for k, v in second.items()})
 
@@ -393,6 +462,56 @@ def test_single_pump_float32_against_the_compensated_twin():
     inputs = TC.single_pump_f32_compensated()
     got = nat.single_pump_host(inputs["dbeta"], dtype=np.float32, **sweep_kw(inputs))
     check_float32("single_pump-f32", "packed", got, inputs, "base_offset")
+
+
+CARRIED_BUDGET_F32 = 2 * TC.F32_RESYNC * 2.0 ** -24    # psa_rk4_kernel.inc.h's rule for a carried factor, "drift <= 128
+#   multiplications ~1.4e-14" between two float64 seeds 64 steps apart (2 x 64 roundings of 2^-53), at the float32 kernels' 16
+#   steps and 2^-24: 1.9e-6
+CARRIED_E_F32 = (
+    "the float32 kernels carry E(z) = 2 gamma exp(i dbeta z) by one rounded rotation per half step between exact seeds 16 steps "
+    "apart (psa_rk4_kernel.inc.h) where the compensated twins take cosf / sinf at every stage (DESIGN.md 4): up to 32 roundings "
+    "in E, 1.9e-6 by that header's rule for a carried factor (stated there for float64; the float32 figure is the same rule at 16 "
+    "steps and 2^-24), which a span with parametric gain carries into the signal.  On the four-wave general chain ONE point, "
+    "nearly phase-matched over its last span with the signal grown towards the pumps, decides the maxima of wave 2's power alone "
+    "(each run's record line names it).  The same carried factor planted into the Kahan chain twin on the CPU takes its p_end / "
+    "p_max maxima from 2.9e-8 / 2.5e-8 to 2.5e-7 / 2.2e-7, the kernels' figures, at that point, and moves nothing else "
+    "(test_truth_long_host.test_a_carried_phase_factor_takes_the_signal_power_over_the_second_bar): the compensated state and "
+    "the chain's boundaries are not involved.  This mark stands in for a fix that has not been made.  "
+    "Measured: ")
+CHAIN3_F32 = [
+    pytest.param(4, False, "packed", marks=xfail(CARRIED_E_F32, "p_max max 2.57e-7 (10.8x the base + offset twin's; p_end 2.99e-7, 6.9x)")),
+    pytest.param(4, False, "scalar", marks=xfail(CARRIED_E_F32, "p_end max 2.65e-7 (9.2x the Kahan twin's), p_max max 2.28e-7 (9.2x)")),
+    (4, True, "packed"), (6, False, "packed"), (6, False, "scalar")]
+
+
+@pytest.mark.parametrize("n_waves,mirrored,layout", CHAIN3_F32)
+def test_chain_of_three_spans_float32(n_waves, mirrored, layout):
+    """Float32, 460 + 12 + 1028 steps, rows every 4, both bars on both launches.  The middle span ends before the first 16-step
+    seed and fold: what the boundary carries is a base with an unfolded offset, rotated and rounded, transferred and rounded.
+    A chain whose spans >= 1 had lost the compensated state would sit at 2.5x .. 4.4x the second bar
+    (test_truth_long_host.test_the_second_bar_sees_a_compensation_lost_at_a_boundary).
+
+    On the four-wave general set wave 2's power alone (p_end / p_max of the trajectory launch) may miss the second bar by what
+    the carried phase factor's drift does to it, and no more; that band is the drift EVALUATED: E off by 2 x 16 x 2^-24 in
+    modulus at every z, planted into the 80-bit chain of the same inputs (truth_cases.chain3_f32_coupling_drift).  The band is
+    LOOSE and says so: the kernel header states the carried factor's figure for float64 only, 1.9e-6 is its rule at float32's 16
+    steps and 2^-24, and a drift of that size with one sign at every z gives 1.6e-6 / 1.4e-6 on the maxima -- six times what the
+    kernels show and about the first bar's floor -- so on these two outputs of these two cases the band catches a gross change
+    and little else.  What the mark cannot hide is everything else: BarMissed can carry p_end / p_max of the trajectory launch
+    alone (check_float32); every other output of both launches under both bars, the yardstick at RTOL_F32 and first_bad_step
+    fail the case with a plain AssertionError."""
+    inputs = TC.chain3_f32(n_waves, mirrored)
+    flags, kind = F32_LAYOUTS[layout]
+    rows, waves = _chain3_launches(inputs, flags, np.float32)
+    assert rows["traj"].dtype == np.complex64
+    case = f"{TC.chain3_name(n_waves, mirrored)}-{layout}"
+    carried = n_waves == 4 and not mirrored
+    budget = TC.chain3_f32_coupling_drift(n_waves, mirrored, CARRIED_BUDGET_F32) if carried else None
+    if carried:
+        print(f"\ntruth | chain3-f32 | {case} | E off by the stated {CARRIED_BUDGET_F32:.1e} planted into the 80-bit chain: "
+              + ", ".join(f"{k} median {budget[k][0]:.2e} max {budget[k][1]:.2e}" for k in SIGNAL_POWER), end="")
+        print(f"\ntruth | chain3-f32 | {case} | " + TC.chain3_signal_report(rows["p_end"], rows["p_max"], rows["traj"], inputs), end="")
+    check_float32("chain3-f32", case, waves, inputs, kind, plain_launch=rows, known=SIGNAL_POWER if carried else (), budget=budget)
 
 
 CONFIG4 = [("mirrored", 100_000, "packed"), ("mirrored", 1_000_000, "packed"), ("general", 100_000, "packed"),

@@ -106,6 +106,50 @@ def test_yardstick_against_40_digit_arithmetic(name):
     assert moved > 1e-3 and err < 1e-17
 
 
+def _mp_waves(theta, a, g, al):
+    """Two pumps and K pairs in yaman_model's form, the FWM phase of every pair given: the physical-frame equations of a span."""
+    K = len(theta)
+    p = [abs(x) ** 2 for x in a]
+    mix = sum(mpmath.expj(theta[k]) * a[2 + 2 * k] * a[3 + 2 * k] for k in range(K))
+    fwm = [mpmath.conj(a[1]) * mix, mpmath.conj(a[0]) * mix]
+    for k in range(K):
+        down = mpmath.expj(-theta[k]) * a[0] * a[1]
+        fwm += [mpmath.conj(a[3 + 2 * k]) * down, mpmath.conj(a[2 + 2 * k]) * down]
+    return [-al / 2 * a[j] + 1j * g * (p[j] + 2 * (sum(p) - p[j])) * a[j] + 2j * g * fwm[j] for j in range(2 + 2 * K)]
+
+
+def test_yardstick_chain_against_40_digit_arithmetic():
+    """truth_ld.chain -- the accumulated phase Theta_s + dbeta_s zeta, the transfers -- and rhs_waves at K = 2, which the cases
+    above do not reach: point 0 of the six-wave chain set, spans of 3 + 2 + 3 steps of 3.75 m with the set's own dbeta, gamma
+    and alpha per span and both transfers, against an mpmath RK4 of the physical-frame equations.  The same 1e-17."""
+    inp = TC.chain3_inputs(6, False, False)
+    spans = [(3.75 * n, n, db[:1], g[:1], al[:1]) for n, (_, _, db, g, al) in zip((3, 2, 3), inp["spans"])]
+    transfers = [t[:1] for t in inp["transfers"]]
+    got = T.chain(T.rhs_waves, inp["a0"][:1], spans, transfers, 1)["a_end"][0]
+    with mpmath.workdps(40):
+        a = [mpmath.mpc(complex(x)) for x in inp["a0"][0]]
+        theta = [mpmath.mpf(0)] * 2
+        for s, (length, n, db, g, al) in enumerate(spans):
+            rate, g, al = [mpmath.mpf(float(r)) for r in db[0]], mpmath.mpf(float(g[0])), mpmath.mpf(float(al[0]))
+            h = mpmath.mpf(length) / n
+            for i in range(n):
+                def f(zeta, y):
+                    return _mp_waves([th + r * zeta for th, r in zip(theta, rate)], y, g, al)
+                k1 = f(i * h, a)
+                k2 = f(i * h + h / 2, [x + h / 2 * k for x, k in zip(a, k1)])
+                k3 = f(i * h + h / 2, [x + h / 2 * k for x, k in zip(a, k2)])
+                k4 = f(i * h + h, [x + h * k for x, k in zip(a, k3)])
+                a = [x + h / 6 * (p + 2 * q + 2 * r + w) for x, p, q, r, w in zip(a, k1, k2, k3, k4)]
+            if s + 1 < len(spans):
+                a = [x * mpmath.mpc(complex(t)) for x, t in zip(a, transfers[s][0])]
+                theta = [th + r * mpmath.mpf(length) for th, r in zip(theta, rate)]
+        scale = max(abs(w) for w in a)
+        err = max(abs(mpmath.mpc(_to_mp(x.real), _to_mp(x.imag)) - w) for x, w in zip(got, a)) / scale
+        moved = max(abs(mpmath.mpc(complex(x)) - w) for x, w in zip(inp["a0"][0], a)) / scale
+    print(f"\nchain3-waves6: 80-bit chain against 40 digits {float(err):.2e} of the largest wave (the state moved by {float(moved):.2e})")
+    assert moved > 1e-3 and err < 1e-17
+
+
 def test_two_statements_of_the_pair_equations_agree():
     """rhs_waves (yaman_model's form) and rhs_pairs (the pairs kernel header's) are one model, written twice."""
     inp = TC.pairs(5)
@@ -249,3 +293,21 @@ def test_the_bar_sees_a_defect_that_rtol_f64_cannot():
           f"ratio {r_med:.1f} {r_max:.1f}")
     assert 0.0 < old < 0.2 * RTOL_F64                  # the old bar passes it with room
     assert not ok and r_med > 3 * 4.0 and r_max > 3 * 8.0     # the new one fails it on both aggregates, three times over
+
+
+@pytest.mark.parametrize("name,inputs", TC.CHAIN3_F64_SETS, ids=[n for n, _ in TC.CHAIN3_F64_SETS])
+def test_the_bar_sees_a_short_boundary_phase(name, inputs):
+    """What the bar adds for a chain: the B-gauge twin with the low 12 mantissa bits of every boundary phase dbeta_s L_s, and so
+    of Theta, cleared (a phase formed in the wrong precision, a Theta that cancels).  Every output stays far inside RTOL_F64 of
+    the clean twin, as the oracle test of the chains would judge it (measured 1.8e-13 .. 6.6e-13 at the largest output), and
+    at least one output of every set misses the bar against the yardstick (measured: every output of every set, on its maximum
+    -- a_end 10x .. 22x, the per-wave powers 18x .. 160x against the factor 8 -- and p_wave_max on its median as well)."""
+    s = inputs()
+    old = {k: float(v.max()) for k, v in TC.errors(s["short_phase"], s["twin"]).items()}
+    e_planted, e_clean = TC.errors(s["short_phase"], s["truth"]), TC.errors(s["twin"], s["truth"])
+    verdict = {k: TC.bar(e_planted[k], e_clean[k], TC.FLOOR_F64) for k in e_planted}
+    print(f"\nplanted-chain | {name} | against the clean twin at most {max(old.values()):.2e} ({max(old, key=old.get)}; RTOL_F64 "
+          f"{RTOL_F64:.0e}) | against the yardstick, ratio to the clean twin's median / max | "
+          + " | ".join(f"{k} {r_med:.1f} {r_max:.1f}{'' if ok else ' MISSES'}" for k, (ok, r_med, r_max) in verdict.items()))
+    assert 0.0 < max(old.values()) < RTOL_F64
+    assert not all(ok for ok, _, _ in verdict.values())

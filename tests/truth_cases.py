@@ -7,6 +7,9 @@ re-seeds), rows every 7 steps (a tail of 2 behind the last row).  Per-point gamm
 
 Every result is a dict in one form: a_end (N, NW), p_wave_end, p_wave_max (N, NW), rows (N, n_saved, NW) or None.
 
+Chains: two spans of every family (chain), and three spans of the 4/6-wave model in float64 and float32 with a middle span
+shorter than a seed interval (chain3, chain3_f32), whose twins restate the kernels' B gauge span by span (chain_b_gauge).
+
 At the end, the sets of the adaptive sweep (tests/test_truth_rk45_host.py, tests/test_gpu_rk45_truth.py): the same 67 points and
 fibre draws, each with the 80-bit run of Dormand-Prince 5(4) and its controller (truth_rk45_ld) and the twin's (rk45_np).
 """
@@ -58,6 +61,16 @@ def errors(got, truth):
     rows = got.get("rows") if got.get("rows") is not None else got.get("traj")
     if rows is not None and truth["rows"] is not None:
         out["rows"] = T.point_err(rows, truth["rows"])
+    return out
+
+
+def pump_power_errors(got, truth):
+    """errors' figure for the per-wave powers with the two pumps' columns alone: their moduli against the point's largest
+    modulus.  -> {p_wave_end, p_wave_max: (N,) float64}."""
+    out = {}
+    for key in ("p_wave_end", "p_wave_max"):
+        mod = np.sqrt(truth[key])
+        out[key] = np.asarray(np.abs(np.sqrt(T.ld(got[key][:, :2])) - mod[:, :2]).max(axis=1) / mod.max(axis=1), dtype=np.float64)
     return out
 
 
@@ -320,8 +333,11 @@ def _rhs32_single_pump(e, a, g, al):
     return (F32(-0.5) * al) * a + C64(1j) * (g * kerr * a) + C64(1j) * (g * M)
 
 
-def rk4_f32(rhs, a0, dbeta, *, z_max, n, save_every, gamma, alpha):
-    """State and arithmetic in float32 / complex64; z = i h in float64 for the phase alone."""
+def rk4_f32(rhs, a0, dbeta, *, z_max, n, save_every, gamma, alpha, kahan=False, carried_for=0):
+    """State and arithmetic in float32 / complex64; z = i h in float64 for the phase alone.
+    kahan: the compensated state update of the scalar float32 kernel (psa_rk4_kernel.inc.h, rk4_step_classic) in the place of
+    y += increment.  carried_for = 16: the phase factor as the float32 kernels have it -- an exact seed every 16 steps and one
+    rotation by the rounded exp(i dbeta h / 2) per half step from there -- in the place of cos / sin at every stage."""
     dbeta = np.asarray(dbeta, dtype=F32)
     n_pts = dbeta.shape[0]
     y = np.array(np.broadcast_to(np.asarray(a0, dtype=C64), (n_pts, np.shape(a0)[-1])))
@@ -329,15 +345,24 @@ def rk4_f32(rhs, a0, dbeta, *, z_max, n, save_every, gamma, alpha):
     al = np.broadcast_to(np.asarray(alpha, dtype=F32), (n_pts,))[:, None]
     h64 = z_max / n
     h, half, sixth = F32(h64), F32(0.5 * h64), F32(h64 / 6.0)
-    rows = [y]
+    rows, lo, rot = [y], np.zeros_like(y), _expi32(dbeta, 0.5 * h64)
     for i in range(n):
-        e0, em, e1 = _expi32(dbeta, i * h64), _expi32(dbeta, (i + 0.5) * h64), _expi32(dbeta, (i + 1) * h64)
+        if carried_for:
+            e0 = _expi32(dbeta, i * h64) if i % carried_for == 0 else e1
+            em = e0 * rot
+            e1 = em * rot
+        else:
+            e0, em, e1 = _expi32(dbeta, i * h64), _expi32(dbeta, (i + 0.5) * h64), _expi32(dbeta, (i + 1) * h64)
         k1 = rhs(e0, y, g, al)
         k2 = rhs(em, y + half * k1, g, al)
         k3 = rhs(em, y + half * k2, g, al)
         k4 = rhs(e1, y + h * k3, g, al)
-        y = y + sixth * (k1 + F32(2) * k2 + F32(2) * k3 + k4)
-        assert y.dtype == C64
+        inc = sixth * (k1 + F32(2) * k2 + F32(2) * k3 + k4)
+        if kahan:
+            inc = inc + lo
+            lo = inc - ((y + inc) - y)
+        y = y + inc
+        assert y.dtype == C64 and e1.dtype == C64
         if (i + 1) % save_every == 0:
             rows.append(y)
     return from_rows(np.stack(rows, axis=1))
@@ -588,6 +613,178 @@ F64_SETS = ([(f"waves4-{'mirrored' if m else 'general'}-{'lossy' if l else 'loss
             + [("comb-M7-kappa0", lambda: comb_without_dispersion(7))])
 F32_SETS = [("waves4_f32-general", lambda: waves4_f32(False)), ("waves4_f32-mirrored", lambda: waves4_f32(True)),
             ("single_pump_f32", single_pump_f32)]
+
+
+# ---- three-span chains of the 4/6-wave model, float64 and float32 ----------------------------------------------------------
+# What chain("waves") leaves out: six waves with transfers on both pairs (theta2 / dbeta2 of the chain epilogue), the forced lane
+# layouts, the per-wave summary, float32, and spans that end before the first re-seed (64 steps in float64, 16 in float32) --
+# in float32 before the first base + offset fold as well, so that the boundary carries a base with an unfolded offset.
+#   float64: 460 + 40 + 1000 steps over 92 + 10 + 240 m, rows every 20: the middle span is two rows long, no span a multiple of 64.
+#   float32: 460 + 12 + 1028 steps over 92 + 3 + 246.72 m, rows every 4; the float32-rounded inputs are what is integrated.
+# The yardstick is truth_ld.chain, the accumulated-phase model in the physical frame; the twins restate the kernels' B gauge
+# (psa_chain.hip) span by span on the compiled plain RK4, so their agreement checks the gauge and not only the arithmetic.
+CHAIN3_SHAPES = {False: ((460, 40, 1000), (92.0, 10.0, 240.0), 20), True: ((460, 12, 1028), (92.0, 3.0, 246.72), 4)}
+CHAIN3_KINDS = ((4, False), (4, True), (6, False))        # (n_waves, mirrored)
+
+
+def chain3_name(n_waves, mirrored, float32=False):
+    return f"chain3{'_f32' if float32 else ''}-{'waves6' if n_waves == 6 else 'mirrored' if mirrored else 'general'}"
+
+
+def chain3_inputs(n_waves, mirrored, float32):
+    """-> a0 (N, NW), spans [(length, n_steps, dbeta (N, K), gamma (N,), alpha (N,))], transfers [2 x (N, NW)], save_every; K =
+    1 or 2, column 0 of a span's dbeta the first pair's mismatch and column 1 the second's.  mirrored: A2 == A1 and A4 == A3 in
+    a0 and in both transfers -- span 0 is mirrored, and the gauge phase of the first boundary ends that."""
+    steps, lengths, save_every = CHAIN3_SHAPES[bool(float32)]
+    rng = np.random.default_rng((4900 if float32 else 4800) + n_waves + mirrored)
+    K = (n_waves - 2) // 2
+    a0 = _amplitudes(rng, N, 2, 2 * K)
+    if mirrored:
+        a0[:, 1], a0[:, 3] = a0[:, 0], a0[:, 2]
+    spans = [(L, n, rng.uniform(-0.05, 0.05, (N, K)), GAMMA * rng.uniform(0.8, 1.6, N), ALPHA * rng.uniform(0.5, 2.0, N))
+             for L, n in zip(lengths, steps)]
+    transfers = [_mid_stage(rng, (N, n_waves)) for _ in range(2)]
+    if mirrored:
+        for t in transfers:
+            t[:, 1], t[:, 3] = t[:, 0], t[:, 2]
+    if float32:
+        a0, transfers = a0.astype(C64), [t.astype(C64) for t in transfers]
+        spans = [(L, n, db.astype(F32), g.astype(F32), al.astype(F32)) for L, n, db, g, al in spans]
+    return dict(a0=a0, spans=spans, transfers=transfers, save_every=save_every)
+
+
+def _clear_low_bits(x, bits=12):
+    """A float64 array with the low ``bits`` of every mantissa cleared."""
+    out = np.array(x, dtype=np.float64)
+    out.view(np.uint64)[...] &= ~np.uint64((1 << bits) - 1)
+    return out
+
+
+def chain_b_gauge(inp, precision, update="plain", later_update=None, phase=lambda ph: ph, span_run=None):
+    """The chain as psa_chain.hip's header states it, on oracle/plain_rk4.py (model "pairs"): every span runs on its local
+    coordinate from the current B state; its rows come back to A with e^{-i Theta^(k)} on wave 2 + 2k; at a boundary the signal
+    columns are multiplied by e^{+i dbeta_{s,k} L_s}, then every wave by its transfer, and Theta^(k) += dbeta_{s,k} L_s.  Theta
+    and all boundary arithmetic are float64; precision "f32" rounds to complex64 after the rotation and again after the
+    transfer, as the epilogue does, and rounds the rotated rows.
+    later_update: the state update of spans >= 1 where it is not ``update`` (planted: a compensation lost at the first boundary).
+    phase: applied to the boundary phase dbeta_s L_s before it is used and accumulated (planted: low bits cleared).
+    span_run: another statement of one span in the place of the compiled one: f(b, dbeta (N, K), z_max=, n=, save_every=, gamma=,
+    alpha=) -> the result dict with its rows.
+    -> the result dict: a_end and rows in the A frame; the powers are the spans' own, phase-blind and so taken in B as the
+    epilogue folds them (the last span's end, the maximum over the spans)."""
+    import plain_rk4
+    cplx = C64 if precision == "f32" else np.complex128
+    b = np.asarray(inp["a0"], dtype=np.complex128)
+    n_pts, nw = b.shape
+    theta, rows, p_max = np.zeros((n_pts, (nw - 2) // 2)), [], None
+    for s, (length, n, dbeta, gamma, alpha) in enumerate(inp["spans"]):
+        dbeta = np.asarray(dbeta, dtype=np.float64).reshape(n_pts, -1)
+        kw = dict(z_max=length, n=n, save_every=inp["save_every"], gamma=gamma, alpha=alpha)
+        span = span_run(b, dbeta, **kw) if span_run else plain_rk4.integrate(
+            "pairs", b, dbeta, precision=precision, update=update if s == 0 or later_update is None else later_update,
+            want_rows=True, **kw)
+        B = span["rows"]
+        assert B.dtype == cplx
+        p_max = span["p_wave_max"] if p_max is None else np.maximum(p_max, span["p_wave_max"])
+        A = B.astype(np.complex128)
+        if s:
+            A[:, :, 2::2] *= np.exp(-1j * theta)[:, None, :]
+        rows.append(A.astype(cplx))
+        if s + 1 < len(inp["spans"]):
+            ph = phase(dbeta * length)
+            b = B[:, -1].astype(np.complex128)
+            b[:, 2::2] *= np.exp(1j * ph)
+            b = b.astype(cplx).astype(np.complex128) * np.asarray(inp["transfers"][s], dtype=np.complex128)
+            b = b.astype(cplx).astype(np.complex128)
+            theta = theta + ph
+    rows = np.concatenate(rows, axis=1)
+    return dict(a_end=rows[:, -1], p_wave_end=span["p_wave_end"], p_wave_max=p_max, rows=rows)
+
+
+def _chain3_truth(inp):
+    return T.chain(T.rhs_waves, inp["a0"], inp["spans"], inp["transfers"], inp["save_every"])
+
+
+@functools.lru_cache(maxsize=None)
+def chain3(n_waves, mirrored):
+    """The float64 set: the 80-bit run, the B-gauge twin, and ``short_phase``, the twin with the low 12 mantissa bits of every
+    boundary phase (and so of Theta) cleared -- the planted defect of the host test."""
+    inp = chain3_inputs(n_waves, mirrored, False)
+    return dict(inp, truth=_chain3_truth(inp), twin=chain_b_gauge(inp, "f64"),
+                short_phase=chain_b_gauge(inp, "f64", phase=_clear_low_bits))
+
+
+@functools.lru_cache(maxsize=None)
+def chain3_f32(n_waves, mirrored):
+    """The float32 set in _f32_set's form (twin: the plain float32 chain; kahan, base_offset, base_offset_no_residue), with the
+    80-bit run of the rounded inputs as the yardstick, and the planted defect of the host test under "<kind>_lost": the
+    compensation kept in span 0 and dropped from the first boundary on."""
+    inp = chain3_inputs(n_waves, mirrored, True)
+    out = dict(inp, truth=_chain3_truth(inp), twin=chain_b_gauge(inp, "f32"))
+    for update in COMPENSATED + ("base_offset_no_residue",):
+        out[update] = chain_b_gauge(inp, "f32", update)
+    for update in COMPENSATED:
+        out[update + "_lost"] = chain_b_gauge(inp, "f32", update, later_update="plain")
+    return out
+
+
+F32_RESYNC = 16                        # psa_rk4_kernel.inc.h: the float32 kernels re-seed their carried phase factor every 16 steps
+
+
+@functools.lru_cache(maxsize=None)
+def chain3_f32_kahan_np(carried):
+    """The four-wave general float32 chain once more, in NumPy with the scalar kernel's Kahan update (rk4_f32): with cos / sin at
+    every stage -- a third compensated statement -- or with ONE thing planted, the phase factor carried as the float32 kernels
+    carry it.  What places the finding of test_gpu_truth.test_chain_of_three_spans_float32 (CARRIED_E_F32 there)."""
+    def span_run(b, dbeta, **kw):
+        return rk4_f32(_rhs32_waves, b, dbeta[:, 0], kahan=True, carried_for=F32_RESYNC if carried else 0, **kw)
+    return chain_b_gauge(chain3_inputs(4, False, True), "f32", span_run=span_run)
+
+
+def chain3_signal_report(p_end, p_max, rows, s):
+    """Where wave 2's power alone is worst in a run of a chain3 set, as one readable line: the point with the largest p_max
+    error and the next one, with their p_end / p_max errors; at the worst point the mismatch of the last span, how far the signal
+    grows (its largest modulus over the point's largest), and the error of the signal's modulus in the saved rows at the start of
+    the last span and at its largest inside it -- whether the error arrives over a boundary or grows within the span."""
+    e = errors(dict(a_end=s["truth"]["a_end"], p_end=p_end, p_max=p_max), s["truth"])
+    first, second = (int(j) for j in np.argsort(e["p_max"])[::-1][:2])
+    mod = np.sqrt(s["truth"]["p_wave_max"][first])
+    start = sum(n // s["save_every"] + 1 for _, n, *_ in s["spans"][:-1])
+    in_rows = np.asarray(np.abs(np.abs(np.asarray(rows)[first, :, 2].astype(T.CLD)) - np.abs(s["truth"]["rows"][first, :, 2]))
+                         / mod.max(), dtype=np.float64)
+    return (f"wave 2's power alone is worst at point {first}: p_end {e['p_end'][first]:.2e} p_max {e['p_max'][first]:.2e}, last span dbeta "
+            f"{float(s['spans'][-1][2][first, 0]):.4f} 1/m over {s['spans'][-1][1]} steps, signal up to {float(mod[2] / mod.max()):.2f} of the "
+            f"largest wave, its modulus in the rows {in_rows[start]:.2e} off at the start of the last span and up to "
+            f"{in_rows[start:].max():.2e} inside it; next point {second}: p_end {e['p_end'][second]:.2e} p_max {e['p_max'][second]:.2e}")
+
+
+def _rhs_waves_coupling_off_by(delta):
+    """truth_ld.rhs_waves with every FWM term scaled by 1 + delta: a phase factor E = 2 gamma exp(i theta) whose modulus is off."""
+    def f(theta, a, gamma, alpha):
+        full = T.rhs_waves(theta, a, gamma, alpha)
+        P = T.power(a)
+        without = (-(alpha[:, None] / T.LD(2)) + T.I * gamma[:, None] * (T.LD(2) * P.sum(axis=1, keepdims=True) - P)) * a
+        return full + T.LD(delta) * (full - without)
+    return f
+
+
+@functools.lru_cache(maxsize=None)
+def chain3_f32_coupling_drift(n_waves, mirrored, off):
+    """What a phase factor off by ``off`` in modulus -- the drift psa_rk4_kernel.inc.h's rule allows a carried factor between two
+    seeds -- does to the outputs of chain3_f32's set, evaluated and not estimated as in g8_long_frame_drift: the 80-bit chain
+    with every FWM term scaled by 1 + off, at every z and with one sign, against the clean one.  -> {output: (median, maximum)
+    of its point_err over the points}: the budgets of a band's median and maximum, for both launches' outputs."""
+    s = chain3_f32(n_waves, mirrored)
+    planted = T.chain(_rhs_waves_coupling_off_by(off), s["a0"], s["spans"], s["transfers"], s["save_every"])
+    e = errors(planted, s["truth"])
+    e.update({k: v for k, v in errors(dict(a_end=planted["a_end"], p_end=planted["p_wave_end"][:, 2],
+                                           p_max=planted["p_wave_max"][:, 2]), s["truth"]).items() if k != "a_end"})
+    return {k: (float(np.median(v)), float(v.max())) for k, v in e.items()}
+
+
+CHAIN3_F64_SETS = [(chain3_name(nw, m), lambda nw=nw, m=m: chain3(nw, m)) for nw, m in CHAIN3_KINDS]
+CHAIN3_F32_SETS = [(chain3_name(nw, m, True), lambda nw=nw, m=m: chain3_f32(nw, m)) for nw, m in CHAIN3_KINDS]
+F64_SETS += CHAIN3_F64_SETS
 
 
 # ---- the adaptive sweep: Dormand-Prince 5(4) against the 80-bit run of its own scheme (truth_rk45_ld) ------------------------
