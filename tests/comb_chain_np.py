@@ -10,28 +10,20 @@ them), built on tests/comb_np.py: the yardstick of tests/test_comb_chain_host.py
   brought back to A with e^{-i Phi_{s,m}} on every line.  ``gauge=False`` leaves the boundary phase and the rotation out: the
   chain that forgot the gauge.
 
+Both are the span loop of tests/chain_np.py over this module's MODEL: its span integrator, its accumulated-phase right-hand
+side and the waves that carry the phase.
+
 spans: (length, n_steps, kappa, gamma, alpha) per span, kappa (M,) or (N, M), gamma / alpha a scalar or (N,); transfers: S-1
 entries (M,) or (N, M).
 """
+import functools
+
 import numpy as np
 
+import chain_np
 import comb_np
 
 GAMMA = 0.0115          # 1/(W m)
-
-
-def _points(a0, spans, transfers=()):
-    sizes = {np.size(v) for sp in spans for v in sp[3:]} | {np.shape(x)[0] for x in [sp[2] for sp in spans] + list(transfers)
-                                                            if np.ndim(x) == 2}
-    if np.ndim(a0) == 2:
-        sizes.add(np.shape(a0)[0])
-    sizes.discard(1)
-    assert len(sizes) <= 1
-    return sizes.pop() if sizes else 1
-
-
-def _per_point(x, N):
-    return np.array(np.broadcast_to(np.asarray(x, dtype=float), (N,)))
 
 
 def rhs_phi(phi, a, gamma, alpha):
@@ -40,70 +32,10 @@ def rhs_phi(phi, a, gamma, alpha):
     return -0.5 * alpha[:, None] * a + 1j * gamma[:, None] * np.conj(u) * comb_np.pair_sum(a * u)
 
 
-def direct(a0, spans, transfers, save_every):
-    """-> rows (N, n_saved_total, M) in the A frame: every span's row 0 (the post-transfer state) and a row after every
-    save_every-th step."""
-    N = _points(a0, spans, transfers)
-    M = np.shape(a0)[-1]
-    y = np.array(np.broadcast_to(np.asarray(a0, dtype=np.complex128), (N, M)))
-    phi0 = np.zeros((N, M))
-    rows = []
-    for k, (L, n, kp, g, al) in enumerate(spans):
-        kp = np.array(np.broadcast_to(np.asarray(kp, dtype=float), (N, M)))
-        g, al = _per_point(g, N), _per_point(al, N)
-        zg = np.linspace(0.0, L, n + 1)
-        rows.append(y.copy())
-        for i in range(n):
-            z, h = zg[i], zg[i + 1] - zg[i]
-            k1 = rhs_phi(phi0 + kp * z, y, g, al)
-            k2 = rhs_phi(phi0 + kp * (z + 0.5 * h), y + 0.5 * h * k1, g, al)
-            k3 = rhs_phi(phi0 + kp * (z + 0.5 * h), y + 0.5 * h * k2, g, al)
-            k4 = rhs_phi(phi0 + kp * (z + h), y + h * k3, g, al)
-            y = y + (h / 6.0) * (k1 + 2.0 * k2 + 2.0 * k3 + k4)
-            if (i + 1) % save_every == 0:
-                rows.append(y.copy())
-        if k + 1 < len(spans):
-            y = y * np.asarray(transfers[k], dtype=np.complex128)
-            phi0 = phi0 + kp * L
-    return np.stack(rows, axis=1)
-
-
-def chain(a0, spans, transfers, save_every, gauge=True):
-    """-> dict(rows (N, n_saved_total, M) A frame, a_end (N, M), p_wave_end, p_wave_max (N, M) over every saved row,
-    first_bad_step (N,) counted over the whole chain (first failure wins), z_out (n_saved_total,))."""
-    N = _points(a0, spans, transfers)
-    M = np.shape(a0)[-1]
-    b = np.array(np.broadcast_to(np.asarray(a0, dtype=np.complex128), (N, M)))
-    phi = np.zeros((N, M))
-    bad = np.full(N, -1, dtype=np.int64)
-    rows, z_out, z0, step0 = [], [], 0.0, 0
-    for k, (L, n, kp, g, al) in enumerate(spans):
-        kp = np.array(np.broadcast_to(np.asarray(kp, dtype=float), (N, M)))
-        r = comb_np.integrate(b, kp, z_max=L, n=n, save_every=save_every, gamma=g, alpha=al, want_traj=True)
-        A = r["traj"].copy()
-        with np.errstate(all="ignore"):
-            if gauge:
-                A *= np.exp(-1j * phi)[:, None, :]
-            rows.append(A)
-            z_out.append(z0 + np.linspace(0.0, L, n + 1)[::save_every])
-            new = (bad < 0) & (r["first_bad_step"] >= 0)
-            bad[new] = r["first_bad_step"][new] + step0
-            z0, step0 = z0 + L, step0 + n
-            if k + 1 < len(spans):
-                b = r["a_end"] * np.asarray(transfers[k], dtype=np.complex128)
-                if gauge:
-                    b = b * np.exp(1j * kp * L)
-                    phi = phi + kp * L
-    rows = np.concatenate(rows, axis=1)
-    with np.errstate(all="ignore"):
-        p = np.abs(rows) ** 2
-    return dict(rows=rows, a_end=rows[:, -1], p_wave_end=p[:, -1], p_wave_max=np.max(p, axis=1), first_bad_step=bad,
-                z_out=np.concatenate(z_out))
-
-
-def mid_stage(gain_db, phase):
-    """sqrt(10^(gain_db/10)) e^{i phase}, written out here so the restatement does not lean on the package."""
-    return np.sqrt(10.0 ** (np.asarray(gain_db, dtype=float) / 10.0)) * np.exp(1j * np.asarray(phase, dtype=float))
+MODEL = chain_np.Model(integrate=functools.partial(comb_np.integrate, want_traj=True), rhs=rhs_phi, gauged=slice(None))
+direct = functools.partial(chain_np.direct, MODEL)
+chain = functools.partial(chain_np.chain, MODEL)
+mid_stage, subset = chain_np.mid_stage, chain_np.subset
 
 
 # ---- the cases of the issue, shared between the CPU and the GPU tests -----------------------------------------------------
@@ -132,13 +64,6 @@ def lossy_case(N, M, seed=11, steps=(600, 1000, 400), lengths=(300.0, 500.0, 200
     transfers = [mid_stage(rng.uniform(-3, 1, (N, M)), rng.uniform(-np.pi, np.pi, (N, M))),
                  mid_stage(rng.uniform(-2, 1, M), rng.uniform(-np.pi, np.pi, M))]
     return a0, spans, transfers
-
-
-def subset(case, idx):
-    """(a0, spans, transfers) of lossy_case cut to the points ``idx``."""
-    a0, spans, transfers = case
-    return (a0[idx], [(L, n, kp[idx], g[idx], al[idx]) for L, n, kp, g, al in spans],
-            [t[idx] if t.ndim == 2 else t for t in transfers])
 
 
 def split_fibre(rng, N, M, n_steps, length, pieces):

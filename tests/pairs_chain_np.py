@@ -10,28 +10,20 @@ i_K]), built on tests/pairs_np.py: the yardstick of tests/test_pairs_chain_host.
   brought back to A with e^{-i Theta_{s,k}} on wave 2 + 2k.  ``gauge=False`` leaves the boundary phase and the rotation out:
   the chain that forgot the gauge.
 
+Both are the span loop of tests/chain_np.py over this module's MODEL: its span integrator, its accumulated-phase right-hand
+side and the waves that carry the phase.
+
 spans: (length, n_steps, dbeta, gamma, alpha) per span, dbeta (K,) or (N, K), gamma / alpha a scalar or (N,); transfers: S-1
 entries (NW,) or (N, NW).
 """
+import functools
+
 import numpy as np
 
+import chain_np
 import pairs_np
 
 GAMMA, P_PUMP = 0.0115, 0.25          # 1/(W m); each of the two pumps, W
-
-
-def _points(a0, spans, transfers=()):
-    sizes = {np.size(v) for sp in spans for v in sp[3:]} | {np.shape(x)[0] for x in [sp[2] for sp in spans] + list(transfers)
-                                                            if np.ndim(x) == 2}
-    if np.ndim(a0) == 2:
-        sizes.add(np.shape(a0)[0])
-    sizes.discard(1)
-    assert len(sizes) <= 1
-    return sizes.pop() if sizes else 1
-
-
-def _per_point(x, N):
-    return np.array(np.broadcast_to(np.asarray(x, dtype=float), (N,)))
 
 
 def integrate(a0, dbeta, *, z_max, n, save_every, gamma, alpha):
@@ -39,7 +31,7 @@ def integrate(a0, dbeta, *, z_max, n, save_every, gamma, alpha):
     dbeta = np.asarray(dbeta, dtype=float)
     N, K = dbeta.shape
     y = np.array(np.broadcast_to(np.asarray(a0, dtype=np.complex128), (N, 2 + 2 * K)))
-    gamma, alpha = _per_point(gamma, N), _per_point(alpha, N)
+    gamma, alpha = chain_np._per_point(gamma, N), chain_np._per_point(alpha, N)
     zg = np.linspace(0.0, z_max, n + 1)
     bad = np.full(N, -1, dtype=np.int64)
     rows = [y.copy()]
@@ -77,72 +69,10 @@ def rhs_theta(theta, a, gamma, alpha):
     return out
 
 
-def direct(a0, spans, transfers, save_every):
-    """-> rows (N, n_saved_total, NW) in the A frame: every span's row 0 (the post-transfer state) and a row after every
-    save_every-th step."""
-    N = _points(a0, spans, transfers)
-    nw = np.shape(a0)[-1]
-    K = (nw - 2) // 2
-    y = np.array(np.broadcast_to(np.asarray(a0, dtype=np.complex128), (N, nw)))
-    theta0 = np.zeros((N, K))
-    rows = []
-    for k, (L, n, db, g, al) in enumerate(spans):
-        db = np.array(np.broadcast_to(np.asarray(db, dtype=float), (N, K)))
-        g, al = _per_point(g, N), _per_point(al, N)
-        zg = np.linspace(0.0, L, n + 1)
-        rows.append(y.copy())
-        for i in range(n):
-            z, h = zg[i], zg[i + 1] - zg[i]
-            k1 = rhs_theta(theta0 + db * z, y, g, al)
-            k2 = rhs_theta(theta0 + db * (z + 0.5 * h), y + 0.5 * h * k1, g, al)
-            k3 = rhs_theta(theta0 + db * (z + 0.5 * h), y + 0.5 * h * k2, g, al)
-            k4 = rhs_theta(theta0 + db * (z + h), y + h * k3, g, al)
-            y = y + (h / 6.0) * (k1 + 2.0 * k2 + 2.0 * k3 + k4)
-            if (i + 1) % save_every == 0:
-                rows.append(y.copy())
-        if k + 1 < len(spans):
-            y = y * np.asarray(transfers[k], dtype=np.complex128)
-            theta0 = theta0 + db * L
-    return np.stack(rows, axis=1)
-
-
-def chain(a0, spans, transfers, save_every, gauge=True):
-    """-> dict(rows (N, n_saved_total, NW) A frame, a_end (N, NW), p_wave_end, p_wave_max (N, NW) over every saved row,
-    first_bad_step (N,) counted over the whole chain (first failure wins), z_out (n_saved_total,))."""
-    N = _points(a0, spans, transfers)
-    nw = np.shape(a0)[-1]
-    K = (nw - 2) // 2
-    b = np.array(np.broadcast_to(np.asarray(a0, dtype=np.complex128), (N, nw)))
-    theta = np.zeros((N, K))
-    bad = np.full(N, -1, dtype=np.int64)
-    rows, z_out, z0, step0 = [], [], 0.0, 0
-    for k, (L, n, db, g, al) in enumerate(spans):
-        db = np.array(np.broadcast_to(np.asarray(db, dtype=float), (N, K)))
-        r = integrate(b, db, z_max=L, n=n, save_every=save_every, gamma=g, alpha=al)
-        A = r["traj"].copy()
-        with np.errstate(all="ignore"):
-            if gauge:
-                A[:, :, 2::2] *= np.exp(-1j * theta)[:, None, :]
-            rows.append(A)
-            z_out.append(z0 + np.linspace(0.0, L, n + 1)[::save_every])
-            new = (bad < 0) & (r["first_bad_step"] >= 0)
-            bad[new] = r["first_bad_step"][new] + step0
-            z0, step0 = z0 + L, step0 + n
-            if k + 1 < len(spans):
-                b = r["a_end"] * np.asarray(transfers[k], dtype=np.complex128)
-                if gauge:
-                    b[:, 2::2] *= np.exp(1j * db * L)
-                    theta = theta + db * L
-    rows = np.concatenate(rows, axis=1)
-    with np.errstate(all="ignore"):
-        p = np.abs(rows) ** 2
-    return dict(rows=rows, a_end=rows[:, -1], p_wave_end=p[:, -1], p_wave_max=np.max(p, axis=1), first_bad_step=bad,
-                z_out=np.concatenate(z_out))
-
-
-def mid_stage(gain_db, phase):
-    """sqrt(10^(gain_db/10)) e^{i phase}, written out here so the restatement does not lean on the package."""
-    return np.sqrt(10.0 ** (np.asarray(gain_db, dtype=float) / 10.0)) * np.exp(1j * np.asarray(phase, dtype=float))
+MODEL = chain_np.Model(integrate=integrate, rhs=rhs_theta, gauged=slice(2, None, 2))
+direct = functools.partial(chain_np.direct, MODEL)
+chain = functools.partial(chain_np.chain, MODEL)
+mid_stage, subset = chain_np.mid_stage, chain_np.subset
 
 
 # ---- the cases of the issue, shared between the CPU and the GPU tests -----------------------------------------------------
@@ -163,13 +93,6 @@ def lossy_case(N, K, seed=11, steps=(600, 1000, 400), lengths=(300.0, 500.0, 200
     transfers = [mid_stage(rng.uniform(-3, 1, (N, nw)), rng.uniform(-np.pi, np.pi, (N, nw))),
                  mid_stage(rng.uniform(-2, 1, nw), rng.uniform(-np.pi, np.pi, nw))]
     return a0, spans, transfers
-
-
-def subset(case, idx):
-    """(a0, spans, transfers) of lossy_case cut to the points ``idx``."""
-    a0, spans, transfers = case
-    return (a0[idx], [(L, n, db[idx], g[idx], al[idx]) for L, n, db, g, al in spans],
-            [t[idx] if t.ndim == 2 else t for t in transfers])
 
 
 def mu_nu(dbeta, L, gamma, p1, p2):

@@ -8,22 +8,17 @@ tests/test_single_pump_chain_host.py and tests/test_gpu_single_pump_chain.py.
   are brought back to A with e^{-i Theta_s} on wave 1.  ``gauge=False`` leaves the boundary phase and the rotation out: the
   chain that forgot the gauge.
 
+Both are the span loop of tests/chain_np.py over this module's MODEL: its span integrator, its accumulated-phase right-hand
+side and the waves that carry the phase.
+
 spans: (length, n_steps, dbeta, gamma, alpha) per span, the last three a scalar or (N,); transfers: S-1 entries (3,) or (N, 3).
 """
+import functools
+
 import numpy as np
 
+import chain_np
 import single_pump_np
-
-
-def _points(a0, spans):
-    sizes = {np.size(v) for sp in spans for v in sp[2:]} | ({np.shape(a0)[0]} if np.ndim(a0) == 2 else set())
-    sizes.discard(1)
-    assert len(sizes) <= 1
-    return sizes.pop() if sizes else 1
-
-
-def _per_point(x, N):
-    return np.array(np.broadcast_to(np.asarray(x, dtype=float), (N,)))
 
 
 def rhs_theta(theta, a, gamma, alpha):
@@ -41,67 +36,10 @@ def rhs_theta(theta, a, gamma, alpha):
     return out
 
 
-def direct(a0, spans, transfers, save_every):
-    """-> rows (N, n_saved_total, 3) in the A frame: every span's row 0 (the post-transfer state) and a row after every
-    save_every-th step."""
-    N = _points(a0, spans)
-    y = np.array(np.broadcast_to(np.asarray(a0, dtype=np.complex128), (N, 3)))
-    theta0 = np.zeros(N)
-    rows = []
-    for k, (L, n, db, g, al) in enumerate(spans):
-        db, g, al = _per_point(db, N), _per_point(g, N), _per_point(al, N)
-        zg = np.linspace(0.0, L, n + 1)
-        rows.append(y.copy())
-        for i in range(n):
-            z, h = zg[i], zg[i + 1] - zg[i]
-            k1 = rhs_theta(theta0 + db * z, y, g, al)
-            k2 = rhs_theta(theta0 + db * (z + 0.5 * h), y + 0.5 * h * k1, g, al)
-            k3 = rhs_theta(theta0 + db * (z + 0.5 * h), y + 0.5 * h * k2, g, al)
-            k4 = rhs_theta(theta0 + db * (z + h), y + h * k3, g, al)
-            y = y + (h / 6.0) * (k1 + 2.0 * k2 + 2.0 * k3 + k4)
-            if (i + 1) % save_every == 0:
-                rows.append(y.copy())
-        if k + 1 < len(spans):
-            y = y * np.asarray(transfers[k], dtype=np.complex128)
-            theta0 = theta0 + db * L
-    return np.stack(rows, axis=1)
-
-
-def chain(a0, spans, transfers, save_every, gauge=True):
-    """-> dict(rows (N, n_saved_total, 3) A frame, a_end (N, 3), p_wave_end, p_wave_max (N, 3) over every saved row,
-    first_bad_step (N,) counted over the whole chain (first failure wins), z_out (n_saved_total,))."""
-    N = _points(a0, spans)
-    b = np.array(np.broadcast_to(np.asarray(a0, dtype=np.complex128), (N, 3)))
-    theta = np.zeros(N)
-    bad = np.full(N, -1, dtype=np.int64)
-    rows, z_out, z0, step0 = [], [], 0.0, 0
-    for k, (L, n, db, g, al) in enumerate(spans):
-        db = _per_point(db, N)
-        r = single_pump_np.integrate(b, db, z_max=L, n=n, save_every=save_every, gamma=g, alpha=al, want_traj=True)
-        A = r["traj"].copy()
-        if gauge:
-            A[:, :, 1] *= np.exp(-1j * theta)[:, None]
-        rows.append(A)
-        z_out.append(z0 + np.linspace(0.0, L, n + 1)[::save_every])
-        new = (bad < 0) & (r["first_bad_step"] >= 0)
-        bad[new] = r["first_bad_step"][new] + step0
-        z0, step0 = z0 + L, step0 + n
-        if k + 1 < len(spans):
-            with np.errstate(all="ignore"):
-                b = r["a_end"] * np.asarray(transfers[k], dtype=np.complex128)
-                if gauge:
-                    b[:, 1] *= np.exp(1j * db * L)
-                    theta = theta + db * L
-    rows = np.concatenate(rows, axis=1)
-    with np.errstate(all="ignore"):
-        p = np.abs(rows) ** 2
-    return dict(rows=rows, a_end=rows[:, -1], p_wave_end=p[:, -1], p_wave_max=np.max(p, axis=1), first_bad_step=bad,
-                z_out=np.concatenate(z_out))
-
-
-def mid_stage(gain_db, phase):
-    """sqrt(10^(gain_db/10)) e^{i phase}, written out here so the restatement does not lean on the package."""
-    return np.sqrt(10.0 ** (np.asarray(gain_db, dtype=float) / 10.0)) * np.exp(1j * np.asarray(phase, dtype=float))
+MODEL = chain_np.Model(integrate=functools.partial(single_pump_np.integrate, want_traj=True), rhs=rhs_theta, gauged=1)
+direct = functools.partial(chain_np.direct, MODEL)
+chain = functools.partial(chain_np.chain, MODEL)
+mid_stage, subset = chain_np.mid_stage, chain_np.subset
 
 
 # ---- the two cases of the issue, shared between the CPU and the GPU tests -------------------------------------------------
@@ -148,10 +86,3 @@ def check_harmonics(gain, a, b):
     e0, e2 = abs(F[0].real / a - 1.0), abs(2.0 * abs(F[2]) / b - 1.0)
     rest = max(abs(F[j]) for j in range(1, F.size) if j != 2) / abs(F[0])
     return e0, e2, rest
-
-
-def subset(case, idx):
-    """(a0, spans, transfers) of lossy_case cut to the points ``idx``."""
-    a0, spans, transfers = case
-    return (a0[idx], [(L, n, db[idx], g[idx], al[idx]) for L, n, db, g, al in spans],
-            [t[idx] if t.ndim == 2 else t for t in transfers])

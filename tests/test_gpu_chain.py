@@ -20,6 +20,7 @@ from psa_amd.config import custom_simulation_config
 from psa_amd.phase_matching import PhaseMatchingConfig, PhaseMatchingMethod
 from psa_amd.simulation import mid_stage, run_concatenated_simulation, run_single_simulation
 from psa_amd.sweep import FibreSpan, rk4_chain, rk4_sweep
+from wave_family import rows, split
 
 pytestmark = pytest.mark.gpu
 
@@ -54,17 +55,6 @@ def test_one_span_is_the_sweep_bit_for_bit(dtype, layout, nw):
                 assert np.array_equal(got[key], ref[key], equal_nan=True), (key, extra)
 
 
-def _split(n, cuts, se):
-    steps = np.full(cuts, (n // se // cuts) * se)
-    steps[-1] = n - steps[:-1].sum()
-    return [int(s) for s in steps]
-
-
-def _rows(steps, se):
-    offs = np.concatenate([[0], np.cumsum(steps)[:-1]])
-    return np.concatenate([o // se + np.arange(s // se + 1) for o, s in zip(offs, steps)])
-
-
 @pytest.mark.parametrize("cuts", [2, 3, 7])
 @pytest.mark.parametrize("nw", [4, 6])
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
@@ -78,12 +68,12 @@ def test_identity_split_equals_the_unsplit_run(cuts, nw, dtype):
                       want_traj=True)
     whole_w = rk4_sweep(db, z_max=L, n_steps=n, save_every=se, gamma=gam, alpha=alp, a0=a0, dbeta2=d2, dtype=dtype,
                         wave_summary=True)
-    steps = _split(n, cuts, se)
+    steps = split(n, cuts, se)
     spans = [FibreSpan(L * s / n, n_steps=s, dbeta=db, gamma=gam, alpha=alp, dbeta2=d2) for s in steps]
     got = rk4_chain(spans, a0=a0, transfers=[np.ones(nw)] * (cuts - 1), save_every=se, dtype=dtype, want_traj=True)
     got_w = rk4_chain(spans, a0=a0, save_every=se, dtype=dtype, wave_summary=True)
     assert got.traj.shape == (n_pts, sum(s // se + 1 for s in steps), nw)
-    np.testing.assert_allclose(got.z_out, np.linspace(0, L, n + 1)[::se][_rows(steps, se)], rtol=1e-12, atol=1e-9)
+    np.testing.assert_allclose(got.z_out, np.linspace(0, L, n + 1)[::se][rows(steps, se)], rtol=1e-12, atol=1e-9)
     if dtype == np.float64:
         def close(a, b):
             return np.max(np.abs(a - b)) <= 1e-9 * np.max(np.abs(b))
@@ -93,7 +83,7 @@ def test_identity_split_equals_the_unsplit_run(cuts, nw, dtype):
             return np.all(np.max(np.abs(a - b), axis=1) <= 1e-4 * np.max(np.abs(b), axis=1))
     assert close(got.a_end, whole.a_end)
     assert close(got.p_max, whole.p_max) and close(got.p_end, whole.p_end)
-    assert close(got.traj, whole.traj[:, _rows(steps, se)])
+    assert close(got.traj, whole.traj[:, rows(steps, se)])
     assert close(got_w.p_wave_max, whole_w.p_wave_max) and close(got_w.p_wave_end, whole_w.p_wave_end)
     assert np.all(got.first_bad_step == -1)
 
@@ -166,7 +156,7 @@ def test_run_concatenated_simulation_matches_the_single_run_when_split():
     z2, A2 = run_concatenated_simulation([dict(span, cfg=custom_simulation_config(z_max=0.2, dz=1e-3)),
                                           dict(span, cfg=custom_simulation_config(z_max=0.3, dz=1e-3))],
                                          omega=om, p_in=p_in, phase_in=ph, length_unit="km")
-    idx = _rows([200, 300], 10)
+    idx = rows([200, 300], 10)
     np.testing.assert_allclose(z2, z1[idx], rtol=1e-12, atol=1e-12)
     assert np.max(np.abs(A2 - A1[idx]) / np.max(np.abs(A1), axis=0)) < 1e-9
 

@@ -15,23 +15,11 @@ import psa_amd._native as nat
 from conftest import RTOL_F64
 from psa_amd import config, dispersion, scan_mismtach, simulation, sweep
 from psa_amd.frequency_plan import omega_from_lambda
+from wave_family import COMB, KEYS, device_sweep, power_err, wave_err
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ("a_end", "p_wave_end", "p_wave_max", "first_bad_step")
 Z_MAX, N_STEPS = 300.0, 1500
-
-
-def wave_err(got, ref):
-    """max |got - ref| over the largest line of the point (amplitudes (N, ..., M) complex)."""
-    ref = np.asarray(ref)
-    scale = np.abs(ref).reshape(ref.shape[0], -1).max(axis=1).reshape((-1,) + (1,) * (ref.ndim - 1))
-    return float(np.max(np.abs(np.asarray(got) - ref) / scale))
-
-
-def power_err(got, ref):
-    """The same bar on a power summary (N, M): the lines' moduli sqrt(P_m) against the point's largest."""
-    return wave_err(np.sqrt(np.asarray(got)).astype(complex), np.sqrt(np.asarray(ref)).astype(complex))
 
 
 @functools.lru_cache(maxsize=None)
@@ -236,33 +224,6 @@ def test_a_failing_lane_leaves_its_wave_neighbours_untouched(M):
         assert np.isnan(bad[key][k].view(float)).all(), key
 
 
-def _device_run(torch, kappa, gamma, alpha, a0, *, n_steps, z_max, save_every, flags, traj_ld=None):
-    """psa_rk4_comb_f64_dev on torch buffers -> the host entry's dictionary (traj from a [rows][M][ld][2] buffer)."""
-    dev = torch.device("cuda:0")
-    N, M = kappa.shape
-    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)   # noqa: E731
-    d_k, d_g, d_al = t(kappa.T), t(np.atleast_1d(gamma)), t(np.atleast_1d(alpha))
-    d_a0 = t(a0.view(np.float64).reshape(N, 2 * M).T)
-    d_aend = torch.empty((2 * M, N), dtype=torch.float64, device=dev)
-    d_we, d_wm = torch.empty((M, N), dtype=torch.float64, device=dev), torch.empty((M, N), dtype=torch.float64, device=dev)
-    d_bad = torch.empty(N, dtype=torch.int64, device=dev)
-    rows = n_steps // save_every + 1
-    d_traj = None if traj_ld is None else torch.full((rows, M, traj_ld, 2), -7.0, dtype=torch.float64, device=dev)
-    nat.comb_device(stream=torch.cuda.current_stream().cuda_stream, n_lines=M, n_points=N, n_steps=n_steps, z_max=z_max,
-                    save_every=save_every, d_kappa_soa=d_k.data_ptr(), d_gamma=d_g.data_ptr(), d_alpha=d_al.data_ptr(),
-                    d_a0_soa=d_a0.data_ptr(), flags=flags, d_a_end_soa=d_aend.data_ptr(), d_p_wave_end_soa=d_we.data_ptr(),
-                    d_p_wave_max_soa=d_wm.data_ptr(), d_first_bad=d_bad.data_ptr(),
-                    d_traj_soa=(0 if d_traj is None else d_traj.data_ptr()))
-    torch.cuda.synchronize()
-    out = dict(a_end=np.ascontiguousarray(d_aend.cpu().numpy().T).view(np.complex128), p_wave_end=d_we.cpu().numpy().T,
-               p_wave_max=d_wm.cpu().numpy().T, first_bad_step=d_bad.cpu().numpy(), traj=None, pad=None)
-    if d_traj is not None:
-        full = d_traj.cpu().numpy()                                          # [rows][M][ld][2]
-        out["traj"] = np.ascontiguousarray(full[:, :, :N].transpose(2, 0, 1, 3)).view(np.complex128)[..., 0]
-        out["pad"] = full[:, :, N:]
-    return out
-
-
 @pytest.mark.parametrize("M", [5, 12])
 def test_device_entry_equals_the_host_entry_bit_for_bit(M):
     torch = pytest.importorskip("torch")
@@ -271,7 +232,7 @@ def test_device_entry_equals_the_host_entry_bit_for_bit(M):
     kw = dict(n_steps=500, z_max=100.0, save_every=10)
     host = nat.comb_host(kappa, gamma=gamma, alpha=1.15e-4, a0=a0, want_traj=True, **kw)
     flags = nat.BCAST_ALPHA | nat.OPT_CHECK_NAN
-    got = _device_run(torch, kappa, gamma, 1.15e-4, a0, flags=flags, traj_ld=N, **kw)
+    got = device_sweep(torch, COMB, kappa.shape[1], kappa, gamma, 1.15e-4, a0, flags=flags, traj_ld=N, **kw)
     for key in KEYS + ("traj",):
         assert np.array_equal(got[key], host[key]), key
 
@@ -286,8 +247,8 @@ def test_padded_trajectory_rows_equal_the_dense_ones():
     kappa, a0, gamma, alpha = comb_np.random_inputs(N, 3, 13)
     kw = dict(n_steps=5, z_max=2.5, save_every=2)
     flags = nat.OPT_CHECK_NAN
-    dense = _device_run(torch, kappa, gamma, alpha, a0, flags=flags, traj_ld=N, **kw)
-    padded = _device_run(torch, kappa, gamma, alpha, a0, flags=flags | nat.OPT_TRAJ_LD, traj_ld=ld, **kw)
+    dense = device_sweep(torch, COMB, kappa.shape[1], kappa, gamma, alpha, a0, flags=flags, traj_ld=N, **kw)
+    padded = device_sweep(torch, COMB, kappa.shape[1], kappa, gamma, alpha, a0, flags=flags | nat.OPT_TRAJ_LD, traj_ld=ld, **kw)
     host = nat.comb_host(kappa, gamma=gamma, alpha=alpha, a0=a0, want_traj=True, **kw)
     for key in KEYS + ("traj",):
         assert np.array_equal(dense[key], padded[key]) and np.array_equal(dense[key], host[key]), key

@@ -12,27 +12,26 @@ import pytest
 
 import comb_np
 import psa_amd._native as nat
+import wave_family
 from conftest import RTOL_F32
 from psa_amd import config, dispersion, scan_mismtach, sweep
+from wave_family import KEYS
 
 pytestmark = pytest.mark.gpu
 
 F32, C64 = np.float32, np.complex64
-KEYS = ("a_end", "p_wave_end", "p_wave_max", "first_bad_step")
 Z_MAX, N_STEPS = 300.0, 1500
 RESYNC = 16                      # psa_rk4_comb_pk_kernel.inc.h: COMB_PK_RESYNC, the seed interval shipped
 
 
 def wave_err(got, ref):
-    """max |got - ref| over the largest line of the point (amplitudes (N, ..., M) complex)."""
-    ref = np.asarray(ref)
-    scale = np.abs(ref).reshape(ref.shape[0], -1).max(axis=1).reshape((-1,) + (1,) * (ref.ndim - 1))
-    return float(np.max(np.abs(np.asarray(got, dtype=np.complex128) - ref) / scale))
+    """wave_family.wave_err of the float32 outputs, widened first."""
+    return wave_family.wave_err(np.asarray(got, dtype=np.complex128), ref)
 
 
 def power_err(got, ref):
-    """The same bar on a power summary (N, M): the lines' moduli sqrt(P_m) against the point's largest."""
-    return wave_err(np.sqrt(np.asarray(got, dtype=np.float64)).astype(complex), np.sqrt(np.asarray(ref)).astype(complex))
+    """wave_family.power_err of the float32 outputs, widened first: the moduli are formed in float64."""
+    return wave_family.power_err(np.asarray(got, dtype=np.float64), ref)
 
 
 def rounded_inputs(*args, **kw):

@@ -13,23 +13,11 @@ import single_pump_np
 from conftest import RTOL_F64
 from psa_amd import config, dispersion, scan_mismtach, simulation, sweep
 from single_pump_np import GAMMA, LENGTH, P_PUMP
+from wave_family import KEYS, SINGLE_PUMP, device_sweep, power_err, wave_err
 
 pytestmark = pytest.mark.gpu
 
 ALPHA = 1.15e-4
-KEYS = ("a_end", "p_wave_end", "p_wave_max", "first_bad_step")
-
-
-def wave_err(got, ref):
-    """max |got - ref| over the largest wave of the point (amplitudes (N, ..., 3) complex)."""
-    ref = np.asarray(ref)
-    scale = np.abs(ref).reshape(ref.shape[0], -1).max(axis=1).reshape((-1,) + (1,) * (ref.ndim - 1))
-    return float(np.max(np.abs(np.asarray(got) - ref) / scale))
-
-
-def power_err(got, ref):
-    """The same bar on a power summary (N, 3): the waves' moduli sqrt(P_j) against the point's largest."""
-    return wave_err(np.sqrt(np.asarray(got)).astype(complex), np.sqrt(np.asarray(ref)).astype(complex))
 
 
 def _inputs(N, seed, per_point, lossy):
@@ -279,33 +267,6 @@ def test_exact_index_equals_the_per_step_index(se):
         assert np.array_equal(got[key][~failed], blk[key][~failed]), key
 
 
-def _device_run(torch, dbeta, gamma, alpha, a0, *, n_steps, z_max, save_every, flags, traj_ld=None):
-    """psa_rk4_single_pump_f64_dev on torch buffers -> the host entry's dictionary (traj from a [rows][3][ld][2] buffer)."""
-    dev = torch.device("cuda:0")
-    N = dbeta.size
-    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)   # noqa: E731
-    d_db, d_g, d_al = t(dbeta), t(np.atleast_1d(gamma)), t(np.atleast_1d(alpha))
-    d_a0 = t(a0.view(np.float64).reshape(N, 6).T)
-    d_aend = torch.empty((6, N), dtype=torch.float64, device=dev)
-    d_we, d_wm = torch.empty((3, N), dtype=torch.float64, device=dev), torch.empty((3, N), dtype=torch.float64, device=dev)
-    d_bad = torch.empty(N, dtype=torch.int64, device=dev)
-    rows = n_steps // save_every + 1
-    d_traj = None if traj_ld is None else torch.full((rows, 3, traj_ld, 2), -7.0, dtype=torch.float64, device=dev)
-    nat.single_pump_device(stream=torch.cuda.current_stream().cuda_stream, n_points=N, n_steps=n_steps, z_max=z_max,
-                           save_every=save_every, d_dbeta=d_db.data_ptr(), d_gamma=d_g.data_ptr(), d_alpha=d_al.data_ptr(),
-                           d_a0_soa=d_a0.data_ptr(), flags=flags, d_a_end_soa=d_aend.data_ptr(),
-                           d_p_wave_end_soa=d_we.data_ptr(), d_p_wave_max_soa=d_wm.data_ptr(), d_first_bad=d_bad.data_ptr(),
-                           d_traj_soa=(0 if d_traj is None else d_traj.data_ptr()))
-    torch.cuda.synchronize()
-    out = dict(a_end=np.ascontiguousarray(d_aend.cpu().numpy().T).view(np.complex128), p_wave_end=d_we.cpu().numpy().T,
-               p_wave_max=d_wm.cpu().numpy().T, first_bad_step=d_bad.cpu().numpy(), traj=None, pad=None)
-    if d_traj is not None:
-        full = d_traj.cpu().numpy()                                          # [rows][3][ld][2]
-        out["traj"] = np.ascontiguousarray(full[:, :, :N].transpose(2, 0, 1, 3)).view(np.complex128)[..., 0]
-        out["pad"] = full[:, :, N:]
-    return out
-
-
 def test_device_entry_equals_the_host_entry_bit_for_bit():
     torch = pytest.importorskip("torch")
     N = 203
@@ -313,7 +274,7 @@ def test_device_entry_equals_the_host_entry_bit_for_bit():
     kw = dict(n_steps=1000, z_max=100.0, save_every=10)
     host = nat.single_pump_host(dbeta, gamma=gamma, alpha=ALPHA, a0=a0, want_traj=True, **kw)
     flags = nat.BCAST_ALPHA | nat.OPT_CHECK_NAN | nat.OPT_EXACT_STEP
-    got = _device_run(torch, dbeta, gamma, ALPHA, a0, flags=flags, traj_ld=N, **kw)
+    got = device_sweep(torch, SINGLE_PUMP, None, dbeta, gamma, ALPHA, a0, flags=flags, traj_ld=N, **kw)
     for key in KEYS + ("traj",):
         assert np.array_equal(got[key], host[key]), key
 
@@ -328,8 +289,8 @@ def test_padded_trajectory_rows_equal_the_dense_ones():
     dbeta, a0, gamma, alpha = _inputs(N, 13, True, True)
     kw = dict(n_steps=5, z_max=2.5, save_every=2)
     flags = nat.OPT_CHECK_NAN | nat.OPT_EXACT_STEP
-    dense = _device_run(torch, dbeta, gamma, alpha, a0, flags=flags, traj_ld=N, **kw)
-    padded = _device_run(torch, dbeta, gamma, alpha, a0, flags=flags | nat.OPT_TRAJ_LD, traj_ld=ld, **kw)
+    dense = device_sweep(torch, SINGLE_PUMP, None, dbeta, gamma, alpha, a0, flags=flags, traj_ld=N, **kw)
+    padded = device_sweep(torch, SINGLE_PUMP, None, dbeta, gamma, alpha, a0, flags=flags | nat.OPT_TRAJ_LD, traj_ld=ld, **kw)
     host = nat.single_pump_host(dbeta, gamma=gamma, alpha=alpha, a0=a0, want_traj=True, **kw)
     for key in KEYS + ("traj",):
         assert np.array_equal(dense[key], padded[key]) and np.array_equal(dense[key], host[key]), key

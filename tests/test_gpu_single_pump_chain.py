@@ -1,62 +1,29 @@
-"""Single-pump fibre chains on the GPU (psa_rk4_single_pump_chain_f64, sweep.rk4_chain_single_pump,
+"""Single-pump fibre chains on the GPU: what only this family has (psa_rk4_single_pump_chain_f64, sweep.rk4_chain_single_pump,
 simulation.run_concatenated_single_pump_simulation, scan_mismtach.scan_single_pump_copier_psa_phase) against the NumPy
-restatement tests/single_pump_chain_np.py at the project's bar RTOL_F64 (1e-9 of the point's largest wave):
+restatement tests/single_pump_chain_np.py at the project's bar RTOL_F64 (1e-9 of the point's largest wave).  What every
+wave-summary chain owes its caller is in tests/test_gpu_wave_chain.py.
 
 * one span is psa_rk4_single_pump_f64 bit for bit;
-* one fibre cut into 2, 3 and 7 spans with identity transfers is the unsplit sweep;
-* a lossy three-span chain with unequal dbeta, gamma, alpha, a per-point and a broadcast transfer: 300 points cross a
-  256-thread epilogue block and are no multiple of 64;
-* spans of 1, 63, 64, 65 and 130 steps in one chain (the kernel re-seeds its phase every 64 steps);
 * a failure in span 2 is reported at the chain's step index, and its NaN stays in the summaries and the gain;
-* the `_dev` entry on a caller's workspace of exactly the stated size and padded trajectory rows, bit-equal to the host form.
-  psa_traj_ld pads only where the wave regions lie a multiple of 2 MiB apart, so 300 points have ld == N; the padded leading
-  dimension is reached with 131 072 points on a 7-step chain;
-* devices=[0, 0] equals one device; the single-run form split against the unsplit run; the phase-scan driver against the
-  copier - PSA closed form and against a direct chain call."""
-import functools
-
+* the single-run form split against the unsplit run;
+* the phase-scan driver against the copier - PSA closed form and against a direct chain call."""
 import numpy as np
 import pytest
 
 import psa_amd._native as nat
 import single_pump_chain_np as chain_np
 from conftest import RTOL_F64
-from psa_amd import config, dispersion, scan_mismtach, simulation, sweep
-from psa_amd.sweep import FibreSpan, rk4_chain_single_pump, rk4_sweep_single_pump
+from psa_amd import config, dispersion, scan_mismtach, simulation
+from psa_amd.sweep import FibreSpan, rk4_chain_single_pump
+from wave_family import KEYS, fibre, power_err, rows, single_pump_inputs, wave_err
 
 pytestmark = pytest.mark.gpu
-
-KEYS = ("a_end", "p_wave_end", "p_wave_max", "first_bad_step")
-
-
-def wave_err(got, ref):
-    """max |got - ref| over the largest wave of the point (amplitudes (N, ..., 3) complex)."""
-    ref = np.asarray(ref)
-    scale = np.abs(ref).reshape(ref.shape[0], -1).max(axis=1).reshape((-1,) + (1,) * (ref.ndim - 1))
-    return float(np.max(np.abs(np.asarray(got) - ref) / scale))
-
-
-def power_err(got, ref):
-    """The same bar on a power summary (N, 3): the waves' moduli sqrt(P_j) against the point's largest."""
-    return wave_err(np.sqrt(np.asarray(got)).astype(complex), np.sqrt(np.asarray(ref)).astype(complex))
-
-
-def _fibre(spans):
-    return [FibreSpan(L, n_steps=n, dbeta=db, gamma=g, alpha=al) for L, n, db, g, al in spans]
-
-
-def _inputs(N, seed):
-    rng = np.random.default_rng(seed)
-    dbeta = rng.uniform(-4.5, 0.5, N) * 0.0115 * 0.5
-    p = np.column_stack([rng.uniform(0.3, 0.6, N), 10 ** rng.uniform(-8, -3, N), 10 ** rng.uniform(-8, -3, N)])
-    a0 = np.sqrt(p) * np.exp(1j * rng.uniform(-3, 3, (N, 3)))
-    return dbeta, a0, 0.0115 * rng.uniform(0.9, 1.1, N), 1.15e-4 * rng.uniform(0.5, 1.5, N)
 
 
 @pytest.mark.parametrize("want_traj", [True, False], ids=["traj", "summary"])
 def test_one_span_is_the_sweep_bit_for_bit(want_traj):
     n = 37
-    dbeta, a0, gamma, _ = _inputs(n, 1)
+    dbeta, a0, gamma, _ = single_pump_inputs(n, 1)
     kw = dict(save_every=10, a0=a0, want_traj=want_traj)
     ref = nat.single_pump_host(dbeta, n_steps=1000, z_max=100.0, gamma=gamma, alpha=1.15e-4, **kw)
     got = nat.single_pump_chain_host(dbeta[None], n_steps=[1000], seg_len=[100.0], gamma=gamma[None], alpha=[1.15e-4], **kw)
@@ -66,96 +33,6 @@ def test_one_span_is_the_sweep_bit_for_bit(want_traj):
         else:
             assert np.array_equal(got[key], ref[key], equal_nan=True), key
     assert got["first_bad_step"].shape == (n,) and (got["traj"] is not None) == want_traj
-
-
-def _split(n, cuts, se):
-    steps = np.full(cuts, (n // se // cuts) * se)
-    steps[-1] = n - steps[:-1].sum()
-    return [int(s) for s in steps]
-
-
-def _rows(steps, se):
-    offs = np.concatenate([[0], np.cumsum(steps)[:-1]])
-    return np.concatenate([o // se + np.arange(s // se + 1) for o, s in zip(offs, steps)])
-
-
-@functools.lru_cache(maxsize=None)
-def _unsplit():
-    n_pts, n, L, se = 33, 1400, 700.0, 10
-    dbeta, a0, gamma, alpha = _inputs(n_pts, 2)
-    whole = rk4_sweep_single_pump(dbeta, z_max=L, n_steps=n, save_every=se, gamma=gamma, alpha=alpha, a0=a0, want_traj=True)
-    return dbeta, a0, gamma, alpha, whole
-
-
-@pytest.mark.parametrize("cuts", [2, 3, 7])
-def test_identity_split_equals_the_unsplit_run(cuts):
-    n_pts, n, L, se = 33, 1400, 700.0, 10
-    dbeta, a0, gamma, alpha, whole = _unsplit()
-    steps = _split(n, cuts, se)
-    spans = [FibreSpan(L * s / n, n_steps=s, dbeta=dbeta, gamma=gamma, alpha=alpha) for s in steps]
-    got = rk4_chain_single_pump(spans, a0=a0, transfers=[np.ones(3)] * (cuts - 1), save_every=se, want_traj=True)
-    assert got.traj.shape == (n_pts, sum(s // se + 1 for s in steps), 3) and got.n_steps == n
-    np.testing.assert_allclose(got.z_out, np.linspace(0, L, n + 1)[::se][_rows(steps, se)], rtol=1e-12, atol=1e-9)
-
-    def err(a, b):
-        return float(np.max(np.abs(a - b)) / np.max(np.abs(b)))
-    errs = dict(a_end=err(got.a_end, whole.a_end), p_wave_end=err(got.p_wave_end, whole.p_wave_end),
-                p_wave_max=err(got.p_wave_max, whole.p_wave_max), rows=err(got.traj, whole.traj[:, _rows(steps, se)]))
-    print(f"{cuts} spans against the unsplit sweep: " + " ".join(f"{k} {v:.2e}" for k, v in errs.items()))
-    assert max(errs.values()) < RTOL_F64
-    assert np.all(got.first_bad_step == -1)
-    # without the trajectory the summaries are the same numbers
-    lean = rk4_chain_single_pump(spans, a0=a0, save_every=se)
-    for key in KEYS:
-        assert np.array_equal(getattr(lean, key), getattr(got, key)), key
-    assert lean.traj is None
-
-
-@functools.lru_cache(maxsize=None)
-def _lossy_reference():
-    """300 points through the restatement once, every step saved; any save stride is read off the rows."""
-    case = chain_np.lossy_case(300)
-    ref = chain_np.chain(*case, 1)
-    assert (ref["first_bad_step"] == -1).all()
-    return case, ref["rows"], ref["z_out"]
-
-
-def _strided(rows, z_out, steps, se):
-    """Rows of a chain saved every ``se`` steps, out of the rows saved at every step."""
-    offs = np.concatenate([[0], np.cumsum(np.asarray(steps) + 1)[:-1]])
-    idx = np.concatenate([o + np.arange(0, s + 1, se) for o, s in zip(offs, steps)])
-    return rows[:, idx], z_out[idx]
-
-
-@pytest.mark.parametrize("save_every", [1, 20])
-def test_lossy_chain_with_transfers_against_the_restatement(save_every):
-    (a0, spans, transfers), rows, z_all = _lossy_reference()
-    want, z_want = _strided(rows, z_all, [n for _, n, *_ in spans], save_every)
-    got = rk4_chain_single_pump(_fibre(spans), a0=a0, transfers=transfers, save_every=save_every, want_traj=True)
-    assert got.traj.shape == want.shape
-    errs = (wave_err(got.traj, want), wave_err(got.a_end, want[:, -1]), power_err(got.p_wave_end, np.abs(want[:, -1]) ** 2),
-            power_err(got.p_wave_max, np.max(np.abs(want) ** 2, axis=1)))
-    print(f"lossy 3-span chain, 300 points, save_every={save_every}: rows {errs[0]:.2e} a_end {errs[1]:.2e} "
-          f"p_wave_end {errs[2]:.2e} p_wave_max {errs[3]:.2e}")
-    assert max(errs) < RTOL_F64
-    np.testing.assert_allclose(got.z_out, z_want, rtol=1e-14, atol=0.0)
-    assert np.all(got.first_bad_step == -1) and np.array_equal(got.traj[:, -1], got.a_end)
-    assert np.array_equal(got.row_offsets, np.concatenate([[0], np.cumsum([n // save_every + 1 for _, n, *_ in spans])]))
-
-
-def test_loop_edges_in_one_chain():
-    """Spans of 1, 63, 64, 65 and 130 steps, every step saved, per-point transfers between them."""
-    N, steps = 70, (1, 63, 64, 65, 130)
-    rng = np.random.default_rng(5)
-    _, a0, _, _ = _inputs(N, 6)
-    spans = [(0.5 * n, n, rng.uniform(-4.5, 0.5, N) * 0.0115 * 0.5, 0.0115 * rng.uniform(0.9, 1.3, N),
-              1.15e-4 * rng.uniform(0.0, 2.0, N)) for n in steps]
-    transfers = [chain_np.mid_stage(rng.uniform(-2, 1, (N, 3)), rng.uniform(-np.pi, np.pi, (N, 3))) for _ in steps[1:]]
-    ref = chain_np.chain(a0, spans, transfers, 1)
-    got = rk4_chain_single_pump(_fibre(spans), a0=a0, transfers=transfers, save_every=1, want_traj=True)
-    errs = (wave_err(got.traj, ref["rows"]), wave_err(got.a_end, ref["a_end"]), power_err(got.p_wave_max, ref["p_wave_max"]))
-    print(f"loop edges: rows {errs[0]:.2e} a_end {errs[1]:.2e} p_wave_max {errs[2]:.2e}")
-    assert got.traj.shape == (N, sum(steps) + len(steps), 3) and max(errs) < RTOL_F64 and np.all(got.first_bad_step == -1)
 
 
 def test_first_bad_step_of_a_failure_in_span_two_is_cumulative():
@@ -170,10 +47,10 @@ def test_first_bad_step_of_a_failure_in_span_two_is_cumulative():
     spans = [(40.0, 400, db, 0.0115, 1e-4), (60.0, 600, db, gam2, 0.0)]
     ref = chain_np.chain(a0, spans, [np.ones(3)], 10)
     assert np.array_equal(ref["first_bad_step"], [-1, 401, -1, 401, -1])
-    got = rk4_chain_single_pump(_fibre(spans), a0=a0, transfers=[np.ones(3)], save_every=10, exact_step=True)
+    got = rk4_chain_single_pump(fibre(spans), a0=a0, transfers=[np.ones(3)], save_every=10, exact_step=True)
     third = spans + [(10.0, 100, db, 0.0115, 0.0)]
     tr3 = [np.ones(3), simulation.single_pump_mid_stage((-1.0, -3.0, 0.5), (0.4, 1.0, -2.0))]
-    got3 = rk4_chain_single_pump(_fibre(third), a0=a0, save_every=10, exact_step=True, transfers=tr3)
+    got3 = rk4_chain_single_pump(fibre(third), a0=a0, save_every=10, exact_step=True, transfers=tr3)
     for r in (got, got3):
         np.testing.assert_array_equal(r.first_bad_step, [-1, 401, -1, 401, -1])
         assert np.all(np.isnan(r.p_wave_max[[1, 3]])) and np.all(np.isfinite(r.p_wave_max[[0, 2, 4]]))
@@ -190,73 +67,6 @@ def test_first_bad_step_of_a_failure_in_span_two_is_cumulative():
     assert max(errs) < RTOL_F64
 
 
-def _device_chain(torch, a0, spans, transfers, *, save_every, flags, ld):
-    """psa_rk4_single_pump_chain_f64_dev on torch buffers with a workspace of exactly the stated size (and a guard behind it)
-    -> the host entry's dictionary, the trajectory's padding and the guard."""
-    dev = torch.device("cuda:0")
-    N, S = a0.shape[0], len(spans)
-    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)   # noqa: E731
-    d_db, d_g, d_al = (t(np.stack([sp[k] for sp in spans])) for k in (2, 3, 4))
-    d_a0 = t(a0.view(np.float64).reshape(N, 6).T)
-    tr = np.stack([np.broadcast_to(x, (N, 3)) for x in transfers])                       # (S-1, N, 3)
-    d_tr = t(np.ascontiguousarray(tr).view(np.float64).reshape(S - 1, N, 6).transpose(0, 2, 1))
-    d_aend = torch.empty((6, N), dtype=torch.float64, device=dev)
-    d_we, d_wm = torch.empty((3, N), dtype=torch.float64, device=dev), torch.empty((3, N), dtype=torch.float64, device=dev)
-    d_bad = torch.empty(N, dtype=torch.int64, device=dev)
-    steps = [sp[1] for sp in spans]
-    rows = sum(n // save_every + 1 for n in steps)
-    d_traj = torch.full((rows, 3, ld, 2), -7.0, dtype=torch.float64, device=dev)
-    ws_bytes = nat.single_pump_chain_workspace_bytes(N)
-    d_ws = torch.full((ws_bytes + 4096,), 0x5A, dtype=torch.uint8, device=dev)
-    nat.single_pump_chain_device(stream=torch.cuda.current_stream().cuda_stream, n_points=N, n_steps=steps,
-                                 seg_len=[sp[0] for sp in spans], save_every=save_every, d_dbeta=d_db.data_ptr(),
-                                 d_gamma=d_g.data_ptr(), d_alpha=d_al.data_ptr(), d_a0_soa=d_a0.data_ptr(),
-                                 d_transfer_soa=d_tr.data_ptr(), flags=flags, d_a_end_soa=d_aend.data_ptr(),
-                                 d_p_wave_end_soa=d_we.data_ptr(), d_p_wave_max_soa=d_wm.data_ptr(),
-                                 d_first_bad=d_bad.data_ptr(), d_traj_soa=d_traj.data_ptr(), d_workspace=d_ws.data_ptr())
-    torch.cuda.synchronize()
-    full = d_traj.cpu().numpy()                                                          # [rows][3][ld][2]
-    return dict(a_end=np.ascontiguousarray(d_aend.cpu().numpy().T).view(np.complex128), p_wave_end=d_we.cpu().numpy().T,
-                p_wave_max=d_wm.cpu().numpy().T, first_bad_step=d_bad.cpu().numpy(),
-                traj=np.ascontiguousarray(full[:, :, :N].transpose(2, 0, 1, 3)).view(np.complex128)[..., 0],
-                pad=full[:, :, N:], guard=d_ws[ws_bytes:].cpu().numpy())
-
-
-@pytest.mark.parametrize("N,steps,lengths", [(300, (60, 100, 40), (300.0, 500.0, 200.0)), (131072, (2, 3, 2), (1.0, 1.5, 1.0))],
-                         ids=["300", "131072-padded"])
-def test_device_entry_equals_the_host_entry_bit_for_bit(N, steps, lengths):
-    """PSA_OPT_TRAJ_LD on the `_dev` form: ld = psa_traj_ld(N, 8), which is N for 300 points and N + 272 for 131 072.  The
-    padding and the bytes behind the workspace are never written; a handful of the padded case's points also go against
-    the restatement, which an epilogue that ignored the leading dimension would miss."""
-    import torch
-    se = 20 if N == 300 else 1
-    ld = nat.traj_ld(N)
-    assert ld == (N if N == 300 else N + 272)
-    case = chain_np.lossy_case(N, steps=steps, lengths=lengths)
-    a0, spans, transfers = case
-    host = nat.single_pump_chain_host(np.stack([sp[2] for sp in spans]), n_steps=steps, seg_len=lengths, save_every=se,
-                                      gamma=np.stack([sp[3] for sp in spans]), alpha=np.stack([sp[4] for sp in spans]), a0=a0,
-                                      transfers=np.stack([np.broadcast_to(x, (N, 3)) for x in transfers]), want_traj=True)
-    got = _device_chain(torch, a0, spans, transfers, save_every=se, flags=nat.OPT_CHECK_NAN | nat.OPT_EXACT_STEP | nat.OPT_TRAJ_LD,
-                        ld=ld)
-    for key in KEYS + ("traj",):
-        assert np.array_equal(got[key], host[key]), key
-    assert np.all(got["pad"] == -7.0) and np.all(got["guard"] == 0x5A)
-    idx = np.array([0, 1, 63, 64, 255, 256, N // 2, N - 2, N - 1])
-    ref = chain_np.chain(*chain_np.subset(case, idx), se)
-    assert wave_err(got["traj"][idx], ref["rows"]) < RTOL_F64 and power_err(got["p_wave_max"][idx], ref["p_wave_max"]) < RTOL_F64
-
-
-def test_two_devices_equal_one():
-    a0, spans, transfers = chain_np.lossy_case(41, steps=(60, 100, 40))
-    kw = dict(a0=a0, transfers=transfers, save_every=20, want_traj=True)
-    one = rk4_chain_single_pump(_fibre(spans), **kw)
-    two = rk4_chain_single_pump(_fibre(spans), devices=[0, 0], **kw)
-    for key in KEYS + ("traj",):
-        assert np.array_equal(getattr(one, key), getattr(two, key)), key
-    assert one.traj.shape == (41, 4 + 6 + 3, 3)
-
-
 def test_single_run_form_split_against_the_unsplit_run(golden):
     dv = golden("G11")["disp_m"]
     d = dispersion.DispersionParams(omega_ref=dv[0], beta2=dv[1], beta3=dv[2], beta4=dv[3])
@@ -267,7 +77,7 @@ def test_single_run_form_split_against_the_unsplit_run(golden):
     z2, A2 = simulation.run_concatenated_single_pump_simulation(
         [dict(fibre, cfg=config.custom_simulation_config(z_max=0.2, dz=1e-3)),
          dict(fibre, cfg=config.custom_simulation_config(z_max=0.3, dz=1e-3))], **kw)
-    idx = _rows([200, 300], 10)
+    idx = rows([200, 300], 10)
     np.testing.assert_allclose(z2, z1[idx], rtol=1e-12, atol=1e-12)
     err = float(np.max(np.abs(A2 - A1[idx]) / np.max(np.abs(A1), axis=0)))
     print(f"split 200 + 300 steps against the unsplit run: {err:.2e}")

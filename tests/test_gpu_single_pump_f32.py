@@ -1,7 +1,7 @@
 """The float32 single-pump sweep on the GPU (psa_rk4_single_pump_f32: two sweep points per lane, packed math) against the
 float64 NumPy restatement tests/single_pump_np.py fed the float32-ROUNDED inputs (dbeta, gamma, alpha and a0 are rounded to
 float32 / complex64 first and then widened, so input rounding is not counted), at the project's bar RTOL_F32 (1e-4 of the
-point's largest wave) with the wave_err / power_err measures of tests/test_gpu_single_pump.py.
+point's largest wave) with the wave_err / power_err measures of tests/wave_family.py.
 
 Shapes are the smallest that can go wrong: 203 points are one full packed wave (128 points), a partial one and an odd tail;
 1 500 steps are no multiple of RESYNC = 16; 65 541 points are 513 packed waves, the first size that takes 256-thread
@@ -18,11 +18,10 @@ import single_pump_np
 from conftest import RTOL_F32
 from psa_amd import config, dispersion, scan_mismtach, sweep
 from single_pump_np import GAMMA, LENGTH
-from test_gpu_single_pump import _inputs, power_err, wave_err
+from test_gpu_single_pump import _inputs
+from wave_family import KEYS, power_err, wave_err
 
 pytestmark = pytest.mark.gpu
-
-KEYS = ("a_end", "p_wave_end", "p_wave_max", "first_bad_step")
 
 
 def _bits(a):
