@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Developer probe: device dbeta producer vs the host NumPy producer on a large random grid (how often are they bit-equal,
-how far apart at worst).  The host array path itself is within an ulp of the reference's scalar path (array pow)."""
+how far apart at worst).  The host array path itself is within an ulp of the reference's scalar path (array pow).
+The pass/fail versions, against exact arithmetic instead of one float64 path against another, are
+tests/test_gpu_dbeta_exact.py (a 64 x 64 cut of the wide grid below included) and tests/test_dbeta_exact_host.py."""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
