@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "psa_launch_rules.h"
+
 namespace psa {
 
 // Everything one sweep launch needs; passed by value as the kernel argument.
@@ -116,37 +118,28 @@ struct CombArgs {
     long long a0_ld;
 };
 
-enum CheckMode : int { CHECK_NONE = 0, CHECK_BLOCK = 1, CHECK_EXACT = 2 };
-
-// Sweep launchers (psa_rk4_f64.hip / psa_rk4_f32.hip): one kernel launch on s, nothing for n_points == 0.  They own
-// every launch-related PSA_OPT_* bit of `flags` (check mode, LDS staging, block size, LOSSLESS, the float64 lane layout,
-// float32 packing) and take the trajectory from a.traj and the per-wave summary from a.p_wave_end being non-null.  The
-// caller has validated the arguments (the per-wave summary: no trajectory, no LDS staging, no BLOCK64).
+// ---- sweep launchers: one kernel launch on s, nothing for n_points == 0; the caller has validated the arguments.  What they
+// share is stated once: the rules (check mode, workgroup size, grid, LDS bytes; CheckMode) in psa_launch_rules.h, the dispatch
+// and the launch in psa_launch.inc.h.  All take the trajectory from a.traj being non-null.
+int simd_count(hipStream_t s);   // SIMDs (4 per CU) of the device a launch on s goes to, cached per device (psa_rk4_f64.hip)
+// 4/6 waves: they own every launch-related PSA_OPT_* bit of `flags` (check mode, LDS staging, block size, LOSSLESS, the float64
+// lane layout, float32 packing); the per-wave summary comes from a.p_wave_end being non-null (then no trajectory, LDS staging
+// or BLOCK64).  256-thread workgroups unless BLOCK64 or LDS staging asks for 64; the two- and four-lane layouts take the rule.
 hipError_t launch_sweep_f64(hipStream_t s, int n_waves, uint32_t flags, const SweepArgs<double> &a);
 hipError_t launch_sweep_f32(hipStream_t s, int n_waves, uint32_t flags, const SweepArgs<float> &a);
-// Multi-channel sweep launcher (psa_rk4_pairs.hip): one launch on s of L * n_points lanes, L = pairs_lanes_per_point;
-// nothing for n_points == 0.  Reads PSA_OPT_CHECK_NAN / EXACT_STEP / LOSSLESS / BLOCK64 of `flags` and takes the trajectory
-// from a.traj being non-null; the caller has validated the arguments (1 <= n_pairs <= 16, the lanes fit the launch grid, with
-// a trajectory traj_ld * 16 < 2^32).
-int pairs_lanes_per_point(int n_pairs);
+// Multi-channel: pairs_lanes_per_point(n_pairs) * n_points lanes.  Reads CHECK_NAN / EXACT_STEP / LOSSLESS / BLOCK64; with a
+// trajectory the workgroup is 256 whatever BLOCK64 says (1 <= n_pairs <= 16, the lanes fit the grid, traj_ld * 16 < 2^32).
 hipError_t launch_sweep_pairs_f64(hipStream_t s, uint32_t flags, const PairsArgs &a);
-// Single-pump sweep launchers (psa_rk4_single_pump.hip: one lane per point; psa_rk4_single_pump_f32.hip: two points per lane):
-// one launch on s, nothing for n_points == 0.  They read PSA_OPT_CHECK_NAN / EXACT_STEP / LOSSLESS / BLOCK64 of `flags` (float32
-// has one register layout: LOSSLESS selects nothing there) and take the trajectory from a.traj being non-null; the caller has
-// validated the arguments (with a trajectory, traj_ld * 16 < 2^32 in float64 and traj_ld * 8 < 2^31 in float32).
+// Single pump, one lane per point / two float32 points per lane.  They read CHECK_NAN / EXACT_STEP / LOSSLESS / BLOCK64
+// (float32 has one register layout: LOSSLESS selects nothing); traj_ld * 16 < 2^32 in float64, traj_ld * 8 < 2^31 in float32.
 hipError_t launch_sweep_single_pump_f64(hipStream_t s, uint32_t flags, const SinglePumpArgs<double> &a);
 hipError_t launch_sweep_single_pump_f32(hipStream_t s, uint32_t flags, const SinglePumpArgs<float> &a);
-// SIMDs (4 per CU) of the device a launch on s goes to (psa_rk4_single_pump.hip): what both launchers size their workgroups by
-int single_pump_simd_count(hipStream_t s);
-// Multi-line sweep launchers (psa_rk4_comb.hip: one lane per point; psa_rk4_comb_f32.hip: two points per lane): one launch on
-// s, nothing for n_points == 0.  They read PSA_OPT_CHECK_NAN (the test runs after every step: PSA_OPT_EXACT_STEP selects
-// nothing), LOSSLESS (float32 has one register layout: it selects nothing there) and BLOCK64 of `flags` and take the trajectory
-// from a.traj being non-null; the caller has validated the arguments (3 <= n_lines <= PSA_MAX_LINES, with a trajectory
-// traj_ld * 16 < 2^32 in float64 and traj_ld * 8 < 2^31 in float32).
+// Multi-line, lanes as the single pump.  They read CHECK_NAN as a bool (the test runs after every step: EXACT_STEP selects
+// nothing), LOSSLESS (nothing in float32) and BLOCK64 and pass the dynamic LDS bytes of their M and workgroup
+// (3 <= n_lines <= PSA_MAX_LINES; trajectory bounds as the single pump).
 hipError_t launch_sweep_comb_f64(hipStream_t s, uint32_t flags, const CombArgs<double> &a);
 hipError_t launch_sweep_comb_f32(hipStream_t s, uint32_t flags, const CombArgs<float> &a);
-// Adaptive sweep launcher (psa_rk45.hip): one launch on s, nothing for n_points == 0; PSA_OPT_LOSSLESS is the only flag
-// it reads and the dense-output rows come from a.traj being non-null.  The caller has validated the arguments.
+// Adaptive (psa_rk45.hip): LOSSLESS is the only flag it reads; the workgroup is the rule without BLOCK64.
 hipError_t launch_rk45_sweep_f64(hipStream_t s, int n_waves, uint32_t flags, const AdaptiveArgs<double> &a);
 
 // aux kernels (psa_aux.hip)

@@ -8,13 +8,14 @@
 //   * controller: SAFETY 0.9, factor in [0.2, 10], exponent -1/5, factor <= 1 after a rejection in the same step,
 //     h clamped to [10 * ulp(z), h_max] at the start of every step; a NaN error norm is a rejection by 0.2, so a
 //     non-finite state ends with status 1 (step below the minimum) exactly as scipy's solver fails;
-//   * the RHS is yaman_stage<double, NW, false, LOSS> (psa_rk4_kernel.inc.h) with 2*gamma*exp(i dbeta z) from an exact
+//   * the RHS is yaman_stage<double, NW, false, LOSS> (psa_rk4_stage.inc.h) with 2*gamma*exp(i dbeta z) from an exact
 //     sincos at every stage's own z (5 per attempt and pair: stage 7 shares stage 6's z).
 // Lanes run independent step counts.  The loop body is the same for an accepted and a rejected attempt: y, z, the FSAL
 // vector and the step are chosen with selects, and only the dense-output row stores and the loop exit diverge.  An
 // attempt costs 6 RHS evaluations (64 DP instructions each for 4 waves), the stage combinations, 5 sincos per pair and
 // the error norm; DESIGN.md has the count.  max_steps (accepted + rejected attempts) bounds every lane's loop.
-#include "psa_rk4_kernel.inc.h"
+#include "psa_launch.inc.h"
+#include "psa_rk4_stage.inc.h"
 
 namespace psa {
 namespace {
@@ -279,23 +280,13 @@ __global__ void __launch_bounds__(256) rk45_sweep_kernel(const AdaptiveArgs<doub
 
 }  // namespace
 
-// 64-thread workgroups while the sweep's waves fit half the SIMDs, 256 beyond (as launch_sweep_f64)
+// Its own: no flag but LOSSLESS is read, so the workgroup size is the shared rule without BLOCK64; the kernel takes either size
 hipError_t launch_rk45_sweep_f64(hipStream_t s, int n_waves, uint32_t flags, const AdaptiveArgs<double> &a) {
-    if (a.n_points == 0) return hipSuccess;
-    int dev = 0, cus = 256;
-    if (s == nullptr || hipStreamGetDevice(s, &dev) != hipSuccess) (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    const long long waves = (a.n_points + 63) / 64;
-    const int block = 2 * waves <= 4LL * cus ? 64 : 256;
-    const dim3 grid((unsigned)((a.n_points + block - 1) / block));
-    const bool rows = a.traj != nullptr, lossless = (flags & PSA_OPT_LOSSLESS) != 0;
+    const int block = workgroup_size(0, a.n_points, simd_count(s));
     return with_int<4, 6>(n_waves, [&](auto nw) {
-    return with_bool(lossless, [&](auto ll) {
-    return with_bool(rows, [&](auto rw) {
-        const void *k = reinterpret_cast<const void *>(rk45_sweep_kernel<nw, !ll, rw>);
-        void *args[] = {const_cast<AdaptiveArgs<double> *>(&a)};
-        (void)hipLaunchKernel(k, grid, dim3(block), args, 0, s);
-        return hipGetLastError();
+    return with_bool((flags & PSA_OPT_LOSSLESS) != 0, [&](auto ll) {
+    return with_bool(a.traj != nullptr, [&](auto rw) {
+        return launch_lanes(reinterpret_cast<const void *>(rk45_sweep_kernel<nw, !ll, rw>), a.n_points, block, 0, a, s);
     }); }); });
 }
 

@@ -36,7 +36,10 @@
 //    disabled).  It is reached as `bad < 0 && nonfinite_on(y)`: `bad` is written only from results of nonfinite_on, which
 //    are the same in every lane of a point, so the lanes of a point skip or run an exchange together.
 #pragma once
-#include "psa_rk4_kernel.inc.h"
+#include <type_traits>
+
+#include "psa_internal.h"
+#include "psa_rk4_prims.inc.h"
 
 namespace psa {
 

@@ -35,7 +35,8 @@
 //
 // Out of scope: RK45, lane-group layouts, process-group sharding, non-uniform grids.  (Float32: psa_rk4_comb_pk_kernel.inc.h.)
 #pragma once
-#include "psa_rk4_kernel.inc.h"
+#include "psa_launch.inc.h"
+#include "psa_rk4_prims.inc.h"
 
 namespace psa {
 
@@ -97,10 +98,6 @@ __device__ __forceinline__ void comb_stage(const double (&a)[2 * M], const doubl
 struct CombConsts {
     double hd, g_d, ha_d, g_h, ha_h;   // h; gamma and -alpha/2 times d = h/2 (stages 1, 2, 4) and times h (stage 3)
 };
-
-// Where the registers (256 VGPRs + 256 AGPRs at one wave per SIMD) do not hold the whole state without scratch memory, the
-// rotators live in LDS: 16 M bytes per lane, which the launcher passes as the dynamic LDS size.
-constexpr bool comb_rotators_in_lds(const int m) { return m >= 10; }
 
 // One RK4 step; u enters at z_step and leaves rotated to z_step + h.  rotator(m, c, s) delivers exp(i kappa_m h/2).
 template <int M, bool LOSS, typename Rotator>

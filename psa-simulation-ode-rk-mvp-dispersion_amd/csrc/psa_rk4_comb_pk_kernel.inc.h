@@ -31,7 +31,8 @@
 //
 // Out of scope: a lossless instantiation, a scalar (one point per lane) kernel, chains, RK45, lane-group layouts.
 #pragma once
-#include "psa_rk4_pk_kernel.inc.h"
+#include "psa_launch.inc.h"
+#include "psa_rk4_pk_frame.inc.h"
 
 namespace psa {
 
@@ -40,10 +41,6 @@ namespace psa {
 #define PSA_COMB_F32_RESYNC Phase<float>::RESYNC
 #endif
 constexpr int COMB_PK_RESYNC = PSA_COMB_F32_RESYNC;
-
-// 2M-vectors of f32x2 the lane keeps in LDS instead of registers: 0 none, 1 the rotators, 2 and dl, 3 and yb.  16 M bytes per
-// vector and lane, which the launcher passes as the dynamic LDS size (M = 12, 256 threads, 3 vectors: 144 KiB).
-constexpr int comb_pk_lds_vectors(const int m) { return m >= 10 ? 3 : (m >= 8 ? 1 : 0); }
 
 // k = dA/dz of a = [Re A_0, Im A_0, ..., Re A_{M-1}, Im A_{M-1}] at u = (ur, ui); ha = -alpha/2.  Line m's (Re k_m, Im k_m) goes
 // to emit(m, ., .) as soon as it exists; a[2m] and a[2m + 1] are not read after it, so emit may overwrite them.

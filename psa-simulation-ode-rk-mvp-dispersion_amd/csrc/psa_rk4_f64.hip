@@ -7,8 +7,8 @@
 namespace psa {
 
 // SIMDs (4 per CU) of the device the launch goes to -- the stream's device, which need not be the thread's current one
-// (the _dev entry points take the caller's stream); cached per device ordinal.
-static int simd_count(hipStream_t s) {
+// (the _dev entry points take the caller's stream); cached per device ordinal.  Every sweep launcher sizes its workgroups by it.
+int simd_count(hipStream_t s) {
     static std::atomic<int> cache[64];
     int dev = -1;
     if (s == nullptr || hipStreamGetDevice(s, &dev) != hipSuccess) {
@@ -70,12 +70,7 @@ hipError_t launch_sweep_f64(hipStream_t s, int n_waves, uint32_t flags, const Sw
         if (n_waves == 4 && !p.traj && !p.lds && a.save_every == PSA_FIXED_ROW && a.n_steps >= PSA_FIXED_ROW) p.row = PSA_FIXED_ROW;
         return launch_family<OneLane<double>>(s, p, a);
     }
-    // 64-thread workgroups while the sweep's waves fit half the SIMDs (a sweep of few waves is spread over as many CUs as
-    // it has waves), 256 beyond (four waves per workgroup land on the four SIMDs of one CU: the placement that gives every
-    // wave its own SIMD when the sweep fills the chip -- 1 024 single-wave workgroups measured 12 % slower at N = 32 768
-    // because some SIMDs received two)
-    const long long waves = ((long long)lanes * a.n_points + 63) / 64;
-    p.block = ((flags & PSA_OPT_BLOCK64) || 2 * waves <= (long long)simds) ? 64 : 256;
+    p.block = workgroup_size(flags, (long long)lanes * a.n_points, simds);
     p.lossless = (flags & PSA_OPT_LOSSLESS) != 0;
     return lanes == 2 ? launch_family<SplitLanes>(s, p, a) : launch_family<QuadLanes>(s, p, a);
 }

@@ -46,13 +46,11 @@
 //
 // Out of scope: float32, LDS staging, RK45, a dedicated save_every == 1 loop.
 #pragma once
+#include "psa_launch.inc.h"
 #include "psa_rk4_carried.inc.h"
-#include "psa_rk4_quad_kernel.inc.h"
+#include "psa_rk4_prims.inc.h"
 
 namespace psa {
-
-constexpr int ROW_HALF_MIRROR = 0x141;   // row_half_mirror: lane i <-> 7 - i of each 8
-constexpr int ROW_MIRROR = 0x140;        // row_mirror: lane i <-> 15 - i of each 16
 
 // Sum of v over the L lanes of a point, the same bits in every one of them.  v must be the result of an fma or an add.
 template <int L> __device__ __forceinline__ double pairs_allreduce(double v) {

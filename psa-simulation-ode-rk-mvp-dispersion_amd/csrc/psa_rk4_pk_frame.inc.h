@@ -15,7 +15,7 @@
 // a piece is added: a kernel array that a lambda captures is no longer split into registers before inlining, so even the
 // order of two declarations can change the code.
 #pragma once
-#include "psa_rk4_kernel.inc.h"
+#include "psa_rk4_prims.inc.h"
 
 namespace psa {
 

@@ -14,6 +14,7 @@
 // to other code (store2 as a method: 2 VGPRs more in every one), and this unit's device code is held to the text it had before
 // the frame existed.
 #pragma once
+#include "psa_rk4_kernel.inc.h"
 #include "psa_rk4_pk_frame.inc.h"
 
 namespace psa {
@@ -100,7 +101,7 @@ __global__ void __launch_bounds__(BLOCK) rk4_sweep_pk_kernel(const SweepArgs<flo
 // Two float32 points per lane: register layout with the loss links only (no lossless form); the per-wave summary
 // without trajectory, in 256-thread workgroups.
 struct PackedPoints {
-    static long long lanes(long long n_points) { return (n_points + 1) / 2; }
+    static long long lanes(long long n_points) { return packed_lanes(n_points); }
     template <int NW, int CHECK, bool TRAJ, int BLOCK, bool LDS, bool LOSS, bool WSUM, int ROW = 0>
     static constexpr auto kernel() {
         if constexpr (ROW != 0 || LDS || !LOSS || (WSUM && (TRAJ || BLOCK != 256))) return nullptr;

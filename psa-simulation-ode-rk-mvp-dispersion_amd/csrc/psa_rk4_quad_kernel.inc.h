@@ -21,18 +21,10 @@
 // index by replay) are the shared ones of psa_rk4_carried.inc.h -- see that file; trajectory stores as rk4_sweep_kernel.
 #pragma once
 #include "psa_rk4_carried.inc.h"
+#include "psa_rk4_kernel.inc.h"
 #include "psa_rk4_split_kernel.inc.h"
 
 namespace psa {
-
-template <int CTRL> __device__ __forceinline__ double quad_xchg(const double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-constexpr int QUAD_PAIR = 0xB1;    // quad_perm:[1,0,3,2]: the pair partner
-constexpr int QUAD_OTHER = 0x4E;   // quad_perm:[2,3,0,1]: the same role in the other pair
 
 // (ox, oy) = (bx, by) + c * dA/dz of the lane's wave (stage coefficient c folded into g, tg, ha, E as in yaman_stage)
 template <bool LOSS>

@@ -33,6 +33,7 @@
 // save_every == 1 trajectory loop (every stride goes through the event loop).  Float32 is
 // psa_rk4_single_pump_pk_kernel.inc.h.
 #pragma once
+#include "psa_launch.inc.h"
 #include "psa_rk4_carried.inc.h"
 
 namespace psa {

@@ -31,7 +31,8 @@
 //
 // Out of scope: a lossless instantiation, a mirrored / lane-pair variant, a save_every == 1 fast loop, chains, RK45.
 #pragma once
-#include "psa_rk4_pk_kernel.inc.h"
+#include "psa_launch.inc.h"
+#include "psa_rk4_pk_frame.inc.h"
 
 namespace psa {
 

@@ -24,6 +24,7 @@
 // rk4_sweep_kernel on its even lanes (see the kernel below).
 #pragma once
 #include "psa_rk4_carried.inc.h"
+#include "psa_rk4_kernel.inc.h"
 
 namespace psa {
 

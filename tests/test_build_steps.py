@@ -75,3 +75,36 @@ def test_every_eight_byte_valu_encoding_ends_up_aligned(tmp_path):
     # the literal-carrying v_mov (4-byte opcode + 32-bit literal) has no 8-byte VOP3 form: it must be left as it is
     text = open(dst).read()
     assert "v_mov_b32_e32 v22, 0x12345678" in text and "v_fmac_f64_e64" in text
+
+
+CSRC = os.path.dirname(SCRIPT)
+SWEEP_UNITS = {"psa_rk4_f64", "psa_rk4_f32", "psa_rk4_pairs", "psa_rk4_single_pump", "psa_rk4_single_pump_f32", "psa_rk4_comb",
+               "psa_rk4_comb_f32"}
+
+
+def _would_rebuild(*touched):
+    """(objects, link) that `make` would rebuild in csrc if the given headers were newer than everything: a dry run."""
+    cmd = ["make", "-n"] + [a for h in touched for a in ("-W", h)]
+    out = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, check=True).stdout
+    return set(re.findall(r"-o (psa_\w+)\.o\b", out)), "libpsa_hip.so" in out
+
+
+def test_header_dependencies_are_the_compilers():
+    """csrc/Makefile takes every object's header dependencies from the .d file its compile wrote: a header rebuilds the units
+    that include it and no other.  The multi-channel, single-pump and float64 comb units do not include the 4/6-wave kernel."""
+    import glob
+    import shutil
+    if shutil.which("make") is None or not glob.glob(os.path.join(CSRC, "*.d")):
+        pytest.skip("no in-tree build with dependency files")
+    objs, link = _would_rebuild()
+    if objs or link:
+        pytest.skip("the in-tree build is not up to date")
+    objs, link = _would_rebuild("psa_rk4_comb_kernel.inc.h")
+    assert objs == {"psa_rk4_comb"} and link
+    objs, link = _would_rebuild("psa_rk4_kernel.inc.h")
+    includers = {os.path.basename(d)[:-2] for d in glob.glob(os.path.join(CSRC, "*.d"))
+                 if re.search(r"(^|\s)psa_rk4_kernel\.inc\.h(\s|$)", open(d).read())}
+    assert {"psa_rk4_f64", "psa_rk4_f32"} <= objs and objs == includers and link
+    assert not objs & {"psa_rk4_comb", "psa_rk4_single_pump", "psa_rk4_pairs"}
+    objs, link = _would_rebuild("psa_launch_rules.h")
+    assert SWEEP_UNITS | {"psa_rk45", "psa_capi"} <= objs and link

@@ -260,8 +260,11 @@ def test_the_unit_compiles_without_scratch_in_every_instantiation():
     mk = open(os.path.join(csrc, "Makefile"), encoding="utf-8").read()
     sched = re.search(r"^SCHED\s*\?=\s*(.+)$", mk, re.M).group(1).split()
     align = re.search(r"^ALIGN\s*\?=\s*(.+)$", mk, re.M).group(1).split()
-    # OBJS, the flags' list and the encoding-alignment rule's list name the unit beside its float64 sibling; it has its dependencies
-    assert mk.count("psa_rk4_comb.o psa_rk4_comb_f32.o") == 3 and re.search(r"^psa_rk4_comb_f32\.o:.*psa_rk4_comb_pk_kernel\.inc\.h", mk, re.M)
+    # the unit stands beside its float64 sibling in the one list of sweep units, which OBJS, the flags and the encoding-alignment
+    # rule all read; its header dependencies are the compiler's (tests/test_build_steps.py)
+    assert "psa_rk4_comb.o psa_rk4_comb_f32.o" in re.search(r"^SWEEP\s*:=\s*(.+)$", mk, re.M).group(1)
+    assert re.search(r"^OBJS\s*:=\s*\$\(SWEEP\)", mk, re.M) and re.search(r"^\$\(SWEEP\): HIPFLAGS \+= \$\(SCHED\) \$\(ALIGN\)$", mk, re.M)
+    assert re.search(r"^\$\(SWEEP\): %\.o: %\.hip align_encodings\.py$", mk, re.M) and "-include $(OBJS:.o=.d)" in mk
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     out = subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--cuda-device-only", "-c",
                           "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "-Wall", "-Wno-unused-function", *sched, *align,
